@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: cell-updates/s of the Rothermel fire-spread step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5] [--envs E] [--size S]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5] [--envs E] [--size S] [--dump-outputs DIR]
 
 One "step" = one ``RothermelFireManager.update`` per environment of the batch
 (simfire/game/managers/fire.py:616-719).  Default workload = BASELINE config C3: 1024x1024
@@ -17,7 +17,8 @@ cell-updates performed x 4 B + active cell-updates x 24 B - over the step kernel
 with HIP events on the library's stream.  After the timed rollout, outside the timed region, the result
 block of every environment and the fire maps of a sample are compared with ``oracle/fire_dense.c`` run
 on the host cores over the same rollout (``"verified"``); that oracle run is also the timed
-``cpu_baseline`` (kind "port").
+``cpu_baseline`` (kind "port").  ``--dump-outputs DIR`` writes what the last timed rollout left its caller as .npy
+files (``dump_outputs``): the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -69,6 +70,10 @@ def parse(argv=None):
     ap.add_argument("--no-rehearsal", action="store_true", help="skip the untimed dress rehearsal of the timed region")
     ap.add_argument("--plumbing-only", action="store_true",
                     help="launch / rendezvous / all-gather plumbing without touching a GPU (CPU test of --gpus N)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed rollout left its caller as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB; rank 0): the result block, elapsed_time, and the fire maps and burn_amounts of a seeded sample "
+                         "of environments")
     a = ap.parse_args(argv)
     a.workload_given = a.workload is not None
     a.workload = a.workload or "c3"
@@ -503,6 +508,31 @@ def load_pmc(w, steps, warmup):
     return None
 
 
+DUMP_MAP_BYTES = 48 << 20      # fire maps (float32) + burn_amounts (float64) of the sampled environments; the result block comes on top
+
+
+def dump_outputs(eng, block, out_dir):
+    """--dump-outputs: what the caller of the timed rollout holds after its last step - the result block of every environment (episode
+    returns; all ranks' rows), elapsed_time, and the fire maps and burn_amounts of a fixed, seeded sample of (rank 0's) environments: whole
+    maps while they fit in DUMP_MAP_BYTES, else a seeded sample of their cells (``sample_cells``: flat indices).  Returns the file names."""
+    H, W, E = eng.H, eng.W, eng.n_envs
+    rng = np.random.default_rng(20261015)
+    envs = np.sort(rng.choice(E, size=int(min(E, max(1, DUMP_MAP_BYTES // (H * W * 12)))), replace=False))
+    maps = np.stack([eng.fire_map(int(e)) for e in envs]).astype(np.float32)
+    burn = np.stack([eng.burn(int(e)) for e in envs])
+    out = {"result_block": np.asarray(block, dtype=np.float64), "elapsed_time": eng.status()[1].astype(np.float64),
+           "sample_envs": envs.astype(np.float64)}
+    if H * W * 12 > DUMP_MAP_BYTES:
+        cells = np.sort(rng.choice(H * W, size=DUMP_MAP_BYTES // (12 * len(envs) + 8), replace=False))
+        maps, burn = maps.reshape(len(envs), -1)[:, cells], burn.reshape(len(envs), -1)[:, cells]
+        out["sample_cells"] = cells.astype(np.float64)
+    out["fire_map"], out["burn_amounts"] = maps, burn
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return sorted(out)
+
+
 def reference_python_timing():
     p = os.path.join(ROOT, "tests", "golden", "reference_timing.json")
     if os.path.exists(p):
@@ -692,6 +722,7 @@ def main():
             verified = bool(v[0].item())
     dt = float(np.median(dts))
     res = gathered.cpu().numpy()
+    dumped = dump_outputs(eng, res, a.dump_outputs) if a.dump_outputs and rank == 0 else None      # (before `measure` resets the engine)
 
     # kernel time and work of the timed window, on EVERY rank (a replay of the same deterministic rollout with HIP events around the
     # launch and the statistics counters on): the north star asks for achieved HBM GB/s at 1, 2, 4 and 8 GPUs
@@ -940,6 +971,8 @@ def main():
         if world > 1:
             # the all-gathered block really holds every rank's rows (rank r's environments report their own ignition seeds' fires)
             out["ranks_seen_by_collective"] = int(sum(1 for r in range(world) if res[r * w.n_envs:(r + 1) * w.n_envs, 1].max() > 0))
+        if dumped:
+            out["dumped_outputs"] = {"dir": a.dump_outputs, "files": [n + ".npy" for n in dumped]}
         print(json.dumps(out))
         sys.stdout.flush()
     if dist is not None:

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import _golden
+import _h5
 from oracle import fire_dense
 
 pytestmark = pytest.mark.gpu
@@ -328,7 +329,7 @@ def test_save_data_matches_reference(tmp_path):
 
 
 @pytest.mark.parametrize("data_type", ["jsonl", "json", "h5"])
-def test_save_data_other_formats(tmp_path, data_type):
+def test_save_data_other_formats(tmp_path, data_type, monkeypatch):
     """``data_type`` ``json`` / ``jsonl`` (one ``{"<elapsed_steps>": fire_map}`` line per update, appended across
     run() calls, static planes as ``<name>.json`` = ``{"data": [...]}``) and ``h5`` (dataset ``data``): simulation.py:
     906-958, 1077-1104.  The reference's Config accepts only npy / h5 (config.py:111), so json is set on the config
@@ -338,7 +339,7 @@ def test_save_data_other_formats(tmp_path, data_type):
     from simfire_amd.config import Config
     from simfire_amd.simulation import FireSimulation
     if data_type == "h5":
-        h5py = pytest.importorskip("h5py")
+        h5py = _h5.h5py_module(monkeypatch)            # (the real h5py, or tests/_h5.py's stand-in where it is not installed)
     d = _golden.load("save_data_c1_32.npz")
     y = yaml.safe_load(open(os.path.join(CFG, "functional_config.yml")))
     y["area"]["screen_size"] = [32, 32]

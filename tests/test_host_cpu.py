@@ -246,17 +246,54 @@ def test_bench_self_launch_plumbing():
     assert odd.returncode != 0 and "do not split evenly" in odd.stderr
 
 
+def test_bench_dump_outputs_are_float_seeded_and_within_64_mb(tmp_path):
+    """bench.py --dump-outputs on a stand-in engine (the GPU test checks the values): float32 / float64 files, at most 64 MB for C3's
+    and C4's grids and for a grid of which not even one environment fits (then a seeded sample of cells), the same sample every run."""
+    import bench
+
+    class Stub:
+        def __init__(self, H, W, E):
+            self.H, self.W, self.n_envs = H, W, E
+
+        def fire_map(self, e):
+            return (np.arange(self.H * self.W).reshape(self.H, self.W) * (e + 1) % 6).astype(np.uint8)
+
+        def burn(self, e):
+            return np.full((self.H, self.W), float(e))
+
+        def status(self):
+            return np.zeros((self.n_envs, 8), np.int32), np.arange(self.n_envs, dtype=np.float64)
+
+    for H, W, E in ((1024, 1024, 256), (2048, 2048, 128), (4096, 4096, 2)):
+        runs = []
+        for k in range(2):
+            d = tmp_path / f"{H}_{k}"
+            names = bench.dump_outputs(Stub(H, W, E), np.ones((E, 8), np.int32), str(d))
+            arrs = {n: np.load(d / f"{n}.npy") for n in names}
+            assert sum(os.path.getsize(d / f"{n}.npy") for n in names) <= 64 << 20
+            assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+            runs.append(arrs)
+        assert all((runs[0][n] == runs[1][n]).all() for n in runs[0])
+        envs = runs[0]["sample_envs"].astype(int)
+        fm = runs[0]["fire_map"].reshape(len(envs), -1)
+        cells = runs[0]["sample_cells"].astype(np.int64) if "sample_cells" in runs[0] else np.arange(H * W)
+        assert (H * W > 4 << 20) == ("sample_cells" in runs[0])
+        for i, e in enumerate(envs):
+            assert (fm[i] == Stub(H, W, E).fire_map(e).ravel()[cells]).all()
+
+
 @pytest.mark.parametrize("data_type", ["npy", "jsonl", "json", "h5"])
-def test_savedata_writer_against_the_reference_run(tmp_path, data_type):
+def test_savedata_writer_against_the_reference_run(tmp_path, data_type, monkeypatch):
     """simfire_amd/savedata.py (host code) fed the per-update maps and observation planes the REFERENCE produced
     (tests/golden/save_data_c1_32.npz, recorded by make_golden_savedata.py) in two run() calls of 7 and 5 updates:
     file list, metadata and history of simulation.py:887-959, 1059-1104 for every data_type."""
     import json
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import _golden
+    import _h5
     from simfire_amd.savedata import write_history
     if data_type == "h5":
-        h5py = pytest.importorskip("h5py")
+        h5py = _h5.h5py_module(monkeypatch)            # (the real h5py, or tests/_h5.py's stand-in where it is not installed)
     d = _golden.load("save_data_c1_32.npz")
     names = [str(n) for n in d["static_names"]]
     static = {n: d[f"attr_{n}"] for n in names}
