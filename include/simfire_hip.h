@@ -269,6 +269,38 @@ int sf_loop_step(sf_sim *sim, const int32_t *points, int32_t *status_out, double
 int sf_loop_stop(sf_sim *sim);
 int sf_loop_restarts(sf_sim *sim, int32_t *count_out);
 
+/* ---------------------------------------------------------------------------------------------- CFD wind field
+ * The stable-fluids velocity solver behind `wind.function: cfd`: WindControllerCFD + Fluid
+ * (simfire/world/wind_mechanics/wind_controller.py:100-185, cfd_wind.py:8-298), batched over n_envs independent
+ * environments of one grid size, bit-identical to the reference's float64 loops.  Grids are square (the reference's
+ * set_bnd raises IndexError on any other, cfd_wind.py:104-165) with 4 <= n <= 4096.  Arrays are [n][n] row-major with
+ * the reference's first index i first (x[i][j]).  The density plane is not computed: it never feeds the velocity. */
+typedef struct sf_cfd sf_cfd; /* opaque */
+typedef struct sf_cfd_params {
+    int32_t n;                /* screen_size[0] == screen_size[1]                                        */
+    int32_t n_envs;           /* independent solvers batched in one launch (one workgroup each)          */
+    int32_t result_accuracy;  /* Gauss-Seidel passes of every lin_solve (Fluid.itr, cfd_wind.py:176)    */
+    int32_t direction;        /* inflow side: 0 north, 1 east, 2 south, 3 west (wind_controller.py:156-170) */
+    double timestep_dt;       /* Fluid.dt                                                                */
+    double viscosity;         /* Fluid.visc (diffuse's coefficient for the velocity, cfd_wind.py:50-51)  */
+    double speed;             /* wind_speed added by the inflow                                          */
+} sf_cfd_params;
+
+/* Fluid.__init__ (cfd_wind.py:9-40): Vx, Vy, Vx0, Vy0 zeroed, every terrain mask zero (no terrain).  n < 4 -> SF_ESHAPE. */
+int sf_cfd_create(const sf_cfd_params *params, sf_cfd **out);
+int sf_cfd_destroy(sf_cfd *h);
+/* Terrain mask of environment env (-1: every environment): uint8 [n][n], 1 where elevation > np.average(elevation)
+ * (wind_controller.py:131-143; the caller forms it), else 0. */
+int sf_cfd_set_terrain(sf_cfd *h, int32_t env, const uint8_t *mask);
+/* n_steps Fluid.step()s (cfd_wind.py:49-60) on every environment; step k of this call is preceded by the inflow of
+ * iterate_wind_step (wind_controller.py:156-170) when inflow_every > 0 && k % inflow_every == 0.  Training as in
+ * generate_cfd_wind_layer (generate_cfd_wind_layer.py:99-105) for T iterations is (2T, 2); iterate_wind_step() is
+ * (1, 1) and fvect.step() (1, 0).  The host splits the call into launches of bounded length; the state stays on the device. */
+int sf_cfd_step(sf_cfd *h, int32_t n_steps, int32_t inflow_every);
+/* Fluid.Vx / Fluid.Vy of environment env (get_wind_velocity_field_x/_y, wind_controller.py:178-182): float64 [n][n]
+ * each; a null pointer is skipped. */
+int sf_cfd_get_velocity(sf_cfd *h, int32_t env, double *vx, double *vy);
+
 #ifdef __cplusplus
 }
 #endif

@@ -119,6 +119,8 @@ int sf_get_tuning(sf_sim *sim, int32_t knob, int32_t *value_out);
 int sf_last_step_launch(sf_sim *sim, int32_t *kind_out);
 /* 1 = visit every tile every step instead of consulting the tile activity map (cross-check) */
 int sf_set_dense(sf_sim *sim, int32_t dense);
+/* sf_cfd_step that also reports the GPU time of its launches (HIP events on the handle's stream). */
+int sf_cfd_step_timed(sf_cfd *h, int32_t n_steps, int32_t inflow_every, float *ms_out);
 
 #ifdef __cplusplus
 }

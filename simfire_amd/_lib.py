@@ -27,6 +27,11 @@ class SfParams(C.Structure):
                 ("M_f", C.c_double), ("per_env_terrain", C.c_int32)]
 
 
+class SfCfdParams(C.Structure):
+    _fields_ = [("n", C.c_int32), ("n_envs", C.c_int32), ("result_accuracy", C.c_int32), ("direction", C.c_int32),
+                ("timestep_dt", C.c_double), ("viscosity", C.c_double), ("speed", C.c_double)]
+
+
 # name -> argtypes; every function returns int except the two string getters
 _VP, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
 SIGNATURES = {
@@ -96,6 +101,12 @@ SIGNATURES = {
     "sf_set_async": [_VP, _I32],
     "sf_sync": [_VP],
     "sf_set_threshold": [_VP, C.c_double],
+    "sf_cfd_create": [C.POINTER(SfCfdParams), C.POINTER(_VP)],
+    "sf_cfd_destroy": [_VP],
+    "sf_cfd_set_terrain": [_VP, _I32, _VP],
+    "sf_cfd_step": [_VP, _I32, _I32],
+    "sf_cfd_step_timed": [_VP, _I32, _I32, C.POINTER(C.c_float)],
+    "sf_cfd_get_velocity": [_VP, _I32, _VP, _VP],
 }
 STRING_GETTERS = ("sf_last_error", "sf_version")
 

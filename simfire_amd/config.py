@@ -8,7 +8,8 @@ and ``wind``.
 
 Layer *generation* is host-side, one-off work outside the hot path:
 functional ``flat`` / ``gaussian`` topography, ``chaparral`` fuel and ``simple`` wind are built
-here exactly like the reference does; ``perlin`` needs the un-vendored ``noise`` wheel and
+here exactly like the reference does; ``cfd`` wind is trained on the GPU (``wind.py``, a count of iterations in
+``wind.cfd.train_steps`` instead of the reference's wall clock); ``perlin`` needs the un-vendored ``noise`` wheel and
 ``operational`` / ``historical`` need network + GIS wheels, so those raise ``ConfigError`` unless
 the caller supplies the arrays directly through ``Config.from_arrays``.
 """
@@ -159,8 +160,7 @@ class Config:
             self.yaml_data = copy.deepcopy(config_dict)
         else:
             raise ValueError("Either a path or a config dictionary must be specified.")
-        if cfd_precompute:
-            raise ConfigError("CFD wind pre-computation is outside the scope of simfire_amd")
+        self._cfd_precompute = bool(cfd_precompute)
         self._arrays: Dict[str, np.ndarray] = {}
         self.fuel_codes: Optional[np.ndarray] = None
         self._build()
@@ -176,6 +176,7 @@ class Config:
         ``noise`` dependencies."""
         self = cls.__new__(cls)
         self.path = None
+        self._cfd_precompute = False
         self.yaml_data = copy.deepcopy(config_dict)
         fuel = np.asarray(fuel)
         self._arrays = {"fuel": fuel, "elevation": np.asarray(elevation, dtype=np.float64)}
@@ -212,7 +213,10 @@ class Config:
             self.terrain = self._load_terrain()
             self.fire = self._load_fire()
             self.environment = EnvironmentConfig(**y["environment"])
-            self.wind = self._load_wind()
+            if self._cfd_precompute:
+                self.cfd_setup = self._cfd_wind_setup()          # config.py:267-270: the wind is not loaded
+            else:
+                self.wind = self._load_wind()
         except KeyError as exc:
             raise ConfigError(f"Missing configuration key: {exc}")
 
@@ -326,8 +330,40 @@ class Config:
                 raise ConfigError(f"wind.perlin is missing the parameter {err}") from None
             return WindConfig(sp.astype(np.float64), dr.astype(np.float64), FunctionalConfig("perlin", ps), FunctionalConfig("perlin", pd))
         if name == "cfd":
-            raise ConfigError("`cfd` wind needs a CFD pre-computation; pass the wind fields through Config.from_arrays instead")
+            # config.py:866-891: the reference trains for `time_to_train` wall-clock seconds and caches the field in files; here
+            # the field is trained on the GPU for a count of iterations, `wind.cfd.train_steps`, and nothing is written
+            from .wind import cfd_wind_fields
+            cfd = self._cfd_block(H, W, ("result_accuracy", "timestep_dt", "viscosity", "speed", "direction", "train_steps"))
+            sp, dr = cfd_wind_fields(self.terrain.topography_layer.data, result_accuracy=cfd["result_accuracy"],
+                                     timestep_dt=cfd["timestep_dt"], viscosity=cfd["viscosity"], speed=cfd["speed"],
+                                     direction=cfd["direction"], train_steps=cfd["train_steps"])
+            return WindConfig(sp.astype(np.float64), dr.astype(np.float64), FunctionalConfig("cfd", cfd), FunctionalConfig("cfd", cfd))
         raise ConfigError(f"Wind type {name} is not supported")
+
+    def _cfd_block(self, H: int, W: int, keys: Tuple[str, ...]) -> Dict[str, Any]:
+        """The `wind.cfd` block, checked before any device call: every key present, a square grid, a known direction."""
+        cfd = self.yaml_data["wind"].get("cfd")
+        if not isinstance(cfd, dict):
+            raise ConfigError("`cfd` wind needs a `wind.cfd` block")
+        missing = [k for k in keys if k not in cfd]
+        if missing:
+            raise ConfigError(f"`cfd` wind is missing the key(s) {', '.join('wind.cfd.' + k for k in missing)}")
+        if H != W:
+            raise ConfigError(f"`cfd` wind needs a square screen_size, got {(H, W)}")
+        from .wind import direction_code
+        direction_code(cfd["direction"])
+        return cfd
+
+    def _cfd_wind_setup(self):
+        """config.py:948-972: a WindControllerCFD over the topography layer, its scale from area.pixel_scale."""
+        from .wind import WindControllerCFD
+        H, W = self._shape()
+        cfd = self._cfd_block(H, W, ("result_accuracy", "timestep_dt", "viscosity", "speed", "direction"))
+        return WindControllerCFD(screen_size=tuple(self.yaml_data["area"]["screen_size"]), result_accuracy=cfd["result_accuracy"],
+                                 scale=self.yaml_data["area"]["pixel_scale"], timestep=cfd["timestep_dt"],
+                                 diffusion=cfd.get("diffusion", 0.0), viscosity=cfd["viscosity"],
+                                 terrain_features=self.terrain.topography_layer.data, wind_speed=cfd["speed"],
+                                 wind_direction=cfd["direction"], time_to_train=cfd.get("time_to_train", 1000))
 
     # ---------------------------------------------------------------------- re-seeding
     def reset_terrain(self, topography_seed: Optional[int] = None, topography_type: Optional[str] = None,

@@ -85,6 +85,12 @@ static int fail(int code, const char *fmt, ...)
     } while (0)
 
 extern "C" const char *sf_last_error(void) { return g_err.c_str(); }
+// the other translation units report through the same per-thread message (simfire_hip_cfd.hip)
+int sf_fail_message(int code, const char *msg)
+{
+    g_err = msg;
+    return code;
+}
 extern "C" const char *sf_version(void) { return "simfire_hip 0.2 (gfx950)"; }      // 0.2: the knob numbers and the 16 counter slots of simfire_hip_lab.h as they stand since round 5; sf_get_fire_map_delta
 
 #include "sf_common.h"
