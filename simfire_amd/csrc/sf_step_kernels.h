@@ -932,6 +932,7 @@ __global__ __launch_bounds__(256) void k_graph_pass_tiles(StepArgs a)
 }
 #endif
 
+#ifndef SF_RUN_UNIT
 typedef void (*StepKernel)(StepArgs);
 static StepKernel pick_step_kernel(int rb, bool fused)
 {
@@ -942,6 +943,7 @@ static StepKernel pick_step_kernel(int rb, bool fused)
     default: return fused ? k_step_fused<8> : k_step<8>;
     }
 }
+#endif
 
 // Fold the flags of the last launch of a sf_step call into the committed state, zero the ring.
 #ifndef SF_RUN_UNIT

@@ -56,6 +56,7 @@
 #include <algorithm>
 #include <map>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include <dlfcn.h>
@@ -97,6 +98,7 @@ extern "C" const char *sf_version(void) { return "simfire_hip 0.2 (gfx950)"; }  
 #include "sf_step_kernels.h"
 #include "sf_aux_kernels.h"
 #include "sf_run_kernels.h"
+#include "sf_run_table.h"
 
 // Launch-geometry knobs of a handle (sf_set_tuning, include/simfire_hip_lab.h: SF_TUNE_*).  Results never depend on them; the
 // defaults are the measured choices of NOTEBOOK.md 5.  The library does not read the environment for them (the measurement scripts under
@@ -121,7 +123,7 @@ struct sf_sim {
     uint8_t *cells_alloc = nullptr, *cells = nullptr;      // blocked cell plane of the resident launch (allocated at its first use)
     bool bl_cur = false;               // the blocked plane holds the sprite masks / status bytes; the row-major planes are stale
     double *burn = nullptr, *rt = nullptr;
-    mutable std::map<unsigned long long, int> occ_cache;      // team kernels: workgroups per CU by hipOccupancyMaxActiveBlocksPerMultiprocessor (team_occupancy)
+    mutable std::map<std::tuple<const void *, unsigned, size_t>, int> occ_cache;      // k_run instantiations: workgroups per CU by hipOccupancyMaxActiveBlocksPerMultiprocessor (occupancy)
     double *rtc = nullptr;             // the R table(s) cell-major (k_rt_cellmajor): built when the resident launch first needs it, stale after every change of rt
     bool rtc_valid = false;
     std::vector<char> rtc_stale;       // per table: its cell-major copy does not match rt (all of them until the copy exists)
@@ -197,7 +199,7 @@ struct sf_sim {
     uint32_t *todo_cnt = nullptr;      // k_win: how many environments it left updates for (their numbers: run_order); two counts, by the parity of win_seq
     unsigned win_seq = 0;              // k_win launches so far
     uint32_t *run_cost = nullptr, *run_order = nullptr;   // k_run: clocks / 16 an environment's workgroup took in the last resident launch [E]; launch order built from it (k_order)
-    size_t attr_run[32] = {}, attr_team[8] = {}, attr_team_c4[2] = {}, attr_join[2] = {};       // dynamic LDS sizes the k_run instantiations have been enabled for (hipFuncSetAttribute is not free)
+    mutable std::map<const void *, size_t> lds_allowed;       // dynamic LDS the resident kernels have been enabled for, by host handle (allow_lds)
     uint8_t *parents = nullptr;        // spread-graph parent masks, allocated by sf_enable_spread_graph
     bool graph_on = false;
     // sf_get_fire_map_delta: the fire maps as the host last saw them (u8 [E][H][P], allocated at the first call), per environment whether that
@@ -231,23 +233,6 @@ struct sf_sim {
 
 static int ensure_commit(sf_sim *s);
 extern "C" int sf_loop_stop(sf_sim *s);
-// simfire_hip_run2.hip / _run3.hip / _run4.hip: the launches of the k_run instantiations that live in the library's other translation units
-// (teams and the closed loop; two / four bitmap words per thread; two-word teams).  StepArgs crosses as bytes.
-hipError_t sf_run2_launch_team(int att, int diag, unsigned grid, unsigned block, size_t lds, bool set_lds, hipStream_t stream,
-                               const void *args, size_t args_bytes, int n_steps, int vcap);
-hipError_t sf_run4_launch_team2(int att, int diag, unsigned grid, unsigned block, size_t lds, bool set_lds, hipStream_t stream,
-                                const void *args, size_t args_bytes, int n_steps, int vcap);
-hipError_t sf_run3_launch_plain(int which, int att, int diag, unsigned grid, unsigned block, size_t lds, bool set_lds, hipStream_t stream,
-                                const void *args, size_t args_bytes, int n_steps, int vcap, int bsz);
-hipError_t sf_run2_team_occupancy(int att, int diag, unsigned block, size_t lds, int *per_cu);
-hipError_t sf_run2_join_occupancy(int att, unsigned block, size_t lds, int *per_cu);
-hipError_t sf_run4_team2_occupancy(int att, int diag, int mit, unsigned block, size_t lds, int *per_cu);
-hipError_t sf_run2_launch_join(int att, unsigned grid, unsigned block, size_t lds, bool set_lds, hipStream_t stream,
-                               const void *args, size_t args_bytes, int n_steps, int vcap);
-hipError_t sf_run2_launch_loop(int att, int diag, unsigned grid, unsigned block, size_t lds, bool set_lds, hipStream_t stream,
-                               const void *args, size_t args_bytes, int vcap);
-hipError_t sf_run3_launch_loop2(int att, unsigned grid, unsigned block, size_t lds, bool set_lds, hipStream_t stream,
-                                const void *args, size_t args_bytes, int vcap);
 // every entry point except sf_loop_step ends the closed loop (sf_loop_start) first: the handle's stream is busy with the resident launch
 #define LOOP_QUIESCE(s) do { if ((s)->loop_on) { int _rq = sf_loop_stop(s); if (_rq) return _rq; } } while (0)
 static int ensure_rm(sf_sim *s);
@@ -1084,7 +1069,7 @@ static int alloc_bl(sf_sim *s)
     HIPCHK(hipMemsetAsync(s->cells_alloc, 0, bytes, s->stream));
     return SF_OK;
 }
-// Will sf_step(n >= 2) of this handle pick the resident launch (the automatic rule of step_impl)?  Then a reset writes the
+// Will sf_step(n >= 2) of this handle pick the resident launch (the automatic rule of plan_step)?  Then a reset writes the
 // blocked plane straight away.
 static bool prefers_bl(const sf_sim *s)
 {
@@ -1160,37 +1145,98 @@ extern "C" int sf_last_step_launch(sf_sim *s, int32_t *kind)
     return SF_OK;
 }
 
-constexpr int SF_INTERNAL_NO_RESIDENT = 1;       // step_impl: the resident launch was asked for (mitigated rollout) but cannot run
-
-// The resident launch: k_run<D>, D = bitmap words a thread owns (rows per thread x words per row) rounded up to 1, 2 or 4 (grids up to
-// 1024 x 1024 in 16 waves: D = 1, thirteen registers fewer than D = 4).
-static int launch_k_run(sf_sim *s, const StepArgs &a, int n_steps, int waves, int vcap, size_t lds, int bsz)
+// ----------------------------------------------------------------------------- resident launches
+// One word per thread: [attenuation off / on][diagonal spread read at run time / known to be on - every reference config]; control lines
+// inside the launch: an instantiation without them (MIT = 0) where diagonal spread is known to be on, the others look at the argument.
+// (every other k_run instantiation lives in the library's other translation units: simfire_hip_run2.hip / _run3.hip / _run4.hip)
+static RunTable sf_run1_table()
 {
-    const int need = ((s->g.H + waves * 64 - 1) / (waves * 64)) * s->g.VW;
-    const int which = need <= 1 ? 0 : (need <= 2 ? 1 : 2);      // (two words per thread = 1024 rows in 8 waves: the many-environments regime; the kernel for four spills there, +7 %)
-    typedef void (*run_fn)(StepArgs, int, int, int);
-    const int ia = s->g.att ? 1 : 0, id = s->g.diag ? 1 : 0;
-    if (which > 0) {
-        // two / four words per thread: instantiated in the library's third translation unit (simfire_hip_run3.hip)
-        size_t &attr3 = s->attr_run[which == 2 ? 20 + ia : ((id && !a.mit) ? 16 + ia : (which * 2 + ia) * 2 + id)];      // (16 / 17: the instantiations without control lines inside the launch)
-        const bool set_lds = lds > 64 * 1024 && lds > attr3;
-        HIPCHK(sf_run3_launch_plain(which, ia, id, (unsigned)s->g.E, (unsigned)waves * 64, lds, set_lds, s->stream, &a, sizeof a, n_steps, vcap, bsz));
-        if (set_lds) attr3 = lds;
-        return SF_OK;
+    static const RunEntry runs[] = {SF_RUN_ENTRY(1, 0, -1, -1, 0), SF_RUN_ENTRY(1, 0, 1, -1, 0), SF_RUN_ENTRY(1, 1, -1, -1, 0),
+                                    SF_RUN_ENTRY(1, 1, 1, -1, 0), SF_RUN_ENTRY(1, 0, 1, 0, 0), SF_RUN_ENTRY(1, 1, 1, 0, 0)};
+    return {runs, (int)(sizeof runs / sizeof runs[0]), sizeof(StepArgs)};
+}
+RunTable sf_run2_table(), sf_run3_table(), sf_run4_table();
+
+enum RunKind { kRunPlain, kRunTeam, kRunJoin, kRunLoop };
+
+// Bitmap words a thread of a k_run workgroup owns (rows per thread x words per row), rounded up to an instantiated 1, 2 or 4 (grids up to
+// 1024 x 1024 in 16 waves: one, thirteen registers fewer than four).
+static int run_words(int rows, int waves, int vw)
+{
+    const int need = ((rows + waves * 64 - 1) / (waves * 64)) * vw;
+    return need <= 1 ? 1 : (need <= 2 ? 2 : kRunMaxD);      // (two words per thread = 1024 rows in 8 waves: the many-environments regime; the kernel for four spills there, +7 %)
+}
+
+// The instantiation k_run<MAXD, ATT, DIAG, MIT, TEAM> a launch of this kind takes.  lines: control lines come inside the launch.
+static RunKey run_key(const Geo &g, RunKind kind, int words, bool lines)
+{
+    const int att = g.att ? 1 : 0, diag = g.diag ? 1 : -1;
+    switch (kind) {
+    case kRunJoin: return {1, att, 1, 0, 2};                      // (one-word rows, diagonal spread, no control lines inside the launch)
+    case kRunLoop: return {words, att, -1, -2, 0};                // (the closed loop looks diagonal spread up at run time)
+    // teams: diagonal spread on, no control lines inside the launch on two-word rows = BASELINE config C4: its own instantiations, without the
+    // control-line code and its registers; one-word teams look control lines up at run time
+    case kRunTeam: return {words, att, diag, (words == 2 && g.diag && !lines) ? 0 : -1, 1};
+    default:
+        if (words > 2) return {kRunMaxD, att, -1, -1, 0};        // (four words per thread: diagonal spread looked up at run time only)
+        return {words, att, diag, (g.diag && !lines) ? 0 : -1, 0};
     }
-    // one word per thread: [attenuation off / on][diagonal spread read at run time / known to be on - every reference config]; control
-    // lines inside the launch: an instantiation without them (MIT = 0) where diagonal spread is known to be on, the others look at the argument
-    static const run_fn table[2][2] = {{k_run<1, 0, -1, -1>, k_run<1, 0, 1, -1>}, {k_run<1, 1, -1, -1>, k_run<1, 1, 1, -1>}};
-    static const run_fn table_nomit[2][2] = {{k_run<1, 0, -1, -1>, k_run<1, 0, 1, 0>}, {k_run<1, 1, -1, -1>, k_run<1, 1, 1, 0>}};
-    const bool nomit = !a.mit;
-    const run_fn kern = nomit ? table_nomit[ia][id] : table[ia][id];
-    size_t &attr = s->attr_run[nomit ? 12 + ia * 2 + id : ia * 2 + id];
-    if (lds > 64 * 1024 && lds > attr) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = lds;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)s->g.E), dim3((unsigned)waves * 64), lds, s->stream, a, n_steps, vcap, bsz);
+}
+
+// The host handle of an instantiation, from the tables of the four translation units (sf_run_table.h); null: none, or a unit that was built
+// with another StepArgs.
+static const void *run_fn(const RunKey &k)
+{
+    static const RunTable tables[] = {sf_run1_table(), sf_run2_table(), sf_run3_table(), sf_run4_table()};
+    for (const RunTable &t : tables)
+        for (int i = 0; i < t.n; ++i)
+            if (t.entries[i].key == k) return t.args_bytes == sizeof(StepArgs) ? t.entries[i].fn : nullptr;
+    return nullptr;
+}
+
+// More than 64 KB of dynamic LDS has to be allowed for a kernel first: once per kernel and size (hipFuncSetAttribute is not free).
+static hipError_t allow_lds(const sf_sim *s, const void *fn, size_t lds)
+{
+    if (lds <= 64 * 1024) return hipSuccess;
+    auto it = s->lds_allowed.find(fn);
+    if (it != s->lds_allowed.end() && it->second >= lds) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) s->lds_allowed[fn] = lds;
+    return e;
+}
+
+// Every resident launch (k_run, k_win) goes through here: fn is the kernel's host handle, args its arguments.
+static int launch_resident(sf_sim *s, const void *fn, unsigned grid, unsigned block, size_t lds, void **args)
+{
+    HIPCHK(allow_lds(s, fn, lds));
+    HIPCHK(hipLaunchKernel(fn, dim3(grid), dim3(block), args, lds, s->stream));
     return SF_OK;
+}
+static int launch_run(sf_sim *s, const RunKey &k, unsigned grid, unsigned block, size_t lds, StepArgs &a, int n_steps, int vcap, int bsz)
+{
+    const void *fn = run_fn(k);
+    if (!fn) return fail(SF_EHIP, "k_run<%d, %d, %d, %d, %d> is not in this library (or its unit was built with another StepArgs)", k.maxd, k.att, k.diag, k.mit, k.team);
+    void *args[] = {&a, &n_steps, &vcap, &bsz};
+    return launch_resident(s, fn, grid, block, lds, args);
+}
+
+// Workgroups of this instantiation (block threads, lds bytes of dynamic LDS) one CU holds at once, as the runtime computes it from the
+// kernel's registers and LDS (hipOccupancyMaxActiveBlocksPerMultiprocessor): what the host sizes a team launch's grid by - the members of a
+// team wait for each other inside the launch, so a grid the chip cannot hold at once would be a team that is never complete.  Asked once
+// per kernel and geometry; -1: the runtime would not say.
+static int occupancy(const sf_sim *s, const RunKey &k, unsigned block, size_t lds)
+{
+    const void *fn = run_fn(k);
+    const auto key = std::make_tuple(fn, block, lds);
+    auto it = s->occ_cache.find(key);
+    if (it != s->occ_cache.end()) return it->second;
+    int occ = -1;
+    if (!fn || allow_lds(s, fn, lds) != hipSuccess || hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, (int)block, lds) != hipSuccess) {
+        (void)hipGetLastError();
+        occ = -1;
+    }
+    s->occ_cache[key] = occ;
+    return occ;
 }
 
 struct TeamGeo;
@@ -1232,30 +1278,16 @@ static TeamGeo team_geometry(const sf_sim *s)
     return t;
 }
 
-static int team_buffers(sf_sim *s, const TeamGeo &t);
-
 // Workgroups per CU of the team kernel this geometry launches (the smaller figure of its instantiations with / without control lines inside
-// the launch), from the runtime's occupancy calculator; asked once per geometry.  -1: the runtime would not say (the LDS formula stands).
+// the launch).  -1: the runtime would not say (the LDS formula stands).
 static int team_occupancy(const sf_sim *s, const TeamGeo &t, bool join)
 {
-    const Geo &g = s->g;
-    const int rows = t.rcap ? t.rcap : g.H;
-    const int which = join ? 2 : (((rows + t.waves * 64 - 1) / (t.waves * 64)) * g.VW <= 1 ? 0 : 1);
-    const int ia = g.att ? 1 : 0, id = g.diag ? 1 : 0;
-    const unsigned long long key = (unsigned long long)which | (unsigned long long)ia << 2 | (unsigned long long)id << 3 | (unsigned long long)t.waves << 8 | (unsigned long long)t.lds << 16;
-    auto it = s->occ_cache.find(key);
-    if (it != s->occ_cache.end()) return it->second;
-    int occ = -1, o2 = -1;
-    hipError_t e = hipSuccess;
-    if (which == 2) e = sf_run2_join_occupancy(ia, (unsigned)t.waves * 64, t.lds, &occ);
-    else if (which == 0) e = sf_run2_team_occupancy(ia, id, (unsigned)t.waves * 64, t.lds, &occ);
-    else {
-        e = sf_run4_team2_occupancy(ia, id, 0, (unsigned)t.waves * 64, t.lds, &occ);
-        if (e == hipSuccess && sf_run4_team2_occupancy(ia, id, 1, (unsigned)t.waves * 64, t.lds, &o2) == hipSuccess && o2 < occ) occ = o2;
-    }
-    if (e != hipSuccess) { (void)hipGetLastError(); occ = -1; }
-    s->occ_cache[key] = occ;
-    return occ;
+    const unsigned block = (unsigned)t.waves * 64;
+    if (join) return occupancy(s, run_key(s->g, kRunJoin, 1, false), block, t.lds);
+    const int words = run_words(t.rcap ? t.rcap : s->g.H, t.waves, s->g.VW);
+    const int occ = occupancy(s, run_key(s->g, kRunTeam, words, false), block, t.lds);
+    const int o2 = occ < 0 ? -1 : occupancy(s, run_key(s->g, kRunTeam, words, true), block, t.lds);
+    return (o2 >= 0 && o2 < occ) ? o2 : occ;
 }
 
 // Teams that GROW inside the launch (k_run<TEAM = 2>, sf_run_kernels.h): one-word rows, one 16-wave workgroup per CU, every environment starts
@@ -1276,42 +1308,6 @@ static TeamGeo join_geometry(const sf_sim *s)
     t.ok = true;
     return t;
 }
-static int launch_k_run_join(sf_sim *s, StepArgs &a, int n_steps, const TeamGeo &t, int recut, bool eager)
-{
-    const Geo &g = s->g;
-    { int rc = team_buffers(s, t); if (rc) return rc; }
-    if (!s->xj) {
-        int rc = dev_alloc(s, &s->xj, (size_t)3 * g.E + 2); if (rc) return rc;
-        rc = dev_alloc(s, &s->xcut, (size_t)g.E); if (rc) return rc;
-        rc = dev_alloc(s, &s->jlog, (size_t)1 + 3 * kJoinLog); if (rc) return rc;
-    }
-    HIPCHK(hipMemsetAsync(s->jlog, 0, sizeof(uint32_t), s->stream));
-    s->jlog_valid = true;
-    hipLaunchKernelGGL(k_team_plan, dim3(1), dim3(1024), 0, s->stream, g.E, t.slots, 1, 1, 0u, 0u, 1, s->run_cost, s->team_tab, s->team_size, s->xg, s->xdone, 0,
-                       s->xj, s->xcut);
-    s->team_plan_ones = 0;             // (this plan spreads the environments over the XCDs: not the table a launch of fixed teams of one keeps)
-    a.cost = s->run_cost;
-    a.team_tab = s->team_tab; a.xg = s->xg; a.xbuf = s->xbuf; a.xdone = s->xdone; a.xerr = s->xerr_mapped;
-    a.xrow = team_xrow(g); a.team_rcap = 0;
-    a.team_far = s->tune.v[SF_TUNE_TEAM_PLACEMENT] == 2;
-    a.order = nullptr; a.todo = nullptr; a.todo_out = nullptr; a.todo_skip = 0; a.todo_cnt = nullptr; a.todo_list = nullptr; a.todo_cnt_next = nullptr;
-    a.team_recut = recut;
-    a.xj = s->xj; a.xcut = s->xcut; a.tsize = s->team_size; a.jlog = s->jlog;
-    // (k_team_plan's model of a team: the chain no member's update gets shorter than, what belonging to a team costs per update; eager - tests -:
-    // every workgroup that is free joins whatever runs)
-    // Where the newcomers come from: the environment's own XCD (default: the team's step boundaries and cuts stay in one L2 - measured on C3, 1000 updates:
-    // teams spread over the XCDs pay ~12 k clocks per update for belonging, and every cut writes back and invalidates a whole L2 under 31 other
-    // environments; 10.9 -> 12.7 us per update); SF_TUNE_TEAM_PLACEMENT 1 = from anywhere, 2 = the own XCD but every hand-off as if they were apart
-    const int place = s->tune.v[SF_TUNE_TEAM_PLACEMENT];
-    a.join_local = place == 1 ? 0 : (place == 2 ? 2 : 1);
-    a.join_floor = eager ? 0 : 12000; a.join_ovh = eager ? 0 : (a.join_local == 1 ? 3000 : 12000);
-    const int ia = g.att ? 1 : 0;
-    const bool set_lds = t.lds > 64 * 1024 && t.lds > s->attr_join[ia];
-    HIPCHK(sf_run2_launch_join(ia, (unsigned)t.slots, (unsigned)t.waves * 64, t.lds, set_lds, s->stream, &a, sizeof a, n_steps, t.vcap));
-    if (set_lds) s->attr_join[ia] = t.lds;
-    return SF_OK;
-}
-
 static int team_buffers(sf_sim *s, const TeamGeo &t)
 {
     const Geo &g = s->g;
@@ -1335,6 +1331,47 @@ static int team_buffers(sf_sim *s, const TeamGeo &t)
     return SF_OK;
 }
 
+// The fields of StepArgs every team launch (k_run<TEAM>) sets from the handle.  rcap: bitmap rows a member keeps (0 = all); cost: the cost array
+// the launch reads and records, or null.
+static void team_args(const sf_sim *s, StepArgs &a, int rcap, uint32_t *cost)
+{
+    a.cost = cost;
+    a.team_tab = s->team_tab; a.xg = s->xg; a.xbuf = s->xbuf; a.xdone = s->xdone; a.xerr = s->xerr_mapped;
+    a.xrow = team_xrow(s->g); a.team_rcap = rcap;
+    // placement of the members: 0 (default) = the slots of one XCD, 1 = consecutive slots (eight XCDs in turn), 2 = as 0 but the
+    // hand-off written through as if they were apart - results never depend on it (tests run all three)
+    a.team_far = s->tune.v[SF_TUNE_TEAM_PLACEMENT] == 2;
+    a.order = nullptr;
+}
+
+static int launch_k_run_join(sf_sim *s, StepArgs &a, int n_steps, const TeamGeo &t, bool eager)
+{
+    const Geo &g = s->g;
+    { int rc = team_buffers(s, t); if (rc) return rc; }
+    if (!s->xj) {
+        int rc = dev_alloc(s, &s->xj, (size_t)3 * g.E + 2); if (rc) return rc;
+        rc = dev_alloc(s, &s->xcut, (size_t)g.E); if (rc) return rc;
+        rc = dev_alloc(s, &s->jlog, (size_t)1 + 3 * kJoinLog); if (rc) return rc;
+    }
+    HIPCHK(hipMemsetAsync(s->jlog, 0, sizeof(uint32_t), s->stream));
+    s->jlog_valid = true;
+    hipLaunchKernelGGL(k_team_plan, dim3(1), dim3(1024), 0, s->stream, g.E, t.slots, 1, 1, 0u, 0u, 1, s->run_cost, s->team_tab, s->team_size, s->xg, s->xdone, 0,
+                       s->xj, s->xcut);
+    s->team_plan_ones = 0;             // (this plan spreads the environments over the XCDs: not the table a launch of fixed teams of one keeps)
+    team_args(s, a, 0, s->run_cost);
+    a.xj = s->xj; a.xcut = s->xcut; a.tsize = s->team_size; a.jlog = s->jlog;
+    // (k_team_plan's model of a team: the chain no member's update gets shorter than, what belonging to a team costs per update; eager - tests -:
+    // every workgroup that is free joins whatever runs)
+    // Where the newcomers come from: the environment's own XCD (default: the team's step boundaries and cuts stay in one L2 - measured on C3, 1000 updates:
+    // teams spread over the XCDs pay ~12 k clocks per update for belonging, and every cut writes back and invalidates a whole L2 under 31 other
+    // environments; 10.9 -> 12.7 us per update); SF_TUNE_TEAM_PLACEMENT 1 = from anywhere, 2 = the own XCD but every hand-off as if they were apart
+    const int place = s->tune.v[SF_TUNE_TEAM_PLACEMENT];
+    a.join_local = place == 1 ? 0 : (place == 2 ? 2 : 1);
+    a.join_floor = eager ? 0 : 12000; a.join_ovh = eager ? 0 : (a.join_local == 1 ? 3000 : 12000);
+    return launch_run(s, run_key(g, kRunJoin, 1, false), (unsigned)t.slots, (unsigned)t.waves * 64, t.lds, a, n_steps, t.vcap, 64);
+}
+
+
 // keep_cost: the launch neither reads nor records what the environments cost (the catch-up launch behind a windowed one)
 static int launch_k_run_team(sf_sim *s, StepArgs &a, int n_steps, const TeamGeo &t, int t_min, int t_max, int steps_before, bool keep_cost = false)
 {
@@ -1354,79 +1391,71 @@ static int launch_k_run_team(sf_sim *s, StepArgs &a, int n_steps, const TeamGeo 
         hipLaunchKernelGGL(k_team_plan, dim3(1), dim3(1024), 0, s->stream, g.E, t.slots, t_min, t_max, ovh, floor_c, scatter,
                            s->run_cost, s->team_tab, s->team_size, s->xg, s->xdone, keep_cost ? 1 : 0, (uint32_t *)nullptr, (unsigned long long *)nullptr);
     s->team_plan_ones = ones_key;
-    a.cost = keep_cost ? nullptr : s->run_cost;
-    a.team_tab = s->team_tab; a.xg = s->xg; a.xbuf = s->xbuf; a.xdone = s->xdone; a.xerr = s->xerr_mapped;
-    a.xrow = team_xrow(g); a.team_rcap = t.rcap;
-    // placement of the members: 0 (default) = the slots of one XCD, 1 = consecutive slots (eight XCDs in turn), 2 = as 0 but the
-    // hand-off written through as if they were apart - results never depend on it (tests run all three)
-    const int place = s->tune.v[SF_TUNE_TEAM_PLACEMENT];
-    a.team_far = place == 2;
-    a.order = nullptr;
-    // (the team kernels are instantiated in the library's other translation units, simfire_hip_run2.hip / _run4.hip: [words per thread 1 / 2]
-    // [attenuation off / on]; diagonal spread and control lines inside the launch are looked up at run time)
-    const int rows = t.rcap ? t.rcap : g.H;
-    const int need = ((rows + t.waves * 64 - 1) / (t.waves * 64)) * g.VW;
-    const int which = need <= 1 ? 0 : 1, ia = g.att ? 1 : 0;
-    const int id = g.diag ? 1 : 0;
-    size_t &attr = (which && id && !a.mit) ? s->attr_team_c4[ia] : s->attr_team[(which * 2 + ia) * 2 + id];
-    const bool set_lds = t.lds > 64 * 1024 && t.lds > attr;
-    if (which) HIPCHK(sf_run4_launch_team2(ia, id, (unsigned)t.slots, (unsigned)t.waves * 64, t.lds, set_lds, s->stream, &a, sizeof a, n_steps, t.vcap));
-    else HIPCHK(sf_run2_launch_team(ia, id, (unsigned)t.slots, (unsigned)t.waves * 64, t.lds, set_lds, s->stream, &a, sizeof a, n_steps, t.vcap));
-    if (set_lds) attr = t.lds;
-    return SF_OK;
+    team_args(s, a, t.rcap, keep_cost ? nullptr : s->run_cost);
+    const int words = run_words(t.rcap ? t.rcap : g.H, t.waves, g.VW);
+    return launch_run(s, run_key(g, kRunTeam, words, a.mit != nullptr), (unsigned)t.slots, (unsigned)t.waves * 64, t.lds, a, n_steps, t.vcap, 64);
 }
 
-static int step_impl(sf_sim *s, int n_steps, float *ms, const int32_t *mit_dev = nullptr, int mit_k = 0)
+// ----------------------------------------------------------------------------- the launch plan of a sf_step call
+// Which launches a call makes, decided from the handle alone (plan_step: nothing here changes it): the per-step launches - k_select + k_step,
+// one fused launch per step or the per-cell kernel - or the resident launch k_run (nw > 0), with k_win in front of it or not.
+struct StepPlan {
+    bool generic, fused;               // per-step launches: the per-cell kernel / one fused launch per step
+    int nw, vcap, bsz;                 // the resident launch: waves per workgroup (0: the per-step launches), vector list entries, vectors per batch
+    size_t lds;
+    int win;                           // StepArgs::win
+    bool result;                       // the resident launch leaves the result block behind
+    TeamGeo tgeo, jgeo;
+    bool team_forced, team_wide, team_auto;
+    bool win_first;                    // k_win in front of k_run (more environments than CUs, young fires)
+    bool win_only;                     // ... and nothing is left behind it for sure: no k_run launch
+    bool balance;                      // segments that start their environments most expensive first (k_order)
+    bool team_any, team_segments;
+};
+
+// The choices that follow from win_first (plan_step; again where the call cannot have the window phase after all).
+static void plan_modes(const sf_sim *s, StepPlan &p, int n_steps)
 {
-    if (!s) return fail(SF_EINVAL, "sf_step: null handle");
-    if (n_steps < 0) return fail(SF_EINVAL, "sf_step: n_steps must be >= 0");
-    if (!s->have_rt) return fail(SF_ESTATE, "sf_step: call sf_set_layers or sf_set_rtable first");
-    if (!s->was_reset) return fail(SF_ESTATE, "sf_step: call sf_reset first");
-    if (ms) *ms = 0.f;
-    if (n_steps == 0) return SF_OK;
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    const bool row_was_fresh = s->status_fresh;      // the result block on the device is current as this call starts
-    s->status_fresh = false;
-    StepArgs a;
-    a.loop_db = nullptr;      // (not the closed loop of sf_loop_start)
-    a.row_valid = 0;
-    a.team_recut = 0;
-    // (0 ms: a team whose members do not all arrive at its start in the same instant starts as one at once - tests of that path)
-    a.team_timeout = 100000ull * (unsigned long long)(s->tune.v[SF_TUNE_TEAM_TIMEOUT_MS] == 0 ? 2000 : (s->tune.v[SF_TUNE_TEAM_TIMEOUT_MS] < 1 ? 1 : s->tune.v[SF_TUNE_TEAM_TIMEOUT_MS]));
-    a.team_start_timeout = s->tune.v[SF_TUNE_TEAM_TIMEOUT_MS] == 0 ? 0ull : a.team_timeout;
-    s->last_launches = 0;
-    const int n_requested = n_steps;
-    if (n_steps != 1 || mit_dev || s->last_was_step1) s->step1_polls = 0;       // (another kind of call, or nobody looked at the last update's result)
-    const bool polled = n_steps == 1 && !mit_dev && s->step1_polls >= 2;
-    a.res_block = nullptr; a.res_elapsed = nullptr; a.res_sink = nullptr; a.thist = s->thist;
-    a.order = nullptr; a.cost = nullptr;
-    a.g = s->g; a.status = s->status; a.age = s->age; a.cells = nullptr; a.burn = s->burn; a.rt = s->rt; a.rtc = nullptr; a.win_hint = nullptr;
-    a.commit = s->commit; a.tmp = s->tmp; a.flags = s->flags; a.counters = s->counters_on ? s->counters : nullptr;
-    a.parents = s->graph_on ? s->parents : nullptr;
-    const dim3 block(kWaves * 64);
-    const long long n_wave_tiles = (long long)s->g.E * s->g.TY * s->g.TX;
+    const int seg_knob = s->tune.v[SF_TUNE_RUN_SEGMENT];
+    // More environments than the chip holds workgroups: the launch would end with whatever large fire happened to start late.
+    // The rollout is cut into segments, and every segment starts its environments in the order of what they cost in the one
+    // before (k_order: most expensive first) - the tail of a segment is then made of the cheapest environments.
+    p.balance = seg_knob > 0 && s->g.E > s->n_cu * (p.nw <= 8 ? 2 : 1) && !p.win_first;       // (with every environment resident from the start there is nothing to order; nor behind k_win: the few environments that have updates left)
+    // Teams (k_run<TEAM>): forced by sf_set_tuning; always on grids of two-word rows; on one-word rows in long calls, which are then
+    // cut into segments like above - the first one runs one workgroup per environment and records what every environment costs,
+    // the following ones size the teams from that (k_team_plan) and cut the bands where the fires are by then.
+    p.team_any = (p.team_forced || p.team_wide || p.team_auto) && p.bsz == 64 && !p.win_first;      // (behind k_win: ONE launch of the plain kernel for what is left - found by the soak, world 6005034: teams sized by cost cut the call into segments, and every segment's launch made the left-over updates again)
+    p.team_segments = p.team_any && seg_knob > 0 && !p.balance;
+    p.win_only = false;
+    if (p.win_first) {
+        // Is anything left for sure not?  A fire that spans F cells (rows and columns alike: one cell after sf_reset, a cell more per side and
+        // update, fire.py:163-234) sits in a window placed to the row and - where a window placed to the vector may not hold it for the call -
+        // around the middle of the (F + 14) / 16 + 1 vectors it can straddle at worst (run_window, PL4): (64 - F) / 2 rows and 32 - 8 x vectors
+        // columns lie between it and the window's ring on every open side, and it needs one per update (+ 1: the ring itself).
+        const int F = s->fire_rows, wv = (F + 14) / 16 + 1;
+        const int room = wv > 3 ? 0 : std::min((64 - F) / 2, 32 - 8 * wv);
+        p.win_only = n_steps + 1 <= room && p.win == 1;      // (SF_TUNE_RUN_WINDOW = k > 1 leaves the window after k updates: tests)
+    }
+}
+
+// lines: control lines come inside the launch (sf_step_mitigated).
+static StepPlan plan_step(const sf_sim *s, int n_steps, bool lines)
+{
+    StepPlan p = {};
+    const Geo &g = s->g;
+    const Tuning &tn = s->tune;
+    // run(1) loops: after two step(1) + status pairs in a row (sf_sim::step1_polls) the single update runs as the resident launch
+    const bool polled = n_steps == 1 && !lines && !s->last_was_step1 && s->step1_polls >= 2;
+    const long long n_wave_tiles = (long long)g.E * g.TY * g.TX;
     // few tiles: one fused launch per step; many: select the live tiles first, then persistent waves
     // (measured crossover on 1024^2 environments: 16 envs = 8192 tiles fused 11.2 vs 13.3 us, 32 envs 14.8 vs 14.0 us)
-    const bool fused = s->fused_mode == 1 || (s->fused_mode < 0 && n_wave_tiles <= 12288);
-    const StepKernel kern = pick_step_kernel(s->g.RB, fused);
-    a.tflags = s->tflags; a.tile_list = s->tile_list; a.n_active = s->n_active; a.seam = s->seam; a.settled = s->settled; a.tdirty = s->tdirty;
-    const dim3 sel_grid((unsigned)((n_wave_tiles + kSelectThreads - 1) / kSelectThreads));
-    const Tuning &tn = s->tune;
-    const int waves_per_cu = tn.v[SF_TUNE_WAVES_PER_CU];   // persistent grid of k_step
-    long long want = fused ? (n_wave_tiles + kWaves - 1) / kWaves : (long long)s->n_cu * waves_per_cu / kWaves;
-    if (!fused && want * kWaves > n_wave_tiles) want = (n_wave_tiles + kWaves - 1) / kWaves;
-    const dim3 step_grid((unsigned)(want < 1 ? 1 : want));
-    const bool generic = s->g.ab > 1 || s->generic;
+    p.fused = s->fused_mode == 1 || (s->fused_mode < 0 && n_wave_tiles <= 12288);
+    p.generic = g.ab > 1 || s->generic;
+    p.win = tn.v[SF_TUNE_RUN_WINDOW] < 0 ? 0 : tn.v[SF_TUNE_RUN_WINDOW];
     // Environment-resident launch (k_run): all n steps of an environment in one workgroup.  Not with the
     // per-step by-products (spread graph, history) and not for the wide sprite planes.
-    int run_waves = 0, run_vcap = 0;
-    size_t run_lds = 0;
-    TeamGeo tgeo = {}, jgeo = {};
-    bool team_forced = false, team_wide = false, team_auto = false;
-    bool win_first = false;            // k_win in front of k_run (more environments than CUs, young fires)
-    if (!generic && !a.parents && !s->history && s->fused_mode != 0 && s->fused_mode != 1) {
+    if (!p.generic && !(s->graph_on && s->parents) && !s->history && s->fused_mode != 0 && s->fused_mode != 1) {
         const int waves_knob = tn.v[SF_TUNE_RUN_WAVES], envs_knob = tn.v[SF_TUNE_RUN_MIN_ENVS], vcap_knob = tn.v[SF_TUNE_RUN_VCAP];
-        const Geo &g = s->g;
         int nw = waves_knob < 1 ? 1 : (waves_knob > 16 ? 16 : waves_knob);
         const int need = (g.H + 63) / 64;                     // a thread per bitmap row is all the interest pass can use
         if (nw > need) nw = need;
@@ -1447,9 +1476,10 @@ static int step_impl(sf_sim *s, int n_steps, float *ms, const int32_t *mit_dev =
         // gaps (sf_run_kernels.h).  The k_run launch behind it makes what is left - the updates of fires that outgrew their windows - in the
         // 8-wave workgroups of this regime.  (Round 5 kept 16-wave k_run workgroups in rounds of 256 while every fire was surely young: 9.8 us per
         // update on 1024 environments in the driver's window.)  SF_TUNE_RUN_COMPACT = 2: the window kernel in front whatever the batch size (tests).
-        win_first = tn.v[SF_TUNE_RUN_WINDOW] != 0 && tn.v[SF_TUNE_RUN_COMPACT] != 0 && (g.E > s->n_cu || tn.v[SF_TUNE_RUN_COMPACT] == 2) && !mit_dev && g.VW == 1 &&
-                    g.H >= 64 && g.H <= 1024 && g.PV >= 4 && !g.dense && s->fire_rows > 0 && s->fire_rows <= 62 && n_steps <= 64 && !tn.set[SF_TUNE_RUN_WAVES] &&
-                    g.diag && (tn.v[SF_TUNE_RUN_TEAM] == 0 || tn.v[SF_TUNE_RUN_TEAM] == 1) && s->fused_mode != 2;
+        // (k_win needs the window phase: SF_TUNE_RUN_WINDOW > 0)
+        p.win_first = p.win != 0 && tn.v[SF_TUNE_RUN_COMPACT] != 0 && (g.E > s->n_cu || tn.v[SF_TUNE_RUN_COMPACT] == 2) && !lines && g.VW == 1 &&
+                      g.H >= 64 && g.H <= 1024 && g.PV >= 4 && !g.dense && s->fire_rows > 0 && s->fire_rows <= 62 && n_steps <= 64 && !tn.set[SF_TUNE_RUN_WAVES] &&
+                      g.diag && (tn.v[SF_TUNE_RUN_TEAM] == 0 || tn.v[SF_TUNE_RUN_TEAM] == 1) && s->fused_mode != 2;
         // (the launch behind k_win: while every fire surely ends the call inside 64 rows, 16-wave workgroups - an environment whose fire reached the
         // ring of a window placed to the vector gets a new window of 64 rows around where the fire stands now, 2 us per update instead of the
         // general loop's 6 in an 8-wave workgroup; everybody else's workgroup returns at once)
@@ -1465,14 +1495,14 @@ static int step_impl(sf_sim *s, int n_steps, float *ms, const int32_t *mit_dev =
         // CU that owns it and the per-step launches, which spread tiles over the whole chip, win by 1.4 - 2 x)
         // ... which the team launch (k_run<TEAM>: several workgroups per environment, each with the bitmaps of its own band of rows) takes away:
         // grids of two-word rows run there in the automatic mode too
-        tgeo = team_geometry(s);
-        jgeo = join_geometry(s);
+        p.tgeo = team_geometry(s);
+        p.jgeo = join_geometry(s);
         const int team_knob = tn.v[SF_TUNE_RUN_TEAM];
-        team_forced = tgeo.ok && team_knob >= 2 && team_knob <= kTeamMax && team_knob <= g.TY && team_knob >= tgeo.t_min && (long long)g.E * team_knob <= tgeo.slots;
+        p.team_forced = p.tgeo.ok && team_knob >= 2 && team_knob <= kTeamMax && team_knob <= g.TY && team_knob >= p.tgeo.t_min && (long long)g.E * team_knob <= p.tgeo.slots;
         // (control lines inside the launch: every row needs an owner, so the members' windows of rows have to hold the whole grid between them)
-        if (mit_dev && tgeo.rcap > 0 && (long long)team_knob * tgeo.rcap < g.H) team_forced = false;
-        team_wide = tgeo.ok && team_knob != 1 && g.VW == 2 && !mit_dev;      // (control lines inside the launch: every row needs an owner, a window of rows leaves some without)
-        const bool wanted = s->fused_mode == 2 || ((n_steps >= 2 || mit_dev || polled) && (g.VW == 1 || team_wide) && g.E >= envs_knob);
+        if (lines && p.tgeo.rcap > 0 && (long long)team_knob * p.tgeo.rcap < g.H) p.team_forced = false;
+        p.team_wide = p.tgeo.ok && team_knob != 1 && g.VW == 2 && !lines;      // (control lines inside the launch: every row needs an owner, a window of rows leaves some without)
+        const bool wanted = s->fused_mode == 2 || ((n_steps >= 2 || lines || polled) && (g.VW == 1 || p.team_wide) && g.E >= envs_knob);
         // Rows of one word: NOT automatic.  Measured on C3 / C5 (profiles/r03_team/): a member's step is a latency chain that does not get
         // shorter with half the rows, and a team's step boundary costs 5 - 10 k clocks (publish, wait for the slowest member, read), so
         // teams of 8-wave members lose to one 16-wave workgroup per environment until a fire is far larger than these get (C3: 11.0 ->
@@ -1481,215 +1511,260 @@ static int step_impl(sf_sim *s, int n_steps, float *ms, const int32_t *mit_dev =
         // of their own, and teams sized by cost are automatic from the second 64-step segment on (C5, 64 environments: 18.2 -> 17.3 us per
         // step; 128 environments: 9.9 -> 10.6, not automatic).  The gain is small because a member's step is never shorter than the ~12 k
         // clocks of the chain and the team kernel itself is ~10 % slower for an environment that stays whole.
-        team_auto = tgeo.ok && g.VW == 1 && g.E < tgeo.slots && (team_knob == -1 || (team_knob == 0 && g.E >= 2 && g.E * 4 <= s->n_cu && tgeo.waves == 16));
+        p.team_auto = p.tgeo.ok && g.VW == 1 && g.E < p.tgeo.slots && (team_knob == -1 || (team_knob == 0 && g.E >= 2 && g.E * 4 <= s->n_cu && p.tgeo.waves == 16));
         // (one environment - FireSimulation.run(), C2 -: its fire fits one workgroup for hundreds of steps, and the segments of a team rollout -
         // a plan, a prologue that reads the bitmaps and an epilogue per launch - cost a lone young fire 16 %: 3.23 against 3.74 us per step)
-        if (fits && wanted) { run_waves = nw; run_vcap = vcap; run_lds = lds; }
+        if (fits && wanted) { p.nw = nw; p.vcap = vcap; p.lds = lds; }
     }
-    if (mit_dev && !run_waves) return SF_INTERNAL_NO_RESIDENT;      // the caller falls back to scatter + step pairs
-    a.mit = mit_dev; a.mit_k = mit_k; a.todo = nullptr; a.todo_out = nullptr; a.todo_skip = 0; a.todo_cnt = nullptr; a.todo_list = nullptr; a.todo_cnt_next = nullptr;
-    a.win = tn.v[SF_TUNE_RUN_WINDOW] < 0 ? 0 : tn.v[SF_TUNE_RUN_WINDOW];
-    if (run_waves) {
+    const int bsz_knob = tn.v[SF_TUNE_RUN_BATCH];       // vectors per batch (<= 64)
+    p.bsz = bsz_knob < 8 ? 8 : (bsz_knob > 64 ? 64 : bsz_knob);
+    p.result = tn.v[SF_TUNE_RUN_RESULT] != 0;           // the launch leaves the result block behind (every workgroup counts its own environment when its steps are done)
+    plan_modes(s, p, n_steps);
+    return p;
+}
+
+// One launch of the resident rollout's segment loop: how many updates, and which kernel makes them.
+struct Segment {
+    int n;                             // updates
+    int recut;                         // StepArgs::team_recut
+    bool join, team;                   // k_run<TEAM = 2> / k_run<TEAM = 1> (else the plain kernel)
+    bool windows;                      // the team launch leaves what did not fit its windows of rows to a second launch
+    int t_min, t_max;                  // team sizes (k_team_plan)
+    int team_max;                      // sf_sim::last_team_max
+};
+
+// The segment of a resident rollout that starts after `done` of its n_steps updates.
+static Segment plan_segment(const sf_sim *s, const StepPlan &p, int n_steps, int done, bool lines)
+{
+    const Geo &g = s->g;
+    const Tuning &tn = s->tune;
+    const TeamGeo &tgeo = p.tgeo;
+    const int seg_knob = tn.v[SF_TUNE_RUN_SEGMENT];
+    Segment sg = {};
+    sg.n = p.balance && n_steps - done > seg_knob + seg_knob / 2 ? seg_knob : n_steps - done;
+    // (two-word rows: twice the segment - every launch costs a plan, a prologue that reads the environment's whole bitmap and an
+    // epilogue; measured on C4's share: 64 / 128 / 256 steps per launch = 26.3 / 26.1 / 26.8 us per step - the cuts have to follow the fires)
+    // (one-word rows, teams sized by cost: C5 10.56 / 10.23 / 10.31 us per step with 64 / 128 / 256)
+    const int tseg = (p.team_wide || p.team_auto) && !p.team_forced ? 2 * seg_knob : seg_knob;
+    // Teams of a fixed size - forced, or every workgroup slot taken at the smallest size (C4's share: 128 x 2 = 256) -: nothing to
+    // plan between segments, so the rollout is ONE launch and the teams cut their bands anew inside it (k_run, team_recut).  Cut
+    // into launches a rollout lasts the sum of the launches' slowest environments instead of the slowest sum (measured on C4's
+    // share: + 12 %, profiles/segment_penalty_probe.py) and pays a plan, a prologue and an epilogue per segment.
+    const int tk = tn.v[SF_TUNE_RUN_TEAM];
+    const bool team_fixed = p.team_segments && tn.v[SF_TUNE_TEAM_RECUT] != 0 && !(tgeo.rcap > 0 && tk == -1) &&
+                            (long long)tgeo.t_min * (tgeo.rcap ? tgeo.rcap : g.H) >= g.H &&
+                            (p.team_forced || (p.team_wide && tgeo.slots - (long long)g.E * tgeo.t_min < (g.E + 3) / 4));
+    if (p.team_segments && !team_fixed && n_steps - done > tseg + tseg / 2) sg.n = tseg;
+    sg.recut = team_fixed ? (p.team_forced ? 2 * seg_knob : tseg) : 0;
+    // Two-word rows, YOUNG fires: one member holds any fire whose rows (+ what it can grow during the launch + the cut's margins)
+    // fit its window of team_rcap rows - and a young fire cut in two only pays the step boundary (C4's share, the driver's
+    // window: 8.7 us per step with two members).  The host knows an upper bound without asking the device: a fire spans one row
+    // after sf_reset and advances one row per update at most.  A call that ends with every fire still under 480 rows gives every
+    // environment ONE member.
+    bool young = false;
+    if (p.team_wide && !p.team_forced && tk == 0 && tgeo.rcap > 0 && s->fire_rows > 0) {
+        // (cut_bands: the fire's tile rows, + ceil((updates + 1) / tile height) + 1 tile rows either side)
+        const long long room = (long long)tgeo.rcap - s->fire_rows - 2LL * done - 7LL * g.LR * g.RB - 2;
+        const long long fit = room / 2;              // updates the window is sure to hold
+        // (only where the whole call stays young - measured on C4's share: one member for the first ~ 380 of 1000 updates and two
+        // for the rest loses to two members throughout, 23.5 against 21.9 us per step; the driver's 20 after 5: 7.0 against 8.7)
+        // (C4's share, calls of 60 / 100 / 150 / 250 / 350 updates after 20: one member 7.8 / 8.3 / 9.6 / 11.9 / 15.8 us per step, two 9.1 / 9.3 / 10.8 / 12.1 / 14.1)
+        if (done == 0 && fit >= n_steps && s->fire_rows + 2LL * n_steps <= 480) { young = true; sg.n = n_steps - done; sg.recut = 0; }
+    }
+    // Teams that grow inside the launch (k_run<TEAM = 2>): long calls on one-word rows with at most one environment per CU - the CUs of
+    // fires that go out (C3: three quarters of them over 1000 updates) join the fires that are left.  SF_TUNE_RUN_JOIN.
+    const int join_knob = tn.v[SF_TUNE_RUN_JOIN];
+    const int join_min = join_knob > 1 ? join_knob : (join_knob < -1 ? -join_knob : 192);
+    // (Measured on C3 over 1000 updates with 256 / 192 / 128 / 96 / 64 environments: 10.8 -> 10.0, 10.5 -> 9.4, 9.8 -> 8.8, 9.6 -> 8.7, 9.5 -> 8.6 us per update -
+    // 32 / 16 / 8 / 2 environments: 8.6 -> 8.1, 8.2 -> 7.6, 7.8 -> 7.2, 7.3 -> 7.1 - from 64 down against the teams sized by cost between segments, which
+    // this replaces wherever it applies (they remain for calls with control lines inside the launch: C5);
+    // ONE environment - FireSimulation.run(), C2 - keeps the plain kernel: its fire is young for hundreds of updates, and this kernel has no window
+    // phase - measured on C2, 300 updates after 20: 5.1 against 6.0 us per update.  The knob set by hand wins.)
+    sg.join = !p.win_first && join_knob != 0 && !p.team_forced && !p.team_wide && ((g.E >= 2 && !tn.set[SF_TUNE_RUN_TEAM]) || tn.set[SF_TUNE_RUN_JOIN]) && !p.balance && !lines && p.bsz == 64 && done == 0 &&
+              n_steps >= join_min && !tn.set[SF_TUNE_RUN_WAVES] && !tn.set[SF_TUNE_RUN_VCAP] && p.jgeo.ok;
+    if (sg.join) { sg.n = n_steps; sg.recut = seg_knob >= 4 ? seg_knob / 2 : 2; sg.team_max = kTeamMax; }
+    sg.team = !p.win_first && !sg.join && p.team_any && !p.balance && (p.team_forced || p.team_wide || (s->cost_steps > 0 && n_steps - done >= seg_knob / 2));
+    if (sg.team) {
+        sg.team_max = p.team_forced ? tk : (kTeamMax < g.TY ? kTeamMax : g.TY);
+        // Windows of rows (two-word rows): a fire that is small enough runs in ONE workgroup with the window around it, the largest ones
+        // get up to four; whoever was given too small a team for its fire (known only on the device) is left untouched, noted in
+        // todo[] and done by the second launch - two members, half the grid each, which always fits.
+        // (Only with SF_TUNE_RUN_TEAM = -1: measured on C4's share, 128 x 2048^2, the cost-sized teams lose to two members for every
+        // environment - 55 against 37 us per step around step 1000 - because teams of different sizes do not pack into the slots of one
+        // XCD and their step boundaries then go through memory, 16 k instead of 12 k clocks each.)
+        sg.windows = tgeo.rcap > 0 && !p.team_forced && tk == -1;
+        sg.t_min = young ? 1 : (p.team_forced ? tk : (sg.windows ? 1 : tgeo.t_min));
+        sg.t_max = young ? 1 : (team_fixed && !p.team_forced ? tgeo.t_min : sg.team_max);
+    }
+    return sg;
+}
+
+// ----------------------------------------------------------------------------- running the plan
+// The fields of StepArgs every launch of a handle's kernels takes from the handle as it stands (a launch sets the rest).
+static StepArgs handle_args(const sf_sim *s)
+{
+    StepArgs a;
+    memset(&a, 0, sizeof a);
+    a.g = s->g; a.status = s->status; a.age = s->age; a.cells = s->cells; a.burn = s->burn; a.rt = s->rt;
+    a.commit = s->commit; a.tmp = s->tmp; a.flags = s->flags; a.tflags = s->tflags; a.tile_list = s->tile_list;
+    a.n_active = s->n_active; a.seam = s->seam; a.settled = s->settled; a.tdirty = s->tdirty; a.thist = s->thist; a.vbits = s->vbits;
+    a.launch = 0; a.from_commit = 1; a.ring = s->ring;
+    return a;
+}
+
+// The resident rollout: k_win in front (p.win_first), then the segment loop.
+static int run_resident(sf_sim *s, const StepPlan &p, StepArgs &a, int n_steps, bool row_was_fresh)
+{
+    const Geo &g = s->g;
+    const int32_t *mit_dev = a.mit;
+    const int mit_k = a.mit_k;
+    if (p.result) {
+        if (s->tdirty_all) HIPCHK(hipMemsetAsync(s->tdirty, 1, s->n_tiles_max, s->stream));
+        s->tdirty_all = false;
+    }
+    a.cost = s->run_cost;
+    s->last_team_max = 0;
+    if (p.win_first) {
+        // k_win: every environment's updates inside its window; what is left goes to s->todo
+        const size_t wlds = (win_lds_bytes(16) + 15) / 16 * 16 + kRunCtl * 4;
+        a.todo_out = s->todo; a.order = nullptr;
+        a.row_valid = (row_was_fresh && p.result) ? 1 : 0;
+        // (two counts that take turns, both zero to begin with: every k_win clears the one its successor appends to)
+        if (!s->todo_cnt) { int rc0 = dev_alloc(s, &s->todo_cnt, (size_t)16); if (rc0) return rc0; HIPCHK(hipMemsetAsync(s->todo_cnt, 0, 16 * sizeof(uint32_t), s->stream)); }
+        a.todo_cnt = s->todo_cnt + (s->win_seq & 1); a.todo_cnt_next = s->todo_cnt + ((s->win_seq + 1) & 1); a.todo_list = s->run_order;      // (the order array: no ordered segments in a call k_win goes in front of)
+        s->win_seq++;
+        if (p.result) { a.res_block = s->status_block; a.res_elapsed = s->elapsed_dev; a.res_sink = s->sink; }
+        const void *wk = g.att ? reinterpret_cast<const void *>(k_win<1>) : reinterpret_cast<const void *>(k_win<0>);
+        void *args[] = {&a, &n_steps};
+        { int rc0 = launch_resident(s, wk, (unsigned)g.E, 1024, wlds, args); if (rc0) return rc0; }
+        a.todo_out = nullptr; a.res_block = nullptr; a.res_elapsed = nullptr; a.res_sink = nullptr;
+        s->last_launches++;
+        a.todo = s->todo; a.todo_skip = 1;
+    }
+    for (int done = 0; done < n_steps && !p.win_only;) {
+        const Segment sg = plan_segment(s, p, n_steps, done, mit_dev != nullptr);
+        a.team_recut = sg.recut;
+        if (p.balance) {
+            hipLaunchKernelGGL(k_order, dim3(1), dim3(1024), 0, s->stream, g.E, (const uint32_t *)s->run_cost, s->run_order);
+            a.order = s->run_order;
+        }
+        a.mit = mit_dev ? mit_dev + (size_t)done * g.E * mit_k * 3 : nullptr;
+        if (p.result && done + sg.n == n_steps) { a.res_block = s->status_block; a.res_elapsed = s->elapsed_dev; a.res_sink = s->sink; }
+        // (the block is current for the call's FIRST launch only if it was when the call started - and only that launch may go by it: the
+        // launches before the last one of a call do not write it)
+        a.row_valid = (row_was_fresh && done == 0 && !p.win_first && p.result) ? 1 : 0;
+        if (sg.join) {
+            int rc0 = launch_k_run_join(s, a, sg.n, p.jgeo, s->tune.v[SF_TUNE_RUN_JOIN] < 0);
+            if (rc0) return rc0;
+        } else if (sg.team) {
+            a.todo = nullptr; a.todo_out = sg.windows ? s->todo : nullptr;
+            int rc0 = launch_k_run_team(s, a, sg.n, p.tgeo, sg.t_min, sg.t_max, s->cost_steps);
+            if (rc0) return rc0;
+            if (sg.windows) {
+                a.todo = s->todo; a.todo_out = nullptr; a.row_valid = 0;      // (the launch in front may have changed what the block counts)
+                rc0 = launch_k_run_team(s, a, sg.n, p.tgeo, p.tgeo.t_min, p.tgeo.t_min, 0, true);
+                if (rc0) return rc0;
+                a.todo = nullptr;
+            }
+            a.cost = s->run_cost;
+        } else {
+            int rc0 = launch_run(s, run_key(g, kRunPlain, run_words(g.H, p.nw, g.VW), a.mit != nullptr), (unsigned)g.E, (unsigned)p.nw * 64, p.lds, a,
+                                 sg.n, p.vcap, p.bsz);
+            if (rc0) return rc0;
+            if (g.VW > 1) s->vbits_fl_valid = false;
+        }
+        if (sg.join || sg.team) s->last_team_max = sg.team_max;
+        s->cost_steps = sg.n;
+        done += sg.n;
+        s->last_launches++;
+    }
+    if (p.win_only) s->cost_steps = n_steps;
+    s->status_fresh = p.result;
+    s->tiles_valid = false;                // the tile activity map / seam planes are not kept by k_run
+    s->last_kind = p.win_first ? 4 : 2;
+    return SF_OK;
+}
+
+// A sf_step call as planned: the buffers its launches need, then the resident rollout or the per-step loop.  mit_dev / mit_k: control
+// lines inside the resident launch (p planned with lines).
+static int run_step(sf_sim *s, StepPlan p, int n_steps, float *ms, const int32_t *mit_dev, int mit_k)
+{
+    const Geo &g = s->g;
+    const Tuning &tn = s->tune;
+    const bool row_was_fresh = s->status_fresh;      // the result block on the device is current as this call starts
+    s->status_fresh = false;
+    s->last_launches = 0;
+    const int n_requested = n_steps;
+    if (n_steps != 1 || mit_dev || s->last_was_step1) s->step1_polls = 0;       // (another kind of call, or nobody looked at the last update's result)
+    if (p.nw) {
         int rc0 = ensure_commit(s);            // k_run starts from commit[] and leaves the new states there
         if (rc0) return rc0;
         // (a team launch reads all three planes of the vector bitmap; a launch of the plain kernel on rows of several words has kept only the first)
-        if ((team_forced || team_wide || team_auto) && !s->vbits_fl_valid) s->vbits_valid = false;
+        if ((p.team_forced || p.team_wide || p.team_auto) && !s->vbits_fl_valid) s->vbits_valid = false;
         rc0 = ensure_vbits(s);
         if (rc0) return rc0;
         rc0 = ensure_bl(s);
         if (rc0) return rc0;
-        if (run_waves && a.win) {              // the window phase reads the cell-major copy of the R table
+        if (p.win) {                           // the window phase reads the cell-major copy of the R table
             rc0 = ensure_rtc(s);
-            if (rc0 == SF_ENOTSUP) a.win = 0;          // (no memory for the cell-major table: this call goes without the window phase)
+            if (rc0 == SF_ENOTSUP) { p.win = 0; p.win_first = false; plan_modes(s, p, n_steps); }      // (no memory for the cell-major table: this call goes without the window phase)
             else if (rc0) return rc0;
-            else { a.rtc = s->rtc; a.win_hint = s->win_hint; }
         }
-    } else if (!generic) {
+    } else if (!p.generic) {
         int rc0 = ensure_tiles(s);
         if (rc0) return rc0;
     }
-    if (!run_waves) { int rc0 = ensure_rm(s); if (rc0) return rc0; }
-    a.vbits = s->vbits;
-    a.cells = s->cells;
+    if (!p.nw) { int rc0 = ensure_rm(s); if (rc0) return rc0; }
+    StepArgs a = handle_args(s);
+    a.counters = s->counters_on ? s->counters : nullptr;
+    a.parents = s->graph_on ? s->parents : nullptr;
+    // (0 ms: a team whose members do not all arrive at its start in the same instant starts as one at once - tests of that path)
+    a.team_timeout = 100000ull * (unsigned long long)(tn.v[SF_TUNE_TEAM_TIMEOUT_MS] == 0 ? 2000 : (tn.v[SF_TUNE_TEAM_TIMEOUT_MS] < 1 ? 1 : tn.v[SF_TUNE_TEAM_TIMEOUT_MS]));
+    a.team_start_timeout = tn.v[SF_TUNE_TEAM_TIMEOUT_MS] == 0 ? 0ull : a.team_timeout;
+    a.mit = mit_dev; a.mit_k = mit_k;
+    a.win = p.win;
+    if (p.nw && p.win) { a.rtc = s->rtc; a.win_hint = s->win_hint; }
     if (ms) HIPCHK(hipEventRecord(s->ev0, s->stream));
-    if (run_waves) {
-        a.launch = 0; a.from_commit = 1; a.ring = s->ring;
-        const int bsz_knob = tn.v[SF_TUNE_RUN_BATCH];       // vectors per batch (<= 64)
-        const int bsz = bsz_knob < 8 ? 8 : (bsz_knob > 64 ? 64 : bsz_knob);
-        // the launch leaves the result block behind (every workgroup counts its own environment when its steps are done)
-        const int res_knob = tn.v[SF_TUNE_RUN_RESULT];
-        if (res_knob) {
-            if (s->tdirty_all) HIPCHK(hipMemsetAsync(s->tdirty, 1, s->n_tiles_max, s->stream));
-            s->tdirty_all = false;
-        }
-        // More environments than the chip holds workgroups: the launch would end with whatever large fire happened to start late.
-        // The rollout is cut into segments, and every segment starts its environments in the order of what they cost in the one
-        // before (k_order: most expensive first) - the tail of a segment is then made of the cheapest environments.
-        const int seg_knob = tn.v[SF_TUNE_RUN_SEGMENT];
-        win_first = win_first && a.win && a.rtc;
-        const bool balance = seg_knob > 0 && s->g.E > s->n_cu * (run_waves <= 8 ? 2 : 1) && !win_first;       // (with every environment resident from the start there is nothing to order; nor behind k_win: the few environments that have updates left)
-        a.cost = s->run_cost;
-        // Teams (k_run<TEAM>): forced by sf_set_tuning; always on grids of two-word rows; on one-word rows in long calls, which are then
-        // cut into segments like above - the first one runs one workgroup per environment and records what every environment costs,
-        // the following ones size the teams from that (k_team_plan) and cut the bands where the fires are by then.
-        const bool team_any = (team_forced || team_wide || team_auto) && bsz == 64 && !win_first;      // (behind k_win: ONE launch of the plain kernel for what is left - found by the soak, world 6005034: teams sized by cost cut the call into segments, and every segment's launch made the left-over updates again)
-        const bool team_segments = team_any && seg_knob > 0 && !balance;
-        s->last_team_max = 0;
-        bool win_only = false;
-        if (win_first) {
-            // k_win: every environment's updates inside its window; what is left goes to s->todo
-            const size_t wlds = (win_lds_bytes(16) + 15) / 16 * 16 + kRunCtl * 4;
-            typedef void (*win_fn)(StepArgs, int);
-            const win_fn wk = s->g.att ? k_win<1> : k_win<0>;
-            size_t &wattr = s->attr_run[30 + (s->g.att ? 1 : 0)];
-            if (wlds > 64 * 1024 && wlds > wattr) {
-                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(wk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds));
-                wattr = wlds;
-            }
-            a.todo_out = s->todo; a.order = nullptr;
-            a.row_valid = (row_was_fresh && res_knob) ? 1 : 0;
-            // (two counts that take turns, both zero to begin with: every k_win clears the one its successor appends to)
-            if (!s->todo_cnt) { int rc0 = dev_alloc(s, &s->todo_cnt, (size_t)16); if (rc0) return rc0; HIPCHK(hipMemsetAsync(s->todo_cnt, 0, 16 * sizeof(uint32_t), s->stream)); }
-            a.todo_cnt = s->todo_cnt + (s->win_seq & 1); a.todo_cnt_next = s->todo_cnt + ((s->win_seq + 1) & 1); a.todo_list = s->run_order;      // (the order array: no ordered segments in a call k_win goes in front of)
-            s->win_seq++;
-            if (res_knob) { a.res_block = s->status_block; a.res_elapsed = s->elapsed_dev; a.res_sink = s->sink; }
-            hipLaunchKernelGGL(wk, dim3((unsigned)s->g.E), dim3(1024), wlds, s->stream, a, n_steps);
-            HIPCHK(hipGetLastError());
-            a.todo_out = nullptr; a.res_block = nullptr; a.res_elapsed = nullptr; a.res_sink = nullptr;
-            s->last_launches++;
-            // Is anything left for sure not?  A fire that spans F cells (rows and columns alike: one cell after sf_reset, a cell more per side and
-            // update, fire.py:163-234) sits in a window placed to the row and - where a window placed to the vector may not hold it for the call -
-            // around the middle of the (F + 14) / 16 + 1 vectors it can straddle at worst (run_window, PL4): (64 - F) / 2 rows and 32 - 8 x vectors
-            // columns lie between it and the window's ring on every open side, and it needs one per update (+ 1: the ring itself).
-            const int F = s->fire_rows, wv = (F + 14) / 16 + 1;
-            const int room = wv > 3 ? 0 : std::min((64 - F) / 2, 32 - 8 * wv);
-            win_only = n_steps + 1 <= room && a.win == 1;      // (SF_TUNE_RUN_WINDOW = k > 1 leaves the window after k updates: tests)
-            a.todo = s->todo; a.todo_skip = 1;
-        }
-        for (int done = 0; done < n_steps && !win_only;) {
-            int seg = balance && n_steps - done > seg_knob + seg_knob / 2 ? seg_knob : n_steps - done;
-            // (two-word rows: twice the segment - every launch costs a plan, a prologue that reads the environment's whole bitmap and an
-            // epilogue; measured on C4's share: 64 / 128 / 256 steps per launch = 26.3 / 26.1 / 26.8 us per step - the cuts have to follow the fires)
-            // (one-word rows, teams sized by cost: C5 10.56 / 10.23 / 10.31 us per step with 64 / 128 / 256)
-            const int tseg = (team_wide || team_auto) && !team_forced ? 2 * seg_knob : seg_knob;
-            // Teams of a fixed size - forced, or every workgroup slot taken at the smallest size (C4's share: 128 x 2 = 256) -: nothing to
-            // plan between segments, so the rollout is ONE launch and the teams cut their bands anew inside it (k_run, team_recut).  Cut
-            // into launches a rollout lasts the sum of the launches' slowest environments instead of the slowest sum (measured on C4's
-            // share: + 12 %, profiles/segment_penalty_probe.py) and pays a plan, a prologue and an epilogue per segment.
-            const int tk0 = tn.v[SF_TUNE_RUN_TEAM];
-            const bool team_fixed = team_segments && tn.v[SF_TUNE_TEAM_RECUT] != 0 && !(tgeo.rcap > 0 && tk0 == -1) &&
-                                    (long long)tgeo.t_min * (tgeo.rcap ? tgeo.rcap : s->g.H) >= s->g.H &&
-                                    (team_forced || (team_wide && tgeo.slots - (long long)s->g.E * tgeo.t_min < (s->g.E + 3) / 4));
-            if (team_segments && !team_fixed && n_steps - done > tseg + tseg / 2) seg = tseg;
-            a.team_recut = team_fixed ? (team_forced ? 2 * seg_knob : tseg) : 0;
-            // Two-word rows, YOUNG fires: one member holds any fire whose rows (+ what it can grow during the launch + the cut's margins)
-            // fit its window of team_rcap rows - and a young fire cut in two only pays the step boundary (C4's share, the driver's
-            // window: 8.7 us per step with two members).  The host knows an upper bound without asking the device: a fire spans one row
-            // after sf_reset and advances one row per update at most.  A call that ends with every fire still under 480 rows gives every
-            // environment ONE member.
-            bool young = false;
-            if (team_wide && !team_forced && tk0 == 0 && tgeo.rcap > 0 && s->fire_rows > 0) {
-                // (cut_bands: the fire's tile rows, + ceil((updates + 1) / tile height) + 1 tile rows either side)
-                const long long room = (long long)tgeo.rcap - s->fire_rows - 2LL * done - 7LL * s->g.LR * s->g.RB - 2;
-                const long long fit = room / 2;              // updates the window is sure to hold
-                // (only where the whole call stays young - measured on C4's share: one member for the first ~ 380 of 1000 updates and two
-                // for the rest loses to two members throughout, 23.5 against 21.9 us per step; the driver's 20 after 5: 7.0 against 8.7)
-                // (C4's share, calls of 60 / 100 / 150 / 250 / 350 updates after 20: one member 7.8 / 8.3 / 9.6 / 11.9 / 15.8 us per step, two 9.1 / 9.3 / 10.8 / 12.1 / 14.1)
-                if (done == 0 && fit >= n_steps && s->fire_rows + 2LL * n_steps <= 480) { young = true; seg = n_steps - done; a.team_recut = 0; }
-            }
-            // Teams that grow inside the launch (k_run<TEAM = 2>): long calls on one-word rows with at most one environment per CU - the CUs of
-            // fires that go out (C3: three quarters of them over 1000 updates) join the fires that are left.  SF_TUNE_RUN_JOIN.
-            const int join_knob = tn.v[SF_TUNE_RUN_JOIN];
-            const int join_min = join_knob > 1 ? join_knob : (join_knob < -1 ? -join_knob : 192);
-            // (Measured on C3 over 1000 updates with 256 / 192 / 128 / 96 / 64 environments: 10.8 -> 10.0, 10.5 -> 9.4, 9.8 -> 8.8, 9.6 -> 8.7, 9.5 -> 8.6 us per update -
-            // 32 / 16 / 8 / 2 environments: 8.6 -> 8.1, 8.2 -> 7.6, 7.8 -> 7.2, 7.3 -> 7.1 - from 64 down against the teams sized by cost between segments, which
-            // this replaces wherever it applies (they remain for calls with control lines inside the launch: C5);
-            // ONE environment - FireSimulation.run(), C2 - keeps the plain kernel: its fire is young for hundreds of updates, and this kernel has no window
-            // phase - measured on C2, 300 updates after 20: 5.1 against 6.0 us per update.  The knob set by hand wins.)
-            const bool use_join = !win_first && join_knob != 0 && !team_forced && !team_wide && ((s->g.E >= 2 && !tn.set[SF_TUNE_RUN_TEAM]) || tn.set[SF_TUNE_RUN_JOIN]) && !balance && !mit_dev && bsz == 64 && done == 0 &&
-                                  n_steps >= join_min && !tn.set[SF_TUNE_RUN_WAVES] && !tn.set[SF_TUNE_RUN_VCAP] && jgeo.ok;
-            if (use_join) { seg = n_steps; a.team_recut = 0; }
-            const bool use_team = !win_first && !use_join && team_any && !balance && (team_forced || team_wide || (s->cost_steps > 0 && n_steps - done >= seg_knob / 2));
-            if (balance) {
-                hipLaunchKernelGGL(k_order, dim3(1), dim3(1024), 0, s->stream, s->g.E, (const uint32_t *)s->run_cost, s->run_order);
-                a.order = s->run_order;
-            }
-            a.mit = mit_dev ? mit_dev + (size_t)done * s->g.E * mit_k * 3 : nullptr;
-            if (res_knob && done + seg == n_steps) { a.res_block = s->status_block; a.res_elapsed = s->elapsed_dev; a.res_sink = s->sink; }
-            // (the block is current for the call's FIRST launch only if it was when the call started - and only that launch may go by it: the
-            // launches before the last one of a call do not write it)
-            a.row_valid = (row_was_fresh && done == 0 && !win_first && res_knob) ? 1 : 0;
-            if (use_join) {
-                const int recut = seg_knob >= 4 ? seg_knob / 2 : 2;
-                int rc0 = launch_k_run_join(s, a, seg, jgeo, recut, join_knob < 0);
-                if (rc0) return rc0;
-                a.team_recut = 0;
-                s->last_team_max = kTeamMax;
-            } else if (use_team) {
-                const int tk = tn.v[SF_TUNE_RUN_TEAM];
-                const int t_max = team_forced ? tk : (kTeamMax < s->g.TY ? kTeamMax : s->g.TY);
-                // Windows of rows (two-word rows): a fire that is small enough runs in ONE workgroup with the window around it, the largest ones
-                // get up to four; whoever was given too small a team for its fire (known only on the device) is left untouched, noted in
-                // todo[] and done by the second launch - two members, half the grid each, which always fits.
-                // (Only with SF_TUNE_RUN_TEAM = -1: measured on C4's share, 128 x 2048^2, the cost-sized teams lose to two members for every
-                // environment - 55 against 37 us per step around step 1000 - because teams of different sizes do not pack into the slots of one
-                // XCD and their step boundaries then go through memory, 16 k instead of 12 k clocks each.)
-                const bool windows = tgeo.rcap > 0 && !team_forced && tk == -1;
-                a.todo = nullptr; a.todo_out = windows ? s->todo : nullptr;
-                int rc0 = young ? launch_k_run_team(s, a, seg, tgeo, 1, 1, s->cost_steps)
-                                : launch_k_run_team(s, a, seg, tgeo, team_forced ? tk : (windows ? 1 : tgeo.t_min), team_fixed && !team_forced ? tgeo.t_min : t_max, s->cost_steps);
-                if (rc0) return rc0;
-                if (windows) {
-                    a.todo = s->todo; a.todo_out = nullptr; a.row_valid = 0;      // (the launch in front may have changed what the block counts)
-                    rc0 = launch_k_run_team(s, a, seg, tgeo, tgeo.t_min, tgeo.t_min, 0, true);
-                    if (rc0) return rc0;
-                    a.todo = nullptr;
-                }
-                a.cost = s->run_cost;
-                s->last_team_max = t_max;
-            } else {
-                int rc0 = launch_k_run(s, a, seg, run_waves, run_vcap, run_lds, bsz);
-                if (rc0) return rc0;
-                if (s->g.VW > 1) s->vbits_fl_valid = false;
-            }
-            s->cost_steps = seg;
-            done += seg;
-            s->last_launches++;
-        }
-        if (win_only) s->cost_steps = n_steps;
-        s->status_fresh = res_knob != 0;
-        s->tiles_valid = false;                // the tile activity map / seam planes are not kept by k_run
-        s->last_kind = win_first && a.todo ? 4 : 2;
+    if (p.nw) {
+        int rc0 = run_resident(s, p, a, n_steps, row_was_fresh);
+        if (rc0) return rc0;
         n_steps = 0;                           // nothing left for the per-step loop
     } else if (n_steps > 0) {
         s->vbits_valid = false;                // the per-step kernels do not keep the vector bitmap
-        if (generic) s->tiles_valid = false;   // nor does the per-cell kernel keep the tile maps
-        s->last_kind = generic ? 3 : (fused ? 1 : 0);
+        if (p.generic) s->tiles_valid = false; // nor does the per-cell kernel keep the tile maps
+        s->last_kind = p.generic ? 3 : (p.fused ? 1 : 0);
     }
-    const dim3 cell_grid((unsigned)((s->g.W + 255) / 256), (unsigned)s->g.H, (unsigned)s->g.E);
+    const long long n_wave_tiles = (long long)g.E * g.TY * g.TX;
+    const dim3 sel_grid((unsigned)((n_wave_tiles + kSelectThreads - 1) / kSelectThreads));
+    const int waves_per_cu = tn.v[SF_TUNE_WAVES_PER_CU];   // persistent grid of k_step
+    long long want = p.fused ? (n_wave_tiles + kWaves - 1) / kWaves : (long long)s->n_cu * waves_per_cu / kWaves;
+    if (!p.fused && want * kWaves > n_wave_tiles) want = (n_wave_tiles + kWaves - 1) / kWaves;
+    const dim3 step_grid((unsigned)(want < 1 ? 1 : want));
+    const StepKernel kern = pick_step_kernel(g.RB, p.fused);
+    const dim3 cell_grid((unsigned)((g.W + 255) / 256), (unsigned)g.H, (unsigned)g.E);
     for (int i = 0; i < n_steps; ++i) {
         a.launch = s->seq;
         a.from_commit = s->committed ? 1 : 0;
         a.ring = s->ring;
-        if (generic) {
-            if (s->g.ab == 1) hipLaunchKernelGGL(k_step_cells<uint8_t>, cell_grid, dim3(256), 0, s->stream, a);
-            else if (s->g.ab == 2) hipLaunchKernelGGL(k_step_cells<uint16_t>, cell_grid, dim3(256), 0, s->stream, a);
+        if (p.generic) {
+            if (g.ab == 1) hipLaunchKernelGGL(k_step_cells<uint8_t>, cell_grid, dim3(256), 0, s->stream, a);
+            else if (g.ab == 2) hipLaunchKernelGGL(k_step_cells<uint16_t>, cell_grid, dim3(256), 0, s->stream, a);
             else hipLaunchKernelGGL(k_step_cells<uint32_t>, cell_grid, dim3(256), 0, s->stream, a);
         } else {
-            if (!fused) hipLaunchKernelGGL(k_select, sel_grid, dim3(kSelectThreads), 0, s->stream, a);
-            hipLaunchKernelGGL(kern, step_grid, block, (size_t)kWaves * s->g.lds_wave_bytes, s->stream, a);
+            if (!p.fused) hipLaunchKernelGGL(k_select, sel_grid, dim3(kSelectThreads), 0, s->stream, a);
+            hipLaunchKernelGGL(kern, step_grid, dim3(kWaves * 64), (size_t)kWaves * g.lds_wave_bytes, s->stream, a);
             s->ring ^= 1;
         }
         if (a.parents) {
-            if (generic || fused) hipLaunchKernelGGL(k_graph_pass, cell_grid, dim3(256), 0, s->stream, a);
+            if (p.generic || p.fused) hipLaunchKernelGGL(k_graph_pass, cell_grid, dim3(256), 0, s->stream, a);
             else hipLaunchKernelGGL(k_graph_pass_tiles, dim3((unsigned)(s->n_cu * 8)), dim3(256), 0, s->stream, a);
         }
-        if (s->history) hipLaunchKernelGGL(k_record, cell_grid, dim3(256), 0, s->stream, s->g, (const uint8_t *)s->status,
-                                           (const EnvState *)(s->tmp + (size_t)(a.launch & 1) * s->g.E), s->history, s->history_cap);
+        if (s->history) hipLaunchKernelGGL(k_record, cell_grid, dim3(256), 0, s->stream, g, (const uint8_t *)s->status,
+                                           (const EnvState *)(s->tmp + (size_t)(a.launch & 1) * g.E), s->history, s->history_cap);
         s->seq = (s->seq + 1) % 6;
         s->committed = false;
     }
-    if (s->fire_rows > 0) { const long long fr = (long long)s->fire_rows + 2LL * n_requested; s->fire_rows = fr > s->g.H ? s->g.H : (int)fr; }
+    if (s->fire_rows > 0) { const long long fr = (long long)s->fire_rows + 2LL * n_requested; s->fire_rows = fr > g.H ? g.H : (int)fr; }
     s->last_was_step1 = n_requested == 1 && !mit_dev;
     if (ms) HIPCHK(hipEventRecord(s->ev1, s->stream));
     // no commit here: the states stay in the rings until something asks for them (ensure_commit)
@@ -1699,6 +1774,18 @@ static int step_impl(sf_sim *s, int n_steps, float *ms, const int32_t *mit_dev =
     if ((ms || !s->async) && s->xerr_pinned && *s->xerr_pinned)
         return fail(SF_EHIP, "sf_step: a workgroup of a team launch (k_run<TEAM>) gave up waiting for a team member; the state of this handle is void");
     return SF_OK;
+}
+
+static int step_impl(sf_sim *s, int n_steps, float *ms)
+{
+    if (!s) return fail(SF_EINVAL, "sf_step: null handle");
+    if (n_steps < 0) return fail(SF_EINVAL, "sf_step: n_steps must be >= 0");
+    if (!s->have_rt) return fail(SF_ESTATE, "sf_step: call sf_set_layers or sf_set_rtable first");
+    if (!s->was_reset) return fail(SF_ESTATE, "sf_step: call sf_reset first");
+    if (ms) *ms = 0.f;
+    if (n_steps == 0) return SF_OK;
+    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
+    return run_step(s, plan_step(s, n_steps, false), n_steps, ms, nullptr, 0);
 }
 
 // The per-update history FireSimulation._save_data appends to fire_map.npy (simulation.py:548-549,
@@ -1817,6 +1904,7 @@ extern "C" int sf_step_mitigated(sf_sim *s, int32_t n_steps, const int32_t *pts,
     if (!s->have_rt) return fail(SF_ESTATE, "sf_step: call sf_set_layers or sf_set_rtable first");
     if (!s->was_reset) return fail(SF_ESTATE, "sf_step: call sf_reset first");
     HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
+    const StepPlan plan = plan_step(s, n_steps, true);       // can the resident launch take the lines?  Otherwise scatter + step pairs
     const Geo &g = s->g;
     const size_t per_step = (size_t)g.E * k * 3, rows_bytes = (size_t)g.E * k * 4 * sizeof(int32_t);
     const size_t blk_bytes = device_pointer ? 0 : (size_t)n_steps * per_step * sizeof(int32_t);
@@ -1834,13 +1922,15 @@ extern "C" int sf_step_mitigated(sf_sim *s, int32_t n_steps, const int32_t *pts,
         HIPCHK(hipMemcpyAsync(d, pts, blk_bytes, hipMemcpyHostToDevice, s->stream));
         blk = d;
     }
-    int rc = step_impl(s, n_steps, ms_out, blk, k);
-    if (rc != SF_INTERNAL_NO_RESIDENT) return rc;
+    if (plan.nw) return run_step(s, plan, n_steps, ms_out, blk, k);
     // per-step launches: scatter the step's points, then one update
+    // (the bookkeeping of a call with control lines, whichever way it runs: its step(1) calls are not a run(1) loop)
+    s->status_fresh = false; s->last_launches = 0; s->step1_polls = 0;
+    int rc = SF_OK;
     const bool was_async = s->async;
     s->async = true;
     float total = 0.f;
-    for (int i = 0; i < n_steps && rc != SF_EHIP; ++i) {
+    for (int i = 0; i < n_steps; ++i) {
         hipLaunchKernelGGL(k_expand_pts, dim3((unsigned)((g.E * k + 255) / 256)), dim3(256), 0, s->stream, g.E, k,
                            blk + (size_t)i * per_step, rows);
         rc = scatter_points(s, rows, g.E * k, false);
@@ -1864,35 +1954,23 @@ extern "C" int sf_step_mitigated(sf_sim *s, int32_t n_steps, const int32_t *pts,
 static int loop_launch(sf_sim *s)
 {
     const Geo &g = s->g;
-    StepArgs a;
-    memset(&a, 0, sizeof a);
-    a.g = g; a.status = s->status; a.age = s->age; a.cells = s->cells; a.burn = s->burn; a.rt = s->rt; a.rtc = nullptr; a.win_hint = nullptr;
-    a.commit = s->commit; a.tmp = s->tmp; a.flags = s->flags; a.counters = nullptr; a.tflags = s->tflags; a.tile_list = s->tile_list;
-    a.n_active = s->n_active; a.seam = s->seam; a.settled = s->settled; a.tdirty = s->tdirty; a.thist = s->thist; a.vbits = s->vbits;
-    a.launch = 0; a.from_commit = 1; a.ring = s->ring;
+    StepArgs a = handle_args(s);
     a.mit = s->loop_pts_mem; a.mit_k = s->loop_k;
     a.res_block = s->status_block; a.res_elapsed = s->elapsed_dev; a.res_sink = s->sink;
     a.cost = s->run_cost;
     a.loop_db = s->loop_db_dev; a.loop_pts_host = s->loop_pts_dev; a.loop_res_host = s->loop_res_dev;
     a.loop_seq = s->loop_mem; a.loop_done = s->loop_mem + 32; a.loop_pts = s->loop_pts_mem;
     a.loop_timeout = 400000000ull;             // ~0.2 s without a ring: the workgroups leave, the next sf_loop_step starts them again
-    hipStream_t st = s->stream;
-    HIPCHK(hipMemsetAsync(s->loop_mem, 0, sizeof(uint32_t), st));       // nothing forwarded yet (the word may hold the stop of the launch before)
+    HIPCHK(hipMemsetAsync(s->loop_mem, 0, sizeof(uint32_t), s->stream));       // nothing forwarded yet (the word may hold the stop of the launch before)
     // one 16-wave workgroup per environment - or the light loop's 8-wave one (SF_TUNE_LOOP_LIGHT)
     const int nw_cap = s->loop_light ? 8 : 16;
     const int nw = (g.H + 63) / 64 < nw_cap ? (g.H + 63) / 64 : nw_cap;
-    const bool two_rows = g.H > nw * 64;                 // (8 waves on up to 1024 rows: two bitmap rows per thread, k_run<2, ...>)
     long long all_vec = (long long)g.H * g.PV;
     int vcap = s->loop_light ? 1024 : 4096;
     if (vcap > all_vec) vcap = (int)((all_vec + 63) / 64 * 64);
     const size_t lds = run_lds_bytes(g, nw, vcap);
-    // (the closed loop's own instantiations of k_run live in simfire_hip_run2.hip; two rows per thread: simfire_hip_run3.hip)
-    size_t &attr = two_rows ? s->attr_run[28 + (g.att ? 1 : 0)] : s->attr_run[24 + (g.att ? 1 : 0)];      // (slots of their own: a slot shared with another kernel would leave one of the two without its attribute)
-    const bool set_lds = lds > 64 * 1024 && lds > attr;
-    if (two_rows) HIPCHK(sf_run3_launch_loop2(g.att ? 1 : 0, (unsigned)g.E, (unsigned)nw * 64, lds, set_lds, st, &a, sizeof a, vcap));
-    else HIPCHK(sf_run2_launch_loop(g.att ? 1 : 0, g.diag ? 1 : 0, (unsigned)g.E, (unsigned)nw * 64, lds, set_lds, st, &a, sizeof a, vcap));
-    if (set_lds) attr = lds;
-    return SF_OK;
+    // (8 waves on up to 1024 rows: two bitmap rows per thread, k_run<2, ...>)
+    return launch_run(s, run_key(g, kRunLoop, run_words(g.H, nw, 1), true), (unsigned)g.E, (unsigned)nw * 64, lds, a, 0x7FFFFFFF, vcap, 64);
 }
 
 extern "C" int sf_loop_start(sf_sim *s, int32_t k)
