@@ -173,6 +173,28 @@ int sf_run_delta(sf_sim *sim, int32_t n_steps, int32_t env, int32_t *status_row 
 int sf_get_burn(sf_sim *sim, int32_t env, double *out);
 int sf_set_burn(sf_sim *sim, int32_t env, const double *burn);
 
+/* Environment state: fork, snapshot, restore.  Every call ends a running closed loop (sf_loop_start) first,
+ * needs sf_reset to have run once (SF_ESTATE) and refuses a handle whose last team launch failed.
+ * sf_copy_envs: environment dst[i] becomes environment src[i] in every respect - cells, sprite ages, burn_amounts, the attenuation
+ * books, spread-graph parents, update() calls made, elapsed_time, running, the result row - in ONE launch for all n pairs.  A src may
+ * repeat (one to many); the dst are distinct and none of them is a src of the same call; n == 0 does nothing; anything else is
+ * SF_EINVAL.  With SF_COPY_TERRAIN on a handle created with per_env_terrain, dst also takes src's layers and R table (without
+ * it, and on a shared-terrain handle, dst keeps its own terrain).  In async mode (sf_set_async) the copy is only enqueued. */
+#define SF_COPY_TERRAIN 1
+int sf_copy_envs(sf_sim *sim, const int32_t *src, const int32_t *dst, int32_t n, int32_t flags);
+/* Bytes of one environment's state blob (a versioned header, then the planes; the same whatever the handle's internal layout). */
+int sf_state_bytes(sf_sim *sim, int64_t *bytes_out);
+/* The state of environments envs[0 .. n) into out (n blobs of sf_state_bytes each, back to back - a multiple of 16 bytes; a host
+ * pointer, or device memory when device_pointer != 0, which must then be 16-byte aligned, else SF_EINVAL).  Every byte of a blob is
+ * written: two saves of the same state are equal.  A device-pointer save in async mode is only enqueued (the blobs are there when the
+ * handle's stream has got there: sf_sync); the caller orders its own work on the buffer before the call. */
+int sf_save_state(sf_sim *sim, int32_t n, const int32_t *envs, void *out, int32_t device_pointer);
+/* The reverse: environment envs[i] takes the state of blob i.  A blob whose header does not match this handle (version, grid,
+ * max_fire_duration, diagonal spread, attenuation, max_time, update_rate, pixel_scale threshold, prune_after_quit, spread graph) is
+ * SF_EINVAL and nothing is changed.  A device buffer must be 16-byte aligned (SF_EINVAL).  A device-pointer load waits for the stream
+ * once to read the headers; the restore itself is only enqueued in async mode (the caller keeps the buffer until sf_sync). */
+int sf_load_state(sf_sim *sim, int32_t n, const int32_t *envs, const void *in, int32_t device_pointer);
+
 /* Per-environment result block, the quantities an RL harness turns into episode returns:
  * status[e] = { running (1 = GameStatus.RUNNING), update() calls made (elapsed_steps),
  *               count of cells in each BurnStatus 0..5 };   elapsed_time[e] minutes (may be NULL) */

@@ -63,6 +63,10 @@ SIGNATURES = {
     "sf_run_delta": [_VP, _I32, _I32, _VP, _VP, _VP, _I32, C.POINTER(_I32)],
     "sf_get_burn": [_VP, _I32, _VP],
     "sf_set_burn": [_VP, _I32, _VP],
+    "sf_copy_envs": [_VP, _VP, _VP, _I32, _I32],
+    "sf_state_bytes": [_VP, C.POINTER(_I64)],
+    "sf_save_state": [_VP, _I32, _VP, _VP, _I32],
+    "sf_load_state": [_VP, _I32, _VP, _VP, _I32],
     "sf_get_status": [_VP, _VP, _VP],
     "sf_fire_map_device": [_VP, C.POINTER(_VP), C.POINTER(_I64), C.POINTER(_I64)],
     "sf_status_device": [_VP, C.POINTER(_VP)],

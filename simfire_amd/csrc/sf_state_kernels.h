@@ -1,0 +1,227 @@
+// Environment state: fork inside a handle (k_env_copy), snapshot into a caller buffer and restore from it (k_state_pack /
+// k_state_unpack), and the vector bitmap of a restored environment (k_state_vbits).  Part of simfire_hip.hip only (the run units do
+// not include it); the host side is sf_copy_envs / sf_save_state / sf_load_state there, the blob format is DESIGN.md section 11.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "sf_common.h"
+
+namespace {
+
+// ------------------------------------------------------------------------------------------ fork
+// One per-environment slice of a handle buffer: environment e's bytes are [base + e * stride, base + e * stride + len).
+struct CopySeg {
+    uint8_t *base;
+    long long stride, len;
+};
+constexpr int kCopySegs = 24;       // enough for every slice sf_copy_envs names (22 at most)
+constexpr int kCopyPairs = 128;     // (src, dst) pairs per launch: they travel as kernel arguments, so an enqueued launch owns them
+struct CopyList {
+    CopySeg seg[kCopySegs];
+    int n_seg;
+    int32_t src[kCopyPairs], dst[kCopyPairs];
+};
+
+// blockIdx.y = pair, blockIdx.x with the grid's x extent strides over every slice.  A slice whose two ends sit on 16-byte boundaries
+// is copied in 16-byte vectors, numbered from the 128-byte line its destination starts in: the 8 lanes of a line write it whole (or
+// the part of it that belongs to the slice - the neighbour environment's bytes are never touched).  Other slices (the 24-byte
+// EnvState, per-environment words, the tile flag planes) are a few hundred bytes and go byte by byte.
+__global__ __launch_bounds__(256) void k_env_copy(CopyList L)
+{
+    const int p = blockIdx.y;
+    const long long gtid = (long long)blockIdx.x * blockDim.x + threadIdx.x, gstride = (long long)gridDim.x * blockDim.x;
+    const long long se = L.src[p], de = L.dst[p];
+    for (int k = 0; k < L.n_seg; ++k) {
+        const CopySeg c = L.seg[k];
+        const uint8_t *src = c.base + se * c.stride;
+        uint8_t *dst = c.base + de * c.stride;
+        const long long len = c.len;
+        if ((((uintptr_t)src | (uintptr_t)dst) & 15) == 0) {
+            const long long head = (long long)((uintptr_t)dst & 127);          // bytes of the first line in front of the slice
+            const long long units = (head + len + 15) >> 4;
+            for (long long u = gtid; u < units; u += gstride) {
+                const long long o = u * 16 - head;                              // slice offset of this vector (16-aligned, may be < 0)
+                if (o < 0) continue;
+                if (o + 16 <= len) {
+                    *reinterpret_cast<uint4 *>(dst + o) = *reinterpret_cast<const uint4 *>(src + o);
+                } else {
+                    for (long long b = o; b < len; ++b) dst[b] = src[b];
+                }
+            }
+        } else {
+            for (long long b = gtid; b < len; b += gstride) dst[b] = src[b];
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------- snapshot / restore
+// The blob of one environment (sf_save_state), whatever layout the handle has current:
+//   [0, 128)     StateHeader
+//   [128, 152)   EnvState (commit)          [160, 192) result row (8 x int32)     [192, 200) elapsed_time (f64)
+//   from 256, each section rounded up to 16 bytes: status u8 [H][W] (raw bytes), sprite masks [H][W] x ab bytes (little endian),
+//   burn f64 [H][W] (the stored value: attenuation still owed is in settled), settled u32 [H][W] (attenuation on), parents u8 [H][W]
+//   (spread graph on)
+constexpr uint32_t kStateMagic = 0x54534653u;      // "SFST"
+constexpr uint32_t kStateVersion = 1u;
+struct StateHeader {
+    uint32_t magic, version;
+    int64_t bytes;                                 // the whole blob
+    int32_t H, W, md, ab;
+    int32_t diag, att, has_max_time, prune_after_quit;
+    int32_t has_parents, fire_rows, reserved0, reserved1;      // fire_rows: the saving handle's bound on the fire's height (0 = none)
+    double max_time, update_rate, pixel_scale;
+    uint8_t pad[40];
+};
+static_assert(sizeof(StateHeader) == 128, "StateHeader is 128 bytes");
+constexpr long long kStateFixed = 256;
+__host__ __device__ inline long long st_round(long long b) { return (b + 15) / 16 * 16; }
+struct StateLayout {
+    long long status, age, burn, settled, parents, bytes;
+};
+__host__ __device__ inline StateLayout state_layout(const Geo &g, bool parents)
+{
+    const long long n = (long long)g.H * g.W;
+    StateLayout l;
+    l.status = kStateFixed;
+    l.age = l.status + st_round(n);
+    l.burn = l.age + st_round(n * g.ab);
+    l.settled = l.burn + st_round(n * 8);
+    l.parents = l.settled + (g.att ? st_round(n * 4) : 0);
+    l.bytes = l.parents + (parents ? st_round(n) : 0);
+    return l;
+}
+
+constexpr int kStateEnvs = 128;     // environments per launch (their numbers travel as kernel arguments)
+struct StateArgs {
+    Geo g;
+    uint8_t *status, *age, *cells;                 // cells: the blocked plane when it is current, else null (row-major planes)
+    double *burn;
+    uint32_t *settled;
+    uint8_t *parents;
+    unsigned long long *vbits;
+    EnvState *commit;
+    int32_t *res_block, *res_sink;
+    double *res_elapsed;
+    uint8_t *blob;                                 // blob of list entry i at blob + i * stride
+    long long stride;
+    StateLayout lay;
+    StateHeader hdr;                               // (pack) written in front of every blob
+    int n;
+    int32_t env[kStateEnvs];
+};
+
+// One thread per cell of row blockIdx.y, environment entry blockIdx.z; the first workgroup of an entry also writes the header and
+// the EnvState / result row / elapsed_time.
+__global__ __launch_bounds__(256) void k_state_pack(StateArgs a)
+{
+    const Geo &g = a.g;
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, i = blockIdx.z, e = a.env[i];
+    uint8_t *b = a.blob + (long long)i * a.stride;
+    if (blockIdx.x == 0 && y == 0) {
+        const int t = threadIdx.x;
+        if (t < 32) reinterpret_cast<uint32_t *>(b)[t] = reinterpret_cast<const uint32_t *>(&a.hdr)[t];
+        else if (t < 38) reinterpret_cast<uint32_t *>(b + 128)[t - 32] = reinterpret_cast<const uint32_t *>(a.commit + e)[t - 32];
+        else if (t < 40) reinterpret_cast<uint32_t *>(b + 128)[t - 32] = 0u;
+        else if (t < 48) reinterpret_cast<int32_t *>(b + 160)[t - 40] = a.res_block[(long long)e * 8 + t - 40];
+        else if (t == 48) *reinterpret_cast<double *>(b + 192) = a.res_elapsed[e];
+        else if (t >= 50 && t < 64) reinterpret_cast<uint32_t *>(b + 200)[t - 50] = 0u;      // [200, 256)
+        else if (t == 64) {      // the padding behind every section: a blob holds nothing but the state (two saves of one state are equal)
+            const long long n = (long long)g.H * g.W;
+            const long long ends[5] = {a.lay.status + n, a.lay.age + n * g.ab, a.lay.burn + n * 8, g.att ? a.lay.settled + n * 4 : a.lay.parents,
+                                       a.parents ? a.lay.parents + n : a.lay.bytes};
+            const long long nexts[5] = {a.lay.age, a.lay.burn, a.lay.settled, a.lay.parents, a.lay.bytes};
+            for (int k = 0; k < 5; ++k)
+                for (long long q = ends[k]; q < nexts[k]; ++q) b[q] = 0u;
+        }
+    }
+    if (x >= g.W) return;
+    const long long c = (long long)y * g.W + x, o = (long long)e * g.plane_env + (long long)y * g.P + x;
+    uint8_t st;
+    uint32_t m;
+    if (a.cells) {
+        const uint8_t *cell = a.cells + (long long)e * g.cells_env + bl_cell(g, y, x);
+        m = cell[0];
+        st = cell[kBlStatus];
+    } else {
+        m = age_load(g, a.age + (long long)e * g.age_env * g.ab, (long long)y * g.P + x);
+        st = a.status[o];
+    }
+    b[a.lay.status + c] = st;
+    uint8_t *ma = b + a.lay.age + c * g.ab;
+    for (int k = 0; k < g.ab; ++k) ma[k] = (uint8_t)(m >> (8 * k));
+    reinterpret_cast<double *>(b + a.lay.burn)[c] = a.burn[o];
+    if (g.att) reinterpret_cast<uint32_t *>(b + a.lay.settled)[c] = a.settled[o];
+    if (a.parents) b[a.lay.parents + c] = a.parents[o];
+}
+
+// The reverse, into the layout that is current.  The caller has zeroed the environment's cell planes (guard rows / quads and pitch
+// padding stay zero); threads past W write the zero padding of burn / settled / parents.
+__global__ __launch_bounds__(256) void k_state_unpack(StateArgs a)
+{
+    const Geo &g = a.g;
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, i = blockIdx.z, e = a.env[i];
+    const uint8_t *b = a.blob + (long long)i * a.stride;
+    if (blockIdx.x == 0 && y == 0) {
+        const int t = threadIdx.x;
+        if (t < 6) reinterpret_cast<uint32_t *>(a.commit + e)[t] = reinterpret_cast<const uint32_t *>(b + 128)[t];
+        else if (t >= 8 && t < 16) {
+            const int32_t v = reinterpret_cast<const int32_t *>(b + 160)[t - 8];
+            a.res_block[(long long)e * 8 + t - 8] = v;
+            if (a.res_sink) a.res_sink[(long long)e * 8 + t - 8] = v;
+        } else if (t == 16) a.res_elapsed[e] = *reinterpret_cast<const double *>(b + 192);
+    }
+    if (x >= g.P) return;
+    const long long o = (long long)e * g.plane_env + (long long)y * g.P + x;
+    if (x >= g.W) {
+        a.burn[o] = 0.0;
+        if (g.att) a.settled[o] = 0u;
+        if (a.parents) a.parents[o] = 0u;
+        return;
+    }
+    const long long c = (long long)y * g.W + x;
+    const uint8_t st = b[a.lay.status + c];
+    const uint8_t *ma = b + a.lay.age + c * g.ab;
+    uint32_t m = 0;
+    for (int k = 0; k < g.ab; ++k) m |= (uint32_t)ma[k] << (8 * k);
+    if (a.cells) {
+        uint8_t *cell = a.cells + (long long)e * g.cells_env + bl_cell(g, y, x);
+        cell[0] = (uint8_t)m;
+        cell[kBlStatus] = st;
+    } else {
+        age_store(g, a.age + (long long)e * g.age_env * g.ab, (long long)y * g.P + x, m);
+        a.status[o] = st;
+    }
+    a.burn[o] = reinterpret_cast<const double *>(b + a.lay.burn)[c];
+    if (g.att) a.settled[o] = reinterpret_cast<const uint32_t *>(b + a.lay.settled)[c];
+    if (a.parents) a.parents[o] = b[a.lay.parents + c];
+}
+
+// The three planes of the vector bitmap of a restored environment, from the blob's sprite masks (so that the blocked plane and the
+// row-major planes are served alike): one wave per (row, 64-vector word), as k_rebuild_vbits.
+__global__ __launch_bounds__(64) void k_state_vbits(StateArgs a)
+{
+    const Geo &g = a.g;
+    const int w = blockIdx.x, y = blockIdx.y, i = blockIdx.z, e = a.env[i], lane = threadIdx.x;
+    const int v = w * 64 + lane;
+    const uint8_t *ma = a.blob + (long long)i * a.stride + a.lay.age + (long long)y * g.W * g.ab;
+    bool any = false, first = false, last = false;
+    if (v < g.PV)
+        for (int j = 0; j < 16; ++j) {
+            const int x = v * 16 + j;
+            if (x >= g.W) break;
+            bool nz = false;
+            for (int k = 0; k < g.ab; ++k) nz |= ma[(long long)x * g.ab + k] != 0;
+            any |= nz;
+            if (j == 0) first = nz;
+            if (j == 15) last = nz;
+        }
+    const unsigned long long bb = __ballot(any), f = __ballot(first), l = __ballot(last);
+    if (lane == 0) {
+        const long long o = (long long)e * g.vb_env + (long long)y * g.VW + w, plane = (long long)g.E * g.vb_env;
+        a.vbits[o] = bb; a.vbits[plane + o] = f; a.vbits[2 * plane + o] = l;      // any sprite bit / in the first cell / in the last cell
+    }
+}
+
+}  // namespace

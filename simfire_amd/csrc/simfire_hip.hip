@@ -99,6 +99,7 @@ extern "C" const char *sf_version(void) { return "simfire_hip 0.2 (gfx950)"; }  
 #include "sf_aux_kernels.h"
 #include "sf_run_kernels.h"
 #include "sf_run_table.h"
+#include "sf_state_kernels.h"
 
 // Launch-geometry knobs of a handle (sf_set_tuning, include/simfire_hip_lab.h: SF_TUNE_*).  Results never depend on them; the
 // defaults are the measured choices of NOTEBOOK.md 5.  The library does not read the environment for them (the measurement scripts under
@@ -2307,6 +2308,270 @@ extern "C" int sf_set_burn(sf_sim *s, int32_t env, const double *burn)
     hipLaunchKernelGGL(k_pack_burn, grd, blk, 0, s->stream, g, s->burn, env, (const double *)s->stage);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s->stream));
+    return SF_OK;
+}
+
+// ----------------------------------------------------------------------------- environment state
+// What every state call does first: end the closed loop, insist on a reset, refuse a handle a failed team launch has voided, and fold
+// the step rings into commit[] (after which tmp / flags carry nothing: the next launch starts from commit).
+static int state_entry(sf_sim *s, const char *who)
+{
+    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
+    if (!s->was_reset) return fail(SF_ESTATE, "%s: call sf_reset first", who);
+    { int rc = check_team_error(s, who); if (rc) return rc; }
+    return ensure_commit(s);
+}
+
+extern "C" int sf_copy_envs(sf_sim *s, const int32_t *src, const int32_t *dst, int32_t n, int32_t flags)
+{
+    if (!s) return fail(SF_EINVAL, "sf_copy_envs: null handle");
+    if (n < 0 || (n > 0 && (!src || !dst))) return fail(SF_EINVAL, "sf_copy_envs: bad environment lists");
+    if (flags & ~SF_COPY_TERRAIN) return fail(SF_EINVAL, "sf_copy_envs: unknown flags 0x%x", flags);
+    const Geo &g = s->g;
+    std::vector<char> role((size_t)g.E, 0);       // bit 0: a source, bit 1: a destination
+    for (int i = 0; i < n; ++i) {
+        if (src[i] < 0 || src[i] >= g.E || dst[i] < 0 || dst[i] >= g.E)
+            return fail(SF_EINVAL, "sf_copy_envs: pair %d (%d -> %d) names an environment out of range", i, src[i], dst[i]);
+        if (role[dst[i]] & 2) return fail(SF_EINVAL, "sf_copy_envs: environment %d is a destination twice", dst[i]);
+        role[dst[i]] |= 2;
+    }
+    for (int i = 0; i < n; ++i) role[src[i]] |= 1;
+    for (int e = 0; e < g.E; ++e)
+        if (role[e] == 3) return fail(SF_EINVAL, "sf_copy_envs: environment %d is both a source and a destination", e);
+    if (n == 0) return SF_OK;
+    { int rc = state_entry(s, "sf_copy_envs"); if (rc) return rc; }
+    // Every per-environment slice of the current layout and of the structures derived from it: a handle-wide "rebuild" flag would make
+    // the next step rebuild them for every environment.
+    CopyList L;
+    L.n_seg = 0;
+    auto add = [&](void *base, long long stride, long long len) { L.seg[L.n_seg++] = {static_cast<uint8_t *>(base), stride, len}; };
+    if (s->bl_cur) add(s->cells_alloc, g.cells_env, g.cells_env);
+    else {
+        add(s->status, g.plane_env, g.plane_env);
+        add(s->age_alloc, g.age_env * g.ab, g.age_env * g.ab);
+    }
+    add(s->burn, g.plane_env * 8, g.plane_env * 8);
+    if (s->settled) add(s->settled, g.plane_env * 4, g.plane_env * 4);
+    if (s->parents) add(s->parents, g.plane_env, g.plane_env);
+    add(s->commit, sizeof(EnvState), sizeof(EnvState));
+    add(s->status_block, 32, 32);
+    add(s->elapsed_dev, 8, 8);
+    if (s->sink) add(s->sink, 32, 32);
+    const long long fplane = (long long)g.TYp * g.TXp, tiles = (long long)g.TY * g.TX;
+    for (int k = 0; k < 2; ++k) add(s->tflags + (size_t)k * g.E * fplane, fplane, fplane);
+    for (int k = 0; k < 3; ++k) add(s->vbits + (size_t)k * g.E * g.vb_env, g.vb_env * 8, g.vb_env * 8);
+    add(s->seam, g.seam_env, g.seam_env);
+    add(s->tdirty, tiles, tiles);
+    add(s->thist, tiles * 16, tiles * 16);
+    add(s->win_hint, 8, 8);
+    add(s->run_cost, 4, 4);
+    const bool terrain = (flags & SF_COPY_TERRAIN) && s->rt_set.size() > 1;
+    if (terrain) {
+        const long long tab = 8 * g.plane_env * (long long)sizeof(double), lay = 7LL * g.H * g.W * (long long)sizeof(double);
+        add(s->rt, tab, tab);
+        add(s->lay_all, lay, lay);
+        if (s->rtc) add(s->rtc, tab, tab);       // (a stale copy stays marked stale below)
+    }
+    long long longest = 0;
+    for (int k = 0; k < L.n_seg; ++k) longest = std::max(longest, L.seg[k].len);
+    const unsigned gx = (unsigned)std::min<long long>(1024, std::max<long long>(1, (longest / 16 + 2047) / 2048));      // ~8 vectors per lane of the longest slice
+    for (int i0 = 0; i0 < n; i0 += kCopyPairs) {
+        const int cnt = std::min(kCopyPairs, n - i0);
+        for (int i = 0; i < cnt; ++i) { L.src[i] = src[i0 + i]; L.dst[i] = dst[i0 + i]; }
+        hipLaunchKernelGGL(k_env_copy, dim3(gx, (unsigned)cnt), dim3(256), 0, s->stream, L);
+        HIPCHK(hipGetLastError());
+    }
+    for (int i = 0; i < n; ++i) {
+        if (s->snap) s->snap_valid[dst[i]] = 0;      // (sf_get_fire_map_delta: the next query for dst hands back the whole map once)
+        if (terrain) {
+            s->rt_set[dst[i]] = s->rt_set[src[i]];
+            if (s->rtc_stale.size() == s->rt_set.size()) s->rtc_stale[dst[i]] = s->rtc_stale[src[i]];
+            if (!s->rtc || s->rtc_stale.size() != s->rt_set.size() || s->rtc_stale[dst[i]]) s->rtc_valid = false;
+        }
+    }
+    if (terrain) { s->have_rt = true; for (char c : s->rt_set) if (!c) s->have_rt = false; }
+    // (fire_rows bounds every environment's fire, dst's copy included; status_fresh: dst's row is src's current row)
+    if (!s->async) HIPCHK(hipStreamSynchronize(s->stream));
+    return SF_OK;
+}
+
+static StateHeader state_header(const sf_sim *s)
+{
+    const Geo &g = s->g;
+    StateHeader h;
+    memset(&h, 0, sizeof h);
+    h.magic = kStateMagic; h.version = kStateVersion;
+    h.bytes = state_layout(g, s->parents != nullptr).bytes;
+    h.H = g.H; h.W = g.W; h.md = g.md; h.ab = g.ab;
+    h.diag = g.diag; h.att = g.att; h.has_max_time = g.has_max_time; h.prune_after_quit = g.prune_after_quit;
+    h.has_parents = s->parents != nullptr; h.fire_rows = s->fire_rows;
+    h.max_time = g.has_max_time ? g.max_time : 0.0; h.update_rate = g.update_rate; h.pixel_scale = g.pixel_scale;
+    return h;
+}
+
+// a blob this handle can take: every value its state depends on matches (the first one that does not is named)
+static int header_check(const sf_sim *s, const StateHeader &b, int i)
+{
+    const StateHeader h = state_header(s);
+    const char *what = nullptr;
+    if (b.magic != h.magic) what = "magic number (not a state blob)";
+    else if (b.version != h.version) what = "format version";
+    else if (b.H != h.H || b.W != h.W) what = "grid size";
+    else if (b.md != h.md || b.ab != h.ab) what = "max_fire_duration";
+    else if (b.diag != h.diag) what = "diagonal spread";
+    else if (b.att != h.att) what = "line attenuation";
+    else if (b.has_max_time != h.has_max_time || b.max_time != h.max_time) what = "max_time";
+    else if (b.update_rate != h.update_rate) what = "update_rate";
+    else if (b.pixel_scale != h.pixel_scale) what = "pixel_scale threshold";
+    else if (b.prune_after_quit != h.prune_after_quit) what = "prune_after_quit";
+    else if (b.has_parents != h.has_parents) what = "spread graph";
+    else if (b.bytes != h.bytes) what = "size";
+    if (what) return fail(SF_EINVAL, "sf_load_state: blob %d does not match this handle: %s", i, what);
+    return SF_OK;
+}
+
+static int state_list(const sf_sim *s, int32_t n, const int32_t *envs, const void *buf, int32_t device_pointer, const char *who, bool distinct)
+{
+    if (n < 0 || (n > 0 && (!envs || !buf))) return fail(SF_EINVAL, "%s: bad argument", who);
+    if (device_pointer && ((uintptr_t)buf & 15))      // (the kernels read / write the f64 and u32 sections in place)
+        return fail(SF_EINVAL, "%s: a device buffer must be 16-byte aligned", who);
+    std::vector<char> seen(distinct ? (size_t)s->g.E : 0, 0);
+    for (int i = 0; i < n; ++i) {
+        if (envs[i] < 0 || envs[i] >= s->g.E) return fail(SF_EINVAL, "%s: environment %d out of range", who, envs[i]);
+        if (distinct) {
+            if (seen[envs[i]]) return fail(SF_EINVAL, "%s: environment %d is listed twice", who, envs[i]);
+            seen[envs[i]] = 1;
+        }
+    }
+    return SF_OK;
+}
+
+static StateArgs state_args(sf_sim *s)
+{
+    StateArgs a;
+    memset(&a, 0, sizeof a);
+    a.g = s->g;
+    a.status = s->status; a.age = s->age; a.cells = s->bl_cur ? s->cells : nullptr;
+    a.burn = s->burn; a.settled = s->settled; a.parents = s->parents; a.vbits = s->vbits;
+    a.commit = s->commit; a.res_block = s->status_block; a.res_sink = s->sink; a.res_elapsed = s->elapsed_dev;
+    a.lay = state_layout(s->g, s->parents != nullptr);
+    a.stride = a.lay.bytes;
+    return a;
+}
+// environments per launch, and per pass through the staging buffer of a host-pointer call (<= 64 MB of blobs unless one is larger)
+static int state_chunk(const StateArgs &a, bool device)
+{
+    if (device) return kStateEnvs;
+    return (int)std::max<long long>(1, std::min<long long>(kStateEnvs, (64LL << 20) / a.stride));
+}
+
+extern "C" int sf_state_bytes(sf_sim *s, int64_t *bytes_out)
+{
+    if (!s || !bytes_out) return fail(SF_EINVAL, "sf_state_bytes: null argument");
+    *bytes_out = state_layout(s->g, s->parents != nullptr).bytes;
+    return SF_OK;
+}
+
+extern "C" int sf_save_state(sf_sim *s, int32_t n, const int32_t *envs, void *out, int32_t device_pointer)
+{
+    if (!s) return fail(SF_EINVAL, "sf_save_state: null handle");
+    { int rc = state_list(s, n, envs, out, device_pointer, "sf_save_state", false); if (rc) return rc; }
+    if (n == 0) return SF_OK;
+    { int rc = state_entry(s, "sf_save_state"); if (rc) return rc; }
+    {   // the result rows travel with the state: make them current - as a status query would, but a snapshot is not a look at the result of a
+        // single update: the run(1)-loop heuristic of the step calls (last_was_step1 / step1_polls) stays as it was
+        const bool was_step1 = s->last_was_step1;
+        const int polls = s->step1_polls;
+        int rc = update_status_async(s, nullptr);
+        s->last_was_step1 = was_step1;
+        s->step1_polls = polls;
+        if (rc) return rc;
+    }
+    StateArgs a = state_args(s);
+    a.hdr = state_header(s);
+    const int chunk = state_chunk(a, device_pointer != 0);
+    if (!device_pointer) { int rc = ensure_stage(s, (size_t)chunk * a.stride); if (rc) return rc; }
+    for (int i0 = 0; i0 < n; i0 += chunk) {
+        const int cnt = std::min(chunk, n - i0);
+        a.n = cnt;
+        for (int i = 0; i < cnt; ++i) a.env[i] = envs[i0 + i];
+        uint8_t *dst = device_pointer ? static_cast<uint8_t *>(out) + (size_t)i0 * a.stride : static_cast<uint8_t *>(s->stage);
+        a.blob = dst;
+        hipLaunchKernelGGL(k_state_pack, dim3((unsigned)((a.g.W + 255) / 256), (unsigned)a.g.H, (unsigned)cnt), dim3(256), 0, s->stream, a);
+        HIPCHK(hipGetLastError());
+        if (!device_pointer) {
+            HIPCHK(hipMemcpyAsync(static_cast<uint8_t *>(out) + (size_t)i0 * a.stride, s->stage, (size_t)cnt * a.stride, hipMemcpyDeviceToHost, s->stream));
+            HIPCHK(hipStreamSynchronize(s->stream));
+        }
+    }
+    if (device_pointer && !s->async) HIPCHK(hipStreamSynchronize(s->stream));
+    return check_team_error(s, "sf_save_state");
+}
+
+extern "C" int sf_load_state(sf_sim *s, int32_t n, const int32_t *envs, const void *in, int32_t device_pointer)
+{
+    if (!s) return fail(SF_EINVAL, "sf_load_state: null handle");
+    { int rc = state_list(s, n, envs, in, device_pointer, "sf_load_state", true); if (rc) return rc; }
+    if (n == 0) return SF_OK;
+    HIPCHK(hipSetDevice(s->p.device));
+    const long long bytes = state_layout(s->g, s->parents != nullptr).bytes;
+    // every header is looked at before anything changes (a refused call leaves the handle as it was)
+    std::vector<StateHeader> hdr((size_t)n);
+    if (device_pointer) {
+        LOOP_QUIESCE(s);
+        HIPCHK(hipMemcpy2DAsync(hdr.data(), sizeof(StateHeader), in, (size_t)bytes, sizeof(StateHeader), (size_t)n, hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(hipStreamSynchronize(s->stream));      // (the blobs may come from a save enqueued in front)
+    } else {
+        for (int i = 0; i < n; ++i) memcpy(&hdr[i], static_cast<const uint8_t *>(in) + (size_t)i * bytes, sizeof(StateHeader));
+    }
+    int fire_rows = 0;
+    for (int i = 0; i < n; ++i) {
+        int rc = header_check(s, hdr[i], i);
+        if (rc) return rc;
+        fire_rows = std::max(fire_rows, hdr[i].fire_rows > 0 ? hdr[i].fire_rows : INT32_MAX);
+    }
+    { int rc = state_entry(s, "sf_load_state"); if (rc) return rc; }
+    const Geo &g = s->g;
+    StateArgs a = state_args(s);
+    const int chunk = state_chunk(a, device_pointer != 0);
+    if (!device_pointer) { int rc = ensure_stage(s, (size_t)chunk * a.stride); if (rc) return rc; }
+    const bool per_env_tiles = !s->bl_cur && s->tiles_valid;      // the tile maps / seams are kept: rebuild this environment's
+    const bool recount = g.ab == 1 && !s->generic && !s->tdirty_all;
+    for (int i0 = 0; i0 < n; i0 += chunk) {
+        const int cnt = std::min(chunk, n - i0);
+        a.n = cnt;
+        for (int i = 0; i < cnt; ++i) a.env[i] = envs[i0 + i];
+        if (device_pointer) a.blob = const_cast<uint8_t *>(static_cast<const uint8_t *>(in)) + (size_t)i0 * a.stride;
+        else {
+            HIPCHK(hipMemcpyAsync(s->stage, static_cast<const uint8_t *>(in) + (size_t)i0 * a.stride, (size_t)cnt * a.stride, hipMemcpyHostToDevice, s->stream));
+            a.blob = static_cast<uint8_t *>(s->stage);
+        }
+        for (int i = 0; i < cnt; ++i) {      // the cell planes start from zero: guard rows / quads and the pitch padding stay zero
+            const int e = a.env[i];
+            if (s->bl_cur) HIPCHK(hipMemsetAsync(s->cells_alloc + (size_t)e * g.cells_env, 0, (size_t)g.cells_env, s->stream));
+            else {
+                HIPCHK(hipMemsetAsync(s->status + (size_t)e * g.plane_env, 0, (size_t)g.plane_env, s->stream));
+                HIPCHK(hipMemsetAsync(s->age_alloc + (size_t)e * g.age_env * g.ab, 0, (size_t)g.age_env * g.ab, s->stream));
+            }
+            HIPCHK(hipMemsetAsync(s->win_hint + e, 0, sizeof(unsigned long long), s->stream));      // (advice about a fire that is not there)
+            if (recount) HIPCHK(hipMemsetAsync(s->tdirty + (size_t)e * g.TY * g.TX, 1, (size_t)g.TY * g.TX, s->stream));
+        }
+        hipLaunchKernelGGL(k_state_unpack, dim3((unsigned)((g.P + 255) / 256), (unsigned)g.H, (unsigned)cnt), dim3(256), 0, s->stream, a);
+        hipLaunchKernelGGL(k_state_vbits, dim3((unsigned)g.VW, (unsigned)g.H, (unsigned)cnt), dim3(64), 0, s->stream, a);
+        HIPCHK(hipGetLastError());
+        if (per_env_tiles)
+            for (int i = 0; i < cnt; ++i) {
+                int rc = rebuild_tflags(s, a.env[i], 1);
+                if (!rc) rc = rebuild_seams(s, a.env[i], 1);
+                if (rc) return rc;
+            }
+        if (!device_pointer) HIPCHK(hipStreamSynchronize(s->stream));      // (the staging buffer is reused by the next pass)
+    }
+    if (s->bl_cur) s->tiles_valid = false;
+    for (int i = 0; i < n; ++i) if (s->snap) s->snap_valid[envs[i]] = 0;
+    // fire_rows bounds every environment's fire: the saving handle's bound covers a loaded one (a blob without one makes it unknown)
+    s->fire_rows = (s->fire_rows > 0 && fire_rows != INT32_MAX) ? std::max(s->fire_rows, fire_rows) : 0;
+    if (device_pointer && !s->async) HIPCHK(hipStreamSynchronize(s->stream));
     return SF_OK;
 }
 

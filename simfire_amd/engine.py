@@ -37,6 +37,10 @@ class FireEngine:
             update_rate=float(update_rate), max_time=float(0.0 if max_time is None else max_time),
             h=float(h), S_T=float(S_T), S_e=float(S_e), p_p=float(p_p), M_f=float(M_f),
             per_env_terrain=int(bool(per_env_terrain)))
+        self.prune_after_quit = False
+        self.spread_graph = self.spread_graph_on = False
+        self.async_mode = False
+        self._blobs_in_flight = []          # device state blobs an enqueued save / load may still touch (async mode; released by sync)
         self._h = C.c_void_p()
         self._chk(self._L.sf_create(C.byref(self.params), C.byref(self._h)))
         if os.environ.get("SF_DEBUG_KNOBS") == "1":
@@ -54,6 +58,7 @@ class FireEngine:
         if getattr(self, "_h", None) is not None and self._h.value:
             self._L.sf_destroy(self._h)
             self._h = C.c_void_p()
+            self._blobs_in_flight = []
 
     def __del__(self):
         try:
@@ -223,6 +228,68 @@ class FireEngine:
             raise ValueError(f"burn shape {b.shape} != {(self.H, self.W)}")
         self._chk(self._L.sf_set_burn(self._h, int(env), _ptr(b)))
 
+    # ------------------------------------------------------------------ environment state
+    @staticmethod
+    def _env_list(envs, name):
+        a = np.ascontiguousarray(np.atleast_1d(np.asarray(envs)), dtype=np.int32)
+        if a.ndim != 1:
+            raise ValueError(f"{name} must be a list of environment numbers")
+        return a
+
+    def copy_envs(self, src, dst, terrain=False):
+        """Environment ``dst[i]`` becomes environment ``src[i]`` (one launch for all pairs; ``sf_copy_envs``).  ``terrain``: on a
+        per-environment-terrain handle ``dst`` also takes ``src``'s layers and R table."""
+        s, d = self._env_list(src, "src"), self._env_list(dst, "dst")
+        if s.shape != d.shape:
+            raise ValueError(f"src and dst differ in length ({s.shape[0]} != {d.shape[0]})")
+        self._chk(self._L.sf_copy_envs(self._h, _ptr(s), _ptr(d), int(s.shape[0]), 1 if terrain else 0))
+
+    def state_bytes(self):
+        """Bytes of one environment's state blob (``sf_state_bytes``)."""
+        v = C.c_int64(0)
+        self._chk(self._L.sf_state_bytes(self._h, C.byref(v)))
+        return v.value
+
+    def save_state(self, envs, out=None):
+        """The state of ``envs`` as blobs: numpy uint8 [n, state_bytes()], or written into ``out`` (a contiguous CUDA tensor of at
+        least n * state_bytes() bytes, 16-byte aligned: device to device, nothing crosses to the host) which is returned.  In async mode
+        the device form is only enqueued on the handle's stream: ``sync()`` before torch reads ``out``."""
+        e = self._env_list(envs, "envs")
+        nb = self.state_bytes()
+        if out is None:
+            blob = np.empty((e.shape[0], nb), dtype=np.uint8)
+            self._chk(self._L.sf_save_state(self._h, int(e.shape[0]), _ptr(e), _ptr(blob), 0))
+            return blob
+        if not getattr(out, "is_cuda", False) or not out.is_contiguous() or out.numel() * out.element_size() < e.shape[0] * nb:
+            raise ValueError(f"out must be a contiguous CUDA tensor of at least {e.shape[0] * nb} bytes")
+        self._device_blob_call(out, lambda: self._L.sf_save_state(self._h, int(e.shape[0]), _ptr(e), C.c_void_p(out.data_ptr()), 1))
+        return out
+
+    def _device_blob_call(self, t, call):
+        """A state call on a blob tensor: the handle works on its own stream, so torch's queued work (which may still write the blob, or
+        still use the memory a fresh tensor was given) is waited for first; in async mode the call only enqueues, so the tensor is kept
+        alive until ``sync`` (the caching allocator must not hand its memory out while the handle's stream may still touch it)."""
+        import torch
+        torch.cuda.synchronize(t.device)
+        self._chk(call())
+        if self.async_mode:
+            self._blobs_in_flight.append(t)
+
+    def load_state(self, envs, blob):
+        """Environment ``envs[i]`` takes the state of blob i (numpy uint8 [n, state_bytes()] or a contiguous CUDA tensor holding the
+        blobs back to back; ``sf_load_state``).  A blob from another geometry or configuration raises ValueError and changes nothing."""
+        e = self._env_list(envs, "envs")
+        nb = self.state_bytes()
+        if getattr(blob, "is_cuda", False):
+            if not blob.is_contiguous() or blob.numel() * blob.element_size() < e.shape[0] * nb:
+                raise ValueError(f"blob must be a contiguous CUDA tensor of at least {e.shape[0] * nb} bytes")
+            self._device_blob_call(blob, lambda: self._L.sf_load_state(self._h, int(e.shape[0]), _ptr(e), C.c_void_p(blob.data_ptr()), 1))
+            return
+        b = np.ascontiguousarray(blob, dtype=np.uint8)
+        if b.size < e.shape[0] * nb:
+            raise ValueError(f"blob holds {b.size} bytes, {e.shape[0]} environments need {e.shape[0] * nb}")
+        self._chk(self._L.sf_load_state(self._h, int(e.shape[0]), _ptr(e), _ptr(b), 0))
+
     def status(self):
         """(int32 [E, 8]: running, steps, counts of BurnStatus 0..5; float64 [E] elapsed_time)"""
         st = np.zeros((self.n_envs, 8), dtype=np.int32)
@@ -253,9 +320,11 @@ class FireEngine:
     def set_async(self, on=True):
         """Rollout mode: ``step`` / ``apply_mitigation`` only enqueue work; ``sync`` or any getter waits."""
         self._chk(self._L.sf_set_async(self._h, int(bool(on))))
+        self.async_mode = bool(on)
 
     def sync(self):
         self._chk(self._L.sf_sync(self._h))
+        self._blobs_in_flight.clear()
 
     def set_fused(self, mode=-1):
         """-1 auto, 0 always k_select + k_step, 1 always one fused launch per step, 2 one environment-resident
@@ -344,6 +413,7 @@ class FireEngine:
     def set_prune_after_quit(self, on=True):
         """Environments that QUIT on the runtime check keep pruning when stepped again (fire.py:631-643)."""
         self._chk(self._L.sf_set_prune_after_quit(self._h, int(bool(on))))
+        self.prune_after_quit = bool(on)
 
     def last_launch_kind(self):
         """0 k_select + k_step, 1 fused launch per step, 2 resident launch (k_run), 3 per-cell kernel, 4 the window kernel k_win in front of
@@ -359,6 +429,8 @@ class FireEngine:
     def enable_spread_graph(self, on=True):
         """Record the fire-spread graph (FireSpreadGraph, simfire/utils/graph.py) as parent masks."""
         self._chk(self._L.sf_enable_spread_graph(self._h, int(bool(on))))
+        self.spread_graph_on = bool(on)
+        self.spread_graph = self.spread_graph or bool(on)        # the parent masks exist (they stay allocated once they do; a state blob carries them)
 
     def spread_parents(self, env=0):
         """uint8 [H, W]: bit j set <=> graph edge from neighbour j (GRAPH_DX/DY) into the cell."""

@@ -9,7 +9,9 @@ is a device scatter, ``fire_map`` is copied out when ``run`` returns.
 ``BatchedFireSimulation`` adds a leading environment axis (many independent simulations that
 share terrain and wind) - the form the hardware wants.
 """
+import copy
 import ctypes as C
+import struct
 import warnings
 from datetime import datetime
 from pathlib import Path
@@ -254,6 +256,42 @@ class FireSimulation:
         self.elapsed_time = 0.0
         self.fire_status = GameStatus.RUNNING
         self.active = True
+
+    def __deepcopy__(self, memo):
+        """An independent simulation in the same state (the reference's ``copy.deepcopy(sim)``): a deep copy of the config, a
+        handle of its own built from it, the device state of this one loaded into it (``sf_save_state`` / ``sf_load_state``), and
+        copies of the host-side attributes.  The two share nothing."""
+        if getattr(self.config, "cfd_setup", None) is not None:
+            raise TypeError("FireSimulation cannot be deep-copied while its Config holds a cfd_setup (a live CFD wind solver "
+                            "handle on the GPU); build the copy from a Config without cfd_precompute")
+        cfg = copy.deepcopy(self.config, memo)
+        new = FireSimulation(cfg, device=self._device)
+        memo[id(self)] = new
+        eng, neng = self._engine, new._engine
+        if eng.spread_graph:
+            neng.enable_spread_graph(True)
+        neng.enable_spread_graph(eng.spread_graph_on)
+        if eng.prune_after_quit:
+            neng.set_prune_after_quit(True)
+        if neng.params.pixel_scale != eng.params.pixel_scale:
+            neng.set_threshold(eng.params.pixel_scale)
+        neng.load_state([0], eng.save_state([0]))
+        for name in ("assume_layers_immutable", "strict_fire_map_sync"):
+            if name in self.__dict__:
+                setattr(new, name, self.__dict__[name])
+        new._adopt_map(self._fire_map.view(np.ndarray).copy())
+        new._map_flag.dirty = self._map_flag.dirty
+        new.agent_positions = self._agent_positions.view(np.ndarray).copy()
+        new._agent_flag.dirty = self._agent_flag.dirty
+        new.agents = copy.deepcopy(self.agents, memo)
+        new.elapsed_steps = self.elapsed_steps
+        new.elapsed_time = self.elapsed_time
+        new.fire_status = self.fire_status
+        new.active = self.active
+        new._steps_done = self._steps_done
+        new.start_time = self.start_time
+        new._rendering = self._rendering
+        return new
 
     def invalidate_layers(self) -> None:
         """Forget the device copy of the layers: the next ``reset()`` rebuilds the handle (layers, slopes, R table) from the
@@ -554,6 +592,62 @@ class FireSimulation:
                                   "scope; use spread_graph_edges()")
 
 
+_STATE_HEADER = struct.Struct("<IIq4i4i4i3d40x")      # StateHeader of sf_state_kernels.h (128 bytes)
+_STATE_MAGIC, _STATE_VERSION = 0x54534653, 1
+
+
+class SimState:
+    """The state of some environments of a ``BatchedFireSimulation`` (``get_state``): the device blobs - numpy uint8 [n, bytes]
+    on the host, or a torch uint8 CUDA tensor [n, bytes] - plus what the host keeps per environment (ignition, config).  The
+    blob header is parsed here, in Python, so that a blob for another grid or configuration is refused
+    before anything reaches the device."""
+
+    def __init__(self, blob, envs, ignitions, configs=None, headers=None):
+        self.blob = blob
+        self.envs = np.asarray(envs, dtype=np.int32).reshape(-1)
+        self.ignitions = np.asarray(ignitions, dtype=np.int32).reshape(-1, 2)
+        self.configs = configs
+        if headers is None:
+            headers = np.asarray(blob)[:, :_STATE_HEADER.size]
+        self.headers = [self.parse_header(bytes(np.asarray(h, dtype=np.uint8))) for h in headers]
+
+    @property
+    def on_device(self) -> bool:
+        return getattr(self.blob, "is_cuda", False)
+
+    def __len__(self) -> int:
+        return int(self.envs.shape[0])
+
+    @staticmethod
+    def parse_header(raw: bytes) -> dict:
+        if len(raw) < _STATE_HEADER.size:
+            raise ValueError(f"state blob header: {len(raw)} bytes, need {_STATE_HEADER.size}")
+        (magic, version, nbytes, H, W, md, ab, diag, att, has_max_time, prune, has_parents, fire_rows, _r0, _r1,
+         max_time, update_rate, pixel_scale) = _STATE_HEADER.unpack_from(raw)
+        if magic != _STATE_MAGIC:
+            raise ValueError("not a simfire state blob (magic number)")
+        if version != _STATE_VERSION:
+            raise ValueError(f"state blob format version {version}; this library reads version {_STATE_VERSION}")
+        return dict(bytes=nbytes, H=H, W=W, max_fire_duration=md, ab=ab, diagonal_spread=bool(diag), attenuate_line_ros=bool(att),
+                    has_max_time=bool(has_max_time), max_time=max_time, update_rate=update_rate, pixel_scale=pixel_scale,
+                    prune_after_quit=bool(prune), spread_graph=bool(has_parents), fire_rows=fire_rows)
+
+    def check(self, engine: FireEngine) -> None:
+        """ValueError unless every blob fits ``engine`` (the device checks the same header again)."""
+        p = engine.params
+        want = dict(H=engine.H, W=engine.W, max_fire_duration=p.max_fire_duration, diagonal_spread=bool(p.diagonal_spread),
+                    attenuate_line_ros=bool(p.attenuate_line_ros), has_max_time=bool(p.has_max_time),
+                    max_time=float(p.max_time) if p.has_max_time else 0.0, update_rate=float(p.update_rate),
+                    pixel_scale=float(p.pixel_scale), prune_after_quit=engine.prune_after_quit, spread_graph=engine.spread_graph)
+        for i, h in enumerate(self.headers):
+            for k, v in want.items():
+                if h[k] != v:
+                    raise ValueError(f"state of environment {int(self.envs[i])} does not fit this simulation: {k} = {h[k]!r}, "
+                                     f"the simulation has {v!r}")
+            if h["bytes"] != engine.state_bytes():
+                raise ValueError(f"state blob of {h['bytes']} bytes, this simulation's are {engine.state_bytes()}")
+
+
 class BatchedFireSimulation:
     """``n_envs`` independent fire simulations on one GPU.
 
@@ -607,6 +701,53 @@ class BatchedFireSimulation:
         else:
             for e in envs:
                 self._engine.reset_env(int(e), int(self.ignitions[e, 0]), int(self.ignitions[e, 1]))
+
+    # ---- environment state: fork, snapshot, restore
+    def clone_envs(self, src, dst, terrain: bool = True) -> None:
+        """Environment ``dst[i]`` becomes environment ``src[i]`` in every respect - cells, sprite ages, burn amounts, update count,
+        elapsed time, running - in one device launch for all pairs (a ``src`` may repeat: one state forked into many slots).
+        ``ignitions[dst]`` follows, so that a later ``reset([dst])`` re-ignites where ``src`` started.  With per-environment configs
+        and ``terrain=True``, ``dst`` also takes ``src``'s terrain (``configs`` / ``terrains`` follow); ``terrain=False`` continues
+        ``src``'s fire on ``dst``'s own terrain.  Ends a running closed loop."""
+        s = np.atleast_1d(np.asarray(src, dtype=np.int64)).reshape(-1)
+        d = np.atleast_1d(np.asarray(dst, dtype=np.int64)).reshape(-1)
+        if s.shape != d.shape:
+            raise ValueError(f"src and dst differ in length ({s.shape[0]} != {d.shape[0]})")
+        per_env = self.configs is not None and terrain
+        self._engine.copy_envs(s, d, terrain=per_env)
+        self.ignitions[d] = self.ignitions[s]
+        if per_env:
+            for a, b in zip(s.tolist(), d.tolist()):
+                self.configs[b] = self.configs[a]
+                self.terrains[b] = self.terrains[a]
+
+    def get_state(self, envs=None, device: bool = False) -> SimState:
+        """Snapshot of ``envs`` (default: all): the device state as blobs - host numpy, or with ``device=True`` a torch CUDA tensor
+        that never crosses to the host - plus the host-side fields.  ``set_state`` restores it."""
+        e = np.arange(self.n_envs, dtype=np.int32) if envs is None else np.atleast_1d(np.asarray(envs, dtype=np.int32)).reshape(-1)
+        nb = self._engine.state_bytes()
+        headers = None
+        if device:
+            import torch
+            blob = torch.empty((e.shape[0], nb), dtype=torch.uint8, device=f"cuda:{self._engine.params.device}")
+            self._engine.save_state(e, out=blob)
+            self._engine.sync()                # (async mode: the pack is only enqueued on the handle's stream - the headers are read below)
+            headers = blob[:, :_STATE_HEADER.size].cpu().numpy()
+        else:
+            blob = self._engine.save_state(e)
+        configs = [self.configs[int(i)] for i in e] if self.configs is not None else None
+        return SimState(blob, e, self.ignitions[e].copy(), configs, headers)
+
+    def set_state(self, state: SimState, envs=None) -> None:
+        """Environment ``envs[i]`` (default: the environments the state was taken from) takes the i-th state of ``state``; its
+        ignition follows, its terrain does not (a blob holds no terrain).  A state of another grid or configuration raises
+        ValueError before anything changes."""
+        e = state.envs if envs is None else np.atleast_1d(np.asarray(envs, dtype=np.int32)).reshape(-1)
+        if e.shape[0] != len(state):
+            raise ValueError(f"{e.shape[0]} environments for a state of {len(state)}")
+        state.check(self._engine)
+        self._engine.load_state(e, state.blob)
+        self.ignitions[e] = state.ignitions
 
     def run(self, time: Union[str, int], return_maps: bool = True):
         """Steps every environment that is still RUNNING; returns (fire_maps uint8 [E, H, W] or None,
