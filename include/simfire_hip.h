@@ -207,6 +207,50 @@ int sf_get_status(sf_sim *sim, int32_t *status /* [n_envs][8] */, double *elapse
  * returned here is refreshed by this call (one device-side sweep, no host copy) and is a read-only
  * snapshot until the next one; the address does not change. */
 int sf_fire_map_device(sf_sim *sim, void **ptr, int64_t *row_pitch, int64_t *env_stride);
+/* Observation tensors for a policy: what FireSimulation.fire_map, get_attribute_data() normalised by
+ * get_attribute_bounds() and agent_positions show (simfire/sim/simulation.py:317-403, 480-499), for a list of environments, written
+ * by ONE launch into caller-owned device memory as a contiguous float32 or bfloat16 tensor out[n][C][oh][ow].  The status bytes are
+ * read from whichever plane is current (the resident launch's blocked plane or the row-major plane); nothing is converted, and no
+ * state of the handle changes (the current plane, the tile books, the reference point of sf_get_fire_map_delta, the result block). */
+#define SF_OBS_MAX_CHANNELS 32
+#define SF_OBS_MAX_AGENTS 256
+#define SF_OBS_MAX_POOL 128
+/* channel codes */
+#define SF_OBS_FIRE_MAP 0          /* FireSimulation.fire_map (simulation.py:546-553): the BurnStatus value 0..5          */
+#define SF_OBS_BURN_STATUS 1       /* + s (s = 0..5, enums.py:52-69): 1 where the cell's BurnStatus is s, else 0          */
+#define SF_OBS_W_0 7               /* get_attribute_data()["w_0"] (simulation.py:397): float32                             */
+#define SF_OBS_SIGMA 8             /* ["sigma"] (simulation.py:398): uint32                                                 */
+#define SF_OBS_DELTA 9             /* ["delta"] (simulation.py:399): float32                                                */
+#define SF_OBS_M_X 10              /* ["M_x"] (simulation.py:400): float32                                                  */
+#define SF_OBS_ELEVATION 11        /* ["elevation"] (simulation.py:401): terrain.elevations, float64                       */
+#define SF_OBS_WIND_SPEED 12       /* ["wind_speed"] (simulation.py:402): config.wind.speed as supplied, float64            */
+#define SF_OBS_WIND_DIRECTION 13   /* ["wind_direction"] (simulation.py:403): float64                                       */
+#define SF_OBS_AGENTS 14           /* agent_positions (simulation.py:480-499): the agent id at the cell, else 0           */
+typedef struct sf_obs_params {
+    int32_t n_channels;                        /* C, 1..SF_OBS_MAX_CHANNELS; a code may repeat                             */
+    int32_t channels[SF_OBS_MAX_CHANNELS];     /* SF_OBS_* codes, in output order                                           */
+    int32_t pool_mode[SF_OBS_MAX_CHANNELS];    /* per channel: 0 = mean (f64 sum in row-major order / f^2), 1 = max        */
+    int32_t normalize;                         /* 1: attribute channels become (v - min) / (max - min) in f64 with the      */
+                                               /* bounds of get_attribute_bounds() (simulation.py:334-374); no clamping     */
+    int32_t pool;                              /* f, 1..SF_OBS_MAX_POOL; the (cropped) extent must be divisible by it       */
+    int32_t crop_h, crop_w;                    /* 0, 0: the whole grid; else a window of crop_h x crop_w cells whose top-left */
+                                               /* cell is (row - crop_h / 2, column - crop_w / 2) of the environment's center */
+    int32_t dtype;                             /* 0 = float32, 1 = bfloat16 (the float32 value rounded to nearest even)      */
+    int32_t centers_device;                    /* centers is a device pointer                                               */
+    int32_t agents_k;                          /* entries per environment of agents, 0..SF_OBS_MAX_AGENTS                    */
+    int32_t agents_device;                     /* agents is a device pointer                                                */
+    double pad;                                /* final value of window cells off the grid (crop), in every channel          */
+    const int32_t *centers;                    /* int32 [n][2] = (column, row) per listed environment (crop only)           */
+    const int32_t *agents;                     /* int32 [n][agents_k][3] = (column, row, id) as update_agent_positions takes  */
+                                               /* them (simulation.py:480-499) on a fresh map: a later entry wins a shared   */
+                                               /* cell, an id moved later leaves its earlier cell; id <= 0 or off the grid =  */
+                                               /* padding.  Null: the channel is 0                                            */
+} sf_obs_params;
+/* Environment envs[i] (a host array; repeats allowed) lands in out[i].  oh = extent_h / pool, ow = extent_w / pool.  Anything
+ * invalid is SF_EINVAL before a launch; attribute channels before layers are SF_ESTATE.  In async mode the call only enqueues
+ * (the tensor is complete when the handle's stream has got there); the caller orders its own work on device_out before the call. */
+int sf_observe(sf_sim *sim, const sf_obs_params *params, int32_t n, const int32_t *envs, void *device_out);
+
 /* Device buffer int32 [n_envs][8] filled by sf_update_status_device (same content as
  * sf_get_status) - the block that is all-gathered over RCCL by the multi-GPU host code. */
 int sf_status_device(sf_sim *sim, void **ptr);

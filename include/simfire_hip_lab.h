@@ -117,6 +117,9 @@ int sf_get_tuning(sf_sim *sim, int32_t knob, int32_t *value_out);
  * environments than CUs while their fires are young: two workgroups to a CU; NOTEBOOK.md 5.12), -1 = none yet.  (4 - 6 once were the numbers of
  * structures retired in round 5.) */
 int sf_last_step_launch(sf_sim *sim, int32_t *kind_out);
+/* Which cell plane is current: 1 = the blocked plane of the resident launch, 0 = the row-major planes (what sf_observe reads from; tests
+ * assert with it that the layout they are about was the one read).  No reference counterpart. */
+int sf_cell_layout(sf_sim *sim, int32_t *blocked_out);
 /* 1 = visit every tile every step instead of consulting the tile activity map (cross-check) */
 int sf_set_dense(sf_sim *sim, int32_t dense);
 /* sf_cfd_step that also reports the GPU time of its launches (HIP events on the handle's stream). */

@@ -32,6 +32,17 @@ class SfCfdParams(C.Structure):
                 ("timestep_dt", C.c_double), ("viscosity", C.c_double), ("speed", C.c_double)]
 
 
+OBS_MAX_CHANNELS = 32
+
+
+class SfObsParams(C.Structure):
+    """``sf_obs_params`` (include/simfire_hip.h)."""
+    _fields_ = [("n_channels", C.c_int32), ("channels", C.c_int32 * OBS_MAX_CHANNELS), ("pool_mode", C.c_int32 * OBS_MAX_CHANNELS),
+                ("normalize", C.c_int32), ("pool", C.c_int32), ("crop_h", C.c_int32), ("crop_w", C.c_int32), ("dtype", C.c_int32),
+                ("centers_device", C.c_int32), ("agents_k", C.c_int32), ("agents_device", C.c_int32), ("pad", C.c_double),
+                ("centers", C.c_void_p), ("agents", C.c_void_p)]
+
+
 # name -> argtypes; every function returns int except the two string getters
 _VP, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
 SIGNATURES = {
@@ -69,6 +80,8 @@ SIGNATURES = {
     "sf_load_state": [_VP, _I32, _VP, _VP, _I32],
     "sf_get_status": [_VP, _VP, _VP],
     "sf_fire_map_device": [_VP, C.POINTER(_VP), C.POINTER(_I64), C.POINTER(_I64)],
+    "sf_observe": [_VP, C.POINTER(SfObsParams), _I32, _VP, _VP],
+    "sf_cell_layout": [_VP, C.POINTER(_I32)],
     "sf_status_device": [_VP, C.POINTER(_VP)],
     "sf_update_status_device": [_VP],
     "sf_copy_status_to": [_VP, _VP],

@@ -100,6 +100,7 @@ extern "C" const char *sf_version(void) { return "simfire_hip 0.2 (gfx950)"; }  
 #include "sf_run_kernels.h"
 #include "sf_run_table.h"
 #include "sf_state_kernels.h"
+#include "sf_obs_kernels.h"
 
 // Launch-geometry knobs of a handle (sf_set_tuning, include/simfire_hip_lab.h: SF_TUNE_*).  Results never depend on them; the
 // defaults are the measured choices of NOTEBOOK.md 5.  The library does not read the environment for them (the measurement scripts under
@@ -224,6 +225,11 @@ struct sf_sim {
     int32_t *mit_stage = nullptr;      // sf_step_mitigated: device copy of a host point block / expanded rows of one step
     size_t mit_stage_bytes = 0;
     bool async = false;                // sf_set_async: calls that return no data do not synchronise
+    // sf_observe: its per-call block (ObsHead, environment list, host centers / agents) in device memory and the pinned buffer it is
+    // copied from; obs_ev marks the copy's completion (the next call waits for it before it writes the pinned buffer again)
+    uint8_t *obs_dev = nullptr, *obs_pinned = nullptr;
+    size_t obs_cap = 0;
+    hipEvent_t obs_ev = nullptr;
     bool have_rt = false, was_reset = false, counters_on = false;
     int seq = 0;                       // index (mod 6) of the next step launch
     Tuning tune;                       // sf_set_tuning
@@ -407,7 +413,9 @@ extern "C" int sf_destroy(sf_sim *s)
                     s->status_block, s->elapsed_dev, s->stage, s->parents};
     if (s->status_pinned) (void)hipHostFree(s->status_pinned);
     if (s->delta_pinned) (void)hipHostFree(s->delta_pinned);
-    for (void *dp : {(void *)s->snap, (void *)s->delta_dev}) if (dp) (void)hipFree(dp);
+    for (void *dp : {(void *)s->snap, (void *)s->delta_dev, (void *)s->obs_dev}) if (dp) (void)hipFree(dp);
+    if (s->obs_pinned) (void)hipHostFree(s->obs_pinned);
+    if (s->obs_ev) (void)hipEventDestroy(s->obs_ev);
     for (int i = 0; i < sf_sim::kPtsRing; ++i) {
         if (s->pts_pinned[i]) (void)hipHostFree(s->pts_pinned[i]);
         if (s->ev_pts[i]) (void)hipEventDestroy(s->ev_pts[i]);
@@ -2796,6 +2804,124 @@ extern "C" int sf_fire_map_device(sf_sim *s, void **ptr, int64_t *row_pitch, int
     } else { s->tdirty_all = true; s->status_fresh = false; }      // the caller holds a writable alias of the status plane: recount everything at the next query
     HIPCHK(hipStreamSynchronize(s->stream));
     *ptr = s->status; *row_pitch = s->g.P; *env_stride = s->g.plane_env;
+    return SF_OK;
+}
+
+// ----------------------------------------------------------------------------- observations
+extern "C" int sf_cell_layout(sf_sim *s, int32_t *blocked)
+{
+    if (!s || !blocked) return fail(SF_EINVAL, "sf_cell_layout: null argument");
+    *blocked = s->bl_cur ? 1 : 0;
+    return SF_OK;
+}
+
+// Output cells per k_observe workgroup (TX x TY) for pool factor f and output width ow, and the LDS row stride of its staged region:
+// up to 256 outputs, fewer as f grows, so that the region (TY * f rows of whole vectors) fits kObsLds.
+struct ObsTile { int TX, TY, stride; };
+static ObsTile obs_tile(int f, int ow)
+{
+    int outs = kObsThreads;
+    while (outs > 1 && (long long)outs * f * f > 16384) outs >>= 1;
+    for (;;) {
+        int tx = 1;
+        while (tx * 2 <= outs && tx * 2 <= 64 && tx < ow) tx *= 2;
+        ObsTile t{tx, outs / tx, (tx * f + 30) / 16 * 16};
+        if ((long long)t.TY * f * t.stride <= kObsLds || outs == 1) return t;
+        outs >>= 1;
+    }
+}
+
+extern "C" int sf_observe(sf_sim *s, const sf_obs_params *p, int32_t n, const int32_t *envs, void *device_out)
+{
+    if (!s || !p) return fail(SF_EINVAL, "sf_observe: null argument");
+    const Geo &g = s->g;
+    if (n < 0 || (n > 0 && (!envs || !device_out))) return fail(SF_EINVAL, "sf_observe: bad environment list or output");
+    const int C = p->n_channels;
+    if (C < 1 || C > SF_OBS_MAX_CHANNELS) return fail(SF_EINVAL, "sf_observe: %d channels (1..%d)", C, SF_OBS_MAX_CHANNELS);
+    bool attr = false, agents = false;
+    for (int c = 0; c < C; ++c) {
+        if (p->channels[c] < SF_OBS_FIRE_MAP || p->channels[c] > SF_OBS_AGENTS)
+            return fail(SF_EINVAL, "sf_observe: channel %d has the unknown code %d", c, p->channels[c]);
+        if (p->pool_mode[c] != 0 && p->pool_mode[c] != 1) return fail(SF_EINVAL, "sf_observe: channel %d has the pool mode %d (0 mean, 1 max)", c, p->pool_mode[c]);
+        attr |= p->channels[c] >= SF_OBS_W_0 && p->channels[c] <= SF_OBS_WIND_DIRECTION;
+        agents |= p->channels[c] == SF_OBS_AGENTS;
+    }
+    const int f = p->pool;
+    if (f < 1 || f > SF_OBS_MAX_POOL) return fail(SF_EINVAL, "sf_observe: pool %d (1..%d)", f, SF_OBS_MAX_POOL);
+    const bool crop = p->crop_h != 0 || p->crop_w != 0;
+    if (crop && (p->crop_h < 1 || p->crop_w < 1 || p->crop_h > 65535 || p->crop_w > 65535))
+        return fail(SF_EINVAL, "sf_observe: crop %d x %d", p->crop_h, p->crop_w);
+    if (crop && !p->centers) return fail(SF_EINVAL, "sf_observe: a crop needs centers");
+    const int eh = crop ? p->crop_h : g.H, ew = crop ? p->crop_w : g.W;
+    if (eh % f || ew % f) return fail(SF_EINVAL, "sf_observe: the extent %d x %d is not divisible by pool %d", eh, ew, f);
+    if (p->dtype != 0 && p->dtype != 1) return fail(SF_EINVAL, "sf_observe: dtype %d (0 float32, 1 bfloat16)", p->dtype);
+    const int k = agents && p->agents ? p->agents_k : 0;
+    if (agents && p->agents && (p->agents_k < 0 || p->agents_k > SF_OBS_MAX_AGENTS))
+        return fail(SF_EINVAL, "sf_observe: %d agents per environment (0..%d)", p->agents_k, SF_OBS_MAX_AGENTS);
+    if ((uintptr_t)device_out & (p->dtype ? 1 : 3)) return fail(SF_EINVAL, "sf_observe: the output is not aligned to its element");
+    for (int i = 0; i < n; ++i)
+        if (envs[i] < 0 || envs[i] >= g.E) return fail(SF_EINVAL, "sf_observe: environment %d out of range", envs[i]);
+    if (n == 0) return SF_OK;
+    if (attr && !s->have_rt) return fail(SF_ESTATE, "sf_observe: attribute channels need the layers (sf_set_layers)");
+    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
+    { int rc = check_team_error(s, "sf_observe"); if (rc) return rc; }
+    const int oh = eh / f, ow = ew / f;
+    const ObsTile tl = obs_tile(f, ow);
+    const long long tiles_x = (ow + tl.TX - 1) / tl.TX, tiles = tiles_x * ((oh + tl.TY - 1) / tl.TY);
+    if ((long long)n * tiles > 0x7FFFFFFFLL) return fail(SF_ENOTSUP, "sf_observe: %d environments x %lld tiles exceed the launch grid", n, tiles);
+
+    // the per-call block: ObsHead | envs [n] | centers [n][2] (host) | agents [n][k][3] (host)
+    const size_t o_envs = (sizeof(ObsHead) + 15) / 16 * 16, o_cen = o_envs + ((size_t)n * 4 + 15) / 16 * 16;
+    const bool cen_host = crop && !p->centers_device, ag_host = k > 0 && !p->agents_device;
+    const size_t o_ag = o_cen + (cen_host ? ((size_t)n * 8 + 15) / 16 * 16 : 0);
+    const size_t bytes = o_ag + (ag_host ? (size_t)n * k * 12 : 0);
+    if (!s->obs_ev) HIPCHK(hipEventCreateWithFlags(&s->obs_ev, hipEventDisableTiming));
+    HIPCHK(hipEventSynchronize(s->obs_ev));            // the last call's copy has left the pinned buffer (and its kernel used obs_dev)
+    if (bytes > s->obs_cap) {
+        HIPCHK(hipStreamSynchronize(s->stream));
+        if (s->obs_dev) { HIPCHK(hipFree(s->obs_dev)); s->obs_dev = nullptr; }
+        if (s->obs_pinned) { HIPCHK(hipHostFree(s->obs_pinned)); s->obs_pinned = nullptr; }
+        s->obs_cap = 0;
+        const size_t cap = std::max<size_t>(bytes * 2, 4096);
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&s->obs_dev), cap));
+        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&s->obs_pinned), cap, hipHostMallocDefault));
+        s->obs_cap = cap;
+    }
+    ObsHead h;
+    memset(&h, 0, sizeof h);
+    for (int c = 0; c < C; ++c) { h.code[c] = p->channels[c]; h.mode[c] = p->pool_mode[c]; }
+    // get_attribute_bounds (simulation.py:334-374; FuelConstants / ElevationConstants / WindConstants, enums.py:118-173) in the order of
+    // supported_attributes (simulation.py:317-332)
+    const double lo[7] = {0.0, 1.0, 0.2, 0.12, -282.0, 0.0, 0.0}, hi[7] = {1.0, 3500.0, 6.0, 1.0, 11000.0, 250.0, 360.0};
+    for (int a = 0; a < 7; ++a) { h.lo[a] = lo[a]; h.span[a] = hi[a] - lo[a]; }
+    memcpy(s->obs_pinned, &h, sizeof h);
+    memcpy(s->obs_pinned + o_envs, envs, (size_t)n * 4);
+    if (cen_host) memcpy(s->obs_pinned + o_cen, p->centers, (size_t)n * 8);
+    if (ag_host) memcpy(s->obs_pinned + o_ag, p->agents, (size_t)n * k * 12);
+    HIPCHK(hipMemcpyAsync(s->obs_dev, s->obs_pinned, bytes, hipMemcpyHostToDevice, s->stream));
+    HIPCHK(hipEventRecord(s->obs_ev, s->stream));
+
+    ObsArgs a;
+    memset(&a, 0, sizeof a);
+    a.g = g;
+    a.status = s->status;
+    a.cells = s->bl_cur ? s->cells : nullptr;
+    a.lay = s->lay_all;
+    a.lay_tab = s->rt_set.size() > 1 ? 7LL * g.H * g.W : 0;
+    a.head = reinterpret_cast<const ObsHead *>(s->obs_dev);
+    a.envs = reinterpret_cast<const int32_t *>(s->obs_dev + o_envs);
+    a.centers = !crop ? nullptr : (cen_host ? reinterpret_cast<const int32_t *>(s->obs_dev + o_cen) : p->centers);
+    a.agents = k == 0 ? nullptr : (ag_host ? reinterpret_cast<const int32_t *>(s->obs_dev + o_ag) : p->agents);
+    a.out = device_out;
+    a.n = n; a.C = C; a.f = f; a.ch = eh; a.cw = ew; a.oh = oh; a.ow = ow; a.k = k;
+    a.TX = tl.TX; a.TY = tl.TY; a.tiles_x = (int)tiles_x; a.stride = tl.stride;
+    a.norm = p->normalize != 0; a.bf16 = p->dtype == 1; a.pad = p->pad;
+    hipLaunchKernelGGL(k_observe, dim3((unsigned)((long long)n * tiles)), dim3(kObsThreads), 0, s->stream, a);
+    HIPCHK(hipGetLastError());
+    if (!s->async) {
+        HIPCHK(hipStreamSynchronize(s->stream));
+        return check_team_error(s, "sf_observe");
+    }
     return SF_OK;
 }
 

@@ -497,6 +497,37 @@ class FireEngine:
                 "w_0", "sigma", "delta", "M_x", "elevation", "wind_speed", "wind_direction")], 1))
         return out
 
+    def observe(self, channels, envs=None, normalize=True, pool=1, pool_mode="mean", crop=None, centers=None, agents=None, pad=0.0,
+                dtype=None, out=None):
+        """The observation of ``envs`` (default: all, in order; repeats allowed) as a torch tensor [n, C, oh, ow] on this GPU, written by
+        one launch (``sf_observe``) from whichever cell plane is current - nothing is converted, no state of the
+        handle changes.  ``channels``: names of ``observe.CHANNELS``.  ``crop=(h, w)`` around ``centers`` [n, 2] = (column, row),
+        ``pool`` f (mean or max, per channel with a dict), ``agents`` [n, k, 3] = (column, row, id); host arrays or CUDA int32 tensors.
+        ``out``: a tensor to fill instead of a new one.  Torch's queued work is waited for before the handle's stream writes ``out``; in
+        async mode the call only enqueues and the tensors are kept alive until ``sync()``."""
+        import torch
+        from .observe import ObsSpec
+        spec = ObsSpec(channels, self.n_envs, self.H, self.W, envs=envs, normalize=normalize, pool=pool, pool_mode=pool_mode, crop=crop,
+                       centers=centers, agents=agents, pad=pad, dtype=dtype, out=out)
+        dev = torch.device(f"cuda:{self.params.device}")
+        for t in spec.device_tensors() + ([out] if out is not None else []):
+            if t.device != dev:
+                raise ValueError(f"observe: a tensor on {t.device}, the simulation runs on {dev}")
+        if out is None:
+            out = torch.empty(spec.shape, dtype=spec.dtype, device=dev)
+        p = spec.params()
+        torch.cuda.synchronize(dev)
+        self._chk(self._L.sf_observe(self._h, C.byref(p), spec.n, spec.envs_ptr(), C.c_void_p(out.data_ptr())))
+        if self.async_mode:
+            self._blobs_in_flight.extend([out] + spec.device_tensors())
+        return out
+
+    def cell_layout(self):
+        """1 = the resident launch's blocked cell plane is current, 0 = the row-major planes (what ``observe`` reads)."""
+        v = C.c_int32()
+        self._chk(self._L.sf_cell_layout(self._h, C.byref(v)))
+        return int(v.value)
+
     # ---------------------------------------------------------------- per-update history
     def enable_history(self, capacity):
         """Record the fire map after every executed update (what ``_save_data`` appends to

@@ -522,6 +522,20 @@ class FireSimulation:
                 "elevation": self.terrain.elevations, "wind_speed": self.config.wind.speed,
                 "wind_direction": self.config.wind.direction}
 
+    def observe(self, channels, envs=None, normalize=True, pool=1, pool_mode="mean", crop=None, centers=None, agents=None, pad=0.0,
+                dtype=None, out=None):
+        """``BatchedFireSimulation.observe`` for this simulation (``envs`` defaults to [0]).  Host edits of ``fire_map`` are pushed to the
+        device first, as ``run`` does; ``agent_positions`` comes from this simulation's own array unless ``agents`` is given (one entry
+        per non-zero cell, repeated for every listed environment)."""
+        self._sync_to_device()
+        if agents is None and not isinstance(channels, str) and "agent_positions" in list(channels):
+            from .observe import agents_from_map
+            one = agents_from_map(self._agent_positions.view(np.ndarray))
+            n = 1 if envs is None else len(np.atleast_1d(np.asarray(envs)))
+            agents = np.ascontiguousarray(np.repeat(one, n, axis=0))
+        return self._engine.observe(channels, envs=envs, normalize=normalize, pool=pool, pool_mode=pool_mode, crop=crop, centers=centers,
+                                    agents=agents, pad=pad, dtype=dtype, out=out)
+
     # -------------------------------------------------------------------- seeds / layers
     def get_seeds(self) -> Dict[str, Optional[int]]:
         """simulation.py:574-597: only the seeds that exist for the configured generators."""
@@ -831,6 +845,17 @@ class BatchedFireSimulation:
         last call.  A harness that keeps the tensor across ``run()`` calls must call this (or ``refresh_fire_maps_device``)
         again before it reads."""
         return self._engine.fire_maps_torch()
+
+    def observe(self, channels, envs=None, normalize=True, pool=1, pool_mode="mean", crop=None, centers=None, agents=None, pad=0.0,
+                dtype=None, out=None):
+        """The policy's observation of ``envs`` (default: all) as one torch tensor [n, C, oh, ow] (float32, or ``dtype=torch.bfloat16``)
+        on this GPU: ``fire_map``, ``burn_status:<BurnStatus name>`` indicators, the attribute planes of ``get_attribute_data()``
+        (normalised by ``get_attribute_bounds()`` with ``normalize``) and ``agent_positions`` from ``agents`` [n, k, 3] = (column, row, id),
+        optionally cropped to ``crop=(h, w)`` around ``centers`` [n, 2] = (column, row) (cells off the grid are ``pad``) and pooled by
+        ``pool`` (``pool_mode`` "mean" / "max", or a dict per channel).  One launch, no host copy, no change to the simulation
+        (DESIGN.md section 12).  ``out``: fill this tensor instead."""
+        return self._engine.observe(channels, envs=envs, normalize=normalize, pool=pool, pool_mode=pool_mode, crop=crop, centers=centers,
+                                    agents=agents, pad=pad, dtype=dtype, out=out)
 
     def refresh_fire_maps_device(self) -> None:
         """Bring the plane behind ``fire_maps_device()``'s tensor up to date (the same tensor then shows the current maps)."""
