@@ -120,6 +120,43 @@ int sf_set_layers_fbfm(sf_sim *sim, int32_t env, const int32_t *codes, int32_t n
 int sf_get_attribute_data(sf_sim *sim, int32_t env, float *w_0, uint32_t *sigma, float *delta, float *M_x,
                           double *elevation, double *wind_speed, double *wind_direction, int32_t device_pointers);
 
+/* Seeded worlds drawn on the device: what FireSimulation.set_seeds + reset rebuild
+ * (simfire/sim/simulation.py:713-759, 202-214) for a list of environments of a per_env_terrain handle, in a bounded
+ * number of launches and one wait - nothing but the descriptors crosses PCIe.  The generators are pure functions of
+ * (seed, cell), evaluated in float64 in the order of the host oracles in simfire_amd/workloads.py:
+ *   elevation  SF_GEN_SIMPLEX: perlin topography, elevation_functions.py:75-122 (workloads.perlin_elevation: the
+ *              fractal value rounded to float32, then ((z + 1) / 2) * (hi - lo) + lo in float64); SF_GEN_CONSTANT: lo
+ *              everywhere (flat, elevation_functions.py:9-30)
+ *   fuel       SF_GEN_CONSTANT: w_0, delta, M_x, sigma everywhere - chaparral(seed), terrain.py:29-114, whose four
+ *              legacy-MT19937 draws the host makes (config.chaparral_fuel)
+ *   wind_speed / wind_direction  SF_GEN_SIMPLEX: perlin wind, perlin_wind.py:69-98 with config.py:892-944's float32
+ *              map (workloads.simplex_field, widened to float64; speed in ft/min); SF_GEN_CONSTANT: lo everywhere
+ * The simplex generator is this build's own, not the `noise` wheel's: same parameters, other values.  Seeds s and
+ * s + 256 give the same field.  SF_GEN_NONE leaves a plane as it is.  Then the slopes and R tables of exactly these
+ * environments are rebuilt, bit-identical to what sf_set_layers_env builds from the same planes (sf_get_slopes keeps
+ * reporting the last sf_set_layers* call).  Every descriptor is checked before any device work: a shared-terrain
+ * handle is SF_ESTATE; environments out of range or repeated, scale <= 0, octaves outside 1..16, lo >= hi (simplex)
+ * or an unknown kind are SF_EINVAL.  Ends a running closed loop first.  n == 0 does nothing. */
+#define SF_GEN_NONE 0
+#define SF_GEN_CONSTANT 1
+#define SF_GEN_SIMPLEX 2
+typedef struct sf_noise {
+    int32_t kind;                 /* SF_GEN_*                                                                     */
+    int32_t octaves;              /* simplex: 1..16                                                               */
+    int64_t seed;                 /* simplex: offsets the permutation indices ((i + seed) & 255, 64-bit)          */
+    double scale;                 /* simplex: cells per noise unit (> 0; perlin topography: 1)                    */
+    double persistence, lacunarity;
+    double lo, hi;                /* simplex: range_min < range_max; constant: the value is lo                    */
+} sf_noise;
+typedef struct sf_layer_gen {
+    sf_noise elevation;
+    int32_t fuel;                 /* SF_GEN_NONE or SF_GEN_CONSTANT                                               */
+    int32_t reserved;             /* 0                                                                            */
+    double fuel_values[4];        /* w_0, delta, M_x, sigma                                                       */
+    sf_noise wind_speed, wind_direction;
+} sf_layer_gen;
+int sf_generate_layers(sf_sim *sim, int32_t n, const int32_t *envs, const sf_layer_gen *gen);
+
 /* History of FireSimulation._save_data (simulation.py:548-549, 887-959): the fire map after every
  * executed update, a ring int8 [n_envs][capacity][H][W] in HBM: update number u (0-based, counted from
  * the last reset of that environment = elapsed_steps before it) lands in slot u mod capacity.

@@ -43,6 +43,21 @@ class SfObsParams(C.Structure):
                 ("centers", C.c_void_p), ("agents", C.c_void_p)]
 
 
+SF_GEN_NONE, SF_GEN_CONSTANT, SF_GEN_SIMPLEX = 0, 1, 2
+
+
+class SfNoise(C.Structure):
+    """``sf_noise`` (include/simfire_hip.h)."""
+    _fields_ = [("kind", C.c_int32), ("octaves", C.c_int32), ("seed", C.c_int64), ("scale", C.c_double), ("persistence", C.c_double),
+                ("lacunarity", C.c_double), ("lo", C.c_double), ("hi", C.c_double)]
+
+
+class SfLayerGen(C.Structure):
+    """``sf_layer_gen`` (include/simfire_hip.h): one environment's planes for ``sf_generate_layers``."""
+    _fields_ = [("elevation", SfNoise), ("fuel", C.c_int32), ("reserved", C.c_int32), ("fuel_values", C.c_double * 4),
+                ("wind_speed", SfNoise), ("wind_direction", SfNoise)]
+
+
 # name -> argtypes; every function returns int except the two string getters
 _VP, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
 SIGNATURES = {
@@ -57,6 +72,7 @@ SIGNATURES = {
     "sf_get_rtable_env": [_VP, _I32, _VP],
     "sf_set_layers_fbfm": [_VP, _I32, _VP, _I32, _VP, _VP, _VP, _VP, _VP],
     "sf_get_attribute_data": [_VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32],
+    "sf_generate_layers": [_VP, _I32, _VP, _VP],
     "sf_enable_history": [_VP, _I32],
     "sf_get_history": [_VP, _I32, _I32, _I32, _VP],
     "sf_history_device": [_VP, _VP, _VP],

@@ -150,7 +150,11 @@ def gaussian_elevation(H, W, amplitude, mu_x, mu_y, sigma_x, sigma_y):
 
 class Config:
     def __init__(self, path: Optional[Union[str, Path]] = None, config_dict: Optional[Dict[str, Any]] = None,
-                 cfd_precompute: bool = False) -> None:
+                 cfd_precompute: bool = False, simplex_topography: bool = False) -> None:
+        """``simplex_topography=True``: ``perlin`` topography is built with this build's own simplex generator
+        (``workloads.perlin_elevation``) instead of raising ``ConfigError``.  That is an opt-in: it is NOT the field of the ``noise``
+        wheel the reference calls (simfire/world/elevation_functions.py:113) - same parameters and range, other values (DESIGN.md
+        section 9)."""
         if path is not None and isinstance(path, str):
             path = Path(path)
         self.path = path
@@ -161,6 +165,7 @@ class Config:
         else:
             raise ValueError("Either a path or a config dictionary must be specified.")
         self._cfd_precompute = bool(cfd_precompute)
+        self._simplex_topography = bool(simplex_topography)
         self._arrays: Dict[str, np.ndarray] = {}
         self.fuel_codes: Optional[np.ndarray] = None
         self._build()
@@ -177,6 +182,7 @@ class Config:
         self = cls.__new__(cls)
         self.path = None
         self._cfd_precompute = False
+        self._simplex_topography = False
         self.yaml_data = copy.deepcopy(config_dict)
         fuel = np.asarray(fuel)
         self._arrays = {"fuel": fuel, "elevation": np.asarray(elevation, dtype=np.float64)}
@@ -240,10 +246,19 @@ class Config:
                 topo_layer = ArrayLayer(np.zeros((H, W), dtype=np.int64), name)      # elevation_functions.py:9-30
             elif name == "gaussian":
                 topo_layer = ArrayLayer(gaussian_elevation(H, W, **kwargs), name)
+            elif name == "perlin" and getattr(self, "_simplex_topography", False):
+                from .workloads import perlin_elevation
+                try:
+                    elev = perlin_elevation(H, W, int(kwargs["octaves"]), kwargs["persistence"], kwargs["lacunarity"], int(kwargs["seed"]),
+                                            kwargs["range_min"], kwargs["range_max"])
+                except KeyError as err:
+                    raise ConfigError(f"terrain.topography.functional.perlin is missing the parameter {err}") from None
+                topo_layer = ArrayLayer(elev, name)
             elif name == "perlin":
                 raise ConfigError("perlin topography needs the third-party `noise` package "
                                   "(simfire/world/elevation_functions.py:113); pass the elevation array "
-                                  "through Config.from_arrays instead")
+                                  "through Config.from_arrays instead, or opt in to this build's own simplex "
+                                  "generator with Config(..., simplex_topography=True)")
             else:
                 raise ConfigError(f"The specified topography function ({name}) is not valid.")
             topo_fn = FunctionalConfig(name, kwargs)

@@ -11,11 +11,9 @@ namespace {
 // ------------------------------------------------------------------ layers -> R table
 // np.gradient(elevations, pixel_scale) (fire.py:446): centred 2nd-order differences inside,
 // one-sided 1st-order at the borders; slope_mag / slope_dir (fire.py:447-448) in float64.
-#ifndef SF_RUN_UNIT
-__global__ void k_slopes(int H, int W, const double *el, double ps, double *mag, double *dir)
+// (one function for k_slopes and the batched R-table kernel of sf_generate_layers, k_gen_rtable: the same slopes bit for bit)
+__device__ inline void slope_at(int H, int W, const double *el, double ps, int x, int y, double &mag, double &dir)
 {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x >= W) return;
     const long long i = (long long)y * W + x;
     double gy, gx;
     if (H == 1) gy = 0.0;
@@ -26,8 +24,17 @@ __global__ void k_slopes(int H, int W, const double *el, double ps, double *mag,
     else if (x == 0) gx = (el[i + 1] - el[i]) / ps;
     else if (x == W - 1) gx = (el[i] - el[i - 1]) / ps;
     else gx = (el[i + 1] - el[i - 1]) / (2.0 * ps);
-    mag[i] = sqrt(gx * gx + gy * gy);
-    dir[i] = atan2(gy, gx + 0.000001);
+    mag = sqrt(gx * gx + gy * gy);
+    dir = atan2(gy, gx + 0.000001);
+}
+
+#ifndef SF_RUN_UNIT
+__global__ void k_slopes(int H, int W, const double *el, double ps, double *mag, double *dir)
+{
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= W) return;
+    const long long i = (long long)y * W + x;
+    slope_at(H, W, el, ps, x, y, mag[i], dir[i]);
 }
 #endif
 

@@ -101,6 +101,7 @@ extern "C" const char *sf_version(void) { return "simfire_hip 0.2 (gfx950)"; }  
 #include "sf_run_table.h"
 #include "sf_state_kernels.h"
 #include "sf_obs_kernels.h"
+#include "sf_gen_kernels.h"
 
 // Launch-geometry knobs of a handle (sf_set_tuning, include/simfire_hip_lab.h: SF_TUNE_*).  Results never depend on them; the
 // defaults are the measured choices of NOTEBOOK.md 5.  The library does not read the environment for them (the measurement scripts under
@@ -230,6 +231,8 @@ struct sf_sim {
     uint8_t *obs_dev = nullptr, *obs_pinned = nullptr;
     size_t obs_cap = 0;
     hipEvent_t obs_ev = nullptr;
+    uint8_t *gen_dev = nullptr;        // sf_generate_layers: its descriptors + environment list in device memory
+    size_t gen_cap = 0;
     bool have_rt = false, was_reset = false, counters_on = false;
     int seq = 0;                       // index (mod 6) of the next step launch
     Tuning tune;                       // sf_set_tuning
@@ -413,7 +416,7 @@ extern "C" int sf_destroy(sf_sim *s)
                     s->status_block, s->elapsed_dev, s->stage, s->parents};
     if (s->status_pinned) (void)hipHostFree(s->status_pinned);
     if (s->delta_pinned) (void)hipHostFree(s->delta_pinned);
-    for (void *dp : {(void *)s->snap, (void *)s->delta_dev, (void *)s->obs_dev}) if (dp) (void)hipFree(dp);
+    for (void *dp : {(void *)s->snap, (void *)s->delta_dev, (void *)s->obs_dev, (void *)s->gen_dev}) if (dp) (void)hipFree(dp);
     if (s->obs_pinned) (void)hipHostFree(s->obs_pinned);
     if (s->obs_ev) (void)hipEventDestroy(s->obs_ev);
     for (int i = 0; i < sf_sim::kPtsRing; ++i) {
@@ -655,14 +658,28 @@ static int table_range(sf_sim *s, int env, const char *who, int *lo, int *hi)
     *lo = env; *hi = env + 1;
     return SF_OK;
 }
-static void mark_tables(sf_sim *s, int lo, int hi)
+// tables tabs[0 .. n) were replaced: only their cell-major copies are rebuilt (ensure_rtc)
+static void mark_tables(sf_sim *s, const int32_t *tabs, int n)
 {
-    for (int i = lo; i < hi; ++i) s->rt_set[i] = 1;
     if (s->rtc_stale.size() != s->rt_set.size()) s->rtc_stale.assign(s->rt_set.size(), 1);
-    for (int i = lo; i < hi; ++i) s->rtc_stale[i] = 1;      // (only these tables' cell-major copies are rebuilt: ensure_rtc)
+    for (int k = 0; k < n; ++k) s->rt_set[tabs[k]] = s->rtc_stale[tabs[k]] = 1;
     s->rtc_valid = false;
     s->have_rt = true;
     for (char c : s->rt_set) if (!c) s->have_rt = false;
+}
+static void mark_tables(sf_sim *s, int lo, int hi)
+{
+    std::vector<int32_t> tabs;
+    for (int i = lo; i < hi; ++i) tabs.push_back(i);
+    mark_tables(s, tabs.data(), hi - lo);
+}
+
+// theta = arctan2(src_y - dst_y, dst_x - src_x) of the 8 travel directions, float32 (rothermel.py:102)
+static Thetas rt_thetas()
+{
+    Thetas th;
+    for (int k = 0; k < 8; ++k) th.v[k] = atan2f((float)SF_SRC_DY[k], (float)(-SF_SRC_DX[k]));
+    return th;
 }
 
 // src[i] == nullptr: plane i of table `lo` is already on the device (filled from a fuel-code raster)
@@ -677,9 +694,7 @@ static int set_layers_impl(sf_sim *s, int env, const double *const src[7])
         if (src[i]) HIPCHK(hipMemcpyAsync(s->layer(lo, i), src[i], n * sizeof(double), hipMemcpyHostToDevice, s->stream));
     dim3 blk(256), grd((g.W + 255) / 256, g.H);
     hipLaunchKernelGGL(k_slopes, grd, blk, 0, s->stream, g.H, g.W, s->layer(lo, 4), s->slope_scale, s->smag, s->sdir);
-    Thetas th;
-    for (int k = 0; k < 8; ++k)   // theta = arctan2(src_y - dst_y, dst_x - src_x), float32 (rothermel.py:102)
-        th.v[k] = atan2f((float)SF_SRC_DY[k], (float)(-SF_SRC_DX[k]));
+    const Thetas th = rt_thetas();
     dim3 grd2((g.P + 255) / 256, g.H);
     const size_t tab = (size_t)8 * g.plane_env;
     hipLaunchKernelGGL(k_rtable, grd2, blk, 0, s->stream, g.H, g.W, g.P, s->layer(lo, 0), s->layer(lo, 1), s->layer(lo, 2),
@@ -785,6 +800,74 @@ extern "C" int sf_get_attribute_data(sf_sim *s, int32_t env, float *w_0, uint32_
     if (wind_speed) HIPCHK(hipMemcpyAsync(wind_speed, s->layer(t, 5), n * sizeof(double), kind, s->stream));
     if (wind_direction) HIPCHK(hipMemcpyAsync(wind_direction, s->layer(t, 6), n * sizeof(double), kind, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
+    return SF_OK;
+}
+
+// sf_generate_layers (include/simfire_hip.h; sf_gen_kernels.h): every argument is checked before any device work
+static int check_noise(const sf_noise &p, int e, const char *plane)
+{
+    if (p.kind == SF_GEN_NONE || p.kind == SF_GEN_CONSTANT) return SF_OK;
+    if (p.kind != SF_GEN_SIMPLEX) return fail(SF_EINVAL, "sf_generate_layers: environment %d, %s: unknown kind %d", e, plane, p.kind);
+    if (!(p.scale > 0.0)) return fail(SF_EINVAL, "sf_generate_layers: environment %d, %s: scale must be > 0", e, plane);
+    if (p.octaves < 1 || p.octaves > kGenMaxOctaves)
+        return fail(SF_EINVAL, "sf_generate_layers: environment %d, %s: octaves must be 1..%d", e, plane, kGenMaxOctaves);
+    if (!(p.lo < p.hi)) return fail(SF_EINVAL, "sf_generate_layers: environment %d, %s: range_min must be less than range_max", e, plane);
+    return SF_OK;
+}
+
+extern "C" int sf_generate_layers(sf_sim *s, int32_t n, const int32_t *envs, const sf_layer_gen *gen)
+{
+    if (!s) return fail(SF_EINVAL, "sf_generate_layers: null handle");
+    if (n < 0) return fail(SF_EINVAL, "sf_generate_layers: n = %d", n);
+    if (n > 0 && (!envs || !gen)) return fail(SF_EINVAL, "sf_generate_layers: null argument");
+    if (!s->p.per_env_terrain)
+        return fail(SF_ESTATE, "sf_generate_layers: this handle shares one terrain between all environments (create it with per_env_terrain = 1)");
+    const Geo &g = s->g;
+    std::vector<char> seen(g.E, 0);
+    for (int k = 0; k < n; ++k) {
+        const int e = envs[k];
+        if (e < 0 || e >= g.E) return fail(SF_EINVAL, "sf_generate_layers: environment %d out of range", e);
+        if (seen[e]) return fail(SF_EINVAL, "sf_generate_layers: environment %d listed twice", e);
+        seen[e] = 1;
+        const sf_layer_gen &d = gen[k];
+        int rc = check_noise(d.elevation, e, "elevation");
+        if (!rc) rc = check_noise(d.wind_speed, e, "wind_speed");
+        if (!rc) rc = check_noise(d.wind_direction, e, "wind_direction");
+        if (rc) return rc;
+        if (d.fuel != SF_GEN_NONE && d.fuel != SF_GEN_CONSTANT)
+            return fail(SF_EINVAL, "sf_generate_layers: environment %d, fuel: unknown kind %d", e, d.fuel);
+    }
+    if (n == 0) return SF_OK;
+    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
+    const size_t gen_bytes = (size_t)n * sizeof(sf_layer_gen), bytes = gen_bytes + (size_t)n * sizeof(int32_t);
+    if (s->gen_cap < bytes) {
+        if (s->gen_dev) HIPCHK(hipFree(s->gen_dev));
+        s->gen_dev = nullptr;
+        s->gen_cap = 0;
+        HIPCHK(hipMalloc(&s->gen_dev, bytes));
+        s->gen_cap = bytes;
+    }
+    const sf_layer_gen *gen_d = (const sf_layer_gen *)s->gen_dev;
+    const int32_t *envs_d = (const int32_t *)(s->gen_dev + gen_bytes);
+    HIPCHK(hipMemcpyAsync(s->gen_dev, gen, gen_bytes, hipMemcpyHostToDevice, s->stream));
+    HIPCHK(hipMemcpyAsync(s->gen_dev + gen_bytes, envs, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
+    const long long cells = (long long)g.H * g.W;
+    const Thetas th = rt_thetas();
+    for (int k0 = 0; k0 < n; k0 += kGenChunk) {          // (grid y / z hold at most kGenChunk environments)
+        const int m = std::min(n - k0, kGenChunk);
+        hipLaunchKernelGGL(k_gen_planes, dim3((unsigned)((cells + kGenThreads - 1) / kGenThreads), (unsigned)m, 4), dim3(kGenThreads), 0,
+                           s->stream, g.H, g.W, s->lay_all, envs_d, gen_d, k0);
+        HIPCHK(hipGetLastError());
+    }
+    for (int k0 = 0; k0 < n; k0 += kGenChunk) {
+        const int m = std::min(n - k0, kGenChunk);
+        hipLaunchKernelGGL(k_gen_rtable, dim3((unsigned)((g.P + kGenThreads - 1) / kGenThreads), (unsigned)g.H, (unsigned)m), dim3(kGenThreads), 0,
+                           s->stream, g.H, g.W, g.P, (const double *)s->lay_all, envs_d, k0, s->slope_scale, (float)s->p.h, (float)s->p.S_T,
+                           (float)s->p.S_e, (float)s->p.p_p, (float)s->p.M_f, th, s->rt, (long long)8 * g.plane_env);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(s->stream));
+    mark_tables(s, envs, n);
     return SF_OK;
 }
 

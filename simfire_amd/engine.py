@@ -466,6 +466,51 @@ class FireEngine:
         self._chk(self._L.sf_set_layers_fbfm(self._h, -1 if env is None else int(env), _ptr(codes), len(lut_codes),
                                               _ptr(lut_codes), _ptr(lut_fuel), *[_ptr(a) for a in arrs]))
 
+    @staticmethod
+    def _noise(spec):
+        """An ``sf_noise`` from None (plane untouched), a number (constant plane) or a dict of simplex parameters
+        (seed, scale, octaves, persistence, lacunarity, lo, hi)."""
+        n = _lib.SfNoise()
+        if spec is None:
+            n.kind = _lib.SF_GEN_NONE
+        elif isinstance(spec, dict):
+            n.kind, n.seed, n.octaves = _lib.SF_GEN_SIMPLEX, int(spec["seed"]), int(spec["octaves"])
+            n.scale, n.persistence, n.lacunarity = float(spec.get("scale", 1.0)), float(spec["persistence"]), float(spec["lacunarity"])
+            n.lo, n.hi = float(spec["lo"]), float(spec["hi"])
+        else:
+            n.kind, n.lo = _lib.SF_GEN_CONSTANT, float(spec)
+        return n
+
+    def generate_layers(self, envs, elevation=None, fuel=None, wind_speed=None, wind_direction=None):
+        """Draw the layers of ``envs`` on the device and rebuild their R tables (``sf_generate_layers``): one
+        launch for the planes, one for the tables, one wait.  Per plane, a ``list`` with one entry per environment, or one entry for all:
+        ``None`` leaves the plane as it is, a number fills it, a dict draws simplex noise - ``elevation`` as ``workloads.perlin_elevation``
+        (keys seed, octaves, persistence, lacunarity, lo, hi; scale 1), wind as ``workloads.simplex_field`` (+ scale).  ``fuel``:
+        None or a tuple (w_0, delta, M_x, sigma).  Needs a ``per_env_terrain`` handle; a bad argument raises before any device work."""
+        e = self._env_list(envs, "envs")
+        n = int(e.shape[0])
+
+        def per_env(v, name):
+            if isinstance(v, list):
+                if len(v) != n:
+                    raise ValueError(f"{name}: {len(v)} entries for {n} environments")
+                return list(v)
+            return [v] * n
+        el, fu, ws, wd = (per_env(v, k) for v, k in ((elevation, "elevation"), (fuel, "fuel"), (wind_speed, "wind_speed"),
+                                                      (wind_direction, "wind_direction")))
+        gens = (_lib.SfLayerGen * max(n, 1))()
+        for i in range(n):
+            g = gens[i]
+            g.elevation, g.wind_speed, g.wind_direction = self._noise(el[i]), self._noise(ws[i]), self._noise(wd[i])
+            if fu[i] is not None:
+                vals = [float(v) for v in fu[i]]
+                if len(vals) != 4:
+                    raise ValueError("fuel: (w_0, delta, M_x, sigma)")
+                g.fuel = _lib.SF_GEN_CONSTANT
+                for k in range(4):
+                    g.fuel_values[k] = vals[k]
+        self._chk(self._L.sf_generate_layers(self._h, n, _ptr(e), C.cast(gens, C.c_void_p)))
+
     def attribute_data(self, env=0):
         """``FireSimulation.get_attribute_data`` (simfire/sim/simulation.py:376-403) from the layers
         in GPU memory: w_0 / delta / M_x float32, sigma uint32, elevation / wind float64."""

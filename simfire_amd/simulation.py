@@ -545,6 +545,10 @@ class FireSimulation:
             seeds["elevation"] = t.topography_function.kwargs["seed"]
         if t.fuel_function is not None and "seed" in t.fuel_function.kwargs:
             seeds["fuel"] = t.fuel_function.kwargs["seed"]
+        wind = getattr(self.config, "wind", None)            # (a cfd_precompute config has no wind block)
+        for key, fn in (("wind_speed", getattr(wind, "speed_function", None)), ("wind_direction", getattr(wind, "direction_function", None))):
+            if fn is not None and fn.name == "perlin":       # simulation.py:666-698: only perlin wind has seeds
+                seeds[key] = fn.kwargs["seed"]
         if self.config.fire.seed is not None:
             seeds["fire_initial_position"] = self.config.fire.seed
         return seeds
@@ -557,6 +561,9 @@ class FireSimulation:
             success = True
         if "fuel" in seeds:
             self.config.reset_terrain(fuel_seed=seeds["fuel"])
+            success = True
+        if ("wind_speed" in seeds or "wind_direction" in seeds) and getattr(self.config, "wind", None) is not None:
+            self.config.reset_wind(speed_seed=seeds.get("wind_speed"), direction_seed=seeds.get("wind_direction"))   # simulation.py:733-745
             success = True
         if "fire_initial_position" in seeds:
             self.config.reset_fire(seeds["fire_initial_position"])
@@ -673,10 +680,24 @@ class BatchedFireSimulation:
 
     ``ignitions``: int [n_envs, 2] (x, y), or None to draw them like the reference's ``random``
     fire position (``rng = default_rng(seed); x = rng.integers(W); y = rng.integers(H)``,
-    simfire/utils/config.py:810-813) from ``seeds`` (default ``1234 + env``)."""
+    simfire/utils/config.py:810-813) from ``seeds`` (default ``1234 + env``).
+
+    ``per_env_terrain=True`` with one ``Config``: every environment gets a terrain of its own, all
+    initialised from ``config`` (one ``sf_set_layers`` call), so that ``set_seeds`` can give each its
+    own world.  A sequence of configs always has per-environment terrain.
+
+    Seeds (``get_seeds`` / ``set_seeds``, simfire/sim/simulation.py:574-597, 713-759): ``elevation``
+    (perlin topography, ``Config(..., simplex_topography=True)``), ``fuel`` (chaparral),
+    ``wind_speed`` / ``wind_direction`` (perlin wind) and ``fire_initial_position`` (ignitions drawn
+    from seeds), per environment.  A new layer seed takes effect at the next ``reset`` of the
+    environment, which draws the planes on the GPU (``FireEngine.generate_layers``, DESIGN.md
+    section 13) with the generator parameters of the environment's config; from then on
+    ``configs[e]`` and ``terrains[e]`` are ``None`` (they would describe the old world)."""
+
+    _LAYER_KEYS = ("elevation", "fuel", "wind_speed", "wind_direction")
 
     def __init__(self, config: Config, n_envs: int, ignitions=None, seeds: Optional[Sequence[int]] = None,
-                 device: int = 0) -> None:
+                 device: int = 0, per_env_terrain: bool = False) -> None:
         self.n_envs = int(n_envs)
         self.configs = None
         if not isinstance(config, Config):
@@ -692,24 +713,141 @@ class BatchedFireSimulation:
                                          f"environment 0 ({a!r}); one device handle shares this value")
         self.config = config
         H, W = config.area.screen_size
+        fire_seeds = None
         if ignitions is None:
             seeds = list(seeds) if seeds is not None else [1234 + e for e in range(self.n_envs)]
+            fire_seeds = seeds
             ignitions = np.empty((self.n_envs, 2), dtype=np.int32)
             for e, sd in enumerate(seeds):
-                rng = np.random.default_rng(sd)
-                ignitions[e] = (rng.integers(W, dtype=int), rng.integers(H, dtype=int))
+                ignitions[e] = self._ignition(sd)
         self.ignitions = np.asarray(ignitions, dtype=np.int32).reshape(self.n_envs, 2)
-        self._engine, self.terrain = _engine_from_config(config, self.n_envs, device,
-                                                         per_env_terrain=self.configs is not None)
+        self._per_env = self.configs is not None or bool(per_env_terrain)
+        self._engine, self.terrain = _engine_from_config(config, self.n_envs, device, per_env_terrain=self._per_env)
         if self.configs is not None:
             self.terrains = []
             for e, c in enumerate(self.configs):
                 fuels, elev = _config_layers(c)
                 _set_config_layers(self._engine, c, fuels, elev, e)
                 self.terrains.append(_TerrainView(fuels, elev, (H, W)))
+        elif self._per_env:
+            _set_config_layers(self._engine, config, self.terrain.fuels, self.terrain.elevations, None)   # (replicated into every table)
+        self._init_seeds(fire_seeds)
         self.reset()
 
+    def _ignition(self, seed) -> Tuple[int, int]:
+        """config.py:810-813"""
+        H, W = self.config.area.screen_size
+        rng = np.random.default_rng(seed)
+        return rng.integers(W, dtype=int), rng.integers(H, dtype=int)
+
+    # ---- seeds: new worlds per environment (DESIGN.md section 13)
+    @staticmethod
+    def _generators(c: Config) -> Dict[str, dict]:
+        """The seeded generators of one config: key -> (parameters, seed)."""
+        out = {}
+        t = c.terrain
+        if t.topography_function is not None and t.topography_function.name == "perlin":
+            out["elevation"] = dict(t.topography_function.kwargs)
+        if t.fuel_function is not None and t.fuel_function.name == "chaparral" and "seed" in t.fuel_function.kwargs:
+            out["fuel"] = dict(t.fuel_function.kwargs)
+        wind = getattr(c, "wind", None)
+        for key, fn in (("wind_speed", getattr(wind, "speed_function", None)), ("wind_direction", getattr(wind, "direction_function", None))):
+            if fn is not None and fn.name == "perlin":
+                out[key] = dict(fn.kwargs)
+        return out
+
+    def _init_seeds(self, fire_seeds) -> None:
+        """Per environment: the generator parameters (from its config; kept when ``configs[e]`` is dropped) and the seed record."""
+        cfgs = self.configs if self.configs is not None else [self.config] * self.n_envs
+        self._gen = [self._generators(c) for c in cfgs]
+        keys = [k for k in self._LAYER_KEYS if all(k in g for g in self._gen)]
+        self._seeds = {k: np.array([int(g[k]["seed"]) for g in self._gen], dtype=np.int64) for k in keys}
+        if fire_seeds is not None:
+            self._seeds["fire_initial_position"] = np.array([int(v) for v in fire_seeds], dtype=np.int64)
+        self._pending: Dict[int, set] = {}
+
+    def _env_array(self, envs) -> np.ndarray:
+        e = np.arange(self.n_envs, dtype=np.int64) if envs is None else np.atleast_1d(np.asarray(envs, dtype=np.int64)).reshape(-1)
+        if e.size and (e.min() < 0 or e.max() >= self.n_envs):
+            raise IndexError(f"environment out of range 0..{self.n_envs - 1}")
+        return e
+
+    def get_seeds(self, envs=None) -> Dict[str, np.ndarray]:
+        """simulation.py:574-597 per environment: {key: int64 [n]} for the seeds the configured generators have (the values
+        ``set_seeds`` last gave, pending ones included)."""
+        e = self._env_array(envs)
+        return {k: v[e].copy() for k, v in self._seeds.items()}
+
+    def set_seeds(self, seeds: Dict[str, object], envs=None) -> bool:
+        """simulation.py:713-759 for ``envs`` (default: all): each value an int or one value per environment.  Layer seeds take effect
+        at the next ``reset`` of those environments (the planes are drawn on the GPU then); ``fire_initial_position`` sets their
+        ignitions like the constructor's ``seeds``.  A key the configured generators do not have warns and makes the result False
+        (the valid keys are still applied, as in the reference).  Layer keys on a shared-terrain batch raise ValueError."""
+        e = self._env_array(envs)
+        if not self._per_env and any(k in self._LAYER_KEYS for k in seeds):
+            raise ValueError("set_seeds: layer seeds need a terrain per environment; build the BatchedFireSimulation with "
+                             "per_env_terrain=True (or a sequence of configs)")
+        vals = {}
+        for key, v in seeds.items():
+            a = np.asarray(v, dtype=np.int64)
+            if a.ndim == 0:
+                a = np.full(e.shape[0], int(a), dtype=np.int64)
+            if a.shape != e.shape:
+                raise ValueError(f"set_seeds: {key}: {a.shape[0]} values for {e.shape[0]} environments")
+            vals[key] = a
+        success = False
+        for key, a in vals.items():
+            if key not in self._seeds:
+                continue
+            self._seeds[key][e] = a
+            success = True
+            if key == "fire_initial_position":
+                for i, sd in zip(e.tolist(), a.tolist()):
+                    self.ignitions[i] = self._ignition(sd)
+            else:
+                for i in e.tolist():
+                    self._pending.setdefault(i, set()).add(key)
+        valid = list(self._seeds.keys())
+        for key in seeds:
+            if key not in valid:
+                warnings.warn("No valid keys in the seeds dictionary were given to the set_seeds method. No seeds "
+                              f"will be changed. Valid keys are: {valid}")
+                success = False
+        return success
+
+    def _regenerate(self, envs: List[int]) -> None:
+        """The pending layer seeds of ``envs`` as ONE ``sf_generate_layers`` call."""
+        from .config import chaparral_fuel
+        from .units import mph_to_ftpm
+        el, fu, ws, wd = [], [], [], []
+        for e in envs:
+            keys, g = self._pending[e], self._gen[e]
+            p = g.get("elevation")
+            el.append(dict(seed=int(self._seeds["elevation"][e]), scale=1.0, octaves=int(p["octaves"]), persistence=p["persistence"],
+                           lacunarity=p["lacunarity"], lo=p["range_min"], hi=p["range_max"]) if "elevation" in keys else None)
+            if "fuel" in keys:
+                f = chaparral_fuel(int(self._seeds["fuel"][e]))
+                fu.append((f.w_0, f.delta, f.M_x, f.sigma))
+            else:
+                fu.append(None)
+            for key, out, conv in (("wind_speed", ws, mph_to_ftpm), ("wind_direction", wd, lambda v: v)):
+                p = g.get(key)
+                out.append(dict(seed=int(self._seeds[key][e]), scale=p["scale"], octaves=int(p["octaves"]), persistence=p["persistence"],
+                                lacunarity=p["lacunarity"], lo=conv(p["range_min"]), hi=conv(p["range_max"])) if key in keys else None)
+        self._engine.generate_layers(envs, elevation=el, fuel=fu, wind_speed=ws, wind_direction=wd)
+        for e in envs:
+            del self._pending[e]
+            if self.configs is not None:
+                self.configs[e] = None
+                self.terrains[e] = None
+
     def reset(self, envs: Optional[Sequence[int]] = None) -> None:
+        """simulation.py:202-214 for ``envs`` (default: all): pending layer seeds of these environments are drawn first (one device
+        call for all of them), then every listed environment is re-ignited at ``ignitions[e]``."""
+        todo = range(self.n_envs) if envs is None else [int(e) for e in envs]
+        pend = sorted({e for e in todo if e in self._pending})
+        if pend:
+            self._regenerate(pend)
         if envs is None:
             self._engine.reset(self.ignitions)
         else:
@@ -721,19 +859,30 @@ class BatchedFireSimulation:
         """Environment ``dst[i]`` becomes environment ``src[i]`` in every respect - cells, sprite ages, burn amounts, update count,
         elapsed time, running - in one device launch for all pairs (a ``src`` may repeat: one state forked into many slots).
         ``ignitions[dst]`` follows, so that a later ``reset([dst])`` re-ignites where ``src`` started.  With per-environment configs
-        and ``terrain=True``, ``dst`` also takes ``src``'s terrain (``configs`` / ``terrains`` follow); ``terrain=False`` continues
+        and ``terrain=True``, ``dst`` also takes ``src``'s terrain (``configs`` / ``terrains`` and the layer seeds follow); ``terrain=False`` continues
         ``src``'s fire on ``dst``'s own terrain.  Ends a running closed loop."""
         s = np.atleast_1d(np.asarray(src, dtype=np.int64)).reshape(-1)
         d = np.atleast_1d(np.asarray(dst, dtype=np.int64)).reshape(-1)
         if s.shape != d.shape:
             raise ValueError(f"src and dst differ in length ({s.shape[0]} != {d.shape[0]})")
-        per_env = self.configs is not None and terrain
+        per_env = self._per_env and terrain
         self._engine.copy_envs(s, d, terrain=per_env)
         self.ignitions[d] = self.ignitions[s]
-        if per_env:
+        if "fire_initial_position" in self._seeds:
+            self._seeds["fire_initial_position"][d] = self._seeds["fire_initial_position"][s]
+        if per_env:                               # dst takes src's seed record, and src's seeds still pending: it draws the same world at reset
+            for key in self._LAYER_KEYS:
+                if key in self._seeds:
+                    self._seeds[key][d] = self._seeds[key][s]
+            pend = {a: set(self._pending[a]) for a in s.tolist() if a in self._pending}
             for a, b in zip(s.tolist(), d.tolist()):
-                self.configs[b] = self.configs[a]
-                self.terrains[b] = self.terrains[a]
+                self._gen[b] = self._gen[a]
+                self._pending.pop(b, None)
+                if a in pend:
+                    self._pending[b] = set(pend[a])
+                if self.configs is not None:
+                    self.configs[b] = self.configs[a]
+                    self.terrains[b] = self.terrains[a]
 
     def get_state(self, envs=None, device: bool = False) -> SimState:
         """Snapshot of ``envs`` (default: all): the device state as blobs - host numpy, or with ``device=True`` a torch CUDA tensor
@@ -750,7 +899,10 @@ class BatchedFireSimulation:
         else:
             blob = self._engine.save_state(e)
         configs = [self.configs[int(i)] for i in e] if self.configs is not None else None
-        return SimState(blob, e, self.ignitions[e].copy(), configs, headers)
+        state = SimState(blob, e, self.ignitions[e].copy(), configs, headers)
+        fire = self._seeds.get("fire_initial_position")
+        state.fire_seeds = None if fire is None else fire[e].copy()        # (follows the ignition on set_state)
+        return state
 
     def set_state(self, state: SimState, envs=None) -> None:
         """Environment ``envs[i]`` (default: the environments the state was taken from) takes the i-th state of ``state``; its
@@ -762,6 +914,9 @@ class BatchedFireSimulation:
         state.check(self._engine)
         self._engine.load_state(e, state.blob)
         self.ignitions[e] = state.ignitions
+        fire = getattr(state, "fire_seeds", None)
+        if fire is not None and "fire_initial_position" in self._seeds:
+            self._seeds["fire_initial_position"][e] = fire
 
     def run(self, time: Union[str, int], return_maps: bool = True):
         """Steps every environment that is still RUNNING; returns (fire_maps uint8 [E, H, W] or None,

@@ -218,3 +218,29 @@ def c4(size=2048, n_envs=128, env_offset=0):
 
 def build(name, **kw):
     return {"c1": c1, "c2": c2, "c3": c3, "c4": c4, "c5": c5}[name](**kw)
+
+
+def fractal_simplex(H, W, seed, scale, octaves, persistence, lacunarity):
+    """The float64 fractal value of ``simplex_field`` before its ``[lo, hi]`` map: octaves of ``simplex2`` at (x / scale, y / scale),
+    summed with amplitude x persistence and frequency x lacunarity, divided by the amplitude sum - the same operations in the same
+    order, so ``simplex_field`` equals ``(((fractal_simplex(...) + 1.0) * (hi - lo)) / 2.0 + lo).astype(np.float32)``.  [H, W] float64."""
+    y, x = np.mgrid[0:H, 0:W].astype(np.float64)
+    x, y = x / scale, y / scale
+    total, amp, freq, norm = np.zeros((H, W)), 1.0, 1.0, 0.0
+    for _ in range(octaves):
+        total += simplex2(x * freq, y * freq, base=seed) * amp
+        norm += amp
+        freq *= lacunarity
+        amp *= persistence
+    return total / norm
+
+
+def perlin_elevation(H, W, octaves, persistence, lacunarity, seed, range_min, range_max):
+    """``perlin`` topography (simfire/world/elevation_functions.py:75-122) with this build's own simplex generator: the fractal value
+    at the integer cell (x, y) (scale 1), rounded to float32 as ``noise.snoise2`` returns a C float, then
+    ``((z + 1) / 2) * (range_max - range_min) + range_min`` in float64.  NOT the ``noise`` wheel's field (that adds ``base`` to the
+    coordinates, this generator offsets the permutation indices): same parameters, same range, other values.  [H, W] float64 (feet)."""
+    if range_min >= range_max:
+        raise ValueError(f"range_min={range_min} must be less than range_max={range_max}")
+    z = fractal_simplex(H, W, seed, 1.0, octaves, persistence, lacunarity).astype(np.float32).astype(np.float64)
+    return ((z + 1) / 2) * (range_max - range_min) + range_min
