@@ -288,6 +288,43 @@ typedef struct sf_obs_params {
  * (the tensor is complete when the handle's stream has got there); the caller orders its own work on device_out before the call. */
 int sf_observe(sf_sim *sim, const sf_obs_params *params, int32_t n, const int32_t *envs, void *device_out);
 
+/* Frames of environments: what the reference's screen shows (simfire/game/game.py:117-131: the terrain image,
+ * sprites.py:105-160 with the burned paint, the fire / line / agent sprites of sprites.py:20-203 in SpriteLayer order, enums.py:88-103)
+ * as uint8 RGB, one pixel per cell, downscaled by an integer factor, written by ONE launch into caller-owned device memory.  It replaces
+ * sim.rendering + game.update + Game.save (simulation.py:534-537, game.py:295-315) for a headless caller.  Frame t shows the state AFTER
+ * update t (the reference's screen lags by up to one update; not reproduced).  The status bytes are read from whichever plane is
+ * current, or from the history ring; no state of the handle changes (the current plane, the tile books, the reference point of
+ * sf_get_fire_map_delta, the result block).  The per-table background (fuel colour + contour bit) is rebuilt on the device when the
+ * layers or terrain_rgb changed since it was last built. */
+#define SF_RENDER_MAX_SCALE 64
+#define SF_RENDER_MAX_AGENTS 256
+#define SF_RENDER_CURRENT 0        /* source: the current state                                                               */
+#define SF_RENDER_HISTORY 1        /* source: the history ring of sf_enable_history, updates first .. first + count - 1      */
+#define SF_RENDER_NEAREST 0        /* mode: the cell at (oy * scale, ox * scale)                                              */
+#define SF_RENDER_MEAN 1           /* mode: per channel (sum + n / 2) / n over the block's n cells                           */
+#define SF_RENDER_SPRITES 2        /* mode: the block's highest sprite (agent > wet > scratch > fire line > burning), else mean */
+#define SF_RENDER_FUEL 0           /* background: FuelLayer.image (layers.py:654-667, 744-768)                                */
+#define SF_RENDER_WHITE 1          /* background: white, what the v2.0.1 screen shows (sprites.py:155 draws the fuel image with alpha 0) */
+typedef struct sf_render_params {
+    int32_t source;                /* SF_RENDER_CURRENT / SF_RENDER_HISTORY                                                   */
+    int32_t first, count;          /* history: frame t of an environment shows update first + t (sf_get_history numbering),   */
+                                   /* 1 <= count <= capacity; current: ignored, one frame per environment                      */
+    int32_t scale;                 /* 1..SF_RENDER_MAX_SCALE; oh = ceil(H / scale), ow = ceil(W / scale): the last partial     */
+                                   /* block uses the cells it has                                                              */
+    int32_t mode;                  /* SF_RENDER_NEAREST / MEAN / SPRITES (all the same at scale 1)                              */
+    int32_t background;            /* SF_RENDER_FUEL / SF_RENDER_WHITE                                                         */
+    int32_t contours;              /* 1: contour pixels are black                                                              */
+    int32_t terrain_rgb[3];        /* 0..255: the terrain texture colour functional fuel is blended from                      */
+    int32_t channels_last;         /* 1: out[frame][oh][ow][3], 0: out[frame][3][oh][ow]                                      */
+    int32_t agents_k;              /* entries per environment of agents, 0..SF_RENDER_MAX_AGENTS                               */
+    int32_t agents_device;         /* agents is a device pointer                                                               */
+    const int32_t *agents;         /* int32 [n][agents_k][3] = (column, row, id) as sf_observe takes them; null: no agents    */
+} sf_render_params;
+/* Environment envs[i] (a host array; repeats allowed) lands in frames i * count .. i * count + count - 1 (count = 1 for the current
+ * state).  Anything invalid is SF_EINVAL before a launch; a listed environment without layers (sf_set_layers*, sf_generate_layers)
+ * and a history source without sf_enable_history are SF_ESTATE.  In async mode the call only enqueues. */
+int sf_render(sf_sim *sim, const sf_render_params *params, int32_t n, const int32_t *envs, void *device_out);
+
 /* Device buffer int32 [n_envs][8] filled by sf_update_status_device (same content as
  * sf_get_status) - the block that is all-gathered over RCCL by the multi-GPU host code. */
 int sf_status_device(sf_sim *sim, void **ptr);

@@ -58,6 +58,13 @@ class SfLayerGen(C.Structure):
                 ("wind_speed", SfNoise), ("wind_direction", SfNoise)]
 
 
+class SfRenderParams(C.Structure):
+    """``sf_render_params`` (include/simfire_hip.h)."""
+    _fields_ = [("source", C.c_int32), ("first", C.c_int32), ("count", C.c_int32), ("scale", C.c_int32), ("mode", C.c_int32),
+                ("background", C.c_int32), ("contours", C.c_int32), ("terrain_rgb", C.c_int32 * 3), ("channels_last", C.c_int32),
+                ("agents_k", C.c_int32), ("agents_device", C.c_int32), ("agents", C.c_void_p)]
+
+
 # name -> argtypes; every function returns int except the two string getters
 _VP, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
 SIGNATURES = {
@@ -98,6 +105,7 @@ SIGNATURES = {
     "sf_fire_map_device": [_VP, C.POINTER(_VP), C.POINTER(_I64), C.POINTER(_I64)],
     "sf_observe": [_VP, C.POINTER(SfObsParams), _I32, _VP, _VP],
     "sf_cell_layout": [_VP, C.POINTER(_I32)],
+    "sf_render": [_VP, C.POINTER(SfRenderParams), _I32, _VP, _VP],
     "sf_status_device": [_VP, C.POINTER(_VP)],
     "sf_update_status_device": [_VP],
     "sf_copy_status_to": [_VP, _VP],

@@ -101,6 +101,7 @@ extern "C" const char *sf_version(void) { return "simfire_hip 0.2 (gfx950)"; }  
 #include "sf_run_table.h"
 #include "sf_state_kernels.h"
 #include "sf_obs_kernels.h"
+#include "sf_render_kernels.h"
 #include "sf_gen_kernels.h"
 
 // Launch-geometry knobs of a handle (sf_set_tuning, include/simfire_hip_lab.h: SF_TUNE_*).  Results never depend on them; the
@@ -231,6 +232,16 @@ struct sf_sim {
     uint8_t *obs_dev = nullptr, *obs_pinned = nullptr;
     size_t obs_cap = 0;
     hipEvent_t obs_ev = nullptr;
+    // sf_render: per table, layers present / FBFM-coded fuel / background stale; the background words [tables][H * W], the FBFM
+    // colour index plane [tables][H * W] (allocated by the first sf_set_layers_fbfm), the terrain_rgb the fuel colours were made from
+    // (-1: none yet) and the per-call block as for sf_observe
+    std::vector<char> rd_lay, rd_fbfm, rd_stale;
+    uint32_t *rd_bg = nullptr;
+    uint8_t *rd_fuel_ix = nullptr;
+    int64_t rd_rgb = -1;
+    uint8_t *rd_dev = nullptr, *rd_pinned = nullptr;
+    size_t rd_cap = 0;
+    hipEvent_t rd_ev = nullptr;
     uint8_t *gen_dev = nullptr;        // sf_generate_layers: its descriptors + environment list in device memory
     size_t gen_cap = 0;
     bool have_rt = false, was_reset = false, counters_on = false;
@@ -352,6 +363,7 @@ extern "C" int sf_create(const sf_params *p, sf_sim **out)
     TRY(dev_alloc(s, &s->burn, cells));
     TRY(dev_alloc(s, &s->rt, (size_t)8 * g.plane_env * (p->per_env_terrain ? g.E : 1)));
     s->rt_set.assign(p->per_env_terrain ? g.E : 1, 0);
+    s->rd_lay.assign(s->rt_set.size(), 0); s->rd_fbfm.assign(s->rt_set.size(), 0); s->rd_stale.assign(s->rt_set.size(), 1);
     TRY(dev_alloc(s, &s->lay_all, (size_t)7 * g.H * g.W * (p->per_env_terrain ? g.E : 1)));
     TRY(dev_alloc(s, &s->smag, (size_t)g.H * g.W));
     TRY(dev_alloc(s, &s->sdir, (size_t)g.H * g.W));
@@ -419,6 +431,9 @@ extern "C" int sf_destroy(sf_sim *s)
     for (void *dp : {(void *)s->snap, (void *)s->delta_dev, (void *)s->obs_dev, (void *)s->gen_dev}) if (dp) (void)hipFree(dp);
     if (s->obs_pinned) (void)hipHostFree(s->obs_pinned);
     if (s->obs_ev) (void)hipEventDestroy(s->obs_ev);
+    for (void *dp : {(void *)s->rd_bg, (void *)s->rd_fuel_ix, (void *)s->rd_dev}) if (dp) (void)hipFree(dp);
+    if (s->rd_pinned) (void)hipHostFree(s->rd_pinned);
+    if (s->rd_ev) (void)hipEventDestroy(s->rd_ev);
     for (int i = 0; i < sf_sim::kPtsRing; ++i) {
         if (s->pts_pinned[i]) (void)hipHostFree(s->pts_pinned[i]);
         if (s->ev_pts[i]) (void)hipEventDestroy(s->ev_pts[i]);
@@ -708,6 +723,7 @@ static int set_layers_impl(sf_sim *s, int env, const double *const src[7])
     }
     HIPCHK(hipStreamSynchronize(s->stream));
     mark_tables(s, lo, hi);
+    for (int i = lo; i < hi; ++i) { s->rd_lay[i] = 1; s->rd_fbfm[i] = src[0] == nullptr; s->rd_stale[i] = 1; }
     return SF_OK;
 }
 
@@ -741,7 +757,7 @@ extern "C" int sf_set_layers_fbfm(sf_sim *s, int32_t env, const int32_t *codes, 
     HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
     const Geo &g = s->g;
     const size_t n = (size_t)g.H * g.W;
-    rc = ensure_stage(s, n * sizeof(int32_t) + sizeof(int32_t));
+    rc = ensure_stage(s, n * sizeof(int32_t) + (1 + kRdFbfmColours) * sizeof(int32_t));      // codes | bad | sf_render's colour codes
     if (rc) return rc;
     int32_t *codes_dev = (int32_t *)s->stage, *bad_dev = codes_dev + n;
     HIPCHK(hipMemcpyAsync(codes_dev, codes, n * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
@@ -760,6 +776,15 @@ extern "C" int sf_set_layers_fbfm(sf_sim *s, int32_t env, const int32_t *codes, 
     HIPCHK(hipMemcpyAsync(&bad, bad_dev, sizeof bad, hipMemcpyDeviceToHost, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
     if (bad != none) return fail(SF_EINVAL, "sf_set_layers_fbfm: fuel model code %d is not in the table", bad);
+    // the codes' colours for sf_render (FuelLayer._make_image, layers.py:654-667): the codes are dropped after the lookup above
+    if (!s->rd_fuel_ix) HIPCHK(hipMalloc(reinterpret_cast<void **>(&s->rd_fuel_ix), n * s->rt_set.size()));
+    int32_t *tab_dev = bad_dev + 1;
+    HIPCHK(hipMemcpyAsync(tab_dev, kRdFbfmCodes, sizeof kRdFbfmCodes, hipMemcpyHostToDevice, s->stream));
+    hipLaunchKernelGGL(k_render_fuel_ix, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, (long long)n, (const int32_t *)codes_dev,
+                       (const int32_t *)tab_dev, kRdFbfmColours, s->rd_fuel_ix + (size_t)lo * n);
+    HIPCHK(hipGetLastError());
+    for (int i = lo + 1; i < hi; ++i)
+        HIPCHK(hipMemcpyAsync(s->rd_fuel_ix + (size_t)i * n, s->rd_fuel_ix + (size_t)lo * n, n, hipMemcpyDeviceToDevice, s->stream));
     const double *src[7] = {nullptr, nullptr, nullptr, nullptr, elevation, U, U_dir};
     return set_layers_impl(s, env, src);
 }
@@ -868,6 +893,7 @@ extern "C" int sf_generate_layers(sf_sim *s, int32_t n, const int32_t *envs, con
     }
     HIPCHK(hipStreamSynchronize(s->stream));
     mark_tables(s, envs, n);
+    for (int k = 0; k < n; ++k) { s->rd_lay[envs[k]] = 1; s->rd_fbfm[envs[k]] = 0; s->rd_stale[envs[k]] = 1; }
     return SF_OK;
 }
 
@@ -2475,6 +2501,12 @@ extern "C" int sf_copy_envs(sf_sim *s, const int32_t *src, const int32_t *dst, i
     for (int i = 0; i < n; ++i) {
         if (s->snap) s->snap_valid[dst[i]] = 0;      // (sf_get_fire_map_delta: the next query for dst hands back the whole map once)
         if (terrain) {
+            s->rd_lay[dst[i]] = s->rd_lay[src[i]]; s->rd_fbfm[dst[i]] = s->rd_fbfm[src[i]]; s->rd_stale[dst[i]] = 1;
+            if (s->rd_fuel_ix && s->rd_fbfm[src[i]] && dst[i] != src[i]) {
+                const size_t cells = (size_t)g.H * g.W;
+                HIPCHK(hipMemcpyAsync(s->rd_fuel_ix + (size_t)dst[i] * cells, s->rd_fuel_ix + (size_t)src[i] * cells, cells,
+                                      hipMemcpyDeviceToDevice, s->stream));
+            }
             s->rt_set[dst[i]] = s->rt_set[src[i]];
             if (s->rtc_stale.size() == s->rt_set.size()) s->rtc_stale[dst[i]] = s->rtc_stale[src[i]];
             if (!s->rtc || s->rtc_stale.size() != s->rt_set.size() || s->rtc_stale[dst[i]]) s->rtc_valid = false;
@@ -3004,6 +3036,154 @@ extern "C" int sf_observe(sf_sim *s, const sf_obs_params *p, int32_t n, const in
     if (!s->async) {
         HIPCHK(hipStreamSynchronize(s->stream));
         return check_team_error(s, "sf_observe");
+    }
+    return SF_OK;
+}
+
+// ----------------------------------------------------------------------------- frames
+// Output rows per k_render workgroup and its LDS bytes: the staged source rows (R * scale rows of P bytes) and the output bytes of the
+// band (channels last: one segment of R * ow * 3 bytes, else three of R * ow), each segment with 16 bytes of alignment slack.
+struct RenderTile { int R, st_bytes, out_seg, lds; };
+static RenderTile render_tile(const Geo &g, int scale, int oh, int ow, bool cl)
+{
+    constexpr int kBudget = 32768, kMax = 65536 - 256;
+    const auto make = [&](int R) {
+        RenderTile t;
+        t.R = R;
+        t.st_bytes = (R * scale * g.P + 15) / 16 * 16;
+        t.out_seg = cl ? (R * ow * 3 + 16 + 15) / 16 * 16 : (R * ow + 16 + 15) / 16 * 16;
+        t.lds = t.st_bytes + (cl ? 1 : 3) * t.out_seg;
+        return t;
+    };
+    int R = 1;
+    while (R < oh && make(R + 1).lds <= kBudget) ++R;
+    RenderTile t = make(R);
+    if (t.lds > kMax) t.R = 0;
+    return t;
+}
+
+extern "C" int sf_render(sf_sim *s, const sf_render_params *p, int32_t n, const int32_t *envs, void *device_out)
+{
+    if (!s || !p) return fail(SF_EINVAL, "sf_render: null argument");
+    const Geo &g = s->g;
+    if (n < 0 || (n > 0 && (!envs || !device_out))) return fail(SF_EINVAL, "sf_render: bad environment list or output");
+    if (p->source != SF_RENDER_CURRENT && p->source != SF_RENDER_HISTORY)
+        return fail(SF_EINVAL, "sf_render: source %d (0 current, 1 history)", p->source);
+    const bool hist = p->source == SF_RENDER_HISTORY;
+    if (hist && (p->first < 0 || p->count < 1)) return fail(SF_EINVAL, "sf_render: history frames %d from %d", p->count, p->first);
+    if (p->scale < 1 || p->scale > SF_RENDER_MAX_SCALE) return fail(SF_EINVAL, "sf_render: scale %d (1..%d)", p->scale, SF_RENDER_MAX_SCALE);
+    if (p->mode < SF_RENDER_NEAREST || p->mode > SF_RENDER_SPRITES) return fail(SF_EINVAL, "sf_render: mode %d (0 nearest, 1 mean, 2 sprites)", p->mode);
+    if (p->background != SF_RENDER_FUEL && p->background != SF_RENDER_WHITE)
+        return fail(SF_EINVAL, "sf_render: background %d (0 fuel, 1 white)", p->background);
+    if (p->contours != 0 && p->contours != 1) return fail(SF_EINVAL, "sf_render: contours %d (0 or 1)", p->contours);
+    if (p->channels_last != 0 && p->channels_last != 1) return fail(SF_EINVAL, "sf_render: channels_last %d (0 or 1)", p->channels_last);
+    for (int c = 0; c < 3; ++c)
+        if (p->terrain_rgb[c] < 0 || p->terrain_rgb[c] > 255) return fail(SF_EINVAL, "sf_render: terrain_rgb[%d] = %d (0..255)", c, p->terrain_rgb[c]);
+    const int k = p->agents ? p->agents_k : 0;
+    if (p->agents && (p->agents_k < 0 || p->agents_k > SF_RENDER_MAX_AGENTS))
+        return fail(SF_EINVAL, "sf_render: %d agents per environment (0..%d)", p->agents_k, SF_RENDER_MAX_AGENTS);
+    for (int i = 0; i < n; ++i)
+        if (envs[i] < 0 || envs[i] >= g.E) return fail(SF_EINVAL, "sf_render: environment %d out of range", envs[i]);
+    const int s_ = p->scale, oh = (g.H + s_ - 1) / s_, ow = (g.W + s_ - 1) / s_;
+    const bool cl = p->channels_last != 0;
+    const RenderTile tl = render_tile(g, s_, oh, ow, cl);
+    if (tl.R == 0) return fail(SF_ENOTSUP, "sf_render: a row of %d cells does not fit one workgroup's LDS", g.W);
+    const int count = hist ? p->count : 1;
+    const long long frames = (long long)n * count, bands = (oh + tl.R - 1) / tl.R;
+    if (frames * bands > 0x7FFFFFFFLL) return fail(SF_ENOTSUP, "sf_render: %lld frames x %lld bands exceed the launch grid", frames, bands);
+    if (hist && !s->history) return fail(SF_ESTATE, "sf_render: a history source needs sf_enable_history");
+    if (hist && p->count > s->history_cap)
+        return fail(SF_EINVAL, "sf_render: %d updates do not fit the history capacity %d", p->count, s->history_cap);
+    const int n_tab = (int)s->rt_set.size();
+    for (int i = 0; i < n; ++i)
+        if (!s->rd_lay[n_tab == 1 ? 0 : envs[i]]) return fail(SF_ESTATE, "sf_render: environment %d has no layers (sf_set_layers)", envs[i]);
+    if (n == 0) return SF_OK;
+    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
+    { int rc = check_team_error(s, "sf_render"); if (rc) return rc; }
+
+    // which backgrounds to (re)build: the listed environments' stale tables; every functional one when the fuel colours were made
+    // from another terrain_rgb (only the fuel background shows them)
+    const int64_t rgb = p->terrain_rgb[0] | p->terrain_rgb[1] << 8 | p->terrain_rgb[2] << 16;
+    if (p->background == SF_RENDER_FUEL && rgb != s->rd_rgb) {
+        for (int t = 0; t < n_tab; ++t) if (!s->rd_fbfm[t]) s->rd_stale[t] = 1;
+        s->rd_rgb = rgb;
+    }
+    std::vector<int32_t> tabs, fb;
+    {
+        std::vector<char> want(n_tab, 0);
+        for (int i = 0; i < n; ++i) want[n_tab == 1 ? 0 : envs[i]] = 1;
+        for (int t = 0; t < n_tab; ++t)
+            if (want[t] && s->rd_stale[t]) { tabs.push_back(t); fb.push_back(s->rd_fbfm[t]); }
+    }
+    if (!s->rd_bg) HIPCHK(hipMalloc(reinterpret_cast<void **>(&s->rd_bg), (size_t)n_tab * g.H * g.W * sizeof(uint32_t)));
+
+    // the per-call block: envs [n] | tabs [nt] | fbfm [nt] | min / max [nt][2] | agents [n][k][3] (host)
+    const int nt = (int)tabs.size();
+    const auto up16 = [](size_t b) { return (b + 15) / 16 * 16; };
+    const bool ag_host = k > 0 && !p->agents_device;
+    const size_t o_tabs = up16((size_t)n * 4), o_fb = o_tabs + up16((size_t)nt * 4), o_mm = o_fb + up16((size_t)nt * 4);
+    const size_t o_ag = o_mm + (size_t)nt * 16, bytes = o_ag + (ag_host ? (size_t)n * k * 12 : 0);
+    if (!s->rd_ev) HIPCHK(hipEventCreateWithFlags(&s->rd_ev, hipEventDisableTiming));
+    HIPCHK(hipEventSynchronize(s->rd_ev));             // the last call's copy has left the pinned buffer (and its kernels used rd_dev)
+    if (bytes > s->rd_cap) {
+        HIPCHK(hipStreamSynchronize(s->stream));
+        if (s->rd_dev) { HIPCHK(hipFree(s->rd_dev)); s->rd_dev = nullptr; }
+        if (s->rd_pinned) { HIPCHK(hipHostFree(s->rd_pinned)); s->rd_pinned = nullptr; }
+        s->rd_cap = 0;
+        const size_t cap = std::max<size_t>(bytes * 2, 4096);
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&s->rd_dev), cap));
+        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&s->rd_pinned), cap, hipHostMallocDefault));
+        s->rd_cap = cap;
+    }
+    memcpy(s->rd_pinned, envs, (size_t)n * 4);
+    if (nt) { memcpy(s->rd_pinned + o_tabs, tabs.data(), (size_t)nt * 4); memcpy(s->rd_pinned + o_fb, fb.data(), (size_t)nt * 4); }
+    if (ag_host) memcpy(s->rd_pinned + o_ag, p->agents, (size_t)n * k * 12);
+    HIPCHK(hipMemcpyAsync(s->rd_dev, s->rd_pinned, o_mm, hipMemcpyHostToDevice, s->stream));
+    if (ag_host) HIPCHK(hipMemcpyAsync(s->rd_dev + o_ag, s->rd_pinned + o_ag, (size_t)n * k * 12, hipMemcpyHostToDevice, s->stream));
+    HIPCHK(hipEventRecord(s->rd_ev, s->stream));
+
+    if (nt) {
+        RenderBgArgs b;
+        memset(&b, 0, sizeof b);
+        b.H = g.H; b.W = g.W;
+        b.lay = s->lay_all; b.lay_tab = 7LL * g.H * g.W;
+        b.fuel_ix = s->rd_fuel_ix;
+        b.tabs = reinterpret_cast<const int32_t *>(s->rd_dev + o_tabs);
+        b.fbfm = reinterpret_cast<const int32_t *>(s->rd_dev + o_fb);
+        b.mm = reinterpret_cast<double *>(s->rd_dev + o_mm);
+        b.bg = s->rd_bg;
+        b.base = (uint32_t)(s->rd_rgb < 0 ? rgb : s->rd_rgb);
+        for (int c = 0; c < kRdFbfmColours; ++c) {
+            uint32_t w = 0;
+            for (int ch = 0; ch < 3; ++ch) w |= (uint32_t)(uint8_t)(kRdFbfmRgb[c][ch] * 255.0) << (8 * ch);     // astype(np.uint8)
+            b.fbfm_rgb[c] = w;
+        }
+        hipLaunchKernelGGL(k_render_minmax, dim3((unsigned)nt), dim3(1024), 0, s->stream, b);
+        hipLaunchKernelGGL(k_render_bg, dim3((unsigned)g.H, (unsigned)nt), dim3(kRdThreads), 0, s->stream, b);
+        HIPCHK(hipGetLastError());
+        for (int t : tabs) s->rd_stale[t] = 0;
+    }
+
+    RenderArgs a;
+    memset(&a, 0, sizeof a);
+    a.g = g;
+    a.status = s->status;
+    a.cells = !hist && s->bl_cur ? s->cells : nullptr;
+    a.hist = hist ? s->history : nullptr;
+    a.cap = s->history_cap; a.first = hist ? p->first : 0; a.count = count;
+    a.bg = s->rd_bg;
+    a.bg_tab = n_tab > 1 ? (long long)g.H * g.W : 0;
+    a.envs = reinterpret_cast<const int32_t *>(s->rd_dev);
+    a.agents = k == 0 ? nullptr : (ag_host ? reinterpret_cast<const int32_t *>(s->rd_dev + o_ag) : p->agents);
+    a.out = static_cast<uint8_t *>(device_out);
+    a.n_frames = (int)frames; a.k = k;
+    a.s = s_; a.mode = p->mode; a.white = p->background == SF_RENDER_WHITE; a.contours = p->contours; a.cl = cl;
+    a.oh = oh; a.ow = ow; a.R = tl.R; a.stride = g.P; a.st_bytes = tl.st_bytes; a.out_seg = tl.out_seg;
+    hipLaunchKernelGGL(k_render, dim3((unsigned)(frames * bands)), dim3(kRdThreads), (unsigned)tl.lds, s->stream, a);
+    HIPCHK(hipGetLastError());
+    if (!s->async) {
+        HIPCHK(hipStreamSynchronize(s->stream));
+        return check_team_error(s, "sf_render");
     }
     return SF_OK;
 }

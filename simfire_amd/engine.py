@@ -567,6 +567,30 @@ class FireEngine:
             self._blobs_in_flight.extend([out] + spec.device_tensors())
         return out
 
+    def render(self, envs=None, scale=1, mode=None, background="fuel", contours=True, terrain_rgb=None, agents=None, channels_last=True,
+               history=None, out=None):
+        """Frames of ``envs`` (default: all, in order; repeats allowed) as a uint8 torch tensor [n, oh, ow, 3] (or [n, 3, oh, ow]) on
+        this GPU, written by one launch (``sf_render``) from whichever cell plane is current - or, with
+        ``history=(first, count)``, from the history ring (count frames per environment, updates first .. first + count - 1).  No state
+        of the handle changes.  ``agents`` [n, k, 3] = (column, row, id) as for ``observe``.  ``out``: a tensor to fill instead of a new
+        one.  In async mode the call only enqueues and the tensors are kept alive until ``sync()``."""
+        import torch
+        from .render import RenderSpec
+        spec = RenderSpec(self.n_envs, self.H, self.W, envs=envs, scale=scale, mode=mode, background=background, contours=contours,
+                          terrain_rgb=terrain_rgb, agents=agents, channels_last=channels_last, history=history, out=out)
+        dev = torch.device(f"cuda:{self.params.device}")
+        for t in spec.device_tensors() + ([out] if out is not None else []):
+            if t.device != dev:
+                raise ValueError(f"render: a tensor on {t.device}, the simulation runs on {dev}")
+        if out is None:
+            out = torch.empty(spec.shape, dtype=torch.uint8, device=dev)
+        p = spec.params()
+        torch.cuda.synchronize(dev)
+        self._chk(self._L.sf_render(self._h, C.byref(p), spec.n, spec.envs_ptr(), C.c_void_p(out.data_ptr())))
+        if self.async_mode:
+            self._blobs_in_flight.extend([out] + spec.device_tensors())
+        return out
+
     def cell_layout(self):
         """1 = the resident launch's blocked cell plane is current, 0 = the row-major planes (what ``observe`` reads)."""
         v = C.c_int32()

@@ -3,8 +3,8 @@
 ``FireSimulation`` keeps the method names, arguments and return values of the reference class
 (simfire/sim/simulation.py:184-829) for everything that touches the fire-spread path, including
 ``save_data`` (the reference's directory layout, file for file, for ``data_type`` ``npy``, ``json`` / ``jsonl`` and -
-where h5py is installed, as for the reference - ``h5``); display, GIF and spread-graph rendering methods raise
-``NotImplementedError`` (out of scope).  The state lives on the GPU: ``run`` launches the step kernels, ``update_mitigation``
+where h5py is installed, as for the reference - ``h5``); frames and GIFs are rendered on the GPU (``render``, ``recording``,
+``save_gif``: DESIGN.md section 14); the PyGame window and the spread-graph PNG raise ``NotImplementedError`` (out of scope).  The state lives on the GPU: ``run`` launches the step kernels, ``update_mitigation``
 is a device scatter, ``fire_map`` is copied out when ``run`` returns.
 ``BatchedFireSimulation`` adds a leading environment axis (many independent simulations that
 share terrain and wind) - the form the hardware wants.
@@ -208,6 +208,10 @@ class FireSimulation:
         self.config = config
         self._device = device
         self._rendering = False
+        self._recording = False
+        self._frames: List[np.ndarray] = []
+        #: ``render`` options of the frames ``recording`` keeps (scale, mode, background, contours, terrain_rgb)
+        self.recording_options: Dict[str, object] = {}
         self.agents: Dict[int, Tuple[int, int]] = {}
         self.start_time = datetime.now().strftime("%Y-%m-%d_%H-%M-%S")          # simulation.py:56
         self.sf_home = Path(config.simulation.sf_home).expanduser()             # simulation.py:1015
@@ -375,9 +379,10 @@ class FireSimulation:
         self._sync_to_device()
         if self.fire_status == GameStatus.RUNNING and total > 0:
             before = self._steps_done
-            if self.config.simulation.save_data:
-                from .savedata import validate
-                validate(self.config.simulation.data_type)      # (raises before the device is stepped)
+            if self.config.simulation.save_data or self._recording:
+                if self.config.simulation.save_data:
+                    from .savedata import validate
+                    validate(self.config.simulation.data_type)      # (raises before the device is stepped)
                 self._run_saving(before, total)
                 st, el = self._engine.status()
                 row, elapsed, delta = st[0], float(el[0]), "ask"
@@ -397,18 +402,26 @@ class FireSimulation:
     def _run_saving(self, before: int, total: int) -> None:
         """``simulation.save_data``: the reference appends ``fire_map`` to ``fire_map.npy`` after
         every update (simulation.py:548-549).  Here the maps are recorded in GPU memory by the step
-        loop and fetched once per chunk."""
+        loop and fetched once per chunk.  ``recording``: the same chunks become frames on the device
+        (one ``sf_render`` call per chunk), and only the frames are fetched."""
         if self._history_cap == 0:
             self._history_cap = self._HISTORY_CHUNK
             self._engine.enable_history(self._history_cap)
-        done, maps = 0, []
+        save = self.config.simulation.save_data
+        agents = self._frame_agents() if self._recording else None
+        done, got, maps = 0, 0, []
         while done < total:
             n = min(self._history_cap, total - done)
             self._engine.step(n)
             st, _ = self._engine.status()
-            executed = int(st[0, 1]) - before - sum(m.shape[0] for m in maps)
+            executed = int(st[0, 1]) - before - got
             if executed:
-                maps.append(self._engine.history(0, before + sum(m.shape[0] for m in maps), executed))
+                if save:
+                    maps.append(self._engine.history(0, before + got, executed))
+                if self._recording:
+                    frames = self._engine.render(envs=[0], history=(before + got, executed), agents=agents, **self.recording_options)
+                    self._frames.append(frames.cpu().numpy())
+                got += executed
             done += n
             if not st[0, 0]:
                 break
@@ -593,11 +606,57 @@ class FireSimulation:
     @rendering.setter
     def rendering(self, value: bool) -> None:
         if value:
-            raise NotImplementedError("PyGame rendering is outside simfire_amd's scope (SURVEY.md section 2)")
+            raise NotImplementedError("a PyGame window is outside simfire_amd's scope (SURVEY.md section 2); for headless frames use "
+                                      "render(), or recording = True and save_gif() (DESIGN.md section 14)")
         self._rendering = False
 
-    def save_gif(self, path=None):
-        raise NotImplementedError("display / GIF export is outside simfire_amd's scope")
+    @property
+    def recording(self) -> bool:
+        """Headless recording: while True, every ``run`` keeps one frame per executed update (``render`` of the state after it, with
+        ``recording_options``) for ``save_gif``.  Setting it True starts a new clip."""
+        return self._recording
+
+    @recording.setter
+    def recording(self, value: bool) -> None:
+        value = bool(value)
+        if value and not self._recording:
+            self._frames = []
+        if not value and self._recording and not self.config.simulation.save_data and self._history_cap:
+            self._engine.enable_history(0)           # (the ring keeps the step loop on its per-update path)
+            self._history_cap = 0
+        self._recording = value
+
+    @property
+    def frames(self) -> np.ndarray:
+        """uint8 [k, H, W, 3]: the frames recorded since ``recording`` was last set True."""
+        if not self._frames:
+            return np.zeros((0,) + tuple(self.config.area.screen_size) + (3,), dtype=np.uint8)
+        return np.concatenate(self._frames, axis=0)
+
+    def _frame_agents(self):
+        from .observe import agents_from_map
+        one = agents_from_map(self._agent_positions.view(np.ndarray), max_agents=256)
+        return one if one.shape[1] else None
+
+    def render(self, scale: int = 1, mode=None, background: str = "fuel", contours: bool = True, terrain_rgb=None,
+               channels_last: bool = True) -> np.ndarray:
+        """One frame of the current state as a uint8 array [oh, ow, 3] (``BatchedFireSimulation.render``),
+        with this simulation's ``agent_positions``.  Host edits of ``fire_map`` are pushed to the device first, as ``run`` does."""
+        self._sync_to_device()
+        out = self._engine.render(envs=[0], scale=scale, mode=mode, background=background, contours=contours, terrain_rgb=terrain_rgb,
+                                  agents=self._frame_agents(), channels_last=channels_last)
+        return out[0].cpu().numpy()
+
+    def save_gif(self, path=None) -> Path:
+        """simulation.py:831-860: every frame recorded since ``recording`` was last set True, as a GIF (100 ms a frame, looping;
+        game.py:295-315).  ``path``: default ``<sf_home>/gifs/simulation_<now>.gif``; a path without a suffix is a directory, another
+        suffix becomes ``.gif``.  Returns the file written.  No frames: ValueError, as the reference's ``Game.save``."""
+        from .gif import gif_path, write_gif
+        if not self._frames:
+            raise ValueError("no frames were recorded: set recording = True before run()")
+        path = gif_path(path, self.sf_home)
+        write_gif(path, self.frames, duration=100, loop=0)
+        return path
 
     def enable_spread_graph(self, on: bool = True) -> None:
         """Record the fire-spread graph (``simulation.draw_spread_graph: true`` in the config does
@@ -1011,6 +1070,17 @@ class BatchedFireSimulation:
         (DESIGN.md section 12).  ``out``: fill this tensor instead."""
         return self._engine.observe(channels, envs=envs, normalize=normalize, pool=pool, pool_mode=pool_mode, crop=crop, centers=centers,
                                     agents=agents, pad=pad, dtype=dtype, out=out)
+
+    def render(self, envs=None, scale: int = 1, mode=None, background: str = "fuel", contours: bool = True, terrain_rgb=None,
+               agents=None, channels_last: bool = True, out=None):
+        """Frames of the current state of ``envs`` (default: all) for a video logger: one uint8 torch tensor [n, oh, ow, 3] (or
+        [n, 3, oh, ow]) on this GPU, oh = ceil(H / scale).  ``mode``: "nearest", "mean" or "sprites" (default for scale > 1: the
+        block's highest sprite wins, so a fire front stays visible); ``background``: "fuel" (the fuel colours) or "white" (what the
+        reference's screen shows); ``contours``: black contour pixels; ``terrain_rgb``: the texture colour the fuel colours are
+        blended from; ``agents`` [n, k, 3] = (column, row, id) as for ``observe``.  One launch, no host copy, no change to the
+        simulation.  ``out``: fill this tensor instead."""
+        return self._engine.render(envs=envs, scale=scale, mode=mode, background=background, contours=contours, terrain_rgb=terrain_rgb,
+                                   agents=agents, channels_last=channels_last, out=out)
 
     def refresh_fire_maps_device(self) -> None:
         """Bring the plane behind ``fire_maps_device()``'s tensor up to date (the same tensor then shows the current maps)."""
