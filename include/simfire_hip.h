@@ -171,6 +171,18 @@ int sf_history_device(sf_sim *sim, void **ptr, int32_t *capacity);
  * init_xy = int32 [n_envs][2] = (x, y). */
 int sf_reset(sf_sim *sim, const int32_t *init_xy);
 int sf_reset_env(sf_sim *sim, int32_t env, int32_t x, int32_t y);
+/* New episodes in many environments, one call: every environment taken is left exactly as sf_reset_env leaves
+ * it, the others are not touched.  Both calls end a running closed loop first, need sf_reset to have run once (SF_ESTATE) and refuse a
+ * handle whose last team launch failed; in async mode (sf_set_async) they only enqueue, otherwise they wait once at their end.
+ * sf_reset_envs: environments envs[0 .. n) with ignitions xy[i] = (x, y), host arrays.  An environment may repeat (its last ignition
+ * wins); n == 0 does nothing; an environment out of range or an ignition off the grid is SF_EINVAL before anything is enqueued.
+ * sf_reset_where: environment e is taken iff device_mask[e] != 0 (uint8 [n_envs] in device memory) - or, with a null mask, iff it
+ * is not running (what its result row shows: QUIT, still pruning or not; its state on the device: nothing is read back) - and
+ * ignites at xy[e] (int32 [n_envs][2], a host array, or a device array when xy_device_pointer != 0).  An environment whose ignition lies off the grid is left untouched.  The host cannot
+ * know which environments were taken, so the next sf_get_fire_map_delta of every environment returns -1 once. */
+int sf_reset_envs(sf_sim *sim, int32_t n, const int32_t *envs, const int32_t *xy /* [n][2] host */);
+int sf_reset_where(sf_sim *sim, const uint8_t *device_mask /* [n_envs] or NULL: not running */,
+                   const int32_t *xy /* [n_envs][2] */, int32_t xy_device_pointer);
 
 /* FireSimulation.update_mitigation (simulation.py:449-478) for any number of environments:
  * pts = int32 [n][4] rows (env, x, y, type); type in {3,4,5}, other types are skipped with the

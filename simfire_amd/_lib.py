@@ -85,6 +85,10 @@ SIGNATURES = {
     "sf_history_device": [_VP, _VP, _VP],
     "sf_reset": [_VP, _VP],
     "sf_reset_env": [_VP, _I32, _I32, _I32],
+    "sf_reset_envs": [_VP, _I32, _VP, _VP],
+    "sf_reset_where": [_VP, _VP, _VP, _I32],
+    "sf_time_resets": [_VP, _I32],
+    "sf_get_reset_ms": [_VP, C.POINTER(C.c_float)],
     "sf_apply_mitigation": [_VP, _VP, _I32],
     "sf_apply_mitigation_device": [_VP, _VP, _I32],
     "sf_load_fire_map": [_VP, _I32, _VP],

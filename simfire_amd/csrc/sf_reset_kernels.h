@@ -1,0 +1,137 @@
+// Batched reset: new episodes in many environments of a handle at once (k_reset_envs zeroes their slices, k_reset_ignite puts
+// the ignitions, states and result rows down behind it on the same stream).  Part of simfire_hip.hip only (the run units do not
+// include it); the host side is sf_reset_envs / sf_reset_where there, what is written per environment is DESIGN.md section 15.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "sf_common.h"
+
+namespace {
+
+// One per-environment slice of a handle buffer, as CopySeg (sf_state_kernels.h): environment e's bytes are
+// [base + e * stride, base + e * stride + len).  Here the slice is zeroed.
+struct ResetSeg {
+    uint8_t *base;
+    long long stride, len;
+};
+constexpr int kResetSegs = 16;      // enough for every slice sf_reset_envs / sf_reset_where name (14 at most)
+struct ResetArgs {
+    Geo g;
+    ResetSeg seg[kResetSegs];
+    int n_seg;
+    // which environments.  List form: envs[n] (distinct) with xy[n][2].  Mask form (envs == null, n == E): environment e is taken iff
+    // mask[e] != 0 - or, without a mask, iff commit[e].running != 1: what its result row shows as not running (0, or 2 = QUIT on the
+    // runtime check and still pruning, sf_set_prune_after_quit) - and its ignition xy[e] lies on the grid.
+    const int32_t *envs;
+    const uint8_t *mask;
+    const int32_t *xy;
+    int n;
+    // what k_reset_ignite writes (k_init_env's arguments, + the seam planes and the window hint)
+    uint8_t *status, *age, *cells;       // cells: the blocked plane when it is current, else null (row-major planes)
+    EnvState *commit;
+    uint8_t *tflags;
+    int ring;
+    unsigned long long *vbits, *win_hint;
+    uint8_t *seam;                       // null unless the row-major planes are current and the sprite plane is 1 byte wide
+    uint8_t *tdirty;                     // null unless the tile histograms are known (they are zeroed then: all UNBURNED)
+    int32_t *res_block, *res_sink;
+    double *res_elapsed;
+};
+
+// Entry i of the launch: the environment it resets, or -1.  Both kernels decide by this function; k_reset_envs changes nothing it
+// reads (commit[] is written by k_reset_ignite only, the mask and the ignitions are the caller's).
+__device__ __forceinline__ int reset_pick(const ResetArgs &a, int i, int &x, int &y)
+{
+    int e = i;
+    if (a.envs) e = a.envs[i];
+    else if (a.mask ? a.mask[i] == 0 : a.commit[i].running == 1) return -1;
+    x = a.xy[2 * i]; y = a.xy[2 * i + 1];
+    if (x < 0 || x >= a.g.W || y < 0 || y >= a.g.H) return -1;      // (list form: the host has refused these before the launch)
+    return e;
+}
+
+// blockIdx.y = entry, blockIdx.x with the grid's x extent strides over every slice; the workgroups of an entry that is not taken
+// return after that one load.  The addressing is k_env_copy's: a slice whose start sits on a 16-byte boundary is zeroed in 16-byte
+// vectors numbered from the 128-byte line it starts in - the 8 lanes of a line write it whole (or the part of it that belongs to
+// the slice: the neighbour environment's bytes are never touched); other slices (the tile flag planes) are a few hundred bytes and
+// go byte by byte.  Stores only: nothing is read from the slices.
+__global__ __launch_bounds__(256) void k_reset_envs(ResetArgs a)
+{
+    int x, y;
+    const long long e = reset_pick(a, blockIdx.y, x, y);
+    if (e < 0) return;
+    const long long gtid = (long long)blockIdx.x * blockDim.x + threadIdx.x, gstride = (long long)gridDim.x * blockDim.x;
+    const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+    for (int k = 0; k < a.n_seg; ++k) {
+        const ResetSeg c = a.seg[k];
+        uint8_t *dst = c.base + e * c.stride;
+        const long long len = c.len;
+        if (((uintptr_t)dst & 15) == 0) {
+            const long long head = (long long)((uintptr_t)dst & 127);          // bytes of the first line in front of the slice
+            const long long units = (head + len + 15) >> 4;
+            for (long long u = gtid; u < units; u += gstride) {
+                const long long o = u * 16 - head;                              // slice offset of this vector (16-aligned, may be < 0)
+                if (o < 0) continue;
+                if (o + 16 <= len) {
+                    *reinterpret_cast<uint4 *>(dst + o) = zero;
+                } else {
+                    for (long long b = o; b < len; ++b) dst[b] = 0u;
+                }
+            }
+        } else {
+            for (long long b = gtid; b < len; b += gstride) dst[b] = 0u;
+        }
+    }
+}
+
+// One thread per entry, launched behind k_reset_envs on the same stream: what k_init_env writes for the environment, the seam bytes
+// k_rebuild_seams would find for a lone ignition cell, and the window hint.
+__global__ __launch_bounds__(256) void k_reset_ignite(ResetArgs a)
+{
+    const Geo &g = a.g;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    int x, y;
+    const int e = reset_pick(a, i, x, y);
+    if (e < 0) return;
+    const int tyw = y / (g.LR * g.RB), tx = (x / 16) / g.LC;
+    if (a.tdirty) a.tdirty[((long long)e * g.TY + tyw) * g.TX + tx] = 1;      // only the ignition's tile is to be recounted
+    if (a.cells) {                      // the blocked cell plane is the current one (1-byte sprite masks)
+        uint8_t *cell = a.cells + (long long)e * g.cells_env + bl_cell(g, y, x);
+        cell[kBlStatus] = SF_BURNING;
+        cell[0] = 1u;
+    } else {
+        a.status[(long long)e * g.plane_env + (long long)y * g.P + x] = SF_BURNING;
+        age_store(g, a.age + (long long)e * g.age_env * g.ab, (long long)y * g.P + x, 1u);   // ignition step 0
+    }
+    if (a.seam) {                       // the copies of the sprite columns either side of a chunk boundary (k_rebuild_seams)
+        const int cw = g.LC * 16;
+        int b = -1, side = 0;
+        if ((x + 1) % cw == 0) { b = (x + 1) / cw; side = 0; }
+        else if (x % cw == 0) { b = x / cw; side = 1; }
+        if (b >= 1 && b < g.chunks_x) a.seam[(long long)e * g.seam_env + (long long)(b * 2 + side) * g.Hs + y + kSeamPad] = 1u;
+    }
+    a.tflags[(((long long)a.ring * g.E + e) * g.TYp + tyw + 1) * g.TXp + tx + 1] = 1 | 4 | 8 | 16 | 32;   // all edge bits: conservative
+    {
+        const long long o = (long long)e * g.vb_env + (long long)y * g.VW + (x >> 10), plane = (long long)g.E * g.vb_env;
+        const unsigned long long bit = 1ull << ((x >> 4) & 63);
+        a.vbits[o] = bit;
+        if ((x & 15) == 0) a.vbits[plane + o] = bit;
+        if ((x & 15) == 15) a.vbits[2 * plane + o] = bit;
+    }
+    a.win_hint[e] = 0ull;               // (where the old fire stood says nothing about the new one)
+    EnvState s;
+    s.running = 1; s.steps = 0; s.complete = 0; s.elapsed = 0.0;
+    s.time_quit = g.has_max_time && (g.update_rate > g.max_time || 0.0 > g.max_time);
+    a.commit[e] = s;
+    const int32_t row[8] = {1, 0, g.H * g.W - 1, 1, 0, 0, 0, 0};
+    for (int k = 0; k < 8; ++k) {
+        a.res_block[(long long)e * 8 + k] = row[k];
+        if (a.res_sink) a.res_sink[(long long)e * 8 + k] = row[k];
+    }
+    a.res_elapsed[e] = 0.0;
+}
+
+}  // namespace

@@ -100,6 +100,7 @@ extern "C" const char *sf_version(void) { return "simfire_hip 0.2 (gfx950)"; }  
 #include "sf_run_kernels.h"
 #include "sf_run_table.h"
 #include "sf_state_kernels.h"
+#include "sf_reset_kernels.h"
 #include "sf_obs_kernels.h"
 #include "sf_render_kernels.h"
 #include "sf_gen_kernels.h"
@@ -242,6 +243,12 @@ struct sf_sim {
     uint8_t *rd_dev = nullptr, *rd_pinned = nullptr;
     size_t rd_cap = 0;
     hipEvent_t rd_ev = nullptr;
+    // sf_reset_envs / sf_reset_where: the environment list and host ignitions of a call in device memory and the pinned buffer they
+    // are copied from; rs_ev marks the copy's completion (as obs_ev)
+    uint8_t *rs_dev = nullptr, *rs_pinned = nullptr;
+    size_t rs_cap = 0;
+    hipEvent_t rs_ev = nullptr;
+    bool rs_timed = false, rs_have_ms = false;   // sf_time_resets: ev0 / ev1 recorded around the launches of every batched reset
     uint8_t *gen_dev = nullptr;        // sf_generate_layers: its descriptors + environment list in device memory
     size_t gen_cap = 0;
     bool have_rt = false, was_reset = false, counters_on = false;
@@ -431,6 +438,9 @@ extern "C" int sf_destroy(sf_sim *s)
     for (void *dp : {(void *)s->snap, (void *)s->delta_dev, (void *)s->obs_dev, (void *)s->gen_dev}) if (dp) (void)hipFree(dp);
     if (s->obs_pinned) (void)hipHostFree(s->obs_pinned);
     if (s->obs_ev) (void)hipEventDestroy(s->obs_ev);
+    if (s->rs_dev) (void)hipFree(s->rs_dev);
+    if (s->rs_pinned) (void)hipHostFree(s->rs_pinned);
+    if (s->rs_ev) (void)hipEventDestroy(s->rs_ev);
     for (void *dp : {(void *)s->rd_bg, (void *)s->rd_fuel_ix, (void *)s->rd_dev}) if (dp) (void)hipFree(dp);
     if (s->rd_pinned) (void)hipHostFree(s->rd_pinned);
     if (s->rd_ev) (void)hipEventDestroy(s->rd_ev);
@@ -2587,6 +2597,147 @@ static int state_chunk(const StateArgs &a, bool device)
     if (device) return kStateEnvs;
     return (int)std::max<long long>(1, std::min<long long>(kStateEnvs, (64LL << 20) / a.stride));
 }
+
+// ----------------------------------------------------------------------------- batched reset
+// A call's environment list / host ignitions -> device memory through the pinned buffer, one copy; *dev is where they are.
+static int reset_stage(sf_sim *s, const void *a, size_t na, const void *b, size_t nb, uint8_t **dev)
+{
+    const size_t bytes = na + nb;
+    if (!s->rs_ev) HIPCHK(hipEventCreateWithFlags(&s->rs_ev, hipEventDisableTiming));
+    HIPCHK(hipEventSynchronize(s->rs_ev));             // the last call's copy has left the pinned buffer
+    if (bytes > s->rs_cap) {
+        HIPCHK(hipStreamSynchronize(s->stream));       // (its kernels have used rs_dev)
+        if (s->rs_dev) { HIPCHK(hipFree(s->rs_dev)); s->rs_dev = nullptr; }
+        if (s->rs_pinned) { HIPCHK(hipHostFree(s->rs_pinned)); s->rs_pinned = nullptr; }
+        s->rs_cap = 0;
+        const size_t cap = std::max<size_t>(bytes * 2, 4096);
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&s->rs_dev), cap));
+        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&s->rs_pinned), cap, hipHostMallocDefault));
+        s->rs_cap = cap;
+    }
+    if (na) memcpy(s->rs_pinned, a, na);
+    if (nb) memcpy(s->rs_pinned + na, b, nb);
+    HIPCHK(hipMemcpyAsync(s->rs_dev, s->rs_pinned, bytes, hipMemcpyHostToDevice, s->stream));
+    HIPCHK(hipEventRecord(s->rs_ev, s->stream));
+    *dev = s->rs_dev;
+    return SF_OK;
+}
+
+// The two launches of a batched reset.  envs_dev: the list form's environments (distinct), else the mask form over all of them.
+// Writes, for every environment taken, what reset_range + k_init_env + rebuild_seams leave for it in the layout that is current.
+static int reset_launch(sf_sim *s, const int32_t *envs_dev, const uint8_t *mask, const int32_t *xy_dev, int n)
+{
+    const Geo &g = s->g;
+    ResetArgs a;
+    memset(&a, 0, sizeof a);
+    a.g = g;
+    auto add = [&](void *base, long long stride, long long len) { a.seg[a.n_seg++] = {static_cast<uint8_t *>(base), stride, len}; };
+    if (s->bl_cur) add(s->cells_alloc, g.cells_env, g.cells_env);
+    else {
+        add(s->status, g.plane_env, g.plane_env);
+        add(s->age_alloc, g.age_env * g.ab, g.age_env * g.ab);
+    }
+    add(s->burn, g.plane_env * 8, g.plane_env * 8);
+    if (s->settled) add(s->settled, g.plane_env * 4, g.plane_env * 4);
+    if (s->parents) add(s->parents, g.plane_env, g.plane_env);
+    if (s->snap) add(s->snap, g.plane_env, g.plane_env);
+    const long long fplane = (long long)g.TYp * g.TXp, tiles = (long long)g.TY * g.TX;
+    for (int k = 0; k < 2; ++k) add(s->tflags + (size_t)k * g.E * fplane, fplane, fplane);
+    for (int k = 0; k < 3; ++k) add(s->vbits + (size_t)k * g.E * g.vb_env, g.vb_env * 8, g.vb_env * 8);
+    const bool seams = !s->bl_cur && g.ab == 1;       // (the tile bookkeeping is not kept while the blocked plane is current: tiles_valid is false)
+    if (seams) add(s->seam, g.seam_env, g.seam_env);
+    // the tile histograms of a reset environment are known (all UNBURNED, the ignition's tile to be recounted) unless every histogram
+    // of the handle is marked stale anyway: reset_range's condition for a partial reset
+    const bool hist_known = g.ab == 1 && !s->generic && !s->tdirty_all;
+    if (hist_known) {
+        add(s->tdirty, tiles, tiles);
+        add(s->thist, tiles * 16, tiles * 16);
+    }
+    a.envs = envs_dev; a.mask = mask; a.xy = xy_dev; a.n = n;
+    a.status = s->status; a.age = s->age; a.cells = s->bl_cur ? s->cells : nullptr;
+    a.commit = s->commit; a.tflags = s->tflags; a.ring = s->ring; a.vbits = s->vbits; a.win_hint = s->win_hint;
+    a.seam = seams ? s->seam : nullptr;
+    a.tdirty = hist_known ? s->tdirty : nullptr;
+    a.res_block = s->status_block; a.res_sink = s->sink; a.res_elapsed = s->elapsed_dev;
+    long long longest = 0;
+    for (int k = 0; k < a.n_seg; ++k) longest = std::max(longest, a.seg[k].len);
+    const unsigned gx = (unsigned)std::min<long long>(1024, std::max<long long>(1, (longest / 16 + 2047) / 2048));      // ~8 vectors per lane of the longest slice
+    if (s->rs_timed) HIPCHK(hipEventRecord(s->ev0, s->stream));
+    hipLaunchKernelGGL(k_reset_envs, dim3(gx, (unsigned)n), dim3(256), 0, s->stream, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_reset_ignite, dim3((n + 255) / 256), dim3(256), 0, s->stream, a);
+    HIPCHK(hipGetLastError());
+    if (s->rs_timed) { HIPCHK(hipEventRecord(s->ev1, s->stream)); s->rs_have_ms = true; }
+    if (!hist_known) s->tdirty_all = true;
+    return SF_OK;
+}
+
+extern "C" int sf_time_resets(sf_sim *s, int32_t on)
+{
+    if (!s) return fail(SF_EINVAL, "sf_time_resets: null handle");
+    s->rs_timed = on != 0;
+    s->rs_have_ms = false;
+    return SF_OK;
+}
+
+extern "C" int sf_get_reset_ms(sf_sim *s, float *ms_out)
+{
+    if (!s || !ms_out) return fail(SF_EINVAL, "sf_get_reset_ms: null argument");
+    if (!s->rs_have_ms) return fail(SF_ESTATE, "sf_get_reset_ms: no batched reset has been timed (sf_time_resets)");
+    HIPCHK(hipSetDevice(s->p.device));
+    HIPCHK(hipEventSynchronize(s->ev1));
+    HIPCHK(hipEventElapsedTime(ms_out, s->ev0, s->ev1));
+    return SF_OK;
+}
+
+extern "C" int sf_reset_envs(sf_sim *s, int32_t n, const int32_t *envs, const int32_t *xy)
+{
+    if (!s) return fail(SF_EINVAL, "sf_reset_envs: null handle");
+    if (n < 0 || (n > 0 && (!envs || !xy))) return fail(SF_EINVAL, "sf_reset_envs: bad environment list");
+    const Geo &g = s->g;
+    for (int i = 0; i < n; ++i) {
+        if (envs[i] < 0 || envs[i] >= g.E) return fail(SF_EINVAL, "sf_reset_envs: environment %d out of range", envs[i]);
+        if (xy[2 * i] < 0 || xy[2 * i] >= g.W || xy[2 * i + 1] < 0 || xy[2 * i + 1] >= g.H)
+            return fail(SF_EINVAL, "sf_reset_envs: ignition (%d, %d) of environment %d is outside the %dx%d grid", xy[2 * i], xy[2 * i + 1],
+                        envs[i], g.H, g.W);
+    }
+    if (n == 0) return SF_OK;
+    { int rc = state_entry(s, "sf_reset_envs"); if (rc) return rc; }
+    // an environment named twice keeps the last ignition given for it: no two entries of the launch write one environment
+    std::vector<int32_t> last((size_t)g.E, -1), le, lxy;
+    for (int i = 0; i < n; ++i) last[envs[i]] = i;
+    for (int i = 0; i < n; ++i)
+        if (last[envs[i]] == i) { le.push_back(envs[i]); lxy.push_back(xy[2 * i]); lxy.push_back(xy[2 * i + 1]); }
+    const int m = (int)le.size();
+    uint8_t *dev = nullptr;
+    { int rc = reset_stage(s, le.data(), (size_t)m * 4, lxy.data(), (size_t)m * 8, &dev); if (rc) return rc; }
+    { int rc = reset_launch(s, reinterpret_cast<const int32_t *>(dev), nullptr, reinterpret_cast<const int32_t *>(dev + (size_t)m * 4), m); if (rc) return rc; }
+    if (s->snap) for (int i = 0; i < m; ++i) s->snap_valid[le[i]] = 1;      // (sf_get_fire_map_delta: a reset map is all UNBURNED; the next delta reports the ignition)
+    if (!s->async) HIPCHK(hipStreamSynchronize(s->stream));
+    return SF_OK;
+}
+
+extern "C" int sf_reset_where(sf_sim *s, const uint8_t *device_mask, const int32_t *xy, int32_t xy_device_pointer)
+{
+    if (!s) return fail(SF_EINVAL, "sf_reset_where: null handle");
+    if (!xy) return fail(SF_EINVAL, "sf_reset_where: null ignitions");
+    const Geo &g = s->g;
+    { int rc = state_entry(s, "sf_reset_where"); if (rc) return rc; }
+    const int32_t *xy_dev = xy;
+    if (!xy_device_pointer) {
+        uint8_t *dev = nullptr;
+        int rc = reset_stage(s, xy, (size_t)g.E * 8, nullptr, 0, &dev);
+        if (rc) return rc;
+        xy_dev = reinterpret_cast<const int32_t *>(dev);
+    }
+    { int rc = reset_launch(s, nullptr, device_mask, xy_dev, g.E); if (rc) return rc; }
+    // which environments were taken is known on the device only: no host mirror of a map can be told to zero itself, so the next
+    // delta query of every environment hands back the whole map once
+    if (s->snap) std::fill(s->snap_valid.begin(), s->snap_valid.end(), 0);
+    if (!s->async) HIPCHK(hipStreamSynchronize(s->stream));
+    return SF_OK;
+}
+
 
 extern "C" int sf_state_bytes(sf_sim *s, int64_t *bytes_out)
 {

@@ -118,6 +118,76 @@ class FireEngine:
     def reset_env(self, env, x, y):
         self._chk(self._L.sf_reset_env(self._h, int(env), int(x), int(y)))
 
+    def _ignitions(self, xy, n, name):
+        """Host ignitions int32 [n, 2] = (x, y), every one on the grid (checked here: no device call has been made yet)."""
+        a = np.asarray(xy)
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"{name}: ignitions must be integers, got {a.dtype}")
+        if a.shape != (n, 2):
+            raise ValueError(f"{name}: ignitions must have shape {(n, 2)}, got {a.shape}")
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        bad = np.flatnonzero((a[:, 0] < 0) | (a[:, 0] >= self.W) | (a[:, 1] < 0) | (a[:, 1] >= self.H))
+        if bad.size:
+            i = int(bad[0])
+            raise ValueError(f"{name}: ignition ({a[i, 0]}, {a[i, 1]}) of entry {i} is outside the {self.H}x{self.W} grid")
+        return a
+
+    def reset_envs(self, envs, xy):
+        """New episodes in ``envs`` (environment ``envs[i]`` ignites at ``xy[i]`` = (x, y)), one launch for all of them
+        (``sf_reset_envs``).  An environment may repeat: its last ignition wins.  In async mode the call only enqueues."""
+        e = np.asarray(envs)
+        if e.ndim != 1 or (e.size and e.dtype.kind not in "iu"):
+            raise ValueError("reset_envs: envs must be a list of environment numbers")
+        e = np.ascontiguousarray(e, dtype=np.int32)
+        a = self._ignitions(xy, e.shape[0], "reset_envs")
+        if e.size and (e.min() < 0 or e.max() >= self.n_envs):
+            raise IndexError(f"reset_envs: environment {int(e[(e < 0) | (e >= self.n_envs)][0])} out of range (n_envs = {self.n_envs})")
+        if e.size:
+            self._chk(self._L.sf_reset_envs(self._h, int(e.shape[0]), _ptr(e), _ptr(a)))
+
+    def reset_where(self, mask=None, xy=None):
+        """New episodes in every environment that is not running (``mask=None``; decided on the device, nothing is read back) or that
+        ``mask`` selects (a torch CUDA uint8 / bool tensor [n_envs] on this GPU); environment e ignites at ``xy[e]`` - a NumPy array
+        or a torch CUDA int32 tensor [n_envs, 2] (``sf_reset_where``).  A device ignition off the grid leaves its environment
+        untouched.  Torch's queued work on the tensors is waited for first; in async mode they are kept alive until ``sync``."""
+        tensors = []
+        if mask is not None:
+            import torch
+            if not isinstance(mask, torch.Tensor) or not mask.is_cuda or mask.dtype not in (torch.uint8, torch.bool) \
+                    or tuple(mask.shape) != (self.n_envs,):
+                raise ValueError(f"reset_where: mask must be None or a CUDA uint8 / bool tensor of shape ({self.n_envs},)")
+            mask = mask.contiguous()
+            tensors.append(mask)
+        if xy is None:
+            raise ValueError("reset_where: xy (the ignitions, [n_envs, 2]) is required")
+        if getattr(xy, "is_cuda", False):
+            import torch
+            if xy.dtype != torch.int32 or tuple(xy.shape) != (self.n_envs, 2):
+                raise ValueError(f"reset_where: a device xy must be a CUDA int32 tensor of shape ({self.n_envs}, 2)")
+            xy = xy.contiguous()
+            tensors.append(xy)
+            xy_ptr, xy_dev = C.c_void_p(xy.data_ptr()), 1
+        else:
+            a = self._ignitions(xy, self.n_envs, "reset_where")
+            xy_ptr, xy_dev = _ptr(a), 0
+        mask_ptr = C.c_void_p(mask.data_ptr()) if mask is not None else None
+        if tensors:
+            import torch
+            torch.cuda.synchronize(tensors[0].device)
+        self._chk(self._L.sf_reset_where(self._h, mask_ptr, xy_ptr, xy_dev))
+        if self.async_mode:
+            self._blobs_in_flight.extend(tensors)
+
+    def time_resets(self, on=True):
+        """Measurement only: record HIP events around the launches of every ``reset_envs`` / ``reset_where`` (``sf_time_resets``)."""
+        self._chk(self._L.sf_time_resets(self._h, int(bool(on))))
+
+    def reset_ms(self):
+        """GPU milliseconds of the last timed batched reset's launches (``sf_get_reset_ms``; waits for them)."""
+        ms = C.c_float(0.0)
+        self._chk(self._L.sf_get_reset_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
     def apply_mitigation(self, pts):
         """pts: rows (env, x, y, type)."""
         q = np.ascontiguousarray(np.asarray(pts, dtype=np.int32).reshape(-1, 4))

@@ -909,9 +909,19 @@ class BatchedFireSimulation:
             self._regenerate(pend)
         if envs is None:
             self._engine.reset(self.ignitions)
-        else:
-            for e in envs:
-                self._engine.reset_env(int(e), int(self.ignitions[e, 0]), int(self.ignitions[e, 1]))
+        elif len(todo):
+            self._engine.reset_envs(todo, self.ignitions[todo])       # one launch for the whole list (sf_reset_envs)
+
+    def reset_done(self, mask=None) -> None:
+        """New episodes where the old ones are over, without a look at the result block: every environment that is not running (or, with
+        ``mask`` - a torch CUDA uint8 / bool tensor [n_envs] -, every environment the mask selects) is re-ignited at ``ignitions[e]``
+        (``sf_reset_where``).  ``ignitions[e]`` is where e ignites at its NEXT reset: a harness that wants a fresh ignition per episode
+        sets them ahead (``set_seeds({"fire_initial_position": ...})`` or the array).  Nothing is read back, so the host cannot know
+        whose pending layer seeds to draw: with any pending, use ``reset(envs)``."""
+        if self._pending:
+            raise ValueError(f"reset_done: layer seeds are pending for environments {sorted(self._pending)} (set_seeds); which of them "
+                             "start a new episode is known on the device only - call reset(envs) for them")
+        self._engine.reset_where(mask, self.ignitions)
 
     # ---- environment state: fork, snapshot, restore (DESIGN.md section 11)
     def clone_envs(self, src, dst, terrain: bool = True) -> None:
