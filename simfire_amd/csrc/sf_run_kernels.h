@@ -168,9 +168,13 @@ __device__ __forceinline__ WalkAcc run_walk(const StepArgs &a, const RunEnv &ev,
         // bytes 0..2 = cells x-1, x, x+1 of the rows y-1, y, y+1: cell b sits at byte 4 + b of a row strip
         const int q = (3 + b) >> 2;
         const uint32_t sh = (uint32_t)(3 + b) & 3u;
-        const uint32_t up3 = __builtin_amdgcn_alignbyte(rec[2 + q], rec[1 + q], sh);
-        const uint32_t mid3 = __builtin_amdgcn_alignbyte(rec[8 + q], rec[7 + q], sh);
-        const uint32_t dn3 = __builtin_amdgcn_alignbyte(rec[14 + q], rec[13 + q], sh);
+        // (the three strip reads are issued together and waited for once: left alone, the compiler reuses one register pair for them and
+        // makes them three dependent LDS round trips per cell)
+        uint32_t u0 = rec[1 + q], u1 = rec[2 + q], m0 = rec[7 + q], m1 = rec[8 + q], d0 = rec[13 + q], d1 = rec[14 + q];
+        asm volatile("" : "+v"(u0), "+v"(u1), "+v"(m0), "+v"(m1), "+v"(d0), "+v"(d1));
+        const uint32_t up3 = __builtin_amdgcn_alignbyte(u1, u0, sh);
+        const uint32_t mid3 = __builtin_amdgcn_alignbyte(m1, m0, sh);
+        const uint32_t dn3 = __builtin_amdgcn_alignbyte(d1, d0, sh);
         const int bestk = pick_winner8(up3, mid3, dn3, mk, lo_mask, hi_mask);
         c.cand = valid && bestk >= 0;
         c.yx = (uint32_t)y | ((uint32_t)x << 16);
@@ -906,7 +910,8 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
         __syncthreads();
     }
     unsigned long long join_clk = __builtin_readcyclecounter();      // TEAM = 2, member 0: when the last cut was (what an update costs: the board)
-    unsigned long long x_clocks = 0, x_steps = 0;      // TEAM statistics: clocks wave 0 spent at the team's step boundaries (publish + wait + read), boundaries
+    unsigned long long x_clocks = 0;   // TEAM statistics: clocks wave 0 spent at the team's step boundaries (publish + wait + read)
+    uint32_t x_steps = 0;              // ... and the boundaries (one register: its counter slot has 32 bits for it)
     for (int s = s_begin; s < n_steps && (st.running || mit); ++s) {
         const int k = s % 3, kn = (s + 1) % 3;
 #ifdef SF_PHASES
@@ -1304,8 +1309,13 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
             pc.mark(2);      // vector list written, barrier
 
             // ---- batches of 64 vectors off the shared cursor.  A wave requests the rows of its NEXT batch before it
-            // works on the current one: the walk's memory round trips hide the next batch's.  (Reading a neighbour
-            // vector before or after the current batch rewrites it makes no difference: in-place update, see above.)
+            // works on the current one, and nothing between the request and that work looks at what was requested (`fetch`
+            // selects addresses, never loaded values; the team halo is put in by `batch`): the current batch's work and the
+            // walk's memory round trips hide the next batch's.  The compiled code shows whether that holds - a wait that
+            // names vmcnt behind the prefetch means it does not (profiles/isa_waits.py, tests/test_batch_prefetch_isa_cpu.py).
+            // The rows are waited for once, at the top of the loop, where they become the current batch's (that wait also
+            // retires the walk's last stores: one in-order counter).  (Reading a neighbour vector before or after the
+            // current batch rewrites it makes no difference: in-place update, see above.)
             struct VecIn { uint32_t item; uint4 up, mid, dn, sr; uint32_t l0, l1, l2, r0, r1, r2; };
             // (a young fire's one or two batches: wave w takes batch w, no round trip to the cursor on the way - driver window - 3 %; longer
             // lists are handed out by the cursor from the start: dealing the first round out by wave number cost C4 and the 1024-environment
@@ -1331,11 +1341,10 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
                 in.item = has ? item : 0xFFFFFFFFu;
                 in.mid = *reinterpret_cast<const uint4 *>(p_mid);
                 in.sr = *reinterpret_cast<const uint4 *>(p_mid + kBlStatus);
-                {
-                    const uint4 r_pair = *reinterpret_cast<const uint4 *>(p_pair), r_far = *reinterpret_cast<const uint4 *>(p_far);
-                    in.up = odd ? r_pair : r_far;
-                    in.dn = odd ? r_far : r_pair;
-                }
+                // (through the SELECTED ADDRESSES: selecting between the two loaded rows would need their data, i.e. a full wait for the
+                // prefetch right here, in front of the current batch's work)
+                in.up = *reinterpret_cast<const uint4 *>(p_up);
+                in.dn = *reinterpret_cast<const uint4 *>(p_dn);
                 // The cells just left / right of the vector.  The list runs by rows, so the vector to the left, if it is
                 // interesting at all, is the list entry before this one, i.e. the lane below - and if it is not
                 // interesting, it and the vectors above / below it hold no sprite bit: the edge cells are zero.  Only
@@ -1351,21 +1360,8 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
                     in.r0 = *reinterpret_cast<const uint32_t *>(p_mid + 128);
                     if (diag) { in.r1 = *reinterpret_cast<const uint32_t *>(p_up + 128); in.r2 = *reinterpret_cast<const uint32_t *>(p_dn + 128); }
                 }
-                if (TEAM) {
-                    // The row above the band's first row / below its last row belongs to a neighbour: its sprite masks as of the end of
-                    // the step before come from the LDS halo rows (what the plain loads above returned for them is dropped).  Bands start
-                    // on even rows and end on odd ones: that row is always the `far` one.
-                    const bool hu = has_up && y == R0, hd = has_dn && y == R1 - 1;
-                    if (hu | hd) {
-                        const uint4 *hrow = halo + (hd ? g.PV : 0);
-                        const uint4 hv = hrow[v];
-                        if (hu) in.up = hv; else in.dn = hv;
-                        if (diag) {
-                            if (has && lane == 0 && v > 0) { const uint32_t q = hrow[v - 1].w; if (hu) in.l1 = q; else in.l2 = q; }
-                            if (has && (j0 + lane + 1 == n_chunk || lane == bsz - 1) && x0 + 16 < g.W) { const uint32_t q = hrow[v + 1].x; if (hu) in.r1 = q; else in.r2 = q; }
-                        }
-                    }
-                }
+                // (TEAM: for a band's first / last row the `far` row loaded here belongs to a neighbour and is replaced by the LDS halo row
+                // where the rows are consumed, at the top of `batch` - replacing it here would wait for the loads)
             };
             const uint32_t j_first = dealt ? (uint32_t)(wave * bsz) : grab();
             pc.note(16);     // first batch known
@@ -1393,17 +1389,35 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
                 const int x0 = v * 16;
                 const uint32_t voff = (uint32_t)(y * g.P + x0);             // burn_amounts / settled: row-major
                 uint8_t *vmask = ev.cells + bl_vec(g, y, v) + (y & 1) * 16;  // this vector's mask row; its status row is kBlStatus further
-                const uint4 up = cur.up, mid = cur.mid, dn = cur.dn, sr = cur.sr;
+                const uint4 mid = cur.mid, sr = cur.sr;
+                uint4 up = cur.up, dn = cur.dn;
+                uint32_t cl1 = cur.l1, cl2 = cur.l2, cr1 = cur.r1, cr2 = cur.r2;
+                const bool last_lane = j0 + lane + 1 == n_chunk || lane == bsz - 1;
+                if (TEAM) {
+                    // The row above the band's first row / below its last row belongs to a neighbour: its sprite masks as of the end of
+                    // the step before come from the LDS halo rows (what the plain loads of `fetch` returned for them is dropped; the halo
+                    // rows do not change during a step).  Bands start on even rows and end on odd ones: that row is always the `far` one.
+                    // Done here and not in `fetch`: replacing a loaded value needs the value, and here the rows have to have arrived anyway.
+                    const bool hu = has_up && y == R0, hd = has_dn && y == R1 - 1;      // (idle lanes: y = 0xFFFF, no band row)
+                    if (hu | hd) {
+                        const uint4 *hrow = halo + (hd ? g.PV : 0);
+                        const uint4 hv = hrow[v];
+                        if (hu) up = hv; else dn = hv;
+                        if (diag) {
+                            if (lane == 0 && v > 0) { const uint32_t q = hrow[v - 1].w; if (hu) cl1 = q; else cl2 = q; }
+                            if (last_lane && x0 + 16 < g.W) { const uint32_t q = hrow[v + 1].x; if (hu) cr1 = q; else cr2 = q; }
+                        }
+                    }
+                }
                 const uint32_t item_l = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)item, 0x138, 0xF, 0xF, false);   // wave_shr:1
                 const uint32_t item_r = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)item, 0x130, 0xF, 0xF, false);   // wave_shl:1
-                const bool last_lane = j0 + lane + 1 == n_chunk || lane == bsz - 1;
                 n_vec_done += (lane == 0) ? (n_chunk - j0 < (uint32_t)bsz ? n_chunk - j0 : (uint32_t)bsz) : 0u;
                 const uint4 midL = and4(mid, L4);
                 const uint4 vsrc = and4(or4(up, dn), L4);
                 const uint4 hsrc = diag ? or4(midL, vsrc) : midL;
                 // per row: the cell left of the vector in byte 3 of l?, the cell right of it in byte 0 of r?
-                uint32_t l0 = cur.l0 & 0xFF000000u, l1 = cur.l1 & 0xFF000000u, l2 = cur.l2 & 0xFF000000u;
-                uint32_t r0 = cur.r0 & 0xFFu, r1 = cur.r1 & 0xFFu, r2 = cur.r2 & 0xFFu;
+                uint32_t l0 = cur.l0 & 0xFF000000u, l1 = cl1 & 0xFF000000u, l2 = cl2 & 0xFF000000u;
+                uint32_t r0 = cur.r0 & 0xFFu, r1 = cr1 & 0xFFu, r2 = cr2 & 0xFFu;
                 {
                     const uint32_t dl0 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mid.w, 0x138, 0xF, 0xF, false);
                     const uint32_t dl1 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)up.w, 0x138, 0xF, 0xF, false);
@@ -1798,14 +1812,18 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
     }
     wpc.note(49);            // state committed, bitmaps handed back
     if (a.counters && lane == 0) {
-        unsigned long long *cs = a.counters + (size_t)((blockIdx.x * 16 + wave) & (kCounterShards - 1)) * kCounterRow;
+        // (the wave number through an opaque copy: the address is then worked out here, once per launch, and not ahead of the step loop,
+        // where it held two vector registers through every batch - in the kernels at the register cap, two spilled ones)
+        int cw = wave;
+        asm volatile("" : "+v"(cw));
+        unsigned long long *cs = a.counters + (size_t)((blockIdx.x * 16 + cw) & (kCounterShards - 1)) * kCounterRow;
         if (n_active) atomicAdd(&cs[0], (unsigned long long)n_active);
         if (n_ignite) atomicAdd(&cs[1], (unsigned long long)n_ignite);
         if (n_items_acc) atomicAdd(&cs[2], (unsigned long long)n_items_acc);
         if (n_phase2) atomicAdd(&cs[4], (unsigned long long)n_phase2);   // frontier walks
         if (n_vec_done) atomicAdd(&cs[5], (unsigned long long)n_vec_done);   // 16-cell vectors visited
         if (TEAM && x_steps) {     // (the two slots k_front uses for its records / sprite events)
-            atomicAdd(&cs[6], x_steps | ((unsigned long long)(one_l2 ? x_steps : 0ull) << 32));      // team step boundaries | those through one L2 << 32
+            atomicAdd(&cs[6], (unsigned long long)x_steps | ((unsigned long long)(one_l2 ? x_steps : 0u) << 32));      // team step boundaries | those through one L2 << 32
             atomicAdd(&cs[7], x_clocks);
         }
     }
