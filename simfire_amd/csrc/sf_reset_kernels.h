@@ -7,19 +7,13 @@
 #include <cstdint>
 
 #include "sf_common.h"
+#include "sf_env_segs.h"
 
 namespace {
 
-// One per-environment slice of a handle buffer, as CopySeg (sf_state_kernels.h): environment e's bytes are
-// [base + e * stride, base + e * stride + len).  Here the slice is zeroed.
-struct ResetSeg {
-    uint8_t *base;
-    long long stride, len;
-};
-constexpr int kResetSegs = 16;      // enough for every slice sf_reset_envs / sf_reset_where name (14 at most)
 struct ResetArgs {
     Geo g;
-    ResetSeg seg[kResetSegs];
+    EnvSeg seg[kEnvSegs];               // the slices to zero (sf_env_segs.h)
     int n_seg;
     // which environments.  List form: envs[n] (distinct) with xy[n][2].  Mask form (envs == null, n == E): environment e is taken iff
     // mask[e] != 0 - or, without a mask, iff commit[e].running != 1: what its result row shows as not running (0, or 2 = QUIT on the
@@ -52,37 +46,17 @@ __device__ __forceinline__ int reset_pick(const ResetArgs &a, int i, int &x, int
     return e;
 }
 
-// blockIdx.y = entry, blockIdx.x with the grid's x extent strides over every slice; the workgroups of an entry that is not taken
-// return after that one load.  The addressing is k_env_copy's: a slice whose start sits on a 16-byte boundary is zeroed in 16-byte
-// vectors numbered from the 128-byte line it starts in - the 8 lanes of a line write it whole (or the part of it that belongs to
-// the slice: the neighbour environment's bytes are never touched); other slices (the tile flag planes) are a few hundred bytes and
-// go byte by byte.  Stores only: nothing is read from the slices.
+// blockIdx.y = entry, blockIdx.x with the grid's x extent strides over every slice (env_seg_walk, sf_env_segs.h); the workgroups of
+// an entry that is not taken return after that one load.  Stores only: nothing is read from the slices.
 __global__ __launch_bounds__(256) void k_reset_envs(ResetArgs a)
 {
     int x, y;
     const long long e = reset_pick(a, blockIdx.y, x, y);
     if (e < 0) return;
     const long long gtid = (long long)blockIdx.x * blockDim.x + threadIdx.x, gstride = (long long)gridDim.x * blockDim.x;
-    const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
     for (int k = 0; k < a.n_seg; ++k) {
-        const ResetSeg c = a.seg[k];
-        uint8_t *dst = c.base + e * c.stride;
-        const long long len = c.len;
-        if (((uintptr_t)dst & 15) == 0) {
-            const long long head = (long long)((uintptr_t)dst & 127);          // bytes of the first line in front of the slice
-            const long long units = (head + len + 15) >> 4;
-            for (long long u = gtid; u < units; u += gstride) {
-                const long long o = u * 16 - head;                              // slice offset of this vector (16-aligned, may be < 0)
-                if (o < 0) continue;
-                if (o + 16 <= len) {
-                    *reinterpret_cast<uint4 *>(dst + o) = zero;
-                } else {
-                    for (long long b = o; b < len; ++b) dst[b] = 0u;
-                }
-            }
-        } else {
-            for (long long b = gtid; b < len; b += gstride) dst[b] = 0u;
-        }
+        const EnvSeg c = a.seg[k];
+        env_seg_walk<false>(c.base + e * c.stride, nullptr, c.len, gtid, gstride);
     }
 }
 

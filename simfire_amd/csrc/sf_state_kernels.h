@@ -7,52 +7,27 @@
 #include <cstdint>
 
 #include "sf_common.h"
+#include "sf_env_segs.h"
 
 namespace {
 
 // ------------------------------------------------------------------------------------------ fork
-// One per-environment slice of a handle buffer: environment e's bytes are [base + e * stride, base + e * stride + len).
-struct CopySeg {
-    uint8_t *base;
-    long long stride, len;
-};
-constexpr int kCopySegs = 24;       // enough for every slice sf_copy_envs names (22 at most)
 constexpr int kCopyPairs = 128;     // (src, dst) pairs per launch: they travel as kernel arguments, so an enqueued launch owns them
 struct CopyList {
-    CopySeg seg[kCopySegs];
+    EnvSeg seg[kEnvSegs];
     int n_seg;
     int32_t src[kCopyPairs], dst[kCopyPairs];
 };
 
-// blockIdx.y = pair, blockIdx.x with the grid's x extent strides over every slice.  A slice whose two ends sit on 16-byte boundaries
-// is copied in 16-byte vectors, numbered from the 128-byte line its destination starts in: the 8 lanes of a line write it whole (or
-// the part of it that belongs to the slice - the neighbour environment's bytes are never touched).  Other slices (the 24-byte
-// EnvState, per-environment words, the tile flag planes) are a few hundred bytes and go byte by byte.
+// blockIdx.y = pair, blockIdx.x with the grid's x extent strides over every slice (env_seg_walk, sf_env_segs.h).
 __global__ __launch_bounds__(256) void k_env_copy(CopyList L)
 {
     const int p = blockIdx.y;
     const long long gtid = (long long)blockIdx.x * blockDim.x + threadIdx.x, gstride = (long long)gridDim.x * blockDim.x;
     const long long se = L.src[p], de = L.dst[p];
     for (int k = 0; k < L.n_seg; ++k) {
-        const CopySeg c = L.seg[k];
-        const uint8_t *src = c.base + se * c.stride;
-        uint8_t *dst = c.base + de * c.stride;
-        const long long len = c.len;
-        if ((((uintptr_t)src | (uintptr_t)dst) & 15) == 0) {
-            const long long head = (long long)((uintptr_t)dst & 127);          // bytes of the first line in front of the slice
-            const long long units = (head + len + 15) >> 4;
-            for (long long u = gtid; u < units; u += gstride) {
-                const long long o = u * 16 - head;                              // slice offset of this vector (16-aligned, may be < 0)
-                if (o < 0) continue;
-                if (o + 16 <= len) {
-                    *reinterpret_cast<uint4 *>(dst + o) = *reinterpret_cast<const uint4 *>(src + o);
-                } else {
-                    for (long long b = o; b < len; ++b) dst[b] = src[b];
-                }
-            }
-        } else {
-            for (long long b = gtid; b < len; b += gstride) dst[b] = src[b];
-        }
+        const EnvSeg c = L.seg[k];
+        env_seg_walk<true>(c.base + de * c.stride, c.base + se * c.stride, c.len, gtid, gstride);
     }
 }
 

@@ -47,6 +47,7 @@
 #include <emmintrin.h>
 #include <hip/hip_runtime.h>
 
+#include <cassert>
 #include <cmath>
 #include <cstdarg>
 #include <cstdint>
@@ -116,6 +117,16 @@ static const int kTuneDefault[SF_TUNE_COUNT] = {
     /* SF_TUNE_WAVES_PER_CU */ 24, /* RUN_WAVES */ 16, /* RUN_MIN_ENVS */ 1, /* RUN_VCAP */ 4096, /* RUN_COMPACT */ 1,
     /* RUN_BATCH */ 64, /* RUN_RESULT */ 1, /* RUN_SEGMENT */ 64, /* RUN_TEAM */ 0, /* TEAM_PLACEMENT */ 0, /* TEAM_RECUT */ 1, /* RUN_WINDOW */ 1, /* TEAM_TIMEOUT_MS */ 2000,
     /* RUN_JOIN */ 1, /* LOOP_LIGHT */ 0};
+
+// What a batched call sends ahead of its kernels (environment list, descriptors, host points): a device buffer, the pinned mirror it
+// is copied from, and the event that marks the copy's completion - the next call of the feature waits for it before it writes the
+// mirror again, so a call in async mode never waits for the one before it unless the mirror is still being read (block_reserve /
+// block_send).  One block per feature: a shared one would make one feature's calls wait for another's.
+struct CallBlock {
+    uint8_t *dev = nullptr, *pinned = nullptr;
+    size_t cap = 0;
+    hipEvent_t ev = nullptr;
+};
 
 // ----------------------------------------------------------------------------- handle
 struct sf_sim {
@@ -228,29 +239,18 @@ struct sf_sim {
     int32_t *mit_stage = nullptr;      // sf_step_mitigated: device copy of a host point block / expanded rows of one step
     size_t mit_stage_bytes = 0;
     bool async = false;                // sf_set_async: calls that return no data do not synchronise
-    // sf_observe: its per-call block (ObsHead, environment list, host centers / agents) in device memory and the pinned buffer it is
-    // copied from; obs_ev marks the copy's completion (the next call waits for it before it writes the pinned buffer again)
-    uint8_t *obs_dev = nullptr, *obs_pinned = nullptr;
-    size_t obs_cap = 0;
-    hipEvent_t obs_ev = nullptr;
+    CallBlock obs_blk;                 // sf_observe: ObsHead, environment list, host centers / agents
     // sf_render: per table, layers present / FBFM-coded fuel / background stale; the background words [tables][H * W], the FBFM
     // colour index plane [tables][H * W] (allocated by the first sf_set_layers_fbfm), the terrain_rgb the fuel colours were made from
-    // (-1: none yet) and the per-call block as for sf_observe
+    // (-1: none yet) and the per-call block (lists of environments and tables, the min / max words its kernels write, host agents)
     std::vector<char> rd_lay, rd_fbfm, rd_stale;
     uint32_t *rd_bg = nullptr;
     uint8_t *rd_fuel_ix = nullptr;
     int64_t rd_rgb = -1;
-    uint8_t *rd_dev = nullptr, *rd_pinned = nullptr;
-    size_t rd_cap = 0;
-    hipEvent_t rd_ev = nullptr;
-    // sf_reset_envs / sf_reset_where: the environment list and host ignitions of a call in device memory and the pinned buffer they
-    // are copied from; rs_ev marks the copy's completion (as obs_ev)
-    uint8_t *rs_dev = nullptr, *rs_pinned = nullptr;
-    size_t rs_cap = 0;
-    hipEvent_t rs_ev = nullptr;
+    CallBlock rd_blk;
+    CallBlock rs_blk;                  // sf_reset_envs / sf_reset_where: the environment list and host ignitions of a call
     bool rs_timed = false, rs_have_ms = false;   // sf_time_resets: ev0 / ev1 recorded around the launches of every batched reset
-    uint8_t *gen_dev = nullptr;        // sf_generate_layers: its descriptors + environment list in device memory
-    size_t gen_cap = 0;
+    CallBlock gen_blk;                 // sf_generate_layers: its descriptors + environment list
     bool have_rt = false, was_reset = false, counters_on = false;
     int seq = 0;                       // index (mod 6) of the next step launch
     Tuning tune;                       // sf_set_tuning
@@ -277,6 +277,20 @@ static int check_team_error(const sf_sim *s, const char *where)
     return SF_OK;
 }
 
+// The environment list of a batched call: every entry names an environment of the handle and, where `twice` is given (the words of
+// the refusal), none is named twice.  (n < 0 and null lists are the caller's to refuse: it knows what else must not be null.)
+static int check_envs(const sf_sim *s, const char *who, int32_t n, const int32_t *envs, const char *twice = nullptr)
+{
+    std::vector<char> seen(twice ? (size_t)s->g.E : 0, 0);
+    for (int i = 0; i < n; ++i) {
+        const int e = envs[i];
+        if (e < 0 || e >= s->g.E) return fail(SF_EINVAL, "%s: environment %d out of range", who, e);
+        if (twice && seen[e]) return fail(SF_EINVAL, "%s: environment %d %s", who, e, twice);
+        if (twice) seen[e] = 1;
+    }
+    return SF_OK;
+}
+
 static int ensure_stage(sf_sim *s, size_t bytes)
 {
     if (bytes <= s->stage_bytes) return SF_OK;
@@ -292,6 +306,32 @@ static int dev_alloc(sf_sim *s, T **p, size_t n)
 {
     HIPCHK(hipMalloc(reinterpret_cast<void **>(p), n * sizeof(T)));
     s->bytes += (int64_t)(n * sizeof(T));
+    return SF_OK;
+}
+
+// Room for `bytes` in a call block, its mirror free to be written: the last call's copy has left it.  Growing (to twice the request,
+// 4 KB at least) waits for the stream first: enqueued kernels may still read the device buffer.
+static int block_reserve(sf_sim *s, CallBlock &b, size_t bytes)
+{
+    if (!b.ev) HIPCHK(hipEventCreateWithFlags(&b.ev, hipEventDisableTiming));
+    HIPCHK(hipEventSynchronize(b.ev));
+    if (bytes <= b.cap) return SF_OK;
+    HIPCHK(hipStreamSynchronize(s->stream));
+    if (b.dev) { HIPCHK(hipFree(b.dev)); b.dev = nullptr; }
+    if (b.pinned) { HIPCHK(hipHostFree(b.pinned)); b.pinned = nullptr; }
+    b.cap = 0;
+    const size_t cap = std::max<size_t>(bytes * 2, 4096);
+    HIPCHK(hipMalloc(reinterpret_cast<void **>(&b.dev), cap));
+    HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&b.pinned), cap, hipHostMallocDefault));
+    b.cap = cap;
+    return SF_OK;
+}
+// The mirror's bytes [0, head) and, if any, [off, off + more) -> the device buffer on the handle's stream, then the event.
+static int block_send(sf_sim *s, CallBlock &b, size_t head, size_t off = 0, size_t more = 0)
+{
+    HIPCHK(hipMemcpyAsync(b.dev, b.pinned, head, hipMemcpyHostToDevice, s->stream));
+    if (more) HIPCHK(hipMemcpyAsync(b.dev + off, b.pinned + off, more, hipMemcpyHostToDevice, s->stream));
+    HIPCHK(hipEventRecord(b.ev, s->stream));
     return SF_OK;
 }
 
@@ -435,15 +475,12 @@ extern "C" int sf_destroy(sf_sim *s)
                     s->status_block, s->elapsed_dev, s->stage, s->parents};
     if (s->status_pinned) (void)hipHostFree(s->status_pinned);
     if (s->delta_pinned) (void)hipHostFree(s->delta_pinned);
-    for (void *dp : {(void *)s->snap, (void *)s->delta_dev, (void *)s->obs_dev, (void *)s->gen_dev}) if (dp) (void)hipFree(dp);
-    if (s->obs_pinned) (void)hipHostFree(s->obs_pinned);
-    if (s->obs_ev) (void)hipEventDestroy(s->obs_ev);
-    if (s->rs_dev) (void)hipFree(s->rs_dev);
-    if (s->rs_pinned) (void)hipHostFree(s->rs_pinned);
-    if (s->rs_ev) (void)hipEventDestroy(s->rs_ev);
-    for (void *dp : {(void *)s->rd_bg, (void *)s->rd_fuel_ix, (void *)s->rd_dev}) if (dp) (void)hipFree(dp);
-    if (s->rd_pinned) (void)hipHostFree(s->rd_pinned);
-    if (s->rd_ev) (void)hipEventDestroy(s->rd_ev);
+    for (void *dp : {(void *)s->snap, (void *)s->delta_dev, (void *)s->rd_bg, (void *)s->rd_fuel_ix}) if (dp) (void)hipFree(dp);
+    for (CallBlock *b : {&s->obs_blk, &s->rd_blk, &s->rs_blk, &s->gen_blk}) {
+        if (b->dev) (void)hipFree(b->dev);
+        if (b->pinned) (void)hipHostFree(b->pinned);
+        if (b->ev) (void)hipEventDestroy(b->ev);
+    }
     for (int i = 0; i < sf_sim::kPtsRing; ++i) {
         if (s->pts_pinned[i]) (void)hipHostFree(s->pts_pinned[i]);
         if (s->ev_pts[i]) (void)hipEventDestroy(s->ev_pts[i]);
@@ -858,12 +895,9 @@ extern "C" int sf_generate_layers(sf_sim *s, int32_t n, const int32_t *envs, con
     if (!s->p.per_env_terrain)
         return fail(SF_ESTATE, "sf_generate_layers: this handle shares one terrain between all environments (create it with per_env_terrain = 1)");
     const Geo &g = s->g;
-    std::vector<char> seen(g.E, 0);
+    { int rc = check_envs(s, "sf_generate_layers", n, envs, "listed twice"); if (rc) return rc; }
     for (int k = 0; k < n; ++k) {
         const int e = envs[k];
-        if (e < 0 || e >= g.E) return fail(SF_EINVAL, "sf_generate_layers: environment %d out of range", e);
-        if (seen[e]) return fail(SF_EINVAL, "sf_generate_layers: environment %d listed twice", e);
-        seen[e] = 1;
         const sf_layer_gen &d = gen[k];
         int rc = check_noise(d.elevation, e, "elevation");
         if (!rc) rc = check_noise(d.wind_speed, e, "wind_speed");
@@ -875,17 +909,13 @@ extern "C" int sf_generate_layers(sf_sim *s, int32_t n, const int32_t *envs, con
     if (n == 0) return SF_OK;
     HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
     const size_t gen_bytes = (size_t)n * sizeof(sf_layer_gen), bytes = gen_bytes + (size_t)n * sizeof(int32_t);
-    if (s->gen_cap < bytes) {
-        if (s->gen_dev) HIPCHK(hipFree(s->gen_dev));
-        s->gen_dev = nullptr;
-        s->gen_cap = 0;
-        HIPCHK(hipMalloc(&s->gen_dev, bytes));
-        s->gen_cap = bytes;
-    }
-    const sf_layer_gen *gen_d = (const sf_layer_gen *)s->gen_dev;
-    const int32_t *envs_d = (const int32_t *)(s->gen_dev + gen_bytes);
-    HIPCHK(hipMemcpyAsync(s->gen_dev, gen, gen_bytes, hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipMemcpyAsync(s->gen_dev + gen_bytes, envs, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
+    CallBlock &blk = s->gen_blk;
+    { int rc = block_reserve(s, blk, bytes); if (rc) return rc; }
+    memcpy(blk.pinned, gen, gen_bytes);
+    memcpy(blk.pinned + gen_bytes, envs, (size_t)n * sizeof(int32_t));
+    { int rc = block_send(s, blk, bytes); if (rc) return rc; }
+    const sf_layer_gen *gen_d = (const sf_layer_gen *)blk.dev;
+    const int32_t *envs_d = (const int32_t *)(blk.dev + gen_bytes);
     const long long cells = (long long)g.H * g.W;
     const Thetas th = rt_thetas();
     for (int k0 = 0; k0 < n; k0 += kGenChunk) {          // (grid y / z hold at most kGenChunk environments)
@@ -995,6 +1025,53 @@ static int ensure_commit(sf_sim *s)
     return SF_OK;
 }
 
+// The per-environment slices of the handle's buffers, of the kinds asked for, in the layout that is current (sf_env_segs.h; what each
+// is: DESIGN.md section 11).  Looked up per call: the blocked plane, settled, parents, snap, the sink and rtc exist lazily or not at
+// all, and a slice that does not exist is left out.  out holds kEnvSegs entries; the number written is returned.
+static int env_segs(const sf_sim *s, unsigned kinds, EnvSeg *out)
+{
+    const Geo &g = s->g;
+    int n = 0;
+    auto add = [&](unsigned kind, void *base, long long len) {
+        if (!(kinds & kind) || !base) return;
+        assert(n < kEnvSegs);
+        out[n++] = {static_cast<uint8_t *>(base), len, len};
+    };
+    if (s->bl_cur) add(kSegCells, s->cells_alloc, g.cells_env);
+    else {
+        add(kSegCells, s->status, g.plane_env);
+        add(kSegCells, s->age_alloc, g.age_env * g.ab);      // (with its guard rows)
+    }
+    add(kSegBurn, s->burn, g.plane_env * 8);
+    add(kSegSettled, s->settled, g.plane_env * 4);
+    add(kSegParents, s->parents, g.plane_env);
+    add(kSegSnap, s->snap, g.plane_env);
+    add(kSegState, s->commit, sizeof(EnvState));
+    add(kSegResult, s->status_block, 32);
+    add(kSegResult, s->elapsed_dev, 8);
+    add(kSegResult, s->sink, 32);
+    const long long fplane = (long long)g.TYp * g.TXp, tiles = (long long)g.TY * g.TX;
+    for (int k = 0; k < 2; ++k) add(kSegTflags, s->tflags + (size_t)k * g.E * fplane, fplane);
+    for (int k = 0; k < 3; ++k) add(kSegVbits, s->vbits + (size_t)k * g.E * g.vb_env, g.vb_env * 8);
+    add(kSegSeam, s->seam, g.seam_env);
+    add(kSegHist, s->tdirty, tiles);
+    add(kSegHist, s->thist, tiles * 16);
+    add(kSegHint, s->win_hint, 8);
+    add(kSegCost, s->run_cost, 4);
+    const long long tab = 8 * g.plane_env * (long long)sizeof(double), lay = 7LL * g.H * g.W * (long long)sizeof(double);
+    add(kSegTerrain, s->rt, tab);            // (per table: a caller asks for these on a per-environment-terrain handle only)
+    add(kSegTerrain, s->lay_all, lay);
+    add(kSegTerrain, s->rtc, tab);
+    return n;
+}
+// x extent of the grid of a kernel that walks these slices (env_seg_walk): ~8 vectors per lane of the longest slice
+static unsigned seg_grid_x(const EnvSeg *seg, int n)
+{
+    long long longest = 0;
+    for (int k = 0; k < n; ++k) longest = std::max(longest, seg[k].len);
+    return (unsigned)std::min<long long>(1024, std::max<long long>(1, (longest / 16 + 2047) / 2048));
+}
+
 static int reset_range(sf_sim *s, int env0, int n, const int32_t *xy)
 {
     const Geo &g = s->g;
@@ -1007,44 +1084,28 @@ static int reset_range(sf_sim *s, int env0, int n, const int32_t *xy)
     if (n == g.E) s->status_fresh = true;
     { int rc0 = ensure_commit(s); if (rc0) return rc0; }     // the other environments' states must be current in commit[]
     if (n == g.E) s->cost_steps = 0;                         // new episodes: what the environments cost before says nothing about them
-    HIPCHK(hipMemsetAsync(s->win_hint + env0, 0, (size_t)n * sizeof(unsigned long long), s->stream));      // (where the old fires stood says nothing about the new ones)
     if (n == g.E) {
         // everything is rewritten, nothing to convert: into the blocked plane if the resident launch is what steps this handle
         // (it did last, or nothing has stepped yet and it is the automatic choice), else into the row-major planes
         const bool bl = prefers_bl(s) && (s->bl_cur || s->last_kind == 2 || s->last_kind == -1);
         if (bl) { int rc0 = alloc_bl(s); if (rc0) return rc0; }
         s->bl_cur = bl;
-        HIPCHK(hipMemsetAsync(s->run_cost, 0, (size_t)g.E * sizeof(uint32_t), s->stream));      // new episodes everywhere: no launch order to carry over
     }
-    if (s->bl_cur)
-        HIPCHK(hipMemsetAsync(s->cells_alloc + (size_t)env0 * g.cells_env, 0, (size_t)n * g.cells_env, s->stream));
-    else {
-        HIPCHK(hipMemsetAsync(s->status + (size_t)env0 * g.plane_env, 0, (size_t)n * g.plane_env, s->stream));
-        HIPCHK(hipMemsetAsync(s->age + ((long long)env0 * g.age_env - g.P) * g.ab, 0, (size_t)n * g.age_env * g.ab, s->stream));
-    }
-    HIPCHK(hipMemsetAsync(s->burn + (size_t)env0 * g.plane_env, 0, (size_t)n * g.plane_env * sizeof(double), s->stream));
-    if (s->parents) HIPCHK(hipMemsetAsync(s->parents + (size_t)env0 * g.plane_env, 0, (size_t)n * g.plane_env, s->stream));
-    if (s->settled) HIPCHK(hipMemsetAsync(s->settled + (size_t)env0 * g.plane_env, 0, (size_t)n * g.plane_env * sizeof(uint32_t), s->stream));
-    if (s->snap) {      // sf_get_fire_map_delta: a reset map is all UNBURNED but for the ignition cell, which the next delta reports
-        HIPCHK(hipMemsetAsync(s->snap + (size_t)env0 * g.plane_env, 0, (size_t)n * g.plane_env, s->stream));
-        for (int i = 0; i < n; ++i) s->snap_valid[env0 + i] = 1;
-    }
-    int rc = ensure_stage(s, (size_t)n * 2 * sizeof(int32_t));
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(s->stage, xy, (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
-    const size_t fplane = (size_t)g.TYp * g.TXp;
-    for (int k = 0; k < 2; ++k)
-        HIPCHK(hipMemsetAsync(s->tflags + ((size_t)k * g.E + env0) * fplane, 0, (size_t)n * fplane, s->stream));
-    for (int k = 0; k < 3; ++k)
-        HIPCHK(hipMemsetAsync(s->vbits + ((size_t)k * g.E + env0) * g.vb_env, 0, (size_t)n * g.vb_env * sizeof(unsigned long long), s->stream));
     // Result-block bookkeeping: a freshly reset environment is all UNBURNED but for its ignition cell - its tile histograms are
     // written here (zeros) and only the ignition's tile is marked for a recount.  (A partial reset while everything is marked stale anyway leaves it at that.)
     const bool hist_known = g.ab == 1 && !s->generic && (n == g.E || !s->tdirty_all);
-    if (hist_known) {
-        const size_t per_env = (size_t)g.TY * g.TX;
-        HIPCHK(hipMemsetAsync(s->tdirty + (size_t)env0 * per_env, 0, (size_t)n * per_env, s->stream));
-        HIPCHK(hipMemsetAsync(s->thist + (size_t)env0 * per_env * 8, 0, (size_t)n * per_env * 8 * sizeof(uint16_t), s->stream));
+    // What is zeroed here: a batched reset's slices but the seams (rebuild_seams below), + the window advice (where the old fires
+    // stood says nothing about the new ones) and, with new episodes everywhere, the launch-order cost (no order to carry over)
+    EnvSeg seg[kEnvSegs];
+    const int n_seg = env_segs(s, (kResetKinds & ~kSegSeam & ~(hist_known ? 0u : kSegHist)) | kSegHint | (n == g.E ? kSegCost : 0u), seg);
+    for (int k = 0; k < n_seg; ++k) {
+        assert(seg[k].stride == seg[k].len);      // (the slices of env0 .. env0 + n - 1 are one range)
+        HIPCHK(hipMemsetAsync(seg[k].base + env0 * seg[k].stride, 0, (size_t)(n * seg[k].len), s->stream));
     }
+    if (s->snap) for (int i = 0; i < n; ++i) s->snap_valid[env0 + i] = 1;      // sf_get_fire_map_delta: a reset map is all UNBURNED but for the ignition cell, which the next delta reports
+    int rc = ensure_stage(s, (size_t)n * 2 * sizeof(int32_t));
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(s->stage, xy, (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
     hipLaunchKernelGGL(k_init_env, dim3((n + 255) / 256), dim3(256), 0, s->stream, g, s->status, s->age, s->bl_cur ? s->cells : nullptr, s->commit,
                        s->tflags, s->ring, s->vbits, (const int32_t *)s->stage, env0, n, hist_known ? s->tdirty : nullptr, s->status_block, s->elapsed_dev, s->sink);
     HIPCHK(hipGetLastError());
@@ -2456,9 +2517,8 @@ extern "C" int sf_copy_envs(sf_sim *s, const int32_t *src, const int32_t *dst, i
     if (flags & ~SF_COPY_TERRAIN) return fail(SF_EINVAL, "sf_copy_envs: unknown flags 0x%x", flags);
     const Geo &g = s->g;
     std::vector<char> role((size_t)g.E, 0);       // bit 0: a source, bit 1: a destination
+    { int rc = check_envs(s, "sf_copy_envs", n, src); if (!rc) rc = check_envs(s, "sf_copy_envs", n, dst); if (rc) return rc; }
     for (int i = 0; i < n; ++i) {
-        if (src[i] < 0 || src[i] >= g.E || dst[i] < 0 || dst[i] >= g.E)
-            return fail(SF_EINVAL, "sf_copy_envs: pair %d (%d -> %d) names an environment out of range", i, src[i], dst[i]);
         if (role[dst[i]] & 2) return fail(SF_EINVAL, "sf_copy_envs: environment %d is a destination twice", dst[i]);
         role[dst[i]] |= 2;
     }
@@ -2470,38 +2530,9 @@ extern "C" int sf_copy_envs(sf_sim *s, const int32_t *src, const int32_t *dst, i
     // Every per-environment slice of the current layout and of the structures derived from it: a handle-wide "rebuild" flag would make
     // the next step rebuild them for every environment.
     CopyList L;
-    L.n_seg = 0;
-    auto add = [&](void *base, long long stride, long long len) { L.seg[L.n_seg++] = {static_cast<uint8_t *>(base), stride, len}; };
-    if (s->bl_cur) add(s->cells_alloc, g.cells_env, g.cells_env);
-    else {
-        add(s->status, g.plane_env, g.plane_env);
-        add(s->age_alloc, g.age_env * g.ab, g.age_env * g.ab);
-    }
-    add(s->burn, g.plane_env * 8, g.plane_env * 8);
-    if (s->settled) add(s->settled, g.plane_env * 4, g.plane_env * 4);
-    if (s->parents) add(s->parents, g.plane_env, g.plane_env);
-    add(s->commit, sizeof(EnvState), sizeof(EnvState));
-    add(s->status_block, 32, 32);
-    add(s->elapsed_dev, 8, 8);
-    if (s->sink) add(s->sink, 32, 32);
-    const long long fplane = (long long)g.TYp * g.TXp, tiles = (long long)g.TY * g.TX;
-    for (int k = 0; k < 2; ++k) add(s->tflags + (size_t)k * g.E * fplane, fplane, fplane);
-    for (int k = 0; k < 3; ++k) add(s->vbits + (size_t)k * g.E * g.vb_env, g.vb_env * 8, g.vb_env * 8);
-    add(s->seam, g.seam_env, g.seam_env);
-    add(s->tdirty, tiles, tiles);
-    add(s->thist, tiles * 16, tiles * 16);
-    add(s->win_hint, 8, 8);
-    add(s->run_cost, 4, 4);
-    const bool terrain = (flags & SF_COPY_TERRAIN) && s->rt_set.size() > 1;
-    if (terrain) {
-        const long long tab = 8 * g.plane_env * (long long)sizeof(double), lay = 7LL * g.H * g.W * (long long)sizeof(double);
-        add(s->rt, tab, tab);
-        add(s->lay_all, lay, lay);
-        if (s->rtc) add(s->rtc, tab, tab);       // (a stale copy stays marked stale below)
-    }
-    long long longest = 0;
-    for (int k = 0; k < L.n_seg; ++k) longest = std::max(longest, L.seg[k].len);
-    const unsigned gx = (unsigned)std::min<long long>(1024, std::max<long long>(1, (longest / 16 + 2047) / 2048));      // ~8 vectors per lane of the longest slice
+    const bool terrain = (flags & SF_COPY_TERRAIN) && s->rt_set.size() > 1;      // (a stale rtc copy stays marked stale below)
+    L.n_seg = env_segs(s, terrain ? kForkKinds : kForkKinds & ~kSegTerrain, L.seg);
+    const unsigned gx = seg_grid_x(L.seg, L.n_seg);
     for (int i0 = 0; i0 < n; i0 += kCopyPairs) {
         const int cnt = std::min(kCopyPairs, n - i0);
         for (int i = 0; i < cnt; ++i) { L.src[i] = src[i0 + i]; L.dst[i] = dst[i0 + i]; }
@@ -2568,15 +2599,7 @@ static int state_list(const sf_sim *s, int32_t n, const int32_t *envs, const voi
     if (n < 0 || (n > 0 && (!envs || !buf))) return fail(SF_EINVAL, "%s: bad argument", who);
     if (device_pointer && ((uintptr_t)buf & 15))      // (the kernels read / write the f64 and u32 sections in place)
         return fail(SF_EINVAL, "%s: a device buffer must be 16-byte aligned", who);
-    std::vector<char> seen(distinct ? (size_t)s->g.E : 0, 0);
-    for (int i = 0; i < n; ++i) {
-        if (envs[i] < 0 || envs[i] >= s->g.E) return fail(SF_EINVAL, "%s: environment %d out of range", who, envs[i]);
-        if (distinct) {
-            if (seen[envs[i]]) return fail(SF_EINVAL, "%s: environment %d is listed twice", who, envs[i]);
-            seen[envs[i]] = 1;
-        }
-    }
-    return SF_OK;
+    return check_envs(s, who, n, envs, distinct ? "is listed twice" : nullptr);
 }
 
 static StateArgs state_args(sf_sim *s)
@@ -2602,25 +2625,12 @@ static int state_chunk(const StateArgs &a, bool device)
 // A call's environment list / host ignitions -> device memory through the pinned buffer, one copy; *dev is where they are.
 static int reset_stage(sf_sim *s, const void *a, size_t na, const void *b, size_t nb, uint8_t **dev)
 {
-    const size_t bytes = na + nb;
-    if (!s->rs_ev) HIPCHK(hipEventCreateWithFlags(&s->rs_ev, hipEventDisableTiming));
-    HIPCHK(hipEventSynchronize(s->rs_ev));             // the last call's copy has left the pinned buffer
-    if (bytes > s->rs_cap) {
-        HIPCHK(hipStreamSynchronize(s->stream));       // (its kernels have used rs_dev)
-        if (s->rs_dev) { HIPCHK(hipFree(s->rs_dev)); s->rs_dev = nullptr; }
-        if (s->rs_pinned) { HIPCHK(hipHostFree(s->rs_pinned)); s->rs_pinned = nullptr; }
-        s->rs_cap = 0;
-        const size_t cap = std::max<size_t>(bytes * 2, 4096);
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&s->rs_dev), cap));
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&s->rs_pinned), cap, hipHostMallocDefault));
-        s->rs_cap = cap;
-    }
-    if (na) memcpy(s->rs_pinned, a, na);
-    if (nb) memcpy(s->rs_pinned + na, b, nb);
-    HIPCHK(hipMemcpyAsync(s->rs_dev, s->rs_pinned, bytes, hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipEventRecord(s->rs_ev, s->stream));
-    *dev = s->rs_dev;
-    return SF_OK;
+    CallBlock &blk = s->rs_blk;
+    { int rc = block_reserve(s, blk, na + nb); if (rc) return rc; }
+    if (na) memcpy(blk.pinned, a, na);
+    if (nb) memcpy(blk.pinned + na, b, nb);
+    *dev = blk.dev;
+    return block_send(s, blk, na + nb);
 }
 
 // The two launches of a batched reset.  envs_dev: the list form's environments (distinct), else the mask form over all of them.
@@ -2631,37 +2641,18 @@ static int reset_launch(sf_sim *s, const int32_t *envs_dev, const uint8_t *mask,
     ResetArgs a;
     memset(&a, 0, sizeof a);
     a.g = g;
-    auto add = [&](void *base, long long stride, long long len) { a.seg[a.n_seg++] = {static_cast<uint8_t *>(base), stride, len}; };
-    if (s->bl_cur) add(s->cells_alloc, g.cells_env, g.cells_env);
-    else {
-        add(s->status, g.plane_env, g.plane_env);
-        add(s->age_alloc, g.age_env * g.ab, g.age_env * g.ab);
-    }
-    add(s->burn, g.plane_env * 8, g.plane_env * 8);
-    if (s->settled) add(s->settled, g.plane_env * 4, g.plane_env * 4);
-    if (s->parents) add(s->parents, g.plane_env, g.plane_env);
-    if (s->snap) add(s->snap, g.plane_env, g.plane_env);
-    const long long fplane = (long long)g.TYp * g.TXp, tiles = (long long)g.TY * g.TX;
-    for (int k = 0; k < 2; ++k) add(s->tflags + (size_t)k * g.E * fplane, fplane, fplane);
-    for (int k = 0; k < 3; ++k) add(s->vbits + (size_t)k * g.E * g.vb_env, g.vb_env * 8, g.vb_env * 8);
     const bool seams = !s->bl_cur && g.ab == 1;       // (the tile bookkeeping is not kept while the blocked plane is current: tiles_valid is false)
-    if (seams) add(s->seam, g.seam_env, g.seam_env);
     // the tile histograms of a reset environment are known (all UNBURNED, the ignition's tile to be recounted) unless every histogram
     // of the handle is marked stale anyway: reset_range's condition for a partial reset
     const bool hist_known = g.ab == 1 && !s->generic && !s->tdirty_all;
-    if (hist_known) {
-        add(s->tdirty, tiles, tiles);
-        add(s->thist, tiles * 16, tiles * 16);
-    }
+    a.n_seg = env_segs(s, kResetKinds & ~(seams ? 0u : kSegSeam) & ~(hist_known ? 0u : kSegHist), a.seg);
     a.envs = envs_dev; a.mask = mask; a.xy = xy_dev; a.n = n;
     a.status = s->status; a.age = s->age; a.cells = s->bl_cur ? s->cells : nullptr;
     a.commit = s->commit; a.tflags = s->tflags; a.ring = s->ring; a.vbits = s->vbits; a.win_hint = s->win_hint;
     a.seam = seams ? s->seam : nullptr;
     a.tdirty = hist_known ? s->tdirty : nullptr;
     a.res_block = s->status_block; a.res_sink = s->sink; a.res_elapsed = s->elapsed_dev;
-    long long longest = 0;
-    for (int k = 0; k < a.n_seg; ++k) longest = std::max(longest, a.seg[k].len);
-    const unsigned gx = (unsigned)std::min<long long>(1024, std::max<long long>(1, (longest / 16 + 2047) / 2048));      // ~8 vectors per lane of the longest slice
+    const unsigned gx = seg_grid_x(a.seg, a.n_seg);
     if (s->rs_timed) HIPCHK(hipEventRecord(s->ev0, s->stream));
     hipLaunchKernelGGL(k_reset_envs, dim3(gx, (unsigned)n), dim3(256), 0, s->stream, a);
     HIPCHK(hipGetLastError());
@@ -2695,8 +2686,8 @@ extern "C" int sf_reset_envs(sf_sim *s, int32_t n, const int32_t *envs, const in
     if (!s) return fail(SF_EINVAL, "sf_reset_envs: null handle");
     if (n < 0 || (n > 0 && (!envs || !xy))) return fail(SF_EINVAL, "sf_reset_envs: bad environment list");
     const Geo &g = s->g;
+    { int rc = check_envs(s, "sf_reset_envs", n, envs); if (rc) return rc; }      // (a repeated environment is accepted: below)
     for (int i = 0; i < n; ++i) {
-        if (envs[i] < 0 || envs[i] >= g.E) return fail(SF_EINVAL, "sf_reset_envs: environment %d out of range", envs[i]);
         if (xy[2 * i] < 0 || xy[2 * i] >= g.W || xy[2 * i + 1] < 0 || xy[2 * i + 1] >= g.H)
             return fail(SF_EINVAL, "sf_reset_envs: ignition (%d, %d) of environment %d is outside the %dx%d grid", xy[2 * i], xy[2 * i + 1],
                         envs[i], g.H, g.W);
@@ -2811,6 +2802,8 @@ extern "C" int sf_load_state(sf_sim *s, int32_t n, const int32_t *envs, const vo
     if (!device_pointer) { int rc = ensure_stage(s, (size_t)chunk * a.stride); if (rc) return rc; }
     const bool per_env_tiles = !s->bl_cur && s->tiles_valid;      // the tile maps / seams are kept: rebuild this environment's
     const bool recount = g.ab == 1 && !s->generic && !s->tdirty_all;
+    EnvSeg seg[kEnvSegs];
+    const int n_seg = env_segs(s, kSegCells | kSegHint, seg);
     for (int i0 = 0; i0 < n; i0 += chunk) {
         const int cnt = std::min(chunk, n - i0);
         a.n = cnt;
@@ -2820,14 +2813,9 @@ extern "C" int sf_load_state(sf_sim *s, int32_t n, const int32_t *envs, const vo
             HIPCHK(hipMemcpyAsync(s->stage, static_cast<const uint8_t *>(in) + (size_t)i0 * a.stride, (size_t)cnt * a.stride, hipMemcpyHostToDevice, s->stream));
             a.blob = static_cast<uint8_t *>(s->stage);
         }
-        for (int i = 0; i < cnt; ++i) {      // the cell planes start from zero: guard rows / quads and the pitch padding stay zero
+        for (int i = 0; i < cnt; ++i) {      // the cell planes start from zero: guard rows / quads and the pitch padding stay zero; so does the window advice (about a fire that is not there)
             const int e = a.env[i];
-            if (s->bl_cur) HIPCHK(hipMemsetAsync(s->cells_alloc + (size_t)e * g.cells_env, 0, (size_t)g.cells_env, s->stream));
-            else {
-                HIPCHK(hipMemsetAsync(s->status + (size_t)e * g.plane_env, 0, (size_t)g.plane_env, s->stream));
-                HIPCHK(hipMemsetAsync(s->age_alloc + (size_t)e * g.age_env * g.ab, 0, (size_t)g.age_env * g.ab, s->stream));
-            }
-            HIPCHK(hipMemsetAsync(s->win_hint + e, 0, sizeof(unsigned long long), s->stream));      // (advice about a fire that is not there)
+            for (int k = 0; k < n_seg; ++k) HIPCHK(hipMemsetAsync(seg[k].base + e * seg[k].stride, 0, (size_t)seg[k].len, s->stream));
             if (recount) HIPCHK(hipMemsetAsync(s->tdirty + (size_t)e * g.TY * g.TX, 1, (size_t)g.TY * g.TX, s->stream));
         }
         hipLaunchKernelGGL(k_state_unpack, dim3((unsigned)((g.P + 255) / 256), (unsigned)g.H, (unsigned)cnt), dim3(256), 0, s->stream, a);
@@ -3125,8 +3113,7 @@ extern "C" int sf_observe(sf_sim *s, const sf_obs_params *p, int32_t n, const in
     if (agents && p->agents && (p->agents_k < 0 || p->agents_k > SF_OBS_MAX_AGENTS))
         return fail(SF_EINVAL, "sf_observe: %d agents per environment (0..%d)", p->agents_k, SF_OBS_MAX_AGENTS);
     if ((uintptr_t)device_out & (p->dtype ? 1 : 3)) return fail(SF_EINVAL, "sf_observe: the output is not aligned to its element");
-    for (int i = 0; i < n; ++i)
-        if (envs[i] < 0 || envs[i] >= g.E) return fail(SF_EINVAL, "sf_observe: environment %d out of range", envs[i]);
+    { int rc = check_envs(s, "sf_observe", n, envs); if (rc) return rc; }
     if (n == 0) return SF_OK;
     if (attr && !s->have_rt) return fail(SF_ESTATE, "sf_observe: attribute channels need the layers (sf_set_layers)");
     HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
@@ -3141,18 +3128,8 @@ extern "C" int sf_observe(sf_sim *s, const sf_obs_params *p, int32_t n, const in
     const bool cen_host = crop && !p->centers_device, ag_host = k > 0 && !p->agents_device;
     const size_t o_ag = o_cen + (cen_host ? ((size_t)n * 8 + 15) / 16 * 16 : 0);
     const size_t bytes = o_ag + (ag_host ? (size_t)n * k * 12 : 0);
-    if (!s->obs_ev) HIPCHK(hipEventCreateWithFlags(&s->obs_ev, hipEventDisableTiming));
-    HIPCHK(hipEventSynchronize(s->obs_ev));            // the last call's copy has left the pinned buffer (and its kernel used obs_dev)
-    if (bytes > s->obs_cap) {
-        HIPCHK(hipStreamSynchronize(s->stream));
-        if (s->obs_dev) { HIPCHK(hipFree(s->obs_dev)); s->obs_dev = nullptr; }
-        if (s->obs_pinned) { HIPCHK(hipHostFree(s->obs_pinned)); s->obs_pinned = nullptr; }
-        s->obs_cap = 0;
-        const size_t cap = std::max<size_t>(bytes * 2, 4096);
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&s->obs_dev), cap));
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&s->obs_pinned), cap, hipHostMallocDefault));
-        s->obs_cap = cap;
-    }
+    CallBlock &blk = s->obs_blk;
+    { int rc = block_reserve(s, blk, bytes); if (rc) return rc; }
     ObsHead h;
     memset(&h, 0, sizeof h);
     for (int c = 0; c < C; ++c) { h.code[c] = p->channels[c]; h.mode[c] = p->pool_mode[c]; }
@@ -3160,12 +3137,11 @@ extern "C" int sf_observe(sf_sim *s, const sf_obs_params *p, int32_t n, const in
     // supported_attributes (simulation.py:317-332)
     const double lo[7] = {0.0, 1.0, 0.2, 0.12, -282.0, 0.0, 0.0}, hi[7] = {1.0, 3500.0, 6.0, 1.0, 11000.0, 250.0, 360.0};
     for (int a = 0; a < 7; ++a) { h.lo[a] = lo[a]; h.span[a] = hi[a] - lo[a]; }
-    memcpy(s->obs_pinned, &h, sizeof h);
-    memcpy(s->obs_pinned + o_envs, envs, (size_t)n * 4);
-    if (cen_host) memcpy(s->obs_pinned + o_cen, p->centers, (size_t)n * 8);
-    if (ag_host) memcpy(s->obs_pinned + o_ag, p->agents, (size_t)n * k * 12);
-    HIPCHK(hipMemcpyAsync(s->obs_dev, s->obs_pinned, bytes, hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipEventRecord(s->obs_ev, s->stream));
+    memcpy(blk.pinned, &h, sizeof h);
+    memcpy(blk.pinned + o_envs, envs, (size_t)n * 4);
+    if (cen_host) memcpy(blk.pinned + o_cen, p->centers, (size_t)n * 8);
+    if (ag_host) memcpy(blk.pinned + o_ag, p->agents, (size_t)n * k * 12);
+    { int rc = block_send(s, blk, bytes); if (rc) return rc; }
 
     ObsArgs a;
     memset(&a, 0, sizeof a);
@@ -3174,10 +3150,10 @@ extern "C" int sf_observe(sf_sim *s, const sf_obs_params *p, int32_t n, const in
     a.cells = s->bl_cur ? s->cells : nullptr;
     a.lay = s->lay_all;
     a.lay_tab = s->rt_set.size() > 1 ? 7LL * g.H * g.W : 0;
-    a.head = reinterpret_cast<const ObsHead *>(s->obs_dev);
-    a.envs = reinterpret_cast<const int32_t *>(s->obs_dev + o_envs);
-    a.centers = !crop ? nullptr : (cen_host ? reinterpret_cast<const int32_t *>(s->obs_dev + o_cen) : p->centers);
-    a.agents = k == 0 ? nullptr : (ag_host ? reinterpret_cast<const int32_t *>(s->obs_dev + o_ag) : p->agents);
+    a.head = reinterpret_cast<const ObsHead *>(blk.dev);
+    a.envs = reinterpret_cast<const int32_t *>(blk.dev + o_envs);
+    a.centers = !crop ? nullptr : (cen_host ? reinterpret_cast<const int32_t *>(blk.dev + o_cen) : p->centers);
+    a.agents = k == 0 ? nullptr : (ag_host ? reinterpret_cast<const int32_t *>(blk.dev + o_ag) : p->agents);
     a.out = device_out;
     a.n = n; a.C = C; a.f = f; a.ch = eh; a.cw = ew; a.oh = oh; a.ow = ow; a.k = k;
     a.TX = tl.TX; a.TY = tl.TY; a.tiles_x = (int)tiles_x; a.stride = tl.stride;
@@ -3233,8 +3209,7 @@ extern "C" int sf_render(sf_sim *s, const sf_render_params *p, int32_t n, const 
     const int k = p->agents ? p->agents_k : 0;
     if (p->agents && (p->agents_k < 0 || p->agents_k > SF_RENDER_MAX_AGENTS))
         return fail(SF_EINVAL, "sf_render: %d agents per environment (0..%d)", p->agents_k, SF_RENDER_MAX_AGENTS);
-    for (int i = 0; i < n; ++i)
-        if (envs[i] < 0 || envs[i] >= g.E) return fail(SF_EINVAL, "sf_render: environment %d out of range", envs[i]);
+    { int rc = check_envs(s, "sf_render", n, envs); if (rc) return rc; }
     const int s_ = p->scale, oh = (g.H + s_ - 1) / s_, ow = (g.W + s_ - 1) / s_;
     const bool cl = p->channels_last != 0;
     const RenderTile tl = render_tile(g, s_, oh, ow, cl);
@@ -3274,24 +3249,13 @@ extern "C" int sf_render(sf_sim *s, const sf_render_params *p, int32_t n, const 
     const bool ag_host = k > 0 && !p->agents_device;
     const size_t o_tabs = up16((size_t)n * 4), o_fb = o_tabs + up16((size_t)nt * 4), o_mm = o_fb + up16((size_t)nt * 4);
     const size_t o_ag = o_mm + (size_t)nt * 16, bytes = o_ag + (ag_host ? (size_t)n * k * 12 : 0);
-    if (!s->rd_ev) HIPCHK(hipEventCreateWithFlags(&s->rd_ev, hipEventDisableTiming));
-    HIPCHK(hipEventSynchronize(s->rd_ev));             // the last call's copy has left the pinned buffer (and its kernels used rd_dev)
-    if (bytes > s->rd_cap) {
-        HIPCHK(hipStreamSynchronize(s->stream));
-        if (s->rd_dev) { HIPCHK(hipFree(s->rd_dev)); s->rd_dev = nullptr; }
-        if (s->rd_pinned) { HIPCHK(hipHostFree(s->rd_pinned)); s->rd_pinned = nullptr; }
-        s->rd_cap = 0;
-        const size_t cap = std::max<size_t>(bytes * 2, 4096);
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&s->rd_dev), cap));
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&s->rd_pinned), cap, hipHostMallocDefault));
-        s->rd_cap = cap;
-    }
-    memcpy(s->rd_pinned, envs, (size_t)n * 4);
-    if (nt) { memcpy(s->rd_pinned + o_tabs, tabs.data(), (size_t)nt * 4); memcpy(s->rd_pinned + o_fb, fb.data(), (size_t)nt * 4); }
-    if (ag_host) memcpy(s->rd_pinned + o_ag, p->agents, (size_t)n * k * 12);
-    HIPCHK(hipMemcpyAsync(s->rd_dev, s->rd_pinned, o_mm, hipMemcpyHostToDevice, s->stream));
-    if (ag_host) HIPCHK(hipMemcpyAsync(s->rd_dev + o_ag, s->rd_pinned + o_ag, (size_t)n * k * 12, hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipEventRecord(s->rd_ev, s->stream));
+    CallBlock &blk = s->rd_blk;
+    { int rc = block_reserve(s, blk, bytes); if (rc) return rc; }
+    memcpy(blk.pinned, envs, (size_t)n * 4);
+    if (nt) { memcpy(blk.pinned + o_tabs, tabs.data(), (size_t)nt * 4); memcpy(blk.pinned + o_fb, fb.data(), (size_t)nt * 4); }
+    if (ag_host) memcpy(blk.pinned + o_ag, p->agents, (size_t)n * k * 12);
+    // (the lists, and the agents behind the min / max words: those are the kernels' to write)
+    { int rc = block_send(s, blk, o_mm, o_ag, ag_host ? (size_t)n * k * 12 : 0); if (rc) return rc; }
 
     if (nt) {
         RenderBgArgs b;
@@ -3299,9 +3263,9 @@ extern "C" int sf_render(sf_sim *s, const sf_render_params *p, int32_t n, const 
         b.H = g.H; b.W = g.W;
         b.lay = s->lay_all; b.lay_tab = 7LL * g.H * g.W;
         b.fuel_ix = s->rd_fuel_ix;
-        b.tabs = reinterpret_cast<const int32_t *>(s->rd_dev + o_tabs);
-        b.fbfm = reinterpret_cast<const int32_t *>(s->rd_dev + o_fb);
-        b.mm = reinterpret_cast<double *>(s->rd_dev + o_mm);
+        b.tabs = reinterpret_cast<const int32_t *>(blk.dev + o_tabs);
+        b.fbfm = reinterpret_cast<const int32_t *>(blk.dev + o_fb);
+        b.mm = reinterpret_cast<double *>(blk.dev + o_mm);
         b.bg = s->rd_bg;
         b.base = (uint32_t)(s->rd_rgb < 0 ? rgb : s->rd_rgb);
         for (int c = 0; c < kRdFbfmColours; ++c) {
@@ -3324,8 +3288,8 @@ extern "C" int sf_render(sf_sim *s, const sf_render_params *p, int32_t n, const 
     a.cap = s->history_cap; a.first = hist ? p->first : 0; a.count = count;
     a.bg = s->rd_bg;
     a.bg_tab = n_tab > 1 ? (long long)g.H * g.W : 0;
-    a.envs = reinterpret_cast<const int32_t *>(s->rd_dev);
-    a.agents = k == 0 ? nullptr : (ag_host ? reinterpret_cast<const int32_t *>(s->rd_dev + o_ag) : p->agents);
+    a.envs = reinterpret_cast<const int32_t *>(blk.dev);
+    a.agents = k == 0 ? nullptr : (ag_host ? reinterpret_cast<const int32_t *>(blk.dev + o_ag) : p->agents);
     a.out = static_cast<uint8_t *>(device_out);
     a.n_frames = (int)frames; a.k = k;
     a.s = s_; a.mode = p->mode; a.white = p->background == SF_RENDER_WHITE; a.contours = p->contours; a.cl = cl;

@@ -125,3 +125,44 @@ def test_reset_with_a_list_is_one_engine_call():
         sim.reset([0, 2])
     with pytest.raises(ValueError):
         sim.reset_done()
+
+
+def test_segment_capacity_covers_the_largest_selection():
+    """The slice table (``env_segs``, simfire_hip.hip) against the capacity of the kernel arguments that carry a selection of it
+    (``kEnvSegs``, sf_env_segs.h), from the source text: every ``add(kind, ...)`` of the table counted by kind - the loops by their
+    trip counts, the cells of the current layout by the larger branch - and summed over the kinds a fork and a batched reset name."""
+    csrc = os.path.join(ROOT, "simfire_amd", "csrc")
+    header = open(os.path.join(csrc, "sf_env_segs.h")).read()
+    host = open(os.path.join(csrc, "simfire_hip.hip")).read()
+    kinds = re.findall(r"^\s*(kSeg\w+) = 1u << \d+,", header, re.M)
+    assert len(kinds) == len(set(kinds)) >= 14
+    cap = int(re.search(r"constexpr int kEnvSegs = (\d+);", header).group(1))
+    body = re.search(r"static int env_segs\(.*?\n\{\n(.*?)\n\}\n", host, re.S).group(1)
+    count = dict.fromkeys(kinds, 0)
+    branch = []                                          # slices of kSegCells on each side of the layout branch
+    for line in body.splitlines():
+        m = re.search(r"\badd\((kSeg\w+),", line)
+        if not m or "auto add" in line:
+            continue
+        loop = re.search(r"for \(int k = 0; k < (\d+); \+\+k\)", line)
+        if m.group(1) == "kSegCells":
+            branch.append(line)
+        else:
+            count[m.group(1)] += int(loop.group(1)) if loop else 1
+    assert len(branch) == 3 and "bl_cur" in branch[0]    # the blocked plane | status + the sprite-mask plane
+    count["kSegCells"] = 2
+    assert all(count.values()), count                    # every kind has a slice
+    assert len(re.findall(r"\badd\(", host)) == len(re.findall(r"\badd\(kSeg", body))          # (no second table beside it)
+
+    def selection(name):
+        expr = re.search(r"constexpr unsigned %s = ([^;]*);" % name, header).group(1)
+        names = [k.strip() for k in expr.split("|")]
+        assert set(names) <= set(kinds) and len(names) == len(set(names)), names
+        return sum(count[k] for k in names)
+
+    fork, reset = selection("kForkKinds"), selection("kResetKinds")
+    assert (fork, reset) == (22, 14)
+    assert sum(count.values()) == 23                     # (the fork leaves out snap)
+    assert max(fork, reset) <= cap
+    for arg in (r"struct CopyList \{\s*EnvSeg seg\[kEnvSegs\];", r"EnvSeg seg\[kEnvSegs\];\s*// the slices to zero"):
+        assert re.search(arg, open(os.path.join(csrc, "sf_state_kernels.h")).read() + open(os.path.join(csrc, "sf_reset_kernels.h")).read())
