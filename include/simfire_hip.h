@@ -300,6 +300,60 @@ typedef struct sf_obs_params {
  * (the tensor is complete when the handle's stream has got there); the caller orders its own work on device_out before the call. */
 int sf_observe(sf_sim *sim, const sf_obs_params *params, int32_t n, const int32_t *envs, void *device_out);
 
+/* Agents on the device: K agents per environment that walk the grid and draw control lines where they stand,
+ * stepped from a policy's action tensor without a host read.  The reference records agent positions only (simulation.py:480-499) and
+ * leaves the loop to the harness (the run docstring, 505-509); the semantics are this library's own.
+ * Action word a = move + 5 * interact (int32): move 0 stay, 1 row - 1, 2 row + 1, 3 column - 1, 4 column + 1; interact 0 none,
+ * 1 FIRELINE, 2 SCRATCHLINE, 3 WETLINE; any value outside 0..19 is (stay, none).
+ * One sf_agents_step for environment e, r0 its result row (sf_get_status) before the tick:
+ *   r0[0] != 1: the agents make no move and emit no point, terms = 0, done = 1, reward = 0, and steps a - d do not touch the episode
+ *         statistics.  Being done, the environment still goes through e and f: final_len / final_ret report the statistics as they
+ *         stand (without auto_reset the same stale values on every tick until the caller resets it and places its agents anew), and
+ *         with auto_reset it is reset, its agents go back to their start cells and its statistics are cleared in this same tick.
+ *   else  a. each agent moves; a move that would leave the grid does not happen and counts in terms[3]; agents may share a cell
+ *         b. an agent with interact != 0 emits (column, row, type) at its NEW cell - with only_unburned only if that cell is UNBURNED
+ *            before this tick's points; emitted points count in terms[1]; precedence on one cell is sf_apply_mitigation's
+ *         c. update_mitigation(points of e); run(n_updates)          (sf_step_mitigated for the first update, sf_step for the rest)
+ *         d. r1 the row afterwards: terms[0] = (r1[3] + r1[4]) - (r0[3] + r0[4]); terms[2] = agents whose cell is BURNING now;
+ *            reward = (float)(w[0] * terms[0] + w[1] * terms[1] + w[2] * terms[2] + w[3] * terms[3]) evaluated in double, left to right;
+ *            episode length += 1, episode return += (double)reward;
+ *            done = r1[0] != 1 || (done_on_burn && terms[2] > 0) || (max_ticks > 0 && episode length >= max_ticks)
+ *   e. outputs: reward, done, terms, and for done environments final_len / final_ret (the episode's length and return; else 0)
+ *   f. with auto_reset every done environment is reset as by sf_reset_where(done, the ignitions given to sf_agents_create), its
+ *      agents go back to their start cells and its episode statistics are cleared; without it nothing is reset.
+ * Nothing is read back: in async mode the call only enqueues, otherwise it waits once at its end.  The agent buffers belong to
+ * the handle, not to an environment's state: sf_copy_envs and sf_save_state / sf_load_state do not carry them.  With
+ * sf_set_prune_after_quit an environment that QUIT on the runtime check is still pruned by the updates of step c. */
+typedef struct sf_agent_params {
+    int32_t k;                  /* agents per environment, 1..64 (the bound of sf_loop_start); 0 frees the agent buffers      */
+    int32_t n_updates;          /* update() calls per tick, >= 1                                                             */
+    int32_t only_unburned;      /* 1: a line is drawn on UNBURNED cells only; 0: always (also on a BURNING cell)             */
+    int32_t done_on_burn;       /* 1: an agent standing in the fire ends the episode                                         */
+    int32_t max_ticks;          /* > 0: the episode ends after this many ticks                                               */
+    int32_t auto_reset;         /* 1: done environments start a new episode inside the call                                  */
+    float w[4];                 /* reward weights of terms[0..3]                                                             */
+} sf_agent_params;
+typedef struct sf_agent_out {   /* device memory, any may be NULL                                                            */
+    float *reward;              /* [n_envs]                                                                                  */
+    uint8_t *done;              /* [n_envs]                                                                                  */
+    int32_t *terms;             /* [n_envs][4]: newly BURNING + BURNED cells, points emitted, agents in the fire, blocked moves */
+    int32_t *final_len;         /* [n_envs]                                                                                  */
+    double *final_ret;          /* [n_envs]                                                                                  */
+} sf_agent_out;
+/* Allocates the agent state (all agents at (0, 0), ids 1..k, start cells (0, 0)); called again it replaces the state, k = 0 frees
+ * it.  ignitions_xy: int32 [n_envs][2] host, where a done environment re-ignites (unused, may be NULL, without auto_reset).  k or
+ * n_updates out of range or an ignition off the grid: SF_EINVAL. */
+int sf_agents_create(sf_sim *sim, const sf_agent_params *params, const int32_t *ignitions_xy /* [n_envs][2] host */);
+/* The k agents of environment envs[i] stand at xy[i] (int32 [n][k][2] = (column, row), host arrays); an environment named twice
+ * keeps its last entry.  also_start != 0: these cells also become the environment's start cells and its episode statistics are
+ * cleared (a new episode).  An environment out of range or a cell off the grid is SF_EINVAL before anything is enqueued. */
+int sf_agents_place(sf_sim *sim, int32_t n, const int32_t *envs, const int32_t *xy /* [n][k][2] host */, int32_t also_start);
+/* One tick (above).  device_actions: int32 [n_envs][k] in device memory; out may be NULL.  Before sf_agents_create: SF_ESTATE. */
+int sf_agents_step(sf_sim *sim, const int32_t *device_actions /* [n_envs][k] */, const sf_agent_out *out);
+/* The positions, int32 [n_envs][k][3] = (column, row, id = j + 1) in device memory: what sf_observe / sf_render take as agents
+ * (agents_device = 1).  The address holds until the next sf_agents_create. */
+int sf_agents_device(sf_sim *sim, void **xyid /* int32 [n_envs][k][3] */);
+
 /* Frames of environments: what the reference's screen shows (simfire/game/game.py:117-131: the terrain image,
  * sprites.py:105-160 with the burned paint, the fire / line / agent sprites of sprites.py:20-203 in SpriteLayer order, enums.py:88-103)
  * as uint8 RGB, one pixel per cell, downscaled by an integer factor, written by ONE launch into caller-owned device memory.  It replaces

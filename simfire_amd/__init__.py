@@ -5,5 +5,6 @@ manager update + rate-of-spread formula as HIP kernels, and the host-side mirror
 reference classes that call it.
 """
 from .enums import BurnStatus, GameStatus, RoSAttenuation  # noqa: F401
+from .vecenv import BatchedFireEnv  # noqa: F401
 
-__all__ = ["BurnStatus", "GameStatus", "RoSAttenuation"]
+__all__ = ["BurnStatus", "GameStatus", "RoSAttenuation", "BatchedFireEnv"]

@@ -65,6 +65,18 @@ class SfRenderParams(C.Structure):
                 ("agents_k", C.c_int32), ("agents_device", C.c_int32), ("agents", C.c_void_p)]
 
 
+class SfAgentParams(C.Structure):
+    """``sf_agent_params`` (include/simfire_hip.h)."""
+    _fields_ = [("k", C.c_int32), ("n_updates", C.c_int32), ("only_unburned", C.c_int32), ("done_on_burn", C.c_int32),
+                ("max_ticks", C.c_int32), ("auto_reset", C.c_int32), ("w", C.c_float * 4)]
+
+
+class SfAgentOut(C.Structure):
+    """``sf_agent_out`` (include/simfire_hip.h): device pointers, any may be null."""
+    _fields_ = [("reward", C.c_void_p), ("done", C.c_void_p), ("terms", C.c_void_p), ("final_len", C.c_void_p),
+                ("final_ret", C.c_void_p)]
+
+
 # name -> argtypes; every function returns int except the two string getters
 _VP, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
 SIGNATURES = {
@@ -87,6 +99,10 @@ SIGNATURES = {
     "sf_reset_env": [_VP, _I32, _I32, _I32],
     "sf_reset_envs": [_VP, _I32, _VP, _VP],
     "sf_reset_where": [_VP, _VP, _VP, _I32],
+    "sf_agents_create": [_VP, C.POINTER(SfAgentParams), _VP],
+    "sf_agents_place": [_VP, _I32, _VP, _VP, _I32],
+    "sf_agents_step": [_VP, _VP, C.POINTER(SfAgentOut)],
+    "sf_agents_device": [_VP, C.POINTER(_VP)],
     "sf_time_resets": [_VP, _I32],
     "sf_get_reset_ms": [_VP, C.POINTER(C.c_float)],
     "sf_apply_mitigation": [_VP, _VP, _I32],

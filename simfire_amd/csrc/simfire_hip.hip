@@ -105,6 +105,7 @@ extern "C" const char *sf_version(void) { return "simfire_hip 0.2 (gfx950)"; }  
 #include "sf_obs_kernels.h"
 #include "sf_render_kernels.h"
 #include "sf_gen_kernels.h"
+#include "sf_agent_kernels.h"
 
 // Launch-geometry knobs of a handle (sf_set_tuning, include/simfire_hip_lab.h: SF_TUNE_*).  Results never depend on them; the
 // defaults are the measured choices of NOTEBOOK.md 5.  The library does not read the environment for them (the measurement scripts under
@@ -251,6 +252,17 @@ struct sf_sim {
     CallBlock rs_blk;                  // sf_reset_envs / sf_reset_where: the environment list and host ignitions of a call
     bool rs_timed = false, rs_have_ms = false;   // sf_time_resets: ev0 / ev1 recorded around the launches of every batched reset
     CallBlock gen_blk;                 // sf_generate_layers: its descriptors + environment list
+    // sf_agents_* (DESIGN.md section 16): the parameters of sf_agents_create (ag.k == 0: no agent state), ONE device allocation that
+    // holds every agent buffer - positions, start cells, this tick's points, the counts and episode statistics between the two
+    // kernels of a tick, the done mask, the ignitions of a new episode - and the call block of sf_agents_place.  Not slices of
+    // env_segs: fork, snapshot and restore do not carry agents.
+    sf_agent_params ag = {};
+    uint8_t *ag_mem = nullptr;
+    size_t ag_bytes = 0;
+    int32_t *ag_xyid = nullptr, *ag_start = nullptr, *ag_points = nullptr, *ag_prev = nullptr, *ag_terms = nullptr, *ag_len = nullptr, *ag_ign = nullptr;
+    double *ag_ret = nullptr;
+    uint8_t *ag_done = nullptr;
+    CallBlock ag_blk;
     bool have_rt = false, was_reset = false, counters_on = false;
     int seq = 0;                       // index (mod 6) of the next step launch
     Tuning tune;                       // sf_set_tuning
@@ -475,8 +487,8 @@ extern "C" int sf_destroy(sf_sim *s)
                     s->status_block, s->elapsed_dev, s->stage, s->parents};
     if (s->status_pinned) (void)hipHostFree(s->status_pinned);
     if (s->delta_pinned) (void)hipHostFree(s->delta_pinned);
-    for (void *dp : {(void *)s->snap, (void *)s->delta_dev, (void *)s->rd_bg, (void *)s->rd_fuel_ix}) if (dp) (void)hipFree(dp);
-    for (CallBlock *b : {&s->obs_blk, &s->rd_blk, &s->rs_blk, &s->gen_blk}) {
+    for (void *dp : {(void *)s->snap, (void *)s->delta_dev, (void *)s->rd_bg, (void *)s->rd_fuel_ix, (void *)s->ag_mem}) if (dp) (void)hipFree(dp);
+    for (CallBlock *b : {&s->obs_blk, &s->rd_blk, &s->rs_blk, &s->gen_blk, &s->ag_blk}) {
         if (b->dev) (void)hipFree(b->dev);
         if (b->pinned) (void)hipHostFree(b->pinned);
         if (b->ev) (void)hipEventDestroy(b->ev);
@@ -2726,6 +2738,158 @@ extern "C" int sf_reset_where(sf_sim *s, const uint8_t *device_mask, const int32
     // delta query of every environment hands back the whole map once
     if (s->snap) std::fill(s->snap_valid.begin(), s->snap_valid.end(), 0);
     if (!s->async) HIPCHK(hipStreamSynchronize(s->stream));
+    return SF_OK;
+}
+
+// ----------------------------------------------------------------------------- agents
+static int agents_free(sf_sim *s)
+{
+    if (s->ag_mem) {
+        HIPCHK(hipStreamSynchronize(s->stream));      // (enqueued ticks may still use the buffers)
+        HIPCHK(hipFree(s->ag_mem));
+        s->bytes -= (int64_t)s->ag_bytes;
+    }
+    s->ag_mem = nullptr; s->ag_bytes = 0;
+    s->ag_xyid = s->ag_start = s->ag_points = s->ag_prev = s->ag_terms = s->ag_len = s->ag_ign = nullptr;
+    s->ag_ret = nullptr; s->ag_done = nullptr;
+    memset(&s->ag, 0, sizeof s->ag);
+    return SF_OK;
+}
+
+extern "C" int sf_agents_create(sf_sim *s, const sf_agent_params *p, const int32_t *ignitions_xy)
+{
+    if (!s || !p) return fail(SF_EINVAL, "sf_agents_create: null argument");
+    const Geo &g = s->g;
+    if (p->k < 0 || p->k > kAgentsMax) return fail(SF_EINVAL, "sf_agents_create: %d agents per environment (1..%d; 0 frees)", p->k, kAgentsMax);
+    if (p->k > 0) {
+        if (p->n_updates < 1) return fail(SF_EINVAL, "sf_agents_create: n_updates = %d must be >= 1", p->n_updates);
+        if (p->max_ticks < 0) return fail(SF_EINVAL, "sf_agents_create: max_ticks = %d must be >= 0", p->max_ticks);
+        if (p->auto_reset && !ignitions_xy) return fail(SF_EINVAL, "sf_agents_create: auto_reset needs the ignitions");
+        for (int e = 0; ignitions_xy && e < g.E; ++e)
+            if (ignitions_xy[2 * e] < 0 || ignitions_xy[2 * e] >= g.W || ignitions_xy[2 * e + 1] < 0 || ignitions_xy[2 * e + 1] >= g.H)
+                return fail(SF_EINVAL, "sf_agents_create: ignition (%d, %d) of environment %d is outside the %dx%d grid", ignitions_xy[2 * e],
+                            ignitions_xy[2 * e + 1], e, g.H, g.W);
+    }
+    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
+    { int rc = agents_free(s); if (rc) return rc; }
+    if (p->k == 0) return SF_OK;
+    // one allocation, every buffer on a 16-byte boundary: xyid | start | points | prev | terms | len | ign | ret | done
+    const size_t E = (size_t)g.E, K = (size_t)p->k;
+    const size_t sizes[9] = {E * K * 12, E * K * 8, E * K * 12, E * 4, E * 16, E * 4, E * 8, E * 8, E};
+    size_t off[9], total = 0;
+    for (int i = 0; i < 9; ++i) { off[i] = total; total += (sizes[i] + 15) / 16 * 16; }
+    HIPCHK(hipMalloc(reinterpret_cast<void **>(&s->ag_mem), total));
+    s->ag_bytes = total; s->bytes += (int64_t)total;
+    int32_t **ip[7] = {&s->ag_xyid, &s->ag_start, &s->ag_points, &s->ag_prev, &s->ag_terms, &s->ag_len, &s->ag_ign};
+    for (int i = 0; i < 7; ++i) *ip[i] = reinterpret_cast<int32_t *>(s->ag_mem + off[i]);
+    s->ag_ret = reinterpret_cast<double *>(s->ag_mem + off[7]);
+    s->ag_done = s->ag_mem + off[8];
+    std::vector<uint8_t> h(total, 0);
+    int32_t *xyid = reinterpret_cast<int32_t *>(h.data() + off[0]);
+    for (size_t i = 0; i < E * K; ++i) xyid[3 * i + 2] = (int32_t)(i % K) + 1;
+    if (ignitions_xy) memcpy(h.data() + off[6], ignitions_xy, E * 8);
+    HIPCHK(hipMemcpyAsync(s->ag_mem, h.data(), total, hipMemcpyHostToDevice, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));          // (h is pageable and leaves scope)
+    s->ag = *p;
+    return SF_OK;
+}
+
+extern "C" int sf_agents_place(sf_sim *s, int32_t n, const int32_t *envs, const int32_t *xy, int32_t also_start)
+{
+    if (!s) return fail(SF_EINVAL, "sf_agents_place: null handle");
+    if (!s->ag.k) return fail(SF_ESTATE, "sf_agents_place: call sf_agents_create first");
+    if (n < 0 || (n > 0 && (!envs || !xy))) return fail(SF_EINVAL, "sf_agents_place: bad environment list");
+    const Geo &g = s->g;
+    const int K = s->ag.k;
+    { int rc = check_envs(s, "sf_agents_place", n, envs); if (rc) return rc; }
+    for (long long i = 0; i < (long long)n * K; ++i)
+        if (xy[2 * i] < 0 || xy[2 * i] >= g.W || xy[2 * i + 1] < 0 || xy[2 * i + 1] >= g.H)
+            return fail(SF_EINVAL, "sf_agents_place: cell (%d, %d) of agent %d of environment %d is outside the %dx%d grid", xy[2 * i],
+                        xy[2 * i + 1], (int)(i % K), envs[i / K], g.H, g.W);
+    if (n == 0) return SF_OK;
+    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
+    // an environment named twice keeps its last entry: no two threads of the launch write one agent
+    std::vector<int32_t> last((size_t)g.E, -1), keep;
+    for (int i = 0; i < n; ++i) last[envs[i]] = i;
+    for (int i = 0; i < n; ++i) if (last[envs[i]] == i) keep.push_back(i);
+    const int m = (int)keep.size();
+    // the call block: envs [m] | xy [m][K][2]
+    const size_t o_xy = ((size_t)m * 4 + 15) / 16 * 16, bytes = o_xy + (size_t)m * K * 8;
+    CallBlock &blk = s->ag_blk;
+    { int rc = block_reserve(s, blk, bytes); if (rc) return rc; }
+    for (int i = 0; i < m; ++i) {
+        reinterpret_cast<int32_t *>(blk.pinned)[i] = envs[keep[i]];
+        memcpy(blk.pinned + o_xy + (size_t)i * K * 8, xy + (size_t)keep[i] * K * 2, (size_t)K * 8);
+    }
+    { int rc = block_send(s, blk, bytes); if (rc) return rc; }
+    hipLaunchKernelGGL(k_agents_place, dim3((unsigned)((m * K + 255) / 256)), dim3(256), 0, s->stream, m, K,
+                       reinterpret_cast<const int32_t *>(blk.dev), reinterpret_cast<const int32_t *>(blk.dev + o_xy), also_start != 0 ? 1 : 0,
+                       s->ag_xyid, s->ag_start, s->ag_len, s->ag_ret);
+    HIPCHK(hipGetLastError());
+    if (!s->async) HIPCHK(hipStreamSynchronize(s->stream));
+    return SF_OK;
+}
+
+extern "C" int sf_agents_device(sf_sim *s, void **xyid)
+{
+    if (!s || !xyid) return fail(SF_EINVAL, "sf_agents_device: null argument");
+    if (!s->ag.k) return fail(SF_ESTATE, "sf_agents_device: call sf_agents_create first");
+    *xyid = s->ag_xyid;
+    return SF_OK;
+}
+
+static AgentArgs agent_args(const sf_sim *s, const int32_t *actions, const sf_agent_out *out)
+{
+    AgentArgs a;
+    memset(&a, 0, sizeof a);
+    a.g = s->g;
+    a.status = s->status;
+    a.cells = s->bl_cur ? s->cells : nullptr;        // (whichever plane is current NOW: the step between the two kernels may change it)
+    a.rows = s->status_block;
+    a.actions = actions;
+    a.xyid = s->ag_xyid; a.start = s->ag_start; a.points = s->ag_points; a.prev_cnt = s->ag_prev; a.terms = s->ag_terms;
+    a.ep_len = s->ag_len; a.ep_ret = s->ag_ret; a.done = s->ag_done;
+    a.K = s->ag.k; a.only_unburned = s->ag.only_unburned != 0; a.done_on_burn = s->ag.done_on_burn != 0;
+    a.max_ticks = s->ag.max_ticks; a.auto_reset = s->ag.auto_reset != 0;
+    for (int i = 0; i < 4; ++i) a.w[i] = (double)s->ag.w[i];
+    if (out) { a.o_reward = out->reward; a.o_done = out->done; a.o_terms = out->terms; a.o_len = out->final_len; a.o_ret = out->final_ret; }
+    return a;
+}
+
+// One tick for every environment, nothing read back: result rows -> k_agents_act -> the step calls as they stand (one update with
+// the device points, then the plain step path) -> result rows -> k_agents_finish -> the batched reset with the done mask.
+extern "C" int sf_agents_step(sf_sim *s, const int32_t *device_actions, const sf_agent_out *out)
+{
+    if (!s) return fail(SF_EINVAL, "sf_agents_step: null handle");
+    if (!s->ag.k) return fail(SF_ESTATE, "sf_agents_step: call sf_agents_create first");
+    if (!device_actions) return fail(SF_EINVAL, "sf_agents_step: null actions");
+    if (!s->have_rt) return fail(SF_ESTATE, "sf_agents_step: call sf_set_layers or sf_set_rtable first");
+    const Geo &g = s->g;
+    { int rc = state_entry(s, "sf_agents_step"); if (rc) return rc; }
+    const bool was_async = s->async;
+    s->async = true;                                 // (every piece below only enqueues: the one wait is at the end)
+    int rc = update_status_async(s, nullptr);        // r0: the rows as a status query leaves them
+    if (!rc) {
+        hipLaunchKernelGGL(k_agents_act, dim3((unsigned)g.E), dim3(kAgentsMax), 0, s->stream, agent_args(s, device_actions, out));
+        rc = sf_step_mitigated(s, 1, s->ag_points, s->ag.k, 1, nullptr);
+    }
+    if (!rc && s->ag.n_updates > 1) rc = step_impl(s, s->ag.n_updates - 1, nullptr);
+    if (!rc) rc = update_status_async(s, nullptr);   // r1 (commits the step rings too)
+    if (!rc) {
+        hipLaunchKernelGGL(k_agents_finish, dim3((unsigned)g.E), dim3(kAgentsMax), 0, s->stream, agent_args(s, device_actions, out));
+        if (s->ag.auto_reset) {
+            rc = reset_launch(s, nullptr, s->ag_done, s->ag_ign, g.E);
+            // (section 15's bookkeeping of the mask form: which environments were taken is known on the device only)
+            if (!rc && s->snap) std::fill(s->snap_valid.begin(), s->snap_valid.end(), 0);
+        }
+    }
+    s->async = was_async;
+    if (rc) return rc;
+    HIPCHK(hipGetLastError());
+    if (!s->async) {
+        HIPCHK(hipStreamSynchronize(s->stream));
+        return check_team_error(s, "sf_agents_step");
+    }
     return SF_OK;
 }
 

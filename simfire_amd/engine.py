@@ -40,6 +40,7 @@ class FireEngine:
         self.prune_after_quit = False
         self.spread_graph = self.spread_graph_on = False
         self.async_mode = False
+        self.n_agents = 0                   # agents per environment (agents_create); 0: no agent state
         self._blobs_in_flight = []          # device state blobs an enqueued save / load may still touch (async mode; released by sync)
         self._h = C.c_void_p()
         self._chk(self._L.sf_create(C.byref(self.params), C.byref(self._h)))
@@ -187,6 +188,101 @@ class FireEngine:
         ms = C.c_float(0.0)
         self._chk(self._L.sf_get_reset_ms(self._h, C.byref(ms)))
         return float(ms.value)
+
+    # ------------------------------------------------------------------ agents on the device
+    def agents_create(self, n_agents, ignitions=None, n_updates=1, weights=(-1.0, 0.0, 0.0, 0.0), only_unburned=True,
+                      done_on_burn=False, max_ticks=0, auto_reset=True):
+        """Agent state for ``n_agents`` (1..64) agents per environment (``sf_agents_create``; called again it replaces the state,
+        ``n_agents=0`` frees it).  ``ignitions`` [n_envs, 2] = (x, y): where a done environment re-ignites under ``auto_reset``.
+        All agents start at (0, 0) until ``agents_place``.  Argument errors are raised before any device call."""
+        k = int(n_agents)
+        if k < 0 or k > 64:
+            raise ValueError(f"agents_create: {k} agents per environment (1..64; 0 frees)")
+        w = [float(v) for v in weights]
+        if len(w) != 4:
+            raise ValueError("agents_create: weights are the four factors of terms[0..3]")
+        if k and int(n_updates) < 1:
+            raise ValueError(f"agents_create: n_updates = {n_updates} must be >= 1")
+        if k and int(max_ticks) < 0:
+            raise ValueError(f"agents_create: max_ticks = {max_ticks} must be >= 0")
+        ign = None
+        if k and ignitions is not None:
+            ign = self._ignitions(ignitions, self.n_envs, "agents_create")
+        elif k and auto_reset:
+            raise ValueError("agents_create: auto_reset needs the ignitions")
+        p = _lib.SfAgentParams(k=k, n_updates=int(n_updates), only_unburned=int(bool(only_unburned)),
+                               done_on_burn=int(bool(done_on_burn)), max_ticks=int(max_ticks), auto_reset=int(bool(auto_reset)))
+        for i in range(4):
+            p.w[i] = w[i]
+        self._chk(self._L.sf_agents_create(self._h, C.byref(p), _ptr(ign) if ign is not None else None))
+        self.n_agents = k
+
+    def agents_place(self, envs, xy, also_start=True):
+        """The agents of environment ``envs[i]`` stand at ``xy[i]`` (int [n, n_agents, 2] = (column, row); ``sf_agents_place``).
+        ``also_start``: these cells become the start cells a done environment's agents go back to, and the environments' episode
+        statistics are cleared.  In async mode the call only enqueues."""
+        k = self.n_agents
+        if not k:
+            raise _lib.SimfireHipError("agents_place: call agents_create first")
+        e = self._env_list(envs, "envs")
+        a = np.asarray(xy)
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"agents_place: cells must be integers, got {a.dtype}")
+        if a.shape != (e.shape[0], k, 2):
+            raise ValueError(f"agents_place: cells must have shape {(e.shape[0], k, 2)}, got {a.shape}")
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        if e.size and (e.min() < 0 or e.max() >= self.n_envs):
+            raise ValueError(f"agents_place: environment {int(e[(e < 0) | (e >= self.n_envs)][0])} out of range (n_envs = {self.n_envs})")
+        if ((a[..., 0] < 0) | (a[..., 0] >= self.W) | (a[..., 1] < 0) | (a[..., 1] >= self.H)).any():
+            raise ValueError(f"agents_place: a cell is outside the {self.H}x{self.W} grid")
+        if e.size:
+            self._chk(self._L.sf_agents_place(self._h, int(e.shape[0]), _ptr(e), _ptr(a), int(bool(also_start))))
+
+    def agents_step(self, actions, reward=None, done=None, terms=None, final_len=None, final_ret=None):
+        """One tick for every environment from a device action tensor, nothing read back (``sf_agents_step``).  ``actions``: torch
+        CUDA int32 [n_envs, n_agents], word = move + 5 * interact.  Outputs, each optional, torch CUDA tensors on this GPU:
+        ``reward`` float32 [n_envs], ``done`` uint8 / bool [n_envs], ``terms`` int32 [n_envs, 4], ``final_len`` int32 [n_envs],
+        ``final_ret`` float64 [n_envs].  Torch's queued work on the tensors is waited for first; in async mode the call only
+        enqueues and the tensors are kept alive until ``sync``."""
+        import torch
+        k = self.n_agents
+        if not k:
+            raise _lib.SimfireHipError("agents_step: call agents_create first")
+        E = self.n_envs
+        dev = torch.device(f"cuda:{self.params.device}")
+
+        def chk(t, name, dtypes, shape):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in dtypes or tuple(t.shape) != shape \
+                    or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"agents_step: {name} must be a contiguous {dtypes[0]} tensor of shape {shape} on {dev}")
+            return t
+        chk(actions, "actions", (torch.int32,), (E, k))
+        o = _lib.SfAgentOut()
+        tensors = [actions]
+        for t, name, dtypes, shape in ((reward, "reward", (torch.float32,), (E,)), (done, "done", (torch.uint8, torch.bool), (E,)),
+                                       (terms, "terms", (torch.int32,), (E, 4)), (final_len, "final_len", (torch.int32,), (E,)),
+                                       (final_ret, "final_ret", (torch.float64,), (E,))):
+            if t is not None:
+                setattr(o, name, chk(t, name, dtypes, shape).data_ptr())
+                tensors.append(t)
+        torch.cuda.synchronize(dev)
+        self._chk(self._L.sf_agents_step(self._h, C.c_void_p(actions.data_ptr()), C.byref(o)))
+        if self.async_mode:
+            self._blobs_in_flight.extend(tensors)
+
+    def agents_device(self):
+        """Zero-copy torch view int32 [n_envs, n_agents, 3] = (column, row, id) of the agent positions on this GPU: what ``observe``
+        / ``render`` take as ``agents``.  Valid until the next ``agents_create``; read it after ``sync`` in async mode."""
+        import torch
+        if not self.n_agents:
+            raise _lib.SimfireHipError("agents_device: call agents_create first")
+        p = C.c_void_p()
+        self._chk(self._L.sf_agents_device(self._h, C.byref(p)))
+        shape = (self.n_envs, self.n_agents, 3)
+
+        class _Agents:
+            __cuda_array_interface__ = {"shape": shape, "typestr": "<i4", "data": (p.value, False), "version": 2, "strides": None}
+        return torch.as_tensor(_Agents(), device=f"cuda:{self.params.device}")
 
     def apply_mitigation(self, pts):
         """pts: rows (env, x, y, type)."""

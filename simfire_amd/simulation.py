@@ -420,6 +420,7 @@ class FireSimulation:
                     maps.append(self._engine.history(0, before + got, executed))
                 if self._recording:
                     frames = self._engine.render(envs=[0], history=(before + got, executed), agents=agents, **self.recording_options)
+                    self._engine.sync()      # (the handle is in async mode and its stream is its own: torch's copy must not overtake the render)
                     self._frames.append(frames.cpu().numpy())
                 got += executed
             done += n
@@ -645,6 +646,7 @@ class FireSimulation:
         self._sync_to_device()
         out = self._engine.render(envs=[0], scale=scale, mode=mode, background=background, contours=contours, terrain_rgb=terrain_rgb,
                                   agents=self._frame_agents(), channels_last=channels_last)
+        self._engine.sync()                  # (async mode: the render is only enqueued on the handle's own stream)
         return out[0].cpu().numpy()
 
     def save_gif(self, path=None) -> Path:

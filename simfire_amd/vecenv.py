@@ -1,0 +1,99 @@
+"""``BatchedFireEnv``: a small Gym-style vector environment on top of ``BatchedFireSimulation``.
+
+``step(actions)`` is one ``sf_agents_step`` - moves, control lines, the fire update, reward, done, episode statistics and the reset
+of finished environments, all on the device - followed by one ``observe``.  Every return is a torch CUDA tensor; nothing is read
+back to the host.  The simulation's handle works on a stream of its own that torch does not know, and ``BatchedFireSimulation``
+keeps it in async mode, so ``reset`` and ``step`` wait for that stream once (``engine.sync()``) before they return: the tensors
+are complete when the caller's torch code reads them.
+"""
+import numpy as np
+
+# action word = move + 5 * interact
+MOVES = ("stay", "up", "down", "left", "right")                  # row - 1, row + 1, column - 1, column + 1
+INTERACTIONS = ("none", "fireline", "scratchline", "wetline")
+N_ACTIONS = len(MOVES) * len(INTERACTIONS)
+
+
+def action_word(move, interact=0):
+    """The int32 action word of (move, interact), each an index or a name of ``MOVES`` / ``INTERACTIONS``."""
+    m = MOVES.index(move) if isinstance(move, str) else int(move)
+    i = INTERACTIONS.index(interact) if isinstance(interact, str) else int(interact)
+    if not (0 <= m < len(MOVES) and 0 <= i < len(INTERACTIONS)):
+        raise ValueError(f"action_word: move {move!r}, interact {interact!r}")
+    return m + 5 * i
+
+
+class BatchedFireEnv:
+    """``sim.n_envs`` environments with ``n_agents`` agents each.
+
+    ``start_xy``: int [n_agents, 2] (the same start cells in every environment) or [n_envs, n_agents, 2], (column, row).
+    ``weights``: the reward is ``w0 * newly burning or burned cells + w1 * points drawn + w2 * agents standing in the fire +
+    w3 * moves that would have left the grid``.  ``only_unburned``: lines are drawn on UNBURNED cells only.  An episode ends when
+    the fire is out (or the simulation QUIT), with ``done_on_burn`` when an agent stands in the fire, with ``max_ticks > 0`` after
+    that many ticks; with ``auto_reset`` a finished environment is re-ignited at ``sim.ignitions[e]`` (as they stand when the
+    environment is built) inside the same ``step``, its agents go back to their start cells, and the observation returned is the new
+    episode's.  ``obs``: keyword arguments of ``BatchedFireSimulation.observe`` (``channels`` first of all); its ``agents`` are
+    the device positions.
+
+    Agents are not part of an environment's state: ``clone_envs`` / ``get_state`` / ``set_state`` do not carry them."""
+
+    def __init__(self, sim, n_agents, start_xy, n_updates=1, weights=(-1, 0, 0, 0), only_unburned=True, done_on_burn=False,
+                 max_ticks=0, auto_reset=True, obs=None):
+        self.sim = sim
+        self.engine = sim._engine
+        self.n_envs, self.n_agents = int(sim.n_envs), int(n_agents)
+        if not 1 <= self.n_agents <= 64:
+            raise ValueError(f"BatchedFireEnv: {self.n_agents} agents per environment (1..64)")
+        s = np.asarray(start_xy)
+        if s.dtype.kind not in "iu":
+            raise ValueError(f"BatchedFireEnv: start_xy must be integers, got {s.dtype}")
+        if s.shape == (self.n_agents, 2):
+            s = np.broadcast_to(s, (self.n_envs, self.n_agents, 2))
+        if s.shape != (self.n_envs, self.n_agents, 2):
+            raise ValueError(f"BatchedFireEnv: start_xy must have shape {(self.n_agents, 2)} or {(self.n_envs, self.n_agents, 2)}, got {s.shape}")
+        self.start_xy = np.ascontiguousarray(s, dtype=np.int32)
+        self.obs_kwargs = dict(obs) if obs is not None else dict(channels=["fire_map", "agent_positions"])
+        if "channels" not in self.obs_kwargs:
+            raise ValueError("BatchedFireEnv: obs needs channels")
+        if "agents" in self.obs_kwargs or "envs" in self.obs_kwargs:
+            raise ValueError("BatchedFireEnv: obs takes the agents from the device and always shows every environment")
+        self.engine.agents_create(self.n_agents, sim.ignitions, n_updates=n_updates, weights=weights, only_unburned=only_unburned,
+                                  done_on_burn=done_on_burn, max_ticks=max_ticks, auto_reset=auto_reset)
+        self._all = np.arange(self.n_envs, dtype=np.int32)
+        self.engine.agents_place(self._all, self.start_xy, also_start=True)      # (raises on a cell off the grid)
+
+    def _observe(self):
+        """The observation, complete: the one wait for the handle's stream of a ``reset`` / ``step`` (the outputs of ``agents_step``
+        enqueued before it are complete then, too)."""
+        obs = self.sim.observe(agents=self.engine.agents_device(), **self.obs_kwargs)
+        self.engine.sync()
+        return obs
+
+    def reset(self):
+        """New episodes everywhere (``sim.reset()``), the agents on their start cells.  Returns the observation."""
+        self.sim.reset()
+        self.engine.agents_place(self._all, self.start_xy, also_start=True)
+        return self._observe()
+
+    def step(self, actions):
+        """``actions``: torch CUDA int32 [n_envs, n_agents] (``action_word``).  Returns ``(obs, reward float32 [n_envs],
+        done bool [n_envs], info)`` with ``info = dict(terms int32 [n_envs, 4], final_len int32 [n_envs], final_ret float64
+        [n_envs])``: the episode length and return of the environments that are done, else 0.  New tensors every call."""
+        import torch
+        dev = torch.device(f"cuda:{self.engine.params.device}")
+        E = self.n_envs
+        reward = torch.empty(E, dtype=torch.float32, device=dev)
+        done = torch.empty(E, dtype=torch.bool, device=dev)
+        terms = torch.empty((E, 4), dtype=torch.int32, device=dev)
+        final_len = torch.empty(E, dtype=torch.int32, device=dev)
+        final_ret = torch.empty(E, dtype=torch.float64, device=dev)
+        self.engine.agents_step(actions, reward=reward, done=done, terms=terms, final_len=final_len, final_ret=final_ret)
+        return self._observe(), reward, done, dict(terms=terms, final_len=final_len, final_ret=final_ret)
+
+    def positions(self):
+        """torch int32 [n_envs, n_agents, 3] = (column, row, id): a view of the device positions (current after ``reset`` / ``step``,
+        which wait for the handle's stream)."""
+        return self.engine.agents_device()
+
+    def close(self):
+        self.engine.agents_create(0)
