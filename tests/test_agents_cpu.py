@@ -152,24 +152,147 @@ def test_struct_layouts_match_the_header(struct, cls):
     assert C.sizeof(ct) == size == 40
 
 
+class _PerEnvDense:
+    """``oracle/fire_dense`` with a table per environment: one single-environment oracle each, behind the pre-agent API."""
+
+    def __init__(self, kw, tabs, inits):
+        from oracle import fire_dense
+        self.n_envs = len(tabs)
+        self.o = [fire_dense.DenseOracle(n_envs=1, **kw) for _ in tabs]
+        for o, t, xy in zip(self.o, tabs, inits):
+            o.set_rtable(t)
+            o.reset([xy])
+
+    def status(self):
+        st, el = zip(*(o.status() for o in self.o))
+        return np.concatenate(st), np.concatenate(el)
+
+    def fire_map(self, e):
+        return self.o[e].fire_map(0)
+
+    def apply_mitigation(self, rows):
+        for (e, x, y, t) in rows:
+            self.o[e].apply_mitigation([(0, x, y, t)])      # (one row at a time keeps the order; update_mitigation's precedence is per type)
+
+    def step(self, n):
+        for o in self.o:
+            o.step(n)
+
+    def reset_env(self, e, x, y):
+        self.o[e].reset_env(0, x, y)
+
+
+def _dense_handle(case):
+    from oracle import fire_dense
+    import _agents_worlds as aw
+    kw, R8, E, inits, starts = aw.make_world(case)
+    if aw.CASES[case].get("per_env"):
+        assert all((R8[e] != R8[0]).any() for e in range(1, E))
+        return _PerEnvDense(kw, R8, inits), E
+    a = fire_dense.DenseOracle(n_envs=E, **kw)
+    a.set_rtable(R8)
+    a.reset(inits)
+    return a, E
+
+
+# (E, ignitions, the first start, max_time, pixel_scale, sum of the R table) of the four first cases, as drawn before the optional keys existed
+_OLD_WORLDS = {
+    "24x40_k5_u1_att": (4, [[3, 15], [0, 20], [18, 0], [18, 0]], [15, 0], 11.0, 20.0, 1666698.0),
+    "33x17_k64_u3": (5, [[13, 1], [15, 29], [0, 32], [14, 14], [2, 32]], [16, 16], 10.0, 5.0, 1019887.0),
+    "24x40_k1_u1_att_t6": (6, [[14, 0], [39, 20], [0, 0], [0, 0], [20, 2], [0, 12]], [15, 0], 10.0, 5.0, 1666447.5),
+    "33x17_k5_u3_noreset": (8, [[10, 0], [16, 31], [16, 3], [15, 0], [0, 0], [15, 3], [16, 1], [16, 1]], [16, 0], 6.0, 50.0, 997925.5),
+}
+
+
+def test_the_old_cases_draw_the_worlds_they_always_drew():
+    """The optional keys of the new cases leave the rng order of the four first cases alone: E, the ignitions and the first starts
+    as they were recorded before the keys existed."""
+    import _agents_worlds as aw
+    assert tuple(_OLD_WORLDS) == aw.OLD_CASES
+    for case in aw.OLD_CASES:
+        assert "modes" not in aw.CASES[case] and aw.case_modes(case) == aw.BASE_MODES
+        kw, R8, E, inits, starts = aw.make_world(case)
+        got = (E, inits.tolist(), starts[0, 0].tolist(), kw["max_time"], kw["pixel_scale"], float(R8.sum()))
+        assert got == _OLD_WORLDS[case], (case, got)
+
+
 def test_gpu_cases_cover_what_they_claim():
     """Every case of ``tests/test_agents_gpu.py`` on handle A alone - ``oracle/fire_dense`` standing in for it: the case sees an
     auto-reset (without auto_reset: a done report and an environment found not running), an agent in the fire, a blocked move, an
-    emitted point and, with only_unburned, a refused one."""
-    from oracle import fire_dense
+    emitted point and, with only_unburned, a refused one; where the case names a ``split`` (the rows either side of the team cut,
+    the columns either side of 1024), agents on both sides of it."""
     import _agents_worlds as aw
     for case, c in aw.CASES.items():
-        kw, R8, E, inits, starts = aw.make_world(case)
-        assert 4 <= E <= 8
-        a = fire_dense.DenseOracle(n_envs=E, **kw)
-        a.set_rtable(R8)
-        a.reset(inits)
+        a, E = _dense_handle(case)
+        assert (4 <= E <= 8) if "E" not in c else E == (aw.E_STAND_IN if c["E"] == "cu+8" else c["E"])
         seen = aw.drive(case, a)
         assert seen["in_fire"] and seen["blocked"] and seen["emitted"] and seen["done"], (case, seen)
         assert seen["reset"] if c["auto_reset"] else seen["off"], (case, seen)
         if c["only_unburned"]:
             assert seen["refused"], (case, seen)
-    on = {k: {c[k] for c in aw.CASES.values()} for k in ("att", "only_unburned", "done_on_burn", "auto_reset")}
+        if "split" in c:
+            assert seen["lo"] and seen["hi"], (case, seen["lo"], seen["hi"])
+    old = [aw.CASES[k] for k in aw.OLD_CASES]
+    on = {k: {c[k] for c in old} for k in ("att", "only_unburned", "done_on_burn", "auto_reset")}
     assert all(v == {True, False} for v in on.values()), on
-    assert {c["n_updates"] for c in aw.CASES.values()} == {1, 3} and {c["max_ticks"] for c in aw.CASES.values()} == {0, 6}
-    assert {c["K"] for c in aw.CASES.values()} == {1, 5, 64}
+    assert {c["n_updates"] for c in old} == {1, 3} and {c["max_ticks"] for c in old} == {0, 6}
+    assert {c["K"] for c in old} == {1, 5, 64}
+    # the new cases: every base mode name is the mode of some case that proves its launch structure ran
+    proved = {m for c in aw.CASES.values() if c.get("engage") for m in c["modes"]}
+    assert {"run_team", "run_win", "run_kwin", "auto"} <= proved
+    assert {c.get("diag", True) for c in aw.CASES.values()} == {True, False}
+    assert {c.get("md", 4) for c in aw.CASES.values()} == {4, 8}
+
+
+def _rewards(terms, w, how):
+    """The reward of every term row under one evaluation rule.  "spec": double, left to right, every operation rounded once, then
+    one rounding to float.  "f32": every operation in float.  "fma": double, the three additions contracted
+    with their multiplications (one rounding for a * b + c; exact rational arithmetic stands in for the fused operation)."""
+    from fractions import Fraction
+    out = []
+    for t in terms:
+        if how == "spec":
+            r = w[0] * float(t[0])
+            for i in (1, 2, 3):
+                r = r + w[i] * float(t[i])
+        elif how == "f32":
+            f = np.float32
+            r = f(w[0]) * f(t[0])
+            for i in (1, 2, 3):
+                r = f(r + f(f(w[i]) * f(t[i])))
+        else:
+            r = w[0] * float(t[0])
+            for i in (1, 2, 3):
+                r = float(Fraction(w[i]) * t[i] + Fraction(r))
+        out.append(np.float32(r))
+    return np.array(out, dtype=np.float32)
+
+
+def test_reward_arithmetic_is_told_apart():
+    """The term rows of the case with weights that are not exact in binary (-0.1, 1/3, -1e-3, 0.7 on 72 x 80, terms up to the
+    hundreds): a reward evaluated in float differs from the specified one (double, left to right, one rounding to float) in at
+    least one tick, so the bitwise comparison of the GPU test tells the two apart.
+
+    A contracted evaluation (fused multiply-add) is NOT a different function of these inputs, whatever the seed and the weights:
+    a weight is a float widened (24 significant bits), a term is a cell or agent count below 2^20, so every product w * t has at
+    most 44 significant bits and is exact in double - a fused a * b + c and a rounded a * b followed by + c then round the same
+    exact sum once.  The test asserts that equality on the case's rows and on adversarial ones, instead of a separation that
+    cannot exist; -ffp-contract=off in the build is belt and braces, not something a reward can show."""
+    import _agents_worlds as aw
+    case = "72x80_k5_u2_win"
+    c = aw.CASES[case]
+    a, E = _dense_handle(case)
+    terms = aw.drive(case, a)["terms"]
+    w = [float(np.float32(v)) for v in c["weights"]]
+    assert max(t[0] for t in terms) >= 100 and len(set(terms)) >= 20, (max(t[0] for t in terms), len(set(terms)))
+    spec, f32, fma = (_rewards(terms, w, how) for how in ("spec", "f32", "fma"))
+    assert (spec.view(np.uint32) != f32.view(np.uint32)).any()
+    assert spec.tobytes() == fma.tobytes()
+    rng = np.random.default_rng(96000)
+    hard = [tuple(int(v) for v in rng.integers(-(1 << 20), 1 << 20, size=4)) for _ in range(2000)]
+    wh = [float(np.float32(v)) for v in (-0.1, 1e8 / 3.0, -1e-7, 0.7)]
+    assert _rewards(hard, wh, "spec").tobytes() == _rewards(hard, wh, "fma").tobytes()
+    for t in hard[:200]:
+        for wi, ti in zip(wh, t):
+            from fractions import Fraction
+            assert Fraction(wi * float(ti)) == Fraction(wi) * ti          # the product is exact
