@@ -166,6 +166,30 @@ int sf_enable_history(sf_sim *sim, int32_t capacity);
 int sf_get_history(sf_sim *sim, int32_t env, int32_t first, int32_t count, int8_t *out);
 int sf_history_device(sf_sim *sim, void **ptr, int32_t *capacity);
 
+/* Arrival times: for every cell the update() call that created its FIRST sprite - the sprite creation of
+ * _update_with_new_locs (fire.py:571-587), which the reference forgets once the sprite is pruned and its users rebuild from
+ * fire_map.npy after the run.  Numbered as sf_get_history numbers updates: the reset's ignition cell is 0, a cell ignited by the
+ * first update() call is 1.  The value is an update INDEX, not minutes: elapsed_time does not advance on an update without a
+ * candidate (fire.py:651-652), so a conversion is the caller's business (sf_get_status per update, or update_rate where every
+ * update ran to the end).  The definition counts SPRITES: a cell that sf_load_fire_map paints BURNING has no sprite and no arrival; a
+ * control line drawn over a burned cell does not erase its arrival; a cell that ignites again (a line drawn on a burning cell makes
+ * it eligible, fire.py:192-205) keeps its first.  A new episode (every form of reset) clears the environment's plane.
+ * The plane is kept by a pass BEHIND the step launches, not by them: while recording is on, a call of n updates runs as pieces of at
+ * most max_fire_duration updates, each followed by the pass - the launch structure of every piece is chosen as for a call of that
+ * length, results do not change, a long call pays one launch boundary per piece.  Recording off costs nothing.
+ * sf_enable_arrival: allowed at any time; ends a running closed loop first.  on != 0 allocates and zeroes the plane (uint32 per cell
+ * and environment; counted by sf_memory_bytes): cells that burned out before that moment stay "never", sprites that are live at that
+ * moment are picked up with their true update by the first pass (made here if the handle has been reset).  on == 0 frees it.
+ * While it is on: sf_loop_start is SF_ENOTSUP (a closed loop has no launch boundary to hang the pass on); sf_copy_envs carries the
+ * plane; a state blob carries it, and blobs of a handle with recording and one without do not match (SF_EINVAL).
+ * sf_get_arrival: int32 [H*W] of one environment - the update that ignited the cell, 0 = the reset's ignition, -1 = never.
+ * SF_ESTATE before sf_enable_arrival.
+ * sf_arrival_device: the raw plane for zero-copy consumers - uint32, update + 1, 0 = never; pointer to environment 0, row pitch and
+ * environment stride in bytes.  Complete once the handle's stream has reached the end of the last stepping (or reset) call. */
+int sf_enable_arrival(sf_sim *sim, int32_t on);
+int sf_get_arrival(sf_sim *sim, int32_t env, int32_t *out /* [H*W] */);
+int sf_arrival_device(sf_sim *sim, void **ptr, int64_t *row_pitch, int64_t *env_stride);
+
 /* FireSimulation.reset for every environment (simulation.py:202-214, 555-566): fire_map all
  * UNBURNED except the ignition cell, burn_amounts 0, one sprite of duration 0, elapsed_time 0.
  * init_xy = int32 [n_envs][2] = (x, y). */
@@ -225,7 +249,7 @@ int sf_set_burn(sf_sim *sim, int32_t env, const double *burn);
 /* Environment state: fork, snapshot, restore.  Every call ends a running closed loop (sf_loop_start) first,
  * needs sf_reset to have run once (SF_ESTATE) and refuses a handle whose last team launch failed.
  * sf_copy_envs: environment dst[i] becomes environment src[i] in every respect - cells, sprite ages, burn_amounts, the attenuation
- * books, spread-graph parents, update() calls made, elapsed_time, running, the result row - in ONE launch for all n pairs.  A src may
+ * books, spread-graph parents, arrival times, update() calls made, elapsed_time, running, the result row - in ONE launch for all n pairs.  A src may
  * repeat (one to many); the dst are distinct and none of them is a src of the same call; n == 0 does nothing; anything else is
  * SF_EINVAL.  With SF_COPY_TERRAIN on a handle created with per_env_terrain, dst also takes src's layers and R table (without
  * it, and on a shared-terrain handle, dst keeps its own terrain).  In async mode (sf_set_async) the copy is only enqueued. */
@@ -239,7 +263,8 @@ int sf_state_bytes(sf_sim *sim, int64_t *bytes_out);
  * handle's stream has got there: sf_sync); the caller orders its own work on the buffer before the call. */
 int sf_save_state(sf_sim *sim, int32_t n, const int32_t *envs, void *out, int32_t device_pointer);
 /* The reverse: environment envs[i] takes the state of blob i.  A blob whose header does not match this handle (version, grid,
- * max_fire_duration, diagonal spread, attenuation, max_time, update_rate, pixel_scale threshold, prune_after_quit, spread graph) is
+ * max_fire_duration, diagonal spread, attenuation, max_time, update_rate, pixel_scale threshold, prune_after_quit, spread graph, arrival
+ * recording) is
  * SF_EINVAL and nothing is changed.  A device buffer must be 16-byte aligned (SF_EINVAL).  A device-pointer load waits for the stream
  * once to read the headers; the restore itself is only enqueued in async mode (the caller keeps the buffer until sf_sync). */
 int sf_load_state(sf_sim *sim, int32_t n, const int32_t *envs, const void *in, int32_t device_pointer);

@@ -125,6 +125,15 @@ int sf_last_step_launch(sf_sim *sim, int32_t *kind_out);
 /* Which cell plane is current: 1 = the blocked plane of the resident launch, 0 = the row-major planes (what sf_observe reads from; tests
  * assert with it that the layout they are about was the one read).  No reference counterpart. */
 int sf_cell_layout(sf_sim *sim, int32_t *blocked_out);
+/* The arrival pass (sf_enable_arrival) has two forms: sparse - it walks the vector bitmap of the resident launch - where the blocked plane
+ * is current and the bitmap valid, dense - one thread per cell - elsewhere.  sf_set_arrival_dense(1) forces the dense form everywhere
+ * (tests compare the two; profiles/arrival_probe.py measures both); sf_get_arrival_passes: out[0] / out[1] = passes made in the
+ * sparse / the dense form since the handle was created.  No reference counterpart. */
+int sf_set_arrival_dense(sf_sim *sim, int32_t on);
+int sf_get_arrival_passes(sf_sim *sim, int64_t *out /* [2] */);
+/* One more arrival pass over the state as it stands (it finds nothing new: a cell is written once), with HIP events around its launch:
+ * the GPU milliseconds of a pass in the form the handle would take now.  SF_ESTATE before sf_enable_arrival. */
+int sf_time_arrival_pass(sf_sim *sim, float *ms_out);
 /* 1 = visit every tile every step instead of consulting the tile activity map (cross-check) */
 int sf_set_dense(sf_sim *sim, int32_t dense);
 /* sf_cfd_step that also reports the GPU time of its launches (HIP events on the handle's stream). */

@@ -95,6 +95,12 @@ SIGNATURES = {
     "sf_enable_history": [_VP, _I32],
     "sf_get_history": [_VP, _I32, _I32, _I32, _VP],
     "sf_history_device": [_VP, _VP, _VP],
+    "sf_enable_arrival": [_VP, _I32],
+    "sf_get_arrival": [_VP, _I32, _VP],
+    "sf_arrival_device": [_VP, C.POINTER(_VP), C.POINTER(_I64), C.POINTER(_I64)],
+    "sf_set_arrival_dense": [_VP, _I32],
+    "sf_get_arrival_passes": [_VP, _VP],
+    "sf_time_arrival_pass": [_VP, C.POINTER(C.c_float)],
     "sf_reset": [_VP, _VP],
     "sf_reset_env": [_VP, _I32, _I32, _I32],
     "sf_reset_envs": [_VP, _I32, _VP, _VP],

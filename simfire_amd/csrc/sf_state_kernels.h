@@ -37,7 +37,7 @@ __global__ __launch_bounds__(256) void k_env_copy(CopyList L)
 //   [128, 152)   EnvState (commit)          [160, 192) result row (8 x int32)     [192, 200) elapsed_time (f64)
 //   from 256, each section rounded up to 16 bytes: status u8 [H][W] (raw bytes), sprite masks [H][W] x ab bytes (little endian),
 //   burn f64 [H][W] (the stored value: attenuation still owed is in settled), settled u32 [H][W] (attenuation on), parents u8 [H][W]
-//   (spread graph on)
+//   (spread graph on), arrival u32 [H][W] (arrival recording on: update + 1, 0 = never)
 constexpr uint32_t kStateMagic = 0x54534653u;      // "SFST"
 constexpr uint32_t kStateVersion = 1u;
 struct StateHeader {
@@ -45,7 +45,7 @@ struct StateHeader {
     int64_t bytes;                                 // the whole blob
     int32_t H, W, md, ab;
     int32_t diag, att, has_max_time, prune_after_quit;
-    int32_t has_parents, fire_rows, reserved0, reserved1;      // fire_rows: the saving handle's bound on the fire's height (0 = none)
+    int32_t has_parents, fire_rows, has_arrival, reserved1;    // fire_rows: the saving handle's bound on the fire's height (0 = none)
     double max_time, update_rate, pixel_scale;
     uint8_t pad[40];
 };
@@ -53,9 +53,9 @@ static_assert(sizeof(StateHeader) == 128, "StateHeader is 128 bytes");
 constexpr long long kStateFixed = 256;
 __host__ __device__ inline long long st_round(long long b) { return (b + 15) / 16 * 16; }
 struct StateLayout {
-    long long status, age, burn, settled, parents, bytes;
+    long long status, age, burn, settled, parents, arrival, bytes;
 };
-__host__ __device__ inline StateLayout state_layout(const Geo &g, bool parents)
+__host__ __device__ inline StateLayout state_layout(const Geo &g, bool parents, bool arrival)
 {
     const long long n = (long long)g.H * g.W;
     StateLayout l;
@@ -64,7 +64,8 @@ __host__ __device__ inline StateLayout state_layout(const Geo &g, bool parents)
     l.burn = l.age + st_round(n * g.ab);
     l.settled = l.burn + st_round(n * 8);
     l.parents = l.settled + (g.att ? st_round(n * 4) : 0);
-    l.bytes = l.parents + (parents ? st_round(n) : 0);
+    l.arrival = l.parents + (parents ? st_round(n) : 0);
+    l.bytes = l.arrival + (arrival ? st_round(n * 4) : 0);
     return l;
 }
 
@@ -75,6 +76,7 @@ struct StateArgs {
     double *burn;
     uint32_t *settled;
     uint8_t *parents;
+    uint32_t *arrival;                             // null: arrival recording is off
     unsigned long long *vbits;
     EnvState *commit;
     int32_t *res_block, *res_sink;
@@ -104,10 +106,10 @@ __global__ __launch_bounds__(256) void k_state_pack(StateArgs a)
         else if (t >= 50 && t < 64) reinterpret_cast<uint32_t *>(b + 200)[t - 50] = 0u;      // [200, 256)
         else if (t == 64) {      // the padding behind every section: a blob holds nothing but the state (two saves of one state are equal)
             const long long n = (long long)g.H * g.W;
-            const long long ends[5] = {a.lay.status + n, a.lay.age + n * g.ab, a.lay.burn + n * 8, g.att ? a.lay.settled + n * 4 : a.lay.parents,
-                                       a.parents ? a.lay.parents + n : a.lay.bytes};
-            const long long nexts[5] = {a.lay.age, a.lay.burn, a.lay.settled, a.lay.parents, a.lay.bytes};
-            for (int k = 0; k < 5; ++k)
+            const long long ends[6] = {a.lay.status + n, a.lay.age + n * g.ab, a.lay.burn + n * 8, g.att ? a.lay.settled + n * 4 : a.lay.parents,
+                                       a.parents ? a.lay.parents + n : a.lay.arrival, a.arrival ? a.lay.arrival + n * 4 : a.lay.bytes};
+            const long long nexts[6] = {a.lay.age, a.lay.burn, a.lay.settled, a.lay.parents, a.lay.arrival, a.lay.bytes};
+            for (int k = 0; k < 6; ++k)
                 for (long long q = ends[k]; q < nexts[k]; ++q) b[q] = 0u;
         }
     }
@@ -129,6 +131,7 @@ __global__ __launch_bounds__(256) void k_state_pack(StateArgs a)
     reinterpret_cast<double *>(b + a.lay.burn)[c] = a.burn[o];
     if (g.att) reinterpret_cast<uint32_t *>(b + a.lay.settled)[c] = a.settled[o];
     if (a.parents) b[a.lay.parents + c] = a.parents[o];
+    if (a.arrival) reinterpret_cast<uint32_t *>(b + a.lay.arrival)[c] = a.arrival[o];
 }
 
 // The reverse, into the layout that is current.  The caller has zeroed the environment's cell planes (guard rows / quads and pitch
@@ -153,6 +156,7 @@ __global__ __launch_bounds__(256) void k_state_unpack(StateArgs a)
         a.burn[o] = 0.0;
         if (g.att) a.settled[o] = 0u;
         if (a.parents) a.parents[o] = 0u;
+        if (a.arrival) a.arrival[o] = 0u;
         return;
     }
     const long long c = (long long)y * g.W + x;
@@ -171,6 +175,7 @@ __global__ __launch_bounds__(256) void k_state_unpack(StateArgs a)
     a.burn[o] = reinterpret_cast<const double *>(b + a.lay.burn)[c];
     if (g.att) a.settled[o] = reinterpret_cast<const uint32_t *>(b + a.lay.settled)[c];
     if (a.parents) a.parents[o] = b[a.lay.parents + c];
+    if (a.arrival) a.arrival[o] = reinterpret_cast<const uint32_t *>(b + a.lay.arrival)[c];
 }
 
 // The three planes of the vector bitmap of a restored environment, from the blob's sprite masks (so that the blocked plane and the

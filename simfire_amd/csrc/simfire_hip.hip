@@ -106,6 +106,7 @@ extern "C" const char *sf_version(void) { return "simfire_hip 0.2 (gfx950)"; }  
 #include "sf_render_kernels.h"
 #include "sf_gen_kernels.h"
 #include "sf_agent_kernels.h"
+#include "sf_arrival_kernels.h"
 
 // Launch-geometry knobs of a handle (sf_set_tuning, include/simfire_hip_lab.h: SF_TUNE_*).  Results never depend on them; the
 // defaults are the measured choices of NOTEBOOK.md 5.  The library does not read the environment for them (the measurement scripts under
@@ -219,6 +220,14 @@ struct sf_sim {
     mutable std::map<const void *, size_t> lds_allowed;       // dynamic LDS the resident kernels have been enabled for, by host handle (allow_lds)
     uint8_t *parents = nullptr;        // spread-graph parent masks, allocated by sf_enable_spread_graph
     bool graph_on = false;
+    // sf_enable_arrival: the plane u32 [E][H][P] (update that created a cell's first sprite + 1, 0 = never; null =
+    // recording off), updates made since the last pass (< md between the pieces of a call, 0 between calls), whether the caller of the
+    // step path makes the closing pass itself (sf_step_mitigated's scatter + step pairs), the lab's "always the dense pass" and its
+    // count of passes made in the sparse / the dense form
+    uint32_t *arrival1 = nullptr;
+    int arr_pending = 0;
+    bool arr_hold = false, arr_dense = false;
+    int64_t arr_passes[2] = {0, 0};
     // sf_get_fire_map_delta: the fire maps as the host last saw them (u8 [E][H][P], allocated at the first call), per environment whether that
     // reference point exists, the list of changed cells on the device ([0] = count) and its pinned landing zone
     uint8_t *snap = nullptr;
@@ -278,6 +287,8 @@ extern "C" int sf_loop_stop(sf_sim *s);
 static int ensure_rm(sf_sim *s);
 static int alloc_bl(sf_sim *s);
 static bool prefers_bl(const sf_sim *s);
+static int arrival_pass(sf_sim *s);
+static int arrival_seg(const sf_sim *s, EnvSeg *seg, int n);
 
 // Behind every wait for the handle's stream: has a workgroup of a team launch (k_run<TEAM>) given up waiting for a team member?
 // Then what the launch left behind is void - say so wherever data is handed back, not only in sf_sync / a synchronous sf_step.
@@ -484,7 +495,7 @@ extern "C" int sf_destroy(sf_sim *s)
     for (void *hp : {(void *)s->loop_db, (void *)s->loop_res, (void *)s->loop_pts}) if (hp) (void)hipHostFree(hp);
     for (void *dp : {(void *)s->loop_mem, (void *)s->loop_pts_mem}) if (dp) (void)hipFree(dp);
     void *ptrs[] = {s->team_tab, s->team_size, s->xdone, s->xg, s->xbuf, s->xj, s->xcut, s->jlog, s->status, s->age_alloc, s->cells_alloc, s->burn, s->rt, s->rtc, s->lay_all, s->history, s->smag, s->sdir, s->commit, s->tmp, s->flags, s->counters, s->tflags, s->tile_list, s->n_active, s->seam, s->settled, s->tdirty, s->thist, s->vbits, s->todo, s->run_cost, s->run_order, s->todo_cnt, s->win_hint, s->mit_stage,
-                    s->status_block, s->elapsed_dev, s->stage, s->parents};
+                    s->status_block, s->elapsed_dev, s->stage, s->parents, s->arrival1};
     if (s->status_pinned) (void)hipHostFree(s->status_pinned);
     if (s->delta_pinned) (void)hipHostFree(s->delta_pinned);
     for (void *dp : {(void *)s->snap, (void *)s->delta_dev, (void *)s->rd_bg, (void *)s->rd_fuel_ix, (void *)s->ag_mem}) if (dp) (void)hipFree(dp);
@@ -1109,7 +1120,7 @@ static int reset_range(sf_sim *s, int env0, int n, const int32_t *xy)
     // What is zeroed here: a batched reset's slices but the seams (rebuild_seams below), + the window advice (where the old fires
     // stood says nothing about the new ones) and, with new episodes everywhere, the launch-order cost (no order to carry over)
     EnvSeg seg[kEnvSegs];
-    const int n_seg = env_segs(s, (kResetKinds & ~kSegSeam & ~(hist_known ? 0u : kSegHist)) | kSegHint | (n == g.E ? kSegCost : 0u), seg);
+    const int n_seg = arrival_seg(s, seg, env_segs(s, (kResetKinds & ~kSegSeam & ~(hist_known ? 0u : kSegHist)) | kSegHint | (n == g.E ? kSegCost : 0u), seg));
     for (int k = 0; k < n_seg; ++k) {
         assert(seg[k].stride == seg[k].len);      // (the slices of env0 .. env0 + n - 1 are one range)
         HIPCHK(hipMemsetAsync(seg[k].base + env0 * seg[k].stride, 0, (size_t)(n * seg[k].len), s->stream));
@@ -1127,6 +1138,8 @@ static int reset_range(sf_sim *s, int env0, int n, const int32_t *xy)
     }
     if (!hist_known) s->tdirty_all = true;
     else if (n == g.E) s->tdirty_all = false;
+    rc = arrival_pass(s);               // the ignition is the sprite of update 0
+    if (rc) return rc;
     HIPCHK(hipStreamSynchronize(s->stream));
     return SF_OK;
 }
@@ -1337,6 +1350,42 @@ static int ensure_vbits(sf_sim *s)
     s->vbits_valid = true;
     s->vbits_fl_valid = true;
     return SF_OK;
+}
+
+// ----------------------------------------------------------------------------- arrival times
+// The pass behind the launches (sf_arrival_kernels.h): reads every environment's update count from commit[], so the step rings are
+// folded first.  Sparse where the blocked plane is current and every plane of the vector bitmap is known to match it, else dense over
+// whichever plane is current.  Recording off: nothing.
+static int arrival_pass(sf_sim *s)
+{
+    if (!s->arrival1) return SF_OK;
+    { int rc0 = ensure_commit(s); if (rc0) return rc0; }
+    const Geo &g = s->g;
+    const bool sparse = s->bl_cur && s->vbits_valid && s->vbits_fl_valid && !s->arr_dense;
+    if (sparse) {
+        hipLaunchKernelGGL(k_arrival_bits, dim3((unsigned)((g.H * g.VW + 255) / 256), (unsigned)g.E), dim3(256), 0, s->stream, g, (const uint8_t *)s->cells,
+                           (const unsigned long long *)s->vbits, (const EnvState *)s->commit, s->arrival1);
+    } else {
+        const dim3 grd((unsigned)((g.W + 255) / 256), (unsigned)g.H, (unsigned)g.E), blk(256);
+        const uint8_t *cells = s->bl_cur ? s->cells : nullptr;
+        if (g.ab == 1) hipLaunchKernelGGL(k_arrival_cells<uint8_t>, grd, blk, 0, s->stream, g, (const uint8_t *)s->age, cells, (const EnvState *)s->commit, s->arrival1);
+        else if (g.ab == 2) hipLaunchKernelGGL(k_arrival_cells<uint16_t>, grd, blk, 0, s->stream, g, (const uint8_t *)s->age, cells, (const EnvState *)s->commit, s->arrival1);
+        else hipLaunchKernelGGL(k_arrival_cells<uint32_t>, grd, blk, 0, s->stream, g, (const uint8_t *)s->age, cells, (const EnvState *)s->commit, s->arrival1);
+    }
+    HIPCHK(hipGetLastError());
+    s->arr_passes[sparse ? 0 : 1]++;
+    s->arr_pending = 0;
+    return SF_OK;
+}
+// The plane's per-environment slice behind the n slices env_segs has filled (a reset zeroes it, a fork copies it): appended here and not
+// a kind of sf_env_segs.h - the plane is not one of the buffers the step kernels know.  Returns the new count.
+static int arrival_seg(const sf_sim *s, EnvSeg *seg, int n)
+{
+    if (!s->arrival1) return n;
+    assert(n < kEnvSegs);
+    const long long len = s->g.plane_env * 4;
+    seg[n] = {reinterpret_cast<uint8_t *>(s->arrival1), len, len};
+    return n + 1;
 }
 
 extern "C" int sf_last_step_launch(sf_sim *s, int32_t *kind)
@@ -1888,7 +1937,7 @@ static int run_resident(sf_sim *s, const StepPlan &p, StepArgs &a, int n_steps, 
 
 // A sf_step call as planned: the buffers its launches need, then the resident rollout or the per-step loop.  mit_dev / mit_k: control
 // lines inside the resident launch (p planned with lines).
-static int run_step(sf_sim *s, StepPlan p, int n_steps, float *ms, const int32_t *mit_dev, int mit_k)
+static int run_step_once(sf_sim *s, StepPlan p, int n_steps, float *ms, const int32_t *mit_dev, int mit_k)
 {
     const Geo &g = s->g;
     const Tuning &tn = s->tune;
@@ -1977,6 +2026,43 @@ static int run_step(sf_sim *s, StepPlan p, int n_steps, float *ms, const int32_t
     return SF_OK;
 }
 
+// What every stepping call goes through.  Recording off (sf_enable_arrival): the call as planned, nothing else.  Recording on: the
+// updates in pieces of at most max_fire_duration - of even length, each planned as a call of its length would be (a piece of the
+// point block with it) and followed by the arrival pass -, so that every sprite is still in the masks when a pass looks (DESIGN.md
+// section 17).  The pieces only enqueue; timing and the one wait of a synchronous call span all of them.
+static int run_step(sf_sim *s, const StepPlan &p, int n_steps, float *ms, const int32_t *mit_dev, int mit_k)
+{
+    if (!s->arrival1) return run_step_once(s, p, n_steps, ms, mit_dev, mit_k);
+    const Geo &g = s->g;
+    const bool was_async = s->async;
+    s->async = true;
+    int rc = SF_OK, launches = 0;
+    if (ms && hipEventRecord(s->ev0, s->stream) != hipSuccess) rc = fail(SF_EHIP, "sf_step: hipEventRecord failed");
+    for (int done = 0; done < n_steps && !rc;) {
+        if (s->arr_pending >= g.md) { rc = arrival_pass(s); continue; }      // (a call that failed half way left them behind)
+        const int room = g.md - s->arr_pending;
+        const int pieces = (n_steps - done + room - 1) / room;
+        const int c = s->arr_hold ? std::min(n_steps - done, room) : (n_steps - done + pieces - 1) / pieces;
+        const StepPlan pc = c == n_steps ? p : plan_step(s, c, mit_dev != nullptr);
+        if (mit_dev && !pc.nw) { rc = fail(SF_EHIP, "sf_step_mitigated: a piece of %d updates was not planned as a resident launch", c); break; }
+        rc = run_step_once(s, pc, c, nullptr, mit_dev ? mit_dev + (size_t)done * g.E * mit_k * 3 : nullptr, mit_k);
+        launches += s->last_launches;
+        s->arr_pending += c;
+        done += c;
+        if (!rc && (!s->arr_hold || s->arr_pending >= g.md)) rc = arrival_pass(s);      // behind every piece; a caller that holds: every md updates
+    }
+    s->async = was_async;
+    s->last_launches = launches;
+    s->last_was_step1 = n_steps == 1 && !mit_dev;
+    if (rc) return rc;
+    if (ms) HIPCHK(hipEventRecord(s->ev1, s->stream));
+    if (ms || !s->async) HIPCHK(hipStreamSynchronize(s->stream));
+    if (ms) HIPCHK(hipEventElapsedTime(ms, s->ev0, s->ev1));
+    if ((ms || !s->async) && s->xerr_pinned && *s->xerr_pinned)
+        return fail(SF_EHIP, "sf_step: a workgroup of a team launch (k_run<TEAM>) gave up waiting for a team member; the state of this handle is void");
+    return SF_OK;
+}
+
 static int step_impl(sf_sim *s, int n_steps, float *ms)
 {
     if (!s) return fail(SF_EINVAL, "sf_step: null handle");
@@ -2031,6 +2117,81 @@ extern "C" int sf_history_device(sf_sim *s, void **ptr, int32_t *capacity)
 {
     if (!s || !ptr || !capacity) return fail(SF_EINVAL, "sf_history_device: null argument");
     *ptr = s->history; *capacity = s->history_cap;
+    return SF_OK;
+}
+
+// Arrival times: which update created the first sprite of a cell (fire.py:571-587), kept by a pass behind the
+// step launches (arrival_pass; run_step cuts a call into pieces of at most max_fire_duration updates while this is on).
+extern "C" int sf_enable_arrival(sf_sim *s, int32_t on)
+{
+    if (!s) return fail(SF_EINVAL, "sf_enable_arrival: null handle");
+    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
+    const size_t n = (size_t)s->g.E * s->g.plane_env;
+    if (!on) {
+        if (!s->arrival1) return SF_OK;
+        HIPCHK(hipStreamSynchronize(s->stream));
+        HIPCHK(hipFree(s->arrival1));
+        s->arrival1 = nullptr;
+        s->bytes -= (int64_t)(n * sizeof(uint32_t));
+        return SF_OK;
+    }
+    if (s->arrival1) return SF_OK;
+    { int rc = dev_alloc(s, &s->arrival1, n); if (rc) return rc; }
+    HIPCHK(hipMemsetAsync(s->arrival1, 0, n * sizeof(uint32_t), s->stream));
+    s->arr_pending = 0;
+    if (s->was_reset) { int rc = arrival_pass(s); if (rc) return rc; }      // the sprites that are live now carry their true updates
+    if (!s->async) HIPCHK(hipStreamSynchronize(s->stream));
+    return SF_OK;
+}
+
+extern "C" int sf_get_arrival(sf_sim *s, int32_t env, int32_t *out)
+{
+    if (!s || !out) return fail(SF_EINVAL, "sf_get_arrival: null argument");
+    if (!s->arrival1) return fail(SF_ESTATE, "sf_get_arrival: call sf_enable_arrival first");
+    const Geo &g = s->g;
+    if (env < 0 || env >= g.E) return fail(SF_EINVAL, "sf_get_arrival: environment %d out of range", env);
+    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
+    HIPCHK(hipMemcpy2DAsync(out, (size_t)g.W * 4, s->arrival1 + (size_t)env * g.plane_env, (size_t)g.P * 4, (size_t)g.W * 4, (size_t)g.H,
+                            hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    { int rc = check_team_error(s, "sf_get_arrival"); if (rc) return rc; }
+    for (size_t i = 0, n = (size_t)g.H * g.W; i < n; ++i) out[i] -= 1;      // stored: update + 1, 0 = never
+    return SF_OK;
+}
+
+extern "C" int sf_arrival_device(sf_sim *s, void **ptr, int64_t *row_pitch, int64_t *env_stride)
+{
+    if (!s || !ptr || !row_pitch || !env_stride) return fail(SF_EINVAL, "sf_arrival_device: null argument");
+    if (!s->arrival1) return fail(SF_ESTATE, "sf_arrival_device: call sf_enable_arrival first");
+    *ptr = s->arrival1; *row_pitch = (int64_t)s->g.P * 4; *env_stride = (int64_t)s->g.plane_env * 4;
+    return SF_OK;
+}
+
+extern "C" int sf_set_arrival_dense(sf_sim *s, int32_t on)
+{
+    if (!s) return fail(SF_EINVAL, "sf_set_arrival_dense: null handle");
+    s->arr_dense = on != 0;
+    return SF_OK;
+}
+
+extern "C" int sf_time_arrival_pass(sf_sim *s, float *ms_out)
+{
+    if (!s || !ms_out) return fail(SF_EINVAL, "sf_time_arrival_pass: null argument");
+    if (!s->arrival1) return fail(SF_ESTATE, "sf_time_arrival_pass: call sf_enable_arrival first");
+    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
+    { int rc = ensure_commit(s); if (rc) return rc; }      // (not part of the pass's time)
+    HIPCHK(hipEventRecord(s->ev0, s->stream));
+    { int rc = arrival_pass(s); if (rc) return rc; }
+    HIPCHK(hipEventRecord(s->ev1, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipEventElapsedTime(ms_out, s->ev0, s->ev1));
+    return SF_OK;
+}
+
+extern "C" int sf_get_arrival_passes(sf_sim *s, int64_t *out)
+{
+    if (!s || !out) return fail(SF_EINVAL, "sf_get_arrival_passes: null argument");
+    out[0] = s->arr_passes[0]; out[1] = s->arr_passes[1];
     return SF_OK;
 }
 
@@ -2130,6 +2291,7 @@ extern "C" int sf_step_mitigated(sf_sim *s, int32_t n_steps, const int32_t *pts,
     int rc = SF_OK;
     const bool was_async = s->async;
     s->async = true;
+    s->arr_hold = true;                // (arrival recording: a pass every max_fire_duration pairs and one behind the last, not one per pair)
     float total = 0.f;
     for (int i = 0; i < n_steps; ++i) {
         hipLaunchKernelGGL(k_expand_pts, dim3((unsigned)((g.E * k + 255) / 256)), dim3(256), 0, s->stream, g.E, k,
@@ -2141,6 +2303,8 @@ extern "C" int sf_step_mitigated(sf_sim *s, int32_t n_steps, const int32_t *pts,
         if (rc) break;
         total += ms1;
     }
+    s->arr_hold = false;
+    if (!rc && s->arr_pending) rc = arrival_pass(s);
     s->async = was_async;
     if (rc) return rc;
     if (ms_out) *ms_out = total;
@@ -2187,6 +2351,7 @@ extern "C" int sf_loop_start(sf_sim *s, int32_t k)
     // sleeping loop.  (A stream with a CU mask - hipExtStreamCreateWithCUMask - was tried first: such a stream is a BLOCKING one, a kernel
     // on torch's default stream then waits for the resident loop to leave; profiles/cu_mask_probe.hip has the mask's numbering.)
     const int light = s->tune.v[SF_TUNE_LOOP_LIGHT] > 0 ? 1 : 0;
+    if (s->arrival1) return fail(SF_ENOTSUP, "sf_loop_start: not while arrival times are recorded (sf_enable_arrival): a closed loop has no launch boundary for the pass");
     if (g.ab != 1 || s->generic || g.VW != 1 || s->graph_on || s->history || g.dense || g.H > 16 * 64 || g.E > s->n_cu ||
         (s->fused_mode >= 0 && s->fused_mode != 2))
         return fail(SF_ENOTSUP, "sf_loop_start: needs the environment-resident launch with every environment resident at once "
@@ -2543,7 +2708,7 @@ extern "C" int sf_copy_envs(sf_sim *s, const int32_t *src, const int32_t *dst, i
     // the next step rebuild them for every environment.
     CopyList L;
     const bool terrain = (flags & SF_COPY_TERRAIN) && s->rt_set.size() > 1;      // (a stale rtc copy stays marked stale below)
-    L.n_seg = env_segs(s, terrain ? kForkKinds : kForkKinds & ~kSegTerrain, L.seg);
+    L.n_seg = arrival_seg(s, L.seg, env_segs(s, terrain ? kForkKinds : kForkKinds & ~kSegTerrain, L.seg));
     const unsigned gx = seg_grid_x(L.seg, L.n_seg);
     for (int i0 = 0; i0 < n; i0 += kCopyPairs) {
         const int cnt = std::min(kCopyPairs, n - i0);
@@ -2577,10 +2742,10 @@ static StateHeader state_header(const sf_sim *s)
     StateHeader h;
     memset(&h, 0, sizeof h);
     h.magic = kStateMagic; h.version = kStateVersion;
-    h.bytes = state_layout(g, s->parents != nullptr).bytes;
+    h.bytes = state_layout(g, s->parents != nullptr, s->arrival1 != nullptr).bytes;
     h.H = g.H; h.W = g.W; h.md = g.md; h.ab = g.ab;
     h.diag = g.diag; h.att = g.att; h.has_max_time = g.has_max_time; h.prune_after_quit = g.prune_after_quit;
-    h.has_parents = s->parents != nullptr; h.fire_rows = s->fire_rows;
+    h.has_parents = s->parents != nullptr; h.fire_rows = s->fire_rows; h.has_arrival = s->arrival1 != nullptr;
     h.max_time = g.has_max_time ? g.max_time : 0.0; h.update_rate = g.update_rate; h.pixel_scale = g.pixel_scale;
     return h;
 }
@@ -2601,6 +2766,7 @@ static int header_check(const sf_sim *s, const StateHeader &b, int i)
     else if (b.pixel_scale != h.pixel_scale) what = "pixel_scale threshold";
     else if (b.prune_after_quit != h.prune_after_quit) what = "prune_after_quit";
     else if (b.has_parents != h.has_parents) what = "spread graph";
+    else if (b.has_arrival != h.has_arrival) what = "arrival recording";
     else if (b.bytes != h.bytes) what = "size";
     if (what) return fail(SF_EINVAL, "sf_load_state: blob %d does not match this handle: %s", i, what);
     return SF_OK;
@@ -2620,9 +2786,9 @@ static StateArgs state_args(sf_sim *s)
     memset(&a, 0, sizeof a);
     a.g = s->g;
     a.status = s->status; a.age = s->age; a.cells = s->bl_cur ? s->cells : nullptr;
-    a.burn = s->burn; a.settled = s->settled; a.parents = s->parents; a.vbits = s->vbits;
+    a.burn = s->burn; a.settled = s->settled; a.parents = s->parents; a.arrival = s->arrival1; a.vbits = s->vbits;
     a.commit = s->commit; a.res_block = s->status_block; a.res_sink = s->sink; a.res_elapsed = s->elapsed_dev;
-    a.lay = state_layout(s->g, s->parents != nullptr);
+    a.lay = state_layout(s->g, s->parents != nullptr, s->arrival1 != nullptr);
     a.stride = a.lay.bytes;
     return a;
 }
@@ -2657,7 +2823,7 @@ static int reset_launch(sf_sim *s, const int32_t *envs_dev, const uint8_t *mask,
     // the tile histograms of a reset environment are known (all UNBURNED, the ignition's tile to be recounted) unless every histogram
     // of the handle is marked stale anyway: reset_range's condition for a partial reset
     const bool hist_known = g.ab == 1 && !s->generic && !s->tdirty_all;
-    a.n_seg = env_segs(s, kResetKinds & ~(seams ? 0u : kSegSeam) & ~(hist_known ? 0u : kSegHist), a.seg);
+    a.n_seg = arrival_seg(s, a.seg, env_segs(s, kResetKinds & ~(seams ? 0u : kSegSeam) & ~(hist_known ? 0u : kSegHist), a.seg));
     a.envs = envs_dev; a.mask = mask; a.xy = xy_dev; a.n = n;
     a.status = s->status; a.age = s->age; a.cells = s->bl_cur ? s->cells : nullptr;
     a.commit = s->commit; a.tflags = s->tflags; a.ring = s->ring; a.vbits = s->vbits; a.win_hint = s->win_hint;
@@ -2672,7 +2838,7 @@ static int reset_launch(sf_sim *s, const int32_t *envs_dev, const uint8_t *mask,
     HIPCHK(hipGetLastError());
     if (s->rs_timed) { HIPCHK(hipEventRecord(s->ev1, s->stream)); s->rs_have_ms = true; }
     if (!hist_known) s->tdirty_all = true;
-    return SF_OK;
+    return arrival_pass(s);             // the ignitions are the sprites of update 0 (recording off: nothing)
 }
 
 extern "C" int sf_time_resets(sf_sim *s, int32_t on)
@@ -2897,7 +3063,7 @@ extern "C" int sf_agents_step(sf_sim *s, const int32_t *device_actions, const sf
 extern "C" int sf_state_bytes(sf_sim *s, int64_t *bytes_out)
 {
     if (!s || !bytes_out) return fail(SF_EINVAL, "sf_state_bytes: null argument");
-    *bytes_out = state_layout(s->g, s->parents != nullptr).bytes;
+    *bytes_out = state_layout(s->g, s->parents != nullptr, s->arrival1 != nullptr).bytes;
     return SF_OK;
 }
 
@@ -2943,7 +3109,7 @@ extern "C" int sf_load_state(sf_sim *s, int32_t n, const int32_t *envs, const vo
     { int rc = state_list(s, n, envs, in, device_pointer, "sf_load_state", true); if (rc) return rc; }
     if (n == 0) return SF_OK;
     HIPCHK(hipSetDevice(s->p.device));
-    const long long bytes = state_layout(s->g, s->parents != nullptr).bytes;
+    const long long bytes = state_layout(s->g, s->parents != nullptr, s->arrival1 != nullptr).bytes;
     // every header is looked at before anything changes (a refused call leaves the handle as it was)
     std::vector<StateHeader> hdr((size_t)n);
     if (device_pointer) {

@@ -40,6 +40,7 @@ class FireEngine:
         self.prune_after_quit = False
         self.spread_graph = self.spread_graph_on = False
         self.async_mode = False
+        self.arrival_on = False             # arrival times are recorded (enable_arrival)
         self.n_agents = 0                   # agents per environment (agents_create); 0: no agent state
         self._blobs_in_flight = []          # device state blobs an enqueued save / load may still touch (async mode; released by sync)
         self._h = C.c_void_p()
@@ -779,6 +780,50 @@ class FireEngine:
         if out.shape[0]:
             self._chk(self._L.sf_get_history(self._h, int(env), int(first), int(count), _ptr(out)))
         return out
+
+    # ---------------------------------------------------------------- arrival times
+    def enable_arrival(self, on=True):
+        """Record for every cell the update that created its first sprite (``sf_enable_arrival``): kept by a pass behind the step
+        launches, a call of n updates then runs in pieces of at most ``max_fire_duration``.  Allowed at any time: cells that burned
+        out earlier stay "never", sprites live now carry their true update.  ``on=False`` frees the plane."""
+        self._chk(self._L.sf_enable_arrival(self._h, int(bool(on))))
+        self.arrival_on = bool(on)
+
+    def arrival(self, env=0):
+        """int32 [H, W]: the update that ignited each cell of ``env`` - 0 the reset's ignition, -1 never (``sf_get_arrival``).
+        An update index, not minutes."""
+        out = np.empty((self.H, self.W), dtype=np.int32)
+        self._chk(self._L.sf_get_arrival(self._h, int(env), _ptr(out)))
+        return out
+
+    def arrival_torch(self):
+        """Zero-copy view of the raw plane as a torch int32 tensor [n_envs, H, W] on this GPU: update + 1, 0 = never
+        (``sf_arrival_device``).  Read-only; the handle's stream is waited for first.  Valid until ``enable_arrival(False)``."""
+        import torch
+        p, pitch, stride = C.c_void_p(), C.c_int64(), C.c_int64()
+        self._chk(self._L.sf_arrival_device(self._h, C.byref(p), C.byref(pitch), C.byref(stride)))
+        self.sync()
+        shape, strides = (self.n_envs, self.H, self.W), (int(stride.value), int(pitch.value), 4)
+
+        class _Plane:
+            __cuda_array_interface__ = {"shape": shape, "typestr": "<i4", "data": (p.value, False), "version": 2, "strides": strides}
+        return torch.as_tensor(_Plane(), device=f"cuda:{self.params.device}")
+
+    def set_arrival_dense(self, on=True):
+        """Laboratory: the arrival pass always in its dense form (one thread per cell) instead of walking the vector bitmap."""
+        self._chk(self._L.sf_set_arrival_dense(self._h, int(bool(on))))
+
+    def time_arrival_pass(self):
+        """Laboratory: GPU milliseconds of one more arrival pass over the state as it stands (it changes nothing)."""
+        ms = C.c_float(0.0)
+        self._chk(self._L.sf_time_arrival_pass(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    def arrival_passes(self):
+        """Laboratory: (sparse, dense) arrival passes made since the handle was created."""
+        out = np.zeros(2, dtype=np.int64)
+        self._chk(self._L.sf_get_arrival_passes(self._h, _ptr(out)))
+        return int(out[0]), int(out[1])
 
     def set_generic(self, on=True):
         """Per-cell kernel instead of the tiled SWAR kernels (always on for max_fire_duration > 5)."""

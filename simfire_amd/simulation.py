@@ -209,6 +209,7 @@ class FireSimulation:
         self._device = device
         self._rendering = False
         self._recording = False
+        self._record_arrival = False
         self._frames: List[np.ndarray] = []
         #: ``render`` options of the frames ``recording`` keeps (scale, mode, background, contours, terrain_rgb)
         self.recording_options: Dict[str, object] = {}
@@ -248,6 +249,8 @@ class FireSimulation:
         x, y = cfg.fire.fire_initial_position
         if cfg.simulation.draw_spread_graph:
             self._engine.enable_spread_graph(True)
+        if self._record_arrival and not self._engine.arrival_on:      # (a rebuilt handle)
+            self._engine.enable_arrival(True)
         self._engine.reset([(x, y)])
         fresh = np.full(cfg.area.screen_size, int(BurnStatus.UNBURNED))               # int64, simulation.py:561-566
         fresh[y, x] = int(BurnStatus.BURNING)
@@ -277,6 +280,9 @@ class FireSimulation:
         neng.enable_spread_graph(eng.spread_graph_on)
         if eng.prune_after_quit:
             neng.set_prune_after_quit(True)
+        new._record_arrival = self._record_arrival
+        if eng.arrival_on:
+            neng.enable_arrival(True)
         if neng.params.pixel_scale != eng.params.pixel_scale:
             neng.set_threshold(eng.params.pixel_scale)
         neng.load_state([0], eng.save_state([0]))
@@ -628,6 +634,23 @@ class FireSimulation:
         self._recording = value
 
     @property
+    def record_arrival(self) -> bool:
+        """While True the device records, for every cell, the update that ignited it (``arrival_steps``).
+        It may be set at any time: cells that burned out before stay "never".  Setting it False frees the plane."""
+        return self._record_arrival
+
+    @record_arrival.setter
+    def record_arrival(self, value: bool) -> None:
+        self._record_arrival = bool(value)
+        self._engine.enable_arrival(self._record_arrival)
+
+    @property
+    def arrival_steps(self) -> np.ndarray:
+        """int32 [H, W]: the update (``elapsed_steps`` after it, counted from the reset) that ignited each cell - 0 the ignition
+        cell, -1 never.  An update index: ``elapsed_time`` does not advance on updates without a candidate.  Needs ``record_arrival``."""
+        return self._engine.arrival(0)
+
+    @property
     def frames(self) -> np.ndarray:
         """uint8 [k, H, W, 3]: the frames recorded since ``recording`` was last set True."""
         if not self._frames:
@@ -704,7 +727,7 @@ class SimState:
     def parse_header(raw: bytes) -> dict:
         if len(raw) < _STATE_HEADER.size:
             raise ValueError(f"state blob header: {len(raw)} bytes, need {_STATE_HEADER.size}")
-        (magic, version, nbytes, H, W, md, ab, diag, att, has_max_time, prune, has_parents, fire_rows, _r0, _r1,
+        (magic, version, nbytes, H, W, md, ab, diag, att, has_max_time, prune, has_parents, fire_rows, has_arrival, _r1,
          max_time, update_rate, pixel_scale) = _STATE_HEADER.unpack_from(raw)
         if magic != _STATE_MAGIC:
             raise ValueError("not a simfire state blob (magic number)")
@@ -712,7 +735,7 @@ class SimState:
             raise ValueError(f"state blob format version {version}; this library reads version {_STATE_VERSION}")
         return dict(bytes=nbytes, H=H, W=W, max_fire_duration=md, ab=ab, diagonal_spread=bool(diag), attenuate_line_ros=bool(att),
                     has_max_time=bool(has_max_time), max_time=max_time, update_rate=update_rate, pixel_scale=pixel_scale,
-                    prune_after_quit=bool(prune), spread_graph=bool(has_parents), fire_rows=fire_rows)
+                    prune_after_quit=bool(prune), spread_graph=bool(has_parents), fire_rows=fire_rows, arrival=bool(has_arrival))
 
     def check(self, engine: FireEngine) -> None:
         """ValueError unless every blob fits ``engine`` (the device checks the same header again)."""
@@ -720,7 +743,8 @@ class SimState:
         want = dict(H=engine.H, W=engine.W, max_fire_duration=p.max_fire_duration, diagonal_spread=bool(p.diagonal_spread),
                     attenuate_line_ros=bool(p.attenuate_line_ros), has_max_time=bool(p.has_max_time),
                     max_time=float(p.max_time) if p.has_max_time else 0.0, update_rate=float(p.update_rate),
-                    pixel_scale=float(p.pixel_scale), prune_after_quit=engine.prune_after_quit, spread_graph=engine.spread_graph)
+                    pixel_scale=float(p.pixel_scale), prune_after_quit=engine.prune_after_quit, spread_graph=engine.spread_graph,
+                    arrival=bool(getattr(engine, "arrival_on", False)))
         for i, h in enumerate(self.headers):
             for k, v in want.items():
                 if h[k] != v:
@@ -988,6 +1012,23 @@ class BatchedFireSimulation:
         fire = getattr(state, "fire_seeds", None)
         if fire is not None and "fire_initial_position" in self._seeds:
             self._seeds["fire_initial_position"][e] = fire
+
+    # ---- arrival times
+    def enable_arrival(self, on: bool = True) -> None:
+        """Record on the device, for every cell of every environment, the update that ignited it (``arrival``).  Allowed at any
+        time (cells that burned out before stay "never"); ends a running closed loop, and ``loop_start`` is refused while it is on.
+        ``clone_envs`` and ``get_state`` / ``set_state`` carry the planes."""
+        self._engine.enable_arrival(on)
+
+    def arrival(self, envs=None) -> np.ndarray:
+        """int32 [len(envs), H, W] (default: every environment): the update that ignited each cell, counted from the environment's
+        last reset - 0 its ignition cell, -1 never.  An update index, not minutes."""
+        e = range(self.n_envs) if envs is None else np.atleast_1d(np.asarray(envs, dtype=np.int64)).reshape(-1).tolist()
+        H, W = self.config.area.screen_size
+        out = np.empty((len(e), H, W), dtype=np.int32)
+        for i, env in enumerate(e):
+            out[i] = self._engine.arrival(int(env))
+        return out
 
     def run(self, time: Union[str, int], return_maps: bool = True):
         """Steps every environment that is still RUNNING; returns (fire_maps uint8 [E, H, W] or None,
