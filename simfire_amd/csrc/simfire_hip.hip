@@ -221,12 +221,11 @@ struct sf_sim {
     uint8_t *parents = nullptr;        // spread-graph parent masks, allocated by sf_enable_spread_graph
     bool graph_on = false;
     // sf_enable_arrival: the plane u32 [E][H][P] (update that created a cell's first sprite + 1, 0 = never; null =
-    // recording off), updates made since the last pass (< md between the pieces of a call, 0 between calls), whether the caller of the
-    // step path makes the closing pass itself (sf_step_mitigated's scatter + step pairs), the lab's "always the dense pass" and its
-    // count of passes made in the sparse / the dense form
+    // recording off), updates made since the last pass (< md between the pieces of a call, 0 between calls), the lab's "always the
+    // dense pass" and its count of passes made in the sparse / the dense form
     uint32_t *arrival1 = nullptr;
     int arr_pending = 0;
-    bool arr_hold = false, arr_dense = false;
+    bool arr_dense = false;
     int64_t arr_passes[2] = {0, 0};
     // sf_get_fire_map_delta: the fire maps as the host last saw them (u8 [E][H][P], allocated at the first call), per environment whether that
     // reference point exists, the list of changed cells on the device ([0] = count) and its pinned landing zone
@@ -280,10 +279,18 @@ struct sf_sim {
     int64_t bytes = 0;
 };
 
+// The host code of the step path has two layers.  The ENQUEUE layer (enqueue_steps, enqueue_call, enqueue_pair, stage_lines, step_impl,
+// refresh_status, scatter_points, delta_enqueue, reset_launch, arrival_pass) puts work on the handle's stream and keeps the handle's
+// bookkeeping: such a function never waits for the work of the call (growing a buffer that enqueued kernels may read is the one wait:
+// stage_lines, delta_enqueue) and never reads or writes `async` - what it needs to know it takes as an argument.  The CALL layer is the extern "C" entries: argument checks, one prologue (begin_call), enqueue-layer calls, one
+// epilogue (finish_call: the wait of a synchronous call, timing, the team-error check).  A composite entry (sf_rollout, sf_run_delta,
+// sf_agents_step, sf_step_mitigated) is made of enqueue-layer calls, never of other entries.
 static int ensure_commit(sf_sim *s);
-extern "C" int sf_loop_stop(sf_sim *s);
+static int loop_stop(sf_sim *s);
+static int comm_close(sf_sim *s);
+static int destroy(sf_sim *s);
 // every entry point except sf_loop_step ends the closed loop (sf_loop_start) first: the handle's stream is busy with the resident launch
-#define LOOP_QUIESCE(s) do { if ((s)->loop_on) { int _rq = sf_loop_stop(s); if (_rq) return _rq; } } while (0)
+#define LOOP_QUIESCE(s) do { if ((s)->loop_on) { int _rq = loop_stop(s); if (_rq) return _rq; } } while (0)
 static int ensure_rm(sf_sim *s);
 static int alloc_bl(sf_sim *s);
 static bool prefers_bl(const sf_sim *s);
@@ -298,6 +305,41 @@ static int check_team_error(const sf_sim *s, const char *where)
     if (s->xerr_pinned && *s->xerr_pinned)
         return fail(SF_EHIP, "%s: a workgroup of a team launch (k_run<TEAM>) gave up waiting for a team member; the state of this handle is void until every environment is reset", where);
     return SF_OK;
+}
+
+// The prologue of a call (call layer): what the handle must have been given (SF_ESTATE before anything else happens), the device, the
+// end of a closed loop, then - where asked for - the refusal of a handle a failed team launch has voided and the step rings folded
+// into commit[] (after which tmp / flags carry nothing: the next launch starts from commit).
+enum { kNeedRt = 1, kNeedReset = 2, kNotVoid = 4, kCommit = 8, kStateCall = kNeedReset | kNotVoid | kCommit };
+static int check_ready(const sf_sim *s, const char *who, int need)
+{
+    if ((need & kNeedRt) && !s->have_rt) return fail(SF_ESTATE, "%s: call sf_set_layers or sf_set_rtable first", who);
+    if ((need & kNeedReset) && !s->was_reset) return fail(SF_ESTATE, "%s: call sf_reset first", who);
+    return SF_OK;
+}
+static int begin_call(sf_sim *s, const char *who, int need)
+{
+    { int rc = check_ready(s, who, need); if (rc) return rc; }
+    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
+    if (need & kNotVoid) { int rc = check_team_error(s, who); if (rc) return rc; }
+    return (need & kCommit) ? ensure_commit(s) : SF_OK;
+}
+// The epilogue of a call: with `ms`, the GPU time between ev0 (recorded by the enqueue layer in front of the step launches) and here;
+// the wait where the call waits (a timed call always does), and behind it the look at the team launches' error word - under the name
+// `who`; without one (entries outside the step path that wait and have never looked) the wait alone.
+static int finish_call(sf_sim *s, const char *who, bool wait, float *ms)
+{
+    if (ms) HIPCHK(hipEventRecord(s->ev1, s->stream));
+    HIPCHK(hipGetLastError());
+    if (!wait && !ms) return SF_OK;
+    HIPCHK(hipStreamSynchronize(s->stream));
+    if (ms) HIPCHK(hipEventElapsedTime(ms, s->ev0, s->ev1));
+    return who ? check_team_error(s, who) : SF_OK;
+}
+// A look at the result of a single update (a status query, a delta query): what makes step(1) + look pairs a run(1) loop.
+static void note_result_look(sf_sim *s)
+{
+    if (s->last_was_step1) { s->last_was_step1 = false; if (s->step1_polls < 1000) s->step1_polls++; }
 }
 
 // The environment list of a batched call: every entry names an environment of the handle and, where `twice` is given (the words of
@@ -421,8 +463,8 @@ extern "C" int sf_create(const sf_params *p, sf_sim **out)
     choose_rows_per_band(g, rb);
 
     int rc;
-#define TRY(x) do { rc = (x); if (rc != SF_OK) { sf_destroy(s); return rc; } } while (0)
-#define TRYHIP(x) do { hipError_t _e = (x); if (_e != hipSuccess) { sf_destroy(s); return fail(SF_EHIP, "%s failed: %s", #x, hipGetErrorString(_e)); } } while (0)
+#define TRY(x) do { rc = (x); if (rc != SF_OK) { destroy(s); return rc; } } while (0)
+#define TRYHIP(x) do { hipError_t _e = (x); if (_e != hipSuccess) { destroy(s); return fail(SF_EHIP, "%s failed: %s", #x, hipGetErrorString(_e)); } } while (0)
     if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) { delete s; return fail(SF_EHIP, "hipStreamCreate failed"); }
     TRYHIP(hipEventCreate(&s->ev0)); TRYHIP(hipEventCreate(&s->ev1));
     for (int i = 0; i < sf_sim::kPtsRing; ++i) TRYHIP(hipEventCreate(&s->ev_pts[i]));
@@ -484,13 +526,14 @@ extern "C" int sf_create(const sf_params *p, sf_sim **out)
     return SF_OK;
 }
 
-extern "C" int sf_destroy(sf_sim *s)
+extern "C" int sf_destroy(sf_sim *s) { return destroy(s); }
+static int destroy(sf_sim *s)
 {
     if (!s) return SF_OK;
     hipSetDevice(s->p.device);
-    if (s->loop_on) (void)sf_loop_stop(s);
+    if (s->loop_on) (void)loop_stop(s);
     if (s->stream) hipStreamSynchronize(s->stream);
-    if (s->comm) (void)sf_comm_destroy(s);
+    (void)comm_close(s);
     if (s->xerr_pinned) (void)hipHostFree(s->xerr_pinned);
     for (void *hp : {(void *)s->loop_db, (void *)s->loop_res, (void *)s->loop_pts}) if (hp) (void)hipHostFree(hp);
     for (void *dp : {(void *)s->loop_mem, (void *)s->loop_pts_mem}) if (dp) (void)hipFree(dp);
@@ -596,10 +639,7 @@ extern "C" int sf_sync(sf_sim *s)
 {
     if (!s) return fail(SF_EINVAL, "sf_sync: null handle");
     HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    HIPCHK(hipStreamSynchronize(s->stream));
-    if (s->xerr_pinned && *s->xerr_pinned)
-        return fail(SF_EHIP, "sf_sync: a workgroup of a team launch (k_run<TEAM>) gave up waiting for a team member; the state of this handle is void");
-    return SF_OK;
+    return finish_call(s, "sf_sync", true, nullptr);
 }
 
 /* Spread graph (FireSpreadGraph, simfire/utils/graph.py): record for every ignition which of the 8
@@ -1164,7 +1204,7 @@ extern "C" int sf_reset_env(sf_sim *s, int32_t env, int32_t x, int32_t y)
 
 // rows (env, column, row, type) in device memory -> the two scatter kernels (clear, then write with the
 // type precedence of simulation.py:449-478); rows with an out-of-range field are skipped by the kernels
-static int scatter_points(sf_sim *s, const int32_t *pts_dev, int n, bool sync)
+static int scatter_points(sf_sim *s, const int32_t *pts_dev, int n)
 {
     const Geo &g = s->g;
     uint8_t *cells = s->bl_cur ? s->cells : nullptr;
@@ -1177,7 +1217,6 @@ static int scatter_points(sf_sim *s, const int32_t *pts_dev, int n, bool sync)
                        (const EnvState *)s->commit, (const EnvState *)s->tmp, (const uint32_t *)s->flags, s->seq,
                        s->committed ? 1 : 0, pts_dev, n);
     HIPCHK(hipGetLastError());
-    if (sync && !s->async) HIPCHK(hipStreamSynchronize(s->stream));
     return SF_OK;
 }
 
@@ -1212,11 +1251,10 @@ extern "C" int sf_apply_mitigation(sf_sim *s, const int32_t *pts, int32_t n)
     // KB over the host link; no copy to enqueue).  It may still feed kernels enqueued kPtsRing calls ago.
     HIPCHK(hipEventSynchronize(s->ev_pts[slot]));
     memcpy(s->pts_pinned[slot], pts, bytes);
-    int rc = scatter_points(s, s->pts_mapped[slot], n, /*sync=*/false);
+    int rc = scatter_points(s, s->pts_mapped[slot], n);
     if (rc) return rc;
     HIPCHK(hipEventRecord(s->ev_pts[slot], s->stream));
-    if (!s->async) HIPCHK(hipStreamSynchronize(s->stream));
-    return SF_OK;
+    return finish_call(s, nullptr, !s->async, nullptr);
 }
 
 extern "C" int sf_apply_mitigation_device(sf_sim *s, const int32_t *device_pts, int32_t n)
@@ -1225,7 +1263,8 @@ extern "C" int sf_apply_mitigation_device(sf_sim *s, const int32_t *device_pts, 
     if (n < 0 || (n > 0 && !device_pts)) return fail(SF_EINVAL, "sf_apply_mitigation_device: bad point list");
     if (n == 0) return SF_OK;
     HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    return scatter_points(s, device_pts, n, true);
+    const int rc = scatter_points(s, device_pts, n);
+    return rc ? rc : finish_call(s, nullptr, !s->async, nullptr);
 }
 
 extern "C" int sf_load_fire_map(sf_sim *s, int32_t env, const uint8_t *map)
@@ -1935,9 +1974,10 @@ static int run_resident(sf_sim *s, const StepPlan &p, StepArgs &a, int n_steps, 
     return SF_OK;
 }
 
-// A sf_step call as planned: the buffers its launches need, then the resident rollout or the per-step loop.  mit_dev / mit_k: control
-// lines inside the resident launch (p planned with lines).
-static int run_step_once(sf_sim *s, StepPlan p, int n_steps, float *ms, const int32_t *mit_dev, int mit_k)
+// Updates as planned (enqueue layer): the buffers their launches need, then the resident rollout or the per-step loop.  mit_dev / mit_k:
+// control lines inside the resident launch (p planned with lines).  t0 (may be null): an event recorded in front of the step launches,
+// behind the buffers' rebuilds - where a timed call's GPU time starts.
+static int enqueue_steps(sf_sim *s, StepPlan p, int n_steps, const int32_t *mit_dev, int mit_k, hipEvent_t t0)
 {
     const Geo &g = s->g;
     const Tuning &tn = s->tune;
@@ -1974,7 +2014,7 @@ static int run_step_once(sf_sim *s, StepPlan p, int n_steps, float *ms, const in
     a.mit = mit_dev; a.mit_k = mit_k;
     a.win = p.win;
     if (p.nw && p.win) { a.rtc = s->rtc; a.win_hint = s->win_hint; }
-    if (ms) HIPCHK(hipEventRecord(s->ev0, s->stream));
+    if (t0) HIPCHK(hipEventRecord(t0, s->stream));
     if (p.nw) {
         int rc0 = run_resident(s, p, a, n_steps, row_was_fresh);
         if (rc0) return rc0;
@@ -2016,63 +2056,55 @@ static int run_step_once(sf_sim *s, StepPlan p, int n_steps, float *ms, const in
     }
     if (s->fire_rows > 0) { const long long fr = (long long)s->fire_rows + 2LL * n_requested; s->fire_rows = fr > g.H ? g.H : (int)fr; }
     s->last_was_step1 = n_requested == 1 && !mit_dev;
-    if (ms) HIPCHK(hipEventRecord(s->ev1, s->stream));
     // no commit here: the states stay in the rings until something asks for them (ensure_commit)
-    HIPCHK(hipGetLastError());
-    if (ms || !s->async) HIPCHK(hipStreamSynchronize(s->stream));
-    if (ms) HIPCHK(hipEventElapsedTime(ms, s->ev0, s->ev1));
-    if ((ms || !s->async) && s->xerr_pinned && *s->xerr_pinned)
-        return fail(SF_EHIP, "sf_step: a workgroup of a team launch (k_run<TEAM>) gave up waiting for a team member; the state of this handle is void");
     return SF_OK;
 }
 
-// What every stepping call goes through.  Recording off (sf_enable_arrival): the call as planned, nothing else.  Recording on: the
-// updates in pieces of at most max_fire_duration - of even length, each planned as a call of its length would be (a piece of the
+// What the updates of every stepping call go through (enqueue layer).  Recording off (sf_enable_arrival): as planned, nothing else.
+// Recording on: in pieces of at most max_fire_duration - of even length, each planned as a call of its length would be (a piece of the
 // point block with it) and followed by the arrival pass -, so that every sprite is still in the masks when a pass looks (DESIGN.md
-// section 17).  The pieces only enqueue; timing and the one wait of a synchronous call span all of them.
-static int run_step(sf_sim *s, const StepPlan &p, int n_steps, float *ms, const int32_t *mit_dev, int mit_k)
+// section 17).  hold: the caller makes the closing pass itself (the scatter + step pairs of enqueue_pair): a pass every
+// max_fire_duration updates only.  t0 then stands in front of all the pieces.
+static int enqueue_call(sf_sim *s, const StepPlan &p, int n_steps, const int32_t *mit_dev, int mit_k, bool hold, hipEvent_t t0)
 {
-    if (!s->arrival1) return run_step_once(s, p, n_steps, ms, mit_dev, mit_k);
+    if (!s->arrival1) return enqueue_steps(s, p, n_steps, mit_dev, mit_k, t0);
     const Geo &g = s->g;
-    const bool was_async = s->async;
-    s->async = true;
     int rc = SF_OK, launches = 0;
-    if (ms && hipEventRecord(s->ev0, s->stream) != hipSuccess) rc = fail(SF_EHIP, "sf_step: hipEventRecord failed");
+    if (t0 && hipEventRecord(t0, s->stream) != hipSuccess) rc = fail(SF_EHIP, "sf_step: hipEventRecord failed");
     for (int done = 0; done < n_steps && !rc;) {
         if (s->arr_pending >= g.md) { rc = arrival_pass(s); continue; }      // (a call that failed half way left them behind)
         const int room = g.md - s->arr_pending;
         const int pieces = (n_steps - done + room - 1) / room;
-        const int c = s->arr_hold ? std::min(n_steps - done, room) : (n_steps - done + pieces - 1) / pieces;
+        const int c = hold ? std::min(n_steps - done, room) : (n_steps - done + pieces - 1) / pieces;
         const StepPlan pc = c == n_steps ? p : plan_step(s, c, mit_dev != nullptr);
         if (mit_dev && !pc.nw) { rc = fail(SF_EHIP, "sf_step_mitigated: a piece of %d updates was not planned as a resident launch", c); break; }
-        rc = run_step_once(s, pc, c, nullptr, mit_dev ? mit_dev + (size_t)done * g.E * mit_k * 3 : nullptr, mit_k);
+        rc = enqueue_steps(s, pc, c, mit_dev ? mit_dev + (size_t)done * g.E * mit_k * 3 : nullptr, mit_k, nullptr);
         launches += s->last_launches;
         s->arr_pending += c;
         done += c;
-        if (!rc && (!s->arr_hold || s->arr_pending >= g.md)) rc = arrival_pass(s);      // behind every piece; a caller that holds: every md updates
+        if (!rc && (!hold || s->arr_pending >= g.md)) rc = arrival_pass(s);      // behind every piece; a caller that holds: every md updates
     }
-    s->async = was_async;
     s->last_launches = launches;
     s->last_was_step1 = n_steps == 1 && !mit_dev;
-    if (rc) return rc;
-    if (ms) HIPCHK(hipEventRecord(s->ev1, s->stream));
-    if (ms || !s->async) HIPCHK(hipStreamSynchronize(s->stream));
-    if (ms) HIPCHK(hipEventElapsedTime(ms, s->ev0, s->ev1));
-    if ((ms || !s->async) && s->xerr_pinned && *s->xerr_pinned)
-        return fail(SF_EHIP, "sf_step: a workgroup of a team launch (k_run<TEAM>) gave up waiting for a team member; the state of this handle is void");
-    return SF_OK;
+    return rc;
 }
 
-static int step_impl(sf_sim *s, int n_steps, float *ms)
+// Plan + enqueue: n plain updates (enqueue layer; none: nothing).
+static int step_impl(sf_sim *s, int n_steps, bool hold, hipEvent_t t0)
 {
-    if (!s) return fail(SF_EINVAL, "sf_step: null handle");
-    if (n_steps < 0) return fail(SF_EINVAL, "sf_step: n_steps must be >= 0");
-    if (!s->have_rt) return fail(SF_ESTATE, "sf_step: call sf_set_layers or sf_set_rtable first");
-    if (!s->was_reset) return fail(SF_ESTATE, "sf_step: call sf_reset first");
+    return n_steps == 0 ? SF_OK : enqueue_call(s, plan_step(s, n_steps, false), n_steps, nullptr, 0, hold, t0);
+}
+
+// sf_step / sf_step_timed / sf_step_mitigated without points (call layer behind their argument checks).  No updates: the handle's
+// readiness is still looked at, and nothing else happens - a closed loop keeps running.
+static int step_call(sf_sim *s, const char *who, int n_steps, float *ms)
+{
+    if (n_steps < 0) return fail(SF_EINVAL, "%s: n_steps must be >= 0", who);
     if (ms) *ms = 0.f;
-    if (n_steps == 0) return SF_OK;
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    return run_step(s, plan_step(s, n_steps, false), n_steps, ms, nullptr, 0);
+    if (n_steps == 0) return check_ready(s, who, kNeedRt | kNeedReset);
+    { int rc = begin_call(s, who, kNeedRt | kNeedReset); if (rc) return rc; }
+    { int rc = step_impl(s, n_steps, false, ms ? s->ev0 : nullptr); if (rc) return rc; }
+    return finish_call(s, who, !s->async, ms);
 }
 
 // The per-update history FireSimulation._save_data appends to fire_map.npy (simulation.py:548-549,
@@ -2121,7 +2153,7 @@ extern "C" int sf_history_device(sf_sim *s, void **ptr, int32_t *capacity)
 }
 
 // Arrival times: which update created the first sprite of a cell (fire.py:571-587), kept by a pass behind the
-// step launches (arrival_pass; run_step cuts a call into pieces of at most max_fire_duration updates while this is on).
+// step launches (arrival_pass; enqueue_call cuts a call into pieces of at most max_fire_duration updates while this is on).
 extern "C" int sf_enable_arrival(sf_sim *s, int32_t on)
 {
     if (!s) return fail(SF_EINVAL, "sf_enable_arrival: null handle");
@@ -2140,8 +2172,7 @@ extern "C" int sf_enable_arrival(sf_sim *s, int32_t on)
     HIPCHK(hipMemsetAsync(s->arrival1, 0, n * sizeof(uint32_t), s->stream));
     s->arr_pending = 0;
     if (s->was_reset) { int rc = arrival_pass(s); if (rc) return rc; }      // the sprites that are live now carry their true updates
-    if (!s->async) HIPCHK(hipStreamSynchronize(s->stream));
-    return SF_OK;
+    return finish_call(s, nullptr, !s->async, nullptr);
 }
 
 extern "C" int sf_get_arrival(sf_sim *s, int32_t env, int32_t *out)
@@ -2178,14 +2209,10 @@ extern "C" int sf_time_arrival_pass(sf_sim *s, float *ms_out)
 {
     if (!s || !ms_out) return fail(SF_EINVAL, "sf_time_arrival_pass: null argument");
     if (!s->arrival1) return fail(SF_ESTATE, "sf_time_arrival_pass: call sf_enable_arrival first");
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    { int rc = ensure_commit(s); if (rc) return rc; }      // (not part of the pass's time)
+    { int rc = begin_call(s, "sf_time_arrival_pass", kCommit); if (rc) return rc; }      // (the commit is not part of the pass's time)
     HIPCHK(hipEventRecord(s->ev0, s->stream));
     { int rc = arrival_pass(s); if (rc) return rc; }
-    HIPCHK(hipEventRecord(s->ev1, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    HIPCHK(hipEventElapsedTime(ms_out, s->ev0, s->ev1));
-    return SF_OK;
+    return finish_call(s, nullptr, true, ms_out);
 }
 
 extern "C" int sf_get_arrival_passes(sf_sim *s, int64_t *out)
@@ -2234,11 +2261,15 @@ extern "C" int sf_debug_phases(unsigned long long *out16)
 }
 #endif
 
-extern "C" int sf_step(sf_sim *s, int32_t n_steps) { return step_impl(s, n_steps, nullptr); }
+extern "C" int sf_step(sf_sim *s, int32_t n_steps)
+{
+    if (!s) return fail(SF_EINVAL, "sf_step: null handle");
+    return step_call(s, "sf_step", n_steps, nullptr);
+}
 extern "C" int sf_step_timed(sf_sim *s, int32_t n_steps, float *ms_out)
 {
-    if (!ms_out) return fail(SF_EINVAL, "sf_step_timed: null ms_out");
-    return step_impl(s, n_steps, ms_out);
+    if (!s || !ms_out) return fail(SF_EINVAL, "sf_step_timed: null argument");
+    return step_call(s, "sf_step_timed", n_steps, ms_out);
 }
 
 // rows (env, column, row, type) of one step out of a point block [n_steps][E][k][3]
@@ -2247,6 +2278,41 @@ __global__ void k_expand_pts(int E, int k, const int32_t *blk, int32_t *rows)
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= E * k) return;
     rows[4 * i] = i / k; rows[4 * i + 1] = blk[3 * i]; rows[4 * i + 2] = blk[3 * i + 1]; rows[4 * i + 3] = blk[3 * i + 2];
+}
+
+// The point block of a sf_step_mitigated call on the device (enqueue layer; a host block is copied behind the rows [E * k][4] of one step, which
+// the pairs expand into at the head of mit_stage).  Growing the staging buffer waits for the stream: enqueued kernels may read it.
+static int stage_lines(sf_sim *s, int n_steps, const int32_t *pts, int k, int device_pointer, const int32_t **blk)
+{
+    const Geo &g = s->g;
+    const size_t rows_bytes = (size_t)g.E * k * 4 * sizeof(int32_t);
+    const size_t blk_bytes = device_pointer ? 0 : (size_t)n_steps * g.E * k * 3 * sizeof(int32_t);
+    if (blk_bytes + rows_bytes > s->mit_stage_bytes) {
+        HIPCHK(hipStreamSynchronize(s->stream));
+        if (s->mit_stage) HIPCHK(hipFree(s->mit_stage));
+        s->mit_stage = nullptr; s->mit_stage_bytes = 0;
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&s->mit_stage), blk_bytes + rows_bytes));
+        s->mit_stage_bytes = blk_bytes + rows_bytes;
+    }
+    *blk = pts;
+    if (!device_pointer) {
+        int32_t *d = s->mit_stage + (size_t)g.E * k * 4;
+        HIPCHK(hipMemcpyAsync(d, pts, blk_bytes, hipMemcpyHostToDevice, s->stream));
+        *blk = d;
+    }
+    return SF_OK;
+}
+// Step i of a call with control lines that the resident launch cannot take (enqueue layer): scatter the step's points, then one update.
+// The bookkeeping is that of a call with control lines, whichever way it runs: its single updates are not a run(1) loop.  Arrival
+// recording: a pass every max_fire_duration pairs; the one behind the last pair is the caller's (arr_pending != 0).
+static int enqueue_pair(sf_sim *s, const int32_t *blk, int k, int i, hipEvent_t t0)
+{
+    const Geo &g = s->g;
+    if (i == 0) { s->status_fresh = false; s->last_launches = 0; s->step1_polls = 0; }
+    hipLaunchKernelGGL(k_expand_pts, dim3((unsigned)((g.E * k + 255) / 256)), dim3(256), 0, s->stream, g.E, k,
+                       blk + (size_t)i * g.E * k * 3, s->mit_stage);
+    const int rc = scatter_points(s, s->mit_stage, g.E * k);
+    return rc ? rc : step_impl(s, 1, /*hold=*/true, t0);
 }
 
 /* A rollout in which control lines are drawn before every update - the loop
@@ -2258,58 +2324,29 @@ __global__ void k_expand_pts(int E, int k, const int32_t *blk, int32_t *rows)
  * environment's update; otherwise the call enqueues n_steps scatter + step pairs.  ms_out (may be null): GPU milliseconds. */
 extern "C" int sf_step_mitigated(sf_sim *s, int32_t n_steps, const int32_t *pts, int32_t k, int32_t device_pointer, float *ms_out)
 {
+    const char *who = "sf_step_mitigated";
     if (!s) return fail(SF_EINVAL, "sf_step_mitigated: null handle");
     if (n_steps < 0 || k < 0 || (n_steps > 0 && k > 0 && !pts)) return fail(SF_EINVAL, "sf_step_mitigated: bad arguments");
     if (ms_out) *ms_out = 0.f;
     if (n_steps == 0) return SF_OK;
-    if (k == 0) return step_impl(s, n_steps, ms_out);
-    if (!s->have_rt) return fail(SF_ESTATE, "sf_step: call sf_set_layers or sf_set_rtable first");
-    if (!s->was_reset) return fail(SF_ESTATE, "sf_step: call sf_reset first");
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
+    if (k == 0) return step_call(s, who, n_steps, ms_out);
+    { int rc = begin_call(s, who, kNeedRt | kNeedReset); if (rc) return rc; }
     const StepPlan plan = plan_step(s, n_steps, true);       // can the resident launch take the lines?  Otherwise scatter + step pairs
-    const Geo &g = s->g;
-    const size_t per_step = (size_t)g.E * k * 3, rows_bytes = (size_t)g.E * k * 4 * sizeof(int32_t);
-    const size_t blk_bytes = device_pointer ? 0 : (size_t)n_steps * per_step * sizeof(int32_t);
-    if (blk_bytes + rows_bytes > s->mit_stage_bytes) {
-        HIPCHK(hipStreamSynchronize(s->stream));
-        if (s->mit_stage) HIPCHK(hipFree(s->mit_stage));
-        s->mit_stage = nullptr; s->mit_stage_bytes = 0;
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&s->mit_stage), blk_bytes + rows_bytes));
-        s->mit_stage_bytes = blk_bytes + rows_bytes;
+    const int32_t *blk = nullptr;
+    { int rc = stage_lines(s, n_steps, pts, k, device_pointer, &blk); if (rc) return rc; }
+    if (plan.nw) {
+        const int rc = enqueue_call(s, plan, n_steps, blk, k, false, ms_out ? s->ev0 : nullptr);
+        return rc ? rc : finish_call(s, who, !s->async, ms_out);
     }
-    int32_t *rows = s->mit_stage;                                     // [E * k][4], fallback path
-    const int32_t *blk = pts;
-    if (!device_pointer) {
-        int32_t *d = s->mit_stage + (size_t)g.E * k * 4;
-        HIPCHK(hipMemcpyAsync(d, pts, blk_bytes, hipMemcpyHostToDevice, s->stream));
-        blk = d;
-    }
-    if (plan.nw) return run_step(s, plan, n_steps, ms_out, blk, k);
-    // per-step launches: scatter the step's points, then one update
-    // (the bookkeeping of a call with control lines, whichever way it runs: its step(1) calls are not a run(1) loop)
-    s->status_fresh = false; s->last_launches = 0; s->step1_polls = 0;
-    int rc = SF_OK;
-    const bool was_async = s->async;
-    s->async = true;
-    s->arr_hold = true;                // (arrival recording: a pass every max_fire_duration pairs and one behind the last, not one per pair)
-    float total = 0.f;
-    for (int i = 0; i < n_steps; ++i) {
-        hipLaunchKernelGGL(k_expand_pts, dim3((unsigned)((g.E * k + 255) / 256)), dim3(256), 0, s->stream, g.E, k,
-                           blk + (size_t)i * per_step, rows);
-        rc = scatter_points(s, rows, g.E * k, false);
-        if (rc) break;
+    for (int i = 0; i < n_steps; ++i) {      // (timed: the GPU time of the updates alone, so every pair is waited for)
         float ms1 = 0.f;
-        rc = step_impl(s, 1, ms_out ? &ms1 : nullptr);
-        if (rc) break;
-        total += ms1;
+        int rc = enqueue_pair(s, blk, k, i, ms_out ? s->ev0 : nullptr);
+        if (!rc && ms_out) rc = finish_call(s, who, true, &ms1);
+        if (rc) return rc;
+        if (ms_out) *ms_out += ms1;
     }
-    s->arr_hold = false;
-    if (!rc && s->arr_pending) rc = arrival_pass(s);
-    s->async = was_async;
-    if (rc) return rc;
-    if (ms_out) *ms_out = total;
-    if (!s->async) HIPCHK(hipStreamSynchronize(s->stream));
-    return SF_OK;
+    if (s->arr_pending) { int rc = arrival_pass(s); if (rc) return rc; }
+    return finish_call(s, who, !s->async, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------------- closed loop
@@ -2342,7 +2379,7 @@ extern "C" int sf_loop_start(sf_sim *s, int32_t k)
 {
     if (!s) return fail(SF_EINVAL, "sf_loop_start: null handle");
     if (k < 0 || k > 64) return fail(SF_EINVAL, "sf_loop_start: 0 .. 64 points per environment and step (got %d)", k);
-    if (!s->have_rt || !s->was_reset) return fail(SF_ESTATE, "sf_loop_start: call sf_set_layers / sf_set_rtable and sf_reset first");
+    { int rc0 = check_ready(s, "sf_loop_start", kNeedRt | kNeedReset); if (rc0) return rc0; }
     HIPCHK(hipSetDevice(s->p.device));
     const Geo &g = s->g;
     // the resident launch with one workgroup per environment, every environment resident at once
@@ -2356,7 +2393,7 @@ extern "C" int sf_loop_start(sf_sim *s, int32_t k)
         (s->fused_mode >= 0 && s->fused_mode != 2))
         return fail(SF_ENOTSUP, "sf_loop_start: needs the environment-resident launch with every environment resident at once "
                                 "(grids up to 1024 x 1024, max_fire_duration <= 5, no more environments than CUs, no spread graph / history)");
-    if (s->loop_on) { int rc0 = sf_loop_stop(s); if (rc0) return rc0; }
+    LOOP_QUIESCE(s);                   // (a refused call leaves a running loop running)
     s->loop_light = light;
     { int rc0 = ensure_commit(s); if (rc0) return rc0; }
     { int rc0 = ensure_vbits(s); if (rc0) return rc0; }
@@ -2458,9 +2495,9 @@ extern "C" int sf_loop_step(sf_sim *s, const int32_t *pts, int32_t *status_out, 
     return SF_OK;
 }
 
-extern "C" int sf_loop_stop(sf_sim *s)
+extern "C" int sf_loop_stop(sf_sim *s) { return s ? loop_stop(s) : fail(SF_EINVAL, "sf_loop_stop: null handle"); }
+static int loop_stop(sf_sim *s)
 {
-    if (!s) return fail(SF_EINVAL, "sf_loop_stop: null handle");
     if (!s->loop_on) return SF_OK;
     HIPCHK(hipSetDevice(s->p.device));
     volatile uint32_t *db = s->loop_db;
@@ -2492,8 +2529,7 @@ static int get_maps(sf_sim *s, int env0, int n, uint8_t *out)
     hipLaunchKernelGGL(k_unpack_status, grd, blk, 0, s->stream, g, (const uint8_t *)s->status, (const uint8_t *)(s->bl_cur ? s->cells : nullptr), env0, (uint8_t *)s->stage, (uint8_t *)nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, s->stage, bytes, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return check_team_error(s, "sf_get_fire_map(s)");
+    return finish_call(s, "sf_get_fire_map(s)", true, nullptr);
 }
 
 extern "C" int sf_get_fire_map(sf_sim *s, int32_t env, uint8_t *out)
@@ -2587,31 +2623,29 @@ extern "C" int sf_get_fire_map_delta(sf_sim *s, int32_t env, uint32_t *cells_out
     const Geo &g = s->g;
     if (env < 0 || env >= g.E) return fail(SF_EINVAL, "sf_get_fire_map_delta: environment %d out of range", env);
     HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    if (s->last_was_step1) { s->last_was_step1 = false; if (s->step1_polls < 1000) s->step1_polls++; }      // (a look at the result of a single update, like a status query)
+    note_result_look(s);               // (like a status query)
     int mode = 0;
     { int rc = delta_enqueue(s, env, cap, &mode); if (rc) return rc; }
-    HIPCHK(hipStreamSynchronize(s->stream));
-    if (mode == 1) *n_out = -1;
-    else { int rc = delta_finish(s, cap, cells_out, n_out); if (rc) return rc; }
-    return check_team_error(s, "sf_get_fire_map_delta");
+    { int rc = finish_call(s, "sf_get_fire_map_delta", true, nullptr); if (rc) return rc; }
+    if (mode == 1) { *n_out = -1; return SF_OK; }
+    return delta_finish(s, cap, cells_out, n_out);
 }
 
-static int update_status_async(sf_sim *s, int32_t *copy_to);
+static int refresh_status(sf_sim *s, int32_t *copy_to);
 /* FireSimulation.run(n) as ONE call and ONE wait (simulation.py:501-553: the loop of update() calls, then the attributes a caller reads - fire_map,
  * elapsed_steps, elapsed_time, active): sf_step(n_steps) on every environment of the handle, then environment env's row of the result block
  * (sf_get_status), its elapsed_time and the cells of its fire_map that changed (sf_get_fire_map_delta) - three calls' worth of launches and copies
  * enqueued behind each other, waited for once.  *n_out as for sf_get_fire_map_delta (-1: fetch the whole map). */
 extern "C" int sf_run_delta(sf_sim *s, int32_t n_steps, int32_t env, int32_t *status_row, double *elapsed, uint32_t *cells_out, int32_t cap, int32_t *n_out)
 {
-    if (!s || !status_row || !n_out || cap < 0 || (cap > 0 && !cells_out)) return fail(SF_EINVAL, "sf_run_delta: bad argument");
+    if (!s || !status_row || !n_out || cap < 0 || (cap > 0 && !cells_out) || n_steps < 0) return fail(SF_EINVAL, "sf_run_delta: bad argument");
     const Geo &g = s->g;
     if (env < 0 || env >= g.E) return fail(SF_EINVAL, "sf_run_delta: environment %d out of range", env);
-    const bool was_async = s->async;
-    s->async = true;                               // (the steps are only enqueued: the one wait is below)
-    int rc = step_impl(s, n_steps, nullptr);
-    s->async = was_async;
+    int rc = begin_call(s, "sf_run_delta", kNeedRt | kNeedReset);
+    if (!rc) rc = step_impl(s, n_steps, false, nullptr);
     if (rc) return rc;
-    rc = update_status_async(s, nullptr);          // (nothing to launch behind a resident launch: it has left the block behind itself)
+    note_result_look(s);
+    rc = refresh_status(s, nullptr);               // (nothing to launch behind a resident launch: it has left the block behind itself)
     if (rc) return rc;
     int mode = 0;
     rc = delta_enqueue(s, env, cap, &mode, true);
@@ -2622,12 +2656,13 @@ extern "C" int sf_run_delta(sf_sim *s, int32_t n_steps, int32_t env, int32_t *st
         HIPCHK(hipMemcpyAsync(land, s->status_block + (size_t)env * 8, 8 * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
         HIPCHK(hipMemcpyAsync(land + 8, s->elapsed_dev + env, sizeof(double), hipMemcpyDeviceToHost, s->stream));
     }
-    HIPCHK(hipStreamSynchronize(s->stream));
+    rc = finish_call(s, "sf_run_delta", true, nullptr);
+    if (rc) return rc;
     memcpy(status_row, land, 8 * sizeof(int32_t));
     if (elapsed) memcpy(elapsed, land + 8, sizeof(double));
     if (mode == 1) *n_out = -1;
-    else { rc = delta_finish(s, cap, cells_out, n_out); if (rc) return rc; }
-    return check_team_error(s, "sf_run_delta");
+    else rc = delta_finish(s, cap, cells_out, n_out);
+    return rc;
 }
 
 extern "C" int sf_get_burn(sf_sim *s, int32_t env, double *out)
@@ -2648,8 +2683,7 @@ extern "C" int sf_get_burn(sf_sim *s, int32_t env, double *out)
                        (const double *)s->burn, (const EnvState *)s->commit, env, (double *)s->stage);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, s->stage, bytes, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return check_team_error(s, "sf_get_burn");
+    return finish_call(s, "sf_get_burn", true, nullptr);
 }
 
 extern "C" int sf_set_burn(sf_sim *s, int32_t env, const double *burn)
@@ -2677,15 +2711,8 @@ extern "C" int sf_set_burn(sf_sim *s, int32_t env, const double *burn)
 }
 
 // ----------------------------------------------------------------------------- environment state
-// What every state call does first: end the closed loop, insist on a reset, refuse a handle a failed team launch has voided, and fold
-// the step rings into commit[] (after which tmp / flags carry nothing: the next launch starts from commit).
-static int state_entry(sf_sim *s, const char *who)
-{
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    if (!s->was_reset) return fail(SF_ESTATE, "%s: call sf_reset first", who);
-    { int rc = check_team_error(s, who); if (rc) return rc; }
-    return ensure_commit(s);
-}
+// Every state call begins as begin_call(kStateCall): the closed loop ended, a reset insisted on, a voided handle refused, the step
+// rings folded into commit[].
 
 extern "C" int sf_copy_envs(sf_sim *s, const int32_t *src, const int32_t *dst, int32_t n, int32_t flags)
 {
@@ -2703,7 +2730,7 @@ extern "C" int sf_copy_envs(sf_sim *s, const int32_t *src, const int32_t *dst, i
     for (int e = 0; e < g.E; ++e)
         if (role[e] == 3) return fail(SF_EINVAL, "sf_copy_envs: environment %d is both a source and a destination", e);
     if (n == 0) return SF_OK;
-    { int rc = state_entry(s, "sf_copy_envs"); if (rc) return rc; }
+    { int rc = begin_call(s, "sf_copy_envs", kStateCall); if (rc) return rc; }
     // Every per-environment slice of the current layout and of the structures derived from it: a handle-wide "rebuild" flag would make
     // the next step rebuild them for every environment.
     CopyList L;
@@ -2732,8 +2759,7 @@ extern "C" int sf_copy_envs(sf_sim *s, const int32_t *src, const int32_t *dst, i
     }
     if (terrain) { s->have_rt = true; for (char c : s->rt_set) if (!c) s->have_rt = false; }
     // (fire_rows bounds every environment's fire, dst's copy included; status_fresh: dst's row is src's current row)
-    if (!s->async) HIPCHK(hipStreamSynchronize(s->stream));
-    return SF_OK;
+    return finish_call(s, nullptr, !s->async, nullptr);
 }
 
 static StateHeader state_header(const sf_sim *s)
@@ -2871,7 +2897,7 @@ extern "C" int sf_reset_envs(sf_sim *s, int32_t n, const int32_t *envs, const in
                         envs[i], g.H, g.W);
     }
     if (n == 0) return SF_OK;
-    { int rc = state_entry(s, "sf_reset_envs"); if (rc) return rc; }
+    { int rc = begin_call(s, "sf_reset_envs", kStateCall); if (rc) return rc; }
     // an environment named twice keeps the last ignition given for it: no two entries of the launch write one environment
     std::vector<int32_t> last((size_t)g.E, -1), le, lxy;
     for (int i = 0; i < n; ++i) last[envs[i]] = i;
@@ -2882,8 +2908,7 @@ extern "C" int sf_reset_envs(sf_sim *s, int32_t n, const int32_t *envs, const in
     { int rc = reset_stage(s, le.data(), (size_t)m * 4, lxy.data(), (size_t)m * 8, &dev); if (rc) return rc; }
     { int rc = reset_launch(s, reinterpret_cast<const int32_t *>(dev), nullptr, reinterpret_cast<const int32_t *>(dev + (size_t)m * 4), m); if (rc) return rc; }
     if (s->snap) for (int i = 0; i < m; ++i) s->snap_valid[le[i]] = 1;      // (sf_get_fire_map_delta: a reset map is all UNBURNED; the next delta reports the ignition)
-    if (!s->async) HIPCHK(hipStreamSynchronize(s->stream));
-    return SF_OK;
+    return finish_call(s, nullptr, !s->async, nullptr);
 }
 
 extern "C" int sf_reset_where(sf_sim *s, const uint8_t *device_mask, const int32_t *xy, int32_t xy_device_pointer)
@@ -2891,7 +2916,7 @@ extern "C" int sf_reset_where(sf_sim *s, const uint8_t *device_mask, const int32
     if (!s) return fail(SF_EINVAL, "sf_reset_where: null handle");
     if (!xy) return fail(SF_EINVAL, "sf_reset_where: null ignitions");
     const Geo &g = s->g;
-    { int rc = state_entry(s, "sf_reset_where"); if (rc) return rc; }
+    { int rc = begin_call(s, "sf_reset_where", kStateCall); if (rc) return rc; }
     const int32_t *xy_dev = xy;
     if (!xy_device_pointer) {
         uint8_t *dev = nullptr;
@@ -2903,8 +2928,7 @@ extern "C" int sf_reset_where(sf_sim *s, const uint8_t *device_mask, const int32
     // which environments were taken is known on the device only: no host mirror of a map can be told to zero itself, so the next
     // delta query of every environment hands back the whole map once
     if (s->snap) std::fill(s->snap_valid.begin(), s->snap_valid.end(), 0);
-    if (!s->async) HIPCHK(hipStreamSynchronize(s->stream));
-    return SF_OK;
+    return finish_call(s, nullptr, !s->async, nullptr);
 }
 
 // ----------------------------------------------------------------------------- agents
@@ -2992,8 +3016,7 @@ extern "C" int sf_agents_place(sf_sim *s, int32_t n, const int32_t *envs, const 
                        reinterpret_cast<const int32_t *>(blk.dev), reinterpret_cast<const int32_t *>(blk.dev + o_xy), also_start != 0 ? 1 : 0,
                        s->ag_xyid, s->ag_start, s->ag_len, s->ag_ret);
     HIPCHK(hipGetLastError());
-    if (!s->async) HIPCHK(hipStreamSynchronize(s->stream));
-    return SF_OK;
+    return finish_call(s, nullptr, !s->async, nullptr);
 }
 
 extern "C" int sf_agents_device(sf_sim *s, void **xyid)
@@ -3022,25 +3045,27 @@ static AgentArgs agent_args(const sf_sim *s, const int32_t *actions, const sf_ag
     return a;
 }
 
-// One tick for every environment, nothing read back: result rows -> k_agents_act -> the step calls as they stand (one update with
-// the device points, then the plain step path) -> result rows -> k_agents_finish -> the batched reset with the done mask.
+// One tick for every environment, nothing read back, every piece from the enqueue layer: result rows -> k_agents_act -> one update
+// with the device points, then the plain updates -> result rows -> k_agents_finish -> the batched reset with the done mask.
 extern "C" int sf_agents_step(sf_sim *s, const int32_t *device_actions, const sf_agent_out *out)
 {
     if (!s) return fail(SF_EINVAL, "sf_agents_step: null handle");
     if (!s->ag.k) return fail(SF_ESTATE, "sf_agents_step: call sf_agents_create first");
     if (!device_actions) return fail(SF_EINVAL, "sf_agents_step: null actions");
-    if (!s->have_rt) return fail(SF_ESTATE, "sf_agents_step: call sf_set_layers or sf_set_rtable first");
     const Geo &g = s->g;
-    { int rc = state_entry(s, "sf_agents_step"); if (rc) return rc; }
-    const bool was_async = s->async;
-    s->async = true;                                 // (every piece below only enqueues: the one wait is at the end)
-    int rc = update_status_async(s, nullptr);        // r0: the rows as a status query leaves them
+    { int rc = begin_call(s, "sf_agents_step", kNeedRt | kStateCall); if (rc) return rc; }
+    note_result_look(s);
+    int rc = refresh_status(s, nullptr);             // r0: the rows as a status query leaves them
+    const int32_t *pts = nullptr;
+    if (!rc) rc = stage_lines(s, 1, s->ag_points, s->ag.k, 1, &pts);
     if (!rc) {
         hipLaunchKernelGGL(k_agents_act, dim3((unsigned)g.E), dim3(kAgentsMax), 0, s->stream, agent_args(s, device_actions, out));
-        rc = sf_step_mitigated(s, 1, s->ag_points, s->ag.k, 1, nullptr);
+        const StepPlan plan = plan_step(s, 1, true);         // one update with the device points: inside the resident launch, or a pair
+        rc = plan.nw ? enqueue_call(s, plan, 1, pts, s->ag.k, false, nullptr) : enqueue_pair(s, pts, s->ag.k, 0, nullptr);
+        if (!rc && s->arr_pending) rc = arrival_pass(s);
     }
-    if (!rc && s->ag.n_updates > 1) rc = step_impl(s, s->ag.n_updates - 1, nullptr);
-    if (!rc) rc = update_status_async(s, nullptr);   // r1 (commits the step rings too)
+    if (!rc) rc = step_impl(s, s->ag.n_updates - 1, false, nullptr);
+    if (!rc) { note_result_look(s); rc = refresh_status(s, nullptr); }      // r1 (commits the step rings too)
     if (!rc) {
         hipLaunchKernelGGL(k_agents_finish, dim3((unsigned)g.E), dim3(kAgentsMax), 0, s->stream, agent_args(s, device_actions, out));
         if (s->ag.auto_reset) {
@@ -3049,16 +3074,8 @@ extern "C" int sf_agents_step(sf_sim *s, const int32_t *device_actions, const sf
             if (!rc && s->snap) std::fill(s->snap_valid.begin(), s->snap_valid.end(), 0);
         }
     }
-    s->async = was_async;
-    if (rc) return rc;
-    HIPCHK(hipGetLastError());
-    if (!s->async) {
-        HIPCHK(hipStreamSynchronize(s->stream));
-        return check_team_error(s, "sf_agents_step");
-    }
-    return SF_OK;
+    return rc ? rc : finish_call(s, "sf_agents_step", !s->async, nullptr);
 }
-
 
 extern "C" int sf_state_bytes(sf_sim *s, int64_t *bytes_out)
 {
@@ -3072,16 +3089,10 @@ extern "C" int sf_save_state(sf_sim *s, int32_t n, const int32_t *envs, void *ou
     if (!s) return fail(SF_EINVAL, "sf_save_state: null handle");
     { int rc = state_list(s, n, envs, out, device_pointer, "sf_save_state", false); if (rc) return rc; }
     if (n == 0) return SF_OK;
-    { int rc = state_entry(s, "sf_save_state"); if (rc) return rc; }
-    {   // the result rows travel with the state: make them current - as a status query would, but a snapshot is not a look at the result of a
-        // single update: the run(1)-loop heuristic of the step calls (last_was_step1 / step1_polls) stays as it was
-        const bool was_step1 = s->last_was_step1;
-        const int polls = s->step1_polls;
-        int rc = update_status_async(s, nullptr);
-        s->last_was_step1 = was_step1;
-        s->step1_polls = polls;
-        if (rc) return rc;
-    }
+    { int rc = begin_call(s, "sf_save_state", kStateCall); if (rc) return rc; }
+    // the result rows travel with the state: made current as a status query would, but a snapshot is not a look at the result of a
+    // single update (no note_result_look: the run(1)-loop heuristic stays as it was)
+    { int rc = refresh_status(s, nullptr); if (rc) return rc; }
     StateArgs a = state_args(s);
     a.hdr = state_header(s);
     const int chunk = state_chunk(a, device_pointer != 0);
@@ -3125,7 +3136,7 @@ extern "C" int sf_load_state(sf_sim *s, int32_t n, const int32_t *envs, const vo
         if (rc) return rc;
         fire_rows = std::max(fire_rows, hdr[i].fire_rows > 0 ? hdr[i].fire_rows : INT32_MAX);
     }
-    { int rc = state_entry(s, "sf_load_state"); if (rc) return rc; }
+    { int rc = begin_call(s, "sf_load_state", kStateCall); if (rc) return rc; }
     const Geo &g = s->g;
     StateArgs a = state_args(s);
     const int chunk = state_chunk(a, device_pointer != 0);
@@ -3167,11 +3178,10 @@ extern "C" int sf_load_state(sf_sim *s, int32_t n, const int32_t *envs, const vo
     return SF_OK;
 }
 
-static int update_status_async(sf_sim *s, int32_t *copy_to)
+// The result block made current on the device (enqueue layer), also written to copy_to (may be null) and the registered sink.
+static int refresh_status(sf_sim *s, int32_t *copy_to)
 {
     const Geo &g = s->g;
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    if (s->last_was_step1) { s->last_was_step1 = false; if (s->step1_polls < 1000) s->step1_polls++; }
     { int rc0 = ensure_commit(s); if (rc0) return rc0; }
     if (s->status_fresh) {
         // the resident launch has left the block (and the registered sink's copy) behind: nothing to count
@@ -3203,20 +3213,25 @@ static int update_status_async(sf_sim *s, int32_t *copy_to)
     HIPCHK(hipGetLastError());
     return SF_OK;
 }
+// What a status query does first (call layer): the prologue, the note of the look, the refresh.
+static int status_query(sf_sim *s, const char *who, int32_t *copy_to)
+{
+    { int rc = begin_call(s, who, 0); if (rc) return rc; }
+    note_result_look(s);
+    return refresh_status(s, copy_to);
+}
 
 extern "C" int sf_update_status_device(sf_sim *s)
 {
     if (!s) return fail(SF_EINVAL, "sf_update_status_device: null handle");
-    int rc = update_status_async(s, nullptr);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return SF_OK;
+    const int rc = status_query(s, "sf_update_status_device", nullptr);
+    return rc ? rc : finish_call(s, nullptr, true, nullptr);
 }
 
 extern "C" int sf_get_status(sf_sim *s, int32_t *status, double *elapsed)
 {
     if (!s || !status) return fail(SF_EINVAL, "sf_get_status: null argument");
-    int rc = update_status_async(s, nullptr);
+    int rc = status_query(s, "sf_get_status", nullptr);
     if (rc) return rc;
     const size_t nb_st = sizeof(int32_t) * 8 * s->g.E, nb_el = sizeof(double) * s->g.E;
     if (!s->status_pinned) HIPCHK(hipHostMalloc(&s->status_pinned, nb_st + nb_el, hipHostMallocDefault));
@@ -3253,22 +3268,20 @@ extern "C" int sf_get_counters(sf_sim *s, int64_t *out, int32_t reset)
 extern "C" int sf_copy_status_to(sf_sim *s, void *device_dst)
 {
     if (!s || !device_dst) return fail(SF_EINVAL, "sf_copy_status_to: null argument");
-    int rc = update_status_async(s, static_cast<int32_t *>(device_dst));       // (the counting kernel writes the copy too)
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(s->stream));       // (one wait for steps still in flight and the count)
-    return check_team_error(s, "sf_copy_status_to");
+    int rc = status_query(s, "sf_copy_status_to", static_cast<int32_t *>(device_dst));       // (the counting kernel writes the copy too)
+    return rc ? rc : finish_call(s, "sf_copy_status_to", true, nullptr);       // (one wait for steps still in flight and the count)
 }
 
 extern "C" int sf_rollout(sf_sim *s, int32_t n_steps, void *device_dst)
 {
     if (!s || !device_dst) return fail(SF_EINVAL, "sf_rollout: null argument");
-    const bool was_async = s->async;
-    s->async = true;                               // (the steps are only enqueued: the one wait is the result block's)
-    int rc = step_impl(s, n_steps, nullptr);
-    s->async = was_async;
+    if (n_steps < 0) return fail(SF_EINVAL, "sf_rollout: n_steps must be >= 0");
+    int rc = begin_call(s, "sf_rollout", kNeedRt | kNeedReset);
+    if (!rc) rc = step_impl(s, n_steps, false, nullptr);
     if (rc) return rc;
-    if (was_async) return update_status_async(s, static_cast<int32_t *>(device_dst));      // asynchronous mode: enqueued, not waited for (sf_sync / the caller's device synchronisation)
-    return sf_copy_status_to(s, device_dst);
+    note_result_look(s);
+    rc = refresh_status(s, static_cast<int32_t *>(device_dst));
+    return rc ? rc : finish_call(s, "sf_rollout", !s->async, nullptr);      // (asynchronous mode: enqueued, not waited for - sf_sync / the caller's device synchronisation)
 }
 
 extern "C" int sf_set_result_sink(sf_sim *s, void *device_dst)
@@ -3329,16 +3342,15 @@ extern "C" int sf_comm_unique_id(void *id_out)
     return SF_OK;
 }
 
-extern "C" int sf_comm_destroy(sf_sim *s)
+extern "C" int sf_comm_destroy(sf_sim *s) { return s ? comm_close(s) : fail(SF_EINVAL, "sf_comm_destroy: null handle"); }
+static int comm_close(sf_sim *s)
 {
-    if (!s) return fail(SF_EINVAL, "sf_comm_destroy: null handle");
-    if (s->comm) {
-        HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-        HIPCHK(hipStreamSynchronize(s->stream));
-        ncclComm_t c = s->comm;
-        s->comm = nullptr; s->comm_world = 0;
-        RCCLCHK(g_rccl.CommDestroy(c));
-    }
+    if (!s->comm) return SF_OK;
+    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    ncclComm_t c = s->comm;
+    s->comm = nullptr; s->comm_world = 0;
+    RCCLCHK(g_rccl.CommDestroy(c));
     return SF_OK;
 }
 
@@ -3347,7 +3359,7 @@ extern "C" int sf_comm_init(sf_sim *s, int32_t rank, int32_t world_size, const v
     if (!s || !unique_id) return fail(SF_EINVAL, "sf_comm_init: null argument");
     if (world_size < 1 || rank < 0 || rank >= world_size) return fail(SF_EINVAL, "sf_comm_init: rank %d of %d", rank, world_size);
     { int rc = rccl_load(); if (rc) return rc; }
-    { int rc = sf_comm_destroy(s); if (rc) return rc; }
+    { int rc = comm_close(s); if (rc) return rc; }
     HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
     ncclUniqueId id;
     std::memcpy(&id, unique_id, sizeof id);
@@ -3360,12 +3372,11 @@ extern "C" int sf_allgather_status(sf_sim *s, void *device_out)
 {
     if (!s || !device_out) return fail(SF_EINVAL, "sf_allgather_status: null argument");
     if (!s->comm) return fail(SF_ESTATE, "sf_allgather_status: call sf_comm_init first");
-    int rc = update_status_async(s, nullptr);                // the block of this rank's shard (fresh already after a resident launch)
+    int rc = status_query(s, "sf_allgather_status", nullptr);      // the block of this rank's shard (fresh already after a resident launch)
     if (rc) return rc;
     // on the handle's stream: behind the steps in flight and the refresh, no host wait in between
     RCCLCHK(g_rccl.AllGather(s->status_block, device_out, (size_t)8 * s->g.E, ncclInt32, s->comm, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return check_team_error(s, "sf_allgather_status");
+    return finish_call(s, "sf_allgather_status", true, nullptr);
 }
 
 extern "C" int sf_status_device(sf_sim *s, void **ptr)
@@ -3446,8 +3457,7 @@ extern "C" int sf_observe(sf_sim *s, const sf_obs_params *p, int32_t n, const in
     { int rc = check_envs(s, "sf_observe", n, envs); if (rc) return rc; }
     if (n == 0) return SF_OK;
     if (attr && !s->have_rt) return fail(SF_ESTATE, "sf_observe: attribute channels need the layers (sf_set_layers)");
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    { int rc = check_team_error(s, "sf_observe"); if (rc) return rc; }
+    { int rc = begin_call(s, "sf_observe", kNotVoid); if (rc) return rc; }
     const int oh = eh / f, ow = ew / f;
     const ObsTile tl = obs_tile(f, ow);
     const long long tiles_x = (ow + tl.TX - 1) / tl.TX, tiles = tiles_x * ((oh + tl.TY - 1) / tl.TY);
@@ -3489,12 +3499,7 @@ extern "C" int sf_observe(sf_sim *s, const sf_obs_params *p, int32_t n, const in
     a.TX = tl.TX; a.TY = tl.TY; a.tiles_x = (int)tiles_x; a.stride = tl.stride;
     a.norm = p->normalize != 0; a.bf16 = p->dtype == 1; a.pad = p->pad;
     hipLaunchKernelGGL(k_observe, dim3((unsigned)((long long)n * tiles)), dim3(kObsThreads), 0, s->stream, a);
-    HIPCHK(hipGetLastError());
-    if (!s->async) {
-        HIPCHK(hipStreamSynchronize(s->stream));
-        return check_team_error(s, "sf_observe");
-    }
-    return SF_OK;
+    return finish_call(s, "sf_observe", !s->async, nullptr);
 }
 
 // ----------------------------------------------------------------------------- frames
@@ -3554,8 +3559,7 @@ extern "C" int sf_render(sf_sim *s, const sf_render_params *p, int32_t n, const 
     for (int i = 0; i < n; ++i)
         if (!s->rd_lay[n_tab == 1 ? 0 : envs[i]]) return fail(SF_ESTATE, "sf_render: environment %d has no layers (sf_set_layers)", envs[i]);
     if (n == 0) return SF_OK;
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    { int rc = check_team_error(s, "sf_render"); if (rc) return rc; }
+    { int rc = begin_call(s, "sf_render", kNotVoid); if (rc) return rc; }
 
     // which backgrounds to (re)build: the listed environments' stale tables; every functional one when the fuel colours were made
     // from another terrain_rgb (only the fuel background shows them)
@@ -3625,12 +3629,7 @@ extern "C" int sf_render(sf_sim *s, const sf_render_params *p, int32_t n, const 
     a.s = s_; a.mode = p->mode; a.white = p->background == SF_RENDER_WHITE; a.contours = p->contours; a.cl = cl;
     a.oh = oh; a.ow = ow; a.R = tl.R; a.stride = g.P; a.st_bytes = tl.st_bytes; a.out_seg = tl.out_seg;
     hipLaunchKernelGGL(k_render, dim3((unsigned)(frames * bands)), dim3(kRdThreads), (unsigned)tl.lds, s->stream, a);
-    HIPCHK(hipGetLastError());
-    if (!s->async) {
-        HIPCHK(hipStreamSynchronize(s->stream));
-        return check_team_error(s, "sf_render");
-    }
-    return SF_OK;
+    return finish_call(s, "sf_render", !s->async, nullptr);
 }
 
 extern "C" int sf_compute_ros(int64_t n, const float *loc_x, const float *loc_y, const float *new_loc_x,
