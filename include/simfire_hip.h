@@ -157,6 +157,38 @@ typedef struct sf_layer_gen {
 } sf_layer_gen;
 int sf_generate_layers(sf_sim *sim, int32_t n, const int32_t *envs, const sf_layer_gen *gen);
 
+/* A wind change during an episode.  RothermelFireManager reads self.U / self.U_dir at every update()
+ * (simfire/game/managers/fire.py:365, 490-494): a caller who assigns new arrays between two update() calls gets a wind shift.
+ * sf_set_wind is that assignment for the tables of a list of environments: every later update uses the table sf_set_layers_env
+ * would build from the unchanged fuel and elevation planes and the new U (ft/min), U_dir (degrees) - bit for bit -; cells, ages,
+ * burn_amounts (the lazy line attenuation included), elapsed_time, result rows, history, arrival plane and spread graph stay
+ * as they are.  Layer planes 5 and 6 take the new wind (sf_get_attribute_data, sf_observe).  envs == NULL addresses every
+ * table in order: n == 1 on a shared-terrain handle, n == n_envs otherwise; a list on a shared-terrain handle is SF_ESTATE.
+ * Environments out of range or repeated, null pointers, unknown flag bits: SF_EINVAL before any device work; a listed table that
+ * has no layers (only sf_set_rtable): SF_ESTATE; n == 0 does nothing.  Ends a running closed loop first.  Under sf_set_async the
+ * call only enqueues (a host U / U_dir is consumed before it returns; device memory must stay as it is until the handle's stream
+ * has passed the call); otherwise it waits once at its end.  Clears the schedule of a listed environment. */
+#define SF_WIND_UNIFORM 0   /* U, U_dir: float64 [n] */
+#define SF_WIND_FIELD   1   /* U, U_dir: float64 [n][H*W] */
+#define SF_WIND_DEVICE  2   /* or-ed in: the two pointers are device memory */
+int sf_set_wind(sf_sim *sim, int32_t n, const int32_t *envs, const double *U, const double *U_dir, int32_t flags);
+
+/* A wind that depends on the episode's time, decided on the device (fire.py:365, 490-494 with the assignment made by a timetable;
+ * an environment restarted inside sf_agents_step has an update count the host does not know).  Environment envs[i] gets K
+ * segments segs[i][0 .. K): from update first_update on (0-based count of update() calls since the environment's reset) its
+ * uniform wind is (U, U_dir).  segs[.][0].first_update == 0, strictly increasing, 1 <= K <= SF_WIND_MAX_SEGS, reserved == 0, else
+ * SF_EINVAL; K == 0 clears.  Needs a per_env_terrain handle (SF_ESTATE) whose listed tables have layers (SF_ESTATE).  envs == NULL:
+ * every environment in order (n == n_envs).
+ * THE CALL-BOUNDARY RULE: the wind changes where a stepping call begins, not inside it.  In front of the updates of every stepping
+ * call (sf_step, sf_step_mitigated, sf_rollout, sf_run_delta, each of the stepping pieces of sf_agents_step) the segment of every
+ * scheduled environment's update count is compared with the one its table stands for, on the device, and the tables that are due
+ * are rebuilt; the call then runs entirely under those tables.  A restart inside sf_agents_step is picked up by the next call.
+ * sf_loop_start with a schedule set is SF_ENOTSUP.  sf_copy_envs with SF_COPY_TERRAIN copies the schedule with the table, without
+ * it leaves it alone; sf_load_state makes the loaded environments' segment unknown (their next stepping call rebuilds the table). */
+#define SF_WIND_MAX_SEGS 16
+typedef struct sf_wind_seg { int32_t first_update, reserved; double U, U_dir; } sf_wind_seg;
+int sf_set_wind_schedule(sf_sim *sim, int32_t n, const int32_t *envs, int32_t K, const sf_wind_seg *segs /* [n][K] host */);
+
 /* History of FireSimulation._save_data (simulation.py:548-549, 887-959): the fire map after every
  * executed update, a ring int8 [n_envs][capacity][H][W] in HBM: update number u (0-based, counted from
  * the last reset of that environment = elapsed_steps before it) lands in slot u mod capacity.

@@ -134,6 +134,12 @@ int sf_get_arrival_passes(sf_sim *sim, int64_t *out /* [2] */);
 /* One more arrival pass over the state as it stands (it finds nothing new: a cell is written once), with HIP events around its launch:
  * the GPU milliseconds of a pass in the form the handle would take now.  SF_ESTATE before sf_enable_arrival. */
 int sf_time_arrival_pass(sf_sim *sim, float *ms_out);
+/* Wind changes (sf_set_wind, sf_set_wind_schedule).  cache_on = 0 frees the cache of wind-independent terms and
+ * makes every wind change build its tables from the layers (the path a handle takes by itself when it has no memory for the cache);
+ * 1 (default) allows the cache again.  timed != 0: HIP events around the launches of every sf_set_wind and every schedule pass;
+ * sf_get_wind_ms: the GPU milliseconds of the last one (SF_ESTATE before one was timed).  profiles/wind_probe.py measures with them. */
+int sf_set_wind_lab(sf_sim *sim, int32_t cache_on, int32_t timed);
+int sf_get_wind_ms(sf_sim *sim, float *ms_out);
 /* 1 = visit every tile every step instead of consulting the tile activity map (cross-check) */
 int sf_set_dense(sf_sim *sim, int32_t dense);
 /* sf_cfd_step that also reports the GPU time of its launches (HIP events on the handle's stream). */

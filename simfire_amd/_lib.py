@@ -58,6 +58,14 @@ class SfLayerGen(C.Structure):
                 ("wind_speed", SfNoise), ("wind_direction", SfNoise)]
 
 
+SF_WIND_UNIFORM, SF_WIND_FIELD, SF_WIND_DEVICE, SF_WIND_MAX_SEGS = 0, 1, 2, 16
+
+
+class SfWindSeg(C.Structure):
+    """``sf_wind_seg`` (include/simfire_hip.h): from update ``first_update`` on the wind is (U ft/min, U_dir degrees)."""
+    _fields_ = [("first_update", C.c_int32), ("reserved", C.c_int32), ("U", C.c_double), ("U_dir", C.c_double)]
+
+
 class SfRenderParams(C.Structure):
     """``sf_render_params`` (include/simfire_hip.h)."""
     _fields_ = [("source", C.c_int32), ("first", C.c_int32), ("count", C.c_int32), ("scale", C.c_int32), ("mode", C.c_int32),
@@ -92,6 +100,10 @@ SIGNATURES = {
     "sf_set_layers_fbfm": [_VP, _I32, _VP, _I32, _VP, _VP, _VP, _VP, _VP],
     "sf_get_attribute_data": [_VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32],
     "sf_generate_layers": [_VP, _I32, _VP, _VP],
+    "sf_set_wind": [_VP, _I32, _VP, _VP, _VP, _I32],
+    "sf_set_wind_schedule": [_VP, _I32, _VP, _I32, _VP],
+    "sf_set_wind_lab": [_VP, _I32, _I32],
+    "sf_get_wind_ms": [_VP, C.POINTER(C.c_float)],
     "sf_enable_history": [_VP, _I32],
     "sf_get_history": [_VP, _I32, _I32, _I32, _VP],
     "sf_history_device": [_VP, _VP, _VP],

@@ -107,6 +107,7 @@ extern "C" const char *sf_version(void) { return "simfire_hip 0.2 (gfx950)"; }  
 #include "sf_gen_kernels.h"
 #include "sf_agent_kernels.h"
 #include "sf_arrival_kernels.h"
+#include "sf_wind_kernels.h"
 
 // Launch-geometry knobs of a handle (sf_set_tuning, include/simfire_hip_lab.h: SF_TUNE_*).  Results never depend on them; the
 // defaults are the measured choices of NOTEBOOK.md 5.  The library does not read the environment for them (the measurement scripts under
@@ -260,6 +261,22 @@ struct sf_sim {
     CallBlock rs_blk;                  // sf_reset_envs / sf_reset_where: the environment list and host ignitions of a call
     bool rs_timed = false, rs_have_ms = false;   // sf_time_resets: ev0 / ev1 recorded around the launches of every batched reset
     CallBlock gen_blk;                 // sf_generate_layers: its descriptors + environment list
+    // wind changes: the cache plane of wind-independent terms, float [tables][kWindPlanes][H * W], allocated at the
+    // first wind change, and per table whether its part is stale (next to rtc_stale; wt_off: the lab has switched the cache off); the
+    // schedules on the device [E] with their host mirror (segments per environment, the scheduled environments, whether the cache has been
+    // made current for them since the last change of either), the due list of a schedule pass and its winds; the call block (list, scalars,
+    // schedule rows); the lab's events around the launches
+    float *wterms = nullptr;
+    std::vector<char> wt_stale;
+    bool wt_off = false;
+    WindSched *wsched = nullptr;
+    std::vector<int32_t> wind_K, wind_sched;
+    bool wind_sched_ready = false, wind_sched_cached = false;
+    int32_t *wdue = nullptr;
+    uint32_t *wdue_cnt = nullptr;
+    double *wdue_U = nullptr, *wdue_D = nullptr;
+    CallBlock wind_blk;
+    bool wind_timed = false, wind_have_ms = false;
     // sf_agents_* (DESIGN.md section 16): the parameters of sf_agents_create (ag.k == 0: no agent state), ONE device allocation that
     // holds every agent buffer - positions, start cells, this tick's points, the counts and episode statistics between the two
     // kernels of a tick, the done mask, the ignitions of a new episode - and the call block of sf_agents_place.  Not slices of
@@ -296,6 +313,7 @@ static int alloc_bl(sf_sim *s);
 static bool prefers_bl(const sf_sim *s);
 static int arrival_pass(sf_sim *s);
 static int arrival_seg(const sf_sim *s, EnvSeg *seg, int n);
+static int wind_forget(sf_sim *s, const int32_t *envs, int n);
 
 // Behind every wait for the handle's stream: has a workgroup of a team launch (k_run<TEAM>) given up waiting for a team member?
 // Then what the launch left behind is void - say so wherever data is handed back, not only in sf_sync / a synchronous sf_step.
@@ -538,11 +556,11 @@ static int destroy(sf_sim *s)
     for (void *hp : {(void *)s->loop_db, (void *)s->loop_res, (void *)s->loop_pts}) if (hp) (void)hipHostFree(hp);
     for (void *dp : {(void *)s->loop_mem, (void *)s->loop_pts_mem}) if (dp) (void)hipFree(dp);
     void *ptrs[] = {s->team_tab, s->team_size, s->xdone, s->xg, s->xbuf, s->xj, s->xcut, s->jlog, s->status, s->age_alloc, s->cells_alloc, s->burn, s->rt, s->rtc, s->lay_all, s->history, s->smag, s->sdir, s->commit, s->tmp, s->flags, s->counters, s->tflags, s->tile_list, s->n_active, s->seam, s->settled, s->tdirty, s->thist, s->vbits, s->todo, s->run_cost, s->run_order, s->todo_cnt, s->win_hint, s->mit_stage,
-                    s->status_block, s->elapsed_dev, s->stage, s->parents, s->arrival1};
+                    s->status_block, s->elapsed_dev, s->stage, s->parents, s->arrival1, s->wterms, s->wsched, s->wdue, s->wdue_U};
     if (s->status_pinned) (void)hipHostFree(s->status_pinned);
     if (s->delta_pinned) (void)hipHostFree(s->delta_pinned);
     for (void *dp : {(void *)s->snap, (void *)s->delta_dev, (void *)s->rd_bg, (void *)s->rd_fuel_ix, (void *)s->ag_mem}) if (dp) (void)hipFree(dp);
-    for (CallBlock *b : {&s->obs_blk, &s->rd_blk, &s->rs_blk, &s->gen_blk, &s->ag_blk}) {
+    for (CallBlock *b : {&s->obs_blk, &s->rd_blk, &s->rs_blk, &s->gen_blk, &s->ag_blk, &s->wind_blk}) {
         if (b->dev) (void)hipFree(b->dev);
         if (b->pinned) (void)hipHostFree(b->pinned);
         if (b->ev) (void)hipEventDestroy(b->ev);
@@ -788,6 +806,8 @@ static void mark_tables(sf_sim *s, const int32_t *tabs, int n)
 {
     if (s->rtc_stale.size() != s->rt_set.size()) s->rtc_stale.assign(s->rt_set.size(), 1);
     for (int k = 0; k < n; ++k) s->rt_set[tabs[k]] = s->rtc_stale[tabs[k]] = 1;
+    if (!s->wt_stale.empty()) for (int k = 0; k < n; ++k) s->wt_stale[tabs[k]] = 1;      // (the cache of wind-independent terms: ensure_wterms)
+    s->wind_sched_ready = false;
     s->rtc_valid = false;
     s->have_rt = true;
     for (char c : s->rt_set) if (!c) s->have_rt = false;
@@ -834,7 +854,13 @@ static int set_layers_impl(sf_sim *s, int env, const double *const src[7])
     HIPCHK(hipStreamSynchronize(s->stream));
     mark_tables(s, lo, hi);
     for (int i = lo; i < hi; ++i) { s->rd_lay[i] = 1; s->rd_fbfm[i] = src[0] == nullptr; s->rd_stale[i] = 1; }
-    return SF_OK;
+    if (s->wsched) {
+        std::vector<int32_t> tabs;
+        for (int i = lo; i < hi; ++i) tabs.push_back(i);
+        rc = wind_forget(s, tabs.data(), hi - lo);
+        if (!rc && !s->wind_sched.empty()) HIPCHK(hipStreamSynchronize(s->stream));
+    }
+    return rc;
 }
 
 extern "C" int sf_set_layers(sf_sim *s, const double *w_0, const double *delta, const double *M_x,
@@ -997,6 +1023,259 @@ extern "C" int sf_generate_layers(sf_sim *s, int32_t n, const int32_t *envs, con
     HIPCHK(hipStreamSynchronize(s->stream));
     mark_tables(s, envs, n);
     for (int k = 0; k < n; ++k) { s->rd_lay[envs[k]] = 1; s->rd_fbfm[envs[k]] = 0; s->rd_stale[envs[k]] = 1; }
+    return wind_forget(s, envs, n);
+}
+
+// ----------------------------------------------------------------------------- wind changes
+// The wind-independent terms of the listed tables (host list) made current in the cache plane, modelled on ensure_rtc: allocated at
+// the first wind change, filled per run of stale tables.  SF_ENOTSUP: no cache (no memory for it, or switched off by the lab) - the
+// caller builds from the layers.
+static int ensure_wterms(sf_sim *s, const int32_t *tabs, int n)
+{
+    if (s->wt_off) return SF_ENOTSUP;
+    const Geo &g = s->g;
+    const size_t n_tab = s->rt_set.size(), per = (size_t)kWindPlanes * g.H * g.W;
+    if (!s->wterms) {
+        if (hipMalloc(reinterpret_cast<void **>(&s->wterms), per * n_tab * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); s->wterms = nullptr; return SF_ENOTSUP; }
+        s->bytes += (int64_t)(per * n_tab * sizeof(float));
+        s->wt_stale.assign(n_tab, 1);
+    }
+    std::vector<int32_t> stale;
+    for (int k = 0; k < n; ++k) if (s->wt_stale[tabs[k]]) stale.push_back(tabs[k]);
+    std::sort(stale.begin(), stale.end());
+    const Thetas th = rt_thetas();
+    for (size_t i = 0; i < stale.size();) {
+        size_t j = i + 1;
+        while (j < stale.size() && stale[j] == stale[j - 1] + 1 && j - i < 65535) ++j;
+        hipLaunchKernelGGL(k_wind_terms, dim3((unsigned)((g.W + kWindThreads - 1) / kWindThreads), (unsigned)g.H, (unsigned)(j - i)), dim3(kWindThreads), 0,
+                           s->stream, g.H, g.W, (const double *)s->lay_all, (const int32_t *)nullptr, (int)stale[i], s->slope_scale, (float)s->p.h,
+                           (float)s->p.S_T, (float)s->p.S_e, (float)s->p.p_p, (float)s->p.M_f, th, s->wterms);
+        for (size_t k = i; k < j; ++k) s->wt_stale[stale[k]] = 0;
+        i = j;
+    }
+    HIPCHK(hipGetLastError());
+    return SF_OK;
+}
+
+// k_wind_rtable for `count` listed tables, or - cnt_dev - for as many as the device says (at most max_count); enqueue layer
+static int wind_launch(sf_sim *s, const int32_t *list_dev, const uint32_t *cnt_dev, int count, int max_count, const double *U, const double *U_dir,
+                       int field, bool cached)
+{
+    const Geo &g = s->g;
+    WindArgs a;
+    a.H = g.H; a.W = g.W; a.P = g.P;
+    a.lay = s->lay_all; a.cache = s->wterms; a.rt = s->rt; a.rtc = s->rtc;
+    a.tab_stride = (long long)8 * g.plane_env;
+    a.list = list_dev; a.count_dev = cnt_dev; a.count = count;
+    a.U = U; a.U_dir = U_dir; a.field = field;
+    a.ps = s->slope_scale;
+    a.h = (float)s->p.h; a.S_T = (float)s->p.S_T; a.S_e = (float)s->p.S_e; a.p_p = (float)s->p.p_p; a.M_f = (float)s->p.M_f;
+    a.th = rt_thetas();
+    const long long items = (long long)max_count * g.H * ((g.P + kWindThreads - 1) / kWindThreads);
+    const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>(items, (long long)s->n_cu * 8));
+    if (cached) hipLaunchKernelGGL(k_wind_rtable<true>, dim3(grid), dim3(kWindThreads), 0, s->stream, a);
+    else hipLaunchKernelGGL(k_wind_rtable<false>, dim3(grid), dim3(kWindThreads), 0, s->stream, a);
+    HIPCHK(hipGetLastError());
+    return SF_OK;
+}
+
+static void wind_sched_count(sf_sim *s)
+{
+    s->wind_sched.clear();
+    for (int e = 0; e < (int)s->wind_K.size(); ++e) if (s->wind_K[e]) s->wind_sched.push_back(e);
+    s->wind_sched_ready = false;
+}
+
+// An environment list -> the wind call block (enqueue layer); *dev: where it is
+static int wind_list(sf_sim *s, const int32_t *envs, int n, const int32_t **dev)
+{
+    CallBlock &blk = s->wind_blk;
+    { int rc = block_reserve(s, blk, (size_t)n * 4); if (rc) return rc; }
+    memcpy(blk.pinned, envs, (size_t)n * 4);
+    *dev = (const int32_t *)blk.dev;
+    return block_send(s, blk, (size_t)n * 4);
+}
+
+// The tables of these environments were rebuilt from their layers (or their state was loaded): whichever segment a schedule built
+// them for, the next stepping call decides anew.
+static int wind_forget(sf_sim *s, const int32_t *envs, int n)
+{
+    bool any = false;
+    for (int k = 0; k < n && !any; ++k) any = s->wsched && s->wind_K[envs[k]] != 0;
+    if (!any) return SF_OK;
+    const int32_t *list_dev = nullptr;
+    { int rc = wind_list(s, envs, n, &list_dev); if (rc) return rc; }
+    hipLaunchKernelGGL(k_wind_sched_forget, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, n, list_dev, s->wsched);
+    HIPCHK(hipGetLastError());
+    return SF_OK;
+}
+
+// In front of the updates of a stepping call while a schedule is set (enqueue layer): the cache made current for the scheduled
+// tables, the due list made on the device, the due tables rebuilt.  Nothing is read back.
+static int wind_sched_pass(sf_sim *s)
+{
+    const Geo &g = s->g;
+    const int n = (int)s->wind_sched.size();
+    bool cached = s->wind_sched_cached;
+    if (!s->wind_sched_ready) {
+        const int rc = ensure_wterms(s, s->wind_sched.data(), n);
+        if (rc && rc != SF_ENOTSUP) return rc;
+        cached = s->wind_sched_cached = rc == SF_OK;
+        s->wind_sched_ready = true;
+    }
+    if (s->wind_timed) HIPCHK(hipEventRecord(s->ev0, s->stream));
+    HIPCHK(hipMemsetAsync(s->wdue_cnt, 0, sizeof(uint32_t), s->stream));
+    hipLaunchKernelGGL(k_wind_due, dim3((unsigned)((g.E + 255) / 256)), dim3(256), 0, s->stream, g, (const EnvState *)s->commit, (const EnvState *)s->tmp,
+                       (const uint32_t *)s->flags, s->seq, s->committed ? 1 : 0, s->wsched, s->wdue_cnt, s->wdue, s->wdue_U, s->wdue_D);
+    { int rc = wind_launch(s, s->wdue, s->wdue_cnt, 0, n, s->wdue_U, s->wdue_D, 0, cached); if (rc) return rc; }
+    if (s->wind_timed) { HIPCHK(hipEventRecord(s->ev1, s->stream)); s->wind_have_ms = true; }
+    return SF_OK;
+}
+
+// the tables a wind call addresses: the list, or every table in order; what must hold before any device work
+static int wind_targets(const sf_sim *s, const char *who, int32_t n, const int32_t *envs, bool need_per_env, std::vector<int32_t> &tabs)
+{
+    if (n < 0) return fail(SF_EINVAL, "%s: n = %d", who, n);
+    const int n_tab = (int)s->rt_set.size();
+    if ((envs || need_per_env) && !s->p.per_env_terrain)
+        return fail(SF_ESTATE, "%s: this handle shares one terrain between all environments (create it with per_env_terrain = 1)", who);
+    if (envs) { int rc = check_envs(s, who, n, envs, "listed twice"); if (rc) return rc; }
+    else if (n != 0 && n != n_tab) return fail(SF_EINVAL, "%s: without a list n must be the number of tables, %d (got %d)", who, n_tab, n);
+    tabs.resize((size_t)n);
+    for (int i = 0; i < n; ++i) tabs[i] = envs ? envs[i] : i;
+    for (int i = 0; i < n; ++i)
+        if (!s->rd_lay[tabs[i]]) return fail(SF_ESTATE, "%s: table %d has no layers (sf_set_layers*, sf_generate_layers)", who, tabs[i]);
+    return SF_OK;
+}
+
+// fire.py:365, 490-494: self.U / self.U_dir reassigned between two update() calls
+extern "C" int sf_set_wind(sf_sim *s, int32_t n, const int32_t *envs, const double *U, const double *U_dir, int32_t flags)
+{
+    if (!s) return fail(SF_EINVAL, "sf_set_wind: null handle");
+    if (flags & ~(SF_WIND_FIELD | SF_WIND_DEVICE)) return fail(SF_EINVAL, "sf_set_wind: unknown flags 0x%x", flags);
+    if (n > 0 && (!U || !U_dir)) return fail(SF_EINVAL, "sf_set_wind: null argument");
+    std::vector<int32_t> tabs;
+    { int rc = wind_targets(s, "sf_set_wind", n, envs, false, tabs); if (rc) return rc; }
+    if (n == 0) return SF_OK;
+    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
+    const Geo &g = s->g;
+    const bool field = (flags & SF_WIND_FIELD) != 0, device = (flags & SF_WIND_DEVICE) != 0;
+    const size_t cells = (size_t)g.H * g.W, list_bytes = ((size_t)n * 4 + 7) / 8 * 8;
+    const bool scalars = !field && !device;         // the host scalars travel behind the list
+    CallBlock &blk = s->wind_blk;
+    { int rc = block_reserve(s, blk, list_bytes + (scalars ? (size_t)n * 16 : 0)); if (rc) return rc; }
+    memcpy(blk.pinned, tabs.data(), (size_t)n * 4);
+    if (scalars) { memcpy(blk.pinned + list_bytes, U, (size_t)n * 8); memcpy(blk.pinned + list_bytes + (size_t)n * 8, U_dir, (size_t)n * 8); }
+    { int rc = block_send(s, blk, list_bytes + (scalars ? (size_t)n * 16 : 0)); if (rc) return rc; }
+    const int32_t *list_dev = (const int32_t *)blk.dev;
+    const int rcw = ensure_wterms(s, tabs.data(), n);
+    if (rcw && rcw != SF_ENOTSUP) return rcw;
+    const bool cached = rcw == SF_OK;
+    if (s->wind_timed) HIPCHK(hipEventRecord(s->ev0, s->stream));
+    if (field && !device) {
+        // host fields go through the stage buffer, as many tables at a time as fit 64 MB of it (one at least)
+        const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)64 << 20) / (cells * 16)));
+        { int rc = ensure_stage(s, (size_t)chunk * cells * 16); if (rc) return rc; }
+        double *su = (double *)s->stage, *sd = su + (size_t)chunk * cells;
+        for (int i0 = 0; i0 < n; i0 += chunk) {
+            const int cnt = std::min(chunk, n - i0);
+            HIPCHK(hipMemcpyAsync(su, U + (size_t)i0 * cells, (size_t)cnt * cells * 8, hipMemcpyHostToDevice, s->stream));
+            HIPCHK(hipMemcpyAsync(sd, U_dir + (size_t)i0 * cells, (size_t)cnt * cells * 8, hipMemcpyHostToDevice, s->stream));
+            int rc = wind_launch(s, list_dev + i0, nullptr, cnt, cnt, su, sd, 1, cached);
+            if (rc) return rc;
+        }
+    } else {
+        const double *u = scalars ? (const double *)(blk.dev + list_bytes) : U, *d = scalars ? (const double *)(blk.dev + list_bytes) + n : U_dir;
+        int rc = wind_launch(s, list_dev, nullptr, n, n, u, d, field ? 1 : 0, cached);
+        if (rc) return rc;
+    }
+    if (s->wind_timed) { HIPCHK(hipEventRecord(s->ev1, s->stream)); s->wind_have_ms = true; }
+    // the direction-major table was replaced; the cell-major copy, where the buffer exists, was written in the same pass
+    if (s->rtc_stale.size() != s->rt_set.size()) s->rtc_stale.assign(s->rt_set.size(), 1);
+    for (int i = 0; i < n; ++i) {
+        s->rt_set[tabs[i]] = 1;
+        s->rtc_stale[tabs[i]] = s->rtc ? 0 : 1;
+    }
+    s->have_rt = true;
+    for (char c : s->rt_set) if (!c) s->have_rt = false;
+    bool had = false;
+    for (int i = 0; i < n; ++i) if (s->wsched && s->wind_K[tabs[i]]) { had = true; s->wind_K[tabs[i]] = 0; }
+    if (had) {           // a wind set by hand ends the environment's schedule
+        hipLaunchKernelGGL(k_wind_sched_set, dim3((unsigned)n), dim3(SF_WIND_MAX_SEGS), 0, s->stream, n, list_dev, 0, (const sf_wind_seg *)nullptr, s->wsched);
+        HIPCHK(hipGetLastError());
+        wind_sched_count(s);
+    }
+    return finish_call(s, nullptr, !s->async, nullptr);
+}
+
+extern "C" int sf_set_wind_schedule(sf_sim *s, int32_t n, const int32_t *envs, int32_t K, const sf_wind_seg *segs)
+{
+    const char *who = "sf_set_wind_schedule";
+    if (!s) return fail(SF_EINVAL, "%s: null handle", who);
+    if (K < 0 || K > SF_WIND_MAX_SEGS) return fail(SF_EINVAL, "%s: 0 .. %d segments (got %d)", who, SF_WIND_MAX_SEGS, K);
+    if (n > 0 && K > 0 && !segs) return fail(SF_EINVAL, "%s: null argument", who);
+    std::vector<int32_t> tabs;
+    { int rc = wind_targets(s, who, n, envs, true, tabs); if (rc) return rc; }
+    for (int i = 0; i < n; ++i)
+        for (int k = 0; k < K; ++k) {
+            const sf_wind_seg &r = segs[(size_t)i * K + k];
+            if (r.reserved != 0) return fail(SF_EINVAL, "%s: environment %d, segment %d: reserved must be 0", who, tabs[i], k);
+            if (k == 0 ? r.first_update != 0 : r.first_update <= segs[(size_t)i * K + k - 1].first_update)
+                return fail(SF_EINVAL, "%s: environment %d: first_update must be 0 for segment 0 and strictly increasing (segment %d: %d)", who,
+                            tabs[i], k, r.first_update);
+        }
+    if (n == 0) return SF_OK;
+    if (K == 0 && !s->wsched) return SF_OK;
+    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
+    const Geo &g = s->g;
+    if (!s->wsched) {
+        { int rc = dev_alloc(s, &s->wsched, (size_t)g.E); if (rc) return rc; }
+        { int rc = dev_alloc(s, &s->wdue_U, (size_t)2 * g.E); if (rc) return rc; }
+        { int rc = dev_alloc(s, &s->wdue, (size_t)g.E + 2); if (rc) return rc; }
+        s->wdue_D = s->wdue_U + g.E;
+        s->wdue_cnt = reinterpret_cast<uint32_t *>(s->wdue + g.E);
+        HIPCHK(hipMemsetAsync(s->wsched, 0, sizeof(WindSched) * g.E, s->stream));
+        s->wind_K.assign((size_t)g.E, 0);
+    }
+    const size_t list_bytes = ((size_t)n * 4 + 7) / 8 * 8, rows_bytes = (size_t)n * K * sizeof(sf_wind_seg);
+    CallBlock &blk = s->wind_blk;
+    { int rc = block_reserve(s, blk, list_bytes + rows_bytes); if (rc) return rc; }
+    memcpy(blk.pinned, tabs.data(), (size_t)n * 4);
+    if (rows_bytes) memcpy(blk.pinned + list_bytes, segs, rows_bytes);
+    { int rc = block_send(s, blk, list_bytes + rows_bytes); if (rc) return rc; }
+    hipLaunchKernelGGL(k_wind_sched_set, dim3((unsigned)n), dim3(SF_WIND_MAX_SEGS), 0, s->stream, n, (const int32_t *)blk.dev, K,
+                       (const sf_wind_seg *)(blk.dev + list_bytes), s->wsched);
+    HIPCHK(hipGetLastError());
+    for (int i = 0; i < n; ++i) s->wind_K[tabs[i]] = K;
+    wind_sched_count(s);
+    return finish_call(s, nullptr, !s->async, nullptr);
+}
+
+// Laboratory (include/simfire_hip_lab.h): the cache switched off (freed; every wind change then builds from the layers) or on again;
+// HIP events around the launches of every wind change and every schedule pass.
+extern "C" int sf_set_wind_lab(sf_sim *s, int32_t cache_on, int32_t timed)
+{
+    if (!s) return fail(SF_EINVAL, "sf_set_wind_lab: null handle");
+    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
+    if (!cache_on && s->wterms) {
+        HIPCHK(hipStreamSynchronize(s->stream));
+        HIPCHK(hipFree(s->wterms));
+        s->wterms = nullptr;
+        s->bytes -= (int64_t)((size_t)kWindPlanes * s->g.H * s->g.W * s->rt_set.size() * sizeof(float));
+    }
+    s->wt_off = !cache_on;
+    s->wind_sched_ready = false;
+    s->wind_timed = timed != 0;
+    s->wind_have_ms = false;
+    return SF_OK;
+}
+extern "C" int sf_get_wind_ms(sf_sim *s, float *ms_out)
+{
+    if (!s || !ms_out) return fail(SF_EINVAL, "sf_get_wind_ms: null argument");
+    if (!s->wind_have_ms) return fail(SF_ESTATE, "sf_get_wind_ms: no wind change or schedule pass has been timed (sf_set_wind_lab)");
+    HIPCHK(hipSetDevice(s->p.device));
+    HIPCHK(hipEventSynchronize(s->ev1));
+    HIPCHK(hipEventElapsedTime(ms_out, s->ev0, s->ev1));
     return SF_OK;
 }
 
@@ -2067,6 +2346,10 @@ static int enqueue_steps(sf_sim *s, StepPlan p, int n_steps, const int32_t *mit_
 // max_fire_duration updates only.  t0 then stands in front of all the pieces.
 static int enqueue_call(sf_sim *s, const StepPlan &p, int n_steps, const int32_t *mit_dev, int mit_k, bool hold, hipEvent_t t0)
 {
+    if (!s->wind_sched.empty()) {          // a wind schedule is set: the tables that are due, in front of the call's first piece
+        int rc0 = wind_sched_pass(s);
+        if (rc0) return rc0;
+    }
     if (!s->arrival1) return enqueue_steps(s, p, n_steps, mit_dev, mit_k, t0);
     const Geo &g = s->g;
     int rc = SF_OK, launches = 0;
@@ -2388,6 +2671,7 @@ extern "C" int sf_loop_start(sf_sim *s, int32_t k)
     // sleeping loop.  (A stream with a CU mask - hipExtStreamCreateWithCUMask - was tried first: such a stream is a BLOCKING one, a kernel
     // on torch's default stream then waits for the resident loop to leave; profiles/cu_mask_probe.hip has the mask's numbering.)
     const int light = s->tune.v[SF_TUNE_LOOP_LIGHT] > 0 ? 1 : 0;
+    if (!s->wind_sched.empty()) return fail(SF_ENOTSUP, "sf_loop_start: not while a wind schedule is set (sf_set_wind_schedule): a closed loop has no call boundary for the wind to change at");
     if (s->arrival1) return fail(SF_ENOTSUP, "sf_loop_start: not while arrival times are recorded (sf_enable_arrival): a closed loop has no launch boundary for the pass");
     if (g.ab != 1 || s->generic || g.VW != 1 || s->graph_on || s->history || g.dense || g.H > 16 * 64 || g.E > s->n_cu ||
         (s->fused_mode >= 0 && s->fused_mode != 2))
@@ -2737,10 +3021,17 @@ extern "C" int sf_copy_envs(sf_sim *s, const int32_t *src, const int32_t *dst, i
     const bool terrain = (flags & SF_COPY_TERRAIN) && s->rt_set.size() > 1;      // (a stale rtc copy stays marked stale below)
     L.n_seg = arrival_seg(s, L.seg, env_segs(s, terrain ? kForkKinds : kForkKinds & ~kSegTerrain, L.seg));
     const unsigned gx = seg_grid_x(L.seg, L.n_seg);
+    // with the terrain go the slices of section 18, where they exist: the table's part of the wind cache, the environment's schedule
+    // and the segment its table stands for (a launch of their own: the slice table of env_segs is full)
+    CopyList Wl;
+    Wl.n_seg = 0;
+    if (terrain && s->wterms) Wl.seg[Wl.n_seg++] = {reinterpret_cast<uint8_t *>(s->wterms), (long long)kWindPlanes * g.H * g.W * 4, (long long)kWindPlanes * g.H * g.W * 4};
+    if (terrain && s->wsched) Wl.seg[Wl.n_seg++] = {reinterpret_cast<uint8_t *>(s->wsched), (long long)sizeof(WindSched), (long long)sizeof(WindSched)};
     for (int i0 = 0; i0 < n; i0 += kCopyPairs) {
         const int cnt = std::min(kCopyPairs, n - i0);
-        for (int i = 0; i < cnt; ++i) { L.src[i] = src[i0 + i]; L.dst[i] = dst[i0 + i]; }
+        for (int i = 0; i < cnt; ++i) { L.src[i] = Wl.src[i] = src[i0 + i]; L.dst[i] = Wl.dst[i] = dst[i0 + i]; }
         hipLaunchKernelGGL(k_env_copy, dim3(gx, (unsigned)cnt), dim3(256), 0, s->stream, L);
+        if (Wl.n_seg) hipLaunchKernelGGL(k_env_copy, dim3(seg_grid_x(Wl.seg, Wl.n_seg), (unsigned)cnt), dim3(256), 0, s->stream, Wl);
         HIPCHK(hipGetLastError());
     }
     for (int i = 0; i < n; ++i) {
@@ -2755,9 +3046,12 @@ extern "C" int sf_copy_envs(sf_sim *s, const int32_t *src, const int32_t *dst, i
             s->rt_set[dst[i]] = s->rt_set[src[i]];
             if (s->rtc_stale.size() == s->rt_set.size()) s->rtc_stale[dst[i]] = s->rtc_stale[src[i]];
             if (!s->rtc || s->rtc_stale.size() != s->rt_set.size() || s->rtc_stale[dst[i]]) s->rtc_valid = false;
+            if (!s->wt_stale.empty()) s->wt_stale[dst[i]] = s->wt_stale[src[i]];
+            if (s->wsched) s->wind_K[dst[i]] = s->wind_K[src[i]];
         }
     }
     if (terrain) { s->have_rt = true; for (char c : s->rt_set) if (!c) s->have_rt = false; }
+    if (terrain && s->wsched) wind_sched_count(s);
     // (fire_rows bounds every environment's fire, dst's copy included; status_fresh: dst's row is src's current row)
     return finish_call(s, nullptr, !s->async, nullptr);
 }
@@ -3171,6 +3465,7 @@ extern "C" int sf_load_state(sf_sim *s, int32_t n, const int32_t *envs, const vo
         if (!device_pointer) HIPCHK(hipStreamSynchronize(s->stream));      // (the staging buffer is reused by the next pass)
     }
     if (s->bl_cur) s->tiles_valid = false;
+    { int rc = wind_forget(s, envs, n); if (rc) return rc; }      // (a scheduled environment's table stands for the update count it had: decided anew)
     for (int i = 0; i < n; ++i) if (s->snap) s->snap_valid[envs[i]] = 0;
     // fire_rows bounds every environment's fire: the saving handle's bound covers a loaded one (a blob without one makes it unknown)
     s->fire_rows = (s->fire_rows > 0 && fire_rows != INT32_MAX) ? std::max(s->fire_rows, fire_rows) : 0;

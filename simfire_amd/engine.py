@@ -678,6 +678,83 @@ class FireEngine:
                     g.fuel_values[k] = vals[k]
         self._chk(self._L.sf_generate_layers(self._h, n, _ptr(e), C.cast(gens, C.c_void_p)))
 
+    def set_wind(self, speed, direction, envs=None):
+        """A wind change during an episode (``sf_set_wind``): the R tables of ``envs`` (default: every table in
+        order - one on a shared-terrain handle) rebuilt on the device from the new wind and the unchanged fuel and elevation planes;
+        nothing else of the environments' state changes.  ``speed`` (ft/min) and ``direction`` (degrees): scalars or ``[n]`` for a
+        uniform wind per table, ``[H, W]`` or ``[n, H, W]`` for a field - NumPy arrays, or contiguous float64 CUDA tensors on this
+        GPU, which are read in place (torch's current stream is waited for first, as for ``apply_mitigation_torch``'s caller; in
+        async mode the tensors are kept alive until ``sync``).  Clears a listed environment's schedule."""
+        n_tab = self.n_envs if self.params.per_env_terrain else 1
+        e = None if envs is None else self._env_list(envs, "envs")
+        n = n_tab if e is None else int(e.shape[0])
+        on_device = [getattr(a, "is_cuda", None) is not None for a in (speed, direction)]
+        if on_device[0] != on_device[1]:
+            raise ValueError("set_wind: speed and direction must both be arrays or both be CUDA tensors")
+        shapes = {(): 0, (n,): 0, (self.H, self.W): _lib.SF_WIND_FIELD, (n, self.H, self.W): _lib.SF_WIND_FIELD}
+        if on_device[0]:
+            import torch
+            for t, name in ((speed, "speed"), (direction, "direction")):
+                if not t.is_cuda or t.device.index != self.params.device or t.dtype != torch.float64 or not t.is_contiguous():
+                    raise ValueError(f"set_wind: {name} must be a contiguous float64 CUDA tensor on device {self.params.device}")
+            if tuple(speed.shape) != tuple(direction.shape) or tuple(speed.shape) not in shapes:
+                raise ValueError(f"set_wind: speed {tuple(speed.shape)} / direction {tuple(direction.shape)}: scalars, [{n}], "
+                                 f"[{self.H}, {self.W}] or [{n}, {self.H}, {self.W}]")
+            flags = shapes[tuple(speed.shape)] | _lib.SF_WIND_DEVICE
+            lead = (n,) if flags & _lib.SF_WIND_FIELD == 0 else (n, self.H, self.W)
+            if tuple(speed.shape) != lead:              # one value / one field for every listed table
+                speed, direction = speed.expand(lead).contiguous(), direction.expand(lead).contiguous()
+            torch.cuda.synchronize(speed.device)
+            u, d = C.c_void_p(speed.data_ptr()), C.c_void_p(direction.data_ptr())
+        else:
+            sp, dr = np.asarray(speed, dtype=np.float64), np.asarray(direction, dtype=np.float64)
+            if sp.ndim == 0 or dr.ndim == 0:            # (one of the two the same everywhere)
+                sp, dr = np.broadcast_arrays(sp, dr)
+            if sp.shape != dr.shape or sp.shape not in shapes:
+                raise ValueError(f"set_wind: speed {sp.shape} / direction {dr.shape}: scalars, [{n}], [{self.H}, {self.W}] or "
+                                 f"[{n}, {self.H}, {self.W}]")
+            flags = shapes[sp.shape]
+            lead = (n,) if flags == 0 else (n, self.H, self.W)
+            speed, direction = (np.ascontiguousarray(np.broadcast_to(a, lead)) for a in (sp, dr))
+            u, d = _ptr(speed), _ptr(direction)
+        self._chk(self._L.sf_set_wind(self._h, n, None if e is None else _ptr(e), u, d, flags))
+        if on_device[0] and self.async_mode:
+            self._blobs_in_flight.append((speed, direction))
+
+    def set_wind_schedule(self, envs, segments):
+        """Uniform winds by the episode's time, decided on the device (``sf_set_wind_schedule``).  ``segments``:
+        rows ``(first_update, speed ft/min, direction degrees)`` - one list for every environment of ``envs`` (None: all), or one
+        list per environment, all of the same length; the first row starts at update 0, the starts increase strictly, at most 16
+        rows; an empty list clears.  The wind changes where a stepping call begins, never inside one: a call runs entirely under the
+        wind of its environments' update counts at its start.  Needs a ``per_env_terrain`` handle."""
+        e = np.arange(self.n_envs, dtype=np.int32) if envs is None else self._env_list(envs, "envs")
+        n = int(e.shape[0])
+        rows = list(segments)
+        if rows and isinstance(rows[0], (list, tuple)) and rows[0] and isinstance(rows[0][0], (list, tuple)):
+            if len(rows) != n:
+                raise ValueError(f"set_wind_schedule: {len(rows)} schedules for {n} environments")
+            per = [list(r) for r in rows]
+        else:
+            per = [rows] * n
+        K = len(per[0]) if n else 0
+        if any(len(r) != K for r in per):
+            raise ValueError("set_wind_schedule: every environment of one call takes the same number of segments")
+        segs = (_lib.SfWindSeg * max(n * K, 1))()
+        for i, r in enumerate(per):
+            for k, (first, u, d) in enumerate(r):
+                segs[i * K + k] = _lib.SfWindSeg(int(first), 0, float(u), float(d))
+        self._chk(self._L.sf_set_wind_schedule(self._h, n, _ptr(e), K, C.cast(segs, C.c_void_p)))
+
+    def set_wind_lab(self, cache=True, timed=False):
+        """Laboratory (``sf_set_wind_lab``): the cache of wind-independent terms off / on; HIP events around every wind change."""
+        self._chk(self._L.sf_set_wind_lab(self._h, int(bool(cache)), int(bool(timed))))
+
+    def wind_ms(self):
+        """GPU milliseconds of the last timed wind change or schedule pass (``sf_get_wind_ms``)."""
+        ms = C.c_float(0.0)
+        self._chk(self._L.sf_get_wind_ms(self._h, C.byref(ms)))
+        return ms.value
+
     def attribute_data(self, env=0):
         """``FireSimulation.get_attribute_data`` (simfire/sim/simulation.py:376-403) from the layers
         in GPU memory: w_0 / delta / M_x float32, sigma uint32, elevation / wind float64."""

@@ -228,11 +228,7 @@ class FireSimulation:
         # reset at 1024^2), so any in-place edit - one cell of ``config.wind.speed`` included - rebuilds the handle like the
         # reference's reset() rebuilds its terrain and fire manager (simulation.py:202-214).  A harness that never edits its
         # layers in place can set ``sim.assume_layers_immutable = True``: then only object identity and the scalars are compared.
-        key_objs = (cfg.terrain.fuel_layer.data, cfg.terrain.topography_layer.data, cfg.wind.speed, cfg.wind.direction,
-                    getattr(cfg, "fuel_codes", None))
-        key_vals = tuple(getattr(getattr(cfg, a), b) for a, b in _SHARED_FIELDS)
-        if not getattr(self, "assume_layers_immutable", False):
-            key_vals += tuple(_fingerprint(o) for o in key_objs)
+        key_objs, key_vals = self._layers_key()
         prev = getattr(self, "_engine_key", None)
         if (prev is None or len(prev[0]) != len(key_objs) or any(a is not b for a, b in zip(prev[0], key_objs))
                 or prev[1] != key_vals):
@@ -263,6 +259,31 @@ class FireSimulation:
         self.elapsed_time = 0.0
         self.fire_status = GameStatus.RUNNING
         self.active = True
+
+    def _layers_key(self):
+        """What the device handle was built from: the layer objects and, unless ``assume_layers_immutable``, their fingerprints."""
+        cfg = self.config
+        key_objs = (cfg.terrain.fuel_layer.data, cfg.terrain.topography_layer.data, cfg.wind.speed, cfg.wind.direction,
+                    getattr(cfg, "fuel_codes", None))
+        key_vals = tuple(getattr(getattr(cfg, a), b) for a, b in _SHARED_FIELDS)
+        if not getattr(self, "assume_layers_immutable", False):
+            key_vals += tuple(_fingerprint(o) for o in key_objs)
+        return key_objs, key_vals
+
+    def set_wind(self, speed, direction) -> None:
+        """A wind shift between two ``run`` calls: the reference's ``fire_manager.U`` / ``U_dir`` reassigned between two ``update()``
+        calls (fire.py:365, 490-494).  ``speed`` in ft/min and ``direction`` in degrees - the units of ``config.wind.speed`` /
+        ``direction`` - as scalars or ``[H, W]`` arrays.  Every later update spreads under the new wind; the fire's state is
+        untouched.  ``config.wind``, ``environment`` and ``fire_manager.U`` / ``U_dir`` follow, and the next
+        ``reset()`` keeps the handle (the new wind is what it was built from)."""
+        H, W = self.config.area.screen_size
+        sp = np.ascontiguousarray(np.broadcast_to(np.asarray(speed, dtype=np.float64), (H, W)))
+        dr = np.ascontiguousarray(np.broadcast_to(np.asarray(direction, dtype=np.float64), (H, W)))
+        self._engine.set_wind(sp, dr)
+        self.config.wind.speed, self.config.wind.direction = sp, dr
+        self.environment = Environment(self.config.environment.moisture, sp, dr)
+        if getattr(self, "_engine_key", None) is not None:
+            self._engine_key = self._layers_key()
 
     def __deepcopy__(self, memo):
         """An independent simulation in the same state (the reference's ``copy.deepcopy(sim)``): a deep copy of the config, a
@@ -321,6 +342,8 @@ class FireSimulation:
             max_time = sim.config.simulation.runtime
             slope_mag = property(lambda s: sim._engine.get_slopes()[0])
             slope_dir = property(lambda s: sim._engine.get_slopes()[1])
+            U = property(lambda s: sim.config.wind.speed)
+            U_dir = property(lambda s: sim.config.wind.direction)
         return _View()
 
     # -------------------------------------------------------------------------- fire_map
@@ -1012,6 +1035,32 @@ class BatchedFireSimulation:
         fire = getattr(state, "fire_seeds", None)
         if fire is not None and "fire_initial_position" in self._seeds:
             self._seeds["fire_initial_position"][e] = fire
+
+    # ---- wind changes during an episode
+    def set_wind(self, speed_mph, direction, envs=None) -> None:
+        """A wind shift for ``envs`` (default: every environment; on a shared terrain only that): ``speed_mph`` in mph, converted as
+        ``Config`` converts a ``simple`` wind's speed, and ``direction`` in degrees - scalars, ``[n]``, ``[H, W]`` or ``[n, H, W]``,
+        NumPy or float64 CUDA tensors.  The tables become those of a batch built from such configs; the fires go on as they are.
+        ``configs`` / ``terrains`` keep describing the world as it was built."""
+        from .units import mph_to_ftpm
+        if getattr(speed_mph, "is_cuda", None) is None:
+            speed_mph = np.asarray(speed_mph, dtype=np.float64)
+        self._engine.set_wind(mph_to_ftpm(speed_mph), direction, envs)
+
+    def set_wind_schedule(self, envs, segments) -> None:
+        """Winds by the episode's time: rows ``(first_update, speed mph, direction degrees)`` for every environment of ``envs`` (None:
+        all), or one list of rows per environment (``FireEngine.set_wind_schedule``).  The wind changes where a stepping call begins:
+        a ``run`` / ``rollout`` / tick runs entirely under the wind of its environments' update counts at its start; an environment
+        restarted inside a ``BatchedFireEnv.step`` is back under its first row from the next ``step`` on.  Needs per-environment
+        terrain; ``loop_start`` is refused while a schedule is set; an empty list clears."""
+        from .units import mph_to_ftpm
+        rows = list(segments)
+        conv = lambda r: [(int(f), mph_to_ftpm(float(u)), float(d)) for f, u, d in r]
+        if rows and isinstance(rows[0], (list, tuple)) and rows[0] and isinstance(rows[0][0], (list, tuple)):
+            rows = [conv(r) for r in rows]
+        else:
+            rows = conv(rows)
+        self._engine.set_wind_schedule(envs, rows)
 
     # ---- arrival times (DESIGN.md section 17)
     def enable_arrival(self, on: bool = True) -> None:

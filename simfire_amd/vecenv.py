@@ -90,6 +90,15 @@ class BatchedFireEnv:
         self.engine.agents_step(actions, reward=reward, done=done, terms=terms, final_len=final_len, final_ret=final_ret)
         return self._observe(), reward, done, dict(terms=terms, final_len=final_len, final_ret=final_ret)
 
+    def set_wind(self, speed_mph, direction, envs=None):
+        """``BatchedFireSimulation.set_wind``: the wind of ``envs`` from the next tick on."""
+        self.sim.set_wind(speed_mph, direction, envs)
+
+    def set_wind_schedule(self, envs, segments):
+        """``BatchedFireSimulation.set_wind_schedule``: a tick runs under the wind of its environments' update counts at its start; an
+        episode restarted inside ``step`` is under its schedule's first row from the next ``step`` on."""
+        self.sim.set_wind_schedule(envs, segments)
+
     def positions(self):
         """torch int32 [n_envs, n_agents, 3] = (column, row, id): a view of the device positions (current after ``reset`` / ``step``,
         which wait for the handle's stream)."""
