@@ -14,9 +14,10 @@ extern "C" {
 /* same; also reports the GPU time of the n_steps step kernels (HIP events on the handle's
  * stream) so that callers can form bytes / launch-duration. */
 int sf_step_timed(sf_sim *sim, int32_t n_steps, float *ms_out);
-/* on != 0: every sf_reset_envs / sf_reset_where records HIP events on the handle's stream around its two launches;
- * sf_get_reset_ms waits for them and reports the GPU time of the last such call's launches (bytes cleared / launch-duration;
- * SF_ESTATE when none has been timed).  The events are the ones sf_step_timed uses. */
+/* on != 0: every reset (sf_reset, sf_reset_env, sf_reset_envs, sf_reset_where, the auto-reset of sf_agents_step: they all make the
+ * same two launches) records HIP events on the handle's stream around its two launches; sf_get_reset_ms waits for them and reports
+ * the GPU time of the last such call's launches (bytes cleared / launch-duration; SF_ESTATE when none has been timed).  The events
+ * are the ones sf_step_timed uses. */
 int sf_time_resets(sf_sim *sim, int32_t on);
 int sf_get_reset_ms(sf_sim *sim, float *ms_out);
 

@@ -14,7 +14,12 @@ the GPU time of the call's two launches (HIP events on the handle's stream, ``sf
 (computed from the geometry below) over it, as a share of 8 TB/s.
 
   python profiles/reset_batch_probe.py            # -> profiles/reset_batch_timing.txt
-  python profiles/reset_batch_probe.py --quick    # 16 x 256^2, nothing written"""
+  python profiles/reset_batch_probe.py --quick    # 16 x 256^2, nothing written
+  python profiles/reset_batch_probe.py --paths    # the two older entries alone (below), printed; nothing written
+
+``--paths``: wall time of one ``sf_reset_env`` and of one full ``sf_reset`` with their wait, the same shape, rollout and layouts, and
+one small case (1 x 64 x 64, the ``FireSimulation.reset()`` shape) - for A/B runs of two libraries (``SIMFIRE_HIP_LIB``), the way
+``profiles/reset_paths_ab.txt`` was made."""
 import os
 import statistics
 import sys
@@ -132,8 +137,42 @@ def probe(size, E, ns, rollout, lines):
         eng.close()
 
 
+def probe_paths(w, rollout, layouts):
+    """One ``sf_reset_env`` / one full ``sf_reset``, host clock around the call and a ``sync``; two updates before every timed call
+    (not timed) so that each reset meets an episode under way in the layout the line names."""
+    xy = np.ascontiguousarray(w.init_xy, dtype=np.int32)
+    for name, fused in layouts:
+        eng = FireEngine(**w.engine_kwargs())
+        eng.set_layers(*w.layers())
+        eng.set_fused(fused)
+        eng.reset(xy)
+        eng.step(rollout)
+        eng.sync()
+
+        def timed(call):
+            eng.step(2)
+            eng.sync()
+            layout = eng.cell_layout()
+            t0 = time.perf_counter()
+            call()
+            eng.sync()
+            ms = (time.perf_counter() - t0) * 1e3
+            assert eng.cell_layout() == layout
+            return ms
+
+        for what, call in (("sf_reset_env", lambda: eng.reset_env(0, int(xy[0, 0]), int(xy[0, 1]))), ("sf_reset    ", lambda: eng.reset(xy))):
+            timed(call)
+            print("  %-56s %s | %s" % (f"{w.name}, {name} (layout {eng.cell_layout()})", what, med([timed(call) for _ in range(REPS)])), flush=True)
+        eng.close()
+
+
 def main():
     quick = "--quick" in sys.argv
+    if "--paths" in sys.argv:
+        size, E, rollout = (256, 16, 6) if quick else (1024, 256, 100)
+        probe_paths(workloads.c3(size, E), rollout, (("blocked plane current", 2), ("row-major planes current", 0)))
+        probe_paths(workloads.c1(64), 10, (("automatic choice", -1),))
+        return
     lines = []
     if quick:
         probe(256, 16, (1, 8, 16), 6, lines)

@@ -1,6 +1,7 @@
-// Batched reset: new episodes in many environments of a handle at once (k_reset_envs zeroes their slices, k_reset_ignite puts
-// the ignitions, states and result rows down behind it on the same stream).  Part of simfire_hip.hip only (the run units do not
-// include it); the host side is sf_reset_envs / sf_reset_where there, what is written per environment is DESIGN.md section 15.
+// Reset: new episodes in one, many or all environments of a handle at once (k_reset_envs zeroes their slices, k_reset_ignite puts
+// the ignitions, states and result rows down behind it on the same stream).  The only reset there is: sf_reset, sf_reset_env,
+// sf_reset_envs, sf_reset_where and the agents' auto-reset all launch these two (reset_launch in simfire_hip.hip, the one unit
+// that includes this file); what is written per environment is DESIGN.md section 15.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -22,7 +23,7 @@ struct ResetArgs {
     const uint8_t *mask;
     const int32_t *xy;
     int n;
-    // what k_reset_ignite writes (k_init_env's arguments, + the seam planes and the window hint)
+    // what k_reset_ignite writes
     uint8_t *status, *age, *cells;       // cells: the blocked plane when it is current, else null (row-major planes)
     EnvState *commit;
     uint8_t *tflags;
@@ -60,8 +61,9 @@ __global__ __launch_bounds__(256) void k_reset_envs(ResetArgs a)
     }
 }
 
-// One thread per entry, launched behind k_reset_envs on the same stream: what k_init_env writes for the environment, the seam bytes
-// k_rebuild_seams would find for a lone ignition cell, and the window hint.
+// One thread per entry, launched behind k_reset_envs on the same stream: the ignition cell with its tile flag, bitmap words and the
+// seam bytes k_rebuild_seams would find for a lone cell, the window hint, the state of update 0 and the result row that goes with it
+// (running, 0 update() calls, cells per BurnStatus - the launches that follow bring it up to date by difference).
 __global__ __launch_bounds__(256) void k_reset_ignite(ResetArgs a)
 {
     const Geo &g = a.g;

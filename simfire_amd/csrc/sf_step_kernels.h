@@ -957,47 +957,6 @@ __global__ void k_commit(Geo g, EnvState *commit, const EnvState *tmp, uint32_t 
 }
 #endif
 
-#ifndef SF_RUN_UNIT
-__global__ void k_init_env(Geo g, uint8_t *status, uint8_t *age, uint8_t *cells, EnvState *commit, uint8_t *tflags, int ring,
-                           unsigned long long *vbits, const int32_t *xy, int env0, int n, uint8_t *tdirty, int32_t *res_block, double *res_elapsed, int32_t *res_sink)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int e = env0 + i;
-    const int x = xy[2 * i], y = xy[2 * i + 1];
-    // (the caller has zeroed the environment's tile histograms - all UNBURNED - and flags: only the ignition's tile is to be recounted)
-    if (tdirty) tdirty[((long long)e * g.TY + y / (g.LR * g.RB)) * g.TX + (x / 16) / g.LC] = 1;
-    if (cells) {                        // the blocked cell plane is the current one (1-byte sprite masks)
-        uint8_t *cell = cells + (long long)e * g.cells_env + bl_cell(g, y, x);
-        cell[kBlStatus] = SF_BURNING;
-        cell[0] = 1u;
-    } else {
-        status[(long long)e * g.plane_env + (long long)y * g.P + x] = SF_BURNING;   // simulation.py:565-566
-        age_store(g, age + (long long)e * g.age_env * g.ab, (long long)y * g.P + x, 1u);   // ignition step 0
-    }
-    const int tyw = y / (g.LR * g.RB), tx = (x / 16) / g.LC;
-    tflags[(((long long)ring * g.E + e) * g.TYp + tyw + 1) * g.TXp + tx + 1] = 1 | 4 | 8 | 16 | 32;   // all edge bits: conservative
-    {   // vector bitmaps of the resident launch (cleared by the caller): any sprite bit / first cell / last cell
-        const long long o = (long long)e * g.vb_env + (long long)y * g.VW + (x >> 10), plane = (long long)g.E * g.vb_env;
-        const unsigned long long bit = 1ull << ((x >> 4) & 63);
-        vbits[o] = bit;
-        if ((x & 15) == 0) vbits[plane + o] = bit;
-        if ((x & 15) == 15) vbits[2 * plane + o] = bit;
-    }
-    EnvState s;
-    s.running = 1; s.steps = 0; s.complete = 0; s.elapsed = 0.0;
-    s.time_quit = g.has_max_time && (g.update_rate > g.max_time || 0.0 > g.max_time);
-    commit[e] = s;
-    // the environment's row of the result block is known as well (sf_get_status: running, update() calls made, cells per BurnStatus): all
-    // UNBURNED but the ignition cell - the launches that follow bring it up to date by difference (StepArgs::row_valid)
-    if (res_block) {
-        const int32_t row[8] = {1, 0, g.H * g.W - 1, 1, 0, 0, 0, 0};
-        for (int k = 0; k < 8; ++k) { res_block[e * 8 + k] = row[k]; if (res_sink) res_sink[e * 8 + k] = row[k]; }
-        res_elapsed[e] = 0.0;
-    }
-}
-#endif
-
 // Recompute the seam planes of environments [env0, env0 + n) from the sprite-mask plane (after a reset,
 // or when the per-cell kernel, which does not maintain them, hands over to the tiled kernels).
 #ifndef SF_RUN_UNIT

@@ -1414,73 +1414,6 @@ static unsigned seg_grid_x(const EnvSeg *seg, int n)
     return (unsigned)std::min<long long>(1024, std::max<long long>(1, (longest / 16 + 2047) / 2048));
 }
 
-static int reset_range(sf_sim *s, int env0, int n, const int32_t *xy)
-{
-    const Geo &g = s->g;
-    for (int i = 0; i < n; ++i)
-        if (xy[2 * i] < 0 || xy[2 * i] >= g.W || xy[2 * i + 1] < 0 || xy[2 * i + 1] >= g.H)
-            return fail(SF_EINVAL, "reset: ignition (%d, %d) of environment %d is outside the %dx%d grid", xy[2 * i],
-                        xy[2 * i + 1], env0 + i, g.H, g.W);
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    // (the rows of the environments that are reset are written below: a block that was current stays current, a full reset makes it so)
-    if (n == g.E) s->status_fresh = true;
-    { int rc0 = ensure_commit(s); if (rc0) return rc0; }     // the other environments' states must be current in commit[]
-    if (n == g.E) s->cost_steps = 0;                         // new episodes: what the environments cost before says nothing about them
-    if (n == g.E) {
-        // everything is rewritten, nothing to convert: into the blocked plane if the resident launch is what steps this handle
-        // (it did last, or nothing has stepped yet and it is the automatic choice), else into the row-major planes
-        const bool bl = prefers_bl(s) && (s->bl_cur || s->last_kind == 2 || s->last_kind == -1);
-        if (bl) { int rc0 = alloc_bl(s); if (rc0) return rc0; }
-        s->bl_cur = bl;
-    }
-    // Result-block bookkeeping: a freshly reset environment is all UNBURNED but for its ignition cell - its tile histograms are
-    // written here (zeros) and only the ignition's tile is marked for a recount.  (A partial reset while everything is marked stale anyway leaves it at that.)
-    const bool hist_known = g.ab == 1 && !s->generic && (n == g.E || !s->tdirty_all);
-    // What is zeroed here: a batched reset's slices but the seams (rebuild_seams below), + the window advice (where the old fires
-    // stood says nothing about the new ones) and, with new episodes everywhere, the launch-order cost (no order to carry over)
-    EnvSeg seg[kEnvSegs];
-    const int n_seg = arrival_seg(s, seg, env_segs(s, (kResetKinds & ~kSegSeam & ~(hist_known ? 0u : kSegHist)) | kSegHint | (n == g.E ? kSegCost : 0u), seg));
-    for (int k = 0; k < n_seg; ++k) {
-        assert(seg[k].stride == seg[k].len);      // (the slices of env0 .. env0 + n - 1 are one range)
-        HIPCHK(hipMemsetAsync(seg[k].base + env0 * seg[k].stride, 0, (size_t)(n * seg[k].len), s->stream));
-    }
-    if (s->snap) for (int i = 0; i < n; ++i) s->snap_valid[env0 + i] = 1;      // sf_get_fire_map_delta: a reset map is all UNBURNED but for the ignition cell, which the next delta reports
-    int rc = ensure_stage(s, (size_t)n * 2 * sizeof(int32_t));
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(s->stage, xy, (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
-    hipLaunchKernelGGL(k_init_env, dim3((n + 255) / 256), dim3(256), 0, s->stream, g, s->status, s->age, s->bl_cur ? s->cells : nullptr, s->commit,
-                       s->tflags, s->ring, s->vbits, (const int32_t *)s->stage, env0, n, hist_known ? s->tdirty : nullptr, s->status_block, s->elapsed_dev, s->sink);
-    HIPCHK(hipGetLastError());
-    if (!s->bl_cur) {                   // (the tile bookkeeping is not kept while the blocked plane is current: tiles_valid is false)
-        rc = rebuild_seams(s, env0, n);
-        if (rc) return rc;
-    }
-    if (!hist_known) s->tdirty_all = true;
-    else if (n == g.E) s->tdirty_all = false;
-    rc = arrival_pass(s);               // the ignition is the sprite of update 0
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return SF_OK;
-}
-
-extern "C" int sf_reset(sf_sim *s, const int32_t *init_xy)
-{
-    if (!s || !init_xy) return fail(SF_EINVAL, "sf_reset: null argument");
-    int rc = reset_range(s, 0, s->g.E, init_xy);
-    if (rc == SF_OK) { s->was_reset = true; s->vbits_valid = true; s->vbits_fl_valid = true; s->tiles_valid = !s->bl_cur; s->fire_rows = 1; }     // every environment freshly written
-    if (rc == SF_OK && s->xerr_pinned) *s->xerr_pinned = 0;      // (cells, bitmaps, states of every environment are new: what a failed team launch left is gone)
-    return rc;
-}
-
-extern "C" int sf_reset_env(sf_sim *s, int32_t env, int32_t x, int32_t y)
-{
-    if (!s) return fail(SF_EINVAL, "sf_reset_env: null handle");
-    if (env < 0 || env >= s->g.E) return fail(SF_EINVAL, "sf_reset_env: environment %d out of range", env);
-    if (!s->was_reset) return fail(SF_ESTATE, "sf_reset_env: call sf_reset once first");
-    const int32_t xy[2] = {x, y};
-    return reset_range(s, env, 1, xy);
-}
-
 // rows (env, column, row, type) in device memory -> the two scatter kernels (clear, then write with the
 // type precedence of simulation.py:449-478); rows with an out-of-range field are skipped by the kernels
 static int scatter_points(sf_sim *s, const int32_t *pts_dev, int n)
@@ -3119,7 +3052,7 @@ static int state_chunk(const StateArgs &a, bool device)
     return (int)std::max<long long>(1, std::min<long long>(kStateEnvs, (64LL << 20) / a.stride));
 }
 
-// ----------------------------------------------------------------------------- batched reset
+// ----------------------------------------------------------------------------- resets
 // A call's environment list / host ignitions -> device memory through the pinned buffer, one copy; *dev is where they are.
 static int reset_stage(sf_sim *s, const void *a, size_t na, const void *b, size_t nb, uint8_t **dev)
 {
@@ -3131,19 +3064,21 @@ static int reset_stage(sf_sim *s, const void *a, size_t na, const void *b, size_
     return block_send(s, blk, na + nb);
 }
 
-// The two launches of a batched reset.  envs_dev: the list form's environments (distinct), else the mask form over all of them.
-// Writes, for every environment taken, what reset_range + k_init_env + rebuild_seams leave for it in the layout that is current.
-static int reset_launch(sf_sim *s, const int32_t *envs_dev, const uint8_t *mask, const int32_t *xy_dev, int n)
+// The two launches of a reset, the one way an environment gets a new episode: every environment taken is written in the layout that is
+// current.  envs_dev: the list form's environments (distinct), else the mask form over all of them.  full: the list names every
+// environment (sf_reset), so the handle-wide bookkeeping starts afresh too.
+static int reset_launch(sf_sim *s, const int32_t *envs_dev, const uint8_t *mask, const int32_t *xy_dev, int n, bool full = false)
 {
     const Geo &g = s->g;
     ResetArgs a;
     memset(&a, 0, sizeof a);
     a.g = g;
     const bool seams = !s->bl_cur && g.ab == 1;       // (the tile bookkeeping is not kept while the blocked plane is current: tiles_valid is false)
-    // the tile histograms of a reset environment are known (all UNBURNED, the ignition's tile to be recounted) unless every histogram
-    // of the handle is marked stale anyway: reset_range's condition for a partial reset
-    const bool hist_known = g.ab == 1 && !s->generic && !s->tdirty_all;
-    a.n_seg = arrival_seg(s, a.seg, env_segs(s, kResetKinds & ~(seams ? 0u : kSegSeam) & ~(hist_known ? 0u : kSegHist), a.seg));
+    // the tile histograms of a reset environment are known (all UNBURNED, the ignition's tile to be recounted); a partial reset leaves
+    // it at that while every histogram of the handle is marked stale anyway
+    const bool hist_known = g.ab == 1 && !s->generic && (full || !s->tdirty_all);
+    if (full) { s->status_fresh = true; s->cost_steps = 0; }      // every result row is written; the old episodes' costs (run_cost, zeroed) say nothing
+    a.n_seg = arrival_seg(s, a.seg, env_segs(s, (kResetKinds & ~(seams ? 0u : kSegSeam) & ~(hist_known ? 0u : kSegHist)) | (full ? kSegCost : 0u), a.seg));
     a.envs = envs_dev; a.mask = mask; a.xy = xy_dev; a.n = n;
     a.status = s->status; a.age = s->age; a.cells = s->bl_cur ? s->cells : nullptr;
     a.commit = s->commit; a.tflags = s->tflags; a.ring = s->ring; a.vbits = s->vbits; a.win_hint = s->win_hint;
@@ -3152,13 +3087,79 @@ static int reset_launch(sf_sim *s, const int32_t *envs_dev, const uint8_t *mask,
     a.res_block = s->status_block; a.res_sink = s->sink; a.res_elapsed = s->elapsed_dev;
     const unsigned gx = seg_grid_x(a.seg, a.n_seg);
     if (s->rs_timed) HIPCHK(hipEventRecord(s->ev0, s->stream));
-    hipLaunchKernelGGL(k_reset_envs, dim3(gx, (unsigned)n), dim3(256), 0, s->stream, a);
-    HIPCHK(hipGetLastError());
+    // Whole buffers of a large batch: a memset per slice.  Each costs a few microseconds to enqueue and clears ~14 % faster than the
+    // kernel - C3's 2.7 GB in 0.46 ms against 0.50, 1 x 64 x 64 in 59 us against 30 (profiles/reset_paths_ab.txt): even at ~1 GB
+    long long bytes = 0;
+    for (int k = 0; k < a.n_seg; ++k) bytes += g.E * a.seg[k].len;
+    if (full && bytes >= (1LL << 30)) {
+        for (int k = 0; k < a.n_seg; ++k) {
+            assert(a.seg[k].stride == a.seg[k].len);
+            HIPCHK(hipMemsetAsync(a.seg[k].base, 0, (size_t)(g.E * a.seg[k].len), s->stream));
+        }
+    } else {
+        hipLaunchKernelGGL(k_reset_envs, dim3(gx, (unsigned)n), dim3(256), 0, s->stream, a);
+        HIPCHK(hipGetLastError());
+    }
     hipLaunchKernelGGL(k_reset_ignite, dim3((n + 255) / 256), dim3(256), 0, s->stream, a);
     HIPCHK(hipGetLastError());
     if (s->rs_timed) { HIPCHK(hipEventRecord(s->ev1, s->stream)); s->rs_have_ms = true; }
-    if (!hist_known) s->tdirty_all = true;
+    s->tdirty_all = !hist_known;
     return arrival_pass(s);             // the ignitions are the sprites of update 0 (recording off: nothing)
+}
+// Host ignitions: every one on the grid, or SF_EINVAL in the words of the entry `who` (envs: whose they are, null = 0 .. n - 1).
+static int check_ignitions(const sf_sim *s, const char *who, int n, const int32_t *envs, const int32_t *xy)
+{
+    const Geo &g = s->g;
+    for (int i = 0; i < n; ++i)
+        if (xy[2 * i] < 0 || xy[2 * i] >= g.W || xy[2 * i + 1] < 0 || xy[2 * i + 1] >= g.H)
+            return fail(SF_EINVAL, "%s: ignition (%d, %d) of environment %d is outside the %dx%d grid", who, xy[2 * i], xy[2 * i + 1],
+                        envs ? envs[i] : i, g.H, g.W);
+    return SF_OK;
+}
+// The list form from host memory: m distinct environments and their ignitions through the call block, then the launches.
+// (sf_get_fire_map_delta: a reset map is all UNBURNED - the caller zeroes its mirror, the next delta reports the ignition)
+static int reset_list(sf_sim *s, const int32_t *envs, const int32_t *xy, int m, bool full = false)
+{
+    uint8_t *dev = nullptr;
+    { int rc = reset_stage(s, envs, (size_t)m * 4, xy, (size_t)m * 8, &dev); if (rc) return rc; }
+    { int rc = reset_launch(s, reinterpret_cast<const int32_t *>(dev), nullptr, reinterpret_cast<const int32_t *>(dev + (size_t)m * 4), m, full); if (rc) return rc; }
+    if (s->snap) for (int i = 0; i < m; ++i) s->snap_valid[envs[i]] = 1;
+    return SF_OK;
+}
+
+// Every environment, as the list 0 .. E - 1 (without a mask the mask form takes only those that are not running).  Allowed before any
+// reset and on a handle a failed team launch has voided; waits whatever `async` says.
+extern "C" int sf_reset(sf_sim *s, const int32_t *init_xy)
+{
+    if (!s || !init_xy) return fail(SF_EINVAL, "sf_reset: null argument");
+    const int E = s->g.E;
+    { int rc = check_ignitions(s, "reset", E, nullptr, init_xy); if (rc) return rc; }
+    { int rc = begin_call(s, "sf_reset", kCommit); if (rc) return rc; }
+    // everything is rewritten, nothing to convert: into the blocked plane if the resident launch is what steps this handle
+    // (it did last, or nothing has stepped yet and it is the automatic choice), else into the row-major planes
+    const bool bl = prefers_bl(s) && (s->bl_cur || s->last_kind == 2 || s->last_kind == -1);
+    if (bl) { int rc = alloc_bl(s); if (rc) return rc; }
+    s->bl_cur = bl;
+    std::vector<int32_t> all((size_t)E);
+    for (int e = 0; e < E; ++e) all[e] = e;
+    { int rc = reset_list(s, all.data(), init_xy, E, true); if (rc) return rc; }
+    { int rc = finish_call(s, nullptr, true, nullptr); if (rc) return rc; }
+    s->was_reset = true; s->vbits_valid = true; s->vbits_fl_valid = true; s->tiles_valid = !s->bl_cur; s->fire_rows = 1;     // every environment freshly written
+    if (s->xerr_pinned) *s->xerr_pinned = 0;      // (cells, bitmaps, states of every environment are new: what a failed team launch left is gone)
+    return SF_OK;
+}
+
+// One environment: a list of one.  Never refused on a voided handle, and it waits whatever `async` says.
+extern "C" int sf_reset_env(sf_sim *s, int32_t env, int32_t x, int32_t y)
+{
+    if (!s) return fail(SF_EINVAL, "sf_reset_env: null handle");
+    if (env < 0 || env >= s->g.E) return fail(SF_EINVAL, "sf_reset_env: environment %d out of range", env);
+    if (!s->was_reset) return fail(SF_ESTATE, "sf_reset_env: call sf_reset once first");
+    const int32_t xy[2] = {x, y};
+    { int rc = check_ignitions(s, "reset", 1, &env, xy); if (rc) return rc; }
+    { int rc = begin_call(s, "sf_reset_env", kCommit); if (rc) return rc; }
+    { int rc = reset_list(s, &env, xy, 1); if (rc) return rc; }
+    return finish_call(s, nullptr, true, nullptr);
 }
 
 extern "C" int sf_time_resets(sf_sim *s, int32_t on)
@@ -3183,25 +3184,16 @@ extern "C" int sf_reset_envs(sf_sim *s, int32_t n, const int32_t *envs, const in
 {
     if (!s) return fail(SF_EINVAL, "sf_reset_envs: null handle");
     if (n < 0 || (n > 0 && (!envs || !xy))) return fail(SF_EINVAL, "sf_reset_envs: bad environment list");
-    const Geo &g = s->g;
     { int rc = check_envs(s, "sf_reset_envs", n, envs); if (rc) return rc; }      // (a repeated environment is accepted: below)
-    for (int i = 0; i < n; ++i) {
-        if (xy[2 * i] < 0 || xy[2 * i] >= g.W || xy[2 * i + 1] < 0 || xy[2 * i + 1] >= g.H)
-            return fail(SF_EINVAL, "sf_reset_envs: ignition (%d, %d) of environment %d is outside the %dx%d grid", xy[2 * i], xy[2 * i + 1],
-                        envs[i], g.H, g.W);
-    }
+    { int rc = check_ignitions(s, "sf_reset_envs", n, envs, xy); if (rc) return rc; }
     if (n == 0) return SF_OK;
     { int rc = begin_call(s, "sf_reset_envs", kStateCall); if (rc) return rc; }
     // an environment named twice keeps the last ignition given for it: no two entries of the launch write one environment
-    std::vector<int32_t> last((size_t)g.E, -1), le, lxy;
+    std::vector<int32_t> last((size_t)s->g.E, -1), le, lxy;
     for (int i = 0; i < n; ++i) last[envs[i]] = i;
     for (int i = 0; i < n; ++i)
         if (last[envs[i]] == i) { le.push_back(envs[i]); lxy.push_back(xy[2 * i]); lxy.push_back(xy[2 * i + 1]); }
-    const int m = (int)le.size();
-    uint8_t *dev = nullptr;
-    { int rc = reset_stage(s, le.data(), (size_t)m * 4, lxy.data(), (size_t)m * 8, &dev); if (rc) return rc; }
-    { int rc = reset_launch(s, reinterpret_cast<const int32_t *>(dev), nullptr, reinterpret_cast<const int32_t *>(dev + (size_t)m * 4), m); if (rc) return rc; }
-    if (s->snap) for (int i = 0; i < m; ++i) s->snap_valid[le[i]] = 1;      // (sf_get_fire_map_delta: a reset map is all UNBURNED; the next delta reports the ignition)
+    { int rc = reset_list(s, le.data(), lxy.data(), (int)le.size()); if (rc) return rc; }
     return finish_call(s, nullptr, !s->async, nullptr);
 }
 

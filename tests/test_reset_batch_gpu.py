@@ -1,6 +1,11 @@
-"""Batched resets on the GPU (``sf_reset_envs`` / ``sf_reset_where``).  The yardsticks are the existing path
-- a twin handle reset with the ``sf_reset_env`` loop - and ``oracle/fire_dense.c`` replaying every environment's log from its
-last reset; never the new code against itself.  Run with ``pytest -m gpu``."""
+"""Resets on the GPU (``sf_reset`` / ``sf_reset_env`` / ``sf_reset_envs`` / ``sf_reset_where``): every entry runs
+the same two kernels, so a twin handle alone pins nothing.  The yardsticks are the recorded parent - SHA-256 digests of the twin
+worlds of section 1 (``PARENT`` below), taken on the library of the last commit that still had the separate ``sf_reset_env`` path
+(memsets + ``k_init_env`` + ``k_rebuild_seams``), on its ``sf_reset_env`` twin - and ``oracle/fire_dense.c`` replaying every
+environment's log from its last reset.  ``python tests/test_reset_batch_gpu.py`` prints the table of twin A (how ``PARENT`` was
+recorded, with ``SIMFIRE_HIP_LIB`` naming that commit's library).  Run with ``pytest -m gpu``."""
+import hashlib
+
 import numpy as np
 import pytest
 
@@ -44,6 +49,16 @@ def _same(a, b, tag):
     return bb
 
 
+def _digest(eng, maps=False):
+    """SHA-256 of the concatenated state blobs; with ``maps`` also of ``fire_maps()`` and every ``burn(e)`` behind them."""
+    h = hashlib.sha256(_blobs(eng).tobytes())
+    if maps:
+        h.update(eng.fire_maps().tobytes())
+        for e in range(eng.n_envs):
+            h.update(eng.burn(e).tobytes())
+    return h.hexdigest()
+
+
 def _points(rng, E, H, W, p=0.35):
     pts = []
     for e in range(E):
@@ -56,7 +71,8 @@ def _points(rng, E, H, W, p=0.35):
 def _twin_world(seed, mode, H, W, md, att, prune=False, graph=False, E=None, before=(4, 14), after=(10, 31)):
     """Handles A and B built alike and driven through the same random log; at a random update a random subset is reset - A with the
     ``sf_reset_env`` loop, B with one ``sf_reset_envs``.  All state blobs and the result block equal then and after 10 - 30 further
-    updates; on B the blobs of the environments that were not reset are what they were before the call."""
+    updates; on B the blobs of the environments that were not reset are what they were before the call.  Returns the digests of
+    A and of B: (straight after the reset, at the end)."""
     rng = np.random.default_rng(seed)
     E = int(rng.integers(4, 9)) if E is None else E
     kw, R8 = _world(rng, H, W, md, att, diag=True)
@@ -93,6 +109,7 @@ def _twin_world(seed, mode, H, W, md, att, prune=False, graph=False, E=None, bef
     for e in range(E):
         if e not in envs:
             assert now[e].tobytes() == was[e].tobytes(), (seed, mode, "environment not reset changed", e)
+    after_reset = [_digest(x) for x in (a, b)]
     drive(int(rng.integers(*after)))
     _same(a, b, (seed, mode, "at the end"))
     assert a.fire_maps().tobytes() == b.fire_maps().tobytes()
@@ -101,6 +118,7 @@ def _twin_world(seed, mode, H, W, md, att, prune=False, graph=False, E=None, bef
         if graph:
             assert (a.spread_parents(e) == b.spread_parents(e)).all()
     assert b.status()[0][:, 1].max() > 0
+    return [(d, _digest(x, maps=True)) for d, x in zip(after_reset, (a, b))]
 
 
 CASES = {
@@ -112,15 +130,91 @@ CASES = {
 }
 
 
+CASE_1024 = dict(H=1024, W=1024, md=4, att=True, E=4, before=(20, 30), after=(10, 20))
+MODES_1024 = ["run", "fused1"]
+
+# (case, mode) -> twin A's digests (after the reset, at the end) on the parent's library: see the module docstring
+PARENT = {
+    ('37x101_md4_att', 'fused0'): ('5bf4c91e3f3941c3b6e4948c276d388d61fdf0bcd239a7c6428ca1f62f158f60',
+                                   'f3087d5473a57a1eebe5924e45a5b1f4c3705b89504eda099b6ae304f14ce88f'),
+    ('37x101_md4_att', 'fused1'): ('a9d7e1041e2fba4e2a555ec7463964959bfbe45669025b9e3f953c8647fec3b7',
+                                   '1ea9dbba1642d8f56215c253fc84e79b6fbc10e5813a1806987a8df8498314ec'),
+    ('37x101_md4_att', 'run'): ('9881e0f3f151ad46f1fc2e00e5334413fd7f99fbfb96cd5aadac8096278d58e6',
+                                'e1ac8f471ae3ed9bb86eadb80769d10bc0b840b908494bd23db8e9c61e436de3'),
+    ('37x101_md4_att', 'run_win'): ('cbd0b092cae8cbd093ba65b4ae226a6bf0b609147eb519f9ed313304fd09e0f0',
+                                    '7082f2bdb9fa206ab9b37df321c89441ab98b8586baf6e9ff700eb7d41efec33'),
+    ('37x101_md4_att', 'run_team'): ('201cced2ab5e2bcdd48b8f8497dc108d9b0e8c1690fadeb9b9e11fddb46b827f',
+                                     '65f5ede5c2c1c359d24163291dd5960454a954cc82b2ff5d2408ff349eda0737'),
+    ('37x101_md4_att', 'run_kwin'): ('c1c71fa6ce8edc252b8f91e81d5a296fa136e3dca61ece5723f11792c5ef486d',
+                                     '84e422cf11b92b8316941a78ece4f34ded64d7b35016bee8b2a99d258f677c0b'),
+    ('64x64_md7', 'fused0'): ('85e3bbe6a1eca4fa7845e7c787409704620170a257b407aca09b9b12c399a965',
+                              '916fdaa6e760538b5b9c7fea0f632255067acfdebf6d9547fba97d4feeb862d9'),
+    ('64x64_md7', 'fused1'): ('babce581b1d901471b1e205898f9d28cb6fc8ecc5c26dd9c821f7456eeb770ff',
+                              '4234779b9e80ff757b4f830593ede7552e67a47265939aec407062bd191d848d'),
+    ('64x64_md7', 'run'): ('596fc36eeb3fb3bd51b5c82ec61adcec58aebe95ae53143d47da015a96b8edb3',
+                           'd22cd214179d7bf1e84f2f162aa8f56d52c5f82f90005782cfb5436dd41f5868'),
+    ('64x64_md7', 'run_win'): ('bacb9eb84729ca0ef42b99aa56e67147184cda30076408baa11767f38a76646f',
+                               '30b3877ea8dd87707f1fb2eb3ffbf17879456884818efc9ac4881ce8279770f8'),
+    ('64x64_md7', 'run_team'): ('26b52f17aaf7d15dd954517240e1b0570818ddd437f7af5a24efd5c9c98e384a',
+                                '68553e5980871717046e8afac04b3ea474ed5c6a96ab6d2cb9bc7684cbedd57c'),
+    ('64x64_md7', 'run_kwin'): ('8dc4e9d36cca07b8203eac09f8809886687d98d9b0da5b97cb1c7b51e3d71acb',
+                                'aebb2b32cde2f8aeac42e35ec5353bd1a75cd397608a696e6e91d3572b9edbca'),
+    ('225x225_md4_prune', 'fused0'): ('050acb85b7002a3aadebb18f2344f0093b252ca4fb125a5dccad3b26f6c3a509',
+                                      'a0f81ce709b4cee60ec1e9b926db45731dc516dd64352d48362f48e4015c5bdb'),
+    ('225x225_md4_prune', 'fused1'): ('28a38e21b8a95876bff39d9b42690408955a204e2c0cc927279293ed856a8180',
+                                      'aceb4d1c020c0074226a599d3c34b62d276993572f71e1537c69b590203f3bc5'),
+    ('225x225_md4_prune', 'run'): ('f1857320c20bb57df50278902937155eed6a410b0c3219325e432e4851136a9f',
+                                   '44ad8118cf9dff8ab14405f8730272b139ba586837fb7434e8bd9cdada65fb4b'),
+    ('225x225_md4_prune', 'run_win'): ('9b4d09d5dc1d1d22b70e3c455abb02e4203e6814a780f0a04530d36b0b3fba2d',
+                                       'dd7e9bbc5518022943d470669357c3cf3871eedbfcd1e7f089ebbd0474847861'),
+    ('225x225_md4_prune', 'run_team'): ('88eff1de167dc17d14852534920ddc32182b8bb3a8a13add5439bff4ba2ea5d0',
+                                        'e2c8a9bb54b4741c37215874f740d673575d8a2d7e98f218a3a299298bf4943b'),
+    ('225x225_md4_prune', 'run_kwin'): ('16ee45d45bc225763440e9d1827c9c200c1115c53ba47ebf42982ec49a39a652',
+                                        'f3fadb83d89e76ef5915e7654b9f3e97190cd43b69664083f3e8de82244819fe'),
+    ('225x225_md4_att_graph', 'fused0'): ('df63f2b0079d82ea9db417a5141a3d38df430d817010ef7ef3ed9375d672923c',
+                                          'bf4792c960622911a9b3bc4dd3e68269aae0d0b82f9d0353187e50357c047304'),
+    ('225x225_md4_att_graph', 'fused1'): ('8d8f8746f293e86964cf03bb994686b40b1eebb5cb93914992de2fa5a37fdb00',
+                                          '60cae1b285b6c076cc15ea468796af47daaedf977081a9548ebc13dd16f3aa3d'),
+    ('225x225_md4_att_graph', 'run'): ('760feb4987b4dddf2cbb252c9035f9a3de13d3c23c2304f7ce3b38fe0779130f',
+                                       '5b7c8d777e8fefe33c415e07999d11ca3c7b38372db4daa62932878cd8365c07'),
+    ('225x225_md4_att_graph', 'run_win'): ('ac85b570b19338fca85ee389cec7ee0b7aa74622c5c1c7f4867d4ea1dac68c10',
+                                           '14c8a8a4dceabbc3fdadf7ea9425ca9a9fc87c94efaf4aa59229f0d6bb505832'),
+    ('225x225_md4_att_graph', 'run_team'): ('a2eacee1ba1116018f64b1a59e43778c8d4d381d617a66b60f7be9f1188022c8',
+                                            '48f1d2d7ccfae164890c886a822798fd0770d16d46e5104d30936edd1e8ffb4e'),
+    ('225x225_md4_att_graph', 'run_kwin'): ('49e3d910681677b2ea6895f28bc9d53d15888f692871c9da55a65c1695f447fc',
+                                            '726ea9cd7b8ede6b4e1b52dc33e767e4fe24ce05b2cf523f0f6f7d95392533db'),
+    ('225x225_md4_att', 'fused0'): ('60ea9c80c2875f87c74c5b4d2c2921ea8c984093edb9740b07288fa29685e89d',
+                                    '5191432538a31e8fc39567e3098f94a54fe0f5a6bc9ba5afddf0fc9210c074a7'),
+    ('225x225_md4_att', 'fused1'): ('089b126781890824c7828ba570659b7de3207fad6e72584dcabdda460bd9d63b',
+                                    '8a5c86fd3862649fbf774045ddaea2d39dd075debdcc1cb4c86a007545d9fec0'),
+    ('225x225_md4_att', 'run'): ('fb16f4d3f5a7ea1fe2e203b80978b4e3eccc3d9e30dd8db177e6c2c70f9c9378',
+                                 '5c6dcbe3c0f79801bc5b3f1e32dec9a7294a6d1eb1e11a1cdedce9744f7f7009'),
+    ('225x225_md4_att', 'run_win'): ('78caed4c99efc6028a0ddf9f55a89e4a6e1848c48184d30a3e3e83b4942567c8',
+                                     'e2c53e2838fd882e438dbd8e73e076e71c69648881c060707c39977d1b34371d'),
+    ('225x225_md4_att', 'run_team'): ('d4c823096fdf0064c6ba02649b02a3e237c9ee08829c51ed1c36bdfa5367728b',
+                                      '02f5b75b1dd56e4d7e38f43beefd98827e19dd8f14ff7510147c8488909dff5a'),
+    ('225x225_md4_att', 'run_kwin'): ('7d6c5c73be76f42cd6e6d778c63a5948fccf6b66db091fe93c66043932b77f1d',
+                                      '2e97d1aa87b9a88252dec3568b84505c729979a83adf367c3dc8afdd477ee8b4'),
+    ('1024', 'run'): ('73af9fdc38fd264293cf27164e7025d325149ba24502d56fbff722f7b1bc1b00',
+                      '0309631460d7e81105c59db9c9565b546c7f509dc9f365dea33154d28d3eaa38'),
+    ('1024', 'fused1'): ('39ac3a61806b37ee93e8099b63356d6b124dbf594f7eef24b465bc00dfcb6704',
+                         '3698fbd5b3e82884ec87cacf791be5373156c9113a47827e9e0db47b8d9a0ff1'),
+}
+
+
 @pytest.mark.parametrize("mode", list(MODES))
 @pytest.mark.parametrize("case", list(CASES))
 def test_equal_to_the_reset_env_loop(case, mode):
-    _twin_world(81000 + 17 * list(CASES).index(case) + list(MODES).index(mode), mode, **CASES[case])
+    da, db = _twin_world(81000 + 17 * list(CASES).index(case) + list(MODES).index(mode), mode, **CASES[case])
+    print(case, mode, da, db)
+    assert da == PARENT[case, mode] and db == PARENT[case, mode], (case, mode)
 
 
-@pytest.mark.parametrize("mode", ["run", "fused1"])
+@pytest.mark.parametrize("mode", MODES_1024)
 def test_equal_to_the_reset_env_loop_1024(mode):
-    _twin_world(82000 + len(mode), mode, H=1024, W=1024, md=4, att=True, E=4, before=(20, 30), after=(10, 20))
+    da, db = _twin_world(82000 + len(mode), mode, **CASE_1024)
+    print("1024", mode, da, db)
+    assert da == PARENT["1024", mode] and db == PARENT["1024", mode], mode
 
 
 # ------------------------------------------------------------------ 2. equal to the oracle
@@ -180,6 +274,111 @@ def test_equal_to_the_oracle(mode):
                     refs[e] = rep.run(logs[e], [R8])
         for e in range(E):
             _check(eng, e, refs[e], (mode, t, e))
+
+
+# ------------------------------------------------------------------ 2b. the full form (sf_reset) between episodes
+FULL_CASES = {m: (m, None, False) for m in MODES}
+FULL_CASES.update(fused0_then_run=("fused0", "run", False), run_then_fused0=("run", "fused0", False), run_arrival=("run", None, True))
+
+
+@pytest.mark.parametrize("case", list(FULL_CASES))
+def test_full_reset_between_episodes(case):
+    """12 updates with control lines, a full ``reset`` with new ignitions, 12 more updates equal to the oracle after every call.
+    Straight after the reset: the layout the full form chooses, ``run_cost`` zero, every result row that of update 0, the map
+    delta exactly the ignition cell, arrival times 0 there and -1 elsewhere.  Two cases switch the launch structure in between:
+    the layout choice is the branch only a full reset takes - the blocked plane iff the resident launch is what the handle will
+    pick AND it stepped the handle last (or nothing has), so ``fused0 -> set_fused(2)`` starts the new episode on the row-major
+    planes (the first resident launch converts them) and ``run -> set_fused(0)`` leaves the blocked plane."""
+    mode, then, arrival = FULL_CASES[case]
+    rng = np.random.default_rng(83500 + list(FULL_CASES).index(case))
+    H, W = (150, 165) if mode in ("run_team", "run_win", "run_kwin") else (61, 83)
+    E, md = 6, 4
+    kw, R8 = _world(rng, H, W, md, True, diag=True)
+    inits = [(int(rng.integers(W)), int(rng.integers(H))) for _ in range(E)]
+    eng = _make(kw, E, mode, R8, inits)
+    if mode != "run_kwin":
+        assert eng.cell_layout() == (1 if mode in RESIDENT else 0)      # (a handle nothing has stepped yet: the automatic choice)
+    if arrival:
+        eng.enable_arrival(True)
+    for e in range(E):
+        eng.fire_map_delta(e)                               # (the first query sets the reference point up)
+    rep = _Replay(kw, False, False)
+    refs = {}
+
+    def drive(n_updates, chunk, check):
+        t = 0
+        while t < n_updates:
+            pts = _points(rng, E, H, W)
+            if pts:
+                eng.apply_mitigation(pts)
+            n = min(chunk, n_updates - t)
+            eng.step(n)
+            t += n
+            if check:
+                for (e, x, y, ty) in pts:
+                    rep.apply(refs[e], ("mit", [(x, y, ty)]), [R8])
+                for e in range(E):
+                    for _ in range(n):
+                        rep.apply(refs[e], ("step",), [R8])
+                    _check(eng, e, refs[e], (case, t, e))
+
+    drive(12, 2 if mode in RESIDENT else 1, False)
+    st = eng.status()[0]
+    assert st[:, 1].max() > 0 and (st[:, 2] < H * W - 1).any()      # episodes under way: update() calls made, fires that spread
+    if then:
+        eng.set_fused(MODES[then]["fused"])
+    inits = [(int(rng.integers(W)), int(rng.integers(H))) for _ in range(E)]
+    eng.reset(inits)
+    now = then or mode
+    if now != "run_kwin":
+        assert eng.cell_layout() == (1 if now in RESIDENT and mode in RESIDENT else 0), (case, eng.cell_layout())
+    assert (eng.run_cost() == 0).all()
+    st, el = eng.status()
+    assert (st == np.array([1, 0, H * W - 1, 1, 0, 0, 0, 0])).all() and (el == 0).all(), (st, el)
+    for e, (x, y) in enumerate(inits):
+        idx, val = eng.fire_map_delta(e)
+        assert idx.tolist() == [y * W + x] and val.tolist() == [1], (e, idx, val)      # exactly the ignition cell, BURNING
+        if arrival:
+            want = np.full((H, W), -1, dtype=np.int32)
+            want[y, x] = 0
+            assert (eng.arrival(e) == want).all(), e
+    for e in range(E):
+        refs[e] = rep.run([("table", 0), ("reset", inits[e])], [R8])
+    drive(12, 2 if now in RESIDENT else 1, True)
+    assert eng.status()[0][:, 1].max() > 0
+
+
+def test_reset_refusals_change_nothing():
+    """``reset_env`` before any ``reset`` is ``SF_ESTATE``; an ignition off the grid is ``SF_EINVAL`` from ``reset`` and ``reset_env``
+    before anything is enqueued or switched: blobs, result block, ``run_cost`` and the layout - which the full reset would have
+    changed here, the handle being told to step per update from now on - are what they were."""
+    from simfire_amd._lib import SimfireHipError
+    from simfire_amd.engine import FireEngine
+    rng = np.random.default_rng(83900)
+    H, W, E = 37, 101, 4
+    kw, R8 = _world(rng, H, W, 4, True)
+    inits = [(int(rng.integers(W)), int(rng.integers(H))) for _ in range(E)]
+    fresh = FireEngine(n_envs=E, **kw)
+    fresh.set_rtable(R8)
+    with pytest.raises(SimfireHipError, match="sf_reset_env: call sf_reset once first"):
+        fresh.reset_env(0, 1, 1)
+    eng = _make(kw, E, "run", R8, inits)
+    eng.step(6)
+    eng.set_fused(0)
+    assert eng.cell_layout() == 1
+    was, st0, el0, cost0 = _blobs(eng), *eng.status(), eng.run_cost()
+    for bad in ((W, 3), (5, -1)):
+        xy = np.array(inits, dtype=np.int32)
+        xy[2] = bad
+        with pytest.raises(ValueError, match=r"reset: ignition \(%d, %d\) of environment 2 is outside the %dx%d grid" % (*bad, H, W)):
+            eng.reset(xy)
+        with pytest.raises(ValueError, match=r"reset: ignition \(%d, %d\) of environment 2 is outside" % bad):
+            eng.reset_env(2, *bad)
+        st, el = eng.status()
+        assert _blobs(eng).tobytes() == was.tobytes() and (st == st0).all() and el.tobytes() == el0.tobytes(), bad
+        assert eng.cell_layout() == 1 and (eng.run_cost() == cost0).all(), bad
+    eng.reset(inits)                                         # (the same call with ignitions on the grid does switch)
+    assert eng.cell_layout() == 0
 
 
 # ------------------------------------------------------------------ 3. the mask form
@@ -476,3 +675,13 @@ def test_async_mode(mode):
         x.step(3)
     b.sync()
     _same(a, b, "async")
+
+
+if __name__ == "__main__":
+    print("PARENT = {")
+    for ci, case in enumerate(CASES):
+        for mi, mode in enumerate(MODES):
+            print(f"    ({case!r}, {mode!r}): {_twin_world(81000 + 17 * ci + mi, mode, **CASES[case])[0]!r},", flush=True)
+    for mode in MODES_1024:
+        print(f"    ('1024', {mode!r}): {_twin_world(82000 + len(mode), mode, **CASE_1024)[0]!r},", flush=True)
+    print("}")
