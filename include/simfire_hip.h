@@ -377,7 +377,8 @@ int sf_observe(sf_sim *sim, const sf_obs_params *params, int32_t n, const int32_
  *            done = r1[0] != 1 || (done_on_burn && terms[2] > 0) || (max_ticks > 0 && episode length >= max_ticks)
  *   e. outputs: reward, done, terms, and for done environments final_len / final_ret (the episode's length and return; else 0)
  *   f. with auto_reset every done environment is reset as by sf_reset_where(done, the ignitions given to sf_agents_create), its
- *      agents go back to their start cells and its episode statistics are cleared; without it nothing is reset.
+ *      agents go back to their start cells and its episode statistics are cleared; without it nothing is reset.  While
+ *      sf_episodes_set is in force (below) the new episode's ignition, wind and start cells are drawn on the device first.
  * Nothing is read back: in async mode the call only enqueues, otherwise it waits once at its end.  The agent buffers belong to
  * the handle, not to an environment's state: sf_copy_envs and sf_save_state / sf_load_state do not carry them.  With
  * sf_set_prune_after_quit an environment that QUIT on the runtime check is still pruned by the updates of step c. */
@@ -410,6 +411,61 @@ int sf_agents_step(sf_sim *sim, const int32_t *device_actions /* [n_envs][k] */,
 /* The positions, int32 [n_envs][k][3] = (column, row, id = j + 1) in device memory: what sf_observe / sf_render take as agents
  * (agents_device = 1).  The address holds until the next sf_agents_create. */
 int sf_agents_device(sf_sim *sim, void **xyid /* int32 [n_envs][k][3] */);
+
+/* New episodes randomised on the device.  Step f of sf_agents_step re-ignites every done environment at the
+ * same cell, under the same wind, with its agents at the same start cells: a deterministic simulator then replays one world for
+ * ever.  With sf_episodes_set the parameters of a new episode are DRAWN, on the device, for exactly the environments a reset takes,
+ * by a counter-based draw: what episode ep (0, 1, 2, ... counted per environment since sf_episodes_set) of environment env gets
+ * depends on (seed, env, ep) alone - not on the tick, the launch structure or which other environments restart with it.
+ *   mix(z):  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31             (mod 2^64)
+ *   word(seed, env, ep, slot) = mix(mix(seed + G * (env + 1)) + G * ((uint64(ep) << 8) | slot)),  G = 0x9E3779B97F4A7C15
+ *   an integer of [lo, hi] from a 32-bit half h: lo + ((uint64(h) * (hi - lo + 1)) >> 32)
+ *   a double of [a, b) from a word w: a + (b - a) * ((w >> 11) * 2^-53), in double, the product rounded before the sum
+ * Slots 0..63: the ignition attempts (x from the word's high half over the box's columns, y from its low half over its rows);
+ * 64 + j: agent j's start cell (the same split over agent_box); 128: the wind speed, 129: the wind direction.
+ *   SF_EP_IGNITION   the episode ignites at attempt 0's cell.  With SF_EP_LIVE_CELL at the cell of the FIRST attempt whose cell is
+ *                    not dead - dead: all eight rates of the environment's R table are 0 there (unburnable fuel) -; if all 64
+ *                    attempts hit dead cells, attempt 63's cell is taken as it is (the fire then goes out at once).
+ *                    Without SF_EP_IGNITION new episodes ignite where the environment last ignited: the ignitions given to
+ *                    sf_agents_create where agents exist, else those of the last sf_reset.
+ *   SF_EP_WIND       a uniform wind U (ft/min) in [U[0], U[1]), U_dir (degrees) in [U_dir[0], U_dir[1]): the environment's R table is
+ *                    rebuilt as by sf_set_wind behind the reset, inside the same call: the episode runs under its own wind from its
+ *                    first update.  Needs per_env_terrain and layers in every table (SF_ESTATE), and excludes wind schedules: while
+ *                    any schedule is set sf_episodes_set with SF_EP_WIND is SF_ESTATE, and while SF_EP_WIND is set
+ *                    sf_set_wind_schedule is SF_ESTATE.  The cache of wind-independent terms (64 bytes per cell and table; counted
+ *                    by sf_memory_bytes) is made current for every table; without memory for it the tables are built from the layers.
+ *   SF_EP_AGENTS     every agent's start cell (and, on a restart, its position); agents may share a cell and may stand on the
+ *                    ignition.  Allowed before sf_agents_create: it takes effect once agents exist, and a later
+ *                    sf_agents_create keeps the setting.
+ * sf_episodes_set: copies *params, zeroes every environment's episode index; NULL switches randomisation off and frees its buffers.
+ * Unknown flag bits, reserved != 0, a box that is not x0 <= x1, y0 <= y1 on the grid (only the boxes of set flags are looked at), a
+ * range that is not finite with lo <= hi (and U[0] >= 0), SF_EP_LIVE_CELL without SF_EP_IGNITION: SF_EINVAL before any device work.
+ * Without SF_EP_IGNITION on a handle that has neither agents nor been reset: SF_ESTATE.  Ends a running closed loop; waits.
+ * While it is set, step f of sf_agents_step draws before it resets (nothing else of a tick changes; off, a tick is what it was).
+ * sf_episodes_begin: the mask form of sf_reset_where with drawn parameters, for callers without agents (and the first episodes of a
+ * run): all != 0 takes every environment, else device_mask[e] != 0 decides, or - a null mask - "e is not running".  Needs
+ * sf_episodes_set and sf_reset to have run once (SF_ESTATE); ends a running closed loop; under sf_set_async it only enqueues,
+ * otherwise it waits once at its end.  As after sf_reset_where the next sf_get_fire_map_delta of every environment returns -1 once.
+ * sf_episodes_device: zero-copy, for observations and logging - per environment the index of its NEXT episode (uint32), the last
+ * ignition drawn (int32 (x, y); without SF_EP_IGNITION the fixed one) and the last wind drawn (double (U, U_dir); zeros before the
+ * first draw and without SF_EP_WIND).  It reports DRAWS: a later sf_set_wind, sf_reset_envs or sf_copy_envs is not reflected.  The
+ * addresses hold until the next sf_episodes_set; complete once the handle's stream has passed the call that drew.
+ * The episode buffers belong to the handle, as the agent buffers do: sf_copy_envs and sf_save_state / sf_load_state do not carry
+ * them (a forked or restored environment continues its own episode count).  Arrival recording: the plane of a restarted environment
+ * is cleared and gets its ignition as in every reset.  The closed loop (sf_loop_start) has no resets inside it and draws nothing. */
+#define SF_EP_IGNITION  1   /* draw the ignition cell in ign_box                                   */
+#define SF_EP_LIVE_CELL 2   /* ... among cells whose R table is not all zero (64 attempts)         */
+#define SF_EP_WIND      4   /* draw a uniform wind in [U[0], U[1]) x [U_dir[0], U_dir[1])          */
+#define SF_EP_AGENTS    8   /* draw every agent's start cell in agent_box                          */
+typedef struct sf_episode_params {
+    uint64_t seed;
+    int32_t flags, reserved;               /* reserved == 0 */
+    int32_t ign_box[4], agent_box[4];      /* x0, y0, x1, y1, inclusive, on the grid, x0 <= x1, y0 <= y1 */
+    double U[2], U_dir[2];                 /* lo <= hi, finite, U[0] >= 0 */
+} sf_episode_params;
+int sf_episodes_set(sf_sim *sim, const sf_episode_params *params /* NULL: off, buffers freed */);
+int sf_episodes_begin(sf_sim *sim, const uint8_t *device_mask /* [n_envs] or NULL */, int32_t all);
+int sf_episodes_device(sf_sim *sim, void **index /* u32 [n_envs] */, void **ignition /* i32 [n_envs][2] */, void **wind /* f64 [n_envs][2] */);
 
 /* Frames of environments: what the reference's screen shows (simfire/game/game.py:117-131: the terrain image,
  * sprites.py:105-160 with the burned paint, the fire / line / agent sprites of sprites.py:20-203 in SpriteLayer order, enums.py:88-103)

@@ -79,6 +79,15 @@ class SfAgentParams(C.Structure):
                 ("max_ticks", C.c_int32), ("auto_reset", C.c_int32), ("w", C.c_float * 4)]
 
 
+SF_EP_IGNITION, SF_EP_LIVE_CELL, SF_EP_WIND, SF_EP_AGENTS = 1, 2, 4, 8
+
+
+class SfEpisodeParams(C.Structure):
+    """``sf_episode_params`` (include/simfire_hip.h): what a new episode draws on the device."""
+    _fields_ = [("seed", C.c_uint64), ("flags", C.c_int32), ("reserved", C.c_int32), ("ign_box", C.c_int32 * 4),
+                ("agent_box", C.c_int32 * 4), ("U", C.c_double * 2), ("U_dir", C.c_double * 2)]
+
+
 class SfAgentOut(C.Structure):
     """``sf_agent_out`` (include/simfire_hip.h): device pointers, any may be null."""
     _fields_ = [("reward", C.c_void_p), ("done", C.c_void_p), ("terms", C.c_void_p), ("final_len", C.c_void_p),
@@ -121,6 +130,9 @@ SIGNATURES = {
     "sf_agents_place": [_VP, _I32, _VP, _VP, _I32],
     "sf_agents_step": [_VP, _VP, C.POINTER(SfAgentOut)],
     "sf_agents_device": [_VP, C.POINTER(_VP)],
+    "sf_episodes_set": [_VP, C.POINTER(SfEpisodeParams)],
+    "sf_episodes_begin": [_VP, _VP, _I32],
+    "sf_episodes_device": [_VP, C.POINTER(_VP), C.POINTER(_VP), C.POINTER(_VP)],
     "sf_time_resets": [_VP, _I32],
     "sf_get_reset_ms": [_VP, C.POINTER(C.c_float)],
     "sf_apply_mitigation": [_VP, _VP, _I32],

@@ -35,13 +35,20 @@ struct ResetArgs {
     double *res_elapsed;
 };
 
+// The mask form's choice: is environment e taken?  Shared with k_episode_draw (sf_episode_kernels.h), which draws the new episode's
+// parameters for exactly the environments the reset behind it takes.
+__device__ __forceinline__ bool reset_taken(const uint8_t *mask, const EnvState *commit, int e)
+{
+    return mask ? mask[e] != 0 : commit[e].running != 1;
+}
+
 // Entry i of the launch: the environment it resets, or -1.  Both kernels decide by this function; k_reset_envs changes nothing it
 // reads (commit[] is written by k_reset_ignite only, the mask and the ignitions are the caller's).
 __device__ __forceinline__ int reset_pick(const ResetArgs &a, int i, int &x, int &y)
 {
     int e = i;
     if (a.envs) e = a.envs[i];
-    else if (a.mask ? a.mask[i] == 0 : a.commit[i].running == 1) return -1;
+    else if (!reset_taken(a.mask, a.commit, i)) return -1;
     x = a.xy[2 * i]; y = a.xy[2 * i + 1];
     if (x < 0 || x >= a.g.W || y < 0 || y >= a.g.H) return -1;      // (list form: the host has refused these before the launch)
     return e;

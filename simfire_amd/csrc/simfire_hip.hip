@@ -108,6 +108,7 @@ extern "C" const char *sf_version(void) { return "simfire_hip 0.2 (gfx950)"; }  
 #include "sf_agent_kernels.h"
 #include "sf_arrival_kernels.h"
 #include "sf_wind_kernels.h"
+#include "sf_episode_kernels.h"
 
 // Launch-geometry knobs of a handle (sf_set_tuning, include/simfire_hip_lab.h: SF_TUNE_*).  Results never depend on them; the
 // defaults are the measured choices of NOTEBOOK.md 5.  The library does not read the environment for them (the measurement scripts under
@@ -288,6 +289,21 @@ struct sf_sim {
     double *ag_ret = nullptr;
     uint8_t *ag_done = nullptr;
     CallBlock ag_blk;
+    bool ag_has_ign = false;           // sf_agents_create was given ignitions
+    // sf_episodes_* (DESIGN.md section 19): the parameters of sf_episodes_set (ep_on: randomisation is set) and ONE device allocation
+    // for the episode buffers - the next episode's index, the ignition a new episode takes (drawn, or the fixed one), the last wind
+    // drawn, the due list k_episode_draw leaves for k_wind_rtable (the list, its count, the winds) and a mask of ones (all = 1).
+    // The handle's like the agent buffers: not slices of env_segs.  last_ign: the ignitions of the last sf_reset (host copy).
+    // ep_nocache: the cache of wind-independent terms could not be had (no memory, or the lab has it off): not asked for again
+    // until sf_episodes_set / sf_set_wind_lab.
+    sf_episode_params ep = {};
+    bool ep_on = false, ep_nocache = false;
+    uint8_t *ep_mem = nullptr, *ep_ones = nullptr;
+    size_t ep_bytes = 0;
+    uint32_t *ep_index = nullptr, *ep_due_cnt = nullptr;
+    int32_t *ep_ign = nullptr, *ep_due = nullptr;
+    double *ep_wind = nullptr, *ep_due_U = nullptr, *ep_due_D = nullptr;
+    std::vector<int32_t> last_ign;
     bool have_rt = false, was_reset = false, counters_on = false;
     int seq = 0;                       // index (mod 6) of the next step launch
     Tuning tune;                       // sf_set_tuning
@@ -559,7 +575,7 @@ static int destroy(sf_sim *s)
                     s->status_block, s->elapsed_dev, s->stage, s->parents, s->arrival1, s->wterms, s->wsched, s->wdue, s->wdue_U};
     if (s->status_pinned) (void)hipHostFree(s->status_pinned);
     if (s->delta_pinned) (void)hipHostFree(s->delta_pinned);
-    for (void *dp : {(void *)s->snap, (void *)s->delta_dev, (void *)s->rd_bg, (void *)s->rd_fuel_ix, (void *)s->ag_mem}) if (dp) (void)hipFree(dp);
+    for (void *dp : {(void *)s->snap, (void *)s->delta_dev, (void *)s->rd_bg, (void *)s->rd_fuel_ix, (void *)s->ag_mem, (void *)s->ep_mem}) if (dp) (void)hipFree(dp);
     for (CallBlock *b : {&s->obs_blk, &s->rd_blk, &s->rs_blk, &s->gen_blk, &s->ag_blk, &s->wind_blk}) {
         if (b->dev) (void)hipFree(b->dev);
         if (b->pinned) (void)hipHostFree(b->pinned);
@@ -1213,6 +1229,8 @@ extern "C" int sf_set_wind_schedule(sf_sim *s, int32_t n, const int32_t *envs, i
     const char *who = "sf_set_wind_schedule";
     if (!s) return fail(SF_EINVAL, "%s: null handle", who);
     if (K < 0 || K > SF_WIND_MAX_SEGS) return fail(SF_EINVAL, "%s: 0 .. %d segments (got %d)", who, SF_WIND_MAX_SEGS, K);
+    if (s->ep_on && (s->ep.flags & SF_EP_WIND))
+        return fail(SF_ESTATE, "%s: every new episode draws its wind (sf_episodes_set with SF_EP_WIND): a schedule would fight it over the table", who);
     if (n > 0 && K > 0 && !segs) return fail(SF_EINVAL, "%s: null argument", who);
     std::vector<int32_t> tabs;
     { int rc = wind_targets(s, who, n, envs, true, tabs); if (rc) return rc; }
@@ -1265,6 +1283,7 @@ extern "C" int sf_set_wind_lab(sf_sim *s, int32_t cache_on, int32_t timed)
     }
     s->wt_off = !cache_on;
     s->wind_sched_ready = false;
+    s->ep_nocache = false;
     s->wind_timed = timed != 0;
     s->wind_have_ms = false;
     return SF_OK;
@@ -3144,6 +3163,7 @@ extern "C" int sf_reset(sf_sim *s, const int32_t *init_xy)
     for (int e = 0; e < E; ++e) all[e] = e;
     { int rc = reset_list(s, all.data(), init_xy, E, true); if (rc) return rc; }
     { int rc = finish_call(s, nullptr, true, nullptr); if (rc) return rc; }
+    s->last_ign.assign(init_xy, init_xy + (size_t)2 * E);      // (where a new episode ignites when sf_episodes_set draws no ignition)
     s->was_reset = true; s->vbits_valid = true; s->vbits_fl_valid = true; s->tiles_valid = !s->bl_cur; s->fire_rows = 1;     // every environment freshly written
     if (s->xerr_pinned) *s->xerr_pinned = 0;      // (cells, bitmaps, states of every environment are new: what a failed team launch left is gone)
     return SF_OK;
@@ -3228,6 +3248,7 @@ static int agents_free(sf_sim *s)
     s->ag_mem = nullptr; s->ag_bytes = 0;
     s->ag_xyid = s->ag_start = s->ag_points = s->ag_prev = s->ag_terms = s->ag_len = s->ag_ign = nullptr;
     s->ag_ret = nullptr; s->ag_done = nullptr;
+    s->ag_has_ign = false;
     memset(&s->ag, 0, sizeof s->ag);
     return SF_OK;
 }
@@ -3265,8 +3286,11 @@ extern "C" int sf_agents_create(sf_sim *s, const sf_agent_params *p, const int32
     for (size_t i = 0; i < E * K; ++i) xyid[3 * i + 2] = (int32_t)(i % K) + 1;
     if (ignitions_xy) memcpy(h.data() + off[6], ignitions_xy, E * 8);
     HIPCHK(hipMemcpyAsync(s->ag_mem, h.data(), total, hipMemcpyHostToDevice, s->stream));
+    // (section 19: episodes that draw no ignition re-ignite where these agents' environments do)
+    if (ignitions_xy && s->ep_on && !(s->ep.flags & SF_EP_IGNITION)) HIPCHK(hipMemcpyAsync(s->ep_ign, ignitions_xy, E * 8, hipMemcpyHostToDevice, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));          // (h is pageable and leaves scope)
     s->ag = *p;
+    s->ag_has_ign = ignitions_xy != nullptr;
     return SF_OK;
 }
 
@@ -3313,6 +3337,152 @@ extern "C" int sf_agents_device(sf_sim *s, void **xyid)
     return SF_OK;
 }
 
+
+// ----------------------------------------------------------------------------- drawn episodes
+static int episodes_free(sf_sim *s)
+{
+    if (s->ep_mem) {
+        HIPCHK(hipStreamSynchronize(s->stream));      // (enqueued ticks may still use the buffers)
+        HIPCHK(hipFree(s->ep_mem));
+        s->bytes -= (int64_t)s->ep_bytes;
+    }
+    s->ep_mem = s->ep_ones = nullptr; s->ep_bytes = 0;
+    s->ep_index = s->ep_due_cnt = nullptr;
+    s->ep_ign = s->ep_due = nullptr;
+    s->ep_wind = s->ep_due_U = s->ep_due_D = nullptr;
+    memset(&s->ep, 0, sizeof s->ep);
+    s->ep_on = false;
+    return SF_OK;
+}
+
+// New episodes in the environments the mask takes (null: those that are not running), their parameters drawn first (enqueue layer):
+// the draw, the batched reset with the drawn ignitions, then - SF_EP_WIND - the tables of the drawn winds, so that the episode runs
+// under its own wind from its first update.  Nothing is read back.
+static int episode_begin(sf_sim *s, const uint8_t *mask)
+{
+    const Geo &g = s->g;
+    const sf_episode_params &p = s->ep;
+    const bool wind = (p.flags & SF_EP_WIND) != 0;
+    bool cached = false;
+    if (wind) {
+        // the cache of wind-independent terms current for EVERY table (which ones restart is known on the device only), again after
+        // anything staled a part of it (mark_tables); without a cache the tables are built from the layers
+        const int n_tab = (int)s->rt_set.size();
+        bool stale = !s->wterms || s->wt_off;
+        for (int t = 0; t < n_tab && !stale; ++t) stale = s->wt_stale[t] != 0;
+        cached = !stale;
+        if (stale && !s->ep_nocache) {
+            std::vector<int32_t> tabs((size_t)n_tab);
+            for (int t = 0; t < n_tab; ++t) tabs[t] = t;
+            const int rc = ensure_wterms(s, tabs.data(), n_tab);
+            if (rc && rc != SF_ENOTSUP) return rc;
+            cached = rc == SF_OK;
+            s->ep_nocache = !cached;
+        }
+    }
+    EpisodeArgs a;
+    memset(&a, 0, sizeof a);
+    a.H = g.H; a.W = g.W; a.P = g.P; a.E = g.E;
+    a.mask = mask; a.commit = s->commit;
+    a.seed = p.seed; a.flags = p.flags;
+    for (int i = 0; i < 4; ++i) { a.ign_box[i] = p.ign_box[i]; a.agent_box[i] = p.agent_box[i]; }
+    for (int i = 0; i < 2; ++i) { a.U[i] = p.U[i]; a.U_dir[i] = p.U_dir[i]; }
+    a.rt = s->rt; a.tab_stride = s->rt_set.size() > 1 ? (long long)8 * g.plane_env : 0;
+    a.index = s->ep_index; a.ign = s->ep_ign; a.wind = s->ep_wind;
+    a.K = (p.flags & SF_EP_AGENTS) ? s->ag.k : 0;
+    a.start = s->ag_start; a.xyid = s->ag_xyid;
+    a.due_cnt = s->ep_due_cnt; a.due = s->ep_due; a.due_U = s->ep_due_U; a.due_D = s->ep_due_D;
+    if (wind) HIPCHK(hipMemsetAsync(s->ep_due_cnt, 0, sizeof(uint32_t), s->stream));
+    hipLaunchKernelGGL(k_episode_draw, dim3((unsigned)g.E), dim3(kEpAttempts), 0, s->stream, a);
+    HIPCHK(hipGetLastError());
+    { int rc = reset_launch(s, nullptr, mask, s->ep_ign, g.E); if (rc) return rc; }
+    // (section 15's bookkeeping of the mask form: which environments were taken is known on the device only)
+    if (s->snap) std::fill(s->snap_valid.begin(), s->snap_valid.end(), 0);
+    if (wind) {
+        int rc = wind_launch(s, s->ep_due, s->ep_due_cnt, 0, g.E, s->ep_due_U, s->ep_due_D, 0, cached);
+        if (rc) return rc;
+        // rtc_stale as in sf_set_wind: where the cell-major buffer exists the pass has written the listed tables' copies too (a copy
+        // that was stale is no worse for it); where it does not, every table is marked stale when it is allocated (ensure_rtc)
+    }
+    return SF_OK;
+}
+
+extern "C" int sf_episodes_set(sf_sim *s, const sf_episode_params *p)
+{
+    const char *who = "sf_episodes_set";
+    if (!s) return fail(SF_EINVAL, "%s: null handle", who);
+    const Geo &g = s->g;
+    if (p) {
+        if (p->flags & ~(SF_EP_IGNITION | SF_EP_LIVE_CELL | SF_EP_WIND | SF_EP_AGENTS)) return fail(SF_EINVAL, "%s: unknown flags 0x%x", who, p->flags);
+        if (p->reserved != 0) return fail(SF_EINVAL, "%s: reserved must be 0", who);
+        if ((p->flags & SF_EP_LIVE_CELL) && !(p->flags & SF_EP_IGNITION)) return fail(SF_EINVAL, "%s: SF_EP_LIVE_CELL needs SF_EP_IGNITION", who);
+        const struct { int flag; const int32_t *box; const char *name; } boxes[2] = {{SF_EP_IGNITION, p->ign_box, "ign_box"}, {SF_EP_AGENTS, p->agent_box, "agent_box"}};
+        for (const auto &b : boxes)
+            if ((p->flags & b.flag) && (b.box[0] < 0 || b.box[1] < 0 || b.box[2] >= g.W || b.box[3] >= g.H || b.box[0] > b.box[2] || b.box[1] > b.box[3]))
+                return fail(SF_EINVAL, "%s: %s (%d, %d, %d, %d) is not x0 <= x1, y0 <= y1 on the %dx%d grid", who, b.name, b.box[0], b.box[1], b.box[2], b.box[3], g.H, g.W);
+        if (p->flags & SF_EP_WIND) {
+            const bool ok = std::isfinite(p->U[0]) && std::isfinite(p->U[1]) && std::isfinite(p->U_dir[0]) && std::isfinite(p->U_dir[1]) &&
+                            p->U[0] >= 0.0 && p->U[0] <= p->U[1] && p->U_dir[0] <= p->U_dir[1];
+            if (!ok) return fail(SF_EINVAL, "%s: wind ranges U [%g, %g], U_dir [%g, %g] must be finite with lo <= hi and U >= 0", who, p->U[0], p->U[1], p->U_dir[0], p->U_dir[1]);
+            if (!s->p.per_env_terrain) return fail(SF_ESTATE, "%s: SF_EP_WIND: this handle shares one terrain between all environments (create it with per_env_terrain = 1)", who);
+            for (size_t t = 0; t < s->rd_lay.size(); ++t)
+                if (!s->rd_lay[t]) return fail(SF_ESTATE, "%s: SF_EP_WIND: table %d has no layers (sf_set_layers*, sf_generate_layers)", who, (int)t);
+            if (!s->wind_sched.empty()) return fail(SF_ESTATE, "%s: SF_EP_WIND while a wind schedule is set (sf_set_wind_schedule): the two would fight over the table", who);
+        }
+        if (!(p->flags & SF_EP_IGNITION) && !(s->ag.k && s->ag_has_ign) && s->last_ign.empty())
+            return fail(SF_ESTATE, "%s: without SF_EP_IGNITION new episodes ignite where the environment last did: call sf_reset or sf_agents_create (with ignitions) first", who);
+    }
+    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
+    { int rc = episodes_free(s); if (rc) return rc; }
+    if (!p) return SF_OK;
+    // one allocation, every buffer on a 16-byte boundary: index | ign | wind | due | due_cnt | due_U | due_D | ones
+    const size_t E = (size_t)g.E;
+    const size_t sizes[8] = {E * 4, E * 8, E * 16, E * 4, 4, E * 8, E * 8, E};
+    size_t off[8], total = 0;
+    for (int i = 0; i < 8; ++i) { off[i] = total; total += (sizes[i] + 15) / 16 * 16; }
+    HIPCHK(hipMalloc(reinterpret_cast<void **>(&s->ep_mem), total));
+    s->ep_bytes = total; s->bytes += (int64_t)total;
+    s->ep_index = reinterpret_cast<uint32_t *>(s->ep_mem + off[0]);
+    s->ep_ign = reinterpret_cast<int32_t *>(s->ep_mem + off[1]);
+    s->ep_wind = reinterpret_cast<double *>(s->ep_mem + off[2]);
+    s->ep_due = reinterpret_cast<int32_t *>(s->ep_mem + off[3]);
+    s->ep_due_cnt = reinterpret_cast<uint32_t *>(s->ep_mem + off[4]);
+    s->ep_due_U = reinterpret_cast<double *>(s->ep_mem + off[5]);
+    s->ep_due_D = reinterpret_cast<double *>(s->ep_mem + off[6]);
+    s->ep_ones = s->ep_mem + off[7];
+    std::vector<uint8_t> h(total, 0);
+    memset(h.data() + off[7], 1, E);
+    const bool from_agents = s->ag.k && s->ag_has_ign;
+    if (!(p->flags & SF_EP_IGNITION) && !from_agents) memcpy(h.data() + off[1], s->last_ign.data(), E * 8);
+    HIPCHK(hipMemcpyAsync(s->ep_mem, h.data(), total, hipMemcpyHostToDevice, s->stream));
+    if (!(p->flags & SF_EP_IGNITION) && from_agents) HIPCHK(hipMemcpyAsync(s->ep_ign, s->ag_ign, E * 8, hipMemcpyDeviceToDevice, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));          // (h is pageable and leaves scope)
+    s->ep = *p;
+    s->ep_on = true;
+    s->ep_nocache = false;
+    return SF_OK;
+}
+
+extern "C" int sf_episodes_begin(sf_sim *s, const uint8_t *device_mask, int32_t all)
+{
+    const char *who = "sf_episodes_begin";
+    if (!s) return fail(SF_EINVAL, "%s: null handle", who);
+    if (!s->ep_on) return fail(SF_ESTATE, "%s: call sf_episodes_set first", who);
+    const bool tables = (s->ep.flags & (SF_EP_LIVE_CELL | SF_EP_WIND)) != 0;      // the draw reads, or the wind pass rebuilds, R tables
+    { int rc = begin_call(s, who, kStateCall | (tables ? kNeedRt : 0)); if (rc) return rc; }
+    { int rc = episode_begin(s, all ? s->ep_ones : device_mask); if (rc) return rc; }
+    return finish_call(s, nullptr, !s->async, nullptr);
+}
+
+extern "C" int sf_episodes_device(sf_sim *s, void **index, void **ignition, void **wind)
+{
+    if (!s) return fail(SF_EINVAL, "sf_episodes_device: null handle");
+    if (!index || !ignition || !wind) return fail(SF_EINVAL, "sf_episodes_device: null argument");
+    if (!s->ep_on) return fail(SF_ESTATE, "sf_episodes_device: call sf_episodes_set first");
+    *index = s->ep_index; *ignition = s->ep_ign; *wind = s->ep_wind;
+    return SF_OK;
+}
+
 static AgentArgs agent_args(const sf_sim *s, const int32_t *actions, const sf_agent_out *out)
 {
     AgentArgs a;
@@ -3354,7 +3524,8 @@ extern "C" int sf_agents_step(sf_sim *s, const int32_t *device_actions, const sf
     if (!rc) { note_result_look(s); rc = refresh_status(s, nullptr); }      // r1 (commits the step rings too)
     if (!rc) {
         hipLaunchKernelGGL(k_agents_finish, dim3((unsigned)g.E), dim3(kAgentsMax), 0, s->stream, agent_args(s, device_actions, out));
-        if (s->ag.auto_reset) {
+        if (s->ag.auto_reset && s->ep_on) rc = episode_begin(s, s->ag_done);      // section 19: the new episodes are drawn
+        else if (s->ag.auto_reset) {
             rc = reset_launch(s, nullptr, s->ag_done, s->ag_ign, g.E);
             // (section 15's bookkeeping of the mask form: which environments were taken is known on the device only)
             if (!rc && s->snap) std::fill(s->snap_valid.begin(), s->snap_valid.end(), 0);

@@ -42,6 +42,7 @@ class FireEngine:
         self.async_mode = False
         self.arrival_on = False             # arrival times are recorded (enable_arrival)
         self.n_agents = 0                   # agents per environment (agents_create); 0: no agent state
+        self.episodes_on = False            # new episodes draw their parameters on the device (episodes_set)
         self._blobs_in_flight = []          # device state blobs an enqueued save / load may still touch (async mode; released by sync)
         self._h = C.c_void_p()
         self._chk(self._L.sf_create(C.byref(self.params), C.byref(self._h)))
@@ -284,6 +285,87 @@ class FireEngine:
         class _Agents:
             __cuda_array_interface__ = {"shape": shape, "typestr": "<i4", "data": (p.value, False), "version": 2, "strides": None}
         return torch.as_tensor(_Agents(), device=f"cuda:{self.params.device}")
+
+    # ------------------------------------------------------------------ drawn episodes
+    def _box(self, box, name):
+        b = [int(v) for v in box]
+        if len(b) != 4:
+            raise ValueError(f"episodes_set: {name} is (x0, y0, x1, y1), inclusive")
+        if b[0] < 0 or b[1] < 0 or b[2] >= self.W or b[3] >= self.H or b[0] > b[2] or b[1] > b[3]:
+            raise ValueError(f"episodes_set: {name} {tuple(b)} is not x0 <= x1, y0 <= y1 on the {self.H}x{self.W} grid")
+        return b
+
+    def episodes_set(self, seed, ignition_box=None, live_cells=False, wind_speed=None, wind_direction=None, agent_box=None):
+        """Every new episode draws its parameters on the device (``sf_episodes_set``): a function of (seed, environment, episode
+        index) alone.  ``ignition_box`` / ``agent_box`` (x0, y0, x1, y1), inclusive: where the ignition / every agent's start cell
+        is drawn; ``live_cells``: the ignition among cells whose R table is not all zero (64 attempts; needs ``ignition_box``);
+        ``wind_speed`` (lo, hi) ft/min and ``wind_direction`` (lo, hi) degrees: a uniform wind per episode (both or neither; needs
+        ``per_env_terrain`` and layers, excludes wind schedules).  ``None`` leaves a part off: the ignition, the agents' start
+        cells and the wind then stay what they are.  ``seed=None`` switches randomisation off and frees its buffers.  While set,
+        ``agents_step`` draws for every environment its auto-reset takes, and ``episodes_begin`` for those it is told to take.
+        Every environment's episode index starts at 0.  Argument errors are raised before any device call."""
+        if seed is None:
+            self._chk(self._L.sf_episodes_set(self._h, None))
+            self.episodes_on = False
+            return
+        p = _lib.SfEpisodeParams(seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
+        flags = 0
+        if live_cells and ignition_box is None:
+            raise ValueError("episodes_set: live_cells needs an ignition_box")
+        if ignition_box is not None:
+            flags |= _lib.SF_EP_IGNITION | (_lib.SF_EP_LIVE_CELL if live_cells else 0)
+            p.ign_box[:] = self._box(ignition_box, "ignition_box")
+        if agent_box is not None:
+            flags |= _lib.SF_EP_AGENTS
+            p.agent_box[:] = self._box(agent_box, "agent_box")
+        if (wind_speed is None) != (wind_direction is None):
+            raise ValueError("episodes_set: wind_speed and wind_direction go together")
+        if wind_speed is not None:
+            u, d = [float(v) for v in wind_speed], [float(v) for v in wind_direction]
+            if len(u) != 2 or len(d) != 2 or not np.isfinite(u + d).all() or u[0] < 0 or u[0] > u[1] or d[0] > d[1]:
+                raise ValueError(f"episodes_set: wind_speed {tuple(u)} / wind_direction {tuple(d)} must be finite (lo, hi) ranges, "
+                                 "lo <= hi, speed >= 0")
+            flags |= _lib.SF_EP_WIND
+            p.U[:], p.U_dir[:] = u, d
+        p.flags = flags
+        self._chk(self._L.sf_episodes_set(self._h, C.byref(p)))
+        self.episodes_on = True
+
+    def episodes_begin(self, mask=None, all=False):
+        """New episodes with drawn parameters (``sf_episodes_begin``): in every environment (``all=True``), in those ``mask`` selects
+        (a torch CUDA uint8 / bool tensor [n_envs] on this GPU) or, ``mask=None``, in those that are not running - decided on the
+        device, nothing is read back.  The mask form of ``reset_where`` otherwise: torch's queued work on the mask is waited for
+        first; in async mode it is kept alive until ``sync``."""
+        tensors = []
+        if mask is not None and not all:
+            import torch
+            if not isinstance(mask, torch.Tensor) or not mask.is_cuda or mask.dtype not in (torch.uint8, torch.bool) \
+                    or tuple(mask.shape) != (self.n_envs,):
+                raise ValueError(f"episodes_begin: mask must be None or a CUDA uint8 / bool tensor of shape ({self.n_envs},)")
+            mask = mask.contiguous()
+            tensors.append(mask)
+            torch.cuda.synchronize(mask.device)
+        mask_ptr = C.c_void_p(mask.data_ptr()) if tensors else None
+        self._chk(self._L.sf_episodes_begin(self._h, mask_ptr, int(bool(all))))
+        if self.async_mode:
+            self._blobs_in_flight.extend(tensors)
+
+    def episodes_torch(self):
+        """Zero-copy torch views of what the last draw of every environment made (``sf_episodes_device``): ``index`` int32 [n_envs]
+        (the NEXT episode's index; the bits of a uint32), ``ignition`` int32 [n_envs, 2] = (x, y), ``wind`` float64 [n_envs, 2] =
+        (U ft/min, U_dir degrees).  They report draws, not a later ``set_wind``, ``reset_envs`` or ``copy_envs``.  Read-only; the
+        handle's stream is waited for first.  Valid until the next ``episodes_set``."""
+        import torch
+        ptrs = [C.c_void_p(), C.c_void_p(), C.c_void_p()]
+        self._chk(self._L.sf_episodes_device(self._h, *[C.byref(p) for p in ptrs]))
+        self.sync()
+        E, dev = self.n_envs, f"cuda:{self.params.device}"
+
+        def view(ptr, shape, typestr):
+            class _Buf:
+                __cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (ptr.value, False), "version": 2, "strides": None}
+            return torch.as_tensor(_Buf(), device=dev)
+        return dict(index=view(ptrs[0], (E,), "<i4"), ignition=view(ptrs[1], (E, 2), "<i4"), wind=view(ptrs[2], (E, 2), "<f8"))
 
     def apply_mitigation(self, pts):
         """pts: rows (env, x, y, type)."""

@@ -1062,6 +1062,48 @@ class BatchedFireSimulation:
             rows = conv(rows)
         self._engine.set_wind_schedule(envs, rows)
 
+    # ---- new episodes drawn on the device
+    def randomize_episodes(self, seed, ignition_box=None, live_cells: bool = True, wind_speed_mph=None, wind_direction=None,
+                           agent_box=None) -> None:
+        """From now on every new episode that starts on the device - the auto-reset of ``BatchedFireEnv.step``, ``new_episodes`` -
+        DRAWS its parameters there, as a function of (``seed``, environment, the environment's episode count) alone:
+        ``ignition_box`` (x0, y0, x1, y1), inclusive: the ignition cell, with ``live_cells`` among cells that can burn (64 attempts,
+        then whatever the last one hit); ``wind_speed_mph`` (lo, hi) and ``wind_direction`` (lo, hi) degrees: a uniform wind, the
+        speed converted as ``set_wind`` converts it, applied to the range's ends (needs per-environment terrain; excludes
+        ``set_wind_schedule``); ``agent_box``: every agent's start cell.  ``None`` leaves a part as it is: the ignition then stays
+        where the environment last ignited.  ``randomize_episodes(None)`` switches it off.  ``ignitions`` / ``configs`` keep
+        describing the world as it was built; ``episode_info`` shows what was drawn."""
+        if seed is None:
+            self._engine.episodes_set(None)
+            return
+        from .units import mph_to_ftpm
+        if (wind_speed_mph is None) != (wind_direction is None):
+            raise ValueError("randomize_episodes: wind_speed_mph and wind_direction go together")
+        speed = None if wind_speed_mph is None else [float(mph_to_ftpm(float(v))) for v in wind_speed_mph]
+        self._engine.episodes_set(seed, ignition_box=ignition_box, live_cells=bool(live_cells) and ignition_box is not None,
+                                  wind_speed=speed, wind_direction=wind_direction, agent_box=agent_box)
+
+    @property
+    def episodes_randomized(self) -> bool:
+        return bool(self._engine.episodes_on)
+
+    def new_episodes(self, mask=None, all: bool = False) -> None:
+        """New episodes with drawn parameters (after ``randomize_episodes``): everywhere (``all=True``), where ``mask`` - a torch
+        CUDA uint8 / bool tensor [n_envs] - selects, or (``mask=None``) where the old ones are over; decided on the device as in
+        ``reset_done``.  Pending layer seeds are drawn first with ``all=True`` and refused otherwise (``reset_done``)."""
+        if self._pending and all:
+            self._regenerate(sorted(self._pending))
+        elif self._pending:
+            raise ValueError(f"new_episodes: layer seeds are pending for environments {sorted(self._pending)} (set_seeds); which of them "
+                             "start a new episode is known on the device only - call reset(envs) for them")
+        self._engine.episodes_begin(mask, all=all)
+
+    def episode_info(self):
+        """dict of torch CUDA tensors, views of the device buffers: ``index`` int32 [n_envs] the index of every environment's NEXT
+        episode, ``ignition`` int32 [n_envs, 2] the last ignition drawn (x, y), ``wind`` float64 [n_envs, 2] the last wind drawn
+        (ft/min, degrees).  What was DRAWN: a later ``set_wind`` or ``clone_envs`` is not reflected."""
+        return self._engine.episodes_torch()
+
     # ---- arrival times (DESIGN.md section 17)
     def enable_arrival(self, on: bool = True) -> None:
         """Record on the device, for every cell of every environment, the update that ignited it (``arrival``).  Allowed at any

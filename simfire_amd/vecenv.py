@@ -32,7 +32,8 @@ class BatchedFireEnv:
     the fire is out (or the simulation QUIT), with ``done_on_burn`` when an agent stands in the fire, with ``max_ticks > 0`` after
     that many ticks; with ``auto_reset`` a finished environment is re-ignited at ``sim.ignitions[e]`` (as they stand when the
     environment is built) inside the same ``step``, its agents go back to their start cells, and the observation returned is the new
-    episode's.  ``obs``: keyword arguments of ``BatchedFireSimulation.observe`` (``channels`` first of all); its ``agents`` are
+    episode's - or, after ``sim.randomize_episodes``, at a drawn cell, under a drawn wind, with drawn start cells (DESIGN.md
+    section 19).  ``obs``: keyword arguments of ``BatchedFireSimulation.observe`` (``channels`` first of all); its ``agents`` are
     the device positions.
 
     Agents are not part of an environment's state: ``clone_envs`` / ``get_state`` / ``set_state`` do not carry them."""
@@ -70,10 +71,22 @@ class BatchedFireEnv:
         return obs
 
     def reset(self):
-        """New episodes everywhere (``sim.reset()``), the agents on their start cells.  Returns the observation."""
+        """New episodes everywhere (``sim.reset()``), the agents on their start cells.  While the simulation draws its episodes
+        (``sim.randomize_episodes``) they are drawn ones instead (``sim.new_episodes(all=True)``: every environment's next episode
+        index), and with an ``agent_box`` the drawn start cells replace ``start_xy`` - the agents are placed first all the same,
+        which clears the episode statistics.  Returns the observation."""
+        if self.sim.episodes_randomized:
+            self.engine.agents_place(self._all, self.start_xy, also_start=True)
+            self.sim.new_episodes(all=True)
+            return self._observe()
         self.sim.reset()
         self.engine.agents_place(self._all, self.start_xy, also_start=True)
         return self._observe()
+
+    def episode_info(self):
+        """``BatchedFireSimulation.episode_info``: what the last draw of every environment made (index of the next episode,
+        ignition, wind), as device tensors."""
+        return self.sim.episode_info()
 
     def step(self, actions):
         """``actions``: torch CUDA int32 [n_envs, n_agents] (``action_word``).  Returns ``(obs, reward float32 [n_envs],
