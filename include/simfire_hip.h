@@ -222,6 +222,39 @@ int sf_enable_arrival(sf_sim *sim, int32_t on);
 int sf_get_arrival(sf_sim *sim, int32_t env, int32_t *out /* [H*W] */);
 int sf_arrival_device(sf_sim *sim, void **ptr, int64_t *row_pitch, int64_t *env_stride);
 
+/* Values at risk.  The reference keeps no asset values; the entries stand for what a harness of the reference
+ * computes after a run from fire_map.npy (simulation.py:548-549) and a value raster of its own: the worth of every cell that ever
+ * showed BURNING, i.e. whose first sprite was created (fire.py:571-587), and per agent step the part of it that was new.  While a value
+ * plane is set the handle keeps, for every environment,
+ *     damage[e] == the sum of value[e][y][x] over the cells whose arrival is not "never" (sf_get_arrival(e) >= 0), in integers,
+ * complete wherever the arrival plane is complete: behind every stepping call, every form of reset, sf_copy_envs and sf_load_state.
+ * What follows: a cell counts once per episode, when its first sprite is created - the reset's ignition cell included; a cell
+ * that sf_load_fire_map paints BURNING has no sprite and does not count; a control line drawn later gives nothing back; a line
+ * drawn on a burning cell does not count it twice; cells that burned out before sf_enable_arrival do not count.  A new episode
+ * (every form of reset) starts from value[ignition].  The sum is kept by a pass behind the arrival pass, O(fire front), not by the
+ * step kernels; with no plane set every call enqueues what it enqueues without the feature.
+ * sf_values_set: int32 [H*W] for every environment (per_env == 0) or [n_envs][H*W] (per_env != 0), host memory or device memory on
+ * this GPU (device_pointer != 0); the handle keeps a copy of its own (counted by sf_memory_bytes), the caller's memory is free when
+ * the call returns.  |value| <= 2^24, else SF_EINVAL and the handle is as it was: host input is checked before any device work,
+ * device input by a kernel whose verdict the call waits for.  Needs sf_enable_arrival (SF_ESTATE), and while a plane is set
+ * sf_enable_arrival(sim, 0) is SF_ESTATE.  Allowed at any time; ends a running closed loop first (sf_loop_start stays SF_ENOTSUP
+ * as under sf_enable_arrival); damage is recounted from the arrival plane as it stands, under the new plane.  values == NULL switches
+ * the feature off and frees its buffers (and the fifth reward weight with them).
+ * sf_values_get: damage of every environment, complete on return.  SF_ESTATE without a plane.
+ * sf_values_device: for zero-copy consumers - damage (int64 per environment, stride in bytes between environments) and the loss of the
+ * last sf_agents_step tick (int64 [n_envs], contiguous): damage after the tick's updates minus damage before them, 0 for an
+ * environment that was not running before the tick; after an auto-reset tick it still reports the finished episode's last tick
+ * while damage is already the new episode's.  Complete once the handle's stream has reached the end of the last call.
+ * sf_values_set_weight (an entry of this family, not of sf_agents_*: it is refused without a plane): on != 0 adds a fifth product to the reward of sf_agents_step, evaluated like the four (in double, left
+ * to right, rounded to float once): ... + w_value * (double)tick_loss[e]; on == 0 leaves the reward exactly what it is without the
+ * feature.  sf_agent_params.w and sf_agent_out.terms stay four wide.  SF_ESTATE without agents or without a value plane;
+ * sf_agents_create and sf_values_set(NULL) switch the weight off.  State blobs do not carry damage (a restore recounts it), a
+ * fork carries it but not the tick's base. */
+int sf_values_set(sf_sim *sim, const int32_t *values, int32_t per_env, int32_t device_pointer);
+int sf_values_get(sf_sim *sim, int64_t *damage_out /* [n_envs] host */);
+int sf_values_device(sf_sim *sim, void **damage, int64_t *damage_stride, void **tick_loss);
+int sf_values_set_weight(sf_sim *sim, float w_value, int32_t on);
+
 /* FireSimulation.reset for every environment (simulation.py:202-214, 555-566): fire_map all
  * UNBURNED except the ignition cell, burn_amounts 0, one sprite of duration 0, elapsed_time 0.
  * init_xy = int32 [n_envs][2] = (x, y). */

@@ -135,6 +135,12 @@ int sf_get_arrival_passes(sf_sim *sim, int64_t *out /* [2] */);
 /* One more arrival pass over the state as it stands (it finds nothing new: a cell is written once), with HIP events around its launch:
  * the GPU milliseconds of a pass in the form the handle would take now.  SF_ESTATE before sf_enable_arrival. */
 int sf_time_arrival_pass(sf_sim *sim, float *ms_out);
+/* The value pass (sf_values_set) has the two forms of the arrival pass and takes the sparse one under the same
+ * condition.  sf_set_values_dense(1) forces the dense form (the twin of sf_set_arrival_dense; tests compare the two);
+ * sf_get_value_passes: out[0] / out[1] = passes made in the sparse / the dense form since the handle was created, recounts among the
+ * dense.  sf_time_arrival_pass times both passes while a value plane is set.  No reference counterpart. */
+int sf_set_values_dense(sf_sim *sim, int32_t on);
+int sf_get_value_passes(sf_sim *sim, int64_t *out /* [2] */);
 /* Wind changes (sf_set_wind, sf_set_wind_schedule).  cache_on = 0 frees the cache of wind-independent terms and
  * makes every wind change build its tables from the layers (the path a handle takes by itself when it has no memory for the cache);
  * 1 (default) allows the cache again.  timed != 0: HIP events around the launches of every sf_set_wind and every schedule pass;

@@ -122,6 +122,12 @@ SIGNATURES = {
     "sf_set_arrival_dense": [_VP, _I32],
     "sf_get_arrival_passes": [_VP, _VP],
     "sf_time_arrival_pass": [_VP, C.POINTER(C.c_float)],
+    "sf_values_set": [_VP, _VP, _I32, _I32],
+    "sf_values_get": [_VP, _VP],
+    "sf_values_device": [_VP, C.POINTER(_VP), C.POINTER(_I64), C.POINTER(_VP)],
+    "sf_values_set_weight": [_VP, C.c_float, _I32],
+    "sf_set_values_dense": [_VP, _I32],
+    "sf_get_value_passes": [_VP, _VP],
     "sf_reset": [_VP, _VP],
     "sf_reset_env": [_VP, _I32, _I32, _I32],
     "sf_reset_envs": [_VP, _I32, _VP, _VP],

@@ -1,7 +1,7 @@
 // Agents on the device (sf_agents_*): K agents per environment that move on the grid and draw control lines
 // where they stand, stepped from a device action tensor.  k_agents_act turns the action words into moves and this tick's
 // (column, row, type) points in front of the fire update, k_agents_finish turns the result rows on either side of the update into
-// reward, done and episode statistics behind it and sends the agents of finished environments back to their start cells.
+// reward (with the tick's loss of value where a value plane is set), done and episode statistics behind it and sends the agents of finished environments back to their start cells.
 // Part of simfire_hip.hip only (the run units do not include it).  Both kernels read whichever cell plane is current and convert
 // nothing; they write only the agent buffers and the caller's outputs.
 #pragma once
@@ -34,6 +34,14 @@ struct AgentArgs {
     uint8_t *done;             // [E] act: 1 = the environment was not running before the tick; finish: the tick's done flag (the reset's mask)
     int K, only_unburned, done_on_burn, max_ticks, auto_reset;
     double w[4];               // the reward weights, widened from float
+    // values at risk (damage == null: off, and both kernels do what they do without it): damage[e] sits at
+    // damage + e * damage_stride bytes and is complete when either kernel runs
+    const uint8_t *damage;
+    long long damage_stride;
+    long long *tick_base;      // [E] act: damage before the tick
+    long long *tick_loss;      // [E] finish: damage - tick_base, 0 for an environment that was not running before the tick
+    double wv;                 // the fifth weight, widened from float ...
+    int wv_on;                 // ... and whether the fifth product is added at all (sf_values_set_weight)
     // the caller's outputs (device memory; any may be null)
     float *o_reward;
     uint8_t *o_done;
@@ -85,6 +93,7 @@ __global__ __launch_bounds__(kAgentsMax) void k_agents_act(AgentArgs a)
         t[0] = 0; t[1] = n_emit; t[2] = 0; t[3] = n_blocked;
         a.prev_cnt[e] = r0[3] + r0[4];
         a.done[e] = running ? 0 : 1;
+        if (a.damage) a.tick_base[e] = *reinterpret_cast<const long long *>(a.damage + e * a.damage_stride);
     }
 }
 
@@ -106,6 +115,9 @@ __global__ __launch_bounds__(kAgentsMax) void k_agents_finish(AgentArgs a)
         int len = a.ep_len[e];
         double ret = a.ep_ret[e];
         float reward = 0.0f;
+        long long loss = 0;
+        if (a.damage && !was_off) loss = *reinterpret_cast<const long long *>(a.damage + e * a.damage_stride) - a.tick_base[e];
+        if (a.damage) a.tick_loss[e] = loss;
         if (was_off) { t[1] = 0; t[3] = 0; }
         else {
             t[0] = (r1[3] + r1[4]) - a.prev_cnt[e];
@@ -114,6 +126,7 @@ __global__ __launch_bounds__(kAgentsMax) void k_agents_finish(AgentArgs a)
             r = r + a.w[1] * (double)t[1];
             r = r + a.w[2] * (double)t[2];
             r = r + a.w[3] * (double)t[3];
+            if (a.wv_on) r = r + a.wv * (double)loss;     // (a branch, not "+ 0.0": a sum of -0.0 keeps its sign while the weight is off)
             reward = (float)r;
             len += 1;
             ret = ret + (double)reward;

@@ -107,6 +107,7 @@ extern "C" const char *sf_version(void) { return "simfire_hip 0.2 (gfx950)"; }  
 #include "sf_gen_kernels.h"
 #include "sf_agent_kernels.h"
 #include "sf_arrival_kernels.h"
+#include "sf_value_kernels.h"
 #include "sf_wind_kernels.h"
 #include "sf_episode_kernels.h"
 
@@ -229,6 +230,22 @@ struct sf_sim {
     int arr_pending = 0;
     bool arr_dense = false;
     int64_t arr_passes[2] = {0, 0};
+    // sf_values_set: the handle's copy of the value plane, int32 [n][H][P] with n = E (val_per_env) or 1 and zeros
+    // in the pitch padding (null = the feature is off); ONE allocation for the records ValueRec [E], tick_base and tick_loss int64 [E]
+    // and the word the range check of a device plane leaves; the lab's "always the dense pass" and its count of passes made in the
+    // sparse / the dense form; the fifth reward weight of sf_agents_step
+    int32_t *val_plane = nullptr;
+    bool val_per_env = false;
+    uint8_t *val_aux = nullptr;
+    bool val_dense = false;
+    int64_t val_passes[2] = {0, 0};
+    float val_w = 0.0f;
+    bool val_w_on = false;
+    size_t val_plane_bytes() const { return (size_t)(val_per_env ? g.E : 1) * g.plane_env * sizeof(int32_t); }
+    size_t val_aux_bytes() const { return (size_t)g.E * (sizeof(ValueRec) + 16) + 16; }
+    ValueRec *val_rec() const { return reinterpret_cast<ValueRec *>(val_aux); }
+    long long *val_tick(int i) const { return reinterpret_cast<long long *>(val_aux + (size_t)g.E * (sizeof(ValueRec) + 8 * i)); }      // 0: base, 1: loss
+    uint32_t *val_bad() const { return reinterpret_cast<uint32_t *>(val_aux + (size_t)g.E * (sizeof(ValueRec) + 16)); }
     // sf_get_fire_map_delta: the fire maps as the host last saw them (u8 [E][H][P], allocated at the first call), per environment whether that
     // reference point exists, the list of changed cells on the device ([0] = count) and its pinned landing zone
     uint8_t *snap = nullptr;
@@ -329,6 +346,9 @@ static int alloc_bl(sf_sim *s);
 static bool prefers_bl(const sf_sim *s);
 static int arrival_pass(sf_sim *s);
 static int arrival_seg(const sf_sim *s, EnvSeg *seg, int n);
+static int value_seg(const sf_sim *s, EnvSeg *seg, int n);
+static int value_pass(sf_sim *s);
+static int value_recount(sf_sim *s);
 static int wind_forget(sf_sim *s, const int32_t *envs, int n);
 
 // Behind every wait for the handle's stream: has a workgroup of a team launch (k_run<TEAM>) given up waiting for a team member?
@@ -572,7 +592,7 @@ static int destroy(sf_sim *s)
     for (void *hp : {(void *)s->loop_db, (void *)s->loop_res, (void *)s->loop_pts}) if (hp) (void)hipHostFree(hp);
     for (void *dp : {(void *)s->loop_mem, (void *)s->loop_pts_mem}) if (dp) (void)hipFree(dp);
     void *ptrs[] = {s->team_tab, s->team_size, s->xdone, s->xg, s->xbuf, s->xj, s->xcut, s->jlog, s->status, s->age_alloc, s->cells_alloc, s->burn, s->rt, s->rtc, s->lay_all, s->history, s->smag, s->sdir, s->commit, s->tmp, s->flags, s->counters, s->tflags, s->tile_list, s->n_active, s->seam, s->settled, s->tdirty, s->thist, s->vbits, s->todo, s->run_cost, s->run_order, s->todo_cnt, s->win_hint, s->mit_stage,
-                    s->status_block, s->elapsed_dev, s->stage, s->parents, s->arrival1, s->wterms, s->wsched, s->wdue, s->wdue_U};
+                    s->status_block, s->elapsed_dev, s->stage, s->parents, s->arrival1, s->val_plane, s->val_aux, s->wterms, s->wsched, s->wdue, s->wdue_U};
     if (s->status_pinned) (void)hipHostFree(s->status_pinned);
     if (s->delta_pinned) (void)hipHostFree(s->delta_pinned);
     for (void *dp : {(void *)s->snap, (void *)s->delta_dev, (void *)s->rd_bg, (void *)s->rd_fuel_ix, (void *)s->ag_mem, (void *)s->ep_mem}) if (dp) (void)hipFree(dp);
@@ -1645,7 +1665,7 @@ static int arrival_pass(sf_sim *s)
     HIPCHK(hipGetLastError());
     s->arr_passes[sparse ? 0 : 1]++;
     s->arr_pending = 0;
-    return SF_OK;
+    return s->val_plane ? value_pass(s) : SF_OK;      // the plane is complete up to commit[].steps: so is the damage behind this
 }
 // The plane's per-environment slice behind the n slices env_segs has filled (a reset zeroes it, a fork copies it): appended here and not
 // a kind of sf_env_segs.h - the plane is not one of the buffers the step kernels know.  Returns the new count.
@@ -1656,6 +1676,151 @@ static int arrival_seg(const sf_sim *s, EnvSeg *seg, int n)
     const long long len = s->g.plane_env * 4;
     seg[n] = {reinterpret_cast<uint8_t *>(s->arrival1), len, len};
     return n + 1;
+}
+
+// ----------------------------------------------------------------------------- values at risk
+static ValueArgs value_args(const sf_sim *s)
+{
+    ValueArgs a;
+    a.values = s->val_plane; a.values_env = s->val_per_env ? s->g.plane_env : 0;
+    a.arrival1 = s->arrival1; a.commit = s->commit; a.rec = s->val_rec();
+    return a;
+}
+// The pass behind the arrival pass (sf_value_kernels.h; arrival_pass has folded the step rings and completed the plane): the sum
+// over the window in the sparse form under the arrival pass's own condition, else dense, then the commit of the records.
+static int value_pass(sf_sim *s)
+{
+    const Geo &g = s->g;
+    const bool sparse = s->bl_cur && s->vbits_valid && s->vbits_fl_valid && !s->val_dense;
+    if (sparse) hipLaunchKernelGGL(k_value_bits, dim3((unsigned)((g.H * g.VW + 255) / 256), (unsigned)g.E), dim3(256), 0, s->stream, g,
+                                   (const unsigned long long *)s->vbits, value_args(s));
+    else hipLaunchKernelGGL(k_value_cells, dim3((unsigned)((g.W + 255) / 256), (unsigned)g.H, (unsigned)g.E), dim3(256), 0, s->stream, g, value_args(s));
+    hipLaunchKernelGGL(k_value_commit, dim3((unsigned)((g.E + 255) / 256)), dim3(256), 0, s->stream, g.E, (const EnvState *)s->commit, s->val_rec());
+    HIPCHK(hipGetLastError());
+    s->val_passes[sparse ? 0 : 1]++;
+    return SF_OK;
+}
+// Every record from the arrival plane as it stands (sf_values_set, sf_load_state): records of zeros, then the dense form once over
+// every environment - by the invariant exact for all of them.  A handle that was never reset has nothing to count.
+static int value_recount(sf_sim *s)
+{
+    if (!s->val_plane) return SF_OK;
+    const Geo &g = s->g;
+    HIPCHK(hipMemsetAsync(s->val_rec(), 0, (size_t)g.E * sizeof(ValueRec), s->stream));
+    if (!s->was_reset) return SF_OK;
+    if (s->arr_pending) return arrival_pass(s);       // (a call that failed half way left updates behind: the plane first, the pass behind it counts)
+    { int rc = ensure_commit(s); if (rc) return rc; }
+    hipLaunchKernelGGL(k_value_cells, dim3((unsigned)((g.W + 255) / 256), (unsigned)g.H, (unsigned)g.E), dim3(256), 0, s->stream, g, value_args(s));
+    hipLaunchKernelGGL(k_value_commit, dim3((unsigned)((g.E + 255) / 256)), dim3(256), 0, s->stream, g.E, (const EnvState *)s->commit, s->val_rec());
+    HIPCHK(hipGetLastError());
+    s->val_passes[1]++;
+    return SF_OK;
+}
+// The record's slice behind the arrival plane's (a reset zeroes it: upto1 == 0, the pass behind the reset sums the ignition; a fork
+// copies it with the plane): appended like arrival_seg.  Returns the new count.
+static int value_seg(const sf_sim *s, EnvSeg *seg, int n)
+{
+    if (!s->val_plane) return n;
+    assert(n < kEnvSegs);
+    seg[n] = {reinterpret_cast<uint8_t *>(s->val_rec()), (long long)sizeof(ValueRec), (long long)sizeof(ValueRec)};
+    return n + 1;
+}
+static int value_free(sf_sim *s)
+{
+    if (!s->val_plane) return SF_OK;
+    HIPCHK(hipStreamSynchronize(s->stream));
+    s->bytes -= (int64_t)(s->val_plane_bytes() + s->val_aux_bytes());
+    HIPCHK(hipFree(s->val_plane)); s->val_plane = nullptr;
+    HIPCHK(hipFree(s->val_aux)); s->val_aux = nullptr;
+    s->val_w_on = false;
+    return SF_OK;
+}
+
+extern "C" int sf_values_set(sf_sim *s, const int32_t *values, int32_t per_env, int32_t device_pointer)
+{
+    if (!s) return fail(SF_EINVAL, "sf_values_set: null handle");
+    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
+    if (!values) return value_free(s);
+    if (!s->arrival1) return fail(SF_ESTATE, "sf_values_set: call sf_enable_arrival first (the arrival plane says which cells count)");
+    const Geo &g = s->g;
+    const size_t n_planes = per_env ? (size_t)g.E : 1, rows = n_planes * g.H, cells = rows * g.W;
+    if (!device_pointer)
+        for (size_t i = 0; i < cells; ++i)
+            if (values[i] > kValueMax || values[i] < -kValueMax)
+                return fail(SF_EINVAL, "sf_values_set: value %d (entry %lld) is outside -2^24 .. 2^24", values[i], (long long)i);
+    { int rc = check_team_error(s, "sf_values_set"); if (rc) return rc; }
+    // the new plane and, the first time, the records: made and checked before the handle changes (a refused call leaves it as it was)
+    int32_t *plane = nullptr;
+    uint8_t *aux = s->val_aux;
+    const size_t plane_bytes = rows * g.P * sizeof(int32_t);
+    HIPCHK(hipMalloc(reinterpret_cast<void **>(&plane), plane_bytes));
+    if (!aux && hipMalloc(reinterpret_cast<void **>(&aux), s->val_aux_bytes()) != hipSuccess) { (void)hipFree(plane); return fail(SF_EHIP, "sf_values_set: hipMalloc failed"); }
+    hipError_t err = hipMemsetAsync(aux, 0, s->val_aux_bytes(), s->stream);      // (records and ticks start from zero under a new plane)
+    if (err == hipSuccess) err = hipMemsetAsync(plane, 0, plane_bytes, s->stream);
+    if (err == hipSuccess) err = hipMemcpy2DAsync(plane, (size_t)g.P * 4, values, (size_t)g.W * 4, (size_t)g.W * 4, rows,
+                                                  device_pointer ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->stream);
+    uint32_t bad = 0;
+    if (err == hipSuccess && device_pointer) {
+        uint32_t *word = reinterpret_cast<uint32_t *>(aux + (size_t)g.E * (sizeof(ValueRec) + 16));
+        hipLaunchKernelGGL(k_value_range, dim3((unsigned)std::min<size_t>((cells + 255) / 256, 4096)), dim3(256), 0, s->stream, values, (long long)cells, word);
+        err = hipGetLastError();
+        if (err == hipSuccess) err = hipMemcpyAsync(&bad, word, sizeof bad, hipMemcpyDeviceToHost, s->stream);
+    }
+    if (err == hipSuccess) err = hipStreamSynchronize(s->stream);      // (the caller's memory is free again; kernels that read the old plane are through)
+    if (err != hipSuccess || bad) {
+        (void)hipFree(plane);
+        if (!s->val_aux) (void)hipFree(aux);
+        else if (s->was_reset) (void)value_recount(s);      // (the records were zeroed above: counted again under the plane that stays)
+        if (bad) return fail(SF_EINVAL, "sf_values_set: a value of the device plane is outside -2^24 .. 2^24");
+        return fail(SF_EHIP, "sf_values_set: %s", hipGetErrorString(err));
+    }
+    if (s->val_plane) { s->bytes -= (int64_t)s->val_plane_bytes(); HIPCHK(hipFree(s->val_plane)); }
+    else s->bytes += (int64_t)s->val_aux_bytes();
+    s->val_plane = plane; s->val_aux = aux; s->val_per_env = per_env != 0;
+    s->bytes += (int64_t)s->val_plane_bytes();
+    { int rc = value_recount(s); if (rc) return rc; }
+    return finish_call(s, nullptr, !s->async, nullptr);
+}
+
+extern "C" int sf_values_get(sf_sim *s, int64_t *damage_out)
+{
+    if (!s || !damage_out) return fail(SF_EINVAL, "sf_values_get: null argument");
+    if (!s->val_plane) return fail(SF_ESTATE, "sf_values_get: call sf_values_set first");
+    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
+    HIPCHK(hipMemcpy2DAsync(damage_out, 8, s->val_rec(), sizeof(ValueRec), 8, (size_t)s->g.E, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return check_team_error(s, "sf_values_get");
+}
+
+extern "C" int sf_values_device(sf_sim *s, void **damage, int64_t *damage_stride, void **tick_loss)
+{
+    if (!s || !damage || !damage_stride || !tick_loss) return fail(SF_EINVAL, "sf_values_device: null argument");
+    if (!s->val_plane) return fail(SF_ESTATE, "sf_values_device: call sf_values_set first");
+    *damage = s->val_rec(); *damage_stride = (int64_t)sizeof(ValueRec); *tick_loss = s->val_tick(1);
+    return SF_OK;
+}
+
+extern "C" int sf_values_set_weight(sf_sim *s, float w_value, int32_t on)
+{
+    if (!s) return fail(SF_EINVAL, "sf_values_set_weight: null handle");
+    if (!s->ag.k) return fail(SF_ESTATE, "sf_values_set_weight: call sf_agents_create first");
+    if (!s->val_plane) return fail(SF_ESTATE, "sf_values_set_weight: call sf_values_set first");
+    s->val_w = w_value; s->val_w_on = on != 0;
+    return SF_OK;
+}
+
+extern "C" int sf_set_values_dense(sf_sim *s, int32_t on)
+{
+    if (!s) return fail(SF_EINVAL, "sf_set_values_dense: null handle");
+    s->val_dense = on != 0;
+    return SF_OK;
+}
+
+extern "C" int sf_get_value_passes(sf_sim *s, int64_t *out)
+{
+    if (!s || !out) return fail(SF_EINVAL, "sf_get_value_passes: null argument");
+    out[0] = s->val_passes[0]; out[1] = s->val_passes[1];
+    return SF_OK;
 }
 
 extern "C" int sf_last_step_launch(sf_sim *s, int32_t *kind)
@@ -2396,6 +2561,7 @@ extern "C" int sf_enable_arrival(sf_sim *s, int32_t on)
     const size_t n = (size_t)s->g.E * s->g.plane_env;
     if (!on) {
         if (!s->arrival1) return SF_OK;
+        if (s->val_plane) return fail(SF_ESTATE, "sf_enable_arrival: a value plane is set and needs the arrival plane: switch it off first (sf_values_set with NULL)");
         HIPCHK(hipStreamSynchronize(s->stream));
         HIPCHK(hipFree(s->arrival1));
         s->arrival1 = nullptr;
@@ -2971,7 +3137,11 @@ extern "C" int sf_copy_envs(sf_sim *s, const int32_t *src, const int32_t *dst, i
     // the next step rebuild them for every environment.
     CopyList L;
     const bool terrain = (flags & SF_COPY_TERRAIN) && s->rt_set.size() > 1;      // (a stale rtc copy stays marked stale below)
+    // (section 20: the record travels with the arrival plane it was summed over - under ONE plane for all environments.  Planes per
+    // environment stay where they are, like the terrain without SF_COPY_TERRAIN: dst's damage is its own plane over src's arrival,
+    // recounted below)
     L.n_seg = arrival_seg(s, L.seg, env_segs(s, terrain ? kForkKinds : kForkKinds & ~kSegTerrain, L.seg));
+    if (!s->val_per_env) L.n_seg = value_seg(s, L.seg, L.n_seg);
     const unsigned gx = seg_grid_x(L.seg, L.n_seg);
     // with the terrain go the slices of section 18, where they exist: the table's part of the wind cache, the environment's schedule
     // and the segment its table stands for (a launch of their own: the slice table of env_segs is full)
@@ -3004,6 +3174,7 @@ extern "C" int sf_copy_envs(sf_sim *s, const int32_t *src, const int32_t *dst, i
     }
     if (terrain) { s->have_rt = true; for (char c : s->rt_set) if (!c) s->have_rt = false; }
     if (terrain && s->wsched) wind_sched_count(s);
+    if (s->val_per_env) { int rc = value_recount(s); if (rc) return rc; }
     // (fire_rows bounds every environment's fire, dst's copy included; status_fresh: dst's row is src's current row)
     return finish_call(s, nullptr, !s->async, nullptr);
 }
@@ -3097,7 +3268,7 @@ static int reset_launch(sf_sim *s, const int32_t *envs_dev, const uint8_t *mask,
     // it at that while every histogram of the handle is marked stale anyway
     const bool hist_known = g.ab == 1 && !s->generic && (full || !s->tdirty_all);
     if (full) { s->status_fresh = true; s->cost_steps = 0; }      // every result row is written; the old episodes' costs (run_cost, zeroed) say nothing
-    a.n_seg = arrival_seg(s, a.seg, env_segs(s, (kResetKinds & ~(seams ? 0u : kSegSeam) & ~(hist_known ? 0u : kSegHist)) | (full ? kSegCost : 0u), a.seg));
+    a.n_seg = value_seg(s, a.seg, arrival_seg(s, a.seg, env_segs(s, (kResetKinds & ~(seams ? 0u : kSegSeam) & ~(hist_known ? 0u : kSegHist)) | (full ? kSegCost : 0u), a.seg)));
     a.envs = envs_dev; a.mask = mask; a.xy = xy_dev; a.n = n;
     a.status = s->status; a.age = s->age; a.cells = s->bl_cur ? s->cells : nullptr;
     a.commit = s->commit; a.tflags = s->tflags; a.ring = s->ring; a.vbits = s->vbits; a.win_hint = s->win_hint;
@@ -3249,6 +3420,7 @@ static int agents_free(sf_sim *s)
     s->ag_xyid = s->ag_start = s->ag_points = s->ag_prev = s->ag_terms = s->ag_len = s->ag_ign = nullptr;
     s->ag_ret = nullptr; s->ag_done = nullptr;
     s->ag_has_ign = false;
+    s->val_w_on = false;                              // (the fifth weight belongs to the agent state: set again behind sf_agents_create)
     memset(&s->ag, 0, sizeof s->ag);
     return SF_OK;
 }
@@ -3497,6 +3669,11 @@ static AgentArgs agent_args(const sf_sim *s, const int32_t *actions, const sf_ag
     a.K = s->ag.k; a.only_unburned = s->ag.only_unburned != 0; a.done_on_burn = s->ag.done_on_burn != 0;
     a.max_ticks = s->ag.max_ticks; a.auto_reset = s->ag.auto_reset != 0;
     for (int i = 0; i < 4; ++i) a.w[i] = (double)s->ag.w[i];
+    if (s->val_plane) {
+        a.damage = s->val_aux; a.damage_stride = (long long)sizeof(ValueRec);
+        a.tick_base = s->val_tick(0); a.tick_loss = s->val_tick(1);
+        a.wv = (double)s->val_w; a.wv_on = s->val_w_on ? 1 : 0;
+    }
     if (out) { a.o_reward = out->reward; a.o_done = out->done; a.o_terms = out->terms; a.o_len = out->final_len; a.o_ret = out->final_ret; }
     return a;
 }
@@ -3632,6 +3809,7 @@ extern "C" int sf_load_state(sf_sim *s, int32_t n, const int32_t *envs, const vo
     for (int i = 0; i < n; ++i) if (s->snap) s->snap_valid[envs[i]] = 0;
     // fire_rows bounds every environment's fire: the saving handle's bound covers a loaded one (a blob without one makes it unknown)
     s->fire_rows = (s->fire_rows > 0 && fire_rows != INT32_MAX) ? std::max(s->fire_rows, fire_rows) : 0;
+    { int rc = value_recount(s); if (rc) return rc; }      // section 20: the restored planes say what counts
     if (device_pointer && !s->async) HIPCHK(hipStreamSynchronize(s->stream));
     return SF_OK;
 }

@@ -41,6 +41,7 @@ class FireEngine:
         self.spread_graph = self.spread_graph_on = False
         self.async_mode = False
         self.arrival_on = False             # arrival times are recorded (enable_arrival)
+        self.values_on = False              # a value plane is set (values_set)
         self.n_agents = 0                   # agents per environment (agents_create); 0: no agent state
         self.episodes_on = False            # new episodes draw their parameters on the device (episodes_set)
         self._blobs_in_flight = []          # device state blobs an enqueued save / load may still touch (async mode; released by sync)
@@ -218,6 +219,14 @@ class FireEngine:
             p.w[i] = w[i]
         self._chk(self._L.sf_agents_create(self._h, C.byref(p), _ptr(ign) if ign is not None else None))
         self.n_agents = k
+
+    def agents_set_value_weight(self, w):
+        """The fifth reward term of ``agents_step``: ``w * tick_loss[e]``, the value the fire reached during the tick (``values_set``;
+        ``sf_values_set_weight``).  ``None`` switches it off: the reward is then bit for bit what it is without a value plane.
+        Needs agents and a value plane; ``agents_create`` and ``values_set(None)`` switch it off."""
+        if w is not None and not np.isfinite(float(w)):
+            raise ValueError(f"agents_set_value_weight: weight {w!r} is not finite")
+        self._chk(self._L.sf_values_set_weight(self._h, float(0.0 if w is None else w), int(w is not None)))
 
     def agents_place(self, envs, xy, also_start=True):
         """The agents of environment ``envs[i]`` stand at ``xy[i]`` (int [n, n_agents, 2] = (column, row); ``sf_agents_place``).
@@ -967,6 +976,79 @@ class FireEngine:
         class _Plane:
             __cuda_array_interface__ = {"shape": shape, "typestr": "<i4", "data": (p.value, False), "version": 2, "strides": strides}
         return torch.as_tensor(_Plane(), device=f"cuda:{self.params.device}")
+
+    # ---------------------------------------------------------------- values at risk
+    VALUE_MAX = 1 << 24
+
+    def values_set(self, values, per_env=None):
+        """A value plane (``sf_values_set``): while it is set the device keeps ``damage[e]``, the sum of the values of every cell the
+        fire of environment ``e`` has reached in this episode (the cells with ``arrival(e) >= 0``).  ``values``: int32 ``[H, W]`` for
+        every environment or ``[n_envs, H, W]``, |value| <= 2**24 - a NumPy array, or a contiguous int32 CUDA tensor on this GPU
+        (torch's queued work on it is waited for first; the handle keeps a copy of its own).  ``per_env``: inferred from the number
+        of dimensions when None.  ``None`` switches the feature off and frees its memory.  Needs ``enable_arrival``; allowed at any
+        time (the damage is recounted under the new plane).  Shape, dtype and range errors of a NumPy plane are ``ValueError`` before
+        any device call; the range of a tensor is checked on the device (``ValueError`` too, and the handle is as it was)."""
+        if values is None:
+            self._chk(self._L.sf_values_set(self._h, None, 0, 0))
+            self.values_on = False
+            return
+        on_device = getattr(values, "is_cuda", None) is not None
+        shape = tuple(values.shape)
+        if per_env is None:
+            per_env = len(shape) == 3
+        want = (self.n_envs, self.H, self.W) if per_env else (self.H, self.W)
+        if shape != want:
+            raise ValueError(f"values_set: the plane must have shape {want}, got {shape}")
+        if on_device:
+            import torch
+            if not values.is_cuda or values.device.index != self.params.device or values.dtype != torch.int32 or not values.is_contiguous():
+                raise ValueError(f"values_set: a tensor must be a contiguous int32 CUDA tensor on device {self.params.device}")
+            torch.cuda.synchronize(values.device)
+            self._chk(self._L.sf_values_set(self._h, C.c_void_p(values.data_ptr()), int(bool(per_env)), 1))
+        else:
+            a = np.asarray(values)
+            if a.dtype.kind not in "iu":
+                raise ValueError(f"values_set: values must be integers, got {a.dtype}")
+            if a.size and (int(a.max()) > self.VALUE_MAX or int(a.min()) < -self.VALUE_MAX):
+                raise ValueError("values_set: a value is outside -2**24 .. 2**24")
+            a = np.ascontiguousarray(a, dtype=np.int32)
+            self._chk(self._L.sf_values_set(self._h, _ptr(a), int(bool(per_env)), 0))
+        self.values_on = True
+
+    def damage(self):
+        """int64 [n_envs]: the value the fire of every environment has reached in its episode (``sf_values_get``).  Complete on return."""
+        out = np.empty(self.n_envs, dtype=np.int64)
+        self._chk(self._L.sf_values_get(self._h, _ptr(out)))
+        return out
+
+    def values_torch(self):
+        """Zero-copy torch views ``(damage, tick_loss)``, int64 [n_envs] each, on this GPU (``sf_values_device``): the damage as
+        ``damage()`` returns it, and what the last ``agents_step`` tick added to it (0 for an environment that was not running before
+        the tick; after an auto-reset tick still the finished episode's last tick).  Read-only; the handle's stream is waited for
+        first.  Valid until the next ``values_set``."""
+        import torch
+        d, stride, t = C.c_void_p(), C.c_int64(), C.c_void_p()
+        self._chk(self._L.sf_values_device(self._h, C.byref(d), C.byref(stride), C.byref(t)))
+        self.sync()
+        shape, strides = (self.n_envs,), (int(stride.value),)
+
+        class _Damage:
+            __cuda_array_interface__ = {"shape": shape, "typestr": "<i8", "data": (d.value, False), "version": 2, "strides": strides}
+
+        class _Loss:
+            __cuda_array_interface__ = {"shape": shape, "typestr": "<i8", "data": (t.value, False), "version": 2, "strides": None}
+        dev = f"cuda:{self.params.device}"
+        return torch.as_tensor(_Damage(), device=dev), torch.as_tensor(_Loss(), device=dev)
+
+    def set_values_dense(self, on=True):
+        """Laboratory: the value pass always in its dense form (one thread per cell) instead of walking the vector bitmap."""
+        self._chk(self._L.sf_set_values_dense(self._h, int(bool(on))))
+
+    def value_passes(self):
+        """Laboratory: (sparse, dense) value passes made since the handle was created; recounts are dense ones."""
+        out = np.zeros(2, dtype=np.int64)
+        self._chk(self._L.sf_get_value_passes(self._h, _ptr(out)))
+        return int(out[0]), int(out[1])
 
     def set_arrival_dense(self, on=True):
         """Laboratory: the arrival pass always in its dense form (one thread per cell) instead of walking the vector bitmap."""

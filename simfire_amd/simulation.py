@@ -210,6 +210,7 @@ class FireSimulation:
         self._rendering = False
         self._recording = False
         self._record_arrival = False
+        self._values = None                 # the value plane of set_values (kept for a rebuilt handle)
         self._frames: List[np.ndarray] = []
         #: ``render`` options of the frames ``recording`` keeps (scale, mode, background, contours, terrain_rgb)
         self.recording_options: Dict[str, object] = {}
@@ -247,6 +248,9 @@ class FireSimulation:
             self._engine.enable_spread_graph(True)
         if self._record_arrival and not self._engine.arrival_on:      # (a rebuilt handle)
             self._engine.enable_arrival(True)
+        if self._values is not None and not self._engine.values_on:     # (a rebuilt handle)
+            self._engine.enable_arrival(True)
+            self._engine.values_set(self._values)
         self._engine.reset([(x, y)])
         fresh = np.full(cfg.area.screen_size, int(BurnStatus.UNBURNED))               # int64, simulation.py:561-566
         fresh[y, x] = int(BurnStatus.BURNING)
@@ -304,6 +308,9 @@ class FireSimulation:
         new._record_arrival = self._record_arrival
         if eng.arrival_on:
             neng.enable_arrival(True)
+        new._values = self._values
+        if eng.values_on and self._values is not None:
+            neng.values_set(self._values)
         if neng.params.pixel_scale != eng.params.pixel_scale:
             neng.set_threshold(eng.params.pixel_scale)
         neng.load_state([0], eng.save_state([0]))
@@ -666,6 +673,27 @@ class FireSimulation:
     def record_arrival(self, value: bool) -> None:
         self._record_arrival = bool(value)
         self._engine.enable_arrival(self._record_arrival)
+
+    def set_values(self, values) -> None:
+        """A value plane, int [H, W] with |value| <= 2**24 (``None``: off): while it is set, ``damage`` is the sum of the values of
+        every cell the fire has reached since the last ``reset()``.  Switches ``record_arrival`` on: the
+        arrival plane says which cells count."""
+        if values is None:
+            self._engine.values_set(None)
+            self._values = None
+            return
+        a = np.asarray(values)
+        if a.shape != tuple(self.config.area.screen_size):
+            raise ValueError(f"set_values: the plane must have shape {tuple(self.config.area.screen_size)}, got {a.shape}")
+        if not self._engine.arrival_on:
+            self.record_arrival = True
+        self._engine.values_set(a, per_env=False)
+        self._values = np.array(a, dtype=np.int32)
+
+    @property
+    def damage(self) -> int:
+        """The value the fire has reached since the last ``reset()`` (``set_values``)."""
+        return int(self._engine.damage()[0])
 
     @property
     def arrival_steps(self) -> np.ndarray:
@@ -1110,6 +1138,26 @@ class BatchedFireSimulation:
         time (cells that burned out before stay "never"); ends a running closed loop, and ``loop_start`` is refused while it is on.
         ``clone_envs`` and ``get_state`` / ``set_state`` carry the planes."""
         self._engine.enable_arrival(on)
+
+    # ---- values at risk (DESIGN.md section 20)
+    def set_values(self, values) -> None:
+        """A value plane: int ``[H, W]`` for every environment or ``[n_envs, H, W]``, |value| <= 2**24, NumPy or an int32 CUDA
+        tensor (``None``: off).  While it is set the device keeps ``damage``: per environment, the sum of the values of every cell
+        its fire has reached in this episode.  Enables arrival recording itself if it is off."""
+        if values is not None and not self._engine.arrival_on:
+            shape = tuple(values.shape) if hasattr(values, "shape") else np.asarray(values).shape
+            H, W = self.config.area.screen_size
+            if shape not in ((H, W), (self.n_envs, H, W)):
+                raise ValueError(f"set_values: the plane must have shape {(H, W)} or {(self.n_envs, H, W)}, got {shape}")
+            self._engine.enable_arrival(True)
+        self._engine.values_set(values)
+
+    def damage(self, envs=None) -> np.ndarray:
+        """int64 [len(envs)] (default: every environment): the value each environment's fire has reached in its episode."""
+        d = self._engine.damage()
+        if envs is None:
+            return d
+        return d[np.atleast_1d(np.asarray(envs, dtype=np.int64)).reshape(-1)]
 
     def arrival(self, envs=None) -> np.ndarray:
         """int32 [len(envs), H, W] (default: every environment): the update that ignited each cell, counted from the environment's

@@ -36,10 +36,14 @@ class BatchedFireEnv:
     section 19).  ``obs``: keyword arguments of ``BatchedFireSimulation.observe`` (``channels`` first of all); its ``agents`` are
     the device positions.
 
+    ``values``: a value plane (``BatchedFireSimulation.set_values``); ``info["value_lost"]`` is then the int64 tensor of what the
+    tick's fire reached, a view of the device buffer the next ``step`` overwrites.  ``value_weight``: the reward gets the fifth term
+    ``value_weight * value_lost``.  Both default to off: calls and outputs are what they are without them.
+
     Agents are not part of an environment's state: ``clone_envs`` / ``get_state`` / ``set_state`` do not carry them."""
 
     def __init__(self, sim, n_agents, start_xy, n_updates=1, weights=(-1, 0, 0, 0), only_unburned=True, done_on_burn=False,
-                 max_ticks=0, auto_reset=True, obs=None):
+                 max_ticks=0, auto_reset=True, obs=None, values=None, value_weight=None):
         self.sim = sim
         self.engine = sim._engine
         self.n_envs, self.n_agents = int(sim.n_envs), int(n_agents)
@@ -60,6 +64,14 @@ class BatchedFireEnv:
             raise ValueError("BatchedFireEnv: obs takes the agents from the device and always shows every environment")
         self.engine.agents_create(self.n_agents, sim.ignitions, n_updates=n_updates, weights=weights, only_unburned=only_unburned,
                                   done_on_burn=done_on_burn, max_ticks=max_ticks, auto_reset=auto_reset)
+        self.values_on = values is not None
+        if value_weight is not None and not (self.values_on or self.engine.values_on):
+            raise ValueError("BatchedFireEnv: value_weight needs values (or a value plane set on the simulation)")
+        if self.values_on:
+            sim.set_values(values)
+        self.values_on = self.values_on or value_weight is not None
+        if value_weight is not None:
+            self.engine.agents_set_value_weight(value_weight)
         self._all = np.arange(self.n_envs, dtype=np.int32)
         self.engine.agents_place(self._all, self.start_xy, also_start=True)      # (raises on a cell off the grid)
 
@@ -101,7 +113,11 @@ class BatchedFireEnv:
         final_len = torch.empty(E, dtype=torch.int32, device=dev)
         final_ret = torch.empty(E, dtype=torch.float64, device=dev)
         self.engine.agents_step(actions, reward=reward, done=done, terms=terms, final_len=final_len, final_ret=final_ret)
-        return self._observe(), reward, done, dict(terms=terms, final_len=final_len, final_ret=final_ret)
+        info = dict(terms=terms, final_len=final_len, final_ret=final_ret)
+        obs = self._observe()
+        if self.values_on:
+            info["value_lost"] = self.engine.values_torch()[1]
+        return obs, reward, done, info
 
     def set_wind(self, speed_mph, direction, envs=None):
         """``BatchedFireSimulation.set_wind``: the wind of ``envs`` from the next tick on."""
