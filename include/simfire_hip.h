@@ -255,6 +255,40 @@ int sf_values_get(sf_sim *sim, int64_t *damage_out /* [n_envs] host */);
 int sf_values_device(sf_sim *sim, void **damage, int64_t *damage_stride, void **tick_loss);
 int sf_values_set_weight(sf_sim *sim, float w_value, int32_t on);
 
+/* Ensemble statistics: per-cell statistics ACROSS environments.  The reference keeps no ensemble; the entries
+ * stand for what a harness of the reference computes after many runs from their fire_map.npy files (simulation.py:548-549): the
+ * burn-probability map, the earliest and the mean arrival, the expected loss by horizon.  A group is a list of K environments of
+ * this handle (forked, under different winds or control lines: the members of an ensemble); an environment may stand in several
+ * groups and more than once in one - it counts as often as it is listed.  With a1 the raw arrival word of a cell (update + 1,
+ * 0 = never; sf_arrival_device), a member has REACHED the cell by horizon h iff a1 != 0 && (h < 0 || a1 <= h + 1).  Horizons are
+ * update indices as sf_get_arrival numbers them, strictly ascending, the last may be -1: no limit.  Per group g and horizon t:
+ *   count [G][T][H][W] int32    members that reached the cell by horizons[t]
+ *   prob  [G][T][H][W] float32  (float)count / (float)K, correctly rounded
+ *   first [G][H][W]    int32    the smallest update index over the members that reached the cell by the LAST horizon, -1 if none
+ *   mean  [G][H][W]    float32  over the same n members: (float)((double)sum / (double)n), sum their update indices (uint64); -1 if none
+ *   loss  [G][T]       int64    the sum over the members as listed of the values (sf_values_set; the member's own plane under
+ *                               per_env) of the cells that member reached by horizons[t]
+ * All device memory, contiguous, aligned to their element; any may be NULL, not all.  The arrival plane is taken as it stands: a member
+ * that has made fewer updates than a horizon contributes what it has recorded, a frozen member is frozen, a member whose recording was
+ * enabled late carries the limits of sf_enable_arrival.  One launch reads every listed member's plane once, for all horizons and
+ * outputs; no state of the handle changes (no plane is converted, the reference point of sf_get_fire_map_delta and the result block
+ * stay).  Everything is checked before any device work: a NULL argument, no output, G < 1, K outside 1..65535, G * K > 2^20, T outside
+ * 1..SF_ENS_MAX_HORIZONS, horizons not strictly ascending or below -1 or a -1 that is not last, reserved != 0, a member outside
+ * 0..n_envs-1, a misaligned output: SF_EINVAL; before sf_enable_arrival, or loss without a value plane: SF_ESTATE.  In async mode the
+ * call only enqueues: the outputs are complete once the handle's stream has passed it (sf_sync). */
+#define SF_ENS_MAX_HORIZONS 8
+typedef struct sf_ensemble_params {
+    int32_t n_groups, group_size;               /* G, K */
+    int32_t n_horizons;                         /* T */
+    int32_t horizons[SF_ENS_MAX_HORIZONS];
+    int32_t reserved;                           /* 0 */
+} sf_ensemble_params;
+typedef struct sf_ensemble_out {                /* device memory, any may be NULL, not all */
+    int32_t *count; float *prob; int32_t *first; float *mean; int64_t *loss;
+} sf_ensemble_out;
+int sf_ensemble_stats(sf_sim *sim, const sf_ensemble_params *params,
+                      const int32_t *members /* [G][K] host */, const sf_ensemble_out *out);
+
 /* FireSimulation.reset for every environment (simulation.py:202-214, 555-566): fire_map all
  * UNBURNED except the ignition cell, burn_amounts 0, one sprite of duration 0, elapsed_time 0.
  * init_xy = int32 [n_envs][2] = (x, y). */

@@ -94,6 +94,20 @@ class SfAgentOut(C.Structure):
                 ("final_ret", C.c_void_p)]
 
 
+ENS_MAX_HORIZONS = 8
+
+
+class SfEnsembleParams(C.Structure):
+    """``sf_ensemble_params`` (include/simfire_hip.h)."""
+    _fields_ = [("n_groups", C.c_int32), ("group_size", C.c_int32), ("n_horizons", C.c_int32),
+                ("horizons", C.c_int32 * ENS_MAX_HORIZONS), ("reserved", C.c_int32)]
+
+
+class SfEnsembleOut(C.Structure):
+    """``sf_ensemble_out`` (include/simfire_hip.h): device pointers, any may be null, not all."""
+    _fields_ = [("count", C.c_void_p), ("prob", C.c_void_p), ("first", C.c_void_p), ("mean", C.c_void_p), ("loss", C.c_void_p)]
+
+
 # name -> argtypes; every function returns int except the two string getters
 _VP, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
 SIGNATURES = {
@@ -128,6 +142,7 @@ SIGNATURES = {
     "sf_values_set_weight": [_VP, C.c_float, _I32],
     "sf_set_values_dense": [_VP, _I32],
     "sf_get_value_passes": [_VP, _VP],
+    "sf_ensemble_stats": [_VP, C.POINTER(SfEnsembleParams), _VP, C.POINTER(SfEnsembleOut)],
     "sf_reset": [_VP, _VP],
     "sf_reset_env": [_VP, _I32, _I32, _I32],
     "sf_reset_envs": [_VP, _I32, _VP, _VP],

@@ -108,6 +108,7 @@ extern "C" const char *sf_version(void) { return "simfire_hip 0.2 (gfx950)"; }  
 #include "sf_agent_kernels.h"
 #include "sf_arrival_kernels.h"
 #include "sf_value_kernels.h"
+#include "sf_ensemble_kernels.h"
 #include "sf_wind_kernels.h"
 #include "sf_episode_kernels.h"
 
@@ -306,6 +307,7 @@ struct sf_sim {
     double *ag_ret = nullptr;
     uint8_t *ag_done = nullptr;
     CallBlock ag_blk;
+    CallBlock ens_blk;                 // sf_ensemble_stats: the member list of a call
     bool ag_has_ign = false;           // sf_agents_create was given ignitions
     // sf_episodes_* (DESIGN.md section 19): the parameters of sf_episodes_set (ep_on: randomisation is set) and ONE device allocation
     // for the episode buffers - the next episode's index, the ignition a new episode takes (drawn, or the fixed one), the last wind
@@ -596,7 +598,7 @@ static int destroy(sf_sim *s)
     if (s->status_pinned) (void)hipHostFree(s->status_pinned);
     if (s->delta_pinned) (void)hipHostFree(s->delta_pinned);
     for (void *dp : {(void *)s->snap, (void *)s->delta_dev, (void *)s->rd_bg, (void *)s->rd_fuel_ix, (void *)s->ag_mem, (void *)s->ep_mem}) if (dp) (void)hipFree(dp);
-    for (CallBlock *b : {&s->obs_blk, &s->rd_blk, &s->rs_blk, &s->gen_blk, &s->ag_blk, &s->wind_blk}) {
+    for (CallBlock *b : {&s->obs_blk, &s->rd_blk, &s->rs_blk, &s->gen_blk, &s->ag_blk, &s->wind_blk, &s->ens_blk}) {
         if (b->dev) (void)hipFree(b->dev);
         if (b->pinned) (void)hipHostFree(b->pinned);
         if (b->ev) (void)hipEventDestroy(b->ev);
@@ -1821,6 +1823,71 @@ extern "C" int sf_get_value_passes(sf_sim *s, int64_t *out)
     if (!s || !out) return fail(SF_EINVAL, "sf_get_value_passes: null argument");
     out[0] = s->val_passes[0]; out[1] = s->val_passes[1];
     return SF_OK;
+}
+
+// ----------------------------------------------------------------------------- ensemble statistics
+// One launch of k_ensemble (sf_ensemble_kernels.h) over the arrival plane as it stands: the call converts no plane, folds no ring and
+// looks at no result row - it reads arrival1 (complete behind every stepping call) and the value plane, and writes the caller's outputs.
+template <int TP>
+static void ensemble_launch(bool loss, dim3 grd, hipStream_t st, const EnsArgs &a)
+{
+    if (loss) hipLaunchKernelGGL((k_ensemble<TP, true>), grd, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_ensemble<TP, false>), grd, dim3(256), 0, st, a);
+}
+
+extern "C" int sf_ensemble_stats(sf_sim *s, const sf_ensemble_params *p, const int32_t *members, const sf_ensemble_out *out)
+{
+    if (!s || !p || !members || !out) return fail(SF_EINVAL, "sf_ensemble_stats: null argument");
+    if (!out->count && !out->prob && !out->first && !out->mean && !out->loss) return fail(SF_EINVAL, "sf_ensemble_stats: no output asked for");
+    const Geo &g = s->g;
+    const int G = p->n_groups, K = p->group_size, T = p->n_horizons;
+    if (G < 1 || K < 1 || K > 65535 || (long long)G * K > (1LL << 20))
+        return fail(SF_EINVAL, "sf_ensemble_stats: %d groups of %d members (G >= 1, 1 <= K <= 65535, G * K <= 2^20)", G, K);
+    if (T < 1 || T > SF_ENS_MAX_HORIZONS) return fail(SF_EINVAL, "sf_ensemble_stats: %d horizons (1..%d)", T, SF_ENS_MAX_HORIZONS);
+    if (p->reserved != 0) return fail(SF_EINVAL, "sf_ensemble_stats: reserved must be 0");
+    for (int t = 0; t < T; ++t) {
+        const int h = p->horizons[t];
+        if (h < -1 || (h == -1 && t != T - 1)) return fail(SF_EINVAL, "sf_ensemble_stats: horizon %d is %d (>= 0; -1, no limit, only last)", t, h);
+        if (t > 0 && h != -1 && h <= p->horizons[t - 1]) return fail(SF_EINVAL, "sf_ensemble_stats: the horizons are not strictly ascending (%d behind %d)", h, p->horizons[t - 1]);
+    }
+    if (((uintptr_t)out->count | (uintptr_t)out->prob | (uintptr_t)out->first | (uintptr_t)out->mean) & 3 || ((uintptr_t)out->loss & 7))
+        return fail(SF_EINVAL, "sf_ensemble_stats: an output is not aligned to its element");
+    { int rc = check_envs(s, "sf_ensemble_stats", G * K, members); if (rc) return rc; }
+    if (!s->arrival1) return fail(SF_ESTATE, "sf_ensemble_stats: call sf_enable_arrival first (the statistics are read off the arrival plane)");
+    if (out->loss && !s->val_plane) return fail(SF_ESTATE, "sf_ensemble_stats: loss needs a value plane (sf_values_set)");
+    { int rc = begin_call(s, "sf_ensemble_stats", kNotVoid); if (rc) return rc; }
+
+    const size_t bytes = (size_t)G * K * sizeof(int32_t);
+    CallBlock &blk = s->ens_blk;
+    { int rc = block_reserve(s, blk, bytes); if (rc) return rc; }
+    memcpy(blk.pinned, members, bytes);
+    { int rc = block_send(s, blk, bytes); if (rc) return rc; }
+
+    EnsArgs a;
+    memset(&a, 0, sizeof a);
+    a.arrival1 = s->arrival1; a.plane_env = g.plane_env;
+    a.H = g.H; a.W = g.W; a.P = g.P; a.Q = (g.W + 3) / 4;
+    a.members = reinterpret_cast<const int32_t *>(blk.dev);
+    a.G = G; a.K = K; a.T = T;
+    int TP = 1;
+    while (TP < T) TP *= 2;
+    for (int t = 0; t < SF_ENS_MAX_HORIZONS; ++t) {
+        const int h = p->horizons[std::min(t, T - 1)];
+        a.hz[t] = h < 0 ? 0xFFFFFFFEu : (uint32_t)h;
+    }
+    if (out->loss) { a.values = s->val_plane; a.values_env = s->val_per_env ? g.plane_env : 0; }
+    a.vec = g.W % 4 == 0 && !(((uintptr_t)out->count | (uintptr_t)out->prob | (uintptr_t)out->first | (uintptr_t)out->mean) & 15);
+    a.count = out->count; a.prob = out->prob; a.first = out->first; a.mean = out->mean;
+    a.loss = reinterpret_cast<unsigned long long *>(out->loss);
+    if (out->loss) HIPCHK(hipMemsetAsync(out->loss, 0, (size_t)G * T * sizeof(int64_t), s->stream));
+    const long long quads = (long long)g.H * a.Q;
+    const dim3 grd((unsigned)((quads + 255) / 256), (unsigned)std::min(G, kEnsGroupsY), (unsigned)((G + kEnsGroupsY - 1) / kEnsGroupsY));
+    const bool loss = out->loss != nullptr;
+    if (TP == 1) ensemble_launch<1>(loss, grd, s->stream, a);
+    else if (TP == 2) ensemble_launch<2>(loss, grd, s->stream, a);
+    else if (TP == 4) ensemble_launch<4>(loss, grd, s->stream, a);
+    else ensemble_launch<8>(loss, grd, s->stream, a);
+    return finish_call(s, "sf_ensemble_stats", !s->async, nullptr);
 }
 
 extern "C" int sf_last_step_launch(sf_sim *s, int32_t *kind)

@@ -1050,6 +1050,68 @@ class FireEngine:
         self._chk(self._L.sf_get_value_passes(self._h, _ptr(out)))
         return int(out[0]), int(out[1])
 
+    # ---------------------------------------------------------------- ensemble statistics
+    ENS_MAX_HORIZONS = _lib.ENS_MAX_HORIZONS
+
+    def _ensemble_request(self, members, horizons):
+        """The checked arguments of ``ensemble_stats``: (int32 [G, K] contiguous, list of horizons).  ``ValueError`` on anything the
+        library would refuse, before it is called."""
+        if members is None:
+            m = np.arange(self.n_envs, dtype=np.int32).reshape(1, -1)
+        else:
+            m = np.asarray(members)
+            if m.ndim != 2 or m.dtype.kind not in "iu":
+                raise ValueError(f"ensemble_stats: members must be a 2-D integer array [groups, members], got {m.dtype} {m.shape}")
+        G, K = m.shape
+        if G < 1 or not 1 <= K <= 65535 or G * K > 1 << 20:
+            raise ValueError(f"ensemble_stats: {G} groups of {K} members (G >= 1, 1 <= K <= 65535, G * K <= 2**20)")
+        if int(m.min()) < 0 or int(m.max()) >= self.n_envs:
+            raise ValueError(f"ensemble_stats: members holds an environment outside 0..{self.n_envs - 1}")
+        try:
+            hz = [int(h) for h in np.asarray(horizons).reshape(-1).tolist()]
+        except (TypeError, ValueError):
+            raise ValueError(f"ensemble_stats: horizons must be integers, got {horizons!r}") from None
+        if np.asarray(horizons).dtype.kind not in "iu" or not 1 <= len(hz) <= self.ENS_MAX_HORIZONS:
+            raise ValueError(f"ensemble_stats: 1 to {self.ENS_MAX_HORIZONS} integer horizons, got {horizons!r}")
+        for t, h in enumerate(hz):
+            if h < -1 or h > 2 ** 31 - 1 or (h == -1 and t != len(hz) - 1):
+                raise ValueError(f"ensemble_stats: horizon {h} (>= 0; -1, no limit, only as the last)")
+            if t and h != -1 and h <= hz[t - 1]:
+                raise ValueError(f"ensemble_stats: the horizons must be strictly ascending, got {hz}")
+        return np.ascontiguousarray(m, dtype=np.int32), hz
+
+    def ensemble_stats(self, members, horizons=(-1,), count=False, prob=True, first=False, mean=False, loss=False):
+        """Per-cell statistics over groups of environments (``sf_ensemble_stats``), read off the arrival planes
+        as they stand by one launch.  ``members``: [G, K] environment numbers (anything ``np.asarray`` makes a 2-D integer array of;
+        an environment may stand in several groups and more than once in one, and counts as often as listed); ``None``: one group
+        of every environment.  ``horizons``: 1 to 8 update indices, strictly ascending, the last may be -1 (no limit); a member has
+        reached a cell by horizon h if its arrival there is an update <= h.  Returns a dict of torch tensors on this GPU with the
+        outputs asked for: ``count`` int32 [G, T, H, W], ``prob`` float32 [G, T, H, W] = count / K, ``first`` int32 [G, H, W] (the
+        earliest arrival by the last horizon, -1 none), ``mean`` float32 [G, H, W] (the mean arrival of the members that arrived,
+        -1.0 none) and ``loss`` int64 [G, T] (the values of the cells each member reached, summed over the group; needs
+        ``values_set``).  Needs ``enable_arrival``.  No state of the handle changes.  Torch's queued work is waited for first; in
+        async mode the call only enqueues: the tensors are complete after ``sync()`` and kept alive until then."""
+        m, hz = self._ensemble_request(members, horizons)
+        want = [n for n, on in (("count", count), ("prob", prob), ("first", first), ("mean", mean), ("loss", loss)) if on]
+        if not want:
+            raise ValueError("ensemble_stats: no output asked for")
+        call = self._L.sf_ensemble_stats
+        import torch
+        dev = torch.device(f"cuda:{self.params.device}")
+        G, K, T = m.shape[0], m.shape[1], len(hz)
+        shapes = {"count": ((G, T, self.H, self.W), torch.int32), "prob": ((G, T, self.H, self.W), torch.float32),
+                  "first": ((G, self.H, self.W), torch.int32), "mean": ((G, self.H, self.W), torch.float32), "loss": ((G, T), torch.int64)}
+        res = {n: torch.empty(shapes[n][0], dtype=shapes[n][1], device=dev) for n in want}
+        p = _lib.SfEnsembleParams(n_groups=G, group_size=K, n_horizons=T)
+        for t, h in enumerate(hz):
+            p.horizons[t] = h
+        o = _lib.SfEnsembleOut(**{n: res[n].data_ptr() for n in want})
+        torch.cuda.current_stream(dev).synchronize()       # (torch may still be using the memory it has just handed out again)
+        self._chk(call(self._h, C.byref(p), _ptr(m), C.byref(o)))
+        if self.async_mode:
+            self._blobs_in_flight.extend(res.values())
+        return res
+
     def set_arrival_dense(self, on=True):
         """Laboratory: the arrival pass always in its dense form (one thread per cell) instead of walking the vector bitmap."""
         self._chk(self._L.sf_set_arrival_dense(self._h, int(bool(on))))

@@ -1169,6 +1169,31 @@ class BatchedFireSimulation:
             out[i] = self._engine.arrival(int(env))
         return out
 
+    # ---- ensemble statistics
+    def ensemble_stats(self, members=None, horizons=(-1,), count: bool = False, prob: bool = True, first: bool = False,
+                       mean: bool = False, loss: bool = False):
+        """Per-cell statistics over groups of environments, one launch over the arrival planes as they stand: a dict of torch
+        tensors on this GPU, complete on return.  ``members`` [G, K] environment numbers (``None``: one group of every
+        environment; an environment counts as often as it is listed), ``horizons`` up to 8 ascending update indices, -1 last for
+        "no limit".  ``count`` / ``prob`` [G, T, H, W]: the members whose fire has reached the cell by each horizon, and that over K;
+        ``first`` / ``mean`` [G, H, W]: the earliest and the mean arrival (update indices; -1 where no member arrived); ``loss``
+        [G, T] int64: the value reached, summed over the group (needs ``set_values``).  Needs ``enable_arrival``."""
+        out = self._engine.ensemble_stats(members, horizons=horizons, count=count, prob=prob, first=first, mean=mean, loss=loss)
+        self._engine.sync()
+        return out
+
+    def burn_probability(self, members=None, horizons=None, device: bool = False):
+        """The burn-probability map: float32 [G, T, H, W] - per group of ``members`` ([G, K]; ``None``: every environment, one
+        group) the fraction of its members whose fire has reached each cell by each of ``horizons`` (update indices) - or
+        [G, H, W] with ``horizons=None``: as of now.  The usual recipe: ``clone_envs`` one state into the members, vary
+        ``set_wind`` or the control lines per member, ``run`` with ``enable_arrival`` on, then this.  ``device=True`` returns a
+        torch tensor on this GPU, else a NumPy array; complete on return either way (one wait)."""
+        p = self._engine.ensemble_stats(members, horizons=(-1,) if horizons is None else horizons, prob=True)["prob"]
+        self._engine.sync()
+        if horizons is None:
+            p = p[:, 0]
+        return p if device else p.cpu().numpy()
+
     def run(self, time: Union[str, int], return_maps: bool = True):
         """Steps every environment that is still RUNNING; returns (fire_maps uint8 [E, H, W] or None,
         active bool [E])."""
