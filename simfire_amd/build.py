@@ -5,7 +5,8 @@ import sys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
-# five translation units, compiled side by side (the first: host code + every kernel every handle launches; the next three: tables of
+# five translation units, compiled side by side (the first: host code - with sf_handle.h and the sf_host_*.h fragments it includes - +
+# every kernel every handle launches; the next three: tables of
 # the k_run instantiations only some handles launch, which the first launches by handle - teams / the closed loop, several bitmap words
 # per thread, two-word teams; the last: the CFD wind solver, sf_cfd_*)
 SOURCES = ["simfire_hip.hip", "simfire_hip_run2.hip", "simfire_hip_run3.hip", "simfire_hip_run4.hip", "simfire_hip_cfd.hip"]

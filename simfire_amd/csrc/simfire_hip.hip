@@ -66,35 +66,6 @@
 #include "../../include/simfire_hip.h"
 #include "rothermel_dev.h"
 
-// ------------------------------------------------------------------------------- errors
-static thread_local std::string g_err;
-static int fail(int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-#define HIPCHK(expr)                                                                      \
-    do {                                                                                  \
-        hipError_t _e = (expr);                                                           \
-        if (_e != hipSuccess)                                                             \
-            return fail(SF_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e),   \
-                        __FILE__, __LINE__);                                              \
-    } while (0)
-
-extern "C" const char *sf_last_error(void) { return g_err.c_str(); }
-// the other translation units report through the same per-thread message (simfire_hip_cfd.hip)
-int sf_fail_message(int code, const char *msg)
-{
-    g_err = msg;
-    return code;
-}
-extern "C" const char *sf_version(void) { return "simfire_hip 0.2 (gfx950)"; }      // 0.2: the knob numbers and the 16 counter slots of simfire_hip_lab.h as they stand since round 5; sf_get_fire_map_delta
-
 #include "sf_common.h"
 #include "sf_step_kernels.h"
 #include "sf_aux_kernels.h"
@@ -112,349 +83,20 @@ extern "C" const char *sf_version(void) { return "simfire_hip 0.2 (gfx950)"; }  
 #include "sf_wind_kernels.h"
 #include "sf_episode_kernels.h"
 
-// Launch-geometry knobs of a handle (sf_set_tuning, include/simfire_hip_lab.h: SF_TUNE_*).  Results never depend on them; the
-// defaults are the measured choices of NOTEBOOK.md 5.  The library does not read the environment for them (the measurement scripts under
-// profiles/ set them through the Python binding, simfire_amd/engine.py: SF_DEBUG_KNOBS).
-struct Tuning {
-    int v[SF_TUNE_COUNT];
-    bool set[SF_TUNE_COUNT];
-};
-static const int kTuneDefault[SF_TUNE_COUNT] = {
-    /* SF_TUNE_WAVES_PER_CU */ 24, /* RUN_WAVES */ 16, /* RUN_MIN_ENVS */ 1, /* RUN_VCAP */ 4096, /* RUN_COMPACT */ 1,
-    /* RUN_BATCH */ 64, /* RUN_RESULT */ 1, /* RUN_SEGMENT */ 64, /* RUN_TEAM */ 0, /* TEAM_PLACEMENT */ 0, /* TEAM_RECUT */ 1, /* RUN_WINDOW */ 1, /* TEAM_TIMEOUT_MS */ 2000,
-    /* RUN_JOIN */ 1, /* LOOP_LIGHT */ 0};
+// The host code: the handle and the prologue / epilogue of a call (sf_handle.h), then one fragment per feature (sf_host_*.h, included
+// below where their functions stood while this was one file: kernel templates are instantiated in the order the host code names
+// them).  This file keeps create / destroy, the setters, the resident launches, the launch plan and the step path, the closed loop,
+// status, maps and delta.
+#include "sf_handle.h"
 
-// What a batched call sends ahead of its kernels (environment list, descriptors, host points): a device buffer, the pinned mirror it
-// is copied from, and the event that marks the copy's completion - the next call of the feature waits for it before it writes the
-// mirror again, so a call in async mode never waits for the one before it unless the mirror is still being read (block_reserve /
-// block_send).  One block per feature: a shared one would make one feature's calls wait for another's.
-struct CallBlock {
-    uint8_t *dev = nullptr, *pinned = nullptr;
-    size_t cap = 0;
-    hipEvent_t ev = nullptr;
-};
-
-// ----------------------------------------------------------------------------- handle
-struct sf_sim {
-    sf_params p;
-    Geo g;
-    hipStream_t stream = nullptr;
-    int loop_light = 0;                 // 1: the running closed loop is the light one (8-wave workgroups; SF_TUNE_LOOP_LIGHT)
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    uint8_t *status = nullptr, *age_alloc = nullptr, *age = nullptr;
-    uint8_t *cells_alloc = nullptr, *cells = nullptr;      // blocked cell plane of the resident launch (allocated at its first use)
-    bool bl_cur = false;               // the blocked plane holds the sprite masks / status bytes; the row-major planes are stale
-    double *burn = nullptr, *rt = nullptr;
-    mutable std::map<std::tuple<const void *, unsigned, size_t>, int> occ_cache;      // k_run instantiations: workgroups per CU by hipOccupancyMaxActiveBlocksPerMultiprocessor (occupancy)
-    double *rtc = nullptr;             // the R table(s) cell-major (k_rt_cellmajor): built when the resident launch first needs it, stale after every change of rt
-    bool rtc_valid = false;
-    std::vector<char> rtc_stale;       // per table: its cell-major copy does not match rt (all of them until the copy exists)
-    unsigned long long *win_hint = nullptr;      // k_run's window phase: where the fire stood and where the window was when the phase last ended, per environment; 0 = unknown.  ADVICE only (sf_win_kernels.h)
-    double *lay_all = nullptr;         // [tables][7][H*W] dense: w0 delta Mx sigma elev U Udir (kept for the observation planes)
-    double *layer(int table, int i) const { return lay_all + ((size_t)table * 7 + i) * (size_t)g.H * g.W; }
-    int8_t *history = nullptr;         // sf_enable_history: [E][history_cap][H][W] fire maps after each update
-    int history_cap = 0;
-    double *smag = nullptr, *sdir = nullptr;
-    double slope_scale = 0.0;          // pixel_scale of the constructor: np.gradient spacing (fire.py:446), whatever the threshold becomes
-    EnvState *commit = nullptr, *tmp = nullptr;
-    uint32_t *flags = nullptr;
-    unsigned long long *counters = nullptr;
-    uint8_t *tflags = nullptr;
-    size_t tflags_bytes = 0;
-    int ring = 0;                      // tile activity map the next step reads (0/1)
-    uint32_t *tile_list = nullptr, *n_active = nullptr;
-    int n_cu = 256;
-    int fused_mode = -1;               // -1 auto, 0 k_select + k_step, 1 one fused launch per step, 2 one resident launch per sf_step call
-    bool generic = false;              // sf_set_generic: per-cell kernel instead of the tiled SWAR kernels
-    uint8_t *seam = nullptr;           // seam planes (tiled kernels, 1-byte sprite plane)
-    uint32_t *settled = nullptr;       // attenuation bookkeeping per cell (attenuate_line_ros only)
-    uint8_t *tdirty = nullptr;         // per wave tile: status histogram stale
-    uint16_t *thist = nullptr;         // per wave tile: cells per BurnStatus 1..5 (u16 [tiles][8])
-    size_t n_tiles_max = 0;
-    void *status_pinned = nullptr;     // pinned landing zone of the result block (int32 [E][8] + double [E])
-    bool status_fresh = false;         // status_block / elapsed_dev (and the sink) hold the current result block: the resident launch wrote it
-    int32_t *sink = nullptr;           // sf_set_result_sink: caller-owned device copy of the result block, written by every refresh
-    bool tdirty_all = true;            // every histogram is stale (reset, fire_map replaced, geometry changed, per-cell kernel ran)
-    int last_launches = 0;             // k_run launches of the last step call (sf_get_last_launches)
-    // run(1) loops (one update per call, the result block looked at after each - FireSimulation.run(1) in a harness): after two such
-    // pairs in a row the single update runs as the resident launch too, which leaves the block behind itself (measured, step(1) +
-    // status() per call: 41 against 46 us on one environment, 47 against 58 on C3's 256; a loop that only enqueues step(1) calls, or
-    // looks at the maps after each, is faster on the per-step kernels and keeps them)
-    bool last_was_step1 = false;       // the last step call was one update and nothing has looked at its result yet
-    int step1_polls = 0;               // step(1) + status pairs in a row
-    int fire_rows = 0;                 // no environment's fire spans more rows than this (0: not known): 1 after sf_reset, + 2 per update (a fire
-                                       // advances one row per update at most, fire.py:163-234), the grid's height after sf_load_fire_map
-    unsigned long long *vbits = nullptr;   // vector bitmap of the resident launch (k_run)
-    bool vbits_valid = false;          // vbits matches the sprite-mask planes (k_run / reset keep it; the per-step kernels do not)
-    bool vbits_fl_valid = true;        // ... planes 1 / 2 of it too (first / last cell of the vector holds a sprite bit): k_run on rows of several words keeps only
-                                       // plane 0 (plain dilation) unless it runs as teams - which need all three (rebuilt when a team launch follows such a launch)
-    bool tiles_valid = false;          // tile activity map + seam planes match them (the per-step tiled kernels keep them; k_run does not)
-    int last_kind = -1;                // launch structure of the last sf_step call: 0 k_select + k_step, 1 fused, 2 k_run, 3 per-cell
-    int32_t *todo = nullptr;           // team launches with windows of rows: the steps an environment's team could not make (the catch-up launch's) [E]
-    ncclComm_t comm = nullptr;         // sf_comm_init: communicator of the result-block all-gather
-    int comm_world = 0;
-    // k_run<TEAM>: an environment served by several workgroups (sf_run_kernels.h); allocated at the first team launch
-    uint32_t *team_tab = nullptr, *team_size = nullptr, *xdone = nullptr;
-    uint32_t *xj = nullptr;            // k_run<TEAM = 2> (teams that grow inside the launch): names put down / the board / counters (StepArgs::xj)
-    unsigned long long *xcut = nullptr;
-    uint32_t *jlog = nullptr;          // what happened to the teams in the last such launch (sf_get_join_log)
-    bool jlog_valid = false;
-    unsigned long long *xg = nullptr;
-    uint8_t *xbuf = nullptr;
-    uint32_t *xerr_pinned = nullptr, *xerr_mapped = nullptr;
-    int team_slots = 0;                // entries of team_tab
-    long long team_plan_ones = 0;      // != 0: team_tab / team_size hold the plan "every environment one workgroup" for this (E, slots, placement) - k_team_plan need not run again for it
-    // LOOP mode (sf_loop_start): the resident launch driven step by step through host-mapped memory
-    bool loop_on = false;
-    int loop_k = 0;                    // points per environment and step
-    uint32_t loop_seq = 0;             // sequence number of the last step posted
-    uint32_t *loop_db = nullptr, *loop_db_dev = nullptr;         // (pinned, device-mapped) [0] doorbell, [64 ...] "done" numbers [E] (other cache lines)
-    int32_t *loop_res = nullptr, *loop_res_dev = nullptr;        // u32 [E][16]: one 64-byte line per environment (pinned, device-mapped; k_run, loop_finish)
-    int32_t *loop_pts = nullptr, *loop_pts_dev = nullptr;        // [2][slot] points ring (pinned, device-mapped)
-    size_t loop_pts_cap = 0, loop_slot_ints = 0;
-    uint32_t *loop_mem = nullptr;                                // device: [0] forwarded sequence number, [32 ...] done [E]
-    int32_t *loop_pts_mem = nullptr;                             // device copy of the ring
-    size_t loop_pts_mem_cap = 0;
-    int loop_restarts = 0;             // times the launch had left by itself (timeout) and was started again
-    int last_team_max = 0;             // upper bound of the team sizes in the last resident launch (0: it was not a team launch)
-    int cost_steps = 0;                // steps the per-environment cost array covers (0: nothing recorded since the last reset)
-    uint32_t *todo_cnt = nullptr;      // k_win: how many environments it left updates for (their numbers: run_order); two counts, by the parity of win_seq
-    unsigned win_seq = 0;              // k_win launches so far
-    uint32_t *run_cost = nullptr, *run_order = nullptr;   // k_run: clocks / 16 an environment's workgroup took in the last resident launch [E]; launch order built from it (k_order)
-    mutable std::map<const void *, size_t> lds_allowed;       // dynamic LDS the resident kernels have been enabled for, by host handle (allow_lds)
-    uint8_t *parents = nullptr;        // spread-graph parent masks, allocated by sf_enable_spread_graph
-    bool graph_on = false;
-    // sf_enable_arrival: the plane u32 [E][H][P] (update that created a cell's first sprite + 1, 0 = never; null =
-    // recording off), updates made since the last pass (< md between the pieces of a call, 0 between calls), the lab's "always the
-    // dense pass" and its count of passes made in the sparse / the dense form
-    uint32_t *arrival1 = nullptr;
-    int arr_pending = 0;
-    bool arr_dense = false;
-    int64_t arr_passes[2] = {0, 0};
-    // sf_values_set: the handle's copy of the value plane, int32 [n][H][P] with n = E (val_per_env) or 1 and zeros
-    // in the pitch padding (null = the feature is off); ONE allocation for the records ValueRec [E], tick_base and tick_loss int64 [E]
-    // and the word the range check of a device plane leaves; the lab's "always the dense pass" and its count of passes made in the
-    // sparse / the dense form; the fifth reward weight of sf_agents_step
-    int32_t *val_plane = nullptr;
-    bool val_per_env = false;
-    uint8_t *val_aux = nullptr;
-    bool val_dense = false;
-    int64_t val_passes[2] = {0, 0};
-    float val_w = 0.0f;
-    bool val_w_on = false;
-    size_t val_plane_bytes() const { return (size_t)(val_per_env ? g.E : 1) * g.plane_env * sizeof(int32_t); }
-    size_t val_aux_bytes() const { return (size_t)g.E * (sizeof(ValueRec) + 16) + 16; }
-    ValueRec *val_rec() const { return reinterpret_cast<ValueRec *>(val_aux); }
-    long long *val_tick(int i) const { return reinterpret_cast<long long *>(val_aux + (size_t)g.E * (sizeof(ValueRec) + 8 * i)); }      // 0: base, 1: loss
-    uint32_t *val_bad() const { return reinterpret_cast<uint32_t *>(val_aux + (size_t)g.E * (sizeof(ValueRec) + 16)); }
-    // sf_get_fire_map_delta: the fire maps as the host last saw them (u8 [E][H][P], allocated at the first call), per environment whether that
-    // reference point exists, the list of changed cells on the device ([0] = count) and its pinned landing zone
-    uint8_t *snap = nullptr;
-    std::vector<char> snap_valid;
-    uint32_t *delta_dev = nullptr, *delta_pinned = nullptr;
-    int delta_cap = 0;
-    uint32_t delta_base = 0;           // what the list's count stood at after the last query (it counts on: nothing zeroes it)
-    int32_t *status_block = nullptr;   // [E][8]
-    double *elapsed_dev = nullptr;     // [E]
-    void *stage = nullptr;             // dense staging for host copies
-    size_t stage_bytes = 0;
-    // control-line points: a ring of pinned, device-mapped staging buffers which the scatter kernels read
-    // directly, so that in async mode the host can run several scatter + step pairs ahead of the GPU
-    static constexpr int kPtsRing = 16;
-    int32_t *pts_pinned[kPtsRing] = {}, *pts_mapped[kPtsRing] = {};
-    size_t pts_cap = 0;
-    hipEvent_t ev_pts[kPtsRing] = {};
-    int pts_slot = 0;
-    int32_t *mit_stage = nullptr;      // sf_step_mitigated: device copy of a host point block / expanded rows of one step
-    size_t mit_stage_bytes = 0;
-    bool async = false;                // sf_set_async: calls that return no data do not synchronise
-    CallBlock obs_blk;                 // sf_observe: ObsHead, environment list, host centers / agents
-    // sf_render: per table, layers present / FBFM-coded fuel / background stale; the background words [tables][H * W], the FBFM
-    // colour index plane [tables][H * W] (allocated by the first sf_set_layers_fbfm), the terrain_rgb the fuel colours were made from
-    // (-1: none yet) and the per-call block (lists of environments and tables, the min / max words its kernels write, host agents)
-    std::vector<char> rd_lay, rd_fbfm, rd_stale;
-    uint32_t *rd_bg = nullptr;
-    uint8_t *rd_fuel_ix = nullptr;
-    int64_t rd_rgb = -1;
-    CallBlock rd_blk;
-    CallBlock rs_blk;                  // sf_reset_envs / sf_reset_where: the environment list and host ignitions of a call
-    bool rs_timed = false, rs_have_ms = false;   // sf_time_resets: ev0 / ev1 recorded around the launches of every batched reset
-    CallBlock gen_blk;                 // sf_generate_layers: its descriptors + environment list
-    // wind changes: the cache plane of wind-independent terms, float [tables][kWindPlanes][H * W], allocated at the
-    // first wind change, and per table whether its part is stale (next to rtc_stale; wt_off: the lab has switched the cache off); the
-    // schedules on the device [E] with their host mirror (segments per environment, the scheduled environments, whether the cache has been
-    // made current for them since the last change of either), the due list of a schedule pass and its winds; the call block (list, scalars,
-    // schedule rows); the lab's events around the launches
-    float *wterms = nullptr;
-    std::vector<char> wt_stale;
-    bool wt_off = false;
-    WindSched *wsched = nullptr;
-    std::vector<int32_t> wind_K, wind_sched;
-    bool wind_sched_ready = false, wind_sched_cached = false;
-    int32_t *wdue = nullptr;
-    uint32_t *wdue_cnt = nullptr;
-    double *wdue_U = nullptr, *wdue_D = nullptr;
-    CallBlock wind_blk;
-    bool wind_timed = false, wind_have_ms = false;
-    // sf_agents_* (DESIGN.md section 16): the parameters of sf_agents_create (ag.k == 0: no agent state), ONE device allocation that
-    // holds every agent buffer - positions, start cells, this tick's points, the counts and episode statistics between the two
-    // kernels of a tick, the done mask, the ignitions of a new episode - and the call block of sf_agents_place.  Not slices of
-    // env_segs: fork, snapshot and restore do not carry agents.
-    sf_agent_params ag = {};
-    uint8_t *ag_mem = nullptr;
-    size_t ag_bytes = 0;
-    int32_t *ag_xyid = nullptr, *ag_start = nullptr, *ag_points = nullptr, *ag_prev = nullptr, *ag_terms = nullptr, *ag_len = nullptr, *ag_ign = nullptr;
-    double *ag_ret = nullptr;
-    uint8_t *ag_done = nullptr;
-    CallBlock ag_blk;
-    CallBlock ens_blk;                 // sf_ensemble_stats: the member list of a call
-    bool ag_has_ign = false;           // sf_agents_create was given ignitions
-    // sf_episodes_* (DESIGN.md section 19): the parameters of sf_episodes_set (ep_on: randomisation is set) and ONE device allocation
-    // for the episode buffers - the next episode's index, the ignition a new episode takes (drawn, or the fixed one), the last wind
-    // drawn, the due list k_episode_draw leaves for k_wind_rtable (the list, its count, the winds) and a mask of ones (all = 1).
-    // The handle's like the agent buffers: not slices of env_segs.  last_ign: the ignitions of the last sf_reset (host copy).
-    // ep_nocache: the cache of wind-independent terms could not be had (no memory, or the lab has it off): not asked for again
-    // until sf_episodes_set / sf_set_wind_lab.
-    sf_episode_params ep = {};
-    bool ep_on = false, ep_nocache = false;
-    uint8_t *ep_mem = nullptr, *ep_ones = nullptr;
-    size_t ep_bytes = 0;
-    uint32_t *ep_index = nullptr, *ep_due_cnt = nullptr;
-    int32_t *ep_ign = nullptr, *ep_due = nullptr;
-    double *ep_wind = nullptr, *ep_due_U = nullptr, *ep_due_D = nullptr;
-    std::vector<int32_t> last_ign;
-    bool have_rt = false, was_reset = false, counters_on = false;
-    int seq = 0;                       // index (mod 6) of the next step launch
-    Tuning tune;                       // sf_set_tuning
-    bool committed = true;             // commit[] is current (no step launch since the last k_commit / reset)
-    std::vector<char> rt_set;          // per table: layers / R table supplied?
-    int64_t bytes = 0;
-};
-
-// The host code of the step path has two layers.  The ENQUEUE layer (enqueue_steps, enqueue_call, enqueue_pair, stage_lines, step_impl,
-// refresh_status, scatter_points, delta_enqueue, reset_launch, arrival_pass) puts work on the handle's stream and keeps the handle's
-// bookkeeping: such a function never waits for the work of the call (growing a buffer that enqueued kernels may read is the one wait:
-// stage_lines, delta_enqueue) and never reads or writes `async` - what it needs to know it takes as an argument.  The CALL layer is the extern "C" entries: argument checks, one prologue (begin_call), enqueue-layer calls, one
-// epilogue (finish_call: the wait of a synchronous call, timing, the team-error check).  A composite entry (sf_rollout, sf_run_delta,
-// sf_agents_step, sf_step_mitigated) is made of enqueue-layer calls, never of other entries.
-static int ensure_commit(sf_sim *s);
-static int loop_stop(sf_sim *s);
-static int comm_close(sf_sim *s);
-static int destroy(sf_sim *s);
-// every entry point except sf_loop_step ends the closed loop (sf_loop_start) first: the handle's stream is busy with the resident launch
-#define LOOP_QUIESCE(s) do { if ((s)->loop_on) { int _rq = loop_stop(s); if (_rq) return _rq; } } while (0)
-static int ensure_rm(sf_sim *s);
-static int alloc_bl(sf_sim *s);
-static bool prefers_bl(const sf_sim *s);
-static int arrival_pass(sf_sim *s);
-static int arrival_seg(const sf_sim *s, EnvSeg *seg, int n);
-static int value_seg(const sf_sim *s, EnvSeg *seg, int n);
-static int value_pass(sf_sim *s);
-static int value_recount(sf_sim *s);
-static int wind_forget(sf_sim *s, const int32_t *envs, int n);
-
-// Behind every wait for the handle's stream: has a workgroup of a team launch (k_run<TEAM>) given up waiting for a team member?
-// Then what the launch left behind is void - say so wherever data is handed back, not only in sf_sync / a synchronous sf_step.
-// (A reset of every environment rewrites all the state a team launch touches and clears the word: the handle recovers.)
-static int check_team_error(const sf_sim *s, const char *where)
+extern "C" const char *sf_last_error(void) { return g_err.c_str(); }
+// the other translation units report through the same per-thread message (simfire_hip_cfd.hip)
+int sf_fail_message(int code, const char *msg)
 {
-    if (s->xerr_pinned && *s->xerr_pinned)
-        return fail(SF_EHIP, "%s: a workgroup of a team launch (k_run<TEAM>) gave up waiting for a team member; the state of this handle is void until every environment is reset", where);
-    return SF_OK;
+    g_err = msg;
+    return code;
 }
-
-// The prologue of a call (call layer): what the handle must have been given (SF_ESTATE before anything else happens), the device, the
-// end of a closed loop, then - where asked for - the refusal of a handle a failed team launch has voided and the step rings folded
-// into commit[] (after which tmp / flags carry nothing: the next launch starts from commit).
-enum { kNeedRt = 1, kNeedReset = 2, kNotVoid = 4, kCommit = 8, kStateCall = kNeedReset | kNotVoid | kCommit };
-static int check_ready(const sf_sim *s, const char *who, int need)
-{
-    if ((need & kNeedRt) && !s->have_rt) return fail(SF_ESTATE, "%s: call sf_set_layers or sf_set_rtable first", who);
-    if ((need & kNeedReset) && !s->was_reset) return fail(SF_ESTATE, "%s: call sf_reset first", who);
-    return SF_OK;
-}
-static int begin_call(sf_sim *s, const char *who, int need)
-{
-    { int rc = check_ready(s, who, need); if (rc) return rc; }
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    if (need & kNotVoid) { int rc = check_team_error(s, who); if (rc) return rc; }
-    return (need & kCommit) ? ensure_commit(s) : SF_OK;
-}
-// The epilogue of a call: with `ms`, the GPU time between ev0 (recorded by the enqueue layer in front of the step launches) and here;
-// the wait where the call waits (a timed call always does), and behind it the look at the team launches' error word - under the name
-// `who`; without one (entries outside the step path that wait and have never looked) the wait alone.
-static int finish_call(sf_sim *s, const char *who, bool wait, float *ms)
-{
-    if (ms) HIPCHK(hipEventRecord(s->ev1, s->stream));
-    HIPCHK(hipGetLastError());
-    if (!wait && !ms) return SF_OK;
-    HIPCHK(hipStreamSynchronize(s->stream));
-    if (ms) HIPCHK(hipEventElapsedTime(ms, s->ev0, s->ev1));
-    return who ? check_team_error(s, who) : SF_OK;
-}
-// A look at the result of a single update (a status query, a delta query): what makes step(1) + look pairs a run(1) loop.
-static void note_result_look(sf_sim *s)
-{
-    if (s->last_was_step1) { s->last_was_step1 = false; if (s->step1_polls < 1000) s->step1_polls++; }
-}
-
-// The environment list of a batched call: every entry names an environment of the handle and, where `twice` is given (the words of
-// the refusal), none is named twice.  (n < 0 and null lists are the caller's to refuse: it knows what else must not be null.)
-static int check_envs(const sf_sim *s, const char *who, int32_t n, const int32_t *envs, const char *twice = nullptr)
-{
-    std::vector<char> seen(twice ? (size_t)s->g.E : 0, 0);
-    for (int i = 0; i < n; ++i) {
-        const int e = envs[i];
-        if (e < 0 || e >= s->g.E) return fail(SF_EINVAL, "%s: environment %d out of range", who, e);
-        if (twice && seen[e]) return fail(SF_EINVAL, "%s: environment %d %s", who, e, twice);
-        if (twice) seen[e] = 1;
-    }
-    return SF_OK;
-}
-
-static int ensure_stage(sf_sim *s, size_t bytes)
-{
-    if (bytes <= s->stage_bytes) return SF_OK;
-    if (s->stage) HIPCHK(hipFree(s->stage));
-    s->stage = nullptr; s->stage_bytes = 0;
-    HIPCHK(hipMalloc(&s->stage, bytes));
-    s->stage_bytes = bytes;
-    return SF_OK;
-}
-
-template <typename T>
-static int dev_alloc(sf_sim *s, T **p, size_t n)
-{
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(p), n * sizeof(T)));
-    s->bytes += (int64_t)(n * sizeof(T));
-    return SF_OK;
-}
-
-// Room for `bytes` in a call block, its mirror free to be written: the last call's copy has left it.  Growing (to twice the request,
-// 4 KB at least) waits for the stream first: enqueued kernels may still read the device buffer.
-static int block_reserve(sf_sim *s, CallBlock &b, size_t bytes)
-{
-    if (!b.ev) HIPCHK(hipEventCreateWithFlags(&b.ev, hipEventDisableTiming));
-    HIPCHK(hipEventSynchronize(b.ev));
-    if (bytes <= b.cap) return SF_OK;
-    HIPCHK(hipStreamSynchronize(s->stream));
-    if (b.dev) { HIPCHK(hipFree(b.dev)); b.dev = nullptr; }
-    if (b.pinned) { HIPCHK(hipHostFree(b.pinned)); b.pinned = nullptr; }
-    b.cap = 0;
-    const size_t cap = std::max<size_t>(bytes * 2, 4096);
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&b.dev), cap));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&b.pinned), cap, hipHostMallocDefault));
-    b.cap = cap;
-    return SF_OK;
-}
-// The mirror's bytes [0, head) and, if any, [off, off + more) -> the device buffer on the handle's stream, then the event.
-static int block_send(sf_sim *s, CallBlock &b, size_t head, size_t off = 0, size_t more = 0)
-{
-    HIPCHK(hipMemcpyAsync(b.dev, b.pinned, head, hipMemcpyHostToDevice, s->stream));
-    if (more) HIPCHK(hipMemcpyAsync(b.dev + off, b.pinned + off, more, hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipEventRecord(b.ev, s->stream));
-    return SF_OK;
-}
+extern "C" const char *sf_version(void) { return "simfire_hip 0.2 (gfx950)"; }      // 0.2: the knob numbers and the 16 counter slots of simfire_hip_lab.h as they stand since round 5; sf_get_fire_map_delta
 
 static void choose_rows_per_band(Geo &g, int rows)
 {
@@ -530,8 +172,7 @@ extern "C" int sf_create(const sf_params *p, sf_sim **out)
     s->age = s->age_alloc + (size_t)g.P * g.ab;   // row 0 of env 0; guard rows at -1 and H of every env
     TRY(dev_alloc(s, &s->burn, cells));
     TRY(dev_alloc(s, &s->rt, (size_t)8 * g.plane_env * (p->per_env_terrain ? g.E : 1)));
-    s->rt_set.assign(p->per_env_terrain ? g.E : 1, 0);
-    s->rd_lay.assign(s->rt_set.size(), 0); s->rd_fbfm.assign(s->rt_set.size(), 0); s->rd_stale.assign(s->rt_set.size(), 1);
+    s->tables.init(p->per_env_terrain ? g.E : 1);
     TRY(dev_alloc(s, &s->lay_all, (size_t)7 * g.H * g.W * (p->per_env_terrain ? g.E : 1)));
     TRY(dev_alloc(s, &s->smag, (size_t)g.H * g.W));
     TRY(dev_alloc(s, &s->sdir, (size_t)g.H * g.W));
@@ -587,27 +228,21 @@ static int destroy(sf_sim *s)
 {
     if (!s) return SF_OK;
     hipSetDevice(s->p.device);
-    if (s->loop_on) (void)loop_stop(s);
+    if (s->loop.on) (void)loop_stop(s);
     if (s->stream) hipStreamSynchronize(s->stream);
     (void)comm_close(s);
-    if (s->xerr_pinned) (void)hipHostFree(s->xerr_pinned);
-    for (void *hp : {(void *)s->loop_db, (void *)s->loop_res, (void *)s->loop_pts}) if (hp) (void)hipHostFree(hp);
-    for (void *dp : {(void *)s->loop_mem, (void *)s->loop_pts_mem}) if (dp) (void)hipFree(dp);
-    void *ptrs[] = {s->team_tab, s->team_size, s->xdone, s->xg, s->xbuf, s->xj, s->xcut, s->jlog, s->status, s->age_alloc, s->cells_alloc, s->burn, s->rt, s->rtc, s->lay_all, s->history, s->smag, s->sdir, s->commit, s->tmp, s->flags, s->counters, s->tflags, s->tile_list, s->n_active, s->seam, s->settled, s->tdirty, s->thist, s->vbits, s->todo, s->run_cost, s->run_order, s->todo_cnt, s->win_hint, s->mit_stage,
-                    s->status_block, s->elapsed_dev, s->stage, s->parents, s->arrival1, s->val_plane, s->val_aux, s->wterms, s->wsched, s->wdue, s->wdue_U};
+    // every feature frees what it owns; the step path's own buffers are listed here
+    (void)s->team.release(); (void)s->loop.release(); (void)s->delta.release(); (void)s->arrival.release(); (void)s->values.release();
+    (void)s->render.release(); (void)s->wind.release(); (void)s->agents.release(); (void)s->episodes.release();
+    for (CallBlock *b : {&s->obs_blk, &s->render.blk, &s->rs_blk, &s->gen_blk, &s->agents.blk, &s->wind.blk, &s->ens_blk}) b->release();
+    void *ptrs[] = {s->status, s->age_alloc, s->cells_alloc, s->burn, s->rt, s->rtc, s->lay_all, s->history, s->smag, s->sdir, s->commit, s->tmp, s->flags, s->counters, s->tflags, s->tile_list, s->n_active, s->seam, s->settled, s->tdirty, s->thist, s->vbits, s->todo, s->run_cost, s->run_order, s->todo_cnt, s->win_hint, s->mit_stage,
+                    s->status_block, s->elapsed_dev, s->stage, s->parents};
+    for (void *p : ptrs) if (p) hipFree(p);
     if (s->status_pinned) (void)hipHostFree(s->status_pinned);
-    if (s->delta_pinned) (void)hipHostFree(s->delta_pinned);
-    for (void *dp : {(void *)s->snap, (void *)s->delta_dev, (void *)s->rd_bg, (void *)s->rd_fuel_ix, (void *)s->ag_mem, (void *)s->ep_mem}) if (dp) (void)hipFree(dp);
-    for (CallBlock *b : {&s->obs_blk, &s->rd_blk, &s->rs_blk, &s->gen_blk, &s->ag_blk, &s->wind_blk, &s->ens_blk}) {
-        if (b->dev) (void)hipFree(b->dev);
-        if (b->pinned) (void)hipHostFree(b->pinned);
-        if (b->ev) (void)hipEventDestroy(b->ev);
-    }
     for (int i = 0; i < sf_sim::kPtsRing; ++i) {
         if (s->pts_pinned[i]) (void)hipHostFree(s->pts_pinned[i]);
         if (s->ev_pts[i]) (void)hipEventDestroy(s->ev_pts[i]);
     }
-    for (void *p : ptrs) if (p) hipFree(p);
     if (s->ev0) hipEventDestroy(s->ev0);
     if (s->ev1) hipEventDestroy(s->ev1);
     if (s->stream) hipStreamDestroy(s->stream);
@@ -774,8 +409,8 @@ extern "C" int sf_get_team_sizes(sf_sim *s, uint32_t *out)
     if (!s || !out) return fail(SF_EINVAL, "sf_get_team_sizes: null argument");
     HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
     HIPCHK(hipStreamSynchronize(s->stream));
-    if (!s->last_team_max || !s->team_size) { for (int e = 0; e < s->g.E; ++e) out[e] = 0; return SF_OK; }
-    HIPCHK(hipMemcpy(out, s->team_size, (size_t)s->g.E * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (!s->last_team_max || !s->team.size) { for (int e = 0; e < s->g.E; ++e) out[e] = 0; return SF_OK; }
+    HIPCHK(hipMemcpy(out, s->team.size, (size_t)s->g.E * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return SF_OK;
 }
 extern "C" int sf_get_join_log(sf_sim *s, uint32_t *out, int32_t cap, int32_t *n_out)
@@ -784,12 +419,12 @@ extern "C" int sf_get_join_log(sf_sim *s, uint32_t *out, int32_t cap, int32_t *n
     HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
     HIPCHK(hipStreamSynchronize(s->stream));
     *n_out = 0;
-    if (!s->jlog || !s->jlog_valid) return SF_OK;
+    if (!s->team.jlog || !s->team.jlog_valid) return SF_OK;
     uint32_t n = 0;
-    HIPCHK(hipMemcpy(&n, s->jlog, sizeof n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&n, s->team.jlog, sizeof n, hipMemcpyDeviceToHost));
     if (n > (uint32_t)kJoinLog) n = kJoinLog;
     if (n > (uint32_t)cap) n = (uint32_t)cap;
-    if (n) HIPCHK(hipMemcpy(out, s->jlog + 1, (size_t)n * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (n) HIPCHK(hipMemcpy(out, s->team.jlog + 1, (size_t)n * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
     *n_out = (int32_t)n;
     return SF_OK;
 }
@@ -803,11 +438,11 @@ extern "C" int sf_get_team_fallbacks(sf_sim *s, int32_t *out)
 {
     if (!s || !out) return fail(SF_EINVAL, "sf_get_team_fallbacks: null argument");
     *out = 0;
-    if (!s->xdone) return SF_OK;                   // (no team launch yet)
+    if (!s->team.xdone) return SF_OK;                   // (no team launch yet)
     HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
     HIPCHK(hipStreamSynchronize(s->stream));
     uint32_t v = 0;
-    HIPCHK(hipMemcpy(&v, s->xdone + (size_t)2 * s->g.E, sizeof v, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&v, s->team.xdone + (size_t)2 * s->g.E, sizeof v, hipMemcpyDeviceToHost));
     *out = (int32_t)v;
     return SF_OK;
 }
@@ -828,572 +463,9 @@ extern "C" int sf_set_dense(sf_sim *s, int32_t dense)
     return SF_OK;
 }
 
-// which R tables an env argument addresses: env < 0 = all of them
-static int table_range(sf_sim *s, int env, const char *who, int *lo, int *hi)
-{
-    const int n_tab = (int)s->rt_set.size();
-    if (env < 0) { *lo = 0; *hi = n_tab; return SF_OK; }
-    if (n_tab == 1) return fail(SF_ESTATE, "%s: this handle shares one terrain between all environments "
-                                "(create it with per_env_terrain = 1)", who);
-    if (env >= n_tab) return fail(SF_EINVAL, "%s: environment %d out of range", who, env);
-    *lo = env; *hi = env + 1;
-    return SF_OK;
-}
-// tables tabs[0 .. n) were replaced: only their cell-major copies are rebuilt (ensure_rtc)
-static void mark_tables(sf_sim *s, const int32_t *tabs, int n)
-{
-    if (s->rtc_stale.size() != s->rt_set.size()) s->rtc_stale.assign(s->rt_set.size(), 1);
-    for (int k = 0; k < n; ++k) s->rt_set[tabs[k]] = s->rtc_stale[tabs[k]] = 1;
-    if (!s->wt_stale.empty()) for (int k = 0; k < n; ++k) s->wt_stale[tabs[k]] = 1;      // (the cache of wind-independent terms: ensure_wterms)
-    s->wind_sched_ready = false;
-    s->rtc_valid = false;
-    s->have_rt = true;
-    for (char c : s->rt_set) if (!c) s->have_rt = false;
-}
-static void mark_tables(sf_sim *s, int lo, int hi)
-{
-    std::vector<int32_t> tabs;
-    for (int i = lo; i < hi; ++i) tabs.push_back(i);
-    mark_tables(s, tabs.data(), hi - lo);
-}
+#include "sf_host_terrain.h"
 
-// theta = arctan2(src_y - dst_y, dst_x - src_x) of the 8 travel directions, float32 (rothermel.py:102)
-static Thetas rt_thetas()
-{
-    Thetas th;
-    for (int k = 0; k < 8; ++k) th.v[k] = atan2f((float)SF_SRC_DY[k], (float)(-SF_SRC_DX[k]));
-    return th;
-}
-
-// src[i] == nullptr: plane i of table `lo` is already on the device (filled from a fuel-code raster)
-static int set_layers_impl(sf_sim *s, int env, const double *const src[7])
-{
-    int lo, hi, rc = table_range(s, env, "sf_set_layers", &lo, &hi);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    const Geo &g = s->g;
-    const size_t n = (size_t)g.H * g.W;
-    for (int i = 0; i < 7; ++i)
-        if (src[i]) HIPCHK(hipMemcpyAsync(s->layer(lo, i), src[i], n * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    dim3 blk(256), grd((g.W + 255) / 256, g.H);
-    hipLaunchKernelGGL(k_slopes, grd, blk, 0, s->stream, g.H, g.W, s->layer(lo, 4), s->slope_scale, s->smag, s->sdir);
-    const Thetas th = rt_thetas();
-    dim3 grd2((g.P + 255) / 256, g.H);
-    const size_t tab = (size_t)8 * g.plane_env;
-    hipLaunchKernelGGL(k_rtable, grd2, blk, 0, s->stream, g.H, g.W, g.P, s->layer(lo, 0), s->layer(lo, 1), s->layer(lo, 2),
-                       s->layer(lo, 3), s->layer(lo, 5), s->layer(lo, 6), s->smag, s->sdir, (float)s->p.h, (float)s->p.S_T,
-                       (float)s->p.S_e, (float)s->p.p_p, (float)s->p.M_f, th, s->rt + (size_t)lo * tab);
-    HIPCHK(hipGetLastError());
-    for (int i = lo + 1; i < hi; ++i) {   // same terrain for several environments: replicate layers and table
-        HIPCHK(hipMemcpyAsync(s->layer(i, 0), s->layer(lo, 0), 7 * n * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
-        HIPCHK(hipMemcpyAsync(s->rt + (size_t)i * tab, s->rt + (size_t)lo * tab, tab * sizeof(double),
-                              hipMemcpyDeviceToDevice, s->stream));
-    }
-    HIPCHK(hipStreamSynchronize(s->stream));
-    mark_tables(s, lo, hi);
-    for (int i = lo; i < hi; ++i) { s->rd_lay[i] = 1; s->rd_fbfm[i] = src[0] == nullptr; s->rd_stale[i] = 1; }
-    if (s->wsched) {
-        std::vector<int32_t> tabs;
-        for (int i = lo; i < hi; ++i) tabs.push_back(i);
-        rc = wind_forget(s, tabs.data(), hi - lo);
-        if (!rc && !s->wind_sched.empty()) HIPCHK(hipStreamSynchronize(s->stream));
-    }
-    return rc;
-}
-
-extern "C" int sf_set_layers(sf_sim *s, const double *w_0, const double *delta, const double *M_x,
-                             const double *sigma, const double *elevation, const double *U, const double *U_dir)
-{
-    if (!s) return fail(SF_EINVAL, "sf_set_layers: null handle");
-    const double *src[7] = {w_0, delta, M_x, sigma, elevation, U, U_dir};
-    return set_layers_impl(s, -1, src);
-}
-
-extern "C" int sf_set_layers_env(sf_sim *s, int32_t env, const double *w_0, const double *delta, const double *M_x,
-                                 const double *sigma, const double *elevation, const double *U, const double *U_dir)
-{
-    if (!s) return fail(SF_EINVAL, "sf_set_layers_env: null handle");
-    if (env < 0) return fail(SF_EINVAL, "sf_set_layers_env: environment %d out of range", env);
-    const double *src[7] = {w_0, delta, M_x, sigma, elevation, U, U_dir};
-    return set_layers_impl(s, env, src);
-}
-
-// FuelLayer._get_data (simfire/utils/layers.py:670-676): FBFM13 code raster -> Fuel through the
-// FuelModelToFuel table (simfire/enums.py:176-198), done on the device.  The table is the caller's.
-extern "C" int sf_set_layers_fbfm(sf_sim *s, int32_t env, const int32_t *codes, int32_t n_lut, const int32_t *lut_codes,
-                                  const double *lut_fuel, const double *elevation, const double *U, const double *U_dir)
-{
-    if (!s || !codes || !lut_codes || !lut_fuel || !elevation || !U || !U_dir)
-        return fail(SF_EINVAL, "sf_set_layers_fbfm: null argument");
-    if (n_lut < 1 || n_lut > kMaxFuelLut) return fail(SF_EINVAL, "sf_set_layers_fbfm: n_lut must be 1..%d", kMaxFuelLut);
-    int lo, hi, rc = table_range(s, env, "sf_set_layers_fbfm", &lo, &hi);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    const Geo &g = s->g;
-    const size_t n = (size_t)g.H * g.W;
-    rc = ensure_stage(s, n * sizeof(int32_t) + (1 + kRdFbfmColours) * sizeof(int32_t));      // codes | bad | sf_render's colour codes
-    if (rc) return rc;
-    int32_t *codes_dev = (int32_t *)s->stage, *bad_dev = codes_dev + n;
-    HIPCHK(hipMemcpyAsync(codes_dev, codes, n * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
-    const int32_t none = INT32_MIN;
-    HIPCHK(hipMemcpyAsync(bad_dev, &none, sizeof none, hipMemcpyHostToDevice, s->stream));
-    FuelLut lut;
-    lut.n = n_lut;
-    for (int i = 0; i < n_lut; ++i) {
-        lut.code[i] = lut_codes[i];
-        for (int k = 0; k < 4; ++k) lut.fuel[i][k] = lut_fuel[4 * i + k];
-    }
-    hipLaunchKernelGGL(k_fuel_lut, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, (long long)n,
-                       (const int32_t *)codes_dev, lut, s->layer(lo, 0), s->layer(lo, 1), s->layer(lo, 2), s->layer(lo, 3), bad_dev);
-    HIPCHK(hipGetLastError());
-    int32_t bad = none;
-    HIPCHK(hipMemcpyAsync(&bad, bad_dev, sizeof bad, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    if (bad != none) return fail(SF_EINVAL, "sf_set_layers_fbfm: fuel model code %d is not in the table", bad);
-    // the codes' colours for sf_render (FuelLayer._make_image, layers.py:654-667): the codes are dropped after the lookup above
-    if (!s->rd_fuel_ix) HIPCHK(hipMalloc(reinterpret_cast<void **>(&s->rd_fuel_ix), n * s->rt_set.size()));
-    int32_t *tab_dev = bad_dev + 1;
-    HIPCHK(hipMemcpyAsync(tab_dev, kRdFbfmCodes, sizeof kRdFbfmCodes, hipMemcpyHostToDevice, s->stream));
-    hipLaunchKernelGGL(k_render_fuel_ix, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, (long long)n, (const int32_t *)codes_dev,
-                       (const int32_t *)tab_dev, kRdFbfmColours, s->rd_fuel_ix + (size_t)lo * n);
-    HIPCHK(hipGetLastError());
-    for (int i = lo + 1; i < hi; ++i)
-        HIPCHK(hipMemcpyAsync(s->rd_fuel_ix + (size_t)i * n, s->rd_fuel_ix + (size_t)lo * n, n, hipMemcpyDeviceToDevice, s->stream));
-    const double *src[7] = {nullptr, nullptr, nullptr, nullptr, elevation, U, U_dir};
-    return set_layers_impl(s, env, src);
-}
-
-// FireSimulation.get_attribute_data (simfire/sim/simulation.py:376-403): w_0 / delta / M_x as float32,
-// sigma as uint32 (astype truncation), elevation and wind as supplied (float64).  Null pointers are
-// skipped; device_pointers != 0: the outputs are device buffers (observation tensors stay in HBM).
-extern "C" int sf_get_attribute_data(sf_sim *s, int32_t env, float *w_0, uint32_t *sigma, float *delta, float *M_x,
-                                     double *elevation, double *wind_speed, double *wind_direction, int32_t device_pointers)
-{
-    if (!s) return fail(SF_EINVAL, "sf_get_attribute_data: null handle");
-    const int n_tab = (int)s->rt_set.size();
-    if (env < 0 || env >= s->g.E) return fail(SF_EINVAL, "sf_get_attribute_data: environment %d out of range", env);
-    const int t = n_tab == 1 ? 0 : env;
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    const Geo &g = s->g;
-    const size_t n = (size_t)g.H * g.W;
-    const hipMemcpyKind kind = device_pointers ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (w_0 || sigma || delta || M_x) {
-        int rc = ensure_stage(s, 4 * n * sizeof(float));
-        if (rc) return rc;
-        float *st = (float *)s->stage;
-        float *d_w0 = device_pointers && w_0 ? w_0 : st, *d_de = device_pointers && delta ? delta : st + 2 * n,
-              *d_mx = device_pointers && M_x ? M_x : st + 3 * n;
-        uint32_t *d_si = device_pointers && sigma ? sigma : (uint32_t *)(st + n);
-        hipLaunchKernelGGL(k_attribute_planes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, (long long)n,
-                           (const double *)s->layer(t, 0), (const double *)s->layer(t, 1), (const double *)s->layer(t, 2),
-                           (const double *)s->layer(t, 3), d_w0, d_si, d_de, d_mx);
-        HIPCHK(hipGetLastError());
-        if (!device_pointers) {
-            if (w_0) HIPCHK(hipMemcpyAsync(w_0, st, n * 4, kind, s->stream));
-            if (sigma) HIPCHK(hipMemcpyAsync(sigma, st + n, n * 4, kind, s->stream));
-            if (delta) HIPCHK(hipMemcpyAsync(delta, st + 2 * n, n * 4, kind, s->stream));
-            if (M_x) HIPCHK(hipMemcpyAsync(M_x, st + 3 * n, n * 4, kind, s->stream));
-        }
-    }
-    if (elevation) HIPCHK(hipMemcpyAsync(elevation, s->layer(t, 4), n * sizeof(double), kind, s->stream));
-    if (wind_speed) HIPCHK(hipMemcpyAsync(wind_speed, s->layer(t, 5), n * sizeof(double), kind, s->stream));
-    if (wind_direction) HIPCHK(hipMemcpyAsync(wind_direction, s->layer(t, 6), n * sizeof(double), kind, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return SF_OK;
-}
-
-// sf_generate_layers (include/simfire_hip.h; sf_gen_kernels.h): every argument is checked before any device work
-static int check_noise(const sf_noise &p, int e, const char *plane)
-{
-    if (p.kind == SF_GEN_NONE || p.kind == SF_GEN_CONSTANT) return SF_OK;
-    if (p.kind != SF_GEN_SIMPLEX) return fail(SF_EINVAL, "sf_generate_layers: environment %d, %s: unknown kind %d", e, plane, p.kind);
-    if (!(p.scale > 0.0)) return fail(SF_EINVAL, "sf_generate_layers: environment %d, %s: scale must be > 0", e, plane);
-    if (p.octaves < 1 || p.octaves > kGenMaxOctaves)
-        return fail(SF_EINVAL, "sf_generate_layers: environment %d, %s: octaves must be 1..%d", e, plane, kGenMaxOctaves);
-    if (!(p.lo < p.hi)) return fail(SF_EINVAL, "sf_generate_layers: environment %d, %s: range_min must be less than range_max", e, plane);
-    return SF_OK;
-}
-
-extern "C" int sf_generate_layers(sf_sim *s, int32_t n, const int32_t *envs, const sf_layer_gen *gen)
-{
-    if (!s) return fail(SF_EINVAL, "sf_generate_layers: null handle");
-    if (n < 0) return fail(SF_EINVAL, "sf_generate_layers: n = %d", n);
-    if (n > 0 && (!envs || !gen)) return fail(SF_EINVAL, "sf_generate_layers: null argument");
-    if (!s->p.per_env_terrain)
-        return fail(SF_ESTATE, "sf_generate_layers: this handle shares one terrain between all environments (create it with per_env_terrain = 1)");
-    const Geo &g = s->g;
-    { int rc = check_envs(s, "sf_generate_layers", n, envs, "listed twice"); if (rc) return rc; }
-    for (int k = 0; k < n; ++k) {
-        const int e = envs[k];
-        const sf_layer_gen &d = gen[k];
-        int rc = check_noise(d.elevation, e, "elevation");
-        if (!rc) rc = check_noise(d.wind_speed, e, "wind_speed");
-        if (!rc) rc = check_noise(d.wind_direction, e, "wind_direction");
-        if (rc) return rc;
-        if (d.fuel != SF_GEN_NONE && d.fuel != SF_GEN_CONSTANT)
-            return fail(SF_EINVAL, "sf_generate_layers: environment %d, fuel: unknown kind %d", e, d.fuel);
-    }
-    if (n == 0) return SF_OK;
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    const size_t gen_bytes = (size_t)n * sizeof(sf_layer_gen), bytes = gen_bytes + (size_t)n * sizeof(int32_t);
-    CallBlock &blk = s->gen_blk;
-    { int rc = block_reserve(s, blk, bytes); if (rc) return rc; }
-    memcpy(blk.pinned, gen, gen_bytes);
-    memcpy(blk.pinned + gen_bytes, envs, (size_t)n * sizeof(int32_t));
-    { int rc = block_send(s, blk, bytes); if (rc) return rc; }
-    const sf_layer_gen *gen_d = (const sf_layer_gen *)blk.dev;
-    const int32_t *envs_d = (const int32_t *)(blk.dev + gen_bytes);
-    const long long cells = (long long)g.H * g.W;
-    const Thetas th = rt_thetas();
-    for (int k0 = 0; k0 < n; k0 += kGenChunk) {          // (grid y / z hold at most kGenChunk environments)
-        const int m = std::min(n - k0, kGenChunk);
-        hipLaunchKernelGGL(k_gen_planes, dim3((unsigned)((cells + kGenThreads - 1) / kGenThreads), (unsigned)m, 4), dim3(kGenThreads), 0,
-                           s->stream, g.H, g.W, s->lay_all, envs_d, gen_d, k0);
-        HIPCHK(hipGetLastError());
-    }
-    for (int k0 = 0; k0 < n; k0 += kGenChunk) {
-        const int m = std::min(n - k0, kGenChunk);
-        hipLaunchKernelGGL(k_gen_rtable, dim3((unsigned)((g.P + kGenThreads - 1) / kGenThreads), (unsigned)g.H, (unsigned)m), dim3(kGenThreads), 0,
-                           s->stream, g.H, g.W, g.P, (const double *)s->lay_all, envs_d, k0, s->slope_scale, (float)s->p.h, (float)s->p.S_T,
-                           (float)s->p.S_e, (float)s->p.p_p, (float)s->p.M_f, th, s->rt, (long long)8 * g.plane_env);
-        HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipStreamSynchronize(s->stream));
-    mark_tables(s, envs, n);
-    for (int k = 0; k < n; ++k) { s->rd_lay[envs[k]] = 1; s->rd_fbfm[envs[k]] = 0; s->rd_stale[envs[k]] = 1; }
-    return wind_forget(s, envs, n);
-}
-
-// ----------------------------------------------------------------------------- wind changes
-// The wind-independent terms of the listed tables (host list) made current in the cache plane, modelled on ensure_rtc: allocated at
-// the first wind change, filled per run of stale tables.  SF_ENOTSUP: no cache (no memory for it, or switched off by the lab) - the
-// caller builds from the layers.
-static int ensure_wterms(sf_sim *s, const int32_t *tabs, int n)
-{
-    if (s->wt_off) return SF_ENOTSUP;
-    const Geo &g = s->g;
-    const size_t n_tab = s->rt_set.size(), per = (size_t)kWindPlanes * g.H * g.W;
-    if (!s->wterms) {
-        if (hipMalloc(reinterpret_cast<void **>(&s->wterms), per * n_tab * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); s->wterms = nullptr; return SF_ENOTSUP; }
-        s->bytes += (int64_t)(per * n_tab * sizeof(float));
-        s->wt_stale.assign(n_tab, 1);
-    }
-    std::vector<int32_t> stale;
-    for (int k = 0; k < n; ++k) if (s->wt_stale[tabs[k]]) stale.push_back(tabs[k]);
-    std::sort(stale.begin(), stale.end());
-    const Thetas th = rt_thetas();
-    for (size_t i = 0; i < stale.size();) {
-        size_t j = i + 1;
-        while (j < stale.size() && stale[j] == stale[j - 1] + 1 && j - i < 65535) ++j;
-        hipLaunchKernelGGL(k_wind_terms, dim3((unsigned)((g.W + kWindThreads - 1) / kWindThreads), (unsigned)g.H, (unsigned)(j - i)), dim3(kWindThreads), 0,
-                           s->stream, g.H, g.W, (const double *)s->lay_all, (const int32_t *)nullptr, (int)stale[i], s->slope_scale, (float)s->p.h,
-                           (float)s->p.S_T, (float)s->p.S_e, (float)s->p.p_p, (float)s->p.M_f, th, s->wterms);
-        for (size_t k = i; k < j; ++k) s->wt_stale[stale[k]] = 0;
-        i = j;
-    }
-    HIPCHK(hipGetLastError());
-    return SF_OK;
-}
-
-// k_wind_rtable for `count` listed tables, or - cnt_dev - for as many as the device says (at most max_count); enqueue layer
-static int wind_launch(sf_sim *s, const int32_t *list_dev, const uint32_t *cnt_dev, int count, int max_count, const double *U, const double *U_dir,
-                       int field, bool cached)
-{
-    const Geo &g = s->g;
-    WindArgs a;
-    a.H = g.H; a.W = g.W; a.P = g.P;
-    a.lay = s->lay_all; a.cache = s->wterms; a.rt = s->rt; a.rtc = s->rtc;
-    a.tab_stride = (long long)8 * g.plane_env;
-    a.list = list_dev; a.count_dev = cnt_dev; a.count = count;
-    a.U = U; a.U_dir = U_dir; a.field = field;
-    a.ps = s->slope_scale;
-    a.h = (float)s->p.h; a.S_T = (float)s->p.S_T; a.S_e = (float)s->p.S_e; a.p_p = (float)s->p.p_p; a.M_f = (float)s->p.M_f;
-    a.th = rt_thetas();
-    const long long items = (long long)max_count * g.H * ((g.P + kWindThreads - 1) / kWindThreads);
-    const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>(items, (long long)s->n_cu * 8));
-    if (cached) hipLaunchKernelGGL(k_wind_rtable<true>, dim3(grid), dim3(kWindThreads), 0, s->stream, a);
-    else hipLaunchKernelGGL(k_wind_rtable<false>, dim3(grid), dim3(kWindThreads), 0, s->stream, a);
-    HIPCHK(hipGetLastError());
-    return SF_OK;
-}
-
-static void wind_sched_count(sf_sim *s)
-{
-    s->wind_sched.clear();
-    for (int e = 0; e < (int)s->wind_K.size(); ++e) if (s->wind_K[e]) s->wind_sched.push_back(e);
-    s->wind_sched_ready = false;
-}
-
-// An environment list -> the wind call block (enqueue layer); *dev: where it is
-static int wind_list(sf_sim *s, const int32_t *envs, int n, const int32_t **dev)
-{
-    CallBlock &blk = s->wind_blk;
-    { int rc = block_reserve(s, blk, (size_t)n * 4); if (rc) return rc; }
-    memcpy(blk.pinned, envs, (size_t)n * 4);
-    *dev = (const int32_t *)blk.dev;
-    return block_send(s, blk, (size_t)n * 4);
-}
-
-// The tables of these environments were rebuilt from their layers (or their state was loaded): whichever segment a schedule built
-// them for, the next stepping call decides anew.
-static int wind_forget(sf_sim *s, const int32_t *envs, int n)
-{
-    bool any = false;
-    for (int k = 0; k < n && !any; ++k) any = s->wsched && s->wind_K[envs[k]] != 0;
-    if (!any) return SF_OK;
-    const int32_t *list_dev = nullptr;
-    { int rc = wind_list(s, envs, n, &list_dev); if (rc) return rc; }
-    hipLaunchKernelGGL(k_wind_sched_forget, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, n, list_dev, s->wsched);
-    HIPCHK(hipGetLastError());
-    return SF_OK;
-}
-
-// In front of the updates of a stepping call while a schedule is set (enqueue layer): the cache made current for the scheduled
-// tables, the due list made on the device, the due tables rebuilt.  Nothing is read back.
-static int wind_sched_pass(sf_sim *s)
-{
-    const Geo &g = s->g;
-    const int n = (int)s->wind_sched.size();
-    bool cached = s->wind_sched_cached;
-    if (!s->wind_sched_ready) {
-        const int rc = ensure_wterms(s, s->wind_sched.data(), n);
-        if (rc && rc != SF_ENOTSUP) return rc;
-        cached = s->wind_sched_cached = rc == SF_OK;
-        s->wind_sched_ready = true;
-    }
-    if (s->wind_timed) HIPCHK(hipEventRecord(s->ev0, s->stream));
-    HIPCHK(hipMemsetAsync(s->wdue_cnt, 0, sizeof(uint32_t), s->stream));
-    hipLaunchKernelGGL(k_wind_due, dim3((unsigned)((g.E + 255) / 256)), dim3(256), 0, s->stream, g, (const EnvState *)s->commit, (const EnvState *)s->tmp,
-                       (const uint32_t *)s->flags, s->seq, s->committed ? 1 : 0, s->wsched, s->wdue_cnt, s->wdue, s->wdue_U, s->wdue_D);
-    { int rc = wind_launch(s, s->wdue, s->wdue_cnt, 0, n, s->wdue_U, s->wdue_D, 0, cached); if (rc) return rc; }
-    if (s->wind_timed) { HIPCHK(hipEventRecord(s->ev1, s->stream)); s->wind_have_ms = true; }
-    return SF_OK;
-}
-
-// the tables a wind call addresses: the list, or every table in order; what must hold before any device work
-static int wind_targets(const sf_sim *s, const char *who, int32_t n, const int32_t *envs, bool need_per_env, std::vector<int32_t> &tabs)
-{
-    if (n < 0) return fail(SF_EINVAL, "%s: n = %d", who, n);
-    const int n_tab = (int)s->rt_set.size();
-    if ((envs || need_per_env) && !s->p.per_env_terrain)
-        return fail(SF_ESTATE, "%s: this handle shares one terrain between all environments (create it with per_env_terrain = 1)", who);
-    if (envs) { int rc = check_envs(s, who, n, envs, "listed twice"); if (rc) return rc; }
-    else if (n != 0 && n != n_tab) return fail(SF_EINVAL, "%s: without a list n must be the number of tables, %d (got %d)", who, n_tab, n);
-    tabs.resize((size_t)n);
-    for (int i = 0; i < n; ++i) tabs[i] = envs ? envs[i] : i;
-    for (int i = 0; i < n; ++i)
-        if (!s->rd_lay[tabs[i]]) return fail(SF_ESTATE, "%s: table %d has no layers (sf_set_layers*, sf_generate_layers)", who, tabs[i]);
-    return SF_OK;
-}
-
-// fire.py:365, 490-494: self.U / self.U_dir reassigned between two update() calls
-extern "C" int sf_set_wind(sf_sim *s, int32_t n, const int32_t *envs, const double *U, const double *U_dir, int32_t flags)
-{
-    if (!s) return fail(SF_EINVAL, "sf_set_wind: null handle");
-    if (flags & ~(SF_WIND_FIELD | SF_WIND_DEVICE)) return fail(SF_EINVAL, "sf_set_wind: unknown flags 0x%x", flags);
-    if (n > 0 && (!U || !U_dir)) return fail(SF_EINVAL, "sf_set_wind: null argument");
-    std::vector<int32_t> tabs;
-    { int rc = wind_targets(s, "sf_set_wind", n, envs, false, tabs); if (rc) return rc; }
-    if (n == 0) return SF_OK;
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    const Geo &g = s->g;
-    const bool field = (flags & SF_WIND_FIELD) != 0, device = (flags & SF_WIND_DEVICE) != 0;
-    const size_t cells = (size_t)g.H * g.W, list_bytes = ((size_t)n * 4 + 7) / 8 * 8;
-    const bool scalars = !field && !device;         // the host scalars travel behind the list
-    CallBlock &blk = s->wind_blk;
-    { int rc = block_reserve(s, blk, list_bytes + (scalars ? (size_t)n * 16 : 0)); if (rc) return rc; }
-    memcpy(blk.pinned, tabs.data(), (size_t)n * 4);
-    if (scalars) { memcpy(blk.pinned + list_bytes, U, (size_t)n * 8); memcpy(blk.pinned + list_bytes + (size_t)n * 8, U_dir, (size_t)n * 8); }
-    { int rc = block_send(s, blk, list_bytes + (scalars ? (size_t)n * 16 : 0)); if (rc) return rc; }
-    const int32_t *list_dev = (const int32_t *)blk.dev;
-    const int rcw = ensure_wterms(s, tabs.data(), n);
-    if (rcw && rcw != SF_ENOTSUP) return rcw;
-    const bool cached = rcw == SF_OK;
-    if (s->wind_timed) HIPCHK(hipEventRecord(s->ev0, s->stream));
-    if (field && !device) {
-        // host fields go through the stage buffer, as many tables at a time as fit 64 MB of it (one at least)
-        const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)64 << 20) / (cells * 16)));
-        { int rc = ensure_stage(s, (size_t)chunk * cells * 16); if (rc) return rc; }
-        double *su = (double *)s->stage, *sd = su + (size_t)chunk * cells;
-        for (int i0 = 0; i0 < n; i0 += chunk) {
-            const int cnt = std::min(chunk, n - i0);
-            HIPCHK(hipMemcpyAsync(su, U + (size_t)i0 * cells, (size_t)cnt * cells * 8, hipMemcpyHostToDevice, s->stream));
-            HIPCHK(hipMemcpyAsync(sd, U_dir + (size_t)i0 * cells, (size_t)cnt * cells * 8, hipMemcpyHostToDevice, s->stream));
-            int rc = wind_launch(s, list_dev + i0, nullptr, cnt, cnt, su, sd, 1, cached);
-            if (rc) return rc;
-        }
-    } else {
-        const double *u = scalars ? (const double *)(blk.dev + list_bytes) : U, *d = scalars ? (const double *)(blk.dev + list_bytes) + n : U_dir;
-        int rc = wind_launch(s, list_dev, nullptr, n, n, u, d, field ? 1 : 0, cached);
-        if (rc) return rc;
-    }
-    if (s->wind_timed) { HIPCHK(hipEventRecord(s->ev1, s->stream)); s->wind_have_ms = true; }
-    // the direction-major table was replaced; the cell-major copy, where the buffer exists, was written in the same pass
-    if (s->rtc_stale.size() != s->rt_set.size()) s->rtc_stale.assign(s->rt_set.size(), 1);
-    for (int i = 0; i < n; ++i) {
-        s->rt_set[tabs[i]] = 1;
-        s->rtc_stale[tabs[i]] = s->rtc ? 0 : 1;
-    }
-    s->have_rt = true;
-    for (char c : s->rt_set) if (!c) s->have_rt = false;
-    bool had = false;
-    for (int i = 0; i < n; ++i) if (s->wsched && s->wind_K[tabs[i]]) { had = true; s->wind_K[tabs[i]] = 0; }
-    if (had) {           // a wind set by hand ends the environment's schedule
-        hipLaunchKernelGGL(k_wind_sched_set, dim3((unsigned)n), dim3(SF_WIND_MAX_SEGS), 0, s->stream, n, list_dev, 0, (const sf_wind_seg *)nullptr, s->wsched);
-        HIPCHK(hipGetLastError());
-        wind_sched_count(s);
-    }
-    return finish_call(s, nullptr, !s->async, nullptr);
-}
-
-extern "C" int sf_set_wind_schedule(sf_sim *s, int32_t n, const int32_t *envs, int32_t K, const sf_wind_seg *segs)
-{
-    const char *who = "sf_set_wind_schedule";
-    if (!s) return fail(SF_EINVAL, "%s: null handle", who);
-    if (K < 0 || K > SF_WIND_MAX_SEGS) return fail(SF_EINVAL, "%s: 0 .. %d segments (got %d)", who, SF_WIND_MAX_SEGS, K);
-    if (s->ep_on && (s->ep.flags & SF_EP_WIND))
-        return fail(SF_ESTATE, "%s: every new episode draws its wind (sf_episodes_set with SF_EP_WIND): a schedule would fight it over the table", who);
-    if (n > 0 && K > 0 && !segs) return fail(SF_EINVAL, "%s: null argument", who);
-    std::vector<int32_t> tabs;
-    { int rc = wind_targets(s, who, n, envs, true, tabs); if (rc) return rc; }
-    for (int i = 0; i < n; ++i)
-        for (int k = 0; k < K; ++k) {
-            const sf_wind_seg &r = segs[(size_t)i * K + k];
-            if (r.reserved != 0) return fail(SF_EINVAL, "%s: environment %d, segment %d: reserved must be 0", who, tabs[i], k);
-            if (k == 0 ? r.first_update != 0 : r.first_update <= segs[(size_t)i * K + k - 1].first_update)
-                return fail(SF_EINVAL, "%s: environment %d: first_update must be 0 for segment 0 and strictly increasing (segment %d: %d)", who,
-                            tabs[i], k, r.first_update);
-        }
-    if (n == 0) return SF_OK;
-    if (K == 0 && !s->wsched) return SF_OK;
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    const Geo &g = s->g;
-    if (!s->wsched) {
-        { int rc = dev_alloc(s, &s->wsched, (size_t)g.E); if (rc) return rc; }
-        { int rc = dev_alloc(s, &s->wdue_U, (size_t)2 * g.E); if (rc) return rc; }
-        { int rc = dev_alloc(s, &s->wdue, (size_t)g.E + 2); if (rc) return rc; }
-        s->wdue_D = s->wdue_U + g.E;
-        s->wdue_cnt = reinterpret_cast<uint32_t *>(s->wdue + g.E);
-        HIPCHK(hipMemsetAsync(s->wsched, 0, sizeof(WindSched) * g.E, s->stream));
-        s->wind_K.assign((size_t)g.E, 0);
-    }
-    const size_t list_bytes = ((size_t)n * 4 + 7) / 8 * 8, rows_bytes = (size_t)n * K * sizeof(sf_wind_seg);
-    CallBlock &blk = s->wind_blk;
-    { int rc = block_reserve(s, blk, list_bytes + rows_bytes); if (rc) return rc; }
-    memcpy(blk.pinned, tabs.data(), (size_t)n * 4);
-    if (rows_bytes) memcpy(blk.pinned + list_bytes, segs, rows_bytes);
-    { int rc = block_send(s, blk, list_bytes + rows_bytes); if (rc) return rc; }
-    hipLaunchKernelGGL(k_wind_sched_set, dim3((unsigned)n), dim3(SF_WIND_MAX_SEGS), 0, s->stream, n, (const int32_t *)blk.dev, K,
-                       (const sf_wind_seg *)(blk.dev + list_bytes), s->wsched);
-    HIPCHK(hipGetLastError());
-    for (int i = 0; i < n; ++i) s->wind_K[tabs[i]] = K;
-    wind_sched_count(s);
-    return finish_call(s, nullptr, !s->async, nullptr);
-}
-
-// Laboratory (include/simfire_hip_lab.h): the cache switched off (freed; every wind change then builds from the layers) or on again;
-// HIP events around the launches of every wind change and every schedule pass.
-extern "C" int sf_set_wind_lab(sf_sim *s, int32_t cache_on, int32_t timed)
-{
-    if (!s) return fail(SF_EINVAL, "sf_set_wind_lab: null handle");
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    if (!cache_on && s->wterms) {
-        HIPCHK(hipStreamSynchronize(s->stream));
-        HIPCHK(hipFree(s->wterms));
-        s->wterms = nullptr;
-        s->bytes -= (int64_t)((size_t)kWindPlanes * s->g.H * s->g.W * s->rt_set.size() * sizeof(float));
-    }
-    s->wt_off = !cache_on;
-    s->wind_sched_ready = false;
-    s->ep_nocache = false;
-    s->wind_timed = timed != 0;
-    s->wind_have_ms = false;
-    return SF_OK;
-}
-extern "C" int sf_get_wind_ms(sf_sim *s, float *ms_out)
-{
-    if (!s || !ms_out) return fail(SF_EINVAL, "sf_get_wind_ms: null argument");
-    if (!s->wind_have_ms) return fail(SF_ESTATE, "sf_get_wind_ms: no wind change or schedule pass has been timed (sf_set_wind_lab)");
-    HIPCHK(hipSetDevice(s->p.device));
-    HIPCHK(hipEventSynchronize(s->ev1));
-    HIPCHK(hipEventElapsedTime(ms_out, s->ev0, s->ev1));
-    return SF_OK;
-}
-
-static int set_rtable_impl(sf_sim *s, int env, const double *R8)
-{
-    int lo, hi, rc = table_range(s, env, "sf_set_rtable", &lo, &hi);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    const Geo &g = s->g;
-    const size_t n = (size_t)8 * g.H * g.W * sizeof(double);
-    rc = ensure_stage(s, n);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(s->stage, R8, n, hipMemcpyHostToDevice, s->stream));
-    dim3 blk(256), grd((g.P + 255) / 256, g.H, 8);
-    const size_t tab = (size_t)8 * g.plane_env;
-    for (int i = lo; i < hi; ++i)
-        hipLaunchKernelGGL(k_pack_rt, grd, blk, 0, s->stream, g.H, g.W, g.P, (const double *)s->stage, s->rt + (size_t)i * tab);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s->stream));
-    mark_tables(s, lo, hi);
-    return SF_OK;
-}
-
-extern "C" int sf_set_rtable(sf_sim *s, const double *R8)
-{
-    if (!s || !R8) return fail(SF_EINVAL, "sf_set_rtable: null argument");
-    return set_rtable_impl(s, -1, R8);
-}
-
-extern "C" int sf_set_rtable_env(sf_sim *s, int32_t env, const double *R8)
-{
-    if (!s || !R8) return fail(SF_EINVAL, "sf_set_rtable_env: null argument");
-    if (env < 0) return fail(SF_EINVAL, "sf_set_rtable_env: environment %d out of range", env);
-    return set_rtable_impl(s, env, R8);
-}
-
-static int get_rtable_impl(sf_sim *s, int env, double *out)
-{
-    const int n_tab = (int)s->rt_set.size();
-    const int t = n_tab == 1 ? 0 : env;
-    if (t < 0 || t >= n_tab) return fail(SF_EINVAL, "sf_get_rtable: environment %d out of range", env);
-    if (!s->rt_set[t]) return fail(SF_ESTATE, "sf_get_rtable: no layers / table set");
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    const Geo &g = s->g;
-    const size_t n = (size_t)8 * g.H * g.W * sizeof(double);
-    int rc = ensure_stage(s, n);
-    if (rc) return rc;
-    dim3 blk(256), grd((g.W + 255) / 256, g.H, 8);
-    hipLaunchKernelGGL(k_unpack_f64, grd, blk, 0, s->stream, g.H, g.W, g.P,
-                       (const double *)(s->rt + (size_t)t * 8 * g.plane_env), (double *)s->stage);
-    HIPCHK(hipMemcpyAsync(out, s->stage, n, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return SF_OK;
-}
-
-extern "C" int sf_get_rtable(sf_sim *s, double *out)
-{
-    if (!s || !out) return fail(SF_EINVAL, "sf_get_rtable: null argument");
-    return get_rtable_impl(s, 0, out);
-}
-
-extern "C" int sf_get_rtable_env(sf_sim *s, int32_t env, double *out)
-{
-    if (!s || !out) return fail(SF_EINVAL, "sf_get_rtable_env: null argument");
-    return get_rtable_impl(s, env, out);
-}
-
-extern "C" int sf_get_slopes(sf_sim *s, double *mag, double *dir)
-{
-    if (!s || !mag || !dir) return fail(SF_EINVAL, "sf_get_slopes: null argument");
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    const size_t n = (size_t)s->g.H * s->g.W * sizeof(double);
-    HIPCHK(hipMemcpyAsync(mag, s->smag, n, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipMemcpyAsync(dir, s->sdir, n, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return SF_OK;
-}
+#include "sf_host_wind.h"
 
 // The environment states live in the tmp / flags rings while steps are being enqueued; they are folded
 // into commit[] only when something needs them (status queries, resets, burn_amounts transfers).
@@ -1428,7 +500,7 @@ static int env_segs(const sf_sim *s, unsigned kinds, EnvSeg *out)
     add(kSegBurn, s->burn, g.plane_env * 8);
     add(kSegSettled, s->settled, g.plane_env * 4);
     add(kSegParents, s->parents, g.plane_env);
-    add(kSegSnap, s->snap, g.plane_env);
+    add(kSegSnap, s->delta.snap, g.plane_env);
     add(kSegState, s->commit, sizeof(EnvState));
     add(kSegResult, s->status_block, 32);
     add(kSegResult, s->elapsed_dev, 8);
@@ -1504,8 +576,7 @@ extern "C" int sf_apply_mitigation(sf_sim *s, const int32_t *pts, int32_t n)
     // KB over the host link; no copy to enqueue).  It may still feed kernels enqueued kPtsRing calls ago.
     HIPCHK(hipEventSynchronize(s->ev_pts[slot]));
     memcpy(s->pts_pinned[slot], pts, bytes);
-    int rc = scatter_points(s, s->pts_mapped[slot], n);
-    if (rc) return rc;
+    SF_TRY(scatter_points(s, s->pts_mapped[slot], n));
     HIPCHK(hipEventRecord(s->ev_pts[slot], s->stream));
     return finish_call(s, nullptr, !s->async, nullptr);
 }
@@ -1530,14 +601,11 @@ extern "C" int sf_load_fire_map(sf_sim *s, int32_t env, const uint8_t *map)
         if (map[i] > SF_WETLINE) return fail(SF_EINVAL, "sf_load_fire_map: value %d at cell %zu is not a BurnStatus", map[i], i);
     HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
     s->fire_rows = 0;                  // (a map from outside: its fire may be of any size)
-    if (s->snap) s->snap_valid[env] = 0;      // (sf_get_fire_map_delta: no reference point any more)
-    int rc = ensure_stage(s, n);
-    if (rc) return rc;
+    if (s->delta.snap) s->delta.snap_valid[env] = 0;      // (sf_get_fire_map_delta: no reference point any more)
+    SF_TRY(ensure_stage(s, n));
     dim3 blk(256), grd((g.W + 255) / 256, g.H);
-    rc = ensure_commit(s);
-    if (rc) return rc;
-    rc = ensure_rm(s);
-    if (rc) return rc;
+    SF_TRY(ensure_commit(s));
+    SF_TRY(ensure_rm(s));
     s->status_fresh = false;
     if (g.att)
         hipLaunchKernelGGL(k_settle_env, grd, blk, 0, s->stream, g, (const uint8_t *)s->status, s->settled, s->burn,
@@ -1546,7 +614,7 @@ extern "C" int sf_load_fire_map(sf_sim *s, int32_t env, const uint8_t *map)
     hipLaunchKernelGGL(k_pack_status, grd, blk, 0, s->stream, g, s->status, s->settled, (const EnvState *)s->commit, env,
                        (const uint8_t *)s->stage);
     HIPCHK(hipGetLastError());
-    rc = rebuild_tflags(s, env, 1);
+    const int rc = rebuild_tflags(s, env, 1);
     s->tdirty_all = true;
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(s->stream));
@@ -1569,8 +637,7 @@ static int alloc_bl(sf_sim *s)
     if (s->cells_alloc) return SF_OK;
     const Geo &g = s->g;
     const size_t bytes = (size_t)g.E * g.cells_env;
-    int rc = dev_alloc(s, &s->cells_alloc, bytes);
-    if (rc) return rc;
+    SF_TRY(dev_alloc(s, &s->cells_alloc, bytes));
     s->cells = s->cells_alloc + (size_t)g.PV * 128;        // quad 0 of environment 0 (a guard quad above and below every environment)
     HIPCHK(hipMemsetAsync(s->cells_alloc, 0, bytes, s->stream));
     return SF_OK;
@@ -1586,24 +653,20 @@ static bool prefers_bl(const sf_sim *s)
 // the cell-major copy of the R table(s) the window phase of k_run reads (one sweep after every change of the table)
 static int ensure_rtc(sf_sim *s)
 {
-    if (s->rtc_valid) return SF_OK;
+    if (s->tables.rtc_valid()) return SF_OK;
     const Geo &g = s->g;
-    const size_t n_tab = s->rt_set.size(), tab = (size_t)8 * g.plane_env;
+    const size_t n_tab = (size_t)s->tables.size(), tab = (size_t)8 * g.plane_env;
     if (!s->rtc) {
         // (the copy doubles the handle's largest allocation with per-environment terrain; the window phase it serves is optional: a handle
         // that cannot have it runs without - the caller switches the phase off for the call, results never depend on it)
         if (hipMalloc(reinterpret_cast<void **>(&s->rtc), tab * n_tab * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); s->rtc = nullptr; return SF_ENOTSUP; }
         s->bytes += (int64_t)(tab * n_tab * sizeof(double));
-        s->rtc_stale.assign(n_tab, 1);
     }
-    if (s->rtc_stale.size() != n_tab) s->rtc_stale.assign(n_tab, 1);
     for (size_t i = 0; i < n_tab; ++i)
-        if (s->rtc_stale[i]) {
+        if (s->tables[i].rtc_stale)
             hipLaunchKernelGGL(k_rt_cellmajor, dim3((g.P + 255) / 256, g.H), dim3(256), 0, s->stream, g.H, g.P, (const double *)(s->rt + i * tab), s->rtc + i * tab);
-            s->rtc_stale[i] = 0;
-        }
     HIPCHK(hipGetLastError());
-    s->rtc_valid = true;
+    s->tables.rtc_built();
     return SF_OK;
 }
 
@@ -1611,7 +674,7 @@ static int ensure_bl(sf_sim *s)
 {
     if (s->bl_cur) return SF_OK;
     const Geo &g = s->g;
-    { int rc = alloc_bl(s); if (rc) return rc; }
+    SF_TRY(alloc_bl(s));
     hipLaunchKernelGGL(k_rm_to_bl, dim3((g.PV + 63) / 64, g.H, g.E), dim3(64), 0, s->stream, g, (const uint8_t *)s->status, (const uint8_t *)s->age, s->cells);
     HIPCHK(hipGetLastError());
     s->bl_cur = true;
@@ -1625,10 +688,8 @@ static int ensure_tiles(sf_sim *s)
     if (s->tiles_valid) return SF_OK;
     { int rc0 = ensure_rm(s); if (rc0) return rc0; }
     HIPCHK(hipMemsetAsync(s->tflags, 0, s->tflags_bytes, s->stream));
-    int rc = rebuild_tflags(s, 0, s->g.E);
-    if (rc) return rc;
-    rc = rebuild_seams(s, 0, s->g.E);
-    if (rc) return rc;
+    SF_TRY(rebuild_tflags(s, 0, s->g.E));
+    SF_TRY(rebuild_seams(s, 0, s->g.E));
     s->tiles_valid = true;
     return SF_OK;
 }
@@ -1644,251 +705,7 @@ static int ensure_vbits(sf_sim *s)
     return SF_OK;
 }
 
-// ----------------------------------------------------------------------------- arrival times
-// The pass behind the launches (sf_arrival_kernels.h): reads every environment's update count from commit[], so the step rings are
-// folded first.  Sparse where the blocked plane is current and every plane of the vector bitmap is known to match it, else dense over
-// whichever plane is current.  Recording off: nothing.
-static int arrival_pass(sf_sim *s)
-{
-    if (!s->arrival1) return SF_OK;
-    { int rc0 = ensure_commit(s); if (rc0) return rc0; }
-    const Geo &g = s->g;
-    const bool sparse = s->bl_cur && s->vbits_valid && s->vbits_fl_valid && !s->arr_dense;
-    if (sparse) {
-        hipLaunchKernelGGL(k_arrival_bits, dim3((unsigned)((g.H * g.VW + 255) / 256), (unsigned)g.E), dim3(256), 0, s->stream, g, (const uint8_t *)s->cells,
-                           (const unsigned long long *)s->vbits, (const EnvState *)s->commit, s->arrival1);
-    } else {
-        const dim3 grd((unsigned)((g.W + 255) / 256), (unsigned)g.H, (unsigned)g.E), blk(256);
-        const uint8_t *cells = s->bl_cur ? s->cells : nullptr;
-        if (g.ab == 1) hipLaunchKernelGGL(k_arrival_cells<uint8_t>, grd, blk, 0, s->stream, g, (const uint8_t *)s->age, cells, (const EnvState *)s->commit, s->arrival1);
-        else if (g.ab == 2) hipLaunchKernelGGL(k_arrival_cells<uint16_t>, grd, blk, 0, s->stream, g, (const uint8_t *)s->age, cells, (const EnvState *)s->commit, s->arrival1);
-        else hipLaunchKernelGGL(k_arrival_cells<uint32_t>, grd, blk, 0, s->stream, g, (const uint8_t *)s->age, cells, (const EnvState *)s->commit, s->arrival1);
-    }
-    HIPCHK(hipGetLastError());
-    s->arr_passes[sparse ? 0 : 1]++;
-    s->arr_pending = 0;
-    return s->val_plane ? value_pass(s) : SF_OK;      // the plane is complete up to commit[].steps: so is the damage behind this
-}
-// The plane's per-environment slice behind the n slices env_segs has filled (a reset zeroes it, a fork copies it): appended here and not
-// a kind of sf_env_segs.h - the plane is not one of the buffers the step kernels know.  Returns the new count.
-static int arrival_seg(const sf_sim *s, EnvSeg *seg, int n)
-{
-    if (!s->arrival1) return n;
-    assert(n < kEnvSegs);
-    const long long len = s->g.plane_env * 4;
-    seg[n] = {reinterpret_cast<uint8_t *>(s->arrival1), len, len};
-    return n + 1;
-}
-
-// ----------------------------------------------------------------------------- values at risk
-static ValueArgs value_args(const sf_sim *s)
-{
-    ValueArgs a;
-    a.values = s->val_plane; a.values_env = s->val_per_env ? s->g.plane_env : 0;
-    a.arrival1 = s->arrival1; a.commit = s->commit; a.rec = s->val_rec();
-    return a;
-}
-// The pass behind the arrival pass (sf_value_kernels.h; arrival_pass has folded the step rings and completed the plane): the sum
-// over the window in the sparse form under the arrival pass's own condition, else dense, then the commit of the records.
-static int value_pass(sf_sim *s)
-{
-    const Geo &g = s->g;
-    const bool sparse = s->bl_cur && s->vbits_valid && s->vbits_fl_valid && !s->val_dense;
-    if (sparse) hipLaunchKernelGGL(k_value_bits, dim3((unsigned)((g.H * g.VW + 255) / 256), (unsigned)g.E), dim3(256), 0, s->stream, g,
-                                   (const unsigned long long *)s->vbits, value_args(s));
-    else hipLaunchKernelGGL(k_value_cells, dim3((unsigned)((g.W + 255) / 256), (unsigned)g.H, (unsigned)g.E), dim3(256), 0, s->stream, g, value_args(s));
-    hipLaunchKernelGGL(k_value_commit, dim3((unsigned)((g.E + 255) / 256)), dim3(256), 0, s->stream, g.E, (const EnvState *)s->commit, s->val_rec());
-    HIPCHK(hipGetLastError());
-    s->val_passes[sparse ? 0 : 1]++;
-    return SF_OK;
-}
-// Every record from the arrival plane as it stands (sf_values_set, sf_load_state): records of zeros, then the dense form once over
-// every environment - by the invariant exact for all of them.  A handle that was never reset has nothing to count.
-static int value_recount(sf_sim *s)
-{
-    if (!s->val_plane) return SF_OK;
-    const Geo &g = s->g;
-    HIPCHK(hipMemsetAsync(s->val_rec(), 0, (size_t)g.E * sizeof(ValueRec), s->stream));
-    if (!s->was_reset) return SF_OK;
-    if (s->arr_pending) return arrival_pass(s);       // (a call that failed half way left updates behind: the plane first, the pass behind it counts)
-    { int rc = ensure_commit(s); if (rc) return rc; }
-    hipLaunchKernelGGL(k_value_cells, dim3((unsigned)((g.W + 255) / 256), (unsigned)g.H, (unsigned)g.E), dim3(256), 0, s->stream, g, value_args(s));
-    hipLaunchKernelGGL(k_value_commit, dim3((unsigned)((g.E + 255) / 256)), dim3(256), 0, s->stream, g.E, (const EnvState *)s->commit, s->val_rec());
-    HIPCHK(hipGetLastError());
-    s->val_passes[1]++;
-    return SF_OK;
-}
-// The record's slice behind the arrival plane's (a reset zeroes it: upto1 == 0, the pass behind the reset sums the ignition; a fork
-// copies it with the plane): appended like arrival_seg.  Returns the new count.
-static int value_seg(const sf_sim *s, EnvSeg *seg, int n)
-{
-    if (!s->val_plane) return n;
-    assert(n < kEnvSegs);
-    seg[n] = {reinterpret_cast<uint8_t *>(s->val_rec()), (long long)sizeof(ValueRec), (long long)sizeof(ValueRec)};
-    return n + 1;
-}
-static int value_free(sf_sim *s)
-{
-    if (!s->val_plane) return SF_OK;
-    HIPCHK(hipStreamSynchronize(s->stream));
-    s->bytes -= (int64_t)(s->val_plane_bytes() + s->val_aux_bytes());
-    HIPCHK(hipFree(s->val_plane)); s->val_plane = nullptr;
-    HIPCHK(hipFree(s->val_aux)); s->val_aux = nullptr;
-    s->val_w_on = false;
-    return SF_OK;
-}
-
-extern "C" int sf_values_set(sf_sim *s, const int32_t *values, int32_t per_env, int32_t device_pointer)
-{
-    if (!s) return fail(SF_EINVAL, "sf_values_set: null handle");
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    if (!values) return value_free(s);
-    if (!s->arrival1) return fail(SF_ESTATE, "sf_values_set: call sf_enable_arrival first (the arrival plane says which cells count)");
-    const Geo &g = s->g;
-    const size_t n_planes = per_env ? (size_t)g.E : 1, rows = n_planes * g.H, cells = rows * g.W;
-    if (!device_pointer)
-        for (size_t i = 0; i < cells; ++i)
-            if (values[i] > kValueMax || values[i] < -kValueMax)
-                return fail(SF_EINVAL, "sf_values_set: value %d (entry %lld) is outside -2^24 .. 2^24", values[i], (long long)i);
-    { int rc = check_team_error(s, "sf_values_set"); if (rc) return rc; }
-    // the new plane and, the first time, the records: made and checked before the handle changes (a refused call leaves it as it was)
-    int32_t *plane = nullptr;
-    uint8_t *aux = s->val_aux;
-    const size_t plane_bytes = rows * g.P * sizeof(int32_t);
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&plane), plane_bytes));
-    if (!aux && hipMalloc(reinterpret_cast<void **>(&aux), s->val_aux_bytes()) != hipSuccess) { (void)hipFree(plane); return fail(SF_EHIP, "sf_values_set: hipMalloc failed"); }
-    hipError_t err = hipMemsetAsync(aux, 0, s->val_aux_bytes(), s->stream);      // (records and ticks start from zero under a new plane)
-    if (err == hipSuccess) err = hipMemsetAsync(plane, 0, plane_bytes, s->stream);
-    if (err == hipSuccess) err = hipMemcpy2DAsync(plane, (size_t)g.P * 4, values, (size_t)g.W * 4, (size_t)g.W * 4, rows,
-                                                  device_pointer ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->stream);
-    uint32_t bad = 0;
-    if (err == hipSuccess && device_pointer) {
-        uint32_t *word = reinterpret_cast<uint32_t *>(aux + (size_t)g.E * (sizeof(ValueRec) + 16));
-        hipLaunchKernelGGL(k_value_range, dim3((unsigned)std::min<size_t>((cells + 255) / 256, 4096)), dim3(256), 0, s->stream, values, (long long)cells, word);
-        err = hipGetLastError();
-        if (err == hipSuccess) err = hipMemcpyAsync(&bad, word, sizeof bad, hipMemcpyDeviceToHost, s->stream);
-    }
-    if (err == hipSuccess) err = hipStreamSynchronize(s->stream);      // (the caller's memory is free again; kernels that read the old plane are through)
-    if (err != hipSuccess || bad) {
-        (void)hipFree(plane);
-        if (!s->val_aux) (void)hipFree(aux);
-        else if (s->was_reset) (void)value_recount(s);      // (the records were zeroed above: counted again under the plane that stays)
-        if (bad) return fail(SF_EINVAL, "sf_values_set: a value of the device plane is outside -2^24 .. 2^24");
-        return fail(SF_EHIP, "sf_values_set: %s", hipGetErrorString(err));
-    }
-    if (s->val_plane) { s->bytes -= (int64_t)s->val_plane_bytes(); HIPCHK(hipFree(s->val_plane)); }
-    else s->bytes += (int64_t)s->val_aux_bytes();
-    s->val_plane = plane; s->val_aux = aux; s->val_per_env = per_env != 0;
-    s->bytes += (int64_t)s->val_plane_bytes();
-    { int rc = value_recount(s); if (rc) return rc; }
-    return finish_call(s, nullptr, !s->async, nullptr);
-}
-
-extern "C" int sf_values_get(sf_sim *s, int64_t *damage_out)
-{
-    if (!s || !damage_out) return fail(SF_EINVAL, "sf_values_get: null argument");
-    if (!s->val_plane) return fail(SF_ESTATE, "sf_values_get: call sf_values_set first");
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    HIPCHK(hipMemcpy2DAsync(damage_out, 8, s->val_rec(), sizeof(ValueRec), 8, (size_t)s->g.E, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return check_team_error(s, "sf_values_get");
-}
-
-extern "C" int sf_values_device(sf_sim *s, void **damage, int64_t *damage_stride, void **tick_loss)
-{
-    if (!s || !damage || !damage_stride || !tick_loss) return fail(SF_EINVAL, "sf_values_device: null argument");
-    if (!s->val_plane) return fail(SF_ESTATE, "sf_values_device: call sf_values_set first");
-    *damage = s->val_rec(); *damage_stride = (int64_t)sizeof(ValueRec); *tick_loss = s->val_tick(1);
-    return SF_OK;
-}
-
-extern "C" int sf_values_set_weight(sf_sim *s, float w_value, int32_t on)
-{
-    if (!s) return fail(SF_EINVAL, "sf_values_set_weight: null handle");
-    if (!s->ag.k) return fail(SF_ESTATE, "sf_values_set_weight: call sf_agents_create first");
-    if (!s->val_plane) return fail(SF_ESTATE, "sf_values_set_weight: call sf_values_set first");
-    s->val_w = w_value; s->val_w_on = on != 0;
-    return SF_OK;
-}
-
-extern "C" int sf_set_values_dense(sf_sim *s, int32_t on)
-{
-    if (!s) return fail(SF_EINVAL, "sf_set_values_dense: null handle");
-    s->val_dense = on != 0;
-    return SF_OK;
-}
-
-extern "C" int sf_get_value_passes(sf_sim *s, int64_t *out)
-{
-    if (!s || !out) return fail(SF_EINVAL, "sf_get_value_passes: null argument");
-    out[0] = s->val_passes[0]; out[1] = s->val_passes[1];
-    return SF_OK;
-}
-
-// ----------------------------------------------------------------------------- ensemble statistics
-// One launch of k_ensemble (sf_ensemble_kernels.h) over the arrival plane as it stands: the call converts no plane, folds no ring and
-// looks at no result row - it reads arrival1 (complete behind every stepping call) and the value plane, and writes the caller's outputs.
-template <int TP>
-static void ensemble_launch(bool loss, dim3 grd, hipStream_t st, const EnsArgs &a)
-{
-    if (loss) hipLaunchKernelGGL((k_ensemble<TP, true>), grd, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((k_ensemble<TP, false>), grd, dim3(256), 0, st, a);
-}
-
-extern "C" int sf_ensemble_stats(sf_sim *s, const sf_ensemble_params *p, const int32_t *members, const sf_ensemble_out *out)
-{
-    if (!s || !p || !members || !out) return fail(SF_EINVAL, "sf_ensemble_stats: null argument");
-    if (!out->count && !out->prob && !out->first && !out->mean && !out->loss) return fail(SF_EINVAL, "sf_ensemble_stats: no output asked for");
-    const Geo &g = s->g;
-    const int G = p->n_groups, K = p->group_size, T = p->n_horizons;
-    if (G < 1 || K < 1 || K > 65535 || (long long)G * K > (1LL << 20))
-        return fail(SF_EINVAL, "sf_ensemble_stats: %d groups of %d members (G >= 1, 1 <= K <= 65535, G * K <= 2^20)", G, K);
-    if (T < 1 || T > SF_ENS_MAX_HORIZONS) return fail(SF_EINVAL, "sf_ensemble_stats: %d horizons (1..%d)", T, SF_ENS_MAX_HORIZONS);
-    if (p->reserved != 0) return fail(SF_EINVAL, "sf_ensemble_stats: reserved must be 0");
-    for (int t = 0; t < T; ++t) {
-        const int h = p->horizons[t];
-        if (h < -1 || (h == -1 && t != T - 1)) return fail(SF_EINVAL, "sf_ensemble_stats: horizon %d is %d (>= 0; -1, no limit, only last)", t, h);
-        if (t > 0 && h != -1 && h <= p->horizons[t - 1]) return fail(SF_EINVAL, "sf_ensemble_stats: the horizons are not strictly ascending (%d behind %d)", h, p->horizons[t - 1]);
-    }
-    if (((uintptr_t)out->count | (uintptr_t)out->prob | (uintptr_t)out->first | (uintptr_t)out->mean) & 3 || ((uintptr_t)out->loss & 7))
-        return fail(SF_EINVAL, "sf_ensemble_stats: an output is not aligned to its element");
-    { int rc = check_envs(s, "sf_ensemble_stats", G * K, members); if (rc) return rc; }
-    if (!s->arrival1) return fail(SF_ESTATE, "sf_ensemble_stats: call sf_enable_arrival first (the statistics are read off the arrival plane)");
-    if (out->loss && !s->val_plane) return fail(SF_ESTATE, "sf_ensemble_stats: loss needs a value plane (sf_values_set)");
-    { int rc = begin_call(s, "sf_ensemble_stats", kNotVoid); if (rc) return rc; }
-
-    const size_t bytes = (size_t)G * K * sizeof(int32_t);
-    CallBlock &blk = s->ens_blk;
-    { int rc = block_reserve(s, blk, bytes); if (rc) return rc; }
-    memcpy(blk.pinned, members, bytes);
-    { int rc = block_send(s, blk, bytes); if (rc) return rc; }
-
-    EnsArgs a;
-    memset(&a, 0, sizeof a);
-    a.arrival1 = s->arrival1; a.plane_env = g.plane_env;
-    a.H = g.H; a.W = g.W; a.P = g.P; a.Q = (g.W + 3) / 4;
-    a.members = reinterpret_cast<const int32_t *>(blk.dev);
-    a.G = G; a.K = K; a.T = T;
-    int TP = 1;
-    while (TP < T) TP *= 2;
-    for (int t = 0; t < SF_ENS_MAX_HORIZONS; ++t) {
-        const int h = p->horizons[std::min(t, T - 1)];
-        a.hz[t] = h < 0 ? 0xFFFFFFFEu : (uint32_t)h;
-    }
-    if (out->loss) { a.values = s->val_plane; a.values_env = s->val_per_env ? g.plane_env : 0; }
-    a.vec = g.W % 4 == 0 && !(((uintptr_t)out->count | (uintptr_t)out->prob | (uintptr_t)out->first | (uintptr_t)out->mean) & 15);
-    a.count = out->count; a.prob = out->prob; a.first = out->first; a.mean = out->mean;
-    a.loss = reinterpret_cast<unsigned long long *>(out->loss);
-    if (out->loss) HIPCHK(hipMemsetAsync(out->loss, 0, (size_t)G * T * sizeof(int64_t), s->stream));
-    const long long quads = (long long)g.H * a.Q;
-    const dim3 grd((unsigned)((quads + 255) / 256), (unsigned)std::min(G, kEnsGroupsY), (unsigned)((G + kEnsGroupsY - 1) / kEnsGroupsY));
-    const bool loss = out->loss != nullptr;
-    if (TP == 1) ensemble_launch<1>(loss, grd, s->stream, a);
-    else if (TP == 2) ensemble_launch<2>(loss, grd, s->stream, a);
-    else if (TP == 4) ensemble_launch<4>(loss, grd, s->stream, a);
-    else ensemble_launch<8>(loss, grd, s->stream, a);
-    return finish_call(s, "sf_ensemble_stats", !s->async, nullptr);
-}
+#include "sf_host_views.h"
 
 extern "C" int sf_last_step_launch(sf_sim *s, int32_t *kind)
 {
@@ -2063,22 +880,22 @@ static TeamGeo join_geometry(const sf_sim *s)
 static int team_buffers(sf_sim *s, const TeamGeo &t)
 {
     const Geo &g = s->g;
-    if (!s->team_tab || s->team_slots < t.slots) {
-        if (s->team_tab) { HIPCHK(hipFree(s->team_tab)); s->team_tab = nullptr; }
-        { int rc = dev_alloc(s, &s->team_tab, (size_t)t.slots); if (rc) return rc; }
-        s->team_slots = t.slots;
-        s->team_plan_ones = 0;
+    if (!s->team.tab || s->team.slots < t.slots) {
+        if (s->team.tab) { HIPCHK(hipFree(s->team.tab)); s->team.tab = nullptr; }
+        SF_TRY(dev_alloc(s, &s->team.tab, (size_t)t.slots));
+        s->team.slots = t.slots;
+        s->team.plan_ones = 0;
     }
-    if (!s->xg) {
-        int rc = dev_alloc(s, &s->xg, (size_t)g.E * kTeamMax * 3); if (rc) return rc;
-        rc = dev_alloc(s, &s->xbuf, (size_t)g.E * kTeamMax * 4 * team_xrow(g)); if (rc) return rc;
-        rc = dev_alloc(s, &s->xdone, (size_t)2 * g.E + 1); if (rc) return rc;       // members that have left [E] | the teams' start words [E] | teams that started as one
-        HIPCHK(hipMemsetAsync(s->xdone, 0, sizeof(uint32_t) * ((size_t)2 * g.E + 1), s->stream));
-        rc = dev_alloc(s, &s->team_size, (size_t)g.E); if (rc) return rc;
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&s->xerr_pinned), sizeof(uint32_t), hipHostMallocMapped));
-        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&s->xerr_mapped), s->xerr_pinned, 0));
-        *s->xerr_pinned = 0;
-        HIPCHK(hipMemsetAsync(s->xbuf, 0, (size_t)g.E * kTeamMax * 4 * team_xrow(g), s->stream));
+    if (!s->team.xg) {
+        SF_TRY(dev_alloc(s, &s->team.xg, (size_t)g.E * kTeamMax * 3));
+        SF_TRY(dev_alloc(s, &s->team.xbuf, (size_t)g.E * kTeamMax * 4 * team_xrow(g)));
+        SF_TRY(dev_alloc(s, &s->team.xdone, (size_t)2 * g.E + 1));       // members that have left [E] | the teams' start words [E] | teams that started as one
+        HIPCHK(hipMemsetAsync(s->team.xdone, 0, sizeof(uint32_t) * ((size_t)2 * g.E + 1), s->stream));
+        SF_TRY(dev_alloc(s, &s->team.size, (size_t)g.E));
+        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&s->team.xerr_pinned), sizeof(uint32_t), hipHostMallocMapped));
+        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&s->team.xerr_mapped), s->team.xerr_pinned, 0));
+        *s->team.xerr_pinned = 0;
+        HIPCHK(hipMemsetAsync(s->team.xbuf, 0, (size_t)g.E * kTeamMax * 4 * team_xrow(g), s->stream));
     }
     return SF_OK;
 }
@@ -2088,7 +905,7 @@ static int team_buffers(sf_sim *s, const TeamGeo &t)
 static void team_args(const sf_sim *s, StepArgs &a, int rcap, uint32_t *cost)
 {
     a.cost = cost;
-    a.team_tab = s->team_tab; a.xg = s->xg; a.xbuf = s->xbuf; a.xdone = s->xdone; a.xerr = s->xerr_mapped;
+    a.team_tab = s->team.tab; a.xg = s->team.xg; a.xbuf = s->team.xbuf; a.xdone = s->team.xdone; a.xerr = s->team.xerr_mapped;
     a.xrow = team_xrow(s->g); a.team_rcap = rcap;
     // placement of the members: 0 (default) = the slots of one XCD, 1 = consecutive slots (eight XCDs in turn), 2 = as 0 but the
     // hand-off written through as if they were apart - results never depend on it (tests run all three)
@@ -2099,19 +916,19 @@ static void team_args(const sf_sim *s, StepArgs &a, int rcap, uint32_t *cost)
 static int launch_k_run_join(sf_sim *s, StepArgs &a, int n_steps, const TeamGeo &t, bool eager)
 {
     const Geo &g = s->g;
-    { int rc = team_buffers(s, t); if (rc) return rc; }
-    if (!s->xj) {
-        int rc = dev_alloc(s, &s->xj, (size_t)3 * g.E + 2); if (rc) return rc;
-        rc = dev_alloc(s, &s->xcut, (size_t)g.E); if (rc) return rc;
-        rc = dev_alloc(s, &s->jlog, (size_t)1 + 3 * kJoinLog); if (rc) return rc;
+    SF_TRY(team_buffers(s, t));
+    if (!s->team.xj) {
+        SF_TRY(dev_alloc(s, &s->team.xj, (size_t)3 * g.E + 2));
+        SF_TRY(dev_alloc(s, &s->team.xcut, (size_t)g.E));
+        SF_TRY(dev_alloc(s, &s->team.jlog, (size_t)1 + 3 * kJoinLog));
     }
-    HIPCHK(hipMemsetAsync(s->jlog, 0, sizeof(uint32_t), s->stream));
-    s->jlog_valid = true;
-    hipLaunchKernelGGL(k_team_plan, dim3(1), dim3(1024), 0, s->stream, g.E, t.slots, 1, 1, 0u, 0u, 1, s->run_cost, s->team_tab, s->team_size, s->xg, s->xdone, 0,
-                       s->xj, s->xcut);
-    s->team_plan_ones = 0;             // (this plan spreads the environments over the XCDs: not the table a launch of fixed teams of one keeps)
+    HIPCHK(hipMemsetAsync(s->team.jlog, 0, sizeof(uint32_t), s->stream));
+    s->team.jlog_valid = true;
+    hipLaunchKernelGGL(k_team_plan, dim3(1), dim3(1024), 0, s->stream, g.E, t.slots, 1, 1, 0u, 0u, 1, s->run_cost, s->team.tab, s->team.size, s->team.xg, s->team.xdone, 0,
+                       s->team.xj, s->team.xcut);
+    s->team.plan_ones = 0;             // (this plan spreads the environments over the XCDs: not the table a launch of fixed teams of one keeps)
     team_args(s, a, 0, s->run_cost);
-    a.xj = s->xj; a.xcut = s->xcut; a.tsize = s->team_size; a.jlog = s->jlog;
+    a.xj = s->team.xj; a.xcut = s->team.xcut; a.tsize = s->team.size; a.jlog = s->team.jlog;
     // (k_team_plan's model of a team: the chain no member's update gets shorter than, what belonging to a team costs per update; eager - tests -:
     // every workgroup that is free joins whatever runs)
     // Where the newcomers come from: the environment's own XCD (default: the team's step boundaries and cuts stay in one L2 - measured on C3, 1000 updates:
@@ -2128,7 +945,7 @@ static int launch_k_run_join(sf_sim *s, StepArgs &a, int n_steps, const TeamGeo 
 static int launch_k_run_team(sf_sim *s, StepArgs &a, int n_steps, const TeamGeo &t, int t_min, int t_max, int steps_before, bool keep_cost = false)
 {
     const Geo &g = s->g;
-    { int rc = team_buffers(s, t); if (rc) return rc; }
+    SF_TRY(team_buffers(s, t));
     // what a member pays per step for belonging to a team (publish, wait for the slowest member, read: ~6.5 k clocks measured) and the
     // latency chain no member's step gets shorter than (~12 k clocks), in the unit of the cost array
     const uint32_t ovh = (uint32_t)((long long)(steps_before > 0 ? steps_before : 0) * 6500 / 16);
@@ -2139,10 +956,10 @@ static int launch_k_run_team(sf_sim *s, StepArgs &a, int n_steps, const TeamGeo 
     // (k_team_plan + the gap behind it: ~5 us of a 57 us call).
     const int scatter = s->tune.v[SF_TUNE_TEAM_PLACEMENT] == 1 ? 1 : 0;
     const long long ones_key = (t_min == 1 && t_max == 1) ? 1 + (long long)scatter + 2ll * t.slots + ((long long)g.E << 32) : 0;
-    if (!ones_key || s->team_plan_ones != ones_key)
+    if (!ones_key || s->team.plan_ones != ones_key)
         hipLaunchKernelGGL(k_team_plan, dim3(1), dim3(1024), 0, s->stream, g.E, t.slots, t_min, t_max, ovh, floor_c, scatter,
-                           s->run_cost, s->team_tab, s->team_size, s->xg, s->xdone, keep_cost ? 1 : 0, (uint32_t *)nullptr, (unsigned long long *)nullptr);
-    s->team_plan_ones = ones_key;
+                           s->run_cost, s->team.tab, s->team.size, s->team.xg, s->team.xdone, keep_cost ? 1 : 0, (uint32_t *)nullptr, (unsigned long long *)nullptr);
+    s->team.plan_ones = ones_key;
     team_args(s, a, t.rcap, keep_cost ? nullptr : s->run_cost);
     const int words = run_words(t.rcap ? t.rcap : g.H, t.waves, g.VW);
     return launch_run(s, run_key(g, kRunTeam, words, a.mit != nullptr), (unsigned)t.slots, (unsigned)t.waves * 64, t.lds, a, n_steps, t.vcap, 64);
@@ -2530,26 +1347,26 @@ static int enqueue_steps(sf_sim *s, StepPlan p, int n_steps, const int32_t *mit_
 // max_fire_duration updates only.  t0 then stands in front of all the pieces.
 static int enqueue_call(sf_sim *s, const StepPlan &p, int n_steps, const int32_t *mit_dev, int mit_k, bool hold, hipEvent_t t0)
 {
-    if (!s->wind_sched.empty()) {          // a wind schedule is set: the tables that are due, in front of the call's first piece
+    if (!s->wind.sched.empty()) {          // a wind schedule is set: the tables that are due, in front of the call's first piece
         int rc0 = wind_sched_pass(s);
         if (rc0) return rc0;
     }
-    if (!s->arrival1) return enqueue_steps(s, p, n_steps, mit_dev, mit_k, t0);
+    if (!s->arrival.plane) return enqueue_steps(s, p, n_steps, mit_dev, mit_k, t0);
     const Geo &g = s->g;
     int rc = SF_OK, launches = 0;
     if (t0 && hipEventRecord(t0, s->stream) != hipSuccess) rc = fail(SF_EHIP, "sf_step: hipEventRecord failed");
     for (int done = 0; done < n_steps && !rc;) {
-        if (s->arr_pending >= g.md) { rc = arrival_pass(s); continue; }      // (a call that failed half way left them behind)
-        const int room = g.md - s->arr_pending;
+        if (s->arrival.pending >= g.md) { rc = arrival_pass(s); continue; }      // (a call that failed half way left them behind)
+        const int room = g.md - s->arrival.pending;
         const int pieces = (n_steps - done + room - 1) / room;
         const int c = hold ? std::min(n_steps - done, room) : (n_steps - done + pieces - 1) / pieces;
         const StepPlan pc = c == n_steps ? p : plan_step(s, c, mit_dev != nullptr);
         if (mit_dev && !pc.nw) { rc = fail(SF_EHIP, "sf_step_mitigated: a piece of %d updates was not planned as a resident launch", c); break; }
         rc = enqueue_steps(s, pc, c, mit_dev ? mit_dev + (size_t)done * g.E * mit_k * 3 : nullptr, mit_k, nullptr);
         launches += s->last_launches;
-        s->arr_pending += c;
+        s->arrival.pending += c;
         done += c;
-        if (!rc && (!hold || s->arr_pending >= g.md)) rc = arrival_pass(s);      // behind every piece; a caller that holds: every md updates
+        if (!rc && (!hold || s->arrival.pending >= g.md)) rc = arrival_pass(s);      // behind every piece; a caller that holds: every md updates
     }
     s->last_launches = launches;
     s->last_was_step1 = n_steps == 1 && !mit_dev;
@@ -2569,125 +1386,9 @@ static int step_call(sf_sim *s, const char *who, int n_steps, float *ms)
     if (n_steps < 0) return fail(SF_EINVAL, "%s: n_steps must be >= 0", who);
     if (ms) *ms = 0.f;
     if (n_steps == 0) return check_ready(s, who, kNeedRt | kNeedReset);
-    { int rc = begin_call(s, who, kNeedRt | kNeedReset); if (rc) return rc; }
-    { int rc = step_impl(s, n_steps, false, ms ? s->ev0 : nullptr); if (rc) return rc; }
+    SF_TRY(begin_call(s, who, kNeedRt | kNeedReset));
+    SF_TRY(step_impl(s, n_steps, false, ms ? s->ev0 : nullptr));
     return finish_call(s, who, !s->async, ms);
-}
-
-// The per-update history FireSimulation._save_data appends to fire_map.npy (simulation.py:548-549,
-// 887-959: int8 [T, H, W], one map after every executed update), recorded on the device.
-extern "C" int sf_enable_history(sf_sim *s, int32_t capacity)
-{
-    if (!s) return fail(SF_EINVAL, "sf_enable_history: null handle");
-    if (capacity < 0) return fail(SF_EINVAL, "sf_enable_history: capacity must be >= 0");
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    HIPCHK(hipStreamSynchronize(s->stream));
-    const size_t per = (size_t)s->g.E * s->g.H * s->g.W;
-    if (s->history) { HIPCHK(hipFree(s->history)); s->bytes -= (int64_t)(per * s->history_cap); }
-    s->history = nullptr; s->history_cap = 0;
-    if (capacity == 0) return SF_OK;
-    HIPCHK(hipMalloc((void **)&s->history, per * capacity));
-    s->bytes += (int64_t)(per * capacity);
-    s->history_cap = capacity;
-    HIPCHK(hipMemsetAsync(s->history, 0, per * capacity, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return SF_OK;
-}
-
-extern "C" int sf_get_history(sf_sim *s, int32_t env, int32_t first, int32_t count, int8_t *out)
-{
-    if (!s || !out) return fail(SF_EINVAL, "sf_get_history: null argument");
-    if (!s->history) return fail(SF_ESTATE, "sf_get_history: call sf_enable_history first");
-    if (env < 0 || env >= s->g.E) return fail(SF_EINVAL, "sf_get_history: environment %d out of range", env);
-    if (first < 0 || count < 0 || count > s->history_cap)
-        return fail(SF_EINVAL, "sf_get_history: %d updates from %d do not fit the capacity %d", count, first, s->history_cap);
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    const size_t map = (size_t)s->g.H * s->g.W;
-    const int8_t *base = s->history + (size_t)env * s->history_cap * map;
-    const int slot = first % s->history_cap;
-    const int n1 = count < s->history_cap - slot ? count : s->history_cap - slot;    // up to the end of the ring
-    if (n1) HIPCHK(hipMemcpyAsync(out, base + (size_t)slot * map, (size_t)n1 * map, hipMemcpyDeviceToHost, s->stream));
-    if (count > n1) HIPCHK(hipMemcpyAsync(out + (size_t)n1 * map, base, (size_t)(count - n1) * map, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return SF_OK;
-}
-
-extern "C" int sf_history_device(sf_sim *s, void **ptr, int32_t *capacity)
-{
-    if (!s || !ptr || !capacity) return fail(SF_EINVAL, "sf_history_device: null argument");
-    *ptr = s->history; *capacity = s->history_cap;
-    return SF_OK;
-}
-
-// Arrival times: which update created the first sprite of a cell (fire.py:571-587), kept by a pass behind the
-// step launches (arrival_pass; enqueue_call cuts a call into pieces of at most max_fire_duration updates while this is on).
-extern "C" int sf_enable_arrival(sf_sim *s, int32_t on)
-{
-    if (!s) return fail(SF_EINVAL, "sf_enable_arrival: null handle");
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    const size_t n = (size_t)s->g.E * s->g.plane_env;
-    if (!on) {
-        if (!s->arrival1) return SF_OK;
-        if (s->val_plane) return fail(SF_ESTATE, "sf_enable_arrival: a value plane is set and needs the arrival plane: switch it off first (sf_values_set with NULL)");
-        HIPCHK(hipStreamSynchronize(s->stream));
-        HIPCHK(hipFree(s->arrival1));
-        s->arrival1 = nullptr;
-        s->bytes -= (int64_t)(n * sizeof(uint32_t));
-        return SF_OK;
-    }
-    if (s->arrival1) return SF_OK;
-    { int rc = dev_alloc(s, &s->arrival1, n); if (rc) return rc; }
-    HIPCHK(hipMemsetAsync(s->arrival1, 0, n * sizeof(uint32_t), s->stream));
-    s->arr_pending = 0;
-    if (s->was_reset) { int rc = arrival_pass(s); if (rc) return rc; }      // the sprites that are live now carry their true updates
-    return finish_call(s, nullptr, !s->async, nullptr);
-}
-
-extern "C" int sf_get_arrival(sf_sim *s, int32_t env, int32_t *out)
-{
-    if (!s || !out) return fail(SF_EINVAL, "sf_get_arrival: null argument");
-    if (!s->arrival1) return fail(SF_ESTATE, "sf_get_arrival: call sf_enable_arrival first");
-    const Geo &g = s->g;
-    if (env < 0 || env >= g.E) return fail(SF_EINVAL, "sf_get_arrival: environment %d out of range", env);
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    HIPCHK(hipMemcpy2DAsync(out, (size_t)g.W * 4, s->arrival1 + (size_t)env * g.plane_env, (size_t)g.P * 4, (size_t)g.W * 4, (size_t)g.H,
-                            hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    { int rc = check_team_error(s, "sf_get_arrival"); if (rc) return rc; }
-    for (size_t i = 0, n = (size_t)g.H * g.W; i < n; ++i) out[i] -= 1;      // stored: update + 1, 0 = never
-    return SF_OK;
-}
-
-extern "C" int sf_arrival_device(sf_sim *s, void **ptr, int64_t *row_pitch, int64_t *env_stride)
-{
-    if (!s || !ptr || !row_pitch || !env_stride) return fail(SF_EINVAL, "sf_arrival_device: null argument");
-    if (!s->arrival1) return fail(SF_ESTATE, "sf_arrival_device: call sf_enable_arrival first");
-    *ptr = s->arrival1; *row_pitch = (int64_t)s->g.P * 4; *env_stride = (int64_t)s->g.plane_env * 4;
-    return SF_OK;
-}
-
-extern "C" int sf_set_arrival_dense(sf_sim *s, int32_t on)
-{
-    if (!s) return fail(SF_EINVAL, "sf_set_arrival_dense: null handle");
-    s->arr_dense = on != 0;
-    return SF_OK;
-}
-
-extern "C" int sf_time_arrival_pass(sf_sim *s, float *ms_out)
-{
-    if (!s || !ms_out) return fail(SF_EINVAL, "sf_time_arrival_pass: null argument");
-    if (!s->arrival1) return fail(SF_ESTATE, "sf_time_arrival_pass: call sf_enable_arrival first");
-    { int rc = begin_call(s, "sf_time_arrival_pass", kCommit); if (rc) return rc; }      // (the commit is not part of the pass's time)
-    HIPCHK(hipEventRecord(s->ev0, s->stream));
-    { int rc = arrival_pass(s); if (rc) return rc; }
-    return finish_call(s, nullptr, true, ms_out);
-}
-
-extern "C" int sf_get_arrival_passes(sf_sim *s, int64_t *out)
-{
-    if (!s || !out) return fail(SF_EINVAL, "sf_get_arrival_passes: null argument");
-    out[0] = s->arr_passes[0]; out[1] = s->arr_passes[1];
-    return SF_OK;
 }
 
 #ifdef SF_PHASES
@@ -2798,10 +1499,10 @@ extern "C" int sf_step_mitigated(sf_sim *s, int32_t n_steps, const int32_t *pts,
     if (ms_out) *ms_out = 0.f;
     if (n_steps == 0) return SF_OK;
     if (k == 0) return step_call(s, who, n_steps, ms_out);
-    { int rc = begin_call(s, who, kNeedRt | kNeedReset); if (rc) return rc; }
+    SF_TRY(begin_call(s, who, kNeedRt | kNeedReset));
     const StepPlan plan = plan_step(s, n_steps, true);       // can the resident launch take the lines?  Otherwise scatter + step pairs
     const int32_t *blk = nullptr;
-    { int rc = stage_lines(s, n_steps, pts, k, device_pointer, &blk); if (rc) return rc; }
+    SF_TRY(stage_lines(s, n_steps, pts, k, device_pointer, &blk));
     if (plan.nw) {
         const int rc = enqueue_call(s, plan, n_steps, blk, k, false, ms_out ? s->ev0 : nullptr);
         return rc ? rc : finish_call(s, who, !s->async, ms_out);
@@ -2813,7 +1514,7 @@ extern "C" int sf_step_mitigated(sf_sim *s, int32_t n_steps, const int32_t *pts,
         if (rc) return rc;
         if (ms_out) *ms_out += ms1;
     }
-    if (s->arr_pending) { int rc = arrival_pass(s); if (rc) return rc; }
+    if (s->arrival.pending) SF_TRY(arrival_pass(s));
     return finish_call(s, who, !s->async, nullptr);
 }
 
@@ -2825,18 +1526,18 @@ static int loop_launch(sf_sim *s)
 {
     const Geo &g = s->g;
     StepArgs a = handle_args(s);
-    a.mit = s->loop_pts_mem; a.mit_k = s->loop_k;
+    a.mit = s->loop.pts_mem; a.mit_k = s->loop.k;
     a.res_block = s->status_block; a.res_elapsed = s->elapsed_dev; a.res_sink = s->sink;
     a.cost = s->run_cost;
-    a.loop_db = s->loop_db_dev; a.loop_pts_host = s->loop_pts_dev; a.loop_res_host = s->loop_res_dev;
-    a.loop_seq = s->loop_mem; a.loop_done = s->loop_mem + 32; a.loop_pts = s->loop_pts_mem;
+    a.loop_db = s->loop.db_dev; a.loop_pts_host = s->loop.pts_dev; a.loop_res_host = s->loop.res_dev;
+    a.loop_seq = s->loop.mem; a.loop_done = s->loop.mem + 32; a.loop_pts = s->loop.pts_mem;
     a.loop_timeout = 400000000ull;             // ~0.2 s without a ring: the workgroups leave, the next sf_loop_step starts them again
-    HIPCHK(hipMemsetAsync(s->loop_mem, 0, sizeof(uint32_t), s->stream));       // nothing forwarded yet (the word may hold the stop of the launch before)
+    HIPCHK(hipMemsetAsync(s->loop.mem, 0, sizeof(uint32_t), s->stream));       // nothing forwarded yet (the word may hold the stop of the launch before)
     // one 16-wave workgroup per environment - or the light loop's 8-wave one (SF_TUNE_LOOP_LIGHT)
-    const int nw_cap = s->loop_light ? 8 : 16;
+    const int nw_cap = s->loop.light ? 8 : 16;
     const int nw = (g.H + 63) / 64 < nw_cap ? (g.H + 63) / 64 : nw_cap;
     long long all_vec = (long long)g.H * g.PV;
-    int vcap = s->loop_light ? 1024 : 4096;
+    int vcap = s->loop.light ? 1024 : 4096;
     if (vcap > all_vec) vcap = (int)((all_vec + 63) / 64 * 64);
     const size_t lds = run_lds_bytes(g, nw, vcap);
     // (8 waves on up to 1024 rows: two bitmap rows per thread, k_run<2, ...>)
@@ -2856,14 +1557,14 @@ extern "C" int sf_loop_start(sf_sim *s, int32_t k)
     // sleeping loop.  (A stream with a CU mask - hipExtStreamCreateWithCUMask - was tried first: such a stream is a BLOCKING one, a kernel
     // on torch's default stream then waits for the resident loop to leave; profiles/cu_mask_probe.hip has the mask's numbering.)
     const int light = s->tune.v[SF_TUNE_LOOP_LIGHT] > 0 ? 1 : 0;
-    if (!s->wind_sched.empty()) return fail(SF_ENOTSUP, "sf_loop_start: not while a wind schedule is set (sf_set_wind_schedule): a closed loop has no call boundary for the wind to change at");
-    if (s->arrival1) return fail(SF_ENOTSUP, "sf_loop_start: not while arrival times are recorded (sf_enable_arrival): a closed loop has no launch boundary for the pass");
+    if (!s->wind.sched.empty()) return fail(SF_ENOTSUP, "sf_loop_start: not while a wind schedule is set (sf_set_wind_schedule): a closed loop has no call boundary for the wind to change at");
+    if (s->arrival.plane) return fail(SF_ENOTSUP, "sf_loop_start: not while arrival times are recorded (sf_enable_arrival): a closed loop has no launch boundary for the pass");
     if (g.ab != 1 || s->generic || g.VW != 1 || s->graph_on || s->history || g.dense || g.H > 16 * 64 || g.E > s->n_cu ||
         (s->fused_mode >= 0 && s->fused_mode != 2))
         return fail(SF_ENOTSUP, "sf_loop_start: needs the environment-resident launch with every environment resident at once "
                                 "(grids up to 1024 x 1024, max_fire_duration <= 5, no more environments than CUs, no spread graph / history)");
     LOOP_QUIESCE(s);                   // (a refused call leaves a running loop running)
-    s->loop_light = light;
+    s->loop.light = light;
     { int rc0 = ensure_commit(s); if (rc0) return rc0; }
     { int rc0 = ensure_vbits(s); if (rc0) return rc0; }
     { int rc0 = ensure_bl(s); if (rc0) return rc0; }
@@ -2873,35 +1574,35 @@ extern "C" int sf_loop_start(sf_sim *s, int32_t k)
         memset(*host, 0, bytes);
         return SF_OK;
     };
-    if (!s->loop_db) {
-        int rc = pin((void **)&s->loop_db, (void **)&s->loop_db_dev, sizeof(uint32_t) * 64); if (rc) return rc;
-        rc = pin((void **)&s->loop_res, (void **)&s->loop_res_dev, (size_t)64 * g.E); if (rc) return rc;
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&s->loop_mem), sizeof(uint32_t) * (32 + (size_t)g.E)));
+    if (!s->loop.db) {
+        SF_TRY(pin((void **)&s->loop.db, (void **)&s->loop.db_dev, sizeof(uint32_t) * 64));
+        SF_TRY(pin((void **)&s->loop.res, (void **)&s->loop.res_dev, (size_t)64 * g.E));
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&s->loop.mem), sizeof(uint32_t) * (32 + (size_t)g.E)));
     }
-    s->loop_slot_ints = (size_t)g.E * k * 4;        // a slot of the points ring: 16-byte pieces (column, row, type, the step's number)
-    const size_t pts_bytes = sizeof(int32_t) * 2 * (s->loop_slot_ints ? s->loop_slot_ints : 4);
-    if (pts_bytes > s->loop_pts_cap) {
-        if (s->loop_pts) HIPCHK(hipHostFree(s->loop_pts));
-        if (s->loop_pts_mem) HIPCHK(hipFree(s->loop_pts_mem));
-        s->loop_pts = nullptr; s->loop_pts_mem = nullptr; s->loop_pts_cap = 0;
-        int rc = pin((void **)&s->loop_pts, (void **)&s->loop_pts_dev, pts_bytes); if (rc) return rc;
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&s->loop_pts_mem), pts_bytes));
-        s->loop_pts_cap = pts_bytes;
+    s->loop.slot_ints = (size_t)g.E * k * 4;        // a slot of the points ring: 16-byte pieces (column, row, type, the step's number)
+    const size_t pts_bytes = sizeof(int32_t) * 2 * (s->loop.slot_ints ? s->loop.slot_ints : 4);
+    if (pts_bytes > s->loop.pts_cap) {
+        if (s->loop.pts) HIPCHK(hipHostFree(s->loop.pts));
+        if (s->loop.pts_mem) HIPCHK(hipFree(s->loop.pts_mem));
+        s->loop.pts = nullptr; s->loop.pts_mem = nullptr; s->loop.pts_cap = 0;
+        SF_TRY(pin((void **)&s->loop.pts, (void **)&s->loop.pts_dev, pts_bytes));
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&s->loop.pts_mem), pts_bytes));
+        s->loop.pts_cap = pts_bytes;
     }
-    s->loop_k = k; s->loop_seq = 0; s->loop_restarts = 0;
-    volatile uint32_t *db = s->loop_db;
+    s->loop.k = k; s->loop.seq = 0; s->loop.restarts = 0;
+    volatile uint32_t *db = s->loop.db;
     for (int i = 0; i < 64; ++i) db[i] = 0;
-    memset(s->loop_res, 0, (size_t)64 * g.E);
-    memset(s->loop_pts, 0, pts_bytes);             // (pieces of an earlier loop carry ITS step numbers)
+    memset(s->loop.res, 0, (size_t)64 * g.E);
+    memset(s->loop.pts, 0, pts_bytes);             // (pieces of an earlier loop carry ITS step numbers)
     __sync_synchronize();
-    HIPCHK(hipMemsetAsync(s->loop_mem, 0, sizeof(uint32_t) * (32 + (size_t)g.E), s->stream));
-    HIPCHK(hipMemsetAsync(s->loop_pts_mem, 0, pts_bytes, s->stream));
+    HIPCHK(hipMemsetAsync(s->loop.mem, 0, sizeof(uint32_t) * (32 + (size_t)g.E), s->stream));
+    HIPCHK(hipMemsetAsync(s->loop.pts_mem, 0, pts_bytes, s->stream));
     if (s->tdirty_all) HIPCHK(hipMemsetAsync(s->tdirty, 1, s->n_tiles_max, s->stream));
     s->tdirty_all = false;
     s->status_fresh = false;
     { int rc0 = loop_launch(s); if (rc0) return rc0; }
     HIPCHK(hipGetLastError());
-    s->loop_on = true;
+    s->loop.on = true;
     s->tiles_valid = false;
     s->last_kind = 2;
     return SF_OK;
@@ -2912,26 +1613,26 @@ extern "C" int sf_loop_start(sf_sim *s, int32_t k)
 extern "C" int sf_loop_step(sf_sim *s, const int32_t *pts, int32_t *status_out, double *elapsed_out)
 {
     if (!s) return fail(SF_EINVAL, "sf_loop_step: null handle");
-    if (!s->loop_on) return fail(SF_ESTATE, "sf_loop_step: call sf_loop_start first");
+    if (!s->loop.on) return fail(SF_ESTATE, "sf_loop_step: call sf_loop_start first");
     const Geo &g = s->g;
-    const uint32_t seq = s->loop_seq + 1;
+    const uint32_t seq = s->loop.seq + 1;
     if (seq >= 0x7FFFFFF0u) return fail(SF_ESTATE, "sf_loop_step: sequence numbers exhausted; sf_loop_stop and start again");
-    if (s->loop_k > 0) {
+    if (s->loop.k > 0) {
         // the points are their own doorbell: 16-byte pieces that carry the step's number, each written by ONE 16-byte store (the relay takes a
         // piece when it carries the number it waits for)
-        __m128i *slot = reinterpret_cast<__m128i *>(s->loop_pts + (size_t)(seq & 1u) * s->loop_slot_ints);
-        const size_t n = (size_t)g.E * s->loop_k;
+        __m128i *slot = reinterpret_cast<__m128i *>(s->loop.pts + (size_t)(seq & 1u) * s->loop.slot_ints);
+        const size_t n = (size_t)g.E * s->loop.k;
         if (pts) for (size_t i = 0; i < n; ++i) _mm_store_si128(slot + i, _mm_set_epi32((int)seq, pts[3 * i + 2], pts[3 * i + 1], pts[3 * i]));
         else for (size_t i = 0; i < n; ++i) _mm_store_si128(slot + i, _mm_set_epi32((int)seq, 0, 0, 0));
     }
-    volatile uint32_t *db = s->loop_db;
+    volatile uint32_t *db = s->loop.db;
     __sync_synchronize();                                    // the points are in memory before the number that announces them
     db[0] = seq;
-    s->loop_seq = seq;
+    s->loop.seq = seq;
     if (s->fire_rows > 0 && s->fire_rows < g.H) s->fire_rows = s->fire_rows + 2 > g.H ? g.H : s->fire_rows + 2;
     // wait for the "done" number; should the launch have left by itself (no ring for loop_timeout clocks), start it again: every
     // workgroup resumes from its own "done" number, the points of this step are still in their slot
-    const volatile uint32_t *res = reinterpret_cast<const volatile uint32_t *>(s->loop_res);
+    const volatile uint32_t *res = reinterpret_cast<const volatile uint32_t *>(s->loop.res);
     auto arrived = [&](int q) { const volatile uint32_t *l = res + (size_t)q * 16; return l[3] == seq && l[7] == seq && l[11] == seq && l[15] == seq; };
     // (a row is taken out of its line as soon as the line is there: nothing is left to do behind the last arrival)
     auto take = [&](int q) {
@@ -2954,9 +1655,9 @@ extern "C" int sf_loop_step(sf_sim *s, const int32_t *pts, int32_t *status_out, 
             bool all = true;
             for (int q = 0; q < g.E; ++q) all = all && arrived(q);
             if (all) { for (int q = e; q < g.E; ++q) take(q); break; }
-            if (s->xerr_pinned && *s->xerr_pinned) return fail(SF_EHIP, "sf_loop_step: the resident launch failed");
+            if (s->team.xerr_pinned && *s->team.xerr_pinned) return fail(SF_EHIP, "sf_loop_step: the resident launch failed");
             HIPCHK(hipSetDevice(s->p.device));
-            s->loop_restarts++;
+            s->loop.restarts++;
             { int rc0 = loop_launch(s); if (rc0) return rc0; }
             HIPCHK(hipGetLastError());
         }
@@ -2967,13 +1668,13 @@ extern "C" int sf_loop_step(sf_sim *s, const int32_t *pts, int32_t *status_out, 
 extern "C" int sf_loop_stop(sf_sim *s) { return s ? loop_stop(s) : fail(SF_EINVAL, "sf_loop_stop: null handle"); }
 static int loop_stop(sf_sim *s)
 {
-    if (!s->loop_on) return SF_OK;
+    if (!s->loop.on) return SF_OK;
     HIPCHK(hipSetDevice(s->p.device));
-    volatile uint32_t *db = s->loop_db;
+    volatile uint32_t *db = s->loop.db;
     __sync_synchronize();
-    db[0] = s->loop_seq | kLoopStop;
+    db[0] = s->loop.seq | kLoopStop;
     __sync_synchronize();
-    s->loop_on = false;
+    s->loop.on = false;
     HIPCHK(hipStreamSynchronize(s->stream));      // the workgroups commit their environments and leave the result block behind
     s->status_fresh = true;
     return SF_OK;
@@ -2982,7 +1683,7 @@ static int loop_stop(sf_sim *s)
 extern "C" int sf_loop_restarts(sf_sim *s, int32_t *out)
 {
     if (!s || !out) return fail(SF_EINVAL, "sf_loop_restarts: null argument");
-    *out = s->loop_restarts;
+    *out = s->loop.restarts;
     return SF_OK;
 }
 
@@ -2992,8 +1693,7 @@ static int get_maps(sf_sim *s, int env0, int n, uint8_t *out)
     HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
     if (s->last_was_step1) { s->last_was_step1 = false; s->step1_polls = 0; }      // (a loop that looks at the maps after every update: per-step kernels)
     const size_t bytes = (size_t)n * g.H * g.W;
-    int rc = ensure_stage(s, bytes);
-    if (rc) return rc;
+    SF_TRY(ensure_stage(s, bytes));
     dim3 blk(256), grd((g.W + 255) / 256, g.H, n);
     hipLaunchKernelGGL(k_unpack_status, grd, blk, 0, s->stream, g, (const uint8_t *)s->status, (const uint8_t *)(s->bl_cur ? s->cells : nullptr), env0, (uint8_t *)s->stage, (uint8_t *)nullptr);
     HIPCHK(hipGetLastError());
@@ -3014,8 +1714,7 @@ extern "C" int sf_get_fire_maps(sf_sim *s, uint8_t *out)
     const int chunk = 64;   // bound the staging buffer
     for (int e = 0; e < s->g.E; e += chunk) {
         const int n = s->g.E - e < chunk ? s->g.E - e : chunk;
-        int rc = get_maps(s, e, n, out + (size_t)e * s->g.H * s->g.W);
-        if (rc) return rc;
+        SF_TRY(get_maps(s, e, n, out + (size_t)e * s->g.H * s->g.W));
     }
     return SF_OK;
 }
@@ -3033,39 +1732,37 @@ static int delta_enqueue(sf_sim *s, int env, int cap, int *mode, bool with_row =
 {
     const Geo &g = s->g;
     constexpr int kInline = 1024;      // entries that travel with the count (one copy, one wait)
-    if (!s->snap) {
-        int rc = dev_alloc(s, &s->snap, (size_t)g.E * g.plane_env);
-        if (rc) return rc;
-        s->snap_valid.assign((size_t)g.E, 0);
+    if (!s->delta.snap) {
+        SF_TRY(dev_alloc(s, &s->delta.snap, (size_t)g.E * g.plane_env));
+        s->delta.snap_valid.assign((size_t)g.E, 0);
     }
-    if (cap > s->delta_cap || !s->delta_dev) {
+    if (cap > s->delta.cap || !s->delta.dev) {
         HIPCHK(hipStreamSynchronize(s->stream));
-        if (s->delta_dev) { HIPCHK(hipFree(s->delta_dev)); s->delta_dev = nullptr; }
-        if (s->delta_pinned) { HIPCHK(hipHostFree(s->delta_pinned)); s->delta_pinned = nullptr; }
+        if (s->delta.dev) { HIPCHK(hipFree(s->delta.dev)); s->delta.dev = nullptr; }
+        if (s->delta.pinned) { HIPCHK(hipHostFree(s->delta.pinned)); s->delta.pinned = nullptr; }
         const int c = cap > kInline ? cap : kInline;
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&s->delta_dev), ((size_t)c + kDeltaHead) * sizeof(uint32_t)));
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&s->delta_pinned), ((size_t)c + kDeltaHead + 16) * sizeof(uint32_t), hipHostMallocDefault));      // (+ 16: a row that could not travel with a list, sf_run_delta)
-        HIPCHK(hipMemsetAsync(s->delta_dev, 0, sizeof(uint32_t), s->stream));
-        s->delta_cap = c;
-        s->delta_base = 0;
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&s->delta.dev), ((size_t)c + kDeltaHead) * sizeof(uint32_t)));
+        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&s->delta.pinned), ((size_t)c + kDeltaHead + 16) * sizeof(uint32_t), hipHostMallocDefault));      // (+ 16: a row that could not travel with a list, sf_run_delta)
+        HIPCHK(hipMemsetAsync(s->delta.dev, 0, sizeof(uint32_t), s->stream));
+        s->delta.cap = c;
+        s->delta.base = 0;
     }
-    if (!s->snap_valid[env]) {
+    if (!s->delta.snap_valid[env]) {
         // no reference point: the current map becomes it, the caller fetches the whole map
         dim3 blk(256), grd((g.W + 255) / 256, g.H, 1);
-        int rc = ensure_stage(s, (size_t)g.H * g.W);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_unpack_status, grd, blk, 0, s->stream, g, (const uint8_t *)s->status, (const uint8_t *)(s->bl_cur ? s->cells : nullptr), env, (uint8_t *)s->stage, s->snap);
+        SF_TRY(ensure_stage(s, (size_t)g.H * g.W));
+        hipLaunchKernelGGL(k_unpack_status, grd, blk, 0, s->stream, g, (const uint8_t *)s->status, (const uint8_t *)(s->bl_cur ? s->cells : nullptr), env, (uint8_t *)s->stage, s->delta.snap);
         HIPCHK(hipGetLastError());
-        s->snap_valid[env] = 1;
+        s->delta.snap_valid[env] = 1;
         *mode = 1;
         return SF_OK;
     }
     hipLaunchKernelGGL(k_map_delta, dim3((g.PV + 255) / 256, g.H), dim3(256), 0, s->stream, g, (const uint8_t *)s->status, (const uint8_t *)(s->bl_cur ? s->cells : nullptr), env,
-                       s->snap + (size_t)env * g.plane_env, s->delta_dev, cap, s->delta_base,
+                       s->delta.snap + (size_t)env * g.plane_env, s->delta.dev, cap, s->delta.base,
                        with_row ? (const int32_t *)(s->status_block + (size_t)env * 8) : nullptr, (const double *)(s->elapsed_dev + env));
     HIPCHK(hipGetLastError());
     const int first = cap < kInline ? cap : kInline;
-    HIPCHK(hipMemcpyAsync(s->delta_pinned, s->delta_dev, ((size_t)first + kDeltaHead) * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipMemcpyAsync(s->delta.pinned, s->delta.dev, ((size_t)first + kDeltaHead) * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
     *mode = 0;
     return SF_OK;
 }
@@ -3074,14 +1771,14 @@ static int delta_finish(sf_sim *s, int cap, uint32_t *cells_out, int32_t *n_out)
 {
     constexpr int kInline = 1024;
     const int first = cap < kInline ? cap : kInline;
-    const uint32_t n = s->delta_pinned[0] - s->delta_base;
-    s->delta_base = s->delta_pinned[0];
+    const uint32_t n = s->delta.pinned[0] - s->delta.base;
+    s->delta.base = s->delta.pinned[0];
     if (n > (uint32_t)cap) { *n_out = -1; return SF_OK; }      // (the reference point is current: the caller fetches the whole map)
     if (n > (uint32_t)first) {
-        HIPCHK(hipMemcpyAsync(s->delta_pinned + kDeltaHead + first, s->delta_dev + kDeltaHead + first, ((size_t)n - first) * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(hipMemcpyAsync(s->delta.pinned + kDeltaHead + first, s->delta.dev + kDeltaHead + first, ((size_t)n - first) * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
         HIPCHK(hipStreamSynchronize(s->stream));
     }
-    if (n) memcpy(cells_out, s->delta_pinned + kDeltaHead, (size_t)n * sizeof(uint32_t));
+    if (n) memcpy(cells_out, s->delta.pinned + kDeltaHead, (size_t)n * sizeof(uint32_t));
     *n_out = (int32_t)n;
     return SF_OK;
 }
@@ -3094,8 +1791,8 @@ extern "C" int sf_get_fire_map_delta(sf_sim *s, int32_t env, uint32_t *cells_out
     HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
     note_result_look(s);               // (like a status query)
     int mode = 0;
-    { int rc = delta_enqueue(s, env, cap, &mode); if (rc) return rc; }
-    { int rc = finish_call(s, "sf_get_fire_map_delta", true, nullptr); if (rc) return rc; }
+    SF_TRY(delta_enqueue(s, env, cap, &mode));
+    SF_TRY(finish_call(s, "sf_get_fire_map_delta", true, nullptr));
     if (mode == 1) { *n_out = -1; return SF_OK; }
     return delta_finish(s, cap, cells_out, n_out);
 }
@@ -3114,19 +1811,16 @@ extern "C" int sf_run_delta(sf_sim *s, int32_t n_steps, int32_t env, int32_t *st
     if (!rc) rc = step_impl(s, n_steps, false, nullptr);
     if (rc) return rc;
     note_result_look(s);
-    rc = refresh_status(s, nullptr);               // (nothing to launch behind a resident launch: it has left the block behind itself)
-    if (rc) return rc;
+    SF_TRY(refresh_status(s, nullptr));      // (nothing to launch behind a resident launch: it has left the block behind itself)
     int mode = 0;
-    rc = delta_enqueue(s, env, cap, &mode, true);
-    if (rc) return rc;
-    uint32_t *land = s->delta_pinned + 1;          // the row and its elapsed_time have travelled with the list's count ...
+    SF_TRY(delta_enqueue(s, env, cap, &mode, true));
+    uint32_t *land = s->delta.pinned + 1;          // the row and its elapsed_time have travelled with the list's count ...
     if (mode == 1) {                               // ... unless there was no list
-        land = s->delta_pinned + s->delta_cap + kDeltaHead;
+        land = s->delta.pinned + s->delta.cap + kDeltaHead;
         HIPCHK(hipMemcpyAsync(land, s->status_block + (size_t)env * 8, 8 * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
         HIPCHK(hipMemcpyAsync(land + 8, s->elapsed_dev + env, sizeof(double), hipMemcpyDeviceToHost, s->stream));
     }
-    rc = finish_call(s, "sf_run_delta", true, nullptr);
-    if (rc) return rc;
+    SF_TRY(finish_call(s, "sf_run_delta", true, nullptr));
     memcpy(status_row, land, 8 * sizeof(int32_t));
     if (elapsed) memcpy(elapsed, land + 8, sizeof(double));
     if (mode == 1) *n_out = -1;
@@ -3141,13 +1835,10 @@ extern "C" int sf_get_burn(sf_sim *s, int32_t env, double *out)
     if (env < 0 || env >= g.E) return fail(SF_EINVAL, "sf_get_burn: environment %d out of range", env);
     HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
     const size_t bytes = (size_t)g.H * g.W * sizeof(double);
-    int rc = ensure_stage(s, bytes);
-    if (rc) return rc;
+    SF_TRY(ensure_stage(s, bytes));
     dim3 blk(256), grd((g.W + 255) / 256, g.H);
-    rc = ensure_commit(s);
-    if (rc) return rc;
-    rc = ensure_rm(s);
-    if (rc) return rc;
+    SF_TRY(ensure_commit(s));
+    SF_TRY(ensure_rm(s));
     hipLaunchKernelGGL(k_unpack_burn, grd, blk, 0, s->stream, g, (const uint8_t *)s->status, (const uint32_t *)s->settled,
                        (const double *)s->burn, (const EnvState *)s->commit, env, (double *)s->stage);
     HIPCHK(hipGetLastError());
@@ -3162,13 +1853,10 @@ extern "C" int sf_set_burn(sf_sim *s, int32_t env, const double *burn)
     if (env < 0 || env >= g.E) return fail(SF_EINVAL, "sf_set_burn: environment %d out of range", env);
     HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
     const size_t bytes = (size_t)g.H * g.W * sizeof(double);
-    int rc = ensure_stage(s, bytes);
-    if (rc) return rc;
+    SF_TRY(ensure_stage(s, bytes));
     dim3 blk(256), grd((g.W + 255) / 256, g.H);
-    rc = ensure_commit(s);
-    if (rc) return rc;
-    rc = ensure_rm(s);
-    if (rc) return rc;
+    SF_TRY(ensure_commit(s));
+    SF_TRY(ensure_rm(s));
     if (g.att)   // the caller's values are the truth now: nothing is owed any more
         hipLaunchKernelGGL(k_settle_env, grd, blk, 0, s->stream, g, (const uint8_t *)s->status, s->settled, s->burn,
                            (const EnvState *)s->commit, env, 0);
@@ -3179,707 +1867,9 @@ extern "C" int sf_set_burn(sf_sim *s, int32_t env, const double *burn)
     return SF_OK;
 }
 
-// ----------------------------------------------------------------------------- environment state
-// Every state call begins as begin_call(kStateCall): the closed loop ended, a reset insisted on, a voided handle refused, the step
-// rings folded into commit[].
+#include "sf_host_state.h"
 
-extern "C" int sf_copy_envs(sf_sim *s, const int32_t *src, const int32_t *dst, int32_t n, int32_t flags)
-{
-    if (!s) return fail(SF_EINVAL, "sf_copy_envs: null handle");
-    if (n < 0 || (n > 0 && (!src || !dst))) return fail(SF_EINVAL, "sf_copy_envs: bad environment lists");
-    if (flags & ~SF_COPY_TERRAIN) return fail(SF_EINVAL, "sf_copy_envs: unknown flags 0x%x", flags);
-    const Geo &g = s->g;
-    std::vector<char> role((size_t)g.E, 0);       // bit 0: a source, bit 1: a destination
-    { int rc = check_envs(s, "sf_copy_envs", n, src); if (!rc) rc = check_envs(s, "sf_copy_envs", n, dst); if (rc) return rc; }
-    for (int i = 0; i < n; ++i) {
-        if (role[dst[i]] & 2) return fail(SF_EINVAL, "sf_copy_envs: environment %d is a destination twice", dst[i]);
-        role[dst[i]] |= 2;
-    }
-    for (int i = 0; i < n; ++i) role[src[i]] |= 1;
-    for (int e = 0; e < g.E; ++e)
-        if (role[e] == 3) return fail(SF_EINVAL, "sf_copy_envs: environment %d is both a source and a destination", e);
-    if (n == 0) return SF_OK;
-    { int rc = begin_call(s, "sf_copy_envs", kStateCall); if (rc) return rc; }
-    // Every per-environment slice of the current layout and of the structures derived from it: a handle-wide "rebuild" flag would make
-    // the next step rebuild them for every environment.
-    CopyList L;
-    const bool terrain = (flags & SF_COPY_TERRAIN) && s->rt_set.size() > 1;      // (a stale rtc copy stays marked stale below)
-    // (section 20: the record travels with the arrival plane it was summed over - under ONE plane for all environments.  Planes per
-    // environment stay where they are, like the terrain without SF_COPY_TERRAIN: dst's damage is its own plane over src's arrival,
-    // recounted below)
-    L.n_seg = arrival_seg(s, L.seg, env_segs(s, terrain ? kForkKinds : kForkKinds & ~kSegTerrain, L.seg));
-    if (!s->val_per_env) L.n_seg = value_seg(s, L.seg, L.n_seg);
-    const unsigned gx = seg_grid_x(L.seg, L.n_seg);
-    // with the terrain go the slices of section 18, where they exist: the table's part of the wind cache, the environment's schedule
-    // and the segment its table stands for (a launch of their own: the slice table of env_segs is full)
-    CopyList Wl;
-    Wl.n_seg = 0;
-    if (terrain && s->wterms) Wl.seg[Wl.n_seg++] = {reinterpret_cast<uint8_t *>(s->wterms), (long long)kWindPlanes * g.H * g.W * 4, (long long)kWindPlanes * g.H * g.W * 4};
-    if (terrain && s->wsched) Wl.seg[Wl.n_seg++] = {reinterpret_cast<uint8_t *>(s->wsched), (long long)sizeof(WindSched), (long long)sizeof(WindSched)};
-    for (int i0 = 0; i0 < n; i0 += kCopyPairs) {
-        const int cnt = std::min(kCopyPairs, n - i0);
-        for (int i = 0; i < cnt; ++i) { L.src[i] = Wl.src[i] = src[i0 + i]; L.dst[i] = Wl.dst[i] = dst[i0 + i]; }
-        hipLaunchKernelGGL(k_env_copy, dim3(gx, (unsigned)cnt), dim3(256), 0, s->stream, L);
-        if (Wl.n_seg) hipLaunchKernelGGL(k_env_copy, dim3(seg_grid_x(Wl.seg, Wl.n_seg), (unsigned)cnt), dim3(256), 0, s->stream, Wl);
-        HIPCHK(hipGetLastError());
-    }
-    for (int i = 0; i < n; ++i) {
-        if (s->snap) s->snap_valid[dst[i]] = 0;      // (sf_get_fire_map_delta: the next query for dst hands back the whole map once)
-        if (terrain) {
-            s->rd_lay[dst[i]] = s->rd_lay[src[i]]; s->rd_fbfm[dst[i]] = s->rd_fbfm[src[i]]; s->rd_stale[dst[i]] = 1;
-            if (s->rd_fuel_ix && s->rd_fbfm[src[i]] && dst[i] != src[i]) {
-                const size_t cells = (size_t)g.H * g.W;
-                HIPCHK(hipMemcpyAsync(s->rd_fuel_ix + (size_t)dst[i] * cells, s->rd_fuel_ix + (size_t)src[i] * cells, cells,
-                                      hipMemcpyDeviceToDevice, s->stream));
-            }
-            s->rt_set[dst[i]] = s->rt_set[src[i]];
-            if (s->rtc_stale.size() == s->rt_set.size()) s->rtc_stale[dst[i]] = s->rtc_stale[src[i]];
-            if (!s->rtc || s->rtc_stale.size() != s->rt_set.size() || s->rtc_stale[dst[i]]) s->rtc_valid = false;
-            if (!s->wt_stale.empty()) s->wt_stale[dst[i]] = s->wt_stale[src[i]];
-            if (s->wsched) s->wind_K[dst[i]] = s->wind_K[src[i]];
-        }
-    }
-    if (terrain) { s->have_rt = true; for (char c : s->rt_set) if (!c) s->have_rt = false; }
-    if (terrain && s->wsched) wind_sched_count(s);
-    if (s->val_per_env) { int rc = value_recount(s); if (rc) return rc; }
-    // (fire_rows bounds every environment's fire, dst's copy included; status_fresh: dst's row is src's current row)
-    return finish_call(s, nullptr, !s->async, nullptr);
-}
-
-static StateHeader state_header(const sf_sim *s)
-{
-    const Geo &g = s->g;
-    StateHeader h;
-    memset(&h, 0, sizeof h);
-    h.magic = kStateMagic; h.version = kStateVersion;
-    h.bytes = state_layout(g, s->parents != nullptr, s->arrival1 != nullptr).bytes;
-    h.H = g.H; h.W = g.W; h.md = g.md; h.ab = g.ab;
-    h.diag = g.diag; h.att = g.att; h.has_max_time = g.has_max_time; h.prune_after_quit = g.prune_after_quit;
-    h.has_parents = s->parents != nullptr; h.fire_rows = s->fire_rows; h.has_arrival = s->arrival1 != nullptr;
-    h.max_time = g.has_max_time ? g.max_time : 0.0; h.update_rate = g.update_rate; h.pixel_scale = g.pixel_scale;
-    return h;
-}
-
-// a blob this handle can take: every value its state depends on matches (the first one that does not is named)
-static int header_check(const sf_sim *s, const StateHeader &b, int i)
-{
-    const StateHeader h = state_header(s);
-    const char *what = nullptr;
-    if (b.magic != h.magic) what = "magic number (not a state blob)";
-    else if (b.version != h.version) what = "format version";
-    else if (b.H != h.H || b.W != h.W) what = "grid size";
-    else if (b.md != h.md || b.ab != h.ab) what = "max_fire_duration";
-    else if (b.diag != h.diag) what = "diagonal spread";
-    else if (b.att != h.att) what = "line attenuation";
-    else if (b.has_max_time != h.has_max_time || b.max_time != h.max_time) what = "max_time";
-    else if (b.update_rate != h.update_rate) what = "update_rate";
-    else if (b.pixel_scale != h.pixel_scale) what = "pixel_scale threshold";
-    else if (b.prune_after_quit != h.prune_after_quit) what = "prune_after_quit";
-    else if (b.has_parents != h.has_parents) what = "spread graph";
-    else if (b.has_arrival != h.has_arrival) what = "arrival recording";
-    else if (b.bytes != h.bytes) what = "size";
-    if (what) return fail(SF_EINVAL, "sf_load_state: blob %d does not match this handle: %s", i, what);
-    return SF_OK;
-}
-
-static int state_list(const sf_sim *s, int32_t n, const int32_t *envs, const void *buf, int32_t device_pointer, const char *who, bool distinct)
-{
-    if (n < 0 || (n > 0 && (!envs || !buf))) return fail(SF_EINVAL, "%s: bad argument", who);
-    if (device_pointer && ((uintptr_t)buf & 15))      // (the kernels read / write the f64 and u32 sections in place)
-        return fail(SF_EINVAL, "%s: a device buffer must be 16-byte aligned", who);
-    return check_envs(s, who, n, envs, distinct ? "is listed twice" : nullptr);
-}
-
-static StateArgs state_args(sf_sim *s)
-{
-    StateArgs a;
-    memset(&a, 0, sizeof a);
-    a.g = s->g;
-    a.status = s->status; a.age = s->age; a.cells = s->bl_cur ? s->cells : nullptr;
-    a.burn = s->burn; a.settled = s->settled; a.parents = s->parents; a.arrival = s->arrival1; a.vbits = s->vbits;
-    a.commit = s->commit; a.res_block = s->status_block; a.res_sink = s->sink; a.res_elapsed = s->elapsed_dev;
-    a.lay = state_layout(s->g, s->parents != nullptr, s->arrival1 != nullptr);
-    a.stride = a.lay.bytes;
-    return a;
-}
-// environments per launch, and per pass through the staging buffer of a host-pointer call (<= 64 MB of blobs unless one is larger)
-static int state_chunk(const StateArgs &a, bool device)
-{
-    if (device) return kStateEnvs;
-    return (int)std::max<long long>(1, std::min<long long>(kStateEnvs, (64LL << 20) / a.stride));
-}
-
-// ----------------------------------------------------------------------------- resets
-// A call's environment list / host ignitions -> device memory through the pinned buffer, one copy; *dev is where they are.
-static int reset_stage(sf_sim *s, const void *a, size_t na, const void *b, size_t nb, uint8_t **dev)
-{
-    CallBlock &blk = s->rs_blk;
-    { int rc = block_reserve(s, blk, na + nb); if (rc) return rc; }
-    if (na) memcpy(blk.pinned, a, na);
-    if (nb) memcpy(blk.pinned + na, b, nb);
-    *dev = blk.dev;
-    return block_send(s, blk, na + nb);
-}
-
-// The two launches of a reset, the one way an environment gets a new episode: every environment taken is written in the layout that is
-// current.  envs_dev: the list form's environments (distinct), else the mask form over all of them.  full: the list names every
-// environment (sf_reset), so the handle-wide bookkeeping starts afresh too.
-static int reset_launch(sf_sim *s, const int32_t *envs_dev, const uint8_t *mask, const int32_t *xy_dev, int n, bool full = false)
-{
-    const Geo &g = s->g;
-    ResetArgs a;
-    memset(&a, 0, sizeof a);
-    a.g = g;
-    const bool seams = !s->bl_cur && g.ab == 1;       // (the tile bookkeeping is not kept while the blocked plane is current: tiles_valid is false)
-    // the tile histograms of a reset environment are known (all UNBURNED, the ignition's tile to be recounted); a partial reset leaves
-    // it at that while every histogram of the handle is marked stale anyway
-    const bool hist_known = g.ab == 1 && !s->generic && (full || !s->tdirty_all);
-    if (full) { s->status_fresh = true; s->cost_steps = 0; }      // every result row is written; the old episodes' costs (run_cost, zeroed) say nothing
-    a.n_seg = value_seg(s, a.seg, arrival_seg(s, a.seg, env_segs(s, (kResetKinds & ~(seams ? 0u : kSegSeam) & ~(hist_known ? 0u : kSegHist)) | (full ? kSegCost : 0u), a.seg)));
-    a.envs = envs_dev; a.mask = mask; a.xy = xy_dev; a.n = n;
-    a.status = s->status; a.age = s->age; a.cells = s->bl_cur ? s->cells : nullptr;
-    a.commit = s->commit; a.tflags = s->tflags; a.ring = s->ring; a.vbits = s->vbits; a.win_hint = s->win_hint;
-    a.seam = seams ? s->seam : nullptr;
-    a.tdirty = hist_known ? s->tdirty : nullptr;
-    a.res_block = s->status_block; a.res_sink = s->sink; a.res_elapsed = s->elapsed_dev;
-    const unsigned gx = seg_grid_x(a.seg, a.n_seg);
-    if (s->rs_timed) HIPCHK(hipEventRecord(s->ev0, s->stream));
-    // Whole buffers of a large batch: a memset per slice.  Each costs a few microseconds to enqueue and clears ~14 % faster than the
-    // kernel - C3's 2.7 GB in 0.46 ms against 0.50, 1 x 64 x 64 in 59 us against 30 (profiles/reset_paths_ab.txt): even at ~1 GB
-    long long bytes = 0;
-    for (int k = 0; k < a.n_seg; ++k) bytes += g.E * a.seg[k].len;
-    if (full && bytes >= (1LL << 30)) {
-        for (int k = 0; k < a.n_seg; ++k) {
-            assert(a.seg[k].stride == a.seg[k].len);
-            HIPCHK(hipMemsetAsync(a.seg[k].base, 0, (size_t)(g.E * a.seg[k].len), s->stream));
-        }
-    } else {
-        hipLaunchKernelGGL(k_reset_envs, dim3(gx, (unsigned)n), dim3(256), 0, s->stream, a);
-        HIPCHK(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_reset_ignite, dim3((n + 255) / 256), dim3(256), 0, s->stream, a);
-    HIPCHK(hipGetLastError());
-    if (s->rs_timed) { HIPCHK(hipEventRecord(s->ev1, s->stream)); s->rs_have_ms = true; }
-    s->tdirty_all = !hist_known;
-    return arrival_pass(s);             // the ignitions are the sprites of update 0 (recording off: nothing)
-}
-// Host ignitions: every one on the grid, or SF_EINVAL in the words of the entry `who` (envs: whose they are, null = 0 .. n - 1).
-static int check_ignitions(const sf_sim *s, const char *who, int n, const int32_t *envs, const int32_t *xy)
-{
-    const Geo &g = s->g;
-    for (int i = 0; i < n; ++i)
-        if (xy[2 * i] < 0 || xy[2 * i] >= g.W || xy[2 * i + 1] < 0 || xy[2 * i + 1] >= g.H)
-            return fail(SF_EINVAL, "%s: ignition (%d, %d) of environment %d is outside the %dx%d grid", who, xy[2 * i], xy[2 * i + 1],
-                        envs ? envs[i] : i, g.H, g.W);
-    return SF_OK;
-}
-// The list form from host memory: m distinct environments and their ignitions through the call block, then the launches.
-// (sf_get_fire_map_delta: a reset map is all UNBURNED - the caller zeroes its mirror, the next delta reports the ignition)
-static int reset_list(sf_sim *s, const int32_t *envs, const int32_t *xy, int m, bool full = false)
-{
-    uint8_t *dev = nullptr;
-    { int rc = reset_stage(s, envs, (size_t)m * 4, xy, (size_t)m * 8, &dev); if (rc) return rc; }
-    { int rc = reset_launch(s, reinterpret_cast<const int32_t *>(dev), nullptr, reinterpret_cast<const int32_t *>(dev + (size_t)m * 4), m, full); if (rc) return rc; }
-    if (s->snap) for (int i = 0; i < m; ++i) s->snap_valid[envs[i]] = 1;
-    return SF_OK;
-}
-
-// Every environment, as the list 0 .. E - 1 (without a mask the mask form takes only those that are not running).  Allowed before any
-// reset and on a handle a failed team launch has voided; waits whatever `async` says.
-extern "C" int sf_reset(sf_sim *s, const int32_t *init_xy)
-{
-    if (!s || !init_xy) return fail(SF_EINVAL, "sf_reset: null argument");
-    const int E = s->g.E;
-    { int rc = check_ignitions(s, "reset", E, nullptr, init_xy); if (rc) return rc; }
-    { int rc = begin_call(s, "sf_reset", kCommit); if (rc) return rc; }
-    // everything is rewritten, nothing to convert: into the blocked plane if the resident launch is what steps this handle
-    // (it did last, or nothing has stepped yet and it is the automatic choice), else into the row-major planes
-    const bool bl = prefers_bl(s) && (s->bl_cur || s->last_kind == 2 || s->last_kind == -1);
-    if (bl) { int rc = alloc_bl(s); if (rc) return rc; }
-    s->bl_cur = bl;
-    std::vector<int32_t> all((size_t)E);
-    for (int e = 0; e < E; ++e) all[e] = e;
-    { int rc = reset_list(s, all.data(), init_xy, E, true); if (rc) return rc; }
-    { int rc = finish_call(s, nullptr, true, nullptr); if (rc) return rc; }
-    s->last_ign.assign(init_xy, init_xy + (size_t)2 * E);      // (where a new episode ignites when sf_episodes_set draws no ignition)
-    s->was_reset = true; s->vbits_valid = true; s->vbits_fl_valid = true; s->tiles_valid = !s->bl_cur; s->fire_rows = 1;     // every environment freshly written
-    if (s->xerr_pinned) *s->xerr_pinned = 0;      // (cells, bitmaps, states of every environment are new: what a failed team launch left is gone)
-    return SF_OK;
-}
-
-// One environment: a list of one.  Never refused on a voided handle, and it waits whatever `async` says.
-extern "C" int sf_reset_env(sf_sim *s, int32_t env, int32_t x, int32_t y)
-{
-    if (!s) return fail(SF_EINVAL, "sf_reset_env: null handle");
-    if (env < 0 || env >= s->g.E) return fail(SF_EINVAL, "sf_reset_env: environment %d out of range", env);
-    if (!s->was_reset) return fail(SF_ESTATE, "sf_reset_env: call sf_reset once first");
-    const int32_t xy[2] = {x, y};
-    { int rc = check_ignitions(s, "reset", 1, &env, xy); if (rc) return rc; }
-    { int rc = begin_call(s, "sf_reset_env", kCommit); if (rc) return rc; }
-    { int rc = reset_list(s, &env, xy, 1); if (rc) return rc; }
-    return finish_call(s, nullptr, true, nullptr);
-}
-
-extern "C" int sf_time_resets(sf_sim *s, int32_t on)
-{
-    if (!s) return fail(SF_EINVAL, "sf_time_resets: null handle");
-    s->rs_timed = on != 0;
-    s->rs_have_ms = false;
-    return SF_OK;
-}
-
-extern "C" int sf_get_reset_ms(sf_sim *s, float *ms_out)
-{
-    if (!s || !ms_out) return fail(SF_EINVAL, "sf_get_reset_ms: null argument");
-    if (!s->rs_have_ms) return fail(SF_ESTATE, "sf_get_reset_ms: no batched reset has been timed (sf_time_resets)");
-    HIPCHK(hipSetDevice(s->p.device));
-    HIPCHK(hipEventSynchronize(s->ev1));
-    HIPCHK(hipEventElapsedTime(ms_out, s->ev0, s->ev1));
-    return SF_OK;
-}
-
-extern "C" int sf_reset_envs(sf_sim *s, int32_t n, const int32_t *envs, const int32_t *xy)
-{
-    if (!s) return fail(SF_EINVAL, "sf_reset_envs: null handle");
-    if (n < 0 || (n > 0 && (!envs || !xy))) return fail(SF_EINVAL, "sf_reset_envs: bad environment list");
-    { int rc = check_envs(s, "sf_reset_envs", n, envs); if (rc) return rc; }      // (a repeated environment is accepted: below)
-    { int rc = check_ignitions(s, "sf_reset_envs", n, envs, xy); if (rc) return rc; }
-    if (n == 0) return SF_OK;
-    { int rc = begin_call(s, "sf_reset_envs", kStateCall); if (rc) return rc; }
-    // an environment named twice keeps the last ignition given for it: no two entries of the launch write one environment
-    std::vector<int32_t> last((size_t)s->g.E, -1), le, lxy;
-    for (int i = 0; i < n; ++i) last[envs[i]] = i;
-    for (int i = 0; i < n; ++i)
-        if (last[envs[i]] == i) { le.push_back(envs[i]); lxy.push_back(xy[2 * i]); lxy.push_back(xy[2 * i + 1]); }
-    { int rc = reset_list(s, le.data(), lxy.data(), (int)le.size()); if (rc) return rc; }
-    return finish_call(s, nullptr, !s->async, nullptr);
-}
-
-extern "C" int sf_reset_where(sf_sim *s, const uint8_t *device_mask, const int32_t *xy, int32_t xy_device_pointer)
-{
-    if (!s) return fail(SF_EINVAL, "sf_reset_where: null handle");
-    if (!xy) return fail(SF_EINVAL, "sf_reset_where: null ignitions");
-    const Geo &g = s->g;
-    { int rc = begin_call(s, "sf_reset_where", kStateCall); if (rc) return rc; }
-    const int32_t *xy_dev = xy;
-    if (!xy_device_pointer) {
-        uint8_t *dev = nullptr;
-        int rc = reset_stage(s, xy, (size_t)g.E * 8, nullptr, 0, &dev);
-        if (rc) return rc;
-        xy_dev = reinterpret_cast<const int32_t *>(dev);
-    }
-    { int rc = reset_launch(s, nullptr, device_mask, xy_dev, g.E); if (rc) return rc; }
-    // which environments were taken is known on the device only: no host mirror of a map can be told to zero itself, so the next
-    // delta query of every environment hands back the whole map once
-    if (s->snap) std::fill(s->snap_valid.begin(), s->snap_valid.end(), 0);
-    return finish_call(s, nullptr, !s->async, nullptr);
-}
-
-// ----------------------------------------------------------------------------- agents
-static int agents_free(sf_sim *s)
-{
-    if (s->ag_mem) {
-        HIPCHK(hipStreamSynchronize(s->stream));      // (enqueued ticks may still use the buffers)
-        HIPCHK(hipFree(s->ag_mem));
-        s->bytes -= (int64_t)s->ag_bytes;
-    }
-    s->ag_mem = nullptr; s->ag_bytes = 0;
-    s->ag_xyid = s->ag_start = s->ag_points = s->ag_prev = s->ag_terms = s->ag_len = s->ag_ign = nullptr;
-    s->ag_ret = nullptr; s->ag_done = nullptr;
-    s->ag_has_ign = false;
-    s->val_w_on = false;                              // (the fifth weight belongs to the agent state: set again behind sf_agents_create)
-    memset(&s->ag, 0, sizeof s->ag);
-    return SF_OK;
-}
-
-extern "C" int sf_agents_create(sf_sim *s, const sf_agent_params *p, const int32_t *ignitions_xy)
-{
-    if (!s || !p) return fail(SF_EINVAL, "sf_agents_create: null argument");
-    const Geo &g = s->g;
-    if (p->k < 0 || p->k > kAgentsMax) return fail(SF_EINVAL, "sf_agents_create: %d agents per environment (1..%d; 0 frees)", p->k, kAgentsMax);
-    if (p->k > 0) {
-        if (p->n_updates < 1) return fail(SF_EINVAL, "sf_agents_create: n_updates = %d must be >= 1", p->n_updates);
-        if (p->max_ticks < 0) return fail(SF_EINVAL, "sf_agents_create: max_ticks = %d must be >= 0", p->max_ticks);
-        if (p->auto_reset && !ignitions_xy) return fail(SF_EINVAL, "sf_agents_create: auto_reset needs the ignitions");
-        for (int e = 0; ignitions_xy && e < g.E; ++e)
-            if (ignitions_xy[2 * e] < 0 || ignitions_xy[2 * e] >= g.W || ignitions_xy[2 * e + 1] < 0 || ignitions_xy[2 * e + 1] >= g.H)
-                return fail(SF_EINVAL, "sf_agents_create: ignition (%d, %d) of environment %d is outside the %dx%d grid", ignitions_xy[2 * e],
-                            ignitions_xy[2 * e + 1], e, g.H, g.W);
-    }
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    { int rc = agents_free(s); if (rc) return rc; }
-    if (p->k == 0) return SF_OK;
-    // one allocation, every buffer on a 16-byte boundary: xyid | start | points | prev | terms | len | ign | ret | done
-    const size_t E = (size_t)g.E, K = (size_t)p->k;
-    const size_t sizes[9] = {E * K * 12, E * K * 8, E * K * 12, E * 4, E * 16, E * 4, E * 8, E * 8, E};
-    size_t off[9], total = 0;
-    for (int i = 0; i < 9; ++i) { off[i] = total; total += (sizes[i] + 15) / 16 * 16; }
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&s->ag_mem), total));
-    s->ag_bytes = total; s->bytes += (int64_t)total;
-    int32_t **ip[7] = {&s->ag_xyid, &s->ag_start, &s->ag_points, &s->ag_prev, &s->ag_terms, &s->ag_len, &s->ag_ign};
-    for (int i = 0; i < 7; ++i) *ip[i] = reinterpret_cast<int32_t *>(s->ag_mem + off[i]);
-    s->ag_ret = reinterpret_cast<double *>(s->ag_mem + off[7]);
-    s->ag_done = s->ag_mem + off[8];
-    std::vector<uint8_t> h(total, 0);
-    int32_t *xyid = reinterpret_cast<int32_t *>(h.data() + off[0]);
-    for (size_t i = 0; i < E * K; ++i) xyid[3 * i + 2] = (int32_t)(i % K) + 1;
-    if (ignitions_xy) memcpy(h.data() + off[6], ignitions_xy, E * 8);
-    HIPCHK(hipMemcpyAsync(s->ag_mem, h.data(), total, hipMemcpyHostToDevice, s->stream));
-    // (section 19: episodes that draw no ignition re-ignite where these agents' environments do)
-    if (ignitions_xy && s->ep_on && !(s->ep.flags & SF_EP_IGNITION)) HIPCHK(hipMemcpyAsync(s->ep_ign, ignitions_xy, E * 8, hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));          // (h is pageable and leaves scope)
-    s->ag = *p;
-    s->ag_has_ign = ignitions_xy != nullptr;
-    return SF_OK;
-}
-
-extern "C" int sf_agents_place(sf_sim *s, int32_t n, const int32_t *envs, const int32_t *xy, int32_t also_start)
-{
-    if (!s) return fail(SF_EINVAL, "sf_agents_place: null handle");
-    if (!s->ag.k) return fail(SF_ESTATE, "sf_agents_place: call sf_agents_create first");
-    if (n < 0 || (n > 0 && (!envs || !xy))) return fail(SF_EINVAL, "sf_agents_place: bad environment list");
-    const Geo &g = s->g;
-    const int K = s->ag.k;
-    { int rc = check_envs(s, "sf_agents_place", n, envs); if (rc) return rc; }
-    for (long long i = 0; i < (long long)n * K; ++i)
-        if (xy[2 * i] < 0 || xy[2 * i] >= g.W || xy[2 * i + 1] < 0 || xy[2 * i + 1] >= g.H)
-            return fail(SF_EINVAL, "sf_agents_place: cell (%d, %d) of agent %d of environment %d is outside the %dx%d grid", xy[2 * i],
-                        xy[2 * i + 1], (int)(i % K), envs[i / K], g.H, g.W);
-    if (n == 0) return SF_OK;
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    // an environment named twice keeps its last entry: no two threads of the launch write one agent
-    std::vector<int32_t> last((size_t)g.E, -1), keep;
-    for (int i = 0; i < n; ++i) last[envs[i]] = i;
-    for (int i = 0; i < n; ++i) if (last[envs[i]] == i) keep.push_back(i);
-    const int m = (int)keep.size();
-    // the call block: envs [m] | xy [m][K][2]
-    const size_t o_xy = ((size_t)m * 4 + 15) / 16 * 16, bytes = o_xy + (size_t)m * K * 8;
-    CallBlock &blk = s->ag_blk;
-    { int rc = block_reserve(s, blk, bytes); if (rc) return rc; }
-    for (int i = 0; i < m; ++i) {
-        reinterpret_cast<int32_t *>(blk.pinned)[i] = envs[keep[i]];
-        memcpy(blk.pinned + o_xy + (size_t)i * K * 8, xy + (size_t)keep[i] * K * 2, (size_t)K * 8);
-    }
-    { int rc = block_send(s, blk, bytes); if (rc) return rc; }
-    hipLaunchKernelGGL(k_agents_place, dim3((unsigned)((m * K + 255) / 256)), dim3(256), 0, s->stream, m, K,
-                       reinterpret_cast<const int32_t *>(blk.dev), reinterpret_cast<const int32_t *>(blk.dev + o_xy), also_start != 0 ? 1 : 0,
-                       s->ag_xyid, s->ag_start, s->ag_len, s->ag_ret);
-    HIPCHK(hipGetLastError());
-    return finish_call(s, nullptr, !s->async, nullptr);
-}
-
-extern "C" int sf_agents_device(sf_sim *s, void **xyid)
-{
-    if (!s || !xyid) return fail(SF_EINVAL, "sf_agents_device: null argument");
-    if (!s->ag.k) return fail(SF_ESTATE, "sf_agents_device: call sf_agents_create first");
-    *xyid = s->ag_xyid;
-    return SF_OK;
-}
-
-
-// ----------------------------------------------------------------------------- drawn episodes
-static int episodes_free(sf_sim *s)
-{
-    if (s->ep_mem) {
-        HIPCHK(hipStreamSynchronize(s->stream));      // (enqueued ticks may still use the buffers)
-        HIPCHK(hipFree(s->ep_mem));
-        s->bytes -= (int64_t)s->ep_bytes;
-    }
-    s->ep_mem = s->ep_ones = nullptr; s->ep_bytes = 0;
-    s->ep_index = s->ep_due_cnt = nullptr;
-    s->ep_ign = s->ep_due = nullptr;
-    s->ep_wind = s->ep_due_U = s->ep_due_D = nullptr;
-    memset(&s->ep, 0, sizeof s->ep);
-    s->ep_on = false;
-    return SF_OK;
-}
-
-// New episodes in the environments the mask takes (null: those that are not running), their parameters drawn first (enqueue layer):
-// the draw, the batched reset with the drawn ignitions, then - SF_EP_WIND - the tables of the drawn winds, so that the episode runs
-// under its own wind from its first update.  Nothing is read back.
-static int episode_begin(sf_sim *s, const uint8_t *mask)
-{
-    const Geo &g = s->g;
-    const sf_episode_params &p = s->ep;
-    const bool wind = (p.flags & SF_EP_WIND) != 0;
-    bool cached = false;
-    if (wind) {
-        // the cache of wind-independent terms current for EVERY table (which ones restart is known on the device only), again after
-        // anything staled a part of it (mark_tables); without a cache the tables are built from the layers
-        const int n_tab = (int)s->rt_set.size();
-        bool stale = !s->wterms || s->wt_off;
-        for (int t = 0; t < n_tab && !stale; ++t) stale = s->wt_stale[t] != 0;
-        cached = !stale;
-        if (stale && !s->ep_nocache) {
-            std::vector<int32_t> tabs((size_t)n_tab);
-            for (int t = 0; t < n_tab; ++t) tabs[t] = t;
-            const int rc = ensure_wterms(s, tabs.data(), n_tab);
-            if (rc && rc != SF_ENOTSUP) return rc;
-            cached = rc == SF_OK;
-            s->ep_nocache = !cached;
-        }
-    }
-    EpisodeArgs a;
-    memset(&a, 0, sizeof a);
-    a.H = g.H; a.W = g.W; a.P = g.P; a.E = g.E;
-    a.mask = mask; a.commit = s->commit;
-    a.seed = p.seed; a.flags = p.flags;
-    for (int i = 0; i < 4; ++i) { a.ign_box[i] = p.ign_box[i]; a.agent_box[i] = p.agent_box[i]; }
-    for (int i = 0; i < 2; ++i) { a.U[i] = p.U[i]; a.U_dir[i] = p.U_dir[i]; }
-    a.rt = s->rt; a.tab_stride = s->rt_set.size() > 1 ? (long long)8 * g.plane_env : 0;
-    a.index = s->ep_index; a.ign = s->ep_ign; a.wind = s->ep_wind;
-    a.K = (p.flags & SF_EP_AGENTS) ? s->ag.k : 0;
-    a.start = s->ag_start; a.xyid = s->ag_xyid;
-    a.due_cnt = s->ep_due_cnt; a.due = s->ep_due; a.due_U = s->ep_due_U; a.due_D = s->ep_due_D;
-    if (wind) HIPCHK(hipMemsetAsync(s->ep_due_cnt, 0, sizeof(uint32_t), s->stream));
-    hipLaunchKernelGGL(k_episode_draw, dim3((unsigned)g.E), dim3(kEpAttempts), 0, s->stream, a);
-    HIPCHK(hipGetLastError());
-    { int rc = reset_launch(s, nullptr, mask, s->ep_ign, g.E); if (rc) return rc; }
-    // (section 15's bookkeeping of the mask form: which environments were taken is known on the device only)
-    if (s->snap) std::fill(s->snap_valid.begin(), s->snap_valid.end(), 0);
-    if (wind) {
-        int rc = wind_launch(s, s->ep_due, s->ep_due_cnt, 0, g.E, s->ep_due_U, s->ep_due_D, 0, cached);
-        if (rc) return rc;
-        // rtc_stale as in sf_set_wind: where the cell-major buffer exists the pass has written the listed tables' copies too (a copy
-        // that was stale is no worse for it); where it does not, every table is marked stale when it is allocated (ensure_rtc)
-    }
-    return SF_OK;
-}
-
-extern "C" int sf_episodes_set(sf_sim *s, const sf_episode_params *p)
-{
-    const char *who = "sf_episodes_set";
-    if (!s) return fail(SF_EINVAL, "%s: null handle", who);
-    const Geo &g = s->g;
-    if (p) {
-        if (p->flags & ~(SF_EP_IGNITION | SF_EP_LIVE_CELL | SF_EP_WIND | SF_EP_AGENTS)) return fail(SF_EINVAL, "%s: unknown flags 0x%x", who, p->flags);
-        if (p->reserved != 0) return fail(SF_EINVAL, "%s: reserved must be 0", who);
-        if ((p->flags & SF_EP_LIVE_CELL) && !(p->flags & SF_EP_IGNITION)) return fail(SF_EINVAL, "%s: SF_EP_LIVE_CELL needs SF_EP_IGNITION", who);
-        const struct { int flag; const int32_t *box; const char *name; } boxes[2] = {{SF_EP_IGNITION, p->ign_box, "ign_box"}, {SF_EP_AGENTS, p->agent_box, "agent_box"}};
-        for (const auto &b : boxes)
-            if ((p->flags & b.flag) && (b.box[0] < 0 || b.box[1] < 0 || b.box[2] >= g.W || b.box[3] >= g.H || b.box[0] > b.box[2] || b.box[1] > b.box[3]))
-                return fail(SF_EINVAL, "%s: %s (%d, %d, %d, %d) is not x0 <= x1, y0 <= y1 on the %dx%d grid", who, b.name, b.box[0], b.box[1], b.box[2], b.box[3], g.H, g.W);
-        if (p->flags & SF_EP_WIND) {
-            const bool ok = std::isfinite(p->U[0]) && std::isfinite(p->U[1]) && std::isfinite(p->U_dir[0]) && std::isfinite(p->U_dir[1]) &&
-                            p->U[0] >= 0.0 && p->U[0] <= p->U[1] && p->U_dir[0] <= p->U_dir[1];
-            if (!ok) return fail(SF_EINVAL, "%s: wind ranges U [%g, %g], U_dir [%g, %g] must be finite with lo <= hi and U >= 0", who, p->U[0], p->U[1], p->U_dir[0], p->U_dir[1]);
-            if (!s->p.per_env_terrain) return fail(SF_ESTATE, "%s: SF_EP_WIND: this handle shares one terrain between all environments (create it with per_env_terrain = 1)", who);
-            for (size_t t = 0; t < s->rd_lay.size(); ++t)
-                if (!s->rd_lay[t]) return fail(SF_ESTATE, "%s: SF_EP_WIND: table %d has no layers (sf_set_layers*, sf_generate_layers)", who, (int)t);
-            if (!s->wind_sched.empty()) return fail(SF_ESTATE, "%s: SF_EP_WIND while a wind schedule is set (sf_set_wind_schedule): the two would fight over the table", who);
-        }
-        if (!(p->flags & SF_EP_IGNITION) && !(s->ag.k && s->ag_has_ign) && s->last_ign.empty())
-            return fail(SF_ESTATE, "%s: without SF_EP_IGNITION new episodes ignite where the environment last did: call sf_reset or sf_agents_create (with ignitions) first", who);
-    }
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    { int rc = episodes_free(s); if (rc) return rc; }
-    if (!p) return SF_OK;
-    // one allocation, every buffer on a 16-byte boundary: index | ign | wind | due | due_cnt | due_U | due_D | ones
-    const size_t E = (size_t)g.E;
-    const size_t sizes[8] = {E * 4, E * 8, E * 16, E * 4, 4, E * 8, E * 8, E};
-    size_t off[8], total = 0;
-    for (int i = 0; i < 8; ++i) { off[i] = total; total += (sizes[i] + 15) / 16 * 16; }
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&s->ep_mem), total));
-    s->ep_bytes = total; s->bytes += (int64_t)total;
-    s->ep_index = reinterpret_cast<uint32_t *>(s->ep_mem + off[0]);
-    s->ep_ign = reinterpret_cast<int32_t *>(s->ep_mem + off[1]);
-    s->ep_wind = reinterpret_cast<double *>(s->ep_mem + off[2]);
-    s->ep_due = reinterpret_cast<int32_t *>(s->ep_mem + off[3]);
-    s->ep_due_cnt = reinterpret_cast<uint32_t *>(s->ep_mem + off[4]);
-    s->ep_due_U = reinterpret_cast<double *>(s->ep_mem + off[5]);
-    s->ep_due_D = reinterpret_cast<double *>(s->ep_mem + off[6]);
-    s->ep_ones = s->ep_mem + off[7];
-    std::vector<uint8_t> h(total, 0);
-    memset(h.data() + off[7], 1, E);
-    const bool from_agents = s->ag.k && s->ag_has_ign;
-    if (!(p->flags & SF_EP_IGNITION) && !from_agents) memcpy(h.data() + off[1], s->last_ign.data(), E * 8);
-    HIPCHK(hipMemcpyAsync(s->ep_mem, h.data(), total, hipMemcpyHostToDevice, s->stream));
-    if (!(p->flags & SF_EP_IGNITION) && from_agents) HIPCHK(hipMemcpyAsync(s->ep_ign, s->ag_ign, E * 8, hipMemcpyDeviceToDevice, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));          // (h is pageable and leaves scope)
-    s->ep = *p;
-    s->ep_on = true;
-    s->ep_nocache = false;
-    return SF_OK;
-}
-
-extern "C" int sf_episodes_begin(sf_sim *s, const uint8_t *device_mask, int32_t all)
-{
-    const char *who = "sf_episodes_begin";
-    if (!s) return fail(SF_EINVAL, "%s: null handle", who);
-    if (!s->ep_on) return fail(SF_ESTATE, "%s: call sf_episodes_set first", who);
-    const bool tables = (s->ep.flags & (SF_EP_LIVE_CELL | SF_EP_WIND)) != 0;      // the draw reads, or the wind pass rebuilds, R tables
-    { int rc = begin_call(s, who, kStateCall | (tables ? kNeedRt : 0)); if (rc) return rc; }
-    { int rc = episode_begin(s, all ? s->ep_ones : device_mask); if (rc) return rc; }
-    return finish_call(s, nullptr, !s->async, nullptr);
-}
-
-extern "C" int sf_episodes_device(sf_sim *s, void **index, void **ignition, void **wind)
-{
-    if (!s) return fail(SF_EINVAL, "sf_episodes_device: null handle");
-    if (!index || !ignition || !wind) return fail(SF_EINVAL, "sf_episodes_device: null argument");
-    if (!s->ep_on) return fail(SF_ESTATE, "sf_episodes_device: call sf_episodes_set first");
-    *index = s->ep_index; *ignition = s->ep_ign; *wind = s->ep_wind;
-    return SF_OK;
-}
-
-static AgentArgs agent_args(const sf_sim *s, const int32_t *actions, const sf_agent_out *out)
-{
-    AgentArgs a;
-    memset(&a, 0, sizeof a);
-    a.g = s->g;
-    a.status = s->status;
-    a.cells = s->bl_cur ? s->cells : nullptr;        // (whichever plane is current NOW: the step between the two kernels may change it)
-    a.rows = s->status_block;
-    a.actions = actions;
-    a.xyid = s->ag_xyid; a.start = s->ag_start; a.points = s->ag_points; a.prev_cnt = s->ag_prev; a.terms = s->ag_terms;
-    a.ep_len = s->ag_len; a.ep_ret = s->ag_ret; a.done = s->ag_done;
-    a.K = s->ag.k; a.only_unburned = s->ag.only_unburned != 0; a.done_on_burn = s->ag.done_on_burn != 0;
-    a.max_ticks = s->ag.max_ticks; a.auto_reset = s->ag.auto_reset != 0;
-    for (int i = 0; i < 4; ++i) a.w[i] = (double)s->ag.w[i];
-    if (s->val_plane) {
-        a.damage = s->val_aux; a.damage_stride = (long long)sizeof(ValueRec);
-        a.tick_base = s->val_tick(0); a.tick_loss = s->val_tick(1);
-        a.wv = (double)s->val_w; a.wv_on = s->val_w_on ? 1 : 0;
-    }
-    if (out) { a.o_reward = out->reward; a.o_done = out->done; a.o_terms = out->terms; a.o_len = out->final_len; a.o_ret = out->final_ret; }
-    return a;
-}
-
-// One tick for every environment, nothing read back, every piece from the enqueue layer: result rows -> k_agents_act -> one update
-// with the device points, then the plain updates -> result rows -> k_agents_finish -> the batched reset with the done mask.
-extern "C" int sf_agents_step(sf_sim *s, const int32_t *device_actions, const sf_agent_out *out)
-{
-    if (!s) return fail(SF_EINVAL, "sf_agents_step: null handle");
-    if (!s->ag.k) return fail(SF_ESTATE, "sf_agents_step: call sf_agents_create first");
-    if (!device_actions) return fail(SF_EINVAL, "sf_agents_step: null actions");
-    const Geo &g = s->g;
-    { int rc = begin_call(s, "sf_agents_step", kNeedRt | kStateCall); if (rc) return rc; }
-    note_result_look(s);
-    int rc = refresh_status(s, nullptr);             // r0: the rows as a status query leaves them
-    const int32_t *pts = nullptr;
-    if (!rc) rc = stage_lines(s, 1, s->ag_points, s->ag.k, 1, &pts);
-    if (!rc) {
-        hipLaunchKernelGGL(k_agents_act, dim3((unsigned)g.E), dim3(kAgentsMax), 0, s->stream, agent_args(s, device_actions, out));
-        const StepPlan plan = plan_step(s, 1, true);         // one update with the device points: inside the resident launch, or a pair
-        rc = plan.nw ? enqueue_call(s, plan, 1, pts, s->ag.k, false, nullptr) : enqueue_pair(s, pts, s->ag.k, 0, nullptr);
-        if (!rc && s->arr_pending) rc = arrival_pass(s);
-    }
-    if (!rc) rc = step_impl(s, s->ag.n_updates - 1, false, nullptr);
-    if (!rc) { note_result_look(s); rc = refresh_status(s, nullptr); }      // r1 (commits the step rings too)
-    if (!rc) {
-        hipLaunchKernelGGL(k_agents_finish, dim3((unsigned)g.E), dim3(kAgentsMax), 0, s->stream, agent_args(s, device_actions, out));
-        if (s->ag.auto_reset && s->ep_on) rc = episode_begin(s, s->ag_done);      // section 19: the new episodes are drawn
-        else if (s->ag.auto_reset) {
-            rc = reset_launch(s, nullptr, s->ag_done, s->ag_ign, g.E);
-            // (section 15's bookkeeping of the mask form: which environments were taken is known on the device only)
-            if (!rc && s->snap) std::fill(s->snap_valid.begin(), s->snap_valid.end(), 0);
-        }
-    }
-    return rc ? rc : finish_call(s, "sf_agents_step", !s->async, nullptr);
-}
-
-extern "C" int sf_state_bytes(sf_sim *s, int64_t *bytes_out)
-{
-    if (!s || !bytes_out) return fail(SF_EINVAL, "sf_state_bytes: null argument");
-    *bytes_out = state_layout(s->g, s->parents != nullptr, s->arrival1 != nullptr).bytes;
-    return SF_OK;
-}
-
-extern "C" int sf_save_state(sf_sim *s, int32_t n, const int32_t *envs, void *out, int32_t device_pointer)
-{
-    if (!s) return fail(SF_EINVAL, "sf_save_state: null handle");
-    { int rc = state_list(s, n, envs, out, device_pointer, "sf_save_state", false); if (rc) return rc; }
-    if (n == 0) return SF_OK;
-    { int rc = begin_call(s, "sf_save_state", kStateCall); if (rc) return rc; }
-    // the result rows travel with the state: made current as a status query would, but a snapshot is not a look at the result of a
-    // single update (no note_result_look: the run(1)-loop heuristic stays as it was)
-    { int rc = refresh_status(s, nullptr); if (rc) return rc; }
-    StateArgs a = state_args(s);
-    a.hdr = state_header(s);
-    const int chunk = state_chunk(a, device_pointer != 0);
-    if (!device_pointer) { int rc = ensure_stage(s, (size_t)chunk * a.stride); if (rc) return rc; }
-    for (int i0 = 0; i0 < n; i0 += chunk) {
-        const int cnt = std::min(chunk, n - i0);
-        a.n = cnt;
-        for (int i = 0; i < cnt; ++i) a.env[i] = envs[i0 + i];
-        uint8_t *dst = device_pointer ? static_cast<uint8_t *>(out) + (size_t)i0 * a.stride : static_cast<uint8_t *>(s->stage);
-        a.blob = dst;
-        hipLaunchKernelGGL(k_state_pack, dim3((unsigned)((a.g.W + 255) / 256), (unsigned)a.g.H, (unsigned)cnt), dim3(256), 0, s->stream, a);
-        HIPCHK(hipGetLastError());
-        if (!device_pointer) {
-            HIPCHK(hipMemcpyAsync(static_cast<uint8_t *>(out) + (size_t)i0 * a.stride, s->stage, (size_t)cnt * a.stride, hipMemcpyDeviceToHost, s->stream));
-            HIPCHK(hipStreamSynchronize(s->stream));
-        }
-    }
-    if (device_pointer && !s->async) HIPCHK(hipStreamSynchronize(s->stream));
-    return check_team_error(s, "sf_save_state");
-}
-
-extern "C" int sf_load_state(sf_sim *s, int32_t n, const int32_t *envs, const void *in, int32_t device_pointer)
-{
-    if (!s) return fail(SF_EINVAL, "sf_load_state: null handle");
-    { int rc = state_list(s, n, envs, in, device_pointer, "sf_load_state", true); if (rc) return rc; }
-    if (n == 0) return SF_OK;
-    HIPCHK(hipSetDevice(s->p.device));
-    const long long bytes = state_layout(s->g, s->parents != nullptr, s->arrival1 != nullptr).bytes;
-    // every header is looked at before anything changes (a refused call leaves the handle as it was)
-    std::vector<StateHeader> hdr((size_t)n);
-    if (device_pointer) {
-        LOOP_QUIESCE(s);
-        HIPCHK(hipMemcpy2DAsync(hdr.data(), sizeof(StateHeader), in, (size_t)bytes, sizeof(StateHeader), (size_t)n, hipMemcpyDeviceToHost, s->stream));
-        HIPCHK(hipStreamSynchronize(s->stream));      // (the blobs may come from a save enqueued in front)
-    } else {
-        for (int i = 0; i < n; ++i) memcpy(&hdr[i], static_cast<const uint8_t *>(in) + (size_t)i * bytes, sizeof(StateHeader));
-    }
-    int fire_rows = 0;
-    for (int i = 0; i < n; ++i) {
-        int rc = header_check(s, hdr[i], i);
-        if (rc) return rc;
-        fire_rows = std::max(fire_rows, hdr[i].fire_rows > 0 ? hdr[i].fire_rows : INT32_MAX);
-    }
-    { int rc = begin_call(s, "sf_load_state", kStateCall); if (rc) return rc; }
-    const Geo &g = s->g;
-    StateArgs a = state_args(s);
-    const int chunk = state_chunk(a, device_pointer != 0);
-    if (!device_pointer) { int rc = ensure_stage(s, (size_t)chunk * a.stride); if (rc) return rc; }
-    const bool per_env_tiles = !s->bl_cur && s->tiles_valid;      // the tile maps / seams are kept: rebuild this environment's
-    const bool recount = g.ab == 1 && !s->generic && !s->tdirty_all;
-    EnvSeg seg[kEnvSegs];
-    const int n_seg = env_segs(s, kSegCells | kSegHint, seg);
-    for (int i0 = 0; i0 < n; i0 += chunk) {
-        const int cnt = std::min(chunk, n - i0);
-        a.n = cnt;
-        for (int i = 0; i < cnt; ++i) a.env[i] = envs[i0 + i];
-        if (device_pointer) a.blob = const_cast<uint8_t *>(static_cast<const uint8_t *>(in)) + (size_t)i0 * a.stride;
-        else {
-            HIPCHK(hipMemcpyAsync(s->stage, static_cast<const uint8_t *>(in) + (size_t)i0 * a.stride, (size_t)cnt * a.stride, hipMemcpyHostToDevice, s->stream));
-            a.blob = static_cast<uint8_t *>(s->stage);
-        }
-        for (int i = 0; i < cnt; ++i) {      // the cell planes start from zero: guard rows / quads and the pitch padding stay zero; so does the window advice (about a fire that is not there)
-            const int e = a.env[i];
-            for (int k = 0; k < n_seg; ++k) HIPCHK(hipMemsetAsync(seg[k].base + e * seg[k].stride, 0, (size_t)seg[k].len, s->stream));
-            if (recount) HIPCHK(hipMemsetAsync(s->tdirty + (size_t)e * g.TY * g.TX, 1, (size_t)g.TY * g.TX, s->stream));
-        }
-        hipLaunchKernelGGL(k_state_unpack, dim3((unsigned)((g.P + 255) / 256), (unsigned)g.H, (unsigned)cnt), dim3(256), 0, s->stream, a);
-        hipLaunchKernelGGL(k_state_vbits, dim3((unsigned)g.VW, (unsigned)g.H, (unsigned)cnt), dim3(64), 0, s->stream, a);
-        HIPCHK(hipGetLastError());
-        if (per_env_tiles)
-            for (int i = 0; i < cnt; ++i) {
-                int rc = rebuild_tflags(s, a.env[i], 1);
-                if (!rc) rc = rebuild_seams(s, a.env[i], 1);
-                if (rc) return rc;
-            }
-        if (!device_pointer) HIPCHK(hipStreamSynchronize(s->stream));      // (the staging buffer is reused by the next pass)
-    }
-    if (s->bl_cur) s->tiles_valid = false;
-    { int rc = wind_forget(s, envs, n); if (rc) return rc; }      // (a scheduled environment's table stands for the update count it had: decided anew)
-    for (int i = 0; i < n; ++i) if (s->snap) s->snap_valid[envs[i]] = 0;
-    // fire_rows bounds every environment's fire: the saving handle's bound covers a loaded one (a blob without one makes it unknown)
-    s->fire_rows = (s->fire_rows > 0 && fire_rows != INT32_MAX) ? std::max(s->fire_rows, fire_rows) : 0;
-    { int rc = value_recount(s); if (rc) return rc; }      // section 20: the restored planes say what counts
-    if (device_pointer && !s->async) HIPCHK(hipStreamSynchronize(s->stream));
-    return SF_OK;
-}
+#include "sf_host_agents.h"
 
 // The result block made current on the device (enqueue layer), also written to copy_to (may be null) and the registered sink.
 static int refresh_status(sf_sim *s, int32_t *copy_to)
@@ -3919,7 +1909,7 @@ static int refresh_status(sf_sim *s, int32_t *copy_to)
 // What a status query does first (call layer): the prologue, the note of the look, the refresh.
 static int status_query(sf_sim *s, const char *who, int32_t *copy_to)
 {
-    { int rc = begin_call(s, who, 0); if (rc) return rc; }
+    SF_TRY(begin_call(s, who, 0));
     note_result_look(s);
     return refresh_status(s, copy_to);
 }
@@ -3934,8 +1924,7 @@ extern "C" int sf_update_status_device(sf_sim *s)
 extern "C" int sf_get_status(sf_sim *s, int32_t *status, double *elapsed)
 {
     if (!s || !status) return fail(SF_EINVAL, "sf_get_status: null argument");
-    int rc = status_query(s, "sf_get_status", nullptr);
-    if (rc) return rc;
+    SF_TRY(status_query(s, "sf_get_status", nullptr));
     const size_t nb_st = sizeof(int32_t) * 8 * s->g.E, nb_el = sizeof(double) * s->g.E;
     if (!s->status_pinned) HIPCHK(hipHostMalloc(&s->status_pinned, nb_st + nb_el, hipHostMallocDefault));
     char *pin = (char *)s->status_pinned;
@@ -3997,90 +1986,7 @@ extern "C" int sf_set_result_sink(sf_sim *s, void *device_dst)
     return SF_OK;
 }
 
-// ---- the one collective: RCCL through dlopen, so that a one-GPU host needs no librccl
-namespace {
-struct RcclApi {
-    void *lib = nullptr;
-    ncclResult_t (*GetUniqueId)(ncclUniqueId *) = nullptr;
-    ncclResult_t (*CommInitRank)(ncclComm_t *, int, ncclUniqueId, int) = nullptr;
-    ncclResult_t (*AllGather)(const void *, void *, size_t, ncclDataType_t, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-    const char *(*GetErrorString)(ncclResult_t) = nullptr;
-};
-RcclApi g_rccl;
-int rccl_load()
-{
-    if (g_rccl.lib) return SF_OK;
-    // (SIMFIRE_RCCL_LIB: another library with the same five entry points - the tests' single-process stand-in, tests/fake_rccl.cpp,
-    // which lets 8 handles on ONE GPU play the 8 ranks of a node; never set in production)
-    const char *names[] = {getenv("SIMFIRE_RCCL_LIB"), "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
-    void *lib = nullptr;
-    for (const char *n : names) if (n && *n && (lib = dlopen(n, RTLD_NOW | RTLD_LOCAL))) break;
-    if (!lib) return fail(SF_ERCCL, "librccl.so could not be loaded: %s", dlerror());
-    RcclApi a;
-    a.lib = lib;
-    a.GetUniqueId = reinterpret_cast<decltype(a.GetUniqueId)>(dlsym(lib, "ncclGetUniqueId"));
-    a.CommInitRank = reinterpret_cast<decltype(a.CommInitRank)>(dlsym(lib, "ncclCommInitRank"));
-    a.AllGather = reinterpret_cast<decltype(a.AllGather)>(dlsym(lib, "ncclAllGather"));
-    a.CommDestroy = reinterpret_cast<decltype(a.CommDestroy)>(dlsym(lib, "ncclCommDestroy"));
-    a.GetErrorString = reinterpret_cast<decltype(a.GetErrorString)>(dlsym(lib, "ncclGetErrorString"));
-    if (!a.GetUniqueId || !a.CommInitRank || !a.AllGather || !a.CommDestroy || !a.GetErrorString) {
-        dlclose(lib);
-        return fail(SF_ERCCL, "librccl.so lacks one of ncclGetUniqueId / ncclCommInitRank / ncclAllGather / ncclCommDestroy / ncclGetErrorString");
-    }
-    g_rccl = a;
-    return SF_OK;
-}
-#define RCCLCHK(x) do { ncclResult_t _r = (x); if (_r != ncclSuccess) return fail(SF_ERCCL, "%s failed: %s", #x, g_rccl.GetErrorString(_r)); } while (0)
-}  // namespace
-
-extern "C" int sf_comm_unique_id(void *id_out)
-{
-    if (!id_out) return fail(SF_EINVAL, "sf_comm_unique_id: null argument");
-    static_assert(sizeof(ncclUniqueId) == 128, "the header promises 128 bytes");
-    { int rc = rccl_load(); if (rc) return rc; }
-    ncclUniqueId id;
-    RCCLCHK(g_rccl.GetUniqueId(&id));
-    std::memcpy(id_out, &id, sizeof id);
-    return SF_OK;
-}
-
-extern "C" int sf_comm_destroy(sf_sim *s) { return s ? comm_close(s) : fail(SF_EINVAL, "sf_comm_destroy: null handle"); }
-static int comm_close(sf_sim *s)
-{
-    if (!s->comm) return SF_OK;
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    HIPCHK(hipStreamSynchronize(s->stream));
-    ncclComm_t c = s->comm;
-    s->comm = nullptr; s->comm_world = 0;
-    RCCLCHK(g_rccl.CommDestroy(c));
-    return SF_OK;
-}
-
-extern "C" int sf_comm_init(sf_sim *s, int32_t rank, int32_t world_size, const void *unique_id)
-{
-    if (!s || !unique_id) return fail(SF_EINVAL, "sf_comm_init: null argument");
-    if (world_size < 1 || rank < 0 || rank >= world_size) return fail(SF_EINVAL, "sf_comm_init: rank %d of %d", rank, world_size);
-    { int rc = rccl_load(); if (rc) return rc; }
-    { int rc = comm_close(s); if (rc) return rc; }
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    ncclUniqueId id;
-    std::memcpy(&id, unique_id, sizeof id);
-    RCCLCHK(g_rccl.CommInitRank(&s->comm, world_size, id, rank));
-    s->comm_world = world_size;
-    return SF_OK;
-}
-
-extern "C" int sf_allgather_status(sf_sim *s, void *device_out)
-{
-    if (!s || !device_out) return fail(SF_EINVAL, "sf_allgather_status: null argument");
-    if (!s->comm) return fail(SF_ESTATE, "sf_allgather_status: call sf_comm_init first");
-    int rc = status_query(s, "sf_allgather_status", nullptr);      // the block of this rank's shard (fresh already after a resident launch)
-    if (rc) return rc;
-    // on the handle's stream: behind the steps in flight and the refresh, no host wait in between
-    RCCLCHK(g_rccl.AllGather(s->status_block, device_out, (size_t)8 * s->g.E, ncclInt32, s->comm, s->stream));
-    return finish_call(s, "sf_allgather_status", true, nullptr);
-}
+#include "sf_host_comm.h"
 
 extern "C" int sf_status_device(sf_sim *s, void **ptr)
 {
@@ -4103,236 +2009,6 @@ extern "C" int sf_fire_map_device(sf_sim *s, void **ptr, int64_t *row_pitch, int
     HIPCHK(hipStreamSynchronize(s->stream));
     *ptr = s->status; *row_pitch = s->g.P; *env_stride = s->g.plane_env;
     return SF_OK;
-}
-
-// ----------------------------------------------------------------------------- observations
-extern "C" int sf_cell_layout(sf_sim *s, int32_t *blocked)
-{
-    if (!s || !blocked) return fail(SF_EINVAL, "sf_cell_layout: null argument");
-    *blocked = s->bl_cur ? 1 : 0;
-    return SF_OK;
-}
-
-// Output cells per k_observe workgroup (TX x TY) for pool factor f and output width ow, and the LDS row stride of its staged region:
-// up to 256 outputs, fewer as f grows, so that the region (TY * f rows of whole vectors) fits kObsLds.
-struct ObsTile { int TX, TY, stride; };
-static ObsTile obs_tile(int f, int ow)
-{
-    int outs = kObsThreads;
-    while (outs > 1 && (long long)outs * f * f > 16384) outs >>= 1;
-    for (;;) {
-        int tx = 1;
-        while (tx * 2 <= outs && tx * 2 <= 64 && tx < ow) tx *= 2;
-        ObsTile t{tx, outs / tx, (tx * f + 30) / 16 * 16};
-        if ((long long)t.TY * f * t.stride <= kObsLds || outs == 1) return t;
-        outs >>= 1;
-    }
-}
-
-extern "C" int sf_observe(sf_sim *s, const sf_obs_params *p, int32_t n, const int32_t *envs, void *device_out)
-{
-    if (!s || !p) return fail(SF_EINVAL, "sf_observe: null argument");
-    const Geo &g = s->g;
-    if (n < 0 || (n > 0 && (!envs || !device_out))) return fail(SF_EINVAL, "sf_observe: bad environment list or output");
-    const int C = p->n_channels;
-    if (C < 1 || C > SF_OBS_MAX_CHANNELS) return fail(SF_EINVAL, "sf_observe: %d channels (1..%d)", C, SF_OBS_MAX_CHANNELS);
-    bool attr = false, agents = false;
-    for (int c = 0; c < C; ++c) {
-        if (p->channels[c] < SF_OBS_FIRE_MAP || p->channels[c] > SF_OBS_AGENTS)
-            return fail(SF_EINVAL, "sf_observe: channel %d has the unknown code %d", c, p->channels[c]);
-        if (p->pool_mode[c] != 0 && p->pool_mode[c] != 1) return fail(SF_EINVAL, "sf_observe: channel %d has the pool mode %d (0 mean, 1 max)", c, p->pool_mode[c]);
-        attr |= p->channels[c] >= SF_OBS_W_0 && p->channels[c] <= SF_OBS_WIND_DIRECTION;
-        agents |= p->channels[c] == SF_OBS_AGENTS;
-    }
-    const int f = p->pool;
-    if (f < 1 || f > SF_OBS_MAX_POOL) return fail(SF_EINVAL, "sf_observe: pool %d (1..%d)", f, SF_OBS_MAX_POOL);
-    const bool crop = p->crop_h != 0 || p->crop_w != 0;
-    if (crop && (p->crop_h < 1 || p->crop_w < 1 || p->crop_h > 65535 || p->crop_w > 65535))
-        return fail(SF_EINVAL, "sf_observe: crop %d x %d", p->crop_h, p->crop_w);
-    if (crop && !p->centers) return fail(SF_EINVAL, "sf_observe: a crop needs centers");
-    const int eh = crop ? p->crop_h : g.H, ew = crop ? p->crop_w : g.W;
-    if (eh % f || ew % f) return fail(SF_EINVAL, "sf_observe: the extent %d x %d is not divisible by pool %d", eh, ew, f);
-    if (p->dtype != 0 && p->dtype != 1) return fail(SF_EINVAL, "sf_observe: dtype %d (0 float32, 1 bfloat16)", p->dtype);
-    const int k = agents && p->agents ? p->agents_k : 0;
-    if (agents && p->agents && (p->agents_k < 0 || p->agents_k > SF_OBS_MAX_AGENTS))
-        return fail(SF_EINVAL, "sf_observe: %d agents per environment (0..%d)", p->agents_k, SF_OBS_MAX_AGENTS);
-    if ((uintptr_t)device_out & (p->dtype ? 1 : 3)) return fail(SF_EINVAL, "sf_observe: the output is not aligned to its element");
-    { int rc = check_envs(s, "sf_observe", n, envs); if (rc) return rc; }
-    if (n == 0) return SF_OK;
-    if (attr && !s->have_rt) return fail(SF_ESTATE, "sf_observe: attribute channels need the layers (sf_set_layers)");
-    { int rc = begin_call(s, "sf_observe", kNotVoid); if (rc) return rc; }
-    const int oh = eh / f, ow = ew / f;
-    const ObsTile tl = obs_tile(f, ow);
-    const long long tiles_x = (ow + tl.TX - 1) / tl.TX, tiles = tiles_x * ((oh + tl.TY - 1) / tl.TY);
-    if ((long long)n * tiles > 0x7FFFFFFFLL) return fail(SF_ENOTSUP, "sf_observe: %d environments x %lld tiles exceed the launch grid", n, tiles);
-
-    // the per-call block: ObsHead | envs [n] | centers [n][2] (host) | agents [n][k][3] (host)
-    const size_t o_envs = (sizeof(ObsHead) + 15) / 16 * 16, o_cen = o_envs + ((size_t)n * 4 + 15) / 16 * 16;
-    const bool cen_host = crop && !p->centers_device, ag_host = k > 0 && !p->agents_device;
-    const size_t o_ag = o_cen + (cen_host ? ((size_t)n * 8 + 15) / 16 * 16 : 0);
-    const size_t bytes = o_ag + (ag_host ? (size_t)n * k * 12 : 0);
-    CallBlock &blk = s->obs_blk;
-    { int rc = block_reserve(s, blk, bytes); if (rc) return rc; }
-    ObsHead h;
-    memset(&h, 0, sizeof h);
-    for (int c = 0; c < C; ++c) { h.code[c] = p->channels[c]; h.mode[c] = p->pool_mode[c]; }
-    // get_attribute_bounds (simulation.py:334-374; FuelConstants / ElevationConstants / WindConstants, enums.py:118-173) in the order of
-    // supported_attributes (simulation.py:317-332)
-    const double lo[7] = {0.0, 1.0, 0.2, 0.12, -282.0, 0.0, 0.0}, hi[7] = {1.0, 3500.0, 6.0, 1.0, 11000.0, 250.0, 360.0};
-    for (int a = 0; a < 7; ++a) { h.lo[a] = lo[a]; h.span[a] = hi[a] - lo[a]; }
-    memcpy(blk.pinned, &h, sizeof h);
-    memcpy(blk.pinned + o_envs, envs, (size_t)n * 4);
-    if (cen_host) memcpy(blk.pinned + o_cen, p->centers, (size_t)n * 8);
-    if (ag_host) memcpy(blk.pinned + o_ag, p->agents, (size_t)n * k * 12);
-    { int rc = block_send(s, blk, bytes); if (rc) return rc; }
-
-    ObsArgs a;
-    memset(&a, 0, sizeof a);
-    a.g = g;
-    a.status = s->status;
-    a.cells = s->bl_cur ? s->cells : nullptr;
-    a.lay = s->lay_all;
-    a.lay_tab = s->rt_set.size() > 1 ? 7LL * g.H * g.W : 0;
-    a.head = reinterpret_cast<const ObsHead *>(blk.dev);
-    a.envs = reinterpret_cast<const int32_t *>(blk.dev + o_envs);
-    a.centers = !crop ? nullptr : (cen_host ? reinterpret_cast<const int32_t *>(blk.dev + o_cen) : p->centers);
-    a.agents = k == 0 ? nullptr : (ag_host ? reinterpret_cast<const int32_t *>(blk.dev + o_ag) : p->agents);
-    a.out = device_out;
-    a.n = n; a.C = C; a.f = f; a.ch = eh; a.cw = ew; a.oh = oh; a.ow = ow; a.k = k;
-    a.TX = tl.TX; a.TY = tl.TY; a.tiles_x = (int)tiles_x; a.stride = tl.stride;
-    a.norm = p->normalize != 0; a.bf16 = p->dtype == 1; a.pad = p->pad;
-    hipLaunchKernelGGL(k_observe, dim3((unsigned)((long long)n * tiles)), dim3(kObsThreads), 0, s->stream, a);
-    return finish_call(s, "sf_observe", !s->async, nullptr);
-}
-
-// ----------------------------------------------------------------------------- frames
-// Output rows per k_render workgroup and its LDS bytes: the staged source rows (R * scale rows of P bytes) and the output bytes of the
-// band (channels last: one segment of R * ow * 3 bytes, else three of R * ow), each segment with 16 bytes of alignment slack.
-struct RenderTile { int R, st_bytes, out_seg, lds; };
-static RenderTile render_tile(const Geo &g, int scale, int oh, int ow, bool cl)
-{
-    constexpr int kBudget = 32768, kMax = 65536 - 256;
-    const auto make = [&](int R) {
-        RenderTile t;
-        t.R = R;
-        t.st_bytes = (R * scale * g.P + 15) / 16 * 16;
-        t.out_seg = cl ? (R * ow * 3 + 16 + 15) / 16 * 16 : (R * ow + 16 + 15) / 16 * 16;
-        t.lds = t.st_bytes + (cl ? 1 : 3) * t.out_seg;
-        return t;
-    };
-    int R = 1;
-    while (R < oh && make(R + 1).lds <= kBudget) ++R;
-    RenderTile t = make(R);
-    if (t.lds > kMax) t.R = 0;
-    return t;
-}
-
-extern "C" int sf_render(sf_sim *s, const sf_render_params *p, int32_t n, const int32_t *envs, void *device_out)
-{
-    if (!s || !p) return fail(SF_EINVAL, "sf_render: null argument");
-    const Geo &g = s->g;
-    if (n < 0 || (n > 0 && (!envs || !device_out))) return fail(SF_EINVAL, "sf_render: bad environment list or output");
-    if (p->source != SF_RENDER_CURRENT && p->source != SF_RENDER_HISTORY)
-        return fail(SF_EINVAL, "sf_render: source %d (0 current, 1 history)", p->source);
-    const bool hist = p->source == SF_RENDER_HISTORY;
-    if (hist && (p->first < 0 || p->count < 1)) return fail(SF_EINVAL, "sf_render: history frames %d from %d", p->count, p->first);
-    if (p->scale < 1 || p->scale > SF_RENDER_MAX_SCALE) return fail(SF_EINVAL, "sf_render: scale %d (1..%d)", p->scale, SF_RENDER_MAX_SCALE);
-    if (p->mode < SF_RENDER_NEAREST || p->mode > SF_RENDER_SPRITES) return fail(SF_EINVAL, "sf_render: mode %d (0 nearest, 1 mean, 2 sprites)", p->mode);
-    if (p->background != SF_RENDER_FUEL && p->background != SF_RENDER_WHITE)
-        return fail(SF_EINVAL, "sf_render: background %d (0 fuel, 1 white)", p->background);
-    if (p->contours != 0 && p->contours != 1) return fail(SF_EINVAL, "sf_render: contours %d (0 or 1)", p->contours);
-    if (p->channels_last != 0 && p->channels_last != 1) return fail(SF_EINVAL, "sf_render: channels_last %d (0 or 1)", p->channels_last);
-    for (int c = 0; c < 3; ++c)
-        if (p->terrain_rgb[c] < 0 || p->terrain_rgb[c] > 255) return fail(SF_EINVAL, "sf_render: terrain_rgb[%d] = %d (0..255)", c, p->terrain_rgb[c]);
-    const int k = p->agents ? p->agents_k : 0;
-    if (p->agents && (p->agents_k < 0 || p->agents_k > SF_RENDER_MAX_AGENTS))
-        return fail(SF_EINVAL, "sf_render: %d agents per environment (0..%d)", p->agents_k, SF_RENDER_MAX_AGENTS);
-    { int rc = check_envs(s, "sf_render", n, envs); if (rc) return rc; }
-    const int s_ = p->scale, oh = (g.H + s_ - 1) / s_, ow = (g.W + s_ - 1) / s_;
-    const bool cl = p->channels_last != 0;
-    const RenderTile tl = render_tile(g, s_, oh, ow, cl);
-    if (tl.R == 0) return fail(SF_ENOTSUP, "sf_render: a row of %d cells does not fit one workgroup's LDS", g.W);
-    const int count = hist ? p->count : 1;
-    const long long frames = (long long)n * count, bands = (oh + tl.R - 1) / tl.R;
-    if (frames * bands > 0x7FFFFFFFLL) return fail(SF_ENOTSUP, "sf_render: %lld frames x %lld bands exceed the launch grid", frames, bands);
-    if (hist && !s->history) return fail(SF_ESTATE, "sf_render: a history source needs sf_enable_history");
-    if (hist && p->count > s->history_cap)
-        return fail(SF_EINVAL, "sf_render: %d updates do not fit the history capacity %d", p->count, s->history_cap);
-    const int n_tab = (int)s->rt_set.size();
-    for (int i = 0; i < n; ++i)
-        if (!s->rd_lay[n_tab == 1 ? 0 : envs[i]]) return fail(SF_ESTATE, "sf_render: environment %d has no layers (sf_set_layers)", envs[i]);
-    if (n == 0) return SF_OK;
-    { int rc = begin_call(s, "sf_render", kNotVoid); if (rc) return rc; }
-
-    // which backgrounds to (re)build: the listed environments' stale tables; every functional one when the fuel colours were made
-    // from another terrain_rgb (only the fuel background shows them)
-    const int64_t rgb = p->terrain_rgb[0] | p->terrain_rgb[1] << 8 | p->terrain_rgb[2] << 16;
-    if (p->background == SF_RENDER_FUEL && rgb != s->rd_rgb) {
-        for (int t = 0; t < n_tab; ++t) if (!s->rd_fbfm[t]) s->rd_stale[t] = 1;
-        s->rd_rgb = rgb;
-    }
-    std::vector<int32_t> tabs, fb;
-    {
-        std::vector<char> want(n_tab, 0);
-        for (int i = 0; i < n; ++i) want[n_tab == 1 ? 0 : envs[i]] = 1;
-        for (int t = 0; t < n_tab; ++t)
-            if (want[t] && s->rd_stale[t]) { tabs.push_back(t); fb.push_back(s->rd_fbfm[t]); }
-    }
-    if (!s->rd_bg) HIPCHK(hipMalloc(reinterpret_cast<void **>(&s->rd_bg), (size_t)n_tab * g.H * g.W * sizeof(uint32_t)));
-
-    // the per-call block: envs [n] | tabs [nt] | fbfm [nt] | min / max [nt][2] | agents [n][k][3] (host)
-    const int nt = (int)tabs.size();
-    const auto up16 = [](size_t b) { return (b + 15) / 16 * 16; };
-    const bool ag_host = k > 0 && !p->agents_device;
-    const size_t o_tabs = up16((size_t)n * 4), o_fb = o_tabs + up16((size_t)nt * 4), o_mm = o_fb + up16((size_t)nt * 4);
-    const size_t o_ag = o_mm + (size_t)nt * 16, bytes = o_ag + (ag_host ? (size_t)n * k * 12 : 0);
-    CallBlock &blk = s->rd_blk;
-    { int rc = block_reserve(s, blk, bytes); if (rc) return rc; }
-    memcpy(blk.pinned, envs, (size_t)n * 4);
-    if (nt) { memcpy(blk.pinned + o_tabs, tabs.data(), (size_t)nt * 4); memcpy(blk.pinned + o_fb, fb.data(), (size_t)nt * 4); }
-    if (ag_host) memcpy(blk.pinned + o_ag, p->agents, (size_t)n * k * 12);
-    // (the lists, and the agents behind the min / max words: those are the kernels' to write)
-    { int rc = block_send(s, blk, o_mm, o_ag, ag_host ? (size_t)n * k * 12 : 0); if (rc) return rc; }
-
-    if (nt) {
-        RenderBgArgs b;
-        memset(&b, 0, sizeof b);
-        b.H = g.H; b.W = g.W;
-        b.lay = s->lay_all; b.lay_tab = 7LL * g.H * g.W;
-        b.fuel_ix = s->rd_fuel_ix;
-        b.tabs = reinterpret_cast<const int32_t *>(blk.dev + o_tabs);
-        b.fbfm = reinterpret_cast<const int32_t *>(blk.dev + o_fb);
-        b.mm = reinterpret_cast<double *>(blk.dev + o_mm);
-        b.bg = s->rd_bg;
-        b.base = (uint32_t)(s->rd_rgb < 0 ? rgb : s->rd_rgb);
-        for (int c = 0; c < kRdFbfmColours; ++c) {
-            uint32_t w = 0;
-            for (int ch = 0; ch < 3; ++ch) w |= (uint32_t)(uint8_t)(kRdFbfmRgb[c][ch] * 255.0) << (8 * ch);     // astype(np.uint8)
-            b.fbfm_rgb[c] = w;
-        }
-        hipLaunchKernelGGL(k_render_minmax, dim3((unsigned)nt), dim3(1024), 0, s->stream, b);
-        hipLaunchKernelGGL(k_render_bg, dim3((unsigned)g.H, (unsigned)nt), dim3(kRdThreads), 0, s->stream, b);
-        HIPCHK(hipGetLastError());
-        for (int t : tabs) s->rd_stale[t] = 0;
-    }
-
-    RenderArgs a;
-    memset(&a, 0, sizeof a);
-    a.g = g;
-    a.status = s->status;
-    a.cells = !hist && s->bl_cur ? s->cells : nullptr;
-    a.hist = hist ? s->history : nullptr;
-    a.cap = s->history_cap; a.first = hist ? p->first : 0; a.count = count;
-    a.bg = s->rd_bg;
-    a.bg_tab = n_tab > 1 ? (long long)g.H * g.W : 0;
-    a.envs = reinterpret_cast<const int32_t *>(blk.dev);
-    a.agents = k == 0 ? nullptr : (ag_host ? reinterpret_cast<const int32_t *>(blk.dev + o_ag) : p->agents);
-    a.out = static_cast<uint8_t *>(device_out);
-    a.n_frames = (int)frames; a.k = k;
-    a.s = s_; a.mode = p->mode; a.white = p->background == SF_RENDER_WHITE; a.contours = p->contours; a.cl = cl;
-    a.oh = oh; a.ow = ow; a.R = tl.R; a.stride = g.P; a.st_bytes = tl.st_bytes; a.out_seg = tl.out_seg;
-    hipLaunchKernelGGL(k_render, dim3((unsigned)(frames * bands)), dim3(kRdThreads), (unsigned)tl.lds, s->stream, a);
-    return finish_call(s, "sf_render", !s->async, nullptr);
 }
 
 extern "C" int sf_compute_ros(int64_t n, const float *loc_x, const float *loc_y, const float *new_loc_x,

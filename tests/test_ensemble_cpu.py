@@ -124,11 +124,13 @@ def test_header_declares_and_lib_binds_ensemble():
     assert C.sizeof(_lib.SfEnsembleOut) == 5 * C.sizeof(C.c_void_p) == 40
     assert [f[0] for f in _lib.SfEnsembleOut._fields_] == ["count", "prob", "first", "mean", "loss"]
     csrc = os.path.join(ROOT, "simfire_amd", "csrc")
-    src = open(os.path.join(csrc, "simfire_hip.hip")).read()
+    # the host code of the main unit: simfire_hip.hip and the fragments it includes (sf_handle.h, sf_host_*.h)
+    host = sorted(f for f in os.listdir(csrc) if f == "simfire_hip.hip" or f == "sf_handle.h" or f.startswith("sf_host_"))
+    src = "".join(open(os.path.join(csrc, f)).read() for f in host)
     assert re.search(r'extern "C" int sf_ensemble_stats\(', src)
     # the kernel is the main unit's alone; the step path and the two passes do not know it
     for unit in sorted(os.listdir(csrc)):
-        if unit.endswith((".hip", ".h")) and unit not in ("simfire_hip.hip", "sf_ensemble_kernels.h"):
+        if unit.endswith((".hip", ".h")) and unit not in host and unit != "sf_ensemble_kernels.h":
             body = open(os.path.join(csrc, unit)).read()
             assert "sf_ensemble_kernels.h" not in body and "k_ensemble" not in body, unit
     assert src.count('#include "sf_ensemble_kernels.h"') == 1

@@ -133,7 +133,8 @@ def test_segment_capacity_covers_the_largest_selection():
     trip counts, the cells of the current layout by the larger branch - and summed over the kinds a fork and a batched reset name."""
     csrc = os.path.join(ROOT, "simfire_amd", "csrc")
     header = open(os.path.join(csrc, "sf_env_segs.h")).read()
-    host = open(os.path.join(csrc, "simfire_hip.hip")).read()
+    # (the host code of the main unit: simfire_hip.hip and the fragments it includes)
+    host = "".join(open(os.path.join(csrc, f)).read() for f in sorted(f for f in os.listdir(csrc) if f == "simfire_hip.hip" or f == "sf_handle.h" or f.startswith("sf_host_")))
     kinds = re.findall(r"^\s*(kSeg\w+) = 1u << \d+,", header, re.M)
     assert len(kinds) == len(set(kinds)) >= 14
     cap = int(re.search(r"constexpr int kEnvSegs = (\d+);", header).group(1))

@@ -93,7 +93,8 @@ def test_header_declares_and_lib_binds_values():
         assert len(_lib.SIGNATURES[name]) == n, name
     # existing structs stay four wide
     assert re.search(r"float\s+w\[4\]", text) and "sf_values_set" in text[text.index("Values at risk"):]
-    src = open(os.path.join(ROOT, "simfire_amd", "csrc", "simfire_hip.hip")).read()
+    csrc = os.path.join(ROOT, "simfire_amd", "csrc")      # the host code of the main unit: simfire_hip.hip and the fragments it includes
+    src = "".join(open(os.path.join(csrc, f)).read() for f in sorted(f for f in os.listdir(csrc) if f == "simfire_hip.hip" or f == "sf_handle.h" or f.startswith("sf_host_")))
     for name in ENTRIES + LAB_ENTRIES:
         assert re.search(r'extern "C" int %s\(' % name, src), name
     # the kernels are this unit's alone, and the pass hangs behind the arrival pass
