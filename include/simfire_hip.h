@@ -424,6 +424,45 @@ typedef struct sf_obs_params {
  * (the tensor is complete when the handle's stream has got there); the caller orders its own work on device_out before the call. */
 int sf_observe(sf_sim *sim, const sf_obs_params *params, int32_t n, const int32_t *envs, void *device_out);
 
+/* Distance fields: how far every cell - or every one of a list of points - is from the nearest burning cell,
+ * control line or unburned cell.  The reference has no counterpart; the semantics are this library's own, exact and in integers.
+ * For a listed environment, the source set S is every cell (y, x), x < width, whose status byte & 7 is selected by status_mask (bit s
+ * selects BurnStatus s, enums.py:52-69), read from whichever cell plane is current.
+ *   d2[y][x] = min over S of (y - y')^2 + (x - x')^2 as int32; an empty S gives SF_DIST_FAR.  With max_d2 > 0 every value is
+ *   min(d2, max_d2) (an empty S then gives max_d2 everywhere); max_d2 = 0: no cap.
+ *   SF_DIST_I32: that value.  SF_DIST_F32: (float)(sqrt((double)value) / scale) - sqrt and divide in IEEE double, one rounding to
+ *   float32 - bit for bit (np.sqrt(v.astype(np.float64)) / scale).astype(np.float32).
+ *   Plane form (k = 0): out[n][height][width], dense.  Point form (1 <= k <= SF_DIST_MAX_POINTS): points is device int32 [n][k][3] =
+ *   (column, row, id) - the layout of sf_agents_device, which can be passed as it is when envs is every environment in order - and
+ *   the result is out[n][k]; an entry with id <= 0 or a cell off the grid gives -1 (-1.0f).
+ * Ties and nearest-cell indices are not reported: distances only. */
+#define SF_DIST_FAR 2147483647
+#define SF_DIST_I32 0
+#define SF_DIST_F32 1
+#define SF_DIST_MAX_POINTS 256
+typedef struct sf_dist_params {
+    int32_t status_mask;           /* 1..63: bit s selects BurnStatus s                                                       */
+    int32_t max_d2;                /* >= 0: the cap on the squared distance, 0 = none                                         */
+    int32_t dtype;                 /* SF_DIST_I32 / SF_DIST_F32                                                                */
+    int32_t k;                     /* 0: plane form; 1..SF_DIST_MAX_POINTS: points per listed environment                      */
+    double scale;                  /* SF_DIST_F32: the divisor (cells per unit), finite and > 0                                */
+    const int32_t *points;         /* device int32 [n][k][3], or NULL with k == 0                                              */
+    int64_t scratch_bytes;         /* the most scratch the call may use; 0: the default budget of 128 MiB                      */
+    int32_t reserved[2];           /* 0                                                                                        */
+} sf_dist_params;
+/* Environment envs[i] (a host array; any order, repeats allowed) lands in out[i].  Anything invalid is SF_EINVAL before anything is
+ * enqueued (a mask outside 1..63, max_d2 < 0, an unknown dtype, k outside 0..256, k > 0 without points, a scale that is not finite
+ * or <= 0, reserved != 0, an output that is not 4-byte aligned, an environment out of range, a positive scratch_bytes smaller than
+ * one environment's scratch plane of height * pitch * 2 bytes); a handle without layers or reset is SF_ESTATE; a grid with
+ * (height - 1)^2 + (width - 1)^2 >= SF_DIST_FAR or wider than 8192 cells is SF_ENOTSUP.  The call reads the state and writes
+ * nothing but device_out and the library's scratch plane - not the current plane, the tile books, the reference point of
+ * sf_get_fire_map_delta, the result block, any ring, the arrival or value planes.  The scratch plane belongs to the handle: allocated
+ * at the first call, grown (never shrunk) when a later call needs more, freed by sf_destroy - a growth is a hipMalloc and waits for
+ * the device; the list is worked through in chunks so that scratch never exceeds the budget, which changes no bit of the result.
+ * In async mode the call only enqueues (the tensor is complete when the handle's stream has got there); the caller orders its own
+ * work on points and device_out before the call. */
+int sf_distance(sf_sim *sim, const sf_dist_params *params, int32_t n, const int32_t *envs /* [n] host */, void *device_out);
+
 /* Agents on the device: K agents per environment that walk the grid and draw control lines where they stand,
  * stepped from a policy's action tensor without a host read.  The reference records agent positions only (simulation.py:480-499) and
  * leaves the loop to the harness (the run docstring, 505-509); the semantics are this library's own.

@@ -108,6 +108,15 @@ class SfEnsembleOut(C.Structure):
     _fields_ = [("count", C.c_void_p), ("prob", C.c_void_p), ("first", C.c_void_p), ("mean", C.c_void_p), ("loss", C.c_void_p)]
 
 
+SF_DIST_FAR, SF_DIST_I32, SF_DIST_F32, SF_DIST_MAX_POINTS = 2 ** 31 - 1, 0, 1, 256
+
+
+class SfDistParams(C.Structure):
+    """``sf_dist_params`` (include/simfire_hip.h)."""
+    _fields_ = [("status_mask", C.c_int32), ("max_d2", C.c_int32), ("dtype", C.c_int32), ("k", C.c_int32), ("scale", C.c_double),
+                ("points", C.c_void_p), ("scratch_bytes", C.c_int64), ("reserved", C.c_int32 * 2)]
+
+
 # name -> argtypes; every function returns int except the two string getters
 _VP, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
 SIGNATURES = {
@@ -175,6 +184,7 @@ SIGNATURES = {
     "sf_get_status": [_VP, _VP, _VP],
     "sf_fire_map_device": [_VP, C.POINTER(_VP), C.POINTER(_I64), C.POINTER(_I64)],
     "sf_observe": [_VP, C.POINTER(SfObsParams), _I32, _VP, _VP],
+    "sf_distance": [_VP, C.POINTER(SfDistParams), _I32, _VP, _VP],
     "sf_cell_layout": [_VP, C.POINTER(_I32)],
     "sf_render": [_VP, C.POINTER(SfRenderParams), _I32, _VP, _VP],
     "sf_status_device": [_VP, C.POINTER(_VP)],

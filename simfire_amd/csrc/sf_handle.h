@@ -244,6 +244,16 @@ struct EpisodeState {
     }
 };
 
+// sf_distance: the scratch plane g (u16 [chunk][H][P], the vertical distances of the environments a call is
+// working on) - allocated at the first call, grown but never shrunk when a call's chunk needs more, freed with the handle - its size
+// in bytes, and the call block (the environment list of a call)
+struct DistState {
+    uint16_t *plane = nullptr;
+    size_t cap = 0;
+    CallBlock blk;
+    hipError_t release() { cap = 0; return free_dev(plane); }
+};
+
 }  // namespace
 
 // ----------------------------------------------------------------------------- handle
@@ -341,6 +351,7 @@ struct sf_sim {
     WindState wind;
     AgentState agents;
     EpisodeState episodes;
+    DistState dist;
     CallBlock obs_blk;                 // sf_observe: ObsHead, environment list, host centers / agents
     CallBlock rs_blk;                  // sf_reset_envs / sf_reset_where: the environment list and host ignitions of a call
     LabTimer reset_timer;              // sf_time_resets: ev0 / ev1 recorded around the launches of every batched reset

@@ -463,6 +463,88 @@ extern "C" int sf_observe(sf_sim *s, const sf_obs_params *p, int32_t n, const in
     return finish_call(s, "sf_observe", !s->async, nullptr);
 }
 
+// ----------------------------------------------------------------------------- distance fields
+// The environment list goes through the feature's call block; the list is then worked through in chunks of as many environments as
+// the scratch budget holds planes of g: per chunk the two column passes and k_dist_rows (plane form) or k_dist_points.  All of it on
+// the handle's stream, so a chunk's passes follow the chunk before it; no state of the handle changes but the scratch plane.
+extern "C" int sf_distance(sf_sim *s, const sf_dist_params *p, int32_t n, const int32_t *envs, void *device_out)
+{
+    if (!s || !p) return fail(SF_EINVAL, "sf_distance: null argument");
+    const Geo &g = s->g;
+    if (n < 0 || (n > 0 && (!envs || !device_out))) return fail(SF_EINVAL, "sf_distance: bad environment list or output");
+    if (p->status_mask < 1 || p->status_mask > 63) return fail(SF_EINVAL, "sf_distance: status_mask %d (bit s selects BurnStatus s: 1..63)", p->status_mask);
+    if (p->max_d2 < 0) return fail(SF_EINVAL, "sf_distance: max_d2 %d (0: no cap)", p->max_d2);
+    if (p->dtype != SF_DIST_I32 && p->dtype != SF_DIST_F32) return fail(SF_EINVAL, "sf_distance: dtype %d (0 int32, 1 float32)", p->dtype);
+    if (p->k < 0 || p->k > SF_DIST_MAX_POINTS) return fail(SF_EINVAL, "sf_distance: %d points per environment (0..%d)", p->k, SF_DIST_MAX_POINTS);
+    if (p->k > 0 && !p->points) return fail(SF_EINVAL, "sf_distance: k = %d needs points", p->k);
+    if (!std::isfinite(p->scale) || !(p->scale > 0.0)) return fail(SF_EINVAL, "sf_distance: scale must be finite and > 0");
+    if (p->reserved[0] != 0 || p->reserved[1] != 0) return fail(SF_EINVAL, "sf_distance: reserved must be 0");
+    if ((uintptr_t)device_out & 3) return fail(SF_EINVAL, "sf_distance: the output is not aligned to its element");
+    const size_t plane = (size_t)g.plane_env * sizeof(uint16_t);          // one environment's g
+    if (p->scratch_bytes < 0 || (p->scratch_bytes > 0 && (size_t)p->scratch_bytes < plane))
+        return fail(SF_EINVAL, "sf_distance: scratch_bytes %lld is less than one environment's plane (%zu bytes)", (long long)p->scratch_bytes, plane);
+    SF_TRY(check_envs(s, "sf_distance", n, envs));
+    if ((long long)(g.H - 1) * (g.H - 1) + (long long)(g.W - 1) * (g.W - 1) >= (long long)SF_DIST_FAR)
+        return fail(SF_ENOTSUP, "sf_distance: squared distances on a %d x %d grid do not fit int32", g.H, g.W);
+    if (g.W > kDistMaxWidth) return fail(SF_ENOTSUP, "sf_distance: grids wider than %d cells are not supported (width %d)", kDistMaxWidth, g.W);
+    SF_TRY(begin_call(s, "sf_distance", kNeedRt | kNeedReset | kNotVoid));
+    if (n == 0) return SF_OK;
+
+    const size_t budget = p->scratch_bytes > 0 ? (size_t)p->scratch_bytes : (size_t)kDistScratchDefault;
+    const int chunk = (int)std::min<size_t>({(size_t)n, budget / plane, (size_t)32768});      // (32768: the launch grid's y)
+    DistState &d = s->dist;
+    if ((size_t)chunk * plane > d.cap) {              // growing waits for the device: enqueued kernels may still use the plane
+        HIPCHK(hipStreamSynchronize(s->stream));
+        s->bytes -= (int64_t)d.cap;
+        HIPCHK(d.release());
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&d.plane), (size_t)chunk * plane));
+        d.cap = (size_t)chunk * plane;
+        s->bytes += (int64_t)d.cap;
+    }
+    const size_t bytes = (size_t)n * sizeof(int32_t);
+    SF_TRY(block_reserve(s, d.blk, bytes));
+    memcpy(d.blk.pinned, envs, bytes);
+    SF_TRY(block_send(s, d.blk, bytes));
+
+    DistArgs a;
+    memset(&a, 0, sizeof a);
+    a.g = g;
+    a.status = s->status;
+    a.cells = s->bl_cur ? s->cells : nullptr;
+    a.gp = d.plane;
+    a.k = p->k;
+    for (int st = 0; st < 8; ++st)
+        if (st < 6 && ((p->status_mask >> st) & 1)) (st < 4 ? a.tlo : a.thi) |= 1u << (8 * (st & 3));
+    a.limit = p->max_d2 > 0 ? p->max_d2 : SF_DIST_FAR;
+    a.reach = g.W;
+    if (p->max_d2 > 0) {
+        a.reach = (int)std::sqrt((double)p->max_d2);
+        while ((long long)a.reach * a.reach < p->max_d2) a.reach++;
+        a.reach = std::min(a.reach, g.W);
+    }
+    a.f32 = p->dtype == SF_DIST_F32;
+    a.scale = p->scale;
+    a.vec = g.W % 4 == 0 && !((uintptr_t)device_out & 15);
+    a.rows = std::max(1, std::min({1024 / g.P, kDistMaxRows, g.H}));
+    const size_t per_env = (p->k ? (size_t)p->k : (size_t)g.H * g.W) * 4;      // output bytes per listed environment
+    for (int c0 = 0; c0 < n; c0 += chunk) {
+        a.cn = std::min(chunk, n - c0);
+        a.envs = reinterpret_cast<const int32_t *>(d.blk.dev) + c0;
+        a.out = static_cast<uint8_t *>(device_out) + (size_t)c0 * per_env;
+        a.points = p->k ? p->points + (size_t)c0 * p->k * 3 : nullptr;
+        const unsigned col_blocks = (unsigned)(((long long)a.cn * g.PV + kDistColsThreads - 1) / kDistColsThreads);
+        hipLaunchKernelGGL(k_dist_cols_down, dim3(col_blocks), dim3(kDistColsThreads), 0, s->stream, a);
+        hipLaunchKernelGGL(k_dist_cols_up, dim3(col_blocks), dim3(kDistColsThreads), 0, s->stream, a);
+        if (p->k)
+            hipLaunchKernelGGL(k_dist_points, dim3((unsigned)((p->k + kDistRowsThreads / 64 - 1) / (kDistRowsThreads / 64)), (unsigned)a.cn),
+                               dim3(kDistRowsThreads), 0, s->stream, a);
+        else
+            hipLaunchKernelGGL(k_dist_rows, dim3((unsigned)((g.H + a.rows - 1) / a.rows), (unsigned)a.cn), dim3(kDistRowsThreads),
+                               (size_t)a.rows * g.P * sizeof(int32_t), s->stream, a);
+    }
+    return finish_call(s, "sf_distance", !s->async, nullptr);
+}
+
 // ----------------------------------------------------------------------------- frames
 // Output rows per k_render workgroup and its LDS bytes: the staged source rows (R * scale rows of P bytes) and the output bytes of the
 // band (channels last: one segment of R * ow * 3 bytes, else three of R * ow), each segment with 16 bytes of alignment slack.

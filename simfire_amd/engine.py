@@ -902,6 +902,117 @@ class FireEngine:
             self._blobs_in_flight.extend([out] + spec.device_tensors())
         return out
 
+    # ---------------------------------------------------------------- distance fields
+    DIST_FAR = _lib.SF_DIST_FAR
+    DIST_MAX_POINTS = _lib.SF_DIST_MAX_POINTS
+
+    @staticmethod
+    def _distance_request(status, max_dist=None, max_d2=None, dtype="float32", scale=1.0, scratch_bytes=0):
+        """The checked scalar arguments of ``distance``: (status mask, max_d2, dtype code, scale, scratch_bytes).  ``ValueError`` on
+        anything the library would refuse, before it is called."""
+        from .enums import BurnStatus
+
+        def bit(s):
+            if isinstance(s, str):
+                if s not in BurnStatus.__members__:
+                    raise ValueError(f"distance: unknown BurnStatus name {s!r}")
+                return 1 << int(BurnStatus[s])
+            if isinstance(s, (bool, float)) or not isinstance(s, (int, np.integer)) or not 0 <= int(s) <= 5:
+                raise ValueError(f"distance: {s!r} is no BurnStatus (a member, a name or 0..5)")
+            return 1 << int(s)
+        if isinstance(status, (int, np.integer)) and not isinstance(status, (bool, BurnStatus)):
+            mask = int(status)
+        elif isinstance(status, (str, BurnStatus)):
+            mask = bit(status)
+        else:
+            try:
+                items = list(status)
+            except TypeError:
+                raise ValueError(f"distance: status must be a mask 1..63 or BurnStatus members, names or ints, got {status!r}") from None
+            mask = 0
+            for s in items:
+                mask |= bit(s)
+        if not 1 <= mask <= 63:
+            raise ValueError(f"distance: the status mask {mask} selects nothing or more than BurnStatus 0..5 (1..63)")
+        if max_dist is not None and max_d2 is not None:
+            raise ValueError("distance: give max_dist or max_d2, not both")
+        d2 = 0
+        if max_dist is not None:
+            if isinstance(max_dist, (bool, float)) or not isinstance(max_dist, (int, np.integer)) or not 1 <= int(max_dist) <= 46340:
+                raise ValueError(f"distance: max_dist must be an integer number of cells 1..46340 or None, got {max_dist!r}")
+            d2 = int(max_dist) ** 2
+        elif max_d2 is not None:
+            if isinstance(max_d2, (bool, float)) or not isinstance(max_d2, (int, np.integer)) or not 1 <= int(max_d2) <= 2 ** 31 - 1:
+                raise ValueError(f"distance: max_d2 must be an integer 1..2**31 - 1 or None, got {max_d2!r}")
+            d2 = int(max_d2)
+        name = getattr(dtype, "name", None) or str(dtype).replace("torch.", "")
+        if name not in ("int32", "float32"):
+            raise ValueError(f"distance: dtype must be 'int32' or 'float32', got {dtype!r}")
+        try:
+            sc = float(scale)
+        except (TypeError, ValueError):
+            raise ValueError(f"distance: scale must be a number, got {scale!r}") from None
+        if not np.isfinite(sc) or sc <= 0.0:
+            raise ValueError(f"distance: scale must be finite and > 0, got {scale!r}")
+        if isinstance(scratch_bytes, (bool, float)) or not isinstance(scratch_bytes, (int, np.integer)) or int(scratch_bytes) < 0:
+            raise ValueError(f"distance: scratch_bytes must be an integer >= 0, got {scratch_bytes!r}")
+        return mask, d2, (_lib.SF_DIST_I32 if name == "int32" else _lib.SF_DIST_F32), sc, int(scratch_bytes)
+
+    def distance(self, status, envs=None, max_dist=None, points=None, dtype="float32", scale=1.0, out=None, scratch_bytes=0, max_d2=None):
+        """How far the cells - or ``points`` - of ``envs`` (default: all, in order; any order, repeats allowed) are from the nearest cell
+        whose BurnStatus ``status`` selects (``sf_distance``), exact, read from whichever cell plane is current -
+        nothing is converted, no state of the handle changes.  ``status``: a mask (bit s = BurnStatus s, 1..63) or an iterable of
+        ``BurnStatus`` members, names or ints.  ``max_dist``: an integer number of cells R, values are capped at R (``max_d2`` = R * R;
+        the keyword ``max_d2`` takes a cap that is no square); ``None``: no cap, and a grid without a selected cell gives ``DIST_FAR``
+        squared.  ``dtype``: "int32" - the squared distance - or "float32": ``sqrt(d2) / scale``.  ``points``: a torch CUDA int32
+        tensor [n, k, 3] = (column, row, id) with k <= 256, e.g. ``agents_device()``; an entry with id <= 0 or off the grid gives -1.
+        Returns a torch tensor [n, H, W], or [n, k] with points, on this GPU; ``out``: a tensor to fill instead.  ``scratch_bytes``: the
+        most scratch the call may use (0: 128 MiB); less than one environment's plane (H * pitch * 2 bytes) is a ``ValueError``.  Torch's
+        queued work is waited for first; in async mode the call only enqueues: the tensor is complete after ``sync()`` and kept alive
+        until then."""
+        mask, d2, code, sc, scratch = self._distance_request(status, max_dist, max_d2, dtype, scale, scratch_bytes)
+        if envs is None:
+            e = np.arange(self.n_envs, dtype=np.int32)
+        else:
+            e = np.asarray(envs)
+            if e.ndim != 1 or (e.size and e.dtype.kind not in "iu"):
+                raise ValueError("distance: envs must be a list of environment numbers")
+            e = np.ascontiguousarray(e, dtype=np.int32)
+            if e.size and (e.min() < 0 or e.max() >= self.n_envs):
+                raise ValueError(f"distance: environment {int(e[(e < 0) | (e >= self.n_envs)][0])} out of range (n_envs = {self.n_envs})")
+        n = int(e.shape[0])
+        import torch
+        dev = torch.device(f"cuda:{self.params.device}")
+        k = 0
+        tensors = []
+        if points is not None:
+            if not isinstance(points, torch.Tensor) or not points.is_cuda or points.dtype != torch.int32 or points.dim() != 3 \
+                    or points.shape[0] != n or points.shape[2] != 3 or not 1 <= points.shape[1] <= self.DIST_MAX_POINTS:
+                raise ValueError(f"distance: points must be a CUDA int32 tensor of shape ({n}, k, 3) with 1 <= k <= {self.DIST_MAX_POINTS}")
+            if points.device != dev:
+                raise ValueError(f"distance: points on {points.device}, the simulation runs on {dev}")
+            points = points.contiguous()
+            k = int(points.shape[1])
+            tensors.append(points)
+        shape = (n, k) if k else (n, self.H, self.W)
+        tdtype = torch.int32 if code == _lib.SF_DIST_I32 else torch.float32
+        if out is None:
+            out = torch.empty(shape, dtype=tdtype, device=dev)
+        elif not isinstance(out, torch.Tensor) or out.dtype != tdtype or tuple(out.shape) != shape or out.device != dev or not out.is_contiguous():
+            raise ValueError(f"distance: out must be a contiguous {tdtype} tensor of shape {shape} on {dev}")
+        plane = self.H * ((self.W + 15) // 16 * 16) * 2
+        if 0 < scratch < plane:
+            raise ValueError(f"distance: scratch_bytes {scratch} is less than one environment's plane ({plane} bytes)")
+        if n == 0:
+            return out
+        p = _lib.SfDistParams(status_mask=mask, max_d2=d2, dtype=code, k=k, scale=sc, points=points.data_ptr() if k else None,
+                              scratch_bytes=scratch)
+        torch.cuda.synchronize(dev)
+        self._chk(self._L.sf_distance(self._h, C.byref(p), n, _ptr(e), C.c_void_p(out.data_ptr())))
+        if self.async_mode:
+            self._blobs_in_flight.extend([out] + tensors)
+        return out
+
     def render(self, envs=None, scale=1, mode=None, background="fuel", contours=True, terrain_rgb=None, agents=None, channels_last=True,
                history=None, out=None):
         """Frames of ``envs`` (default: all, in order; repeats allowed) as a uint8 torch tensor [n, oh, ow, 3] (or [n, 3, oh, ow]) on

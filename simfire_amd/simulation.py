@@ -586,6 +586,15 @@ class FireSimulation:
         return self._engine.observe(channels, envs=envs, normalize=normalize, pool=pool, pool_mode=pool_mode, crop=crop, centers=centers,
                                     agents=agents, pad=pad, dtype=dtype, out=out)
 
+    def distance_to(self, status=("BURNING",), max_dist=None, squared=False) -> np.ndarray:
+        """The distance in cells from every cell to the nearest cell whose BurnStatus is one of ``status`` (members, names or ints):
+        NumPy float32 [H, W], capped at ``max_dist`` cells (``None``: no cap); ``squared``: the exact squared distance as int32.
+        Host edits of ``fire_map`` are pushed to the device first, as ``run`` does (``BatchedFireSimulation.distance_to``)."""
+        self._sync_to_device()
+        d = self._engine.distance(status, envs=[0], max_dist=max_dist, dtype="int32" if squared else "float32")
+        self._engine.sync()
+        return d[0].cpu().numpy()
+
     # -------------------------------------------------------------------- seeds / layers
     def get_seeds(self) -> Dict[str, Optional[int]]:
         """simulation.py:574-597: only the seeds that exist for the configured generators."""
@@ -1298,6 +1307,18 @@ class BatchedFireSimulation:
         simulation.  ``out``: fill this tensor instead."""
         return self._engine.render(envs=envs, scale=scale, mode=mode, background=background, contours=contours, terrain_rgb=terrain_rgb,
                                    agents=agents, channels_last=channels_last, out=out)
+
+    def distance_to(self, status=("BURNING",), envs=None, max_dist=None, agents=None, squared=False, device=True):
+        """The distance in cells from every cell of ``envs`` (default: all) to the nearest cell whose BurnStatus is one of ``status``
+        (members, names or ints; or a mask): float32 [n, H, W], capped at ``max_dist`` cells (an integer; ``None``: no cap).  With
+        ``agents`` - a torch CUDA int32 tensor [n, k, 3] = (column, row, id) such as the device positions of a ``BatchedFireEnv`` -
+        the distance from those cells only: [n, k], -1 for an entry with id <= 0 or off the grid.  ``squared``: the exact squared
+        distance as int32 instead (``FireEngine.DIST_FAR`` where nothing is selected and there is no cap).  ``device=True`` returns a
+        torch tensor on this GPU, else a NumPy array; complete on return either way (one wait).  One call, no host copy of the maps,
+        no change to the simulation."""
+        d = self._engine.distance(status, envs=envs, max_dist=max_dist, points=agents, dtype="int32" if squared else "float32")
+        self._engine.sync()
+        return d if device else d.cpu().numpy()
 
     def refresh_fire_maps_device(self) -> None:
         """Bring the plane behind ``fire_maps_device()``'s tensor up to date (the same tensor then shows the current maps)."""

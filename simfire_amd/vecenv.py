@@ -40,10 +40,16 @@ class BatchedFireEnv:
     tick's fire reached, a view of the device buffer the next ``step`` overwrites.  ``value_weight``: the reward gets the fifth term
     ``value_weight * value_lost``.  Both default to off: calls and outputs are what they are without them.
 
+    ``fire_distance``: ``None``, or a dict with ``status`` (BurnStatus members, names or ints; default BURNING) and ``max_dist`` (an
+    integer number of cells, default no cap): ``info["fire_distance"]`` is then float32 [n_envs, n_agents], the distance in cells from
+    every agent to the nearest selected cell (``FireEngine.distance``), taken from the state the observation
+    shows - after a tick that re-ignited an environment, the new episode's.  Off by default: calls and ``info`` are what they are
+    without it.
+
     Agents are not part of an environment's state: ``clone_envs`` / ``get_state`` / ``set_state`` do not carry them."""
 
     def __init__(self, sim, n_agents, start_xy, n_updates=1, weights=(-1, 0, 0, 0), only_unburned=True, done_on_burn=False,
-                 max_ticks=0, auto_reset=True, obs=None, values=None, value_weight=None):
+                 max_ticks=0, auto_reset=True, obs=None, values=None, value_weight=None, fire_distance=None):
         self.sim = sim
         self.engine = sim._engine
         self.n_envs, self.n_agents = int(sim.n_envs), int(n_agents)
@@ -62,6 +68,12 @@ class BatchedFireEnv:
             raise ValueError("BatchedFireEnv: obs needs channels")
         if "agents" in self.obs_kwargs or "envs" in self.obs_kwargs:
             raise ValueError("BatchedFireEnv: obs takes the agents from the device and always shows every environment")
+        self.fire_distance = None
+        if fire_distance is not None:
+            if not isinstance(fire_distance, dict) or set(fire_distance) - {"status", "max_dist"}:
+                raise ValueError("BatchedFireEnv: fire_distance is None or a dict of status and max_dist")
+            self.fire_distance = dict(status=fire_distance.get("status", ("BURNING",)), max_dist=fire_distance.get("max_dist"))
+            sim._engine._distance_request(**self.fire_distance)       # (raises on a bad status or cap before anything is created)
         self.engine.agents_create(self.n_agents, sim.ignitions, n_updates=n_updates, weights=weights, only_unburned=only_unburned,
                                   done_on_burn=done_on_burn, max_ticks=max_ticks, auto_reset=auto_reset)
         self.values_on = values is not None
@@ -75,10 +87,13 @@ class BatchedFireEnv:
         self._all = np.arange(self.n_envs, dtype=np.int32)
         self.engine.agents_place(self._all, self.start_xy, also_start=True)      # (raises on a cell off the grid)
 
-    def _observe(self):
+    def _observe(self, info=None):
         """The observation, complete: the one wait for the handle's stream of a ``reset`` / ``step`` (the outputs of ``agents_step``
-        enqueued before it are complete then, too)."""
+        enqueued before it are complete then, too).  With ``fire_distance`` and an ``info`` dict, the agents' distances are enqueued
+        in front of that wait and put into it."""
         obs = self.sim.observe(agents=self.engine.agents_device(), **self.obs_kwargs)
+        if info is not None and self.fire_distance is not None:
+            info["fire_distance"] = self.engine.distance(points=self.engine.agents_device(), dtype="float32", **self.fire_distance)
         self.engine.sync()
         return obs
 
@@ -114,7 +129,7 @@ class BatchedFireEnv:
         final_ret = torch.empty(E, dtype=torch.float64, device=dev)
         self.engine.agents_step(actions, reward=reward, done=done, terms=terms, final_len=final_len, final_ret=final_ret)
         info = dict(terms=terms, final_len=final_len, final_ret=final_ret)
-        obs = self._observe()
+        obs = self._observe(info)
         if self.values_on:
             info["value_lost"] = self.engine.values_torch()[1]
         return obs, reward, done, info
