@@ -463,6 +463,57 @@ typedef struct sf_dist_params {
  * work on points and device_out before the call. */
 int sf_distance(sf_sim *sim, const sf_dist_params *params, int32_t n, const int32_t *envs /* [n] host */, void *device_out);
 
+/* Reach of the fire: the cells the fire can still get to - the flood fill of the seed cells through the open
+ * cells - its size, its worth under the value plane, its mask, and whether given points lie in it.  The reference has
+ * no counterpart; the semantics are this library's own.
+ * For a listed environment, s(y, x) is the status byte & 7 of cell (y, x), x < width, read from whichever cell plane is current.
+ *   seed(y, x) = bit s of source_mask.  open(y, x) = bit s of through_mask and, with a passable plane, passable[y][x] != 0 (device u8,
+ *   dense [height * width], one plane for all or - passable_per_env - one per environment, indexed by the environment's number).
+ *   The two masks are disjoint.  The neighbourhood N is the 8-neighbourhood (connectivity 8) or the 4-neighbourhood (4);
+ *   connectivity 0 takes the handle's own diagonal_spread.
+ *   R is the smallest set with: c in R  iff  open(c) and some n in N(c) is a seed or is in R.
+ *   The pitch padding (x >= width) is never open and never a seed.
+ * The spread rule (fire.py:163-234, 550-589) ignites a cell only next to a BURNING cell, and only an UNBURNED cell or a control
+ * line.  So with source_mask = BURNING, through_mask = UNBURNED | FIRELINE | SCRATCHLINE | WETLINE and connectivity 0, R holds every
+ * cell that becomes BURNING in any later update, for as long as nothing but stepping changes the map: an upper bound, not a forecast.
+ * With through_mask = UNBURNED the same holds as long as no control-line cell ignites (lines ignite only under attenuate_line_ros).
+ * Points: device int32 [n][k][3] = (column, row, id), sf_agents_device's layout, as sf_distance takes them. */
+typedef struct sf_reach_params {
+    int32_t source_mask, through_mask;   /* 1..63, disjoint */
+    int32_t connectivity;                /* 0 (the handle's diagonal_spread), 4, 8 */
+    int32_t k;                           /* 0, or 1..SF_DIST_MAX_POINTS points per listed environment */
+    int32_t max_rounds;                  /* 0: to the fixed point; > 0: stop after that many rounds */
+    int32_t passable_per_env;            /* passable is [n_envs][H*W] (indexed by environment number), else [H*W] */
+    const uint8_t *passable;             /* device, or NULL */
+    const int32_t *points;               /* device int32 [n][k][3] = (column, row, id), sf_agents_device's layout; NULL with k == 0 */
+    int64_t scratch_bytes;               /* 0: the default budget */
+    int32_t reserved[2];                 /* 0 */
+} sf_reach_params;
+typedef struct sf_reach_out {            /* device pointers, any may be NULL, at least one not */
+    int32_t *count;      /* [n]        |R| */
+    int64_t *value;      /* [n]        sum of the value plane over R (sf_values_set; the environment's own plane under per_env) */
+    uint8_t *mask;       /* [n][H][W]  1 in R, else 0; dense */
+    int32_t *seeds;      /* [n]        number of seed cells (0: nothing burning - the reach is empty because there is no fire) */
+    int32_t *point_in;   /* [n][k]     1 / 0; -1 for id <= 0 or a cell off the grid */
+    int32_t *rounds;     /* [n]        rounds taken; negated when max_rounds stopped the fill before the fixed point */
+} sf_reach_out;
+/* Environment envs[i] (a host array; any order, repeats allowed) lands in row i of every output.  Anything invalid is SF_EINVAL before
+ * anything is enqueued (overlapping masks or a mask outside 1..63, an unknown connectivity, k outside 0..256, k > 0 without points,
+ * point_in without k, max_rounds < 0, reserved != 0, every output null, an output that is not aligned to its element - 4 bytes, 8 for
+ * value -, an environment out of range, a positive scratch_bytes below one environment's need); value without a value plane, or a
+ * handle without layers or reset, is SF_ESTATE; a grid wider than 8192 cells is SF_ENOTSUP.
+ * One workgroup fills one environment in rounds until nothing changes; max_rounds > 0 stops after that many: mask, count, value and
+ * point_in then describe the cells reached so far, a subset of R, and rounds is negative.
+ * The call reads the state and writes nothing but its outputs and its own scratch - not the current plane, the tile books, the
+ * reference point of sf_get_fire_map_delta, the result block, any ring, the arrival or value planes.  The scratch belongs to the
+ * handle: per listed environment of a chunk two bit planes and a halo, 16 * ceil(height / 16) * ceil(pitch / 64) * 16 bytes + 20 per
+ * band of 16 rows x 64 cells, rounded up to 256; allocated at the first call, grown (never shrunk) when a later call needs more,
+ * freed by sf_destroy, counted by sf_memory_bytes - a growth is a hipMalloc and waits for the device.  The default budget is 256 MiB;
+ * the list is worked through in chunks so that scratch never exceeds the budget, which changes no bit of the result.
+ * In async mode the call only enqueues (the outputs are complete when the handle's stream has got there); the caller orders its own
+ * work on passable, points and the outputs before the call. */
+int sf_reach(sf_sim *sim, const sf_reach_params *params, int32_t n, const int32_t *envs /* [n] host */, const sf_reach_out *out);
+
 /* Agents on the device: K agents per environment that walk the grid and draw control lines where they stand,
  * stepped from a policy's action tensor without a host read.  The reference records agent positions only (simulation.py:480-499) and
  * leaves the loop to the harness (the run docstring, 505-509); the semantics are this library's own.

@@ -117,6 +117,19 @@ class SfDistParams(C.Structure):
                 ("points", C.c_void_p), ("scratch_bytes", C.c_int64), ("reserved", C.c_int32 * 2)]
 
 
+class SfReachParams(C.Structure):
+    """``sf_reach_params`` (include/simfire_hip.h)."""
+    _fields_ = [("source_mask", C.c_int32), ("through_mask", C.c_int32), ("connectivity", C.c_int32), ("k", C.c_int32),
+                ("max_rounds", C.c_int32), ("passable_per_env", C.c_int32), ("passable", C.c_void_p), ("points", C.c_void_p),
+                ("scratch_bytes", C.c_int64), ("reserved", C.c_int32 * 2)]
+
+
+class SfReachOut(C.Structure):
+    """``sf_reach_out`` (include/simfire_hip.h): device pointers, any may be null, not all."""
+    _fields_ = [("count", C.c_void_p), ("value", C.c_void_p), ("mask", C.c_void_p), ("seeds", C.c_void_p), ("point_in", C.c_void_p),
+                ("rounds", C.c_void_p)]
+
+
 # name -> argtypes; every function returns int except the two string getters
 _VP, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
 SIGNATURES = {
@@ -185,6 +198,7 @@ SIGNATURES = {
     "sf_fire_map_device": [_VP, C.POINTER(_VP), C.POINTER(_I64), C.POINTER(_I64)],
     "sf_observe": [_VP, C.POINTER(SfObsParams), _I32, _VP, _VP],
     "sf_distance": [_VP, C.POINTER(SfDistParams), _I32, _VP, _VP],
+    "sf_reach": [_VP, C.POINTER(SfReachParams), _I32, _VP, C.POINTER(SfReachOut)],
     "sf_cell_layout": [_VP, C.POINTER(_I32)],
     "sf_render": [_VP, C.POINTER(SfRenderParams), _I32, _VP, _VP],
     "sf_status_device": [_VP, C.POINTER(_VP)],

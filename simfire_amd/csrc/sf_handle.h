@@ -254,6 +254,16 @@ struct DistState {
     hipError_t release() { cap = 0; return free_dev(plane); }
 };
 
+// sf_reach: the scratch of the fill (per listed environment of a chunk: two bit planes and the halo,
+// reach_env_bytes) - allocated at the first call, grown but never shrunk, freed with the handle - its size in bytes, and the call
+// block (the environment list of a call)
+struct ReachState {
+    uint8_t *mem = nullptr;
+    size_t cap = 0;
+    CallBlock blk;
+    hipError_t release() { cap = 0; return free_dev(mem); }
+};
+
 }  // namespace
 
 // ----------------------------------------------------------------------------- handle
@@ -352,6 +362,7 @@ struct sf_sim {
     AgentState agents;
     EpisodeState episodes;
     DistState dist;
+    ReachState reach;
     CallBlock obs_blk;                 // sf_observe: ObsHead, environment list, host centers / agents
     CallBlock rs_blk;                  // sf_reset_envs / sf_reset_where: the environment list and host ignitions of a call
     LabTimer reset_timer;              // sf_time_resets: ev0 / ev1 recorded around the launches of every batched reset
@@ -379,6 +390,7 @@ static int destroy(sf_sim *s);
 static int ensure_rm(sf_sim *s);
 static int value_pass(sf_sim *s);
 static int wind_forget(sf_sim *s, const int32_t *envs, int n);
+static hipError_t allow_lds(const sf_sim *s, const void *fn, size_t lds);
 
 // Behind every wait for the handle's stream: has a workgroup of a team launch (k_run<TEAM>) given up waiting for a team member?
 // Then what the launch left behind is void - say so wherever data is handed back, not only in sf_sync / a synchronous sf_step.

@@ -545,6 +545,107 @@ extern "C" int sf_distance(sf_sim *s, const sf_dist_params *p, int32_t n, const 
     return finish_call(s, "sf_distance", !s->async, nullptr);
 }
 
+// ----------------------------------------------------------------------------- reach of the fire
+// The environment list goes through the feature's call block; the list is then worked through in chunks of as many environments as
+// the scratch budget holds (reach_env_bytes each), one k_reach launch per chunk with one workgroup per listed environment.  All of
+// it on the handle's stream; no state of the handle changes but the scratch.
+extern "C" int sf_reach(sf_sim *s, const sf_reach_params *p, int32_t n, const int32_t *envs, const sf_reach_out *out)
+{
+    if (!s || !p || !out) return fail(SF_EINVAL, "sf_reach: null argument");
+    const Geo &g = s->g;
+    if (n < 0 || (n > 0 && !envs)) return fail(SF_EINVAL, "sf_reach: bad environment list");
+    if (p->source_mask < 1 || p->source_mask > 63) return fail(SF_EINVAL, "sf_reach: source_mask %d (bit s selects BurnStatus s: 1..63)", p->source_mask);
+    if (p->through_mask < 1 || p->through_mask > 63) return fail(SF_EINVAL, "sf_reach: through_mask %d (bit s selects BurnStatus s: 1..63)", p->through_mask);
+    if (p->source_mask & p->through_mask) return fail(SF_EINVAL, "sf_reach: source_mask %d and through_mask %d overlap", p->source_mask, p->through_mask);
+    if (p->connectivity != 0 && p->connectivity != 4 && p->connectivity != 8)
+        return fail(SF_EINVAL, "sf_reach: connectivity %d (0: the handle's diagonal_spread, 4, 8)", p->connectivity);
+    if (p->k < 0 || p->k > SF_DIST_MAX_POINTS) return fail(SF_EINVAL, "sf_reach: %d points per environment (0..%d)", p->k, SF_DIST_MAX_POINTS);
+    if (p->k > 0 && !p->points) return fail(SF_EINVAL, "sf_reach: k = %d needs points", p->k);
+    if (out->point_in && p->k == 0) return fail(SF_EINVAL, "sf_reach: point_in needs k > 0");
+    if (p->max_rounds < 0) return fail(SF_EINVAL, "sf_reach: max_rounds %d (0: to the fixed point)", p->max_rounds);
+    if (p->reserved[0] != 0 || p->reserved[1] != 0) return fail(SF_EINVAL, "sf_reach: reserved must be 0");
+    if (!out->count && !out->value && !out->mask && !out->seeds && !out->point_in && !out->rounds)
+        return fail(SF_EINVAL, "sf_reach: every output is null");
+    if (((uintptr_t)out->count | (uintptr_t)out->seeds | (uintptr_t)out->point_in | (uintptr_t)out->rounds) & 3 || ((uintptr_t)out->value & 7))
+        return fail(SF_EINVAL, "sf_reach: an output is not aligned to its element");
+    const size_t need = (size_t)reach_env_bytes(g);
+    if (p->scratch_bytes < 0 || (p->scratch_bytes > 0 && (size_t)p->scratch_bytes < need))
+        return fail(SF_EINVAL, "sf_reach: scratch_bytes %lld is less than one environment's need (%zu bytes)", (long long)p->scratch_bytes, need);
+    SF_TRY(check_envs(s, "sf_reach", n, envs));
+    if (g.W > kReachMaxWidth) return fail(SF_ENOTSUP, "sf_reach: grids wider than %d cells are not supported (width %d)", kReachMaxWidth, g.W);
+    SF_TRY(check_ready(s, "sf_reach", kNeedRt | kNeedReset));
+    if (out->value && !s->values.plane) return fail(SF_ESTATE, "sf_reach: value needs a value plane (sf_values_set)");
+    SF_TRY(begin_call(s, "sf_reach", kNeedRt | kNeedReset | kNotVoid));
+    if (n == 0) return SF_OK;
+
+    const size_t budget = p->scratch_bytes > 0 ? (size_t)p->scratch_bytes : (size_t)kReachScratchDefault;
+    const int chunk = (int)std::min<size_t>({(size_t)n, std::max<size_t>(budget / need, 1), (size_t)65535});
+    ReachState &r = s->reach;
+    if ((size_t)chunk * need > r.cap) {               // growing waits for the device: enqueued kernels may still use the scratch
+        HIPCHK(hipStreamSynchronize(s->stream));
+        s->bytes -= (int64_t)r.cap;
+        HIPCHK(r.release());
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&r.mem), (size_t)chunk * need));
+        r.cap = (size_t)chunk * need;
+        s->bytes += (int64_t)r.cap;
+    }
+    // the call block: the environment list | one ReachArgs per chunk (the kernel takes its arguments from there)
+    const int chunks = (n + chunk - 1) / chunk;
+    const size_t o_args = ((size_t)n * sizeof(int32_t) + 15) / 16 * 16, bytes = o_args + (size_t)chunks * sizeof(ReachArgs);
+    SF_TRY(block_reserve(s, r.blk, bytes));
+    memcpy(r.blk.pinned, envs, (size_t)n * sizeof(int32_t));
+
+    ReachArgs a;
+    memset(&a, 0, sizeof a);
+    a.g = g;
+    a.status = s->status;
+    a.cells = s->bl_cur ? s->cells : nullptr;
+    a.passable = p->passable;
+    a.pass_env = p->passable_per_env ? (long long)g.H * g.W : 0;
+    a.pass_vec = p->passable && g.W % 16 == 0 && !((uintptr_t)p->passable & 15);
+    a.vals = out->value ? s->values.plane : nullptr;
+    a.val_env = s->values.per_env ? g.plane_env : 0;
+    a.k = p->k;
+    a.scratch = r.mem;
+    a.scratch_env = (long long)need;
+    for (int st = 0; st < 6; ++st) {
+        if ((p->source_mask >> st) & 1) (st < 4 ? a.slo : a.shi) |= 1u << (8 * (st & 3));
+        if ((p->through_mask >> st) & 1) (st < 4 ? a.tlo : a.thi) |= 1u << (8 * (st & 3));
+    }
+    a.conn8 = p->connectivity == 0 ? g.diag : (p->connectivity == 8);
+    a.max_rounds = p->max_rounds;
+    a.WORDS = reach_words(g); a.BR = reach_band_rows(g); a.nb = a.BR * a.WORDS;
+    a.mask_vec = out->mask && g.W % 16 == 0 && !((uintptr_t)out->mask & 15);
+    for (int c = 0; c < chunks; ++c) {
+        const int c0 = c * chunk;
+        a.envs = reinterpret_cast<const int32_t *>(r.blk.dev) + c0;
+        a.points = p->k ? p->points + (size_t)c0 * p->k * 3 : nullptr;
+        a.count = out->count ? out->count + c0 : nullptr;
+        a.value = out->value ? reinterpret_cast<long long *>(out->value) + c0 : nullptr;
+        a.mask = out->mask ? out->mask + (size_t)c0 * g.H * g.W : nullptr;
+        a.seeds = out->seeds ? out->seeds + c0 : nullptr;
+        a.point_in = out->point_in ? out->point_in + (size_t)c0 * p->k : nullptr;
+        a.rounds = out->rounds ? out->rounds + c0 : nullptr;
+        memcpy(r.blk.pinned + o_args + (size_t)c * sizeof(ReachArgs), &a, sizeof a);
+    }
+    SF_TRY(block_send(s, r.blk, bytes));
+
+    // one band per thread: F stays in registers for the whole fill (k_reach<true>); else passes of 1024 bands over the scratch planes.
+    // Either way a thread's open words lie in LDS: 136 - 156 KiB at 1024 threads, one workgroup per CU (which 1024 threads are anyway)
+    const bool resident = a.nb <= kReachThreads;
+    const unsigned threads = resident ? (unsigned)((a.nb + 63) / 64 * 64) : (unsigned)kReachThreads;
+    const size_t lds = reach_lds_bytes((int)threads, resident);
+    const void *fn = resident ? reinterpret_cast<const void *>(&k_reach<true>) : reinterpret_cast<const void *>(&k_reach<false>);
+    HIPCHK(allow_lds(s, fn, lds));
+    for (int c = 0; c < chunks; ++c) {
+        const ReachArgs *ap = reinterpret_cast<const ReachArgs *>(r.blk.dev + o_args) + c;
+        const unsigned cn = (unsigned)std::min(chunk, n - c * chunk);
+        if (resident) hipLaunchKernelGGL(k_reach<true>, dim3(cn), dim3(threads), lds, s->stream, ap);
+        else hipLaunchKernelGGL(k_reach<false>, dim3(cn), dim3(threads), lds, s->stream, ap);
+    }
+    return finish_call(s, "sf_reach", !s->async, nullptr);
+}
+
 // ----------------------------------------------------------------------------- frames
 // Output rows per k_render workgroup and its LDS bytes: the staged source rows (R * scale rows of P bytes) and the output bytes of the
 // band (channels last: one segment of R * ow * 3 bytes, else three of R * ow), each segment with 16 bytes of alignment slack.

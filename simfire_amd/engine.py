@@ -907,18 +907,18 @@ class FireEngine:
     DIST_MAX_POINTS = _lib.SF_DIST_MAX_POINTS
 
     @staticmethod
-    def _distance_request(status, max_dist=None, max_d2=None, dtype="float32", scale=1.0, scratch_bytes=0):
-        """The checked scalar arguments of ``distance``: (status mask, max_d2, dtype code, scale, scratch_bytes).  ``ValueError`` on
-        anything the library would refuse, before it is called."""
+    def _status_mask(who, status, what="status"):
+        """A set of BurnStatus values as the mask the library takes (bit s = BurnStatus s, 1..63): ``status`` is that mask, a member,
+        a name, or an iterable of members, names or ints.  ``ValueError`` (named after the caller, ``who``) on anything else."""
         from .enums import BurnStatus
 
         def bit(s):
             if isinstance(s, str):
                 if s not in BurnStatus.__members__:
-                    raise ValueError(f"distance: unknown BurnStatus name {s!r}")
+                    raise ValueError(f"{who}: unknown BurnStatus name {s!r}")
                 return 1 << int(BurnStatus[s])
             if isinstance(s, (bool, float)) or not isinstance(s, (int, np.integer)) or not 0 <= int(s) <= 5:
-                raise ValueError(f"distance: {s!r} is no BurnStatus (a member, a name or 0..5)")
+                raise ValueError(f"{who}: {s!r} is no BurnStatus (a member, a name or 0..5)")
             return 1 << int(s)
         if isinstance(status, (int, np.integer)) and not isinstance(status, (bool, BurnStatus)):
             mask = int(status)
@@ -928,12 +928,19 @@ class FireEngine:
             try:
                 items = list(status)
             except TypeError:
-                raise ValueError(f"distance: status must be a mask 1..63 or BurnStatus members, names or ints, got {status!r}") from None
+                raise ValueError(f"{who}: {what} must be a mask 1..63 or BurnStatus members, names or ints, got {status!r}") from None
             mask = 0
             for s in items:
                 mask |= bit(s)
         if not 1 <= mask <= 63:
-            raise ValueError(f"distance: the status mask {mask} selects nothing or more than BurnStatus 0..5 (1..63)")
+            raise ValueError(f"{who}: the {what} mask {mask} selects nothing or more than BurnStatus 0..5 (1..63)")
+        return mask
+
+    @staticmethod
+    def _distance_request(status, max_dist=None, max_d2=None, dtype="float32", scale=1.0, scratch_bytes=0):
+        """The checked scalar arguments of ``distance``: (status mask, max_d2, dtype code, scale, scratch_bytes).  ``ValueError`` on
+        anything the library would refuse, before it is called."""
+        mask = FireEngine._status_mask("distance", status)
         if max_dist is not None and max_d2 is not None:
             raise ValueError("distance: give max_dist or max_d2, not both")
         d2 = 0
@@ -1012,6 +1019,122 @@ class FireEngine:
         if self.async_mode:
             self._blobs_in_flight.extend([out] + tensors)
         return out
+
+    # ---------------------------------------------------------------- reach of the fire
+    REACH_DEFAULT_SCRATCH = 256 << 20
+
+    @staticmethod
+    def _reach_request(source=("BURNING",), through=("UNBURNED",), connectivity=None, max_rounds=0, scratch_bytes=0):
+        """The checked scalar arguments of ``reach``: (source mask, through mask, connectivity code, max_rounds, scratch_bytes).
+        ``ValueError`` on anything the library would refuse, before it is called."""
+        src = FireEngine._status_mask("reach", source, "source")
+        thr = FireEngine._status_mask("reach", through, "through")
+        if src & thr:
+            raise ValueError(f"reach: source (mask {src}) and through (mask {thr}) must not share a BurnStatus")
+        if connectivity is None:
+            conn = 0
+        elif isinstance(connectivity, (bool, float)) or not isinstance(connectivity, (int, np.integer)) or int(connectivity) not in (0, 4, 8):
+            raise ValueError(f"reach: connectivity must be None (the simulation's diagonal_spread), 4 or 8, got {connectivity!r}")
+        else:
+            conn = int(connectivity)
+        if isinstance(max_rounds, (bool, float)) or not isinstance(max_rounds, (int, np.integer)) or not 0 <= int(max_rounds) < 2 ** 31:
+            raise ValueError(f"reach: max_rounds must be an integer >= 0, got {max_rounds!r}")
+        if isinstance(scratch_bytes, (bool, float)) or not isinstance(scratch_bytes, (int, np.integer)) or int(scratch_bytes) < 0:
+            raise ValueError(f"reach: scratch_bytes must be an integer >= 0, got {scratch_bytes!r}")
+        return src, thr, conn, int(max_rounds), int(scratch_bytes)
+
+    def reach_scratch_bytes(self):
+        """Bytes of scratch ``reach`` needs per listed environment of a chunk: two bit planes and the halo of the bands."""
+        bands = ((self.H + 15) // 16) * (((self.W + 15) // 16 * 16 + 63) // 64)
+        return (bands * 16 * 16 + bands * 20 + 255) // 256 * 256
+
+    def reach(self, source=("BURNING",), through=("UNBURNED",), envs=None, connectivity=None, passable=None, points=None, count=True,
+              value=False, mask=False, seeds=False, rounds=False, max_rounds=0, scratch_bytes=0):
+        """What the fire of ``envs`` (default: all, in order; any order, repeats allowed) can still get to (``sf_reach``; DESIGN.md
+        section 23): the flood fill of the cells whose BurnStatus ``source`` selects through the cells ``through`` selects - and, with
+        ``passable`` (a uint8 CUDA tensor [H, W] for all or [n_envs, H, W] indexed by environment number), only where it is not 0 -
+        over the 8- or 4-neighbourhood (``connectivity``; None: the simulation's ``diagonal_spread``).  ``source`` / ``through``: masks
+        (bit s = BurnStatus s) or iterables of ``BurnStatus`` members, names or ints, as for ``distance``; they must not overlap.  With
+        through = UNBURNED and the three lines the reach holds every cell that can ever burn as long as only stepping changes the map:
+        an upper bound, not a forecast.  Read from whichever cell plane is current; no state of the handle changes.
+        Returns a dict of torch tensors on this GPU, one per output asked for: ``count`` int32 [n], ``value`` int64 [n] (the value
+        plane of ``values_set`` summed over the reach), ``mask`` uint8 [n, H, W], ``seeds`` int32 [n] (source cells), ``rounds`` int32
+        [n] (negative: ``max_rounds`` > 0 stopped the fill early, the outputs are a subset), and with ``points`` - int32 CUDA
+        [n, k, 3] = (column, row, id), k <= 256, e.g. ``agents_device()`` - ``point_in`` int32 [n, k]: 1 / 0, -1 for id <= 0 or off
+        the grid.  ``scratch_bytes``: the most scratch the call may use (0: 256 MiB); less than ``reach_scratch_bytes()`` is a
+        ``ValueError``.  Torch's queued work is waited for first; in async mode the call only enqueues: the tensors are complete after
+        ``sync()`` and kept alive until then."""
+        src, thr, conn, mr, scratch = self._reach_request(source, through, connectivity, max_rounds, scratch_bytes)
+        if envs is None:
+            e = np.arange(self.n_envs, dtype=np.int32)
+        else:
+            e = np.asarray(envs)
+            if e.ndim != 1 or (e.size and e.dtype.kind not in "iu"):
+                raise ValueError("reach: envs must be a list of environment numbers")
+            e = np.ascontiguousarray(e, dtype=np.int32)
+            if e.size and (e.min() < 0 or e.max() >= self.n_envs):
+                raise ValueError(f"reach: environment {int(e[(e < 0) | (e >= self.n_envs)][0])} out of range (n_envs = {self.n_envs})")
+        n = int(e.shape[0])
+        want = dict(count=count, value=value, mask=mask, seeds=seeds, rounds=rounds)
+        for name, flag in want.items():
+            if not isinstance(flag, (bool, np.bool_)):
+                raise ValueError(f"reach: {name} must be True or False, got {flag!r}")
+        if not any(want.values()) and points is None:
+            raise ValueError("reach: nothing asked for (count, value, mask, seeds, rounds or points)")
+        if value and not getattr(self, "values_on", False):
+            raise ValueError("reach: value needs a value plane (values_set)")
+        need = self.reach_scratch_bytes()
+        if 0 < scratch < need:
+            raise ValueError(f"reach: scratch_bytes {scratch} is less than one environment's need ({need} bytes)")
+        if self.W > 8192:
+            raise ValueError(f"reach: grids wider than 8192 cells are not supported (width {self.W})")
+        import torch
+        if passable is not None and (not isinstance(passable, torch.Tensor) or not passable.is_cuda or passable.dtype != torch.uint8
+                                     or tuple(passable.shape) not in ((self.H, self.W), (self.n_envs, self.H, self.W))):
+            raise ValueError(f"reach: passable must be a CUDA uint8 tensor of shape ({self.H}, {self.W}) or ({self.n_envs}, {self.H}, {self.W})")
+        if points is not None and (not isinstance(points, torch.Tensor) or not points.is_cuda or points.dtype != torch.int32 or points.dim() != 3
+                                   or points.shape[0] != n or points.shape[2] != 3 or not 1 <= points.shape[1] <= self.DIST_MAX_POINTS):
+            raise ValueError(f"reach: points must be a CUDA int32 tensor of shape ({n}, k, 3) with 1 <= k <= {self.DIST_MAX_POINTS}")
+        dev = torch.device(f"cuda:{self.params.device}")
+        tensors = []
+        per_env = 0
+        if passable is not None:
+            if passable.device != dev:
+                raise ValueError(f"reach: passable on {passable.device}, the simulation runs on {dev}")
+            per_env = int(passable.dim() == 3)
+            passable = passable.contiguous()
+            tensors.append(passable)
+        k = 0
+        if points is not None:
+            if points.device != dev:
+                raise ValueError(f"reach: points on {points.device}, the simulation runs on {dev}")
+            points = points.contiguous()
+            k = int(points.shape[1])
+            tensors.append(points)
+        res = {}
+        if count:
+            res["count"] = torch.empty((n,), dtype=torch.int32, device=dev)
+        if value:
+            res["value"] = torch.empty((n,), dtype=torch.int64, device=dev)
+        if mask:
+            res["mask"] = torch.empty((n, self.H, self.W), dtype=torch.uint8, device=dev)
+        if seeds:
+            res["seeds"] = torch.empty((n,), dtype=torch.int32, device=dev)
+        if k:
+            res["point_in"] = torch.empty((n, k), dtype=torch.int32, device=dev)
+        if rounds:
+            res["rounds"] = torch.empty((n,), dtype=torch.int32, device=dev)
+        if n == 0:
+            return res
+        p = _lib.SfReachParams(source_mask=src, through_mask=thr, connectivity=conn, k=k, max_rounds=mr, passable_per_env=per_env,
+                               passable=passable.data_ptr() if passable is not None else None, points=points.data_ptr() if k else None,
+                               scratch_bytes=scratch)
+        o = _lib.SfReachOut(**{name: t.data_ptr() for name, t in res.items()})
+        torch.cuda.synchronize(dev)
+        self._chk(self._L.sf_reach(self._h, C.byref(p), n, _ptr(e), C.byref(o)))
+        if self.async_mode:
+            self._blobs_in_flight.extend(list(res.values()) + tensors)
+        return res
 
     def render(self, envs=None, scale=1, mode=None, background="fuel", contours=True, terrain_rgb=None, agents=None, channels_last=True,
                history=None, out=None):

@@ -595,6 +595,17 @@ class FireSimulation:
         self._engine.sync()
         return d[0].cpu().numpy()
 
+    def reach(self, source=("BURNING",), through=("UNBURNED",), connectivity=None, passable=None, value=False):
+        """What the fire can still get to: the flood fill of the cells whose BurnStatus is one of ``source`` through the cells whose
+        BurnStatus is one of ``through`` (members, names or ints; ``passable``: a uint8 CUDA tensor [H, W], 0 = closed), over the 8-
+        or 4-neighbourhood (``connectivity``; None: the configured ``diagonal_spread``).  Returns ``(mask, count, value)``: a NumPy
+        bool [H, W], the number of cells, and - with ``value`` - the value plane summed over them, else None.  Host edits of
+        ``fire_map`` are pushed to the device first, as ``run`` does (``BatchedFireSimulation.reach``)."""
+        self._sync_to_device()
+        r = self._engine.reach(source, through, envs=[0], connectivity=connectivity, passable=passable, count=True, value=bool(value), mask=True)
+        self._engine.sync()
+        return r["mask"][0].cpu().numpy().astype(bool), int(r["count"][0]), int(r["value"][0]) if value else None
+
     # -------------------------------------------------------------------- seeds / layers
     def get_seeds(self) -> Dict[str, Optional[int]]:
         """simulation.py:574-597: only the seeds that exist for the configured generators."""
@@ -1319,6 +1330,26 @@ class BatchedFireSimulation:
         d = self._engine.distance(status, envs=envs, max_dist=max_dist, points=agents, dtype="int32" if squared else "float32")
         self._engine.sync()
         return d if device else d.cpu().numpy()
+
+    def reach(self, source=("BURNING",), through=("UNBURNED",), envs=None, connectivity=None, passable=None, agents=False, value=False,
+              mask=False, device=True):
+        """What the fires of ``envs`` (default: all) can still get to: the flood fill of the cells whose BurnStatus is one of
+        ``source`` through the cells whose BurnStatus is one of ``through`` (members, names or ints; or masks) and, with ``passable``
+        (uint8 CUDA [H, W] or [n_envs, H, W]), only where it is not 0; ``connectivity`` 4, 8 or None (the configured
+        ``diagonal_spread``).  A dict: ``count`` int32 [n], ``seeds`` int32 [n] (0: nothing burning), with ``value`` the value plane
+        summed over the reach (int64 [n]), with ``mask`` uint8 [n, H, W], with ``agents=True`` ``point_in`` int32 [n, k] for the
+        device positions of a ``BatchedFireEnv`` (every environment in order), or a tensor [n, k, 3] = (column, row, id) of the
+        caller's.  ``device=True`` returns torch tensors on this GPU, else NumPy arrays; complete on return either way (one wait).
+        One call, no host copy of the maps, no change to the simulation."""
+        points = None
+        if agents is True:
+            points = self._engine.agents_device()
+        elif agents is not False and agents is not None:
+            points = agents
+        r = self._engine.reach(source, through, envs=envs, connectivity=connectivity, passable=passable, points=points, count=True,
+                               value=bool(value), mask=bool(mask), seeds=True)
+        self._engine.sync()
+        return r if device else {k: v.cpu().numpy() for k, v in r.items()}
 
     def refresh_fire_maps_device(self) -> None:
         """Bring the plane behind ``fire_maps_device()``'s tensor up to date (the same tensor then shows the current maps)."""

@@ -46,10 +46,16 @@ class BatchedFireEnv:
     shows - after a tick that re-ignited an environment, the new episode's.  Off by default: calls and ``info`` are what they are
     without it.
 
+    ``reach``: ``None``, or a dict with ``source``, ``through`` (BurnStatus members, names or ints; default BURNING / UNBURNED),
+    ``connectivity`` (4, 8 or None: the simulation's ``diagonal_spread``) and ``value`` (bool): ``info["reach_cells"]`` is then int32
+    [n_envs], the number of cells the fire can still get to (``FireEngine.reach``), ``info["agent_exposed"]``
+    int32 [n_envs, n_agents], 1 where an agent stands in that set, and with ``value`` ``info["reach_value"]`` int64 [n_envs], the value
+    plane summed over it - all from the state the observation shows.  Off by default: calls and ``info`` are what they are without it.
+
     Agents are not part of an environment's state: ``clone_envs`` / ``get_state`` / ``set_state`` do not carry them."""
 
     def __init__(self, sim, n_agents, start_xy, n_updates=1, weights=(-1, 0, 0, 0), only_unburned=True, done_on_burn=False,
-                 max_ticks=0, auto_reset=True, obs=None, values=None, value_weight=None, fire_distance=None):
+                 max_ticks=0, auto_reset=True, obs=None, values=None, value_weight=None, fire_distance=None, reach=None):
         self.sim = sim
         self.engine = sim._engine
         self.n_envs, self.n_agents = int(sim.n_envs), int(n_agents)
@@ -74,6 +80,17 @@ class BatchedFireEnv:
                 raise ValueError("BatchedFireEnv: fire_distance is None or a dict of status and max_dist")
             self.fire_distance = dict(status=fire_distance.get("status", ("BURNING",)), max_dist=fire_distance.get("max_dist"))
             sim._engine._distance_request(**self.fire_distance)       # (raises on a bad status or cap before anything is created)
+        self.reach = None
+        if reach is not None:
+            if not isinstance(reach, dict) or set(reach) - {"source", "through", "connectivity", "value"}:
+                raise ValueError("BatchedFireEnv: reach is None or a dict of source, through, connectivity and value")
+            if not isinstance(reach.get("value", False), bool):
+                raise ValueError("BatchedFireEnv: reach's value is True or False")
+            self.reach = dict(source=reach.get("source", ("BURNING",)), through=reach.get("through", ("UNBURNED",)),
+                              connectivity=reach.get("connectivity"), value=reach.get("value", False))
+            sim._engine._reach_request(self.reach["source"], self.reach["through"], self.reach["connectivity"])      # (raises before anything is created)
+            if self.reach["value"] and values is None and not self.engine.values_on:
+                raise ValueError("BatchedFireEnv: reach's value needs values (or a value plane set on the simulation)")
         self.engine.agents_create(self.n_agents, sim.ignitions, n_updates=n_updates, weights=weights, only_unburned=only_unburned,
                                   done_on_burn=done_on_burn, max_ticks=max_ticks, auto_reset=auto_reset)
         self.values_on = values is not None
@@ -94,6 +111,11 @@ class BatchedFireEnv:
         obs = self.sim.observe(agents=self.engine.agents_device(), **self.obs_kwargs)
         if info is not None and self.fire_distance is not None:
             info["fire_distance"] = self.engine.distance(points=self.engine.agents_device(), dtype="float32", **self.fire_distance)
+        if info is not None and self.reach is not None:
+            r = self.engine.reach(points=self.engine.agents_device(), count=True, **self.reach)
+            info["reach_cells"], info["agent_exposed"] = r["count"], r["point_in"]
+            if self.reach["value"]:
+                info["reach_value"] = r["value"]
         self.engine.sync()
         return obs
 
