@@ -2,18 +2,31 @@
 
 This is the only module that touches the HIP library; the reference-shaped classes in
 ``fire.py`` / ``simulation.py`` are written on top of it.  Arrays cross the boundary as
-NumPy host arrays (copied during the call); nothing here depends on torch.
+NumPy host arrays (copied during the call) or as torch CUDA tensors, read and written in place; torch is imported only by the
+methods that take or return one.  Layout (binding map): argument checks in ``_args.py``, one request class per feature
+(``observe.py``, ``render.py``, ``distance.py``, ``reach.py``, ``ensemble.py``), and one frame, ``_device_call``, for every call
+that hands the library a tensor.
 """
 import ctypes as C
 import os
 
 import numpy as np
 
-from . import _lib
+from . import _args, _lib
 
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def _device_view(ptr, shape, typestr, strides, device):
+    """Zero-copy torch view of device memory the library owns: ``ptr`` as a tensor of ``shape``, ``typestr`` ("<i4") and byte
+    ``strides`` (None: contiguous) on ``device``.  Valid for as long as the library keeps the allocation."""
+    import torch
+
+    class _View:
+        __cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2, "strides": strides}
+    return torch.as_tensor(_View(), device=device)
 
 
 class FireEngine:
@@ -44,7 +57,7 @@ class FireEngine:
         self.values_on = False              # a value plane is set (values_set)
         self.n_agents = 0                   # agents per environment (agents_create); 0: no agent state
         self.episodes_on = False            # new episodes draw their parameters on the device (episodes_set)
-        self._blobs_in_flight = []          # device state blobs an enqueued save / load may still touch (async mode; released by sync)
+        self._blobs_in_flight = []          # tensors an enqueued call may still touch (async mode: _device_call; released by sync)
         self._h = C.c_void_p()
         self._chk(self._L.sf_create(C.byref(self.params), C.byref(self._h)))
         if os.environ.get("SF_DEBUG_KNOBS") == "1":
@@ -57,6 +70,56 @@ class FireEngine:
 
     def _chk(self, rc):
         _lib.check(rc, self._L)
+
+    @property
+    def torch_device(self):
+        """The GPU of this handle as a ``torch.device``."""
+        import torch
+        return torch.device(f"cuda:{self.params.device}")
+
+    def _device_call(self, fn, *args, tensors=(), wait="device"):
+        """The frame of every call that hands the library torch tensors: ``fn(handle, *args)`` checked, around it what ``tensors``
+        - every tensor the call reads or writes - need.  The handle works on its own stream, so torch's queued work (which may
+        still write a tensor, or still use the memory a fresh one was given) is waited for first: ``wait="device"`` the whole
+        device, ``wait="stream"`` torch's current stream only.  In async mode the call only enqueues, so the tensors are kept alive
+        until ``sync`` (the caching allocator must not hand their memory out while the handle's stream may still touch it).
+        Without tensors it is the plain checked call."""
+        if len(tensors):
+            import torch
+            if wait == "device":
+                torch.cuda.synchronize(tensors[0].device)
+            else:
+                torch.cuda.current_stream(tensors[0].device).synchronize()
+        self._chk(fn(self._h, *args))
+        if self.async_mode:
+            self._blobs_in_flight.extend(tensors)
+
+    def _outputs(self, who, spec, out=None, dtype=None):
+        """The output of a checked request (``observe.ObsSpec`` and its kin) on this GPU: ``out`` or a new tensor of ``spec.shape``
+        and ``dtype`` - or, where the request names several (``spec.outputs``: name -> (shape, dtype)), a dict of new ones - after
+        checking that ``out`` and the tensors the request reads (``spec.device_tensors()``) live on this GPU too."""
+        import torch
+        dev = self.torch_device
+        for t in spec.device_tensors() + ([out] if out is not None else []):
+            if t.device != dev:
+                raise ValueError(f"{who}: a tensor on {t.device}, the simulation runs on {dev}")
+
+        def new(shape, dt):
+            return torch.empty(shape, dtype=getattr(torch, dt) if isinstance(dt, str) else dt, device=dev)
+        if dtype is None:
+            return {name: new(*sd) for name, sd in spec.outputs.items()}
+        return out if out is not None else new(spec.shape, dtype)
+
+    def _get(self, fn, ctype, *args):
+        """One scalar out-parameter of C type ``ctype``: ``fn(handle, *args, &v)`` checked, ``v`` as a Python number."""
+        v = ctype()
+        self._chk(fn(self._h, *args, C.byref(v)))
+        return v.value
+
+    def _switch(self, fn, on):
+        """An on / off flag: ``fn(handle, 0 | 1)`` checked; returns the flag as a bool."""
+        self._chk(fn(self._h, int(bool(on))))
+        return bool(on)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -122,30 +185,12 @@ class FireEngine:
     def reset_env(self, env, x, y):
         self._chk(self._L.sf_reset_env(self._h, int(env), int(x), int(y)))
 
-    def _ignitions(self, xy, n, name):
-        """Host ignitions int32 [n, 2] = (x, y), every one on the grid (checked here: no device call has been made yet)."""
-        a = np.asarray(xy)
-        if a.dtype.kind not in "iu":
-            raise ValueError(f"{name}: ignitions must be integers, got {a.dtype}")
-        if a.shape != (n, 2):
-            raise ValueError(f"{name}: ignitions must have shape {(n, 2)}, got {a.shape}")
-        a = np.ascontiguousarray(a, dtype=np.int32)
-        bad = np.flatnonzero((a[:, 0] < 0) | (a[:, 0] >= self.W) | (a[:, 1] < 0) | (a[:, 1] >= self.H))
-        if bad.size:
-            i = int(bad[0])
-            raise ValueError(f"{name}: ignition ({a[i, 0]}, {a[i, 1]}) of entry {i} is outside the {self.H}x{self.W} grid")
-        return a
-
     def reset_envs(self, envs, xy):
         """New episodes in ``envs`` (environment ``envs[i]`` ignites at ``xy[i]`` = (x, y)), one launch for all of them
         (``sf_reset_envs``).  An environment may repeat: its last ignition wins.  In async mode the call only enqueues."""
-        e = np.asarray(envs)
-        if e.ndim != 1 or (e.size and e.dtype.kind not in "iu"):
-            raise ValueError("reset_envs: envs must be a list of environment numbers")
-        e = np.ascontiguousarray(e, dtype=np.int32)
-        a = self._ignitions(xy, e.shape[0], "reset_envs")
-        if e.size and (e.min() < 0 or e.max() >= self.n_envs):
-            raise IndexError(f"reset_envs: environment {int(e[(e < 0) | (e >= self.n_envs)][0])} out of range (n_envs = {self.n_envs})")
+        e = _args.env_list(envs, who="reset_envs")
+        a = _args.cells(xy, (e.shape[0], 2), self.H, self.W, "reset_envs", "ignition")
+        _args.env_range(e, self.n_envs, "reset_envs", exc=IndexError)
         if e.size:
             self._chk(self._L.sf_reset_envs(self._h, int(e.shape[0]), _ptr(e), _ptr(a)))
 
@@ -156,41 +201,27 @@ class FireEngine:
         untouched.  Torch's queued work on the tensors is waited for first; in async mode they are kept alive until ``sync``."""
         tensors = []
         if mask is not None:
-            import torch
-            if not isinstance(mask, torch.Tensor) or not mask.is_cuda or mask.dtype not in (torch.uint8, torch.bool) \
-                    or tuple(mask.shape) != (self.n_envs,):
-                raise ValueError(f"reset_where: mask must be None or a CUDA uint8 / bool tensor of shape ({self.n_envs},)")
-            mask = mask.contiguous()
+            mask = _args.env_mask(mask, self.n_envs, "reset_where")
             tensors.append(mask)
         if xy is None:
             raise ValueError("reset_where: xy (the ignitions, [n_envs, 2]) is required")
         if getattr(xy, "is_cuda", False):
-            import torch
-            if xy.dtype != torch.int32 or tuple(xy.shape) != (self.n_envs, 2):
-                raise ValueError(f"reset_where: a device xy must be a CUDA int32 tensor of shape ({self.n_envs}, 2)")
-            xy = xy.contiguous()
+            xy = _args.cuda_tensor(xy, "reset_where: a device xy", ("int32",), [(self.n_envs, 2)]).contiguous()
             tensors.append(xy)
             xy_ptr, xy_dev = C.c_void_p(xy.data_ptr()), 1
         else:
-            a = self._ignitions(xy, self.n_envs, "reset_where")
+            a = _args.cells(xy, (self.n_envs, 2), self.H, self.W, "reset_where", "ignition")
             xy_ptr, xy_dev = _ptr(a), 0
         mask_ptr = C.c_void_p(mask.data_ptr()) if mask is not None else None
-        if tensors:
-            import torch
-            torch.cuda.synchronize(tensors[0].device)
-        self._chk(self._L.sf_reset_where(self._h, mask_ptr, xy_ptr, xy_dev))
-        if self.async_mode:
-            self._blobs_in_flight.extend(tensors)
+        self._device_call(self._L.sf_reset_where, mask_ptr, xy_ptr, xy_dev, tensors=tensors)
 
     def time_resets(self, on=True):
         """Measurement only: record HIP events around the launches of every ``reset_envs`` / ``reset_where`` (``sf_time_resets``)."""
-        self._chk(self._L.sf_time_resets(self._h, int(bool(on))))
+        self._switch(self._L.sf_time_resets, on)
 
     def reset_ms(self):
         """GPU milliseconds of the last timed batched reset's launches (``sf_get_reset_ms``; waits for them)."""
-        ms = C.c_float(0.0)
-        self._chk(self._L.sf_get_reset_ms(self._h, C.byref(ms)))
-        return float(ms.value)
+        return self._get(self._L.sf_get_reset_ms, C.c_float)
 
     # ------------------------------------------------------------------ agents on the device (DESIGN.md section 16)
     def agents_create(self, n_agents, ignitions=None, n_updates=1, weights=(-1.0, 0.0, 0.0, 0.0), only_unburned=True,
@@ -210,7 +241,7 @@ class FireEngine:
             raise ValueError(f"agents_create: max_ticks = {max_ticks} must be >= 0")
         ign = None
         if k and ignitions is not None:
-            ign = self._ignitions(ignitions, self.n_envs, "agents_create")
+            ign = _args.cells(ignitions, (self.n_envs, 2), self.H, self.W, "agents_create", "ignition")
         elif k and auto_reset:
             raise ValueError("agents_create: auto_reset needs the ignitions")
         p = _lib.SfAgentParams(k=k, n_updates=int(n_updates), only_unburned=int(bool(only_unburned)),
@@ -236,16 +267,8 @@ class FireEngine:
         if not k:
             raise _lib.SimfireHipError("agents_place: call agents_create first")
         e = self._env_list(envs, "envs")
-        a = np.asarray(xy)
-        if a.dtype.kind not in "iu":
-            raise ValueError(f"agents_place: cells must be integers, got {a.dtype}")
-        if a.shape != (e.shape[0], k, 2):
-            raise ValueError(f"agents_place: cells must have shape {(e.shape[0], k, 2)}, got {a.shape}")
-        a = np.ascontiguousarray(a, dtype=np.int32)
-        if e.size and (e.min() < 0 or e.max() >= self.n_envs):
-            raise ValueError(f"agents_place: environment {int(e[(e < 0) | (e >= self.n_envs)][0])} out of range (n_envs = {self.n_envs})")
-        if ((a[..., 0] < 0) | (a[..., 0] >= self.W) | (a[..., 1] < 0) | (a[..., 1] >= self.H)).any():
-            raise ValueError(f"agents_place: a cell is outside the {self.H}x{self.W} grid")
+        a = _args.cells(xy, (e.shape[0], k, 2), self.H, self.W, "agents_place")
+        _args.env_range(e, self.n_envs, "agents_place")
         if e.size:
             self._chk(self._L.sf_agents_place(self._h, int(e.shape[0]), _ptr(e), _ptr(a), int(bool(also_start))))
 
@@ -255,55 +278,29 @@ class FireEngine:
         ``reward`` float32 [n_envs], ``done`` uint8 / bool [n_envs], ``terms`` int32 [n_envs, 4], ``final_len`` int32 [n_envs],
         ``final_ret`` float64 [n_envs].  Torch's queued work on the tensors is waited for first; in async mode the call only
         enqueues and the tensors are kept alive until ``sync``."""
-        import torch
         k = self.n_agents
         if not k:
             raise _lib.SimfireHipError("agents_step: call agents_create first")
-        E = self.n_envs
-        dev = torch.device(f"cuda:{self.params.device}")
-
-        def chk(t, name, dtypes, shape):
-            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in dtypes or tuple(t.shape) != shape \
-                    or not t.is_contiguous() or t.device != dev:
-                raise ValueError(f"agents_step: {name} must be a contiguous {dtypes[0]} tensor of shape {shape} on {dev}")
-            return t
-        chk(actions, "actions", (torch.int32,), (E, k))
-        o = _lib.SfAgentOut()
-        tensors = [actions]
-        for t, name, dtypes, shape in ((reward, "reward", (torch.float32,), (E,)), (done, "done", (torch.uint8, torch.bool), (E,)),
-                                       (terms, "terms", (torch.int32,), (E, 4)), (final_len, "final_len", (torch.int32,), (E,)),
-                                       (final_ret, "final_ret", (torch.float64,), (E,))):
+        E, dev = self.n_envs, self.torch_device
+        _args.cuda_tensor(actions, "agents_step: actions", ("int32",), [(E, k)], device=dev, contiguous=True)
+        o, tensors = _lib.SfAgentOut(), [actions]
+        for t, name, dtypes, shape in ((reward, "reward", ("float32",), (E,)), (done, "done", ("uint8", "bool"), (E,)),
+                                       (terms, "terms", ("int32",), (E, 4)), (final_len, "final_len", ("int32",), (E,)),
+                                       (final_ret, "final_ret", ("float64",), (E,))):
             if t is not None:
-                setattr(o, name, chk(t, name, dtypes, shape).data_ptr())
+                setattr(o, name, _args.cuda_tensor(t, f"agents_step: {name}", dtypes, [shape], device=dev, contiguous=True).data_ptr())
                 tensors.append(t)
-        torch.cuda.synchronize(dev)
-        self._chk(self._L.sf_agents_step(self._h, C.c_void_p(actions.data_ptr()), C.byref(o)))
-        if self.async_mode:
-            self._blobs_in_flight.extend(tensors)
+        self._device_call(self._L.sf_agents_step, C.c_void_p(actions.data_ptr()), C.byref(o), tensors=tensors)
 
     def agents_device(self):
         """Zero-copy torch view int32 [n_envs, n_agents, 3] = (column, row, id) of the agent positions on this GPU: what ``observe``
         / ``render`` take as ``agents``.  Valid until the next ``agents_create``; read it after ``sync`` in async mode."""
-        import torch
         if not self.n_agents:
             raise _lib.SimfireHipError("agents_device: call agents_create first")
-        p = C.c_void_p()
-        self._chk(self._L.sf_agents_device(self._h, C.byref(p)))
-        shape = (self.n_envs, self.n_agents, 3)
-
-        class _Agents:
-            __cuda_array_interface__ = {"shape": shape, "typestr": "<i4", "data": (p.value, False), "version": 2, "strides": None}
-        return torch.as_tensor(_Agents(), device=f"cuda:{self.params.device}")
+        p = self._get(self._L.sf_agents_device, C.c_void_p)
+        return _device_view(p, (self.n_envs, self.n_agents, 3), "<i4", None, self.torch_device)
 
     # ------------------------------------------------------------------ drawn episodes (DESIGN.md section 19)
-    def _box(self, box, name):
-        b = [int(v) for v in box]
-        if len(b) != 4:
-            raise ValueError(f"episodes_set: {name} is (x0, y0, x1, y1), inclusive")
-        if b[0] < 0 or b[1] < 0 or b[2] >= self.W or b[3] >= self.H or b[0] > b[2] or b[1] > b[3]:
-            raise ValueError(f"episodes_set: {name} {tuple(b)} is not x0 <= x1, y0 <= y1 on the {self.H}x{self.W} grid")
-        return b
-
     def episodes_set(self, seed, ignition_box=None, live_cells=False, wind_speed=None, wind_direction=None, agent_box=None):
         """Every new episode draws its parameters on the device (``sf_episodes_set``): a function of (seed, environment, episode
         index) alone.  ``ignition_box`` / ``agent_box`` (x0, y0, x1, y1), inclusive: where the ignition / every agent's start cell
@@ -323,10 +320,10 @@ class FireEngine:
             raise ValueError("episodes_set: live_cells needs an ignition_box")
         if ignition_box is not None:
             flags |= _lib.SF_EP_IGNITION | (_lib.SF_EP_LIVE_CELL if live_cells else 0)
-            p.ign_box[:] = self._box(ignition_box, "ignition_box")
+            p.ign_box[:] = _args.box(ignition_box, self.H, self.W, "episodes_set", "ignition_box")
         if agent_box is not None:
             flags |= _lib.SF_EP_AGENTS
-            p.agent_box[:] = self._box(agent_box, "agent_box")
+            p.agent_box[:] = _args.box(agent_box, self.H, self.W, "episodes_set", "agent_box")
         if (wind_speed is None) != (wind_direction is None):
             raise ValueError("episodes_set: wind_speed and wind_direction go together")
         if wind_speed is not None:
@@ -347,34 +344,21 @@ class FireEngine:
         first; in async mode it is kept alive until ``sync``."""
         tensors = []
         if mask is not None and not all:
-            import torch
-            if not isinstance(mask, torch.Tensor) or not mask.is_cuda or mask.dtype not in (torch.uint8, torch.bool) \
-                    or tuple(mask.shape) != (self.n_envs,):
-                raise ValueError(f"episodes_begin: mask must be None or a CUDA uint8 / bool tensor of shape ({self.n_envs},)")
-            mask = mask.contiguous()
-            tensors.append(mask)
-            torch.cuda.synchronize(mask.device)
-        mask_ptr = C.c_void_p(mask.data_ptr()) if tensors else None
-        self._chk(self._L.sf_episodes_begin(self._h, mask_ptr, int(bool(all))))
-        if self.async_mode:
-            self._blobs_in_flight.extend(tensors)
+            tensors.append(_args.env_mask(mask, self.n_envs, "episodes_begin"))
+        mask_ptr = C.c_void_p(tensors[0].data_ptr()) if tensors else None
+        self._device_call(self._L.sf_episodes_begin, mask_ptr, int(bool(all)), tensors=tensors)
 
     def episodes_torch(self):
         """Zero-copy torch views of what the last draw of every environment made (``sf_episodes_device``): ``index`` int32 [n_envs]
         (the NEXT episode's index; the bits of a uint32), ``ignition`` int32 [n_envs, 2] = (x, y), ``wind`` float64 [n_envs, 2] =
         (U ft/min, U_dir degrees).  They report draws, not a later ``set_wind``, ``reset_envs`` or ``copy_envs``.  Read-only; the
         handle's stream is waited for first.  Valid until the next ``episodes_set``."""
-        import torch
         ptrs = [C.c_void_p(), C.c_void_p(), C.c_void_p()]
         self._chk(self._L.sf_episodes_device(self._h, *[C.byref(p) for p in ptrs]))
         self.sync()
-        E, dev = self.n_envs, f"cuda:{self.params.device}"
-
-        def view(ptr, shape, typestr):
-            class _Buf:
-                __cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (ptr.value, False), "version": 2, "strides": None}
-            return torch.as_tensor(_Buf(), device=dev)
-        return dict(index=view(ptrs[0], (E,), "<i4"), ignition=view(ptrs[1], (E, 2), "<i4"), wind=view(ptrs[2], (E, 2), "<f8"))
+        E, dev = self.n_envs, self.torch_device
+        return dict(index=_device_view(ptrs[0].value, (E,), "<i4", None, dev), ignition=_device_view(ptrs[1].value, (E, 2), "<i4", None, dev),
+                    wind=_device_view(ptrs[2].value, (E, 2), "<f8", None, dev))
 
     def apply_mitigation(self, pts):
         """pts: rows (env, x, y, type)."""
@@ -385,7 +369,7 @@ class FireEngine:
     def apply_mitigation_torch(self, pts):
         """The same scatter for a torch int32 tensor [n, 4] (env, x, y, type) that already lives on this
         GPU (e.g. the actions of a policy): no host round trip; rows with an out-of-range field are
-        skipped.  The caller orders its own stream before this call (``torch.cuda.synchronize`` or an
+        skipped.  The caller orders its own stream before this call (a device-wide wait or an
         event), the library then works on its own stream."""
         import torch
         if pts.dtype != torch.int32 or pts.dim() != 2 or pts.shape[1] != 4 or not pts.is_cuda:
@@ -393,6 +377,8 @@ class FireEngine:
         pts = pts.contiguous()
         if pts.shape[0]:
             self._chk(self._L.sf_apply_mitigation_device(self._h, C.c_void_p(pts.data_ptr()), int(pts.shape[0])))
+            # one slot, replaced by the next call - not _device_call's list: a rollout makes these calls (and step_mitigated's)
+            # many times in async mode without a sync(), and the list would grow with every one
             self._keep_alive = pts          # until the next call: the scatter may still be queued (async mode)
 
     def load_fire_map(self, env, fire_map):
@@ -409,9 +395,7 @@ class FireEngine:
 
     def step_timed(self, n=1):
         """Returns the GPU milliseconds spent in the n step kernels."""
-        ms = C.c_float(0.0)
-        self._chk(self._L.sf_step_timed(self._h, int(n), C.byref(ms)))
-        return float(ms.value)
+        return self._get(self._L.sf_step_timed, C.c_float, int(n))
 
     def step_mitigated(self, pts, timed=False):
         """``for s in range(n): update_mitigation(pts[s]); step(1)`` as one call.  ``pts``: int32 [n, n_envs, k, 3] =
@@ -489,10 +473,8 @@ class FireEngine:
     # ------------------------------------------------------------------ environment state
     @staticmethod
     def _env_list(envs, name):
-        a = np.ascontiguousarray(np.atleast_1d(np.asarray(envs)), dtype=np.int32)
-        if a.ndim != 1:
-            raise ValueError(f"{name} must be a list of environment numbers")
-        return a
+        """The legacy lenient list: a scalar is a list of one, anything that casts to int32 passes, the range is the library's."""
+        return _args.env_list(envs, name=name, lenient=True)
 
     def copy_envs(self, src, dst, terrain=False):
         """Environment ``dst[i]`` becomes environment ``src[i]`` (one launch for all pairs; ``sf_copy_envs``).  ``terrain``: on a
@@ -504,9 +486,7 @@ class FireEngine:
 
     def state_bytes(self):
         """Bytes of one environment's state blob (``sf_state_bytes``)."""
-        v = C.c_int64(0)
-        self._chk(self._L.sf_state_bytes(self._h, C.byref(v)))
-        return v.value
+        return self._get(self._L.sf_state_bytes, C.c_int64)
 
     def save_state(self, envs, out=None):
         """The state of ``envs`` as blobs: numpy uint8 [n, state_bytes()], or written into ``out`` (a contiguous CUDA tensor of at
@@ -520,18 +500,8 @@ class FireEngine:
             return blob
         if not getattr(out, "is_cuda", False) or not out.is_contiguous() or out.numel() * out.element_size() < e.shape[0] * nb:
             raise ValueError(f"out must be a contiguous CUDA tensor of at least {e.shape[0] * nb} bytes")
-        self._device_blob_call(out, lambda: self._L.sf_save_state(self._h, int(e.shape[0]), _ptr(e), C.c_void_p(out.data_ptr()), 1))
+        self._device_call(self._L.sf_save_state, int(e.shape[0]), _ptr(e), C.c_void_p(out.data_ptr()), 1, tensors=[out])
         return out
-
-    def _device_blob_call(self, t, call):
-        """A state call on a blob tensor: the handle works on its own stream, so torch's queued work (which may still write the blob, or
-        still use the memory a fresh tensor was given) is waited for first; in async mode the call only enqueues, so the tensor is kept
-        alive until ``sync`` (the caching allocator must not hand its memory out while the handle's stream may still touch it)."""
-        import torch
-        torch.cuda.synchronize(t.device)
-        self._chk(call())
-        if self.async_mode:
-            self._blobs_in_flight.append(t)
 
     def load_state(self, envs, blob):
         """Environment ``envs[i]`` takes the state of blob i (numpy uint8 [n, state_bytes()] or a contiguous CUDA tensor holding the
@@ -541,7 +511,7 @@ class FireEngine:
         if getattr(blob, "is_cuda", False):
             if not blob.is_contiguous() or blob.numel() * blob.element_size() < e.shape[0] * nb:
                 raise ValueError(f"blob must be a contiguous CUDA tensor of at least {e.shape[0] * nb} bytes")
-            self._device_blob_call(blob, lambda: self._L.sf_load_state(self._h, int(e.shape[0]), _ptr(e), C.c_void_p(blob.data_ptr()), 1))
+            self._device_call(self._L.sf_load_state, int(e.shape[0]), _ptr(e), C.c_void_p(blob.data_ptr()), 1, tensors=[blob])
             return
         b = np.ascontiguousarray(blob, dtype=np.uint8)
         if b.size < e.shape[0] * nb:
@@ -556,9 +526,7 @@ class FireEngine:
         return st, el
 
     def memory_bytes(self):
-        v = C.c_int64(0)
-        self._chk(self._L.sf_memory_bytes(self._h, C.byref(v)))
-        return int(v.value)
+        return self._get(self._L.sf_memory_bytes, C.c_int64)
 
     def geometry(self):
         """dict(tile_w, tile_h, tiles_x, tiles_y, rows_per_band, pitch, lds_wave_bytes, dense)"""
@@ -577,8 +545,7 @@ class FireEngine:
 
     def set_async(self, on=True):
         """Rollout mode: ``step`` / ``apply_mitigation`` only enqueue work; ``sync`` or any getter waits."""
-        self._chk(self._L.sf_set_async(self._h, int(bool(on))))
-        self.async_mode = bool(on)
+        self.async_mode = self._switch(self._L.sf_set_async, on)
 
     def sync(self):
         self._chk(self._L.sf_sync(self._h))
@@ -626,9 +593,7 @@ class FireEngine:
         self._chk(self._L.sf_loop_stop(self._h))
 
     def loop_restarts(self):
-        v = C.c_int32()
-        self._chk(self._L.sf_loop_restarts(self._h, C.byref(v)))
-        return v.value
+        return self._get(self._L.sf_loop_restarts, C.c_int32)
 
     def run_cost(self):
         """Shader clocks / 16 every environment's workgroup(s) spent in the last resident launch (uint32 [n_envs])."""
@@ -652,33 +617,24 @@ class FireEngine:
 
     def last_launches(self):
         """Environment-resident launches the last step / step_mitigated / rollout call was made of (0: per-step kernels)."""
-        v = C.c_int32()
-        self._chk(self._L.sf_get_last_launches(self._h, C.byref(v)))
-        return int(v.value)
+        return self._get(self._L.sf_get_last_launches, C.c_int32)
 
     def team_fallbacks(self):
         """Teams of a fixed size that found at their start that not all members were resident and whose environment was stepped by
         member 0 alone (same results; since the handle was created)."""
-        v = C.c_int32()
-        self._chk(self._L.sf_get_team_fallbacks(self._h, C.byref(v)))
-        return int(v.value)
+        return self._get(self._L.sf_get_team_fallbacks, C.c_int32)
 
     def get_tuning(self, name):
-        v = C.c_int32()
-        self._chk(self._L.sf_get_tuning(self._h, _lib.TUNE[name], C.byref(v)))
-        return v.value
+        return self._get(self._L.sf_get_tuning, C.c_int32, _lib.TUNE[name])
 
     def set_prune_after_quit(self, on=True):
         """Environments that QUIT on the runtime check keep pruning when stepped again (fire.py:631-643)."""
-        self._chk(self._L.sf_set_prune_after_quit(self._h, int(bool(on))))
-        self.prune_after_quit = bool(on)
+        self.prune_after_quit = self._switch(self._L.sf_set_prune_after_quit, on)
 
     def last_launch_kind(self):
         """0 k_select + k_step, 1 fused launch per step, 2 resident launch (k_run), 3 per-cell kernel, 4 the window kernel k_win in front of
         k_run (more environments than CUs, young fires), -1 none yet."""
-        v = C.c_int32(-1)
-        self._chk(self._L.sf_last_step_launch(self._h, C.byref(v)))
-        return int(v.value)
+        return self._get(self._L.sf_last_step_launch, C.c_int32)
 
     # neighbour order of the parent masks = adj_locs of simfire/utils/graph.py:125-134
     GRAPH_DX = (+1, +1, 0, -1, -1, -1, 0, +1)
@@ -686,8 +642,7 @@ class FireEngine:
 
     def enable_spread_graph(self, on=True):
         """Record the fire-spread graph (FireSpreadGraph, simfire/utils/graph.py) as parent masks."""
-        self._chk(self._L.sf_enable_spread_graph(self._h, int(bool(on))))
-        self.spread_graph_on = bool(on)
+        self.spread_graph_on = self._switch(self._L.sf_enable_spread_graph, on)
         self.spread_graph = self.spread_graph or bool(on)        # the parent masks exist (they stay allocated once they do; a state blob carries them)
 
     def spread_parents(self, env=0):
@@ -783,11 +738,10 @@ class FireEngine:
         if on_device[0] != on_device[1]:
             raise ValueError("set_wind: speed and direction must both be arrays or both be CUDA tensors")
         shapes = {(): 0, (n,): 0, (self.H, self.W): _lib.SF_WIND_FIELD, (n, self.H, self.W): _lib.SF_WIND_FIELD}
+        tensors = []
         if on_device[0]:
-            import torch
             for t, name in ((speed, "speed"), (direction, "direction")):
-                if not t.is_cuda or t.device.index != self.params.device or t.dtype != torch.float64 or not t.is_contiguous():
-                    raise ValueError(f"set_wind: {name} must be a contiguous float64 CUDA tensor on device {self.params.device}")
+                _args.cuda_tensor(t, f"set_wind: {name}", ("float64",), device=self.torch_device, contiguous=True)
             if tuple(speed.shape) != tuple(direction.shape) or tuple(speed.shape) not in shapes:
                 raise ValueError(f"set_wind: speed {tuple(speed.shape)} / direction {tuple(direction.shape)}: scalars, [{n}], "
                                  f"[{self.H}, {self.W}] or [{n}, {self.H}, {self.W}]")
@@ -795,7 +749,7 @@ class FireEngine:
             lead = (n,) if flags & _lib.SF_WIND_FIELD == 0 else (n, self.H, self.W)
             if tuple(speed.shape) != lead:              # one value / one field for every listed table
                 speed, direction = speed.expand(lead).contiguous(), direction.expand(lead).contiguous()
-            torch.cuda.synchronize(speed.device)
+            tensors = [speed, direction]
             u, d = C.c_void_p(speed.data_ptr()), C.c_void_p(direction.data_ptr())
         else:
             sp, dr = np.asarray(speed, dtype=np.float64), np.asarray(direction, dtype=np.float64)
@@ -808,9 +762,7 @@ class FireEngine:
             lead = (n,) if flags == 0 else (n, self.H, self.W)
             speed, direction = (np.ascontiguousarray(np.broadcast_to(a, lead)) for a in (sp, dr))
             u, d = _ptr(speed), _ptr(direction)
-        self._chk(self._L.sf_set_wind(self._h, n, None if e is None else _ptr(e), u, d, flags))
-        if on_device[0] and self.async_mode:
-            self._blobs_in_flight.append((speed, direction))
+        self._device_call(self._L.sf_set_wind, n, None if e is None else _ptr(e), u, d, flags, tensors=tensors)
 
     def set_wind_schedule(self, envs, segments):
         """Uniform winds by the episode's time, decided on the device (``sf_set_wind_schedule``).  ``segments``:
@@ -842,9 +794,7 @@ class FireEngine:
 
     def wind_ms(self):
         """GPU milliseconds of the last timed wind change or schedule pass (``sf_get_wind_ms``)."""
-        ms = C.c_float(0.0)
-        self._chk(self._L.sf_get_wind_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._get(self._L.sf_get_wind_ms, C.c_float)
 
     def attribute_data(self, env=0):
         """``FireSimulation.get_attribute_data`` (simfire/sim/simulation.py:376-403) from the layers
@@ -862,19 +812,12 @@ class FireEngine:
         sigma as int32 (torch has no uint32 arithmetic; the values are < 2^31)."""
         import torch
         envs = list(range(self.n_envs)) if envs is None else [int(e) for e in envs]
-        dev = f"cuda:{self.params.device}"
-        n = len(envs)
-        out = {"w_0": torch.empty((n, self.H, self.W), dtype=torch.float32, device=dev),
-               "sigma": torch.empty((n, self.H, self.W), dtype=torch.int32, device=dev),
-               "delta": torch.empty((n, self.H, self.W), dtype=torch.float32, device=dev),
-               "M_x": torch.empty((n, self.H, self.W), dtype=torch.float32, device=dev),
-               "elevation": torch.empty((n, self.H, self.W), dtype=torch.float64, device=dev),
-               "wind_speed": torch.empty((n, self.H, self.W), dtype=torch.float64, device=dev),
-               "wind_direction": torch.empty((n, self.H, self.W), dtype=torch.float64, device=dev)}
-        torch.cuda.synchronize(dev)
+        keys = {"w_0": torch.float32, "sigma": torch.int32, "delta": torch.float32, "M_x": torch.float32, "elevation": torch.float64,
+                "wind_speed": torch.float64, "wind_direction": torch.float64}
+        out = {k: torch.empty((len(envs), self.H, self.W), dtype=dt, device=self.torch_device) for k, dt in keys.items()}
         for i, e in enumerate(envs):
-            self._chk(self._L.sf_get_attribute_data(self._h, e, *[C.c_void_p(out[k][i].data_ptr()) for k in (
-                "w_0", "sigma", "delta", "M_x", "elevation", "wind_speed", "wind_direction")], 1))
+            planes = [out[k][i] for k in keys]
+            self._device_call(self._L.sf_get_attribute_data, e, *[C.c_void_p(t.data_ptr()) for t in planes], 1, tensors=planes)
         return out
 
     def observe(self, channels, envs=None, normalize=True, pool=1, pool_mode="mean", crop=None, centers=None, agents=None, pad=0.0,
@@ -885,21 +828,12 @@ class FireEngine:
         ``pool`` f (mean or max, per channel with a dict), ``agents`` [n, k, 3] = (column, row, id); host arrays or CUDA int32 tensors.
         ``out``: a tensor to fill instead of a new one.  Torch's queued work is waited for before the handle's stream writes ``out``; in
         async mode the call only enqueues and the tensors are kept alive until ``sync()``."""
-        import torch
         from .observe import ObsSpec
         spec = ObsSpec(channels, self.n_envs, self.H, self.W, envs=envs, normalize=normalize, pool=pool, pool_mode=pool_mode, crop=crop,
                        centers=centers, agents=agents, pad=pad, dtype=dtype, out=out)
-        dev = torch.device(f"cuda:{self.params.device}")
-        for t in spec.device_tensors() + ([out] if out is not None else []):
-            if t.device != dev:
-                raise ValueError(f"observe: a tensor on {t.device}, the simulation runs on {dev}")
-        if out is None:
-            out = torch.empty(spec.shape, dtype=spec.dtype, device=dev)
-        p = spec.params()
-        torch.cuda.synchronize(dev)
-        self._chk(self._L.sf_observe(self._h, C.byref(p), spec.n, spec.envs_ptr(), C.c_void_p(out.data_ptr())))
-        if self.async_mode:
-            self._blobs_in_flight.extend([out] + spec.device_tensors())
+        out, p = self._outputs("observe", spec, out, spec.dtype), spec.params()
+        self._device_call(self._L.sf_observe, C.byref(p), spec.n, _ptr(spec.envs), C.c_void_p(out.data_ptr()),
+                          tensors=[out] + spec.device_tensors())
         return out
 
     # ---------------------------------------------------------------- distance fields (DESIGN.md section 22)
@@ -908,62 +842,12 @@ class FireEngine:
 
     @staticmethod
     def _status_mask(who, status, what="status"):
-        """A set of BurnStatus values as the mask the library takes (bit s = BurnStatus s, 1..63): ``status`` is that mask, a member,
-        a name, or an iterable of members, names or ints.  ``ValueError`` (named after the caller, ``who``) on anything else."""
-        from .enums import BurnStatus
-
-        def bit(s):
-            if isinstance(s, str):
-                if s not in BurnStatus.__members__:
-                    raise ValueError(f"{who}: unknown BurnStatus name {s!r}")
-                return 1 << int(BurnStatus[s])
-            if isinstance(s, (bool, float)) or not isinstance(s, (int, np.integer)) or not 0 <= int(s) <= 5:
-                raise ValueError(f"{who}: {s!r} is no BurnStatus (a member, a name or 0..5)")
-            return 1 << int(s)
-        if isinstance(status, (int, np.integer)) and not isinstance(status, (bool, BurnStatus)):
-            mask = int(status)
-        elif isinstance(status, (str, BurnStatus)):
-            mask = bit(status)
-        else:
-            try:
-                items = list(status)
-            except TypeError:
-                raise ValueError(f"{who}: {what} must be a mask 1..63 or BurnStatus members, names or ints, got {status!r}") from None
-            mask = 0
-            for s in items:
-                mask |= bit(s)
-        if not 1 <= mask <= 63:
-            raise ValueError(f"{who}: the {what} mask {mask} selects nothing or more than BurnStatus 0..5 (1..63)")
-        return mask
+        return _args.status_mask(who, status, what)
 
     @staticmethod
     def _distance_request(status, max_dist=None, max_d2=None, dtype="float32", scale=1.0, scratch_bytes=0):
-        """The checked scalar arguments of ``distance``: (status mask, max_d2, dtype code, scale, scratch_bytes).  ``ValueError`` on
-        anything the library would refuse, before it is called."""
-        mask = FireEngine._status_mask("distance", status)
-        if max_dist is not None and max_d2 is not None:
-            raise ValueError("distance: give max_dist or max_d2, not both")
-        d2 = 0
-        if max_dist is not None:
-            if isinstance(max_dist, (bool, float)) or not isinstance(max_dist, (int, np.integer)) or not 1 <= int(max_dist) <= 46340:
-                raise ValueError(f"distance: max_dist must be an integer number of cells 1..46340 or None, got {max_dist!r}")
-            d2 = int(max_dist) ** 2
-        elif max_d2 is not None:
-            if isinstance(max_d2, (bool, float)) or not isinstance(max_d2, (int, np.integer)) or not 1 <= int(max_d2) <= 2 ** 31 - 1:
-                raise ValueError(f"distance: max_d2 must be an integer 1..2**31 - 1 or None, got {max_d2!r}")
-            d2 = int(max_d2)
-        name = getattr(dtype, "name", None) or str(dtype).replace("torch.", "")
-        if name not in ("int32", "float32"):
-            raise ValueError(f"distance: dtype must be 'int32' or 'float32', got {dtype!r}")
-        try:
-            sc = float(scale)
-        except (TypeError, ValueError):
-            raise ValueError(f"distance: scale must be a number, got {scale!r}") from None
-        if not np.isfinite(sc) or sc <= 0.0:
-            raise ValueError(f"distance: scale must be finite and > 0, got {scale!r}")
-        if isinstance(scratch_bytes, (bool, float)) or not isinstance(scratch_bytes, (int, np.integer)) or int(scratch_bytes) < 0:
-            raise ValueError(f"distance: scratch_bytes must be an integer >= 0, got {scratch_bytes!r}")
-        return mask, d2, (_lib.SF_DIST_I32 if name == "int32" else _lib.SF_DIST_F32), sc, int(scratch_bytes)
+        from . import distance
+        return distance.request(status, max_dist, max_d2, dtype, scale, scratch_bytes)
 
     def distance(self, status, envs=None, max_dist=None, points=None, dtype="float32", scale=1.0, out=None, scratch_bytes=0, max_d2=None):
         """How far the cells - or ``points`` - of ``envs`` (default: all, in order; any order, repeats allowed) are from the nearest cell
@@ -977,47 +861,14 @@ class FireEngine:
         most scratch the call may use (0: 128 MiB); less than one environment's plane (H * pitch * 2 bytes) is a ``ValueError``.  Torch's
         queued work is waited for first; in async mode the call only enqueues: the tensor is complete after ``sync()`` and kept alive
         until then."""
-        mask, d2, code, sc, scratch = self._distance_request(status, max_dist, max_d2, dtype, scale, scratch_bytes)
-        if envs is None:
-            e = np.arange(self.n_envs, dtype=np.int32)
-        else:
-            e = np.asarray(envs)
-            if e.ndim != 1 or (e.size and e.dtype.kind not in "iu"):
-                raise ValueError("distance: envs must be a list of environment numbers")
-            e = np.ascontiguousarray(e, dtype=np.int32)
-            if e.size and (e.min() < 0 or e.max() >= self.n_envs):
-                raise ValueError(f"distance: environment {int(e[(e < 0) | (e >= self.n_envs)][0])} out of range (n_envs = {self.n_envs})")
-        n = int(e.shape[0])
-        import torch
-        dev = torch.device(f"cuda:{self.params.device}")
-        k = 0
-        tensors = []
-        if points is not None:
-            if not isinstance(points, torch.Tensor) or not points.is_cuda or points.dtype != torch.int32 or points.dim() != 3 \
-                    or points.shape[0] != n or points.shape[2] != 3 or not 1 <= points.shape[1] <= self.DIST_MAX_POINTS:
-                raise ValueError(f"distance: points must be a CUDA int32 tensor of shape ({n}, k, 3) with 1 <= k <= {self.DIST_MAX_POINTS}")
-            if points.device != dev:
-                raise ValueError(f"distance: points on {points.device}, the simulation runs on {dev}")
-            points = points.contiguous()
-            k = int(points.shape[1])
-            tensors.append(points)
-        shape = (n, k) if k else (n, self.H, self.W)
-        tdtype = torch.int32 if code == _lib.SF_DIST_I32 else torch.float32
-        if out is None:
-            out = torch.empty(shape, dtype=tdtype, device=dev)
-        elif not isinstance(out, torch.Tensor) or out.dtype != tdtype or tuple(out.shape) != shape or out.device != dev or not out.is_contiguous():
-            raise ValueError(f"distance: out must be a contiguous {tdtype} tensor of shape {shape} on {dev}")
-        plane = self.H * ((self.W + 15) // 16 * 16) * 2
-        if 0 < scratch < plane:
-            raise ValueError(f"distance: scratch_bytes {scratch} is less than one environment's plane ({plane} bytes)")
-        if n == 0:
-            return out
-        p = _lib.SfDistParams(status_mask=mask, max_d2=d2, dtype=code, k=k, scale=sc, points=points.data_ptr() if k else None,
-                              scratch_bytes=scratch)
-        torch.cuda.synchronize(dev)
-        self._chk(self._L.sf_distance(self._h, C.byref(p), n, _ptr(e), C.c_void_p(out.data_ptr())))
-        if self.async_mode:
-            self._blobs_in_flight.extend([out] + tensors)
+        from .distance import DistSpec
+        spec = DistSpec(self.n_envs, self.H, self.W, status, envs=envs, max_dist=max_dist, points=points, dtype=dtype, scale=scale, out=out,
+                        scratch_bytes=scratch_bytes, max_d2=max_d2)
+        out = self._outputs("distance", spec, out, spec.dtype)
+        if spec.n:
+            p = spec.params()
+            self._device_call(self._L.sf_distance, C.byref(p), spec.n, _ptr(spec.envs), C.c_void_p(out.data_ptr()),
+                              tensors=[out] + spec.device_tensors())
         return out
 
     # ---------------------------------------------------------------- reach of the fire (DESIGN.md section 23)
@@ -1025,28 +876,12 @@ class FireEngine:
 
     @staticmethod
     def _reach_request(source=("BURNING",), through=("UNBURNED",), connectivity=None, max_rounds=0, scratch_bytes=0):
-        """The checked scalar arguments of ``reach``: (source mask, through mask, connectivity code, max_rounds, scratch_bytes).
-        ``ValueError`` on anything the library would refuse, before it is called."""
-        src = FireEngine._status_mask("reach", source, "source")
-        thr = FireEngine._status_mask("reach", through, "through")
-        if src & thr:
-            raise ValueError(f"reach: source (mask {src}) and through (mask {thr}) must not share a BurnStatus")
-        if connectivity is None:
-            conn = 0
-        elif isinstance(connectivity, (bool, float)) or not isinstance(connectivity, (int, np.integer)) or int(connectivity) not in (0, 4, 8):
-            raise ValueError(f"reach: connectivity must be None (the simulation's diagonal_spread), 4 or 8, got {connectivity!r}")
-        else:
-            conn = int(connectivity)
-        if isinstance(max_rounds, (bool, float)) or not isinstance(max_rounds, (int, np.integer)) or not 0 <= int(max_rounds) < 2 ** 31:
-            raise ValueError(f"reach: max_rounds must be an integer >= 0, got {max_rounds!r}")
-        if isinstance(scratch_bytes, (bool, float)) or not isinstance(scratch_bytes, (int, np.integer)) or int(scratch_bytes) < 0:
-            raise ValueError(f"reach: scratch_bytes must be an integer >= 0, got {scratch_bytes!r}")
-        return src, thr, conn, int(max_rounds), int(scratch_bytes)
+        from . import reach
+        return reach.request(source, through, connectivity, max_rounds, scratch_bytes)
 
     def reach_scratch_bytes(self):
-        """Bytes of scratch ``reach`` needs per listed environment of a chunk: two bit planes and the halo of the bands."""
-        bands = ((self.H + 15) // 16) * (((self.W + 15) // 16 * 16 + 63) // 64)
-        return (bands * 16 * 16 + bands * 20 + 255) // 256 * 256
+        from . import reach
+        return reach.scratch_need(self.H, self.W)
 
     def reach(self, source=("BURNING",), through=("UNBURNED",), envs=None, connectivity=None, passable=None, points=None, count=True,
               value=False, mask=False, seeds=False, rounds=False, max_rounds=0, scratch_bytes=0):
@@ -1064,76 +899,14 @@ class FireEngine:
         the grid.  ``scratch_bytes``: the most scratch the call may use (0: 256 MiB); less than ``reach_scratch_bytes()`` is a
         ``ValueError``.  Torch's queued work is waited for first; in async mode the call only enqueues: the tensors are complete after
         ``sync()`` and kept alive until then."""
-        src, thr, conn, mr, scratch = self._reach_request(source, through, connectivity, max_rounds, scratch_bytes)
-        if envs is None:
-            e = np.arange(self.n_envs, dtype=np.int32)
-        else:
-            e = np.asarray(envs)
-            if e.ndim != 1 or (e.size and e.dtype.kind not in "iu"):
-                raise ValueError("reach: envs must be a list of environment numbers")
-            e = np.ascontiguousarray(e, dtype=np.int32)
-            if e.size and (e.min() < 0 or e.max() >= self.n_envs):
-                raise ValueError(f"reach: environment {int(e[(e < 0) | (e >= self.n_envs)][0])} out of range (n_envs = {self.n_envs})")
-        n = int(e.shape[0])
-        want = dict(count=count, value=value, mask=mask, seeds=seeds, rounds=rounds)
-        for name, flag in want.items():
-            if not isinstance(flag, (bool, np.bool_)):
-                raise ValueError(f"reach: {name} must be True or False, got {flag!r}")
-        if not any(want.values()) and points is None:
-            raise ValueError("reach: nothing asked for (count, value, mask, seeds, rounds or points)")
-        if value and not getattr(self, "values_on", False):
-            raise ValueError("reach: value needs a value plane (values_set)")
-        need = self.reach_scratch_bytes()
-        if 0 < scratch < need:
-            raise ValueError(f"reach: scratch_bytes {scratch} is less than one environment's need ({need} bytes)")
-        if self.W > 8192:
-            raise ValueError(f"reach: grids wider than 8192 cells are not supported (width {self.W})")
-        import torch
-        if passable is not None and (not isinstance(passable, torch.Tensor) or not passable.is_cuda or passable.dtype != torch.uint8
-                                     or tuple(passable.shape) not in ((self.H, self.W), (self.n_envs, self.H, self.W))):
-            raise ValueError(f"reach: passable must be a CUDA uint8 tensor of shape ({self.H}, {self.W}) or ({self.n_envs}, {self.H}, {self.W})")
-        if points is not None and (not isinstance(points, torch.Tensor) or not points.is_cuda or points.dtype != torch.int32 or points.dim() != 3
-                                   or points.shape[0] != n or points.shape[2] != 3 or not 1 <= points.shape[1] <= self.DIST_MAX_POINTS):
-            raise ValueError(f"reach: points must be a CUDA int32 tensor of shape ({n}, k, 3) with 1 <= k <= {self.DIST_MAX_POINTS}")
-        dev = torch.device(f"cuda:{self.params.device}")
-        tensors = []
-        per_env = 0
-        if passable is not None:
-            if passable.device != dev:
-                raise ValueError(f"reach: passable on {passable.device}, the simulation runs on {dev}")
-            per_env = int(passable.dim() == 3)
-            passable = passable.contiguous()
-            tensors.append(passable)
-        k = 0
-        if points is not None:
-            if points.device != dev:
-                raise ValueError(f"reach: points on {points.device}, the simulation runs on {dev}")
-            points = points.contiguous()
-            k = int(points.shape[1])
-            tensors.append(points)
-        res = {}
-        if count:
-            res["count"] = torch.empty((n,), dtype=torch.int32, device=dev)
-        if value:
-            res["value"] = torch.empty((n,), dtype=torch.int64, device=dev)
-        if mask:
-            res["mask"] = torch.empty((n, self.H, self.W), dtype=torch.uint8, device=dev)
-        if seeds:
-            res["seeds"] = torch.empty((n,), dtype=torch.int32, device=dev)
-        if k:
-            res["point_in"] = torch.empty((n, k), dtype=torch.int32, device=dev)
-        if rounds:
-            res["rounds"] = torch.empty((n,), dtype=torch.int32, device=dev)
-        if n == 0:
-            return res
-        p = _lib.SfReachParams(source_mask=src, through_mask=thr, connectivity=conn, k=k, max_rounds=mr, passable_per_env=per_env,
-                               passable=passable.data_ptr() if passable is not None else None, points=points.data_ptr() if k else None,
-                               scratch_bytes=scratch)
-        o = _lib.SfReachOut(**{name: t.data_ptr() for name, t in res.items()})
-        torch.cuda.synchronize(dev)
-        self._chk(self._L.sf_reach(self._h, C.byref(p), n, _ptr(e), C.byref(o)))
-        if self.async_mode:
-            self._blobs_in_flight.extend(list(res.values()) + tensors)
+        from .reach import ReachSpec
+        spec = ReachSpec(self.n_envs, self.H, self.W, getattr(self, "values_on", False), source=source, through=through, envs=envs,
+                         connectivity=connectivity, passable=passable, points=points, count=count, value=value, mask=mask, seeds=seeds,
+                         rounds=rounds, max_rounds=max_rounds, scratch_bytes=scratch_bytes)
+        res = self._outputs("reach", spec)
+        if spec.n:
+            p, o = spec.params(), spec.out(res)
+            self._device_call(self._L.sf_reach, C.byref(p), spec.n, _ptr(spec.envs), C.byref(o), tensors=list(res.values()) + spec.device_tensors())
         return res
 
     def render(self, envs=None, scale=1, mode=None, background="fuel", contours=True, terrain_rgb=None, agents=None, channels_last=True,
@@ -1143,28 +916,17 @@ class FireEngine:
         ``history=(first, count)``, from the history ring (count frames per environment, updates first .. first + count - 1).  No state
         of the handle changes.  ``agents`` [n, k, 3] = (column, row, id) as for ``observe``.  ``out``: a tensor to fill instead of a new
         one.  In async mode the call only enqueues and the tensors are kept alive until ``sync()``."""
-        import torch
         from .render import RenderSpec
         spec = RenderSpec(self.n_envs, self.H, self.W, envs=envs, scale=scale, mode=mode, background=background, contours=contours,
                           terrain_rgb=terrain_rgb, agents=agents, channels_last=channels_last, history=history, out=out)
-        dev = torch.device(f"cuda:{self.params.device}")
-        for t in spec.device_tensors() + ([out] if out is not None else []):
-            if t.device != dev:
-                raise ValueError(f"render: a tensor on {t.device}, the simulation runs on {dev}")
-        if out is None:
-            out = torch.empty(spec.shape, dtype=torch.uint8, device=dev)
-        p = spec.params()
-        torch.cuda.synchronize(dev)
-        self._chk(self._L.sf_render(self._h, C.byref(p), spec.n, spec.envs_ptr(), C.c_void_p(out.data_ptr())))
-        if self.async_mode:
-            self._blobs_in_flight.extend([out] + spec.device_tensors())
+        out, p = self._outputs("render", spec, out, "uint8"), spec.params()
+        self._device_call(self._L.sf_render, C.byref(p), spec.n, _ptr(spec.envs), C.c_void_p(out.data_ptr()),
+                          tensors=[out] + spec.device_tensors())
         return out
 
     def cell_layout(self):
         """1 = the resident launch's blocked cell plane is current, 0 = the row-major planes (what ``observe`` reads)."""
-        v = C.c_int32()
-        self._chk(self._L.sf_cell_layout(self._h, C.byref(v)))
-        return int(v.value)
+        return self._get(self._L.sf_cell_layout, C.c_int32)
 
     # ---------------------------------------------------------------- per-update history
     def enable_history(self, capacity):
@@ -1188,8 +950,7 @@ class FireEngine:
         """Record for every cell the update that created its first sprite (``sf_enable_arrival``): kept by a pass behind the step
         launches, a call of n updates then runs in pieces of at most ``max_fire_duration``.  Allowed at any time: cells that burned
         out earlier stay "never", sprites live now carry their true update.  ``on=False`` frees the plane."""
-        self._chk(self._L.sf_enable_arrival(self._h, int(bool(on))))
-        self.arrival_on = bool(on)
+        self.arrival_on = self._switch(self._L.sf_enable_arrival, on)
 
     def arrival(self, env=0):
         """int32 [H, W]: the update that ignited each cell of ``env`` - 0 the reset's ignition, -1 never (``sf_get_arrival``).
@@ -1201,15 +962,10 @@ class FireEngine:
     def arrival_torch(self):
         """Zero-copy view of the raw plane as a torch int32 tensor [n_envs, H, W] on this GPU: update + 1, 0 = never
         (``sf_arrival_device``).  Read-only; the handle's stream is waited for first.  Valid until ``enable_arrival(False)``."""
-        import torch
         p, pitch, stride = C.c_void_p(), C.c_int64(), C.c_int64()
         self._chk(self._L.sf_arrival_device(self._h, C.byref(p), C.byref(pitch), C.byref(stride)))
         self.sync()
-        shape, strides = (self.n_envs, self.H, self.W), (int(stride.value), int(pitch.value), 4)
-
-        class _Plane:
-            __cuda_array_interface__ = {"shape": shape, "typestr": "<i4", "data": (p.value, False), "version": 2, "strides": strides}
-        return torch.as_tensor(_Plane(), device=f"cuda:{self.params.device}")
+        return _device_view(p.value, (self.n_envs, self.H, self.W), "<i4", (int(stride.value), int(pitch.value), 4), self.torch_device)
 
     # ---------------------------------------------------------------- values at risk (DESIGN.md section 20)
     VALUE_MAX = 1 << 24
@@ -1234,11 +990,8 @@ class FireEngine:
         if shape != want:
             raise ValueError(f"values_set: the plane must have shape {want}, got {shape}")
         if on_device:
-            import torch
-            if not values.is_cuda or values.device.index != self.params.device or values.dtype != torch.int32 or not values.is_contiguous():
-                raise ValueError(f"values_set: a tensor must be a contiguous int32 CUDA tensor on device {self.params.device}")
-            torch.cuda.synchronize(values.device)
-            self._chk(self._L.sf_values_set(self._h, C.c_void_p(values.data_ptr()), int(bool(per_env)), 1))
+            _args.cuda_tensor(values, "values_set: a tensor", ("int32",), device=self.torch_device, contiguous=True)
+            self._device_call(self._L.sf_values_set, C.c_void_p(values.data_ptr()), int(bool(per_env)), 1, tensors=[values])
         else:
             a = np.asarray(values)
             if a.dtype.kind not in "iu":
@@ -1260,23 +1013,15 @@ class FireEngine:
         ``damage()`` returns it, and what the last ``agents_step`` tick added to it (0 for an environment that was not running before
         the tick; after an auto-reset tick still the finished episode's last tick).  Read-only; the handle's stream is waited for
         first.  Valid until the next ``values_set``."""
-        import torch
         d, stride, t = C.c_void_p(), C.c_int64(), C.c_void_p()
         self._chk(self._L.sf_values_device(self._h, C.byref(d), C.byref(stride), C.byref(t)))
         self.sync()
-        shape, strides = (self.n_envs,), (int(stride.value),)
-
-        class _Damage:
-            __cuda_array_interface__ = {"shape": shape, "typestr": "<i8", "data": (d.value, False), "version": 2, "strides": strides}
-
-        class _Loss:
-            __cuda_array_interface__ = {"shape": shape, "typestr": "<i8", "data": (t.value, False), "version": 2, "strides": None}
-        dev = f"cuda:{self.params.device}"
-        return torch.as_tensor(_Damage(), device=dev), torch.as_tensor(_Loss(), device=dev)
+        dev = self.torch_device
+        return (_device_view(d.value, (self.n_envs,), "<i8", (int(stride.value),), dev), _device_view(t.value, (self.n_envs,), "<i8", None, dev))
 
     def set_values_dense(self, on=True):
         """Laboratory: the value pass always in its dense form (one thread per cell) instead of walking the vector bitmap."""
-        self._chk(self._L.sf_set_values_dense(self._h, int(bool(on))))
+        self._switch(self._L.sf_set_values_dense, on)
 
     def value_passes(self):
         """Laboratory: (sparse, dense) value passes made since the handle was created; recounts are dense ones."""
@@ -1288,31 +1033,8 @@ class FireEngine:
     ENS_MAX_HORIZONS = _lib.ENS_MAX_HORIZONS
 
     def _ensemble_request(self, members, horizons):
-        """The checked arguments of ``ensemble_stats``: (int32 [G, K] contiguous, list of horizons).  ``ValueError`` on anything the
-        library would refuse, before it is called."""
-        if members is None:
-            m = np.arange(self.n_envs, dtype=np.int32).reshape(1, -1)
-        else:
-            m = np.asarray(members)
-            if m.ndim != 2 or m.dtype.kind not in "iu":
-                raise ValueError(f"ensemble_stats: members must be a 2-D integer array [groups, members], got {m.dtype} {m.shape}")
-        G, K = m.shape
-        if G < 1 or not 1 <= K <= 65535 or G * K > 1 << 20:
-            raise ValueError(f"ensemble_stats: {G} groups of {K} members (G >= 1, 1 <= K <= 65535, G * K <= 2**20)")
-        if int(m.min()) < 0 or int(m.max()) >= self.n_envs:
-            raise ValueError(f"ensemble_stats: members holds an environment outside 0..{self.n_envs - 1}")
-        try:
-            hz = [int(h) for h in np.asarray(horizons).reshape(-1).tolist()]
-        except (TypeError, ValueError):
-            raise ValueError(f"ensemble_stats: horizons must be integers, got {horizons!r}") from None
-        if np.asarray(horizons).dtype.kind not in "iu" or not 1 <= len(hz) <= self.ENS_MAX_HORIZONS:
-            raise ValueError(f"ensemble_stats: 1 to {self.ENS_MAX_HORIZONS} integer horizons, got {horizons!r}")
-        for t, h in enumerate(hz):
-            if h < -1 or h > 2 ** 31 - 1 or (h == -1 and t != len(hz) - 1):
-                raise ValueError(f"ensemble_stats: horizon {h} (>= 0; -1, no limit, only as the last)")
-            if t and h != -1 and h <= hz[t - 1]:
-                raise ValueError(f"ensemble_stats: the horizons must be strictly ascending, got {hz}")
-        return np.ascontiguousarray(m, dtype=np.int32), hz
+        from . import ensemble
+        return ensemble.request(self.n_envs, members, horizons)
 
     def ensemble_stats(self, members, horizons=(-1,), count=False, prob=True, first=False, mean=False, loss=False):
         """Per-cell statistics over groups of environments (``sf_ensemble_stats``), read off the arrival planes
@@ -1325,36 +1047,22 @@ class FireEngine:
         -1.0 none) and ``loss`` int64 [G, T] (the values of the cells each member reached, summed over the group; needs
         ``values_set``).  Needs ``enable_arrival``.  No state of the handle changes.  Torch's queued work is waited for first; in
         async mode the call only enqueues: the tensors are complete after ``sync()`` and kept alive until then."""
-        m, hz = self._ensemble_request(members, horizons)
-        want = [n for n, on in (("count", count), ("prob", prob), ("first", first), ("mean", mean), ("loss", loss)) if on]
-        if not want:
-            raise ValueError("ensemble_stats: no output asked for")
-        call = self._L.sf_ensemble_stats
-        import torch
-        dev = torch.device(f"cuda:{self.params.device}")
-        G, K, T = m.shape[0], m.shape[1], len(hz)
-        shapes = {"count": ((G, T, self.H, self.W), torch.int32), "prob": ((G, T, self.H, self.W), torch.float32),
-                  "first": ((G, self.H, self.W), torch.int32), "mean": ((G, self.H, self.W), torch.float32), "loss": ((G, T), torch.int64)}
-        res = {n: torch.empty(shapes[n][0], dtype=shapes[n][1], device=dev) for n in want}
-        p = _lib.SfEnsembleParams(n_groups=G, group_size=K, n_horizons=T)
-        for t, h in enumerate(hz):
-            p.horizons[t] = h
-        o = _lib.SfEnsembleOut(**{n: res[n].data_ptr() for n in want})
-        torch.cuda.current_stream(dev).synchronize()       # (torch may still be using the memory it has just handed out again)
-        self._chk(call(self._h, C.byref(p), _ptr(m), C.byref(o)))
-        if self.async_mode:
-            self._blobs_in_flight.extend(res.values())
+        from .ensemble import EnsembleSpec
+        spec = EnsembleSpec(self.n_envs, self.H, self.W, members, horizons, count=count, prob=prob, first=first, mean=mean, loss=loss)
+        fn = self._L.sf_ensemble_stats
+        res = self._outputs("ensemble_stats", spec)
+        p, o = spec.params(), spec.out(res)
+        # (the current-stream wait: torch may still be using the memory it has just handed out again)
+        self._device_call(fn, C.byref(p), _ptr(spec.members), C.byref(o), tensors=list(res.values()), wait="stream")
         return res
 
     def set_arrival_dense(self, on=True):
         """Laboratory: the arrival pass always in its dense form (one thread per cell) instead of walking the vector bitmap."""
-        self._chk(self._L.sf_set_arrival_dense(self._h, int(bool(on))))
+        self._switch(self._L.sf_set_arrival_dense, on)
 
     def time_arrival_pass(self):
         """Laboratory: GPU milliseconds of one more arrival pass over the state as it stands (it changes nothing)."""
-        ms = C.c_float(0.0)
-        self._chk(self._L.sf_time_arrival_pass(self._h, C.byref(ms)))
-        return float(ms.value)
+        return self._get(self._L.sf_time_arrival_pass, C.c_float)
 
     def arrival_passes(self):
         """Laboratory: (sparse, dense) arrival passes made since the handle was created."""
@@ -1364,11 +1072,11 @@ class FireEngine:
 
     def set_generic(self, on=True):
         """Per-cell kernel instead of the tiled SWAR kernels (always on for max_fire_duration > 5)."""
-        self._chk(self._L.sf_set_generic(self._h, int(bool(on))))
+        self._switch(self._L.sf_set_generic, on)
 
     def set_dense(self, dense=True):
         """Visit every tile every step (cross-check of the tile activity map)."""
-        self._chk(self._L.sf_set_dense(self._h, int(bool(dense))))
+        self._switch(self._L.sf_set_dense, dense)
 
     def fire_map_device(self):
         """(device pointer, row pitch, env stride) of the uint8 status plane (BurnStatus values)."""
@@ -1381,20 +1089,13 @@ class FireEngine:
         observations without a PCIe round trip).  The bytes are the BurnStatus values.  Read-only, and call it
         again after stepping: the plane is refreshed by this call (a snapshot while the resident launch keeps the
         cells in its blocked plane; same address every time)."""
-        import torch
         ptr, pitch, stride = self.fire_map_device()
         self.sync()
-
-        class _Plane:
-            __cuda_array_interface__ = {"shape": (self.n_envs, self.H, self.W), "typestr": "|u1",
-                                        "data": (ptr, False), "version": 2, "strides": (stride, pitch, 1)}
-        return torch.as_tensor(_Plane(), device=f"cuda:{self.params.device}")
+        return _device_view(ptr, (self.n_envs, self.H, self.W), "|u1", (stride, pitch, 1), self.torch_device)
 
     def status_device_ptr(self):
         """Device address of the int32 [E, 8] result block (after ``update_status_device``)."""
-        p = C.c_void_p()
-        self._chk(self._L.sf_status_device(self._h, C.byref(p)))
-        return p.value
+        return self._get(self._L.sf_status_device, C.c_void_p)
 
     def copy_status_to(self, device_ptr):
         """Refresh the result block and copy it into device memory at ``device_ptr``
@@ -1438,7 +1139,7 @@ class FireEngine:
 
     def enable_counters(self, on=True):
         """Statistics for the roofline accounting; off by default (they cost atomics)."""
-        self._chk(self._L.sf_enable_counters(self._h, int(bool(on))))
+        self._switch(self._L.sf_enable_counters, on)
 
     def counters(self, reset=False):
         """dict(active_cell_updates, ignitions, frontier_items) summed since the last reset."""

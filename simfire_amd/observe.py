@@ -4,11 +4,11 @@ Pure Python: every check happens here, before a device call, so that a bad reque
 without a GPU.  The kernel (``k_observe``, simfire_amd/csrc/sf_obs_kernels.h) and the evaluation order are described in DESIGN.md
 section 12; the test suite restates them in NumPy.
 """
-import ctypes as C
 from typing import Dict, Optional, Sequence, Union
 
 import numpy as np
 
+from . import _args
 from .enums import BurnStatus
 
 #: the attribute planes of ``get_attribute_data()`` in the order of ``supported_attributes()`` (simfire/sim/simulation.py:317-332)
@@ -26,16 +26,6 @@ MAX_POOL = 128
 POOL_MODES = {"mean": 0, "max": 1}
 
 
-def _is_tensor(x):
-    return hasattr(x, "data_ptr") and hasattr(x, "is_cuda")
-
-
-def _int(v, name):
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
-        raise ValueError(f"{name} must be an integer, got {v!r}")
-    return int(v)
-
-
 def _torch_dtype(dtype):
     import torch
     if dtype in (None, torch.float32, "float32"):
@@ -43,25 +33,6 @@ def _torch_dtype(dtype):
     if dtype in (torch.bfloat16, "bfloat16"):
         return torch.bfloat16
     raise ValueError(f"dtype must be torch.float32 or torch.bfloat16, got {dtype!r}")
-
-
-def _points(x, n, last, name):
-    """A host array or a CUDA int32 tensor of shape [n, ..., last] -> (contiguous array / tensor, on_device)."""
-    if _is_tensor(x):
-        import torch
-        if not x.is_cuda or x.dtype != torch.int32:
-            raise ValueError(f"{name} as a tensor must be a CUDA int32 tensor")
-        if x.dim() != (2 if last == 2 else 3) or x.shape[0] != n or x.shape[-1] != last:
-            raise ValueError(f"{name} must have the shape [{n}, {'k, ' if last == 3 else ''}{last}], got {tuple(x.shape)}")
-        return x.contiguous(), True
-    a = np.asarray(x)
-    if a.dtype.kind not in "iu" and not (a.size == 0 and a.dtype.kind == "f"):
-        raise ValueError(f"{name} must hold integers, got dtype {a.dtype}")
-    if a.ndim != (2 if last == 2 else 3) or a.shape[0] != n or a.shape[-1] != last:
-        raise ValueError(f"{name} must have the shape [{n}, {'k, ' if last == 3 else ''}{last}], got {a.shape}")
-    if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
-        raise ValueError(f"{name} holds values outside int32")
-    return np.ascontiguousarray(a, dtype=np.int32), False
 
 
 class ObsSpec:
@@ -95,18 +66,10 @@ class ObsSpec:
         else:
             raise ValueError("pool_mode must be 'mean', 'max' or a dict {channel: mode}")
 
-        if envs is None:
-            self.envs = np.arange(n_envs, dtype=np.int32)
-        else:
-            e = np.asarray(envs)
-            if e.ndim != 1 or e.size == 0 or e.dtype.kind not in "iu":
-                raise ValueError("envs must be a non-empty list of environment numbers")
-            if (e < 0).any() or (e >= n_envs).any():
-                raise ValueError(f"envs holds an environment outside 0..{n_envs - 1}")
-            self.envs = np.ascontiguousarray(e, dtype=np.int32)
+        self.envs = _args.env_list(envs, n_envs, none_all=True, empty=False)
         n = self.n = int(self.envs.shape[0])
 
-        self.pool = _int(pool, "pool")
+        self.pool = _args.bounded_int(pool, None, None, "pool must be an integer")
         if not 1 <= self.pool <= MAX_POOL:
             raise ValueError(f"pool must be in 1..{MAX_POOL}, got {self.pool}")
         self.normalize = bool(normalize)
@@ -121,29 +84,27 @@ class ObsSpec:
         else:
             if not isinstance(crop, (tuple, list)) or len(crop) != 2:
                 raise ValueError("crop must be (height, width)")
-            ch, cw = _int(crop[0], "crop height"), _int(crop[1], "crop width")
+            ch, cw = (_args.bounded_int(v, None, None, f"crop {name} must be an integer") for v, name in zip(crop, ("height", "width")))
             if not (1 <= ch <= 65535 and 1 <= cw <= 65535):
                 raise ValueError(f"crop must be positive (at most 65535), got {(ch, cw)}")
             if centers is None:
                 raise ValueError("a crop needs centers [n, 2] = (column, row)")
             self.crop = (ch, cw)
             eh, ew = ch, cw
-            self.centers, self.centers_device = _points(centers, n, 2, "centers")
+            self.centers, self.centers_device = _args.points(centers, n, 2, "centers")
         if eh % self.pool or ew % self.pool:
             raise ValueError(f"the {'cropped ' if crop else ''}extent {eh} x {ew} is not divisible by pool {self.pool}")
 
         if agents is None:
             self.agents, self.agents_device, self.k = None, False, 0
         else:
-            self.agents, self.agents_device = _points(agents, n, 3, "agents")
+            self.agents, self.agents_device = _args.points(agents, n, 3, "agents", k_range=(0, MAX_AGENTS))
             self.k = int(self.agents.shape[1])
-            if self.k > MAX_AGENTS:
-                raise ValueError(f"at most {MAX_AGENTS} agents per environment, got {self.k}")
 
         self.dtype = _torch_dtype(dtype)
         self.shape = (n, len(channels), eh // self.pool, ew // self.pool)
         if out is not None:
-            if not _is_tensor(out) or not out.is_cuda:
+            if not _args.is_tensor(out) or not out.is_cuda:
                 raise ValueError("out must be a CUDA tensor")
             if tuple(out.shape) != self.shape or out.dtype != self.dtype or not out.is_contiguous():
                 raise ValueError(f"out must be a contiguous {self.dtype} tensor of shape {self.shape}, got "
@@ -176,9 +137,6 @@ class ObsSpec:
             p.agents_device = int(self.agents_device)
             p.agents = self.agents.data_ptr() if self.agents_device else self.agents.ctypes.data
         return p
-
-    def envs_ptr(self):
-        return self.envs.ctypes.data_as(C.c_void_p)
 
 
 def agents_from_map(agent_positions: np.ndarray, max_agents: Optional[int] = None) -> np.ndarray:

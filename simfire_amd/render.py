@@ -4,11 +4,9 @@ Pure Python: every check happens here, before a device call, so that a bad reque
 without a GPU.  The kernels (``k_render_bg``, ``k_render``: simfire_amd/csrc/sf_render_kernels.h) and the frame are specified in
 DESIGN.md section 14; the test suite restates them in NumPy.
 """
-import ctypes as C
-
 import numpy as np
 
-from .observe import _int, _is_tensor, _points
+from . import _args
 
 MODES = {"nearest": 0, "mean": 1, "sprites": 2}
 BACKGROUNDS = {"fuel": 0, "white": 1}
@@ -24,18 +22,9 @@ class RenderSpec:
 
     def __init__(self, n_envs: int, H: int, W: int, envs=None, scale: int = 1, mode=None, background: str = "fuel",
                  contours: bool = True, terrain_rgb=None, agents=None, channels_last: bool = True, history=None, out=None):
-        if envs is None:
-            envs = np.arange(n_envs, dtype=np.int32)
-        self.envs = np.ascontiguousarray(np.atleast_1d(np.asarray(envs)))
-        if self.envs.dtype.kind not in "iu" and not (self.envs.size == 0 and self.envs.dtype.kind == "f"):
-            raise ValueError(f"envs must hold integers, got dtype {self.envs.dtype}")
-        if self.envs.ndim != 1:
-            raise ValueError("envs must be a list of environment indices")
-        if self.envs.size and (self.envs.min() < 0 or self.envs.max() >= n_envs):
-            raise ValueError(f"envs must lie in 0..{n_envs - 1}")
-        self.envs = self.envs.astype(np.int32)
+        self.envs = _args.env_list(envs, n_envs, scalar=True, none_all=True)
         n = self.n = int(self.envs.size)
-        self.scale = _int(scale, "scale")
+        self.scale = _args.bounded_int(scale, None, None, "scale must be an integer")
         if not 1 <= self.scale <= MAX_SCALE:
             raise ValueError(f"scale must be 1..{MAX_SCALE}, got {self.scale}")
         if mode is None:
@@ -50,34 +39,26 @@ class RenderSpec:
             raise ValueError(f"contours must be True or False, got {contours!r}")
         self.contours = bool(contours)
         rgb = TERRAIN_RGB if terrain_rgb is None else tuple(terrain_rgb)
-        if len(rgb) != 3 or any(isinstance(c, (bool, np.bool_)) or not isinstance(c, (int, np.integer)) or not 0 <= c <= 255
-                                for c in rgb):
+        if len(rgb) != 3:
             raise ValueError(f"terrain_rgb must be three integers 0..255, got {terrain_rgb!r}")
-        self.terrain_rgb = tuple(int(c) for c in rgb)
+        self.terrain_rgb = tuple(_args.bounded_int(c, 0, 255, "terrain_rgb must be three integers 0..255") for c in rgb)
         self.channels_last = bool(channels_last)
         if history is None:
             self.source, self.first, self.count = 0, 0, 1
         else:
             first, count = history
-            self.source, self.first, self.count = 1, _int(first, "history first"), _int(count, "history count")
-            if self.first < 0 or self.count < 1:
-                raise ValueError(f"history frames must be (first >= 0, count >= 1), got {history!r}")
+            what = "history frames must be integers (first >= 0, count >= 1)"
+            self.source, self.first, self.count = 1, _args.bounded_int(first, 0, None, what), _args.bounded_int(count, 1, None, what)
         if agents is None:
             self.agents, self.agents_device, self.k = None, False, 0
         else:
-            self.agents, self.agents_device = _points(agents, n, 3, "agents")
+            self.agents, self.agents_device = _args.points(agents, n, 3, "agents", k_range=(0, MAX_AGENTS))
             self.k = int(self.agents.shape[1])
-            if self.k > MAX_AGENTS:
-                raise ValueError(f"at most {MAX_AGENTS} agents per environment, got {self.k}")
         self.oh, self.ow = -(-H // self.scale), -(-W // self.scale)
         frames = n * self.count
         self.shape = (frames, self.oh, self.ow, 3) if self.channels_last else (frames, 3, self.oh, self.ow)
         if out is not None:
-            import torch
-            if not _is_tensor(out) or not out.is_cuda or out.dtype != torch.uint8:
-                raise ValueError("out must be a CUDA uint8 tensor")
-            if tuple(out.shape) != self.shape or not out.is_contiguous():
-                raise ValueError(f"out must be a contiguous tensor of shape {self.shape}, got {tuple(out.shape)}")
+            _args.cuda_tensor(out, "out", ("uint8",), [self.shape], contiguous=True)
 
     def device_tensors(self):
         """The tensors the call reads on the device (kept alive until the handle's stream got there in async mode)."""
@@ -97,6 +78,3 @@ class RenderSpec:
             p.agents_device = int(self.agents_device)
             p.agents = self.agents.data_ptr() if self.agents_device else self.agents.ctypes.data
         return p
-
-    def envs_ptr(self):
-        return self.envs.ctypes.data_as(C.c_void_p)

@@ -142,7 +142,7 @@ class BatchedFireEnv:
         done bool [n_envs], info)`` with ``info = dict(terms int32 [n_envs, 4], final_len int32 [n_envs], final_ret float64
         [n_envs])``: the episode length and return of the environments that are done, else 0.  New tensors every call."""
         import torch
-        dev = torch.device(f"cuda:{self.engine.params.device}")
+        dev = self.engine.torch_device
         E = self.n_envs
         reward = torch.empty(E, dtype=torch.float32, device=dev)
         done = torch.empty(E, dtype=torch.bool, device=dev)
