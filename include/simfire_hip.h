@@ -514,6 +514,69 @@ typedef struct sf_reach_out {            /* device pointers, any may be NULL, at
  * work on passable, points and the outputs before the call. */
 int sf_reach(sf_sim *sim, const sf_reach_params *params, int32_t n, const int32_t *envs /* [n] host */, const sf_reach_out *out);
 
+/* Walking distance: how many moves a walker needs to step onto a target cell when it enters only walkable
+ * cells - one cell per move, as the agents of sf_agents_step walk -, and which move comes first.  The reference has no counterpart;
+ * the semantics are this library's own.
+ * For a listed environment, s(y, x) is the status byte & 7 of cell (y, x), x < width, read from whichever cell plane is current.
+ *   target(c) = bit s(c) of target_mask, or targets[c] != 0 when a targets plane is given (device u8, dense [height * width], one
+ *   plane for all or - targets_per_env - one per environment, indexed by the environment's number).  target_mask may be 0 only with
+ *   a targets plane.
+ *   walk(c) = bit s(c) of through_mask and, with a passable plane (same forms, passable_per_env), passable[c] != 0.
+ *   The masks may overlap; a cell that is both is a target.  The pitch padding (x >= width) is never a target and never walkable.
+ *   The neighbourhood N is the 4-neighbourhood (connectivity 4, and 0: the agents' moves) or the 8-neighbourhood (8).
+ *   d is the least solution of: d(c) = 0 on targets; d(c) = 1 + min over n in N(c) with target(n) or walk(n) of d(n) on walkable
+ *   cells - the number of moves of a walker that enters only walkable cells until it steps onto a target.
+ * Plane form, moves int32 [n][height][width]: d(c) on target and walkable cells, SF_WALK_FAR on walkable cells no route leaves,
+ * SF_WALK_BLOCKED on cells that are neither.
+ * Point form, points device int32 [n][k][3] = (column, row, id), sf_agents_device's layout: the walker may stand anywhere, also on a
+ * cell that is not walkable (an agent on the line it has just drawn).  point_moves[i][j] = 0 on a target, else 1 + min d(n) over the
+ * target or walkable neighbours n, SF_WALK_FAR if none has a finite d.  point_step[i][j] (connectivity 4 only) is the move code of the
+ * action word of section 16 - 1: row - 1, 2: row + 1, 3: column - 1, 4: column + 1 - of the LOWEST-numbered neighbour that attains
+ * the minimum; 0 on a target and 0 when no move gets there.  id <= 0 or a cell off the grid gives -1 in both.  On a walkable point
+ * point_moves equals the plane value.
+ * max_moves = M > 0 runs only M levels: every plane and point value that would exceed M, SF_WALK_FAR included, is reported as M (the
+ * convention of sf_distance's max_d2), and point_step is 0 where the true value exceeds M.  M = 0: no cap.
+ * reached [n]: the number of walkable non-target cells with a finite value within the cap.  levels [n]: the number of levels that
+ * added a cell - the largest finite d, or M where the cap ended the search. */
+#define SF_WALK_FAR 2147483647
+#define SF_WALK_BLOCKED (-1)
+typedef struct sf_walk_params {
+    int32_t target_mask, through_mask;   /* 0..63 (0 only with targets) / 1..63 */
+    int32_t connectivity;                /* 0 or 4 (the agents' moves), 8 */
+    int32_t k;                           /* 0, or 1..SF_DIST_MAX_POINTS points per listed environment */
+    int32_t max_moves;                   /* 0: no cap; > 0: that many levels */
+    int32_t passable_per_env;            /* passable is [n_envs][H*W] (indexed by environment number), else [H*W] */
+    int32_t targets_per_env;             /* the same for targets */
+    const uint8_t *passable;             /* device, or NULL */
+    const uint8_t *targets;              /* device, or NULL */
+    const int32_t *points;               /* device int32 [n][k][3] = (column, row, id); NULL with k == 0 */
+    int64_t scratch_bytes;               /* 0: the default budget */
+    int32_t reserved[2];                 /* 0 */
+} sf_walk_params;
+typedef struct sf_walk_out {             /* device pointers, any may be NULL, at least one not */
+    int32_t *moves;        /* [n][H][W]  dense */
+    int32_t *point_moves;  /* [n][k] */
+    int32_t *point_step;   /* [n][k]     connectivity 4 only */
+    int32_t *reached;      /* [n] */
+    int32_t *levels;       /* [n] */
+} sf_walk_out;
+/* Environment envs[i] (a host array; any order, repeats allowed) lands in row i of every output.  Anything invalid is SF_EINVAL before
+ * anything is enqueued (target_mask outside 0..63 or through_mask outside 1..63, target_mask 0 without a targets plane, an unknown
+ * connectivity, k outside 0..256, k > 0 without points or points with k == 0, point_moves or point_step without k, point_step with
+ * connectivity 8, max_moves < 0, reserved != 0, every output null, an output that is not aligned to 4 bytes, an environment out of
+ * range, a positive scratch_bytes below one environment's need); a handle without layers or reset is SF_ESTATE; a grid wider than
+ * 8192 cells is SF_ENOTSUP.
+ * One workgroup searches one environment, level by level, until a level adds nothing or max_moves levels have run.
+ * The call reads the state and writes nothing but its outputs and its own scratch - not the current plane, the tile books, the
+ * reference point of sf_get_fire_map_delta, the result block, any ring, the arrival or value planes.  The scratch belongs to the
+ * handle: per listed environment of a chunk three bit planes and two halos, 16 * ceil(height / 16) * ceil(pitch / 64) * 24 bytes + 40
+ * per band of 16 rows x 64 cells, rounded up to 256; allocated at the first call, grown (never shrunk) when a later call needs more,
+ * freed by sf_destroy, counted by sf_memory_bytes - a growth is a hipMalloc and waits for the device.  The default budget is 256 MiB;
+ * the list is worked through in chunks so that scratch never exceeds the budget, which changes no bit of the result.
+ * In async mode the call only enqueues (the outputs are complete when the handle's stream has got there); the caller orders its own
+ * work on passable, targets, points and the outputs before the call. */
+int sf_walk(sf_sim *sim, const sf_walk_params *params, int32_t n, const int32_t *envs /* [n] host */, const sf_walk_out *out);
+
 /* Agents on the device: K agents per environment that walk the grid and draw control lines where they stand,
  * stepped from a policy's action tensor without a host read.  The reference records agent positions only (simulation.py:480-499) and
  * leaves the loop to the harness (the run docstring, 505-509); the semantics are this library's own.

@@ -130,6 +130,22 @@ class SfReachOut(C.Structure):
                 ("rounds", C.c_void_p)]
 
 
+SF_WALK_FAR, SF_WALK_BLOCKED = 2 ** 31 - 1, -1
+
+
+class SfWalkParams(C.Structure):
+    """``sf_walk_params`` (include/simfire_hip.h)."""
+    _fields_ = [("target_mask", C.c_int32), ("through_mask", C.c_int32), ("connectivity", C.c_int32), ("k", C.c_int32),
+                ("max_moves", C.c_int32), ("passable_per_env", C.c_int32), ("targets_per_env", C.c_int32), ("passable", C.c_void_p),
+                ("targets", C.c_void_p), ("points", C.c_void_p), ("scratch_bytes", C.c_int64), ("reserved", C.c_int32 * 2)]
+
+
+class SfWalkOut(C.Structure):
+    """``sf_walk_out`` (include/simfire_hip.h): device pointers, any may be null, not all."""
+    _fields_ = [("moves", C.c_void_p), ("point_moves", C.c_void_p), ("point_step", C.c_void_p), ("reached", C.c_void_p),
+                ("levels", C.c_void_p)]
+
+
 # name -> argtypes; every function returns int except the two string getters
 _VP, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
 SIGNATURES = {
@@ -199,6 +215,7 @@ SIGNATURES = {
     "sf_observe": [_VP, C.POINTER(SfObsParams), _I32, _VP, _VP],
     "sf_distance": [_VP, C.POINTER(SfDistParams), _I32, _VP, _VP],
     "sf_reach": [_VP, C.POINTER(SfReachParams), _I32, _VP, C.POINTER(SfReachOut)],
+    "sf_walk": [_VP, C.POINTER(SfWalkParams), _I32, _VP, C.POINTER(SfWalkOut)],
     "sf_cell_layout": [_VP, C.POINTER(_I32)],
     "sf_render": [_VP, C.POINTER(SfRenderParams), _I32, _VP, _VP],
     "sf_status_device": [_VP, C.POINTER(_VP)],

@@ -264,6 +264,16 @@ struct ReachState {
     hipError_t release() { cap = 0; return free_dev(mem); }
 };
 
+// sf_walk: the scratch of the search (per listed environment of a chunk: three bit planes and two halos,
+// walk_env_bytes) - allocated at the first call, grown but never shrunk, freed with the handle - its size in bytes, and the call
+// block (the environment list of a call)
+struct WalkState {
+    uint8_t *mem = nullptr;
+    size_t cap = 0;
+    CallBlock blk;
+    hipError_t release() { cap = 0; return free_dev(mem); }
+};
+
 }  // namespace
 
 // ----------------------------------------------------------------------------- handle
@@ -363,6 +373,7 @@ struct sf_sim {
     EpisodeState episodes;
     DistState dist;
     ReachState reach;
+    WalkState walk;
     CallBlock obs_blk;                 // sf_observe: ObsHead, environment list, host centers / agents
     CallBlock rs_blk;                  // sf_reset_envs / sf_reset_where: the environment list and host ignitions of a call
     LabTimer reset_timer;              // sf_time_resets: ev0 / ev1 recorded around the launches of every batched reset

@@ -909,6 +909,42 @@ class FireEngine:
             self._device_call(self._L.sf_reach, C.byref(p), spec.n, _ptr(spec.envs), C.byref(o), tensors=list(res.values()) + spec.device_tensors())
         return res
 
+    # ---------------------------------------------------------------- walking distance
+    WALK_FAR, WALK_BLOCKED = _lib.SF_WALK_FAR, _lib.SF_WALK_BLOCKED
+
+    def walk_scratch_bytes(self):
+        from . import walk
+        return walk.scratch_need(self.H, self.W)
+
+    def walk(self, target=("BURNING",), through=("UNBURNED",), envs=None, connectivity=4, passable=None, targets=None, points=None,
+             max_moves=None, plane=False, step=False, reached=False, levels=False, scratch_bytes=0):
+        """How many moves a walker of ``envs`` (default: all, in order; any order, repeats allowed) needs to step onto a target cell
+        when it enters only walkable cells, one cell per move (``sf_walk``).  Targets: the cells whose
+        BurnStatus ``target`` selects, or - with ``targets``, a uint8 CUDA tensor [H, W] for all or [n_envs, H, W] indexed by
+        environment number - the cells where that is not 0 (``target`` may then be ``None``).  Walkable: the cells ``through`` selects
+        and, with ``passable`` (same forms), only where it is not 0.  ``target`` / ``through``: masks (bit s = BurnStatus s) or
+        iterables of ``BurnStatus`` members, names or ints; they may overlap, a cell that is both is a target.  ``connectivity`` 4
+        (the agents' moves) or 8.  Read from whichever cell plane is current; no state of the handle changes.
+        Returns a dict of int32 torch tensors on this GPU, one per output asked for: with ``plane`` ``moves`` [n, H, W] (the number of
+        moves; ``WALK_FAR`` on walkable cells no route leaves, ``WALK_BLOCKED`` = -1 on cells that are neither), with ``points`` -
+        int32 CUDA [n, k, 3] = (column, row, id), k <= 256, e.g. ``agents_device()`` - ``point_moves`` [n, k] (0 on a target, else 1 +
+        the least value of a target or walkable neighbour; the point itself need not be walkable; -1 for id <= 0 or off the grid) and
+        with ``step`` ``point_step`` [n, k]: the move code 1..4 (row - 1, row + 1, column - 1, column + 1) of the lowest-numbered
+        neighbour on a shortest route, 0 on a target or when no move gets there; ``reached`` [n]: walkable cells with a route;
+        ``levels`` [n]: the largest number of moves found.  ``max_moves`` = M: values above M, ``WALK_FAR`` included, are reported as
+        M, and ``point_step`` is 0 there.  ``scratch_bytes``: the most scratch the call may use (0: 256 MiB); less than
+        ``walk_scratch_bytes()`` is a ``ValueError``.  Torch's queued work is waited for first; in async mode the call only enqueues:
+        the tensors are complete after ``sync()`` and kept alive until then."""
+        from .walk import WalkSpec
+        spec = WalkSpec(self.n_envs, self.H, self.W, target=target, through=through, envs=envs, connectivity=connectivity,
+                        passable=passable, targets=targets, points=points, max_moves=max_moves, plane=plane, step=step, reached=reached,
+                        levels=levels, scratch_bytes=scratch_bytes)
+        res = self._outputs("walk", spec)
+        if spec.n:
+            p, o = spec.params(), spec.out(res)
+            self._device_call(self._L.sf_walk, C.byref(p), spec.n, _ptr(spec.envs), C.byref(o), tensors=list(res.values()) + spec.device_tensors())
+        return res
+
     def render(self, envs=None, scale=1, mode=None, background="fuel", contours=True, terrain_rgb=None, agents=None, channels_last=True,
                history=None, out=None):
         """Frames of ``envs`` (default: all, in order; repeats allowed) as a uint8 torch tensor [n, oh, ow, 3] (or [n, 3, oh, ow]) on

@@ -606,6 +606,19 @@ class FireSimulation:
         self._engine.sync()
         return r["mask"][0].cpu().numpy().astype(bool), int(r["count"][0]), int(r["value"][0]) if value else None
 
+    def moves_to(self, target=("BURNING",), through=("UNBURNED",), connectivity=4, passable=None, targets=None, max_moves=None):
+        """How many moves a walker needs from every cell to step onto a target cell - BurnStatus one of ``target``, or ``targets``
+        (a uint8 CUDA tensor [H, W]) not 0 - when it enters only cells whose BurnStatus is one of ``through`` (and where ``passable``,
+        same form, is not 0), one cell per move over the 4- (the agents' moves) or 8-neighbourhood.  Returns the NumPy int32 plane
+        [H, W]: 0 on targets, 2147483647 on walkable cells no route leaves, -1 on cells that are neither; ``max_moves`` caps the
+        values.  Host edits of ``fire_map`` are pushed to the device first, as ``reach`` does (``BatchedFireSimulation.moves_to``;
+        DESIGN.md section 24)."""
+        self._sync_to_device()
+        r = self._engine.walk(target, through, envs=[0], connectivity=connectivity, passable=passable, targets=targets,
+                              max_moves=max_moves, plane=True)
+        self._engine.sync()
+        return r["moves"][0].cpu().numpy()
+
     # -------------------------------------------------------------------- seeds / layers
     def get_seeds(self) -> Dict[str, Optional[int]]:
         """simulation.py:574-597: only the seeds that exist for the configured generators."""
@@ -1348,6 +1361,27 @@ class BatchedFireSimulation:
             points = agents
         r = self._engine.reach(source, through, envs=envs, connectivity=connectivity, passable=passable, points=points, count=True,
                                value=bool(value), mask=bool(mask), seeds=True)
+        self._engine.sync()
+        return r if device else {k: v.cpu().numpy() for k, v in r.items()}
+
+    def moves_to(self, target=("BURNING",), through=("UNBURNED",), envs=None, connectivity=4, passable=None, targets=None,
+                 max_moves=None, agents=False, step=False, plane=False, device=True):
+        """How many moves a walker in ``envs`` (default: all) needs to step onto a target cell - BurnStatus one of ``target``, or
+        ``targets`` (uint8 CUDA [H, W] or [n_envs, H, W]) not 0 - when it enters only cells whose BurnStatus is one of ``through``
+        (and where ``passable``, same forms, is not 0): one cell per move, ``connectivity`` 4 (the agents' moves) or 8.  A dict of
+        int32 arrays: ``reached`` [n] and ``levels`` [n]; with ``plane`` ``moves`` [n, H, W] (0 on targets, 2147483647 where no route
+        leaves, -1 on cells that are neither target nor walkable); with ``agents=True`` ``point_moves`` [n, k] for the device
+        positions of a ``BatchedFireEnv`` (every environment in order), or for a tensor [n, k, 3] = (column, row, id) of the
+        caller's, and with ``step`` ``point_step`` [n, k], the move code 1..4 of a shortest route's first move (0: stay).
+        ``max_moves`` caps the values.  ``device=True`` returns torch tensors on this GPU, else NumPy arrays; complete on return
+        either way (one wait).  One call, no host copy of the maps, no change to the simulation."""
+        points = None
+        if agents is True:
+            points = self._engine.agents_device()
+        elif agents is not False and agents is not None:
+            points = agents
+        r = self._engine.walk(target, through, envs=envs, connectivity=connectivity, passable=passable, targets=targets, points=points,
+                              max_moves=max_moves, plane=bool(plane), step=bool(step), reached=True, levels=True)
         self._engine.sync()
         return r if device else {k: v.cpu().numpy() for k, v in r.items()}
 

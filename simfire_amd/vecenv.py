@@ -52,10 +52,19 @@ class BatchedFireEnv:
     int32 [n_envs, n_agents], 1 where an agent stands in that set, and with ``value`` ``info["reach_value"]`` int64 [n_envs], the value
     plane summed over it - all from the state the observation shows.  Off by default: calls and ``info`` are what they are without it.
 
+    ``moves_to``: ``None``, or a dict with ``target``, ``through`` (BurnStatus members, names or ints; default BURNING / UNBURNED),
+    ``passable``, ``targets`` (uint8 CUDA [H, W] or [n_envs, H, W]) and ``max_moves``: ``info["moves_to"]`` is then int32
+    [n_envs, n_agents], the number of moves every agent needs to step onto a target cell through walkable cells
+    (``FireEngine.walk``), and ``info["move_toward"]`` int32 [n_envs, n_agents] the first move of a shortest
+    route as a move code 1..4 (0: stay) - an action word with ``interact = 0`` that can be fed straight back to ``step`` -, both from
+    the state the observation shows.  Agents are not routed around each other.  Off by default: calls and ``info`` are what they are
+    without it.
+
     Agents are not part of an environment's state: ``clone_envs`` / ``get_state`` / ``set_state`` do not carry them."""
 
     def __init__(self, sim, n_agents, start_xy, n_updates=1, weights=(-1, 0, 0, 0), only_unburned=True, done_on_burn=False,
-                 max_ticks=0, auto_reset=True, obs=None, values=None, value_weight=None, fire_distance=None, reach=None):
+                 max_ticks=0, auto_reset=True, obs=None, values=None, value_weight=None, fire_distance=None, reach=None,
+                 moves_to=None):
         self.sim = sim
         self.engine = sim._engine
         self.n_envs, self.n_agents = int(sim.n_envs), int(n_agents)
@@ -91,6 +100,18 @@ class BatchedFireEnv:
             sim._engine._reach_request(self.reach["source"], self.reach["through"], self.reach["connectivity"])      # (raises before anything is created)
             if self.reach["value"] and values is None and not self.engine.values_on:
                 raise ValueError("BatchedFireEnv: reach's value needs values (or a value plane set on the simulation)")
+        self.moves_to = None
+        if moves_to is not None:
+            if not isinstance(moves_to, dict) or set(moves_to) - {"target", "through", "passable", "targets", "max_moves"}:
+                raise ValueError("BatchedFireEnv: moves_to is None or a dict of target, through, passable, targets and max_moves")
+            self.moves_to = dict(target=moves_to.get("target", ("BURNING",)), through=moves_to.get("through", ("UNBURNED",)),
+                                 passable=moves_to.get("passable"), targets=moves_to.get("targets"), max_moves=moves_to.get("max_moves"))
+            from . import walk                                      # (raises before anything is created)
+            try:
+                walk.request(self.moves_to["target"], self.moves_to["through"], 4, self.moves_to["max_moves"],
+                             targets=self.moves_to["targets"] is not None)
+            except ValueError as err:
+                raise ValueError(f"BatchedFireEnv: moves_to: {err}") from None
         self.engine.agents_create(self.n_agents, sim.ignitions, n_updates=n_updates, weights=weights, only_unburned=only_unburned,
                                   done_on_burn=done_on_burn, max_ticks=max_ticks, auto_reset=auto_reset)
         self.values_on = values is not None
@@ -116,6 +137,9 @@ class BatchedFireEnv:
             info["reach_cells"], info["agent_exposed"] = r["count"], r["point_in"]
             if self.reach["value"]:
                 info["reach_value"] = r["value"]
+        if info is not None and self.moves_to is not None:
+            r = self.engine.walk(points=self.engine.agents_device(), connectivity=4, step=True, **self.moves_to)
+            info["moves_to"], info["move_toward"] = r["point_moves"], r["point_step"]
         self.engine.sync()
         return obs
 
