@@ -577,6 +577,60 @@ typedef struct sf_walk_out {             /* device pointers, any may be NULL, at
  * work on passable, targets, points and the outputs before the call. */
 int sf_walk(sf_sim *sim, const sf_walk_params *params, int32_t n, const int32_t *envs /* [n] host */, const sf_walk_out *out);
 
+/* Fire behaviour per cell: heat per unit area, head rate of spread, Byram's fireline intensity and flame
+ * length - the quantities of the fire characteristics chart - from the R table the handle holds NOW (it follows sf_set_wind, and a
+ * schedule segment once a stepping call has applied it).  The reference computes I_R on its way to R (rothermel.py:74-92) and keeps
+ * none of this; units are its own: feet, minutes, pounds, BTU.
+ * For a listed environment e, its terrain table and cell c, with the handle's particle parameters:
+ *   I_R(c): the float32 value of rothermel.py:92 as the R tables' chain rounds it (0 where w_0 <= 0);
+ *   HPA(c) = I_R * (384 / sigma) BTU/ft2 (Anderson's residence time), in float64 from the float32 I_R and sigma, rounded once;
+ *   R_head(c) = max_k rt[k][c]; head(c) = the lowest k that attains it, in the order of the table's planes (the fire travels from
+ *   c + that plane's source offset into c), -1 where all eight entries are 0;
+ *   I_B(c) = HPA * R_head / 60 BTU/ft/s; L(c) = 0.45 * I_B ** 0.46 ft (Byram 1959) - both in float64, rounded once, 0 where I_B == 0
+ *   (and where rounding made it negative: eta_M at M_f >= M_x).
+ * s(c) is the status byte & 7, read from whichever cell plane is current.
+ * Planes, dense [n][height][width]: hpa, ros (R_head), intensity (I_B), flame_length (L) float32, head int8.  With status_mask != 0
+ * (bit s = BurnStatus s) a cell whose status the mask does not select shows 0 (head: -1).  workable uint8: 1 where the flame_length
+ * plane's value (asked for or not; 0 on a cell status_mask hides) is <= flame_limit, else 0 - the form sf_walk and sf_reach take as
+ * passable.
+ * Summary over the cells summary_mask selects: max_flame, max_intensity float32 [n] (0 when none is selected) and classes int32 [n][5]:
+ * the selected cells with L in [0, e0) [e0, e1) [e1, e2) [e2, e3) [e3, inf), compared as float32.
+ * Point form, points device int32 [n][k][3] = (column, row, id), sf_agents_device's layout: point_flame[i][j] is the largest L over the
+ * cells of the 3 x 3 block around the point that are on the grid and selected by summary_mask, 0 if there are none; id <= 0 or a
+ * cell off the grid gives -1. */
+typedef struct sf_behavior_params {
+    int32_t status_mask;                 /* 0: every cell, or 1..63 */
+    int32_t summary_mask;                /* 1..63 */
+    int32_t k;                           /* 0, or 1..SF_DIST_MAX_POINTS points per listed environment */
+    int32_t reserved;                    /* 0 */
+    float flame_limit;                   /* >= 0 (workable) */
+    float edges[4];                      /* e0 < e1 < e2 < e3 (classes) */
+    const int32_t *points;               /* device int32 [n][k][3]; NULL with k == 0 */
+} sf_behavior_params;
+typedef struct sf_behavior_out {         /* device pointers, any may be NULL, at least one not */
+    float *hpa, *ros, *intensity, *flame_length;      /* [n][H][W] dense */
+    int8_t *head;                        /* [n][H][W] */
+    uint8_t *workable;                   /* [n][H][W] */
+    float *max_flame, *max_intensity;    /* [n] */
+    int32_t *classes;                    /* [n][5] */
+    float *point_flame;                  /* [n][k] */
+} sf_behavior_out;
+/* Environment envs[i] (a host array; any order, repeats allowed) lands in row i of every output.  Anything invalid is SF_EINVAL before
+ * anything is enqueued (a null argument, every output null, status_mask outside 0..63 or summary_mask outside 1..63, reserved != 0,
+ * edges that do not increase or are NaN, flame_limit < 0 or NaN, k outside 0..256, k > 0 without points or points with k == 0,
+ * point_flame without k or k without point_flame, a float32 or int32 output that is not aligned to 4 bytes, an environment out of
+ * range); a handle without layers or reset is SF_ESTATE, and so is a listed environment whose table came from sf_set_rtable* and has
+ * no layers to take I_R from.
+ * HPA does not depend on the wind or the fire, so it is kept in a cache, float32 [tables][height * width]: allocated at the first call
+ * (4 bytes per cell and table, counted by sf_memory_bytes, freed by sf_destroy), built by k_behavior_hpa - the only transcendentals of
+ * the feature - for the listed tables that are stale: every table at first, then whatever sf_set_layers*, sf_generate_layers,
+ * sf_set_rtable* or sf_copy_envs with SF_COPY_TERRAIN (the destination) has touched since; not sf_set_wind.  Then ONE launch of
+ * k_behavior for the whole list.  The call reads the state and writes nothing but its outputs and its cache - not the current plane,
+ * the tile books, the reference point of sf_get_fire_map_delta, the result block, any ring, the arrival or value planes.
+ * In async mode the call only enqueues (the outputs are complete when the handle's stream has got there); the caller orders its own
+ * work on points and the outputs before the call. */
+int sf_behavior(sf_sim *sim, const sf_behavior_params *params, const sf_behavior_out *out, const int32_t *envs /* [n] host */, int32_t n);
+
 /* Agents on the device: K agents per environment that walk the grid and draw control lines where they stand,
  * stepped from a policy's action tensor without a host read.  The reference records agent positions only (simulation.py:480-499) and
  * leaves the loop to the harness (the run docstring, 505-509); the semantics are this library's own.

@@ -147,6 +147,9 @@ int sf_get_value_passes(sf_sim *sim, int64_t *out /* [2] */);
  * sf_get_wind_ms: the GPU milliseconds of the last one (SF_ESTATE before one was timed).  profiles/wind_probe.py measures with them. */
 int sf_set_wind_lab(sf_sim *sim, int32_t cache_on, int32_t timed);
 int sf_get_wind_ms(sf_sim *sim, float *ms_out);
+/* Fire behaviour (sf_behavior): how many tables' parts of the heat cache k_behavior_hpa has built since the handle
+ * was created (tests assert with it that a wind change rebuilds none, a change of the layers exactly its own).  No reference counterpart. */
+int sf_get_behavior_builds(sf_sim *sim, int64_t *n_out);
 /* 1 = visit every tile every step instead of consulting the tile activity map (cross-check) */
 int sf_set_dense(sf_sim *sim, int32_t dense);
 /* sf_cfd_step that also reports the GPU time of its launches (HIP events on the handle's stream). */

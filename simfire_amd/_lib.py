@@ -146,6 +146,19 @@ class SfWalkOut(C.Structure):
                 ("levels", C.c_void_p)]
 
 
+class SfBehaviorParams(C.Structure):
+    """``sf_behavior_params`` (include/simfire_hip.h)."""
+    _fields_ = [("status_mask", C.c_int32), ("summary_mask", C.c_int32), ("k", C.c_int32), ("reserved", C.c_int32),
+                ("flame_limit", C.c_float), ("edges", C.c_float * 4), ("points", C.c_void_p)]
+
+
+class SfBehaviorOut(C.Structure):
+    """``sf_behavior_out`` (include/simfire_hip.h): device pointers, any may be null, not all."""
+    _fields_ = [("hpa", C.c_void_p), ("ros", C.c_void_p), ("intensity", C.c_void_p), ("flame_length", C.c_void_p), ("head", C.c_void_p),
+                ("workable", C.c_void_p), ("max_flame", C.c_void_p), ("max_intensity", C.c_void_p), ("classes", C.c_void_p),
+                ("point_flame", C.c_void_p)]
+
+
 # name -> argtypes; every function returns int except the two string getters
 _VP, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
 SIGNATURES = {
@@ -216,6 +229,8 @@ SIGNATURES = {
     "sf_distance": [_VP, C.POINTER(SfDistParams), _I32, _VP, _VP],
     "sf_reach": [_VP, C.POINTER(SfReachParams), _I32, _VP, C.POINTER(SfReachOut)],
     "sf_walk": [_VP, C.POINTER(SfWalkParams), _I32, _VP, C.POINTER(SfWalkOut)],
+    "sf_behavior": [_VP, C.POINTER(SfBehaviorParams), C.POINTER(SfBehaviorOut), _VP, _I32],
+    "sf_get_behavior_builds": [_VP, C.POINTER(_I64)],
     "sf_cell_layout": [_VP, C.POINTER(_I32)],
     "sf_render": [_VP, C.POINTER(SfRenderParams), _I32, _VP, _VP],
     "sf_status_device": [_VP, C.POINTER(_VP)],

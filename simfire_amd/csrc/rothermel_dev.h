@@ -27,6 +27,7 @@ __device__ __forceinline__ float cs(float x) { return (float)cos((double)x); }
 struct CellTerms {
     bool burnable;
     float IRxi;    // I_R * xi                 (rothermel.py:92,94,128)
+    float I_R;     // reaction intensity       (rothermel.py:92; sf_behavior)
     float den;     // p_b * eps * Q_ig         (rothermel.py:128)
     float c, b;    // wind coefficients        (rothermel.py:96-97)
     float ratio_e; // (B/B_op) ** -e           (rothermel.py:98,111)
@@ -43,7 +44,7 @@ __device__ inline CellTerms cell_terms(float w_0, float delta, float M_x, float 
     t.burnable = w_0 > 0.0f;                                               // :54
     t.U = U; t.slope_mag = slope_mag; t.slope_dir = slope_dir;
     if (!t.burnable) {
-        t.IRxi = 0.f; t.den = 1.f; t.c = 0.f; t.b = 1.f; t.ratio_e = 0.f; t.Bs = 0.f; t.omega = 0.f;
+        t.IRxi = 0.f; t.I_R = 0.f; t.den = 1.f; t.c = 0.f; t.b = 1.f; t.ratio_e = 0.f; t.Bs = 0.f; t.omega = 0.f;
         return t;
     }
     float eta_S = fminf(0.174f * pw(S_e, -0.19f), 1.0f);                    // :74
@@ -67,6 +68,7 @@ __device__ inline CellTerms cell_terms(float w_0, float delta, float M_x, float 
     t.Bs = 5.275f * pw(B, -0.3f);
     float eps = ex(-138.0f / sigma);                                        // :121
     float Q_ig = 250.0f + 1116.0f * M_f;                                    // :123
+    t.I_R = I_R;
     t.IRxi = I_R * xi;
     t.den = (p_b * eps) * Q_ig;
     t.omega = (90.0f - U_dir) * 0.017453292519943295f;                      // :104 np.radians (f32)

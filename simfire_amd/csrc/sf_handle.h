@@ -274,6 +274,16 @@ struct WalkState {
     hipError_t release() { cap = 0; return free_dev(mem); }
 };
 
+// sf_behavior: the heat cache, float [tables][H * W] (per table whether its part is stale: TableBook) -
+// allocated at the first call, freed with the handle -, the parts built so far (the lab's count) and the call block (the
+// environment list of a call)
+struct BehaviorState {
+    float *hpa = nullptr;
+    int64_t builds = 0;
+    CallBlock blk;
+    hipError_t release() { return free_dev(hpa); }
+};
+
 }  // namespace
 
 // ----------------------------------------------------------------------------- handle
@@ -374,6 +384,7 @@ struct sf_sim {
     DistState dist;
     ReachState reach;
     WalkState walk;
+    BehaviorState behavior;
     CallBlock obs_blk;                 // sf_observe: ObsHead, environment list, host centers / agents
     CallBlock rs_blk;                  // sf_reset_envs / sf_reset_where: the environment list and host ignitions of a call
     LabTimer reset_timer;              // sf_time_resets: ev0 / ev1 recorded around the launches of every batched reset

@@ -4,7 +4,7 @@ This is the only module that touches the HIP library; the reference-shaped class
 ``fire.py`` / ``simulation.py`` are written on top of it.  Arrays cross the boundary as
 NumPy host arrays (copied during the call) or as torch CUDA tensors, read and written in place; torch is imported only by the
 methods that take or return one.  Layout (binding map): argument checks in ``_args.py``, one request class per feature
-(``observe.py``, ``render.py``, ``distance.py``, ``reach.py``, ``ensemble.py``), and one frame, ``_device_call``, for every call
+(``observe.py``, ``render.py``, ``distance.py``, ``reach.py``, ``walk.py``, ``behavior.py``, ``ensemble.py``), and one frame, ``_device_call``, for every call
 that hands the library a tensor.
 """
 import ctypes as C
@@ -944,6 +944,36 @@ class FireEngine:
             p, o = spec.params(), spec.out(res)
             self._device_call(self._L.sf_walk, C.byref(p), spec.n, _ptr(spec.envs), C.byref(o), tensors=list(res.values()) + spec.device_tensors())
         return res
+
+    # ---------------------------------------------------------------- fire behaviour
+    def behavior(self, envs=None, status=None, summary=("BURNING",), flame_limit=None, edges=None, points=None,
+                 planes=("flame_length",), workable=False, stats=False):
+        """Fireline intensity and flame length per cell of ``envs`` (default: all, in order; any order, repeats allowed) from the R
+        table the handle holds now (``sf_behavior``).  Units are the reference's: feet, minutes, pounds, BTU.
+        Returns a dict of torch tensors on this GPU, one per output asked for.  ``planes``: any of ``hpa`` (heat per unit area,
+        BTU/ft2), ``ros`` (the head rate of spread, ft/min), ``intensity`` (Byram's, BTU/ft/s), ``flame_length`` (ft), float32
+        [n, H, W], and ``head`` int8 [n, H, W]: the index into ``SRC_OFFSETS`` of the neighbour the head fire arrives from, -1 where
+        nothing spreads; with ``status`` (a mask, or BurnStatus members, names or ints) the cells it does not select show 0 / -1.
+        ``workable`` (needs ``flame_limit``): uint8 [n, H, W], 1 where the flame-length plane is <= ``flame_limit`` - what ``walk``
+        and ``reach`` take as ``passable``.  ``stats``: over the cells ``summary`` selects ``max_flame`` and ``max_intensity``
+        float32 [n] and ``classes`` int32 [n, 5], the cells with a flame length in [0, e0) [e0, e1) [e1, e2) [e2, e3) [e3, inf) for
+        ``edges`` (default 4, 8, 11, 1e30 ft).  ``points`` - int32 CUDA [n, k, 3] = (column, row, id), k <= 256, e.g.
+        ``agents_device()`` - gives ``point_flame`` float32 [n, k]: the largest flame length among the cells of the 3 x 3 block
+        around the point that ``summary`` selects (0: none; -1 for id <= 0 or off the grid).  No state of the handle changes.
+        Torch's queued work is waited for first; in async mode the call only enqueues: the tensors are complete after ``sync()``
+        and kept alive until then."""
+        from .behavior import BehaviorSpec
+        spec = BehaviorSpec(self.n_envs, self.H, self.W, envs=envs, status=status, summary=summary, flame_limit=flame_limit, edges=edges,
+                            points=points, planes=planes, workable=workable, stats=stats)
+        res = self._outputs("behavior", spec)
+        if spec.n:
+            p, o = spec.params(), spec.out(res)
+            self._device_call(self._L.sf_behavior, C.byref(p), C.byref(o), _ptr(spec.envs), spec.n, tensors=list(res.values()) + spec.device_tensors())
+        return res
+
+    def behavior_builds(self):
+        """Measurement / tests: how many tables' parts of the heat cache ``behavior`` has built so far (``sf_get_behavior_builds``)."""
+        return self._get(self._L.sf_get_behavior_builds, C.c_int64)
 
     def render(self, envs=None, scale=1, mode=None, background="fuel", contours=True, terrain_rgb=None, agents=None, channels_last=True,
                history=None, out=None):

@@ -619,6 +619,18 @@ class FireSimulation:
         self._engine.sync()
         return r["moves"][0].cpu().numpy()
 
+    def fire_behavior(self, status=None, flame_limit=None, planes=("flame_length",)):
+        """Fire behaviour per cell from the rates of spread as they stand: a dict of NumPy [H, W] planes, any of ``hpa`` (heat per
+        unit area, BTU/ft2), ``ros`` (head rate of spread, ft/min), ``intensity`` (Byram's fireline intensity, BTU/ft/s),
+        ``flame_length`` (ft) and ``head`` (int8: the index into ``SRC_OFFSETS`` of the neighbour the head fire comes from, -1 where
+        nothing spreads); with ``status`` the cells it does not select show 0 / -1; with ``flame_limit`` also ``workable`` (uint8: 1
+        where the flame length is <= ``flame_limit``).  Host edits of ``fire_map`` are pushed to the device first, as ``moves_to``
+        does (``BatchedFireSimulation.fire_behavior``)."""
+        self._sync_to_device()
+        r = self._engine.behavior(envs=[0], status=status, flame_limit=flame_limit, planes=planes, workable=flame_limit is not None)
+        self._engine.sync()
+        return {k: v[0].cpu().numpy() for k, v in r.items()}
+
     # -------------------------------------------------------------------- seeds / layers
     def get_seeds(self) -> Dict[str, Optional[int]]:
         """simulation.py:574-597: only the seeds that exist for the configured generators."""
@@ -1382,6 +1394,29 @@ class BatchedFireSimulation:
             points = agents
         r = self._engine.walk(target, through, envs=envs, connectivity=connectivity, passable=passable, targets=targets, points=points,
                               max_moves=max_moves, plane=bool(plane), step=bool(step), reached=True, levels=True)
+        self._engine.sync()
+        return r if device else {k: v.cpu().numpy() for k, v in r.items()}
+
+    def fire_behavior(self, envs=None, status=None, summary=("BURNING",), flame_limit=None, edges=None, agents=False,
+                      planes=("flame_length",), device=True):
+        """How hot the fire is in ``envs`` (default: all): Rothermel's heat per unit area and head rate of spread, Byram's fireline
+        intensity and flame length per cell, from the rate-of-spread tables as they stand (after ``set_wind`` too).  A dict:
+        the ``planes`` asked for - any of ``hpa`` (BTU/ft2), ``ros`` (ft/min), ``intensity`` (BTU/ft/s), ``flame_length`` (ft),
+        float32 [n, H, W], and ``head`` int8 (index into ``SRC_OFFSETS``, -1: nothing spreads), 0 / -1 on cells ``status`` does not
+        select -; with ``flame_limit`` ``workable`` uint8 [n, H, W], 1 where the flame length is <= ``flame_limit``, which
+        ``moves_to`` and ``reach`` take as ``passable`` with no host copy; always ``max_flame`` / ``max_intensity`` float32 [n]
+        and ``classes`` int32 [n, 5] over the cells ``summary`` selects (``edges``: default 4, 8, 11, 1e30 ft); with ``agents=True``
+        ``point_flame`` float32 [n, k] for the device positions of a ``BatchedFireEnv`` (every environment in order), or for a
+        tensor [n, k, 3] = (column, row, id) of the caller's: the largest flame length among the ``summary`` cells of the 3 x 3
+        block around each.  ``device=True`` returns torch tensors on this GPU, else NumPy arrays; complete on return either way
+        (one wait).  One call, no host copy of tables or maps, no change to the simulation."""
+        points = None
+        if agents is True:
+            points = self._engine.agents_device()
+        elif agents is not False and agents is not None:
+            points = agents
+        r = self._engine.behavior(envs=envs, status=status, summary=summary, flame_limit=flame_limit, edges=edges, points=points,
+                                  planes=planes, workable=flame_limit is not None, stats=True)
         self._engine.sync()
         return r if device else {k: v.cpu().numpy() for k, v in r.items()}
 

@@ -60,11 +60,17 @@ class BatchedFireEnv:
     the state the observation shows.  Agents are not routed around each other.  Off by default: calls and ``info`` are what they are
     without it.
 
+    ``behavior``: ``None``, or a dict with ``summary`` (BurnStatus members, names or ints; default BURNING), ``edges`` and
+    ``flame_limit`` (checked, but a tick writes no plane): ``info["flame_length"]`` is then float32 [n_envs, n_agents], the largest flame length (ft)
+    among the ``summary`` cells of the 3 x 3 block around every agent (0: none), and ``info["max_flame"]`` float32 [n_envs] the
+    largest over the environment (``FireEngine.behavior``), both from the state the observation shows.  Off by
+    default: calls and ``info`` are what they are without it.
+
     Agents are not part of an environment's state: ``clone_envs`` / ``get_state`` / ``set_state`` do not carry them."""
 
     def __init__(self, sim, n_agents, start_xy, n_updates=1, weights=(-1, 0, 0, 0), only_unburned=True, done_on_burn=False,
                  max_ticks=0, auto_reset=True, obs=None, values=None, value_weight=None, fire_distance=None, reach=None,
-                 moves_to=None):
+                 moves_to=None, behavior=None):
         self.sim = sim
         self.engine = sim._engine
         self.n_envs, self.n_agents = int(sim.n_envs), int(n_agents)
@@ -112,6 +118,16 @@ class BatchedFireEnv:
                              targets=self.moves_to["targets"] is not None)
             except ValueError as err:
                 raise ValueError(f"BatchedFireEnv: moves_to: {err}") from None
+        self.behavior = None
+        if behavior is not None:
+            if not isinstance(behavior, dict) or set(behavior) - {"flame_limit", "edges", "summary"}:
+                raise ValueError("BatchedFireEnv: behavior is None or a dict of flame_limit, edges and summary")
+            self.behavior = dict(edges=behavior.get("edges"), summary=behavior.get("summary", ("BURNING",)))
+            from . import behavior as _behavior                     # (raises before anything is created)
+            try:
+                _behavior.request(None, self.behavior["summary"], behavior.get("flame_limit"), self.behavior["edges"])
+            except ValueError as err:
+                raise ValueError(f"BatchedFireEnv: {err}") from None
         self.engine.agents_create(self.n_agents, sim.ignitions, n_updates=n_updates, weights=weights, only_unburned=only_unburned,
                                   done_on_burn=done_on_burn, max_ticks=max_ticks, auto_reset=auto_reset)
         self.values_on = values is not None
@@ -140,6 +156,9 @@ class BatchedFireEnv:
         if info is not None and self.moves_to is not None:
             r = self.engine.walk(points=self.engine.agents_device(), connectivity=4, step=True, **self.moves_to)
             info["moves_to"], info["move_toward"] = r["point_moves"], r["point_step"]
+        if info is not None and self.behavior is not None:
+            r = self.engine.behavior(points=self.engine.agents_device(), planes=(), stats=True, **self.behavior)
+            info["flame_length"], info["max_flame"] = r["point_flame"], r["max_flame"]
         self.engine.sync()
         return obs
 
