@@ -1,5 +1,5 @@
-"""Argument checks shared by the binding (``engine.py``) and the request classes (``observe.py``, ``render.py``, ``distance.py``,
-``reach.py``, ``ensemble.py``).
+"""Argument checks shared by the binding (``engine.py``) and the request classes (``observe.py``, ``render.py``, ``ensemble.py``
+and the four queries ``distance.py``, ``reach.py``, ``walk.py``, ``behavior.py``).
 
 Pure Python on NumPy; torch is imported inside the functions that are handed a tensor.  Every check raises before a device call,
 so a bad request fails the same way with or without a GPU.  ``who`` names the caller in the message (``"reach"`` gives
@@ -148,3 +148,34 @@ def points(x, n, last, name, host=True, k_range=None):
     if k_range is not None and not k_range[0] <= x.shape[1] <= k_range[1]:
         raise ValueError(f"{name}: at least {k_range[0]} and at most {k_range[1]} entries per environment, got {x.shape[1]}")
     return x, dev
+
+
+def query_points(who, x, n):
+    """The points of a query (``distance``, ``reach``, ``walk``, ``behavior``): ``None``, or a CUDA int32 tensor [n, k, 3] =
+    (column, row, id) with k in 1..SF_DIST_MAX_POINTS -> (contiguous tensor or ``None``, k)."""
+    from ._lib import SF_DIST_MAX_POINTS
+    if x is None:
+        return None, 0
+    x = points(x, n, 3, f"{who}: points", host=False, k_range=(1, SF_DIST_MAX_POINTS))[0]
+    return x, int(x.shape[1])
+
+
+def flags(who, **want):
+    """Every keyword is ``True`` or ``False`` (a bool, not something truthy), or ``ValueError``."""
+    for name, flag in want.items():
+        if not isinstance(flag, (bool, np.bool_)):
+            raise ValueError(f"{who}: {name} must be True or False, got {flag!r}")
+
+
+def dense_plane(who, name, t, n_envs, H, W):
+    """A uint8 plane of a query: ``None``, or a CUDA tensor [H, W] (one for every environment) or [n_envs, H, W] -> (contiguous
+    tensor or ``None``, 1 if it is per environment else 0)."""
+    if t is None:
+        return None, 0
+    return cuda_tensor(t, f"{who}: {name}", ("uint8",), [(H, W), (n_envs, H, W)]).contiguous(), int(t.dim() == 3)
+
+
+def band_count(H, W):
+    """Bands of 16 rows x 64 columns on an ``H`` x ``W`` grid (rows of pitch roundup(W, 16)): what the scratch of ``reach`` and
+    ``walk`` is counted in."""
+    return ((H + 15) // 16) * (((W + 15) // 16 * 16 + 63) // 64)

@@ -9,7 +9,7 @@ import math
 import numpy as np
 
 from . import _args
-from ._lib import SF_DIST_MAX_POINTS, SfBehaviorOut, SfBehaviorParams
+from ._lib import SfBehaviorOut, SfBehaviorParams
 
 #: the planes a call can write: name -> the torch dtype's name
 PLANES = {"hpa": "float32", "ros": "float32", "intensity": "float32", "flame_length": "float32", "head": "int8"}
@@ -62,15 +62,10 @@ class BehaviorSpec:
         for name in planes:
             if name not in PLANES:
                 raise ValueError(f"behavior: unknown plane {name!r} (one of {', '.join(PLANES)})")
-        for name, flag in dict(workable=workable, stats=stats).items():
-            if not isinstance(flag, (bool, np.bool_)):
-                raise ValueError(f"behavior: {name} must be True or False, got {flag!r}")
+        _args.flags("behavior", workable=workable, stats=stats)
         if workable and self.flame_limit is None:
             raise ValueError("behavior: workable needs flame_limit")
-        self.points, self.k = None, 0
-        if points is not None:
-            self.points = _args.points(points, n, 3, "behavior: points", host=False, k_range=(1, SF_DIST_MAX_POINTS))[0]
-            self.k = int(self.points.shape[1])
+        self.points, self.k = _args.query_points("behavior", points, n)
         if not (planes or workable or stats or self.k):
             raise ValueError("behavior: nothing asked for (planes, workable, stats or points)")
         shapes = {name: ((n, H, W), PLANES[name]) for name in PLANES}

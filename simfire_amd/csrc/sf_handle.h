@@ -244,30 +244,12 @@ struct EpisodeState {
     }
 };
 
-// sf_distance: the scratch plane g (u16 [chunk][H][P], the vertical distances of the environments a call is
-// working on) - allocated at the first call, grown but never shrunk when a call's chunk needs more, freed with the handle - its size
-// in bytes, and the call block (the environment list of a call)
-struct DistState {
-    uint16_t *plane = nullptr;
-    size_t cap = 0;
-    CallBlock blk;
-    hipError_t release() { cap = 0; return free_dev(plane); }
-};
-
-// sf_reach: the scratch of the fill (per listed environment of a chunk: two bit planes and the halo,
-// reach_env_bytes) - allocated at the first call, grown but never shrunk, freed with the handle - its size in bytes, and the call
-// block (the environment list of a call)
-struct ReachState {
-    uint8_t *mem = nullptr;
-    size_t cap = 0;
-    CallBlock blk;
-    hipError_t release() { cap = 0; return free_dev(mem); }
-};
-
-// sf_walk: the scratch of the search (per listed environment of a chunk: three bit planes and two halos,
-// walk_env_bytes) - allocated at the first call, grown but never shrunk, freed with the handle - its size in bytes, and the call
-// block (the environment list of a call)
-struct WalkState {
+// A query with scratch (sf_host_query.h; DESIGN.md section 22, "host frame of a query"): the scratch of the environments a call is
+// working on - allocated at the first call, grown but never shrunk when a call's chunk needs more (scratch_reserve), freed with the
+// handle -, its size in bytes, and the call block (the environment list of a call).  What lies in it, per listed environment of a
+// chunk: sf_distance the plane g, u16 [H][P]; sf_reach two bit planes and the halo (reach_env_bytes); sf_walk three bit planes and
+// two halos (walk_env_bytes).
+struct QueryState {
     uint8_t *mem = nullptr;
     size_t cap = 0;
     CallBlock blk;
@@ -381,9 +363,7 @@ struct sf_sim {
     WindState wind;
     AgentState agents;
     EpisodeState episodes;
-    DistState dist;
-    ReachState reach;
-    WalkState walk;
+    QueryState dist, reach, walk;      // one block and one scratch per feature (as for CallBlock: calls of different features do not wait for each other)
     BehaviorState behavior;
     CallBlock obs_blk;                 // sf_observe: ObsHead, environment list, host centers / agents
     CallBlock rs_blk;                  // sf_reset_envs / sf_reset_where: the environment list and host ignitions of a call
@@ -514,6 +494,31 @@ static int block_send(sf_sim *s, CallBlock &b, size_t head, size_t off = 0, size
     HIPCHK(hipMemcpyAsync(b.dev, b.pinned, head, hipMemcpyHostToDevice, s->stream));
     if (more) HIPCHK(hipMemcpyAsync(b.dev + off, b.pinned + off, more, hipMemcpyHostToDevice, s->stream));
     HIPCHK(hipEventRecord(b.ev, s->stream));
+    return SF_OK;
+}
+// A whole block of up to two host segments (an environment list and what travels with it): the `na` bytes at `a` and, right behind
+// them, the `nc` bytes at `c` - room reserved, copied into the mirror, sent.  *dev: where `a` stands on the device (`c`: na bytes on).
+template <typename T>
+static int block_stage(sf_sim *s, CallBlock &b, const T **dev, const T *a, size_t na, const void *c = nullptr, size_t nc = 0)
+{
+    SF_TRY(block_reserve(s, b, na + nc));
+    if (na) memcpy(b.pinned, a, na);
+    if (nc) memcpy(b.pinned + na, c, nc);
+    *dev = reinterpret_cast<const T *>(b.dev);
+    return block_send(s, b, na + nc);
+}
+
+// Room for `bytes` in a query's scratch: grown, never shrunk.  Growing waits for the stream first (enqueued kernels may still use
+// the scratch) and is counted in the handle's `bytes`.
+static int scratch_reserve(sf_sim *s, QueryState &q, size_t bytes)
+{
+    if (bytes <= q.cap) return SF_OK;
+    HIPCHK(hipStreamSynchronize(s->stream));
+    s->bytes -= (int64_t)q.cap;
+    HIPCHK(q.release());
+    HIPCHK(hipMalloc(reinterpret_cast<void **>(&q.mem), bytes));
+    q.cap = bytes;
+    s->bytes += (int64_t)q.cap;
     return SF_OK;
 }
 

@@ -1,0 +1,381 @@
+// Host code of the queries: sf_distance, sf_reach (23), sf_walk (24) and sf_behavior (25).  Each takes a list
+// of environments, optional points and caller-owned device outputs, reads the state and changes none of it.  Included once from
+// simfire_hip.hip, behind sf_host_views.h.
+//
+// The host frame of a query, in this order: null and argument refusals (SF_EINVAL), the environment list, the grid's width
+// (SF_ENOTSUP), check_ready (SF_ESTATE), the feature's own SF_ESTATE, begin_call; a list of none ends there.  Then the scratch of as
+// many environments as the budget holds (query_chunk, scratch_reserve), the list through the feature's call block, and the launches
+// chunk by chunk.  All of it on the handle's stream, so a chunk's launches follow the chunk before it; a refused call has enqueued
+// nothing.
+#pragma once
+
+// ----------------------------------------------------------------------------- what the queries share
+// k and points.  `stray`: points given with k == 0 are refused too (sf_walk and sf_behavior; sf_distance and sf_reach ignore them).
+static int check_points(const char *who, int k, const void *points, bool stray)
+{
+    if (k < 0 || k > SF_DIST_MAX_POINTS) return fail(SF_EINVAL, "%s: %d points per environment (0..%d)", who, k, SF_DIST_MAX_POINTS);
+    if (k > 0 && !points) return fail(SF_EINVAL, "%s: k = %d needs points", who, k);
+    if (stray && k == 0 && points) return fail(SF_EINVAL, "%s: points need k > 0", who);
+    return SF_OK;
+}
+static int check_reserved(const char *who, int reserved)
+{
+    return reserved ? fail(SF_EINVAL, "%s: reserved must be 0", who) : SF_OK;
+}
+// low_bits: the low address bits of every output or'ed, masked by the element's alignment
+static int check_aligned(const char *who, uintptr_t low_bits)
+{
+    return low_bits ? fail(SF_EINVAL, "%s: an output is not aligned to its element", who) : SF_OK;
+}
+// a budget of the caller's holds one environment's scratch (`what` names it: "plane", "need")
+static int check_scratch(const char *who, int64_t scratch_bytes, size_t need, const char *what)
+{
+    if (scratch_bytes < 0 || (scratch_bytes > 0 && (size_t)scratch_bytes < need))
+        return fail(SF_EINVAL, "%s: scratch_bytes %lld is less than one environment's %s (%zu bytes)", who, (long long)scratch_bytes, what, need);
+    return SF_OK;
+}
+
+// A status mask as the table of one byte permute: byte s of (hi : lo) = 1 if the mask selects BurnStatus s
+static void mask_tables(int mask, uint32_t &lo, uint32_t &hi)
+{
+    lo = hi = 0;
+    for (int st = 0; st < 6; ++st)
+        if ((mask >> st) & 1) (st < 4 ? lo : hi) |= 1u << (8 * (st & 3));
+}
+
+// Environments per chunk of a list of n: as many as the budget holds of `need` bytes each, one at least, `cap` (the launch grid) at most
+static int query_chunk(int n, int64_t scratch_bytes, long long budget_default, size_t need, size_t cap)
+{
+    const size_t budget = scratch_bytes > 0 ? (size_t)scratch_bytes : (size_t)budget_default;
+    return (int)std::min<size_t>({(size_t)n, std::max<size_t>(budget / need, 1), cap});
+}
+
+// ----------------------------------------------------------------------------- distance fields
+// Per chunk the two column passes over the scratch plane g and k_dist_rows (plane form) or k_dist_points.
+extern "C" int sf_distance(sf_sim *s, const sf_dist_params *p, int32_t n, const int32_t *envs, void *device_out)
+{
+    const char *who = "sf_distance";
+    if (!s || !p) return fail(SF_EINVAL, "sf_distance: null argument");
+    const Geo &g = s->g;
+    if (n < 0 || (n > 0 && (!envs || !device_out))) return fail(SF_EINVAL, "sf_distance: bad environment list or output");
+    if (p->status_mask < 1 || p->status_mask > 63) return fail(SF_EINVAL, "sf_distance: status_mask %d (bit s selects BurnStatus s: 1..63)", p->status_mask);
+    if (p->max_d2 < 0) return fail(SF_EINVAL, "sf_distance: max_d2 %d (0: no cap)", p->max_d2);
+    if (p->dtype != SF_DIST_I32 && p->dtype != SF_DIST_F32) return fail(SF_EINVAL, "sf_distance: dtype %d (0 int32, 1 float32)", p->dtype);
+    SF_TRY(check_points(who, p->k, p->points, false));
+    if (!std::isfinite(p->scale) || !(p->scale > 0.0)) return fail(SF_EINVAL, "sf_distance: scale must be finite and > 0");
+    SF_TRY(check_reserved(who, p->reserved[0] | p->reserved[1]));
+    if ((uintptr_t)device_out & 3) return fail(SF_EINVAL, "sf_distance: the output is not aligned to its element");
+    const size_t plane = (size_t)g.plane_env * sizeof(uint16_t);          // one environment's g
+    SF_TRY(check_scratch(who, p->scratch_bytes, plane, "plane"));
+    SF_TRY(check_envs(s, who, n, envs));
+    if ((long long)(g.H - 1) * (g.H - 1) + (long long)(g.W - 1) * (g.W - 1) >= (long long)SF_DIST_FAR)
+        return fail(SF_ENOTSUP, "sf_distance: squared distances on a %d x %d grid do not fit int32", g.H, g.W);
+    if (g.W > kDistMaxWidth) return fail(SF_ENOTSUP, "sf_distance: grids wider than %d cells are not supported (width %d)", kDistMaxWidth, g.W);
+    SF_TRY(begin_call(s, who, kNeedRt | kNeedReset | kNotVoid));
+    if (n == 0) return SF_OK;
+
+    const int chunk = query_chunk(n, p->scratch_bytes, kDistScratchDefault, plane, 32768);      // (32768: the launch grid's y)
+    QueryState &d = s->dist;
+    SF_TRY(scratch_reserve(s, d, (size_t)chunk * plane));
+    const int32_t *envs_dev = nullptr;
+    SF_TRY(block_stage(s, d.blk, &envs_dev, envs, (size_t)n * sizeof(int32_t)));
+
+    DistArgs a;
+    memset(&a, 0, sizeof a);
+    a.g = g;
+    a.status = s->status;
+    a.cells = s->bl_cur ? s->cells : nullptr;
+    a.gp = reinterpret_cast<uint16_t *>(d.mem);
+    a.k = p->k;
+    mask_tables(p->status_mask, a.tlo, a.thi);
+    a.limit = p->max_d2 > 0 ? p->max_d2 : SF_DIST_FAR;
+    a.reach = g.W;
+    if (p->max_d2 > 0) {
+        a.reach = (int)std::sqrt((double)p->max_d2);
+        while ((long long)a.reach * a.reach < p->max_d2) a.reach++;
+        a.reach = std::min(a.reach, g.W);
+    }
+    a.f32 = p->dtype == SF_DIST_F32;
+    a.scale = p->scale;
+    a.vec = g.W % 4 == 0 && !((uintptr_t)device_out & 15);
+    a.rows = std::max(1, std::min({1024 / g.P, kDistMaxRows, g.H}));
+    const size_t per_env = (p->k ? (size_t)p->k : (size_t)g.H * g.W) * 4;      // output bytes per listed environment
+    for (int c0 = 0; c0 < n; c0 += chunk) {
+        a.cn = std::min(chunk, n - c0);
+        a.envs = envs_dev + c0;
+        a.out = static_cast<uint8_t *>(device_out) + (size_t)c0 * per_env;
+        a.points = p->k ? p->points + (size_t)c0 * p->k * 3 : nullptr;
+        const unsigned col_blocks = (unsigned)(((long long)a.cn * g.PV + kDistColsThreads - 1) / kDistColsThreads);
+        hipLaunchKernelGGL(k_dist_cols_down, dim3(col_blocks), dim3(kDistColsThreads), 0, s->stream, a);
+        hipLaunchKernelGGL(k_dist_cols_up, dim3(col_blocks), dim3(kDistColsThreads), 0, s->stream, a);
+        if (p->k)
+            hipLaunchKernelGGL(k_dist_points, dim3((unsigned)((p->k + kDistRowsThreads / 64 - 1) / (kDistRowsThreads / 64)), (unsigned)a.cn),
+                               dim3(kDistRowsThreads), 0, s->stream, a);
+        else
+            hipLaunchKernelGGL(k_dist_rows, dim3((unsigned)((g.H + a.rows - 1) / a.rows), (unsigned)a.cn), dim3(kDistRowsThreads),
+                               (size_t)a.rows * g.P * sizeof(int32_t), s->stream, a);
+    }
+    return finish_call(s, who, !s->async, nullptr);
+}
+
+// ----------------------------------------------------------------------------- band searches: sf_reach and sf_walk (DESIGN.md sections 23, 24)
+// What k_reach and k_walk read alike (WalkArgs begins with a ReachArgs): the state, the passable plane, the two masks (`seeds`: where
+// the search starts - sources, targets), the points' count and the band geometry.
+static void band_args(const sf_sim *s, ReachArgs &r, const uint8_t *passable, int per_env, int k, int seed_mask, int through_mask)
+{
+    const Geo &g = s->g;
+    r.g = g;
+    r.status = s->status;
+    r.cells = s->bl_cur ? s->cells : nullptr;
+    r.passable = passable;
+    r.pass_env = per_env ? (long long)g.H * g.W : 0;
+    r.pass_vec = passable && g.W % 16 == 0 && !((uintptr_t)passable & 15);
+    r.k = k;
+    mask_tables(seed_mask, r.slo, r.shi);
+    mask_tables(through_mask, r.tlo, r.thi);
+    r.WORDS = reach_words(g); r.BR = reach_band_rows(g); r.nb = r.BR * r.WORDS;
+}
+
+// The launches of a band search and the end of its call: one launch per chunk of as many environments as the budget holds (`need`
+// bytes of scratch each), one workgroup per listed environment.  The call block is the environment list | one Args per chunk (the
+// kernel takes its arguments from there): `a` with r - `a` itself or its first member - pointed at the chunk's environments and
+// points, and at(c0) having pointed the outputs at the part of the chunk that begins with list entry c0.
+// One band per thread where the grid allows it: the search's own planes stay in registers and LDS for all of it (k_resident, with
+// `lanes` threads rounded up to whole waves); else passes of kReachThreads bands over the scratch planes (k_passes).  Up to 156 KiB
+// of LDS at 1024 threads, one workgroup per CU (which 1024 threads are anyway).
+static_assert(kWalkThreads == kReachThreads, "band_search: one workgroup size for both searches");
+template <typename Args, typename At>
+static int band_search(sf_sim *s, const char *who, QueryState &q, int32_t n, const int32_t *envs, const int32_t *points, int64_t scratch_bytes,
+                       long long budget_default, size_t need, Args &a, ReachArgs &r, At at, void (*k_resident)(const Args *),
+                       void (*k_passes)(const Args *), int lanes, size_t (*lds_bytes)(int, bool))
+{
+    const int chunk = query_chunk(n, scratch_bytes, budget_default, need, 65535), chunks = (n + chunk - 1) / chunk;
+    SF_TRY(scratch_reserve(s, q, (size_t)chunk * need));
+    r.scratch = q.mem;
+    r.scratch_env = (long long)need;
+    const size_t o_args = ((size_t)n * sizeof(int32_t) + 15) / 16 * 16, bytes = o_args + (size_t)chunks * sizeof(Args);
+    SF_TRY(block_reserve(s, q.blk, bytes));
+    memcpy(q.blk.pinned, envs, (size_t)n * sizeof(int32_t));
+    for (int c = 0; c < chunks; ++c) {
+        const int c0 = c * chunk;
+        r.envs = reinterpret_cast<const int32_t *>(q.blk.dev) + c0;
+        r.points = r.k ? points + (size_t)c0 * r.k * 3 : nullptr;
+        at(c0);
+        memcpy(q.blk.pinned + o_args + (size_t)c * sizeof(Args), &a, sizeof a);
+    }
+    SF_TRY(block_send(s, q.blk, bytes));
+
+    const bool resident = r.nb <= kReachThreads;
+    const unsigned threads = resident ? (unsigned)((lanes + 63) / 64 * 64) : (unsigned)kReachThreads;
+    const size_t lds = lds_bytes((int)threads, resident);
+    const auto kernel = resident ? k_resident : k_passes;
+    HIPCHK(allow_lds(s, reinterpret_cast<const void *>(kernel), lds));
+    for (int c = 0; c < chunks; ++c) {
+        const Args *ap = reinterpret_cast<const Args *>(q.blk.dev + o_args) + c;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)std::min(chunk, n - c * chunk)), dim3(threads), lds, s->stream, ap);
+    }
+    return finish_call(s, who, !s->async, nullptr);
+}
+
+extern "C" int sf_reach(sf_sim *s, const sf_reach_params *p, int32_t n, const int32_t *envs, const sf_reach_out *out)
+{
+    const char *who = "sf_reach";
+    if (!s || !p || !out) return fail(SF_EINVAL, "sf_reach: null argument");
+    const Geo &g = s->g;
+    if (n < 0 || (n > 0 && !envs)) return fail(SF_EINVAL, "sf_reach: bad environment list");
+    if (p->source_mask < 1 || p->source_mask > 63) return fail(SF_EINVAL, "sf_reach: source_mask %d (bit s selects BurnStatus s: 1..63)", p->source_mask);
+    if (p->through_mask < 1 || p->through_mask > 63) return fail(SF_EINVAL, "sf_reach: through_mask %d (bit s selects BurnStatus s: 1..63)", p->through_mask);
+    if (p->source_mask & p->through_mask) return fail(SF_EINVAL, "sf_reach: source_mask %d and through_mask %d overlap", p->source_mask, p->through_mask);
+    if (p->connectivity != 0 && p->connectivity != 4 && p->connectivity != 8)
+        return fail(SF_EINVAL, "sf_reach: connectivity %d (0: the handle's diagonal_spread, 4, 8)", p->connectivity);
+    SF_TRY(check_points(who, p->k, p->points, false));
+    if (out->point_in && p->k == 0) return fail(SF_EINVAL, "sf_reach: point_in needs k > 0");
+    if (p->max_rounds < 0) return fail(SF_EINVAL, "sf_reach: max_rounds %d (0: to the fixed point)", p->max_rounds);
+    SF_TRY(check_reserved(who, p->reserved[0] | p->reserved[1]));
+    if (!out->count && !out->value && !out->mask && !out->seeds && !out->point_in && !out->rounds)
+        return fail(SF_EINVAL, "sf_reach: every output is null");
+    SF_TRY(check_aligned(who, (((uintptr_t)out->count | (uintptr_t)out->seeds | (uintptr_t)out->point_in | (uintptr_t)out->rounds) & 3) | ((uintptr_t)out->value & 7)));
+    const size_t need = (size_t)reach_env_bytes(g);
+    SF_TRY(check_scratch(who, p->scratch_bytes, need, "need"));
+    SF_TRY(check_envs(s, who, n, envs));
+    if (g.W > kReachMaxWidth) return fail(SF_ENOTSUP, "sf_reach: grids wider than %d cells are not supported (width %d)", kReachMaxWidth, g.W);
+    SF_TRY(check_ready(s, who, kNeedRt | kNeedReset));
+    if (out->value && !s->values.plane) return fail(SF_ESTATE, "sf_reach: value needs a value plane (sf_values_set)");
+    SF_TRY(begin_call(s, who, kNeedRt | kNeedReset | kNotVoid));
+    if (n == 0) return SF_OK;
+
+    ReachArgs a;
+    memset(&a, 0, sizeof a);
+    band_args(s, a, p->passable, p->passable_per_env, p->k, p->source_mask, p->through_mask);
+    a.vals = out->value ? s->values.plane : nullptr;
+    a.val_env = s->values.per_env ? g.plane_env : 0;
+    a.conn8 = p->connectivity == 0 ? g.diag : (p->connectivity == 8);
+    a.max_rounds = p->max_rounds;
+    a.mask_vec = out->mask && g.W % 16 == 0 && !((uintptr_t)out->mask & 15);
+    const auto at = [&](int c0) {
+        a.count = out->count ? out->count + c0 : nullptr;
+        a.value = out->value ? reinterpret_cast<long long *>(out->value) + c0 : nullptr;
+        a.mask = out->mask ? out->mask + (size_t)c0 * g.H * g.W : nullptr;
+        a.seeds = out->seeds ? out->seeds + c0 : nullptr;
+        a.point_in = out->point_in ? out->point_in + (size_t)c0 * p->k : nullptr;
+        a.rounds = out->rounds ? out->rounds + c0 : nullptr;
+    };
+    return band_search(s, who, s->reach, n, envs, p->points, p->scratch_bytes, kReachScratchDefault, need, a, a, at, k_reach<true>, k_reach<false>,
+                       a.nb, reach_lds_bytes);
+}
+
+extern "C" int sf_walk(sf_sim *s, const sf_walk_params *p, int32_t n, const int32_t *envs, const sf_walk_out *out)
+{
+    const char *who = "sf_walk";
+    if (!s || !p || !out) return fail(SF_EINVAL, "sf_walk: null argument");
+    const Geo &g = s->g;
+    if (n < 0 || (n > 0 && !envs)) return fail(SF_EINVAL, "sf_walk: bad environment list");
+    if (p->target_mask < 0 || p->target_mask > 63) return fail(SF_EINVAL, "sf_walk: target_mask %d (bit s selects BurnStatus s: 0..63)", p->target_mask);
+    if (p->through_mask < 1 || p->through_mask > 63) return fail(SF_EINVAL, "sf_walk: through_mask %d (bit s selects BurnStatus s: 1..63)", p->through_mask);
+    if (p->target_mask == 0 && !p->targets) return fail(SF_EINVAL, "sf_walk: target_mask 0 needs a targets plane");
+    if (p->connectivity != 0 && p->connectivity != 4 && p->connectivity != 8)
+        return fail(SF_EINVAL, "sf_walk: connectivity %d (0 or 4: the agents' moves, 8)", p->connectivity);
+    SF_TRY(check_points(who, p->k, p->points, true));
+    if ((out->point_moves || out->point_step) && p->k == 0) return fail(SF_EINVAL, "sf_walk: point_moves and point_step need k > 0");
+    if (out->point_step && p->connectivity == 8) return fail(SF_EINVAL, "sf_walk: point_step needs connectivity 4 (the four moves)");
+    if (p->max_moves < 0) return fail(SF_EINVAL, "sf_walk: max_moves %d (0: no cap)", p->max_moves);
+    SF_TRY(check_reserved(who, p->reserved[0] | p->reserved[1]));
+    if (!out->moves && !out->point_moves && !out->point_step && !out->reached && !out->levels)
+        return fail(SF_EINVAL, "sf_walk: every output is null");
+    SF_TRY(check_aligned(who, ((uintptr_t)out->moves | (uintptr_t)out->point_moves | (uintptr_t)out->point_step | (uintptr_t)out->reached | (uintptr_t)out->levels) & 3));
+    const size_t need = (size_t)walk_env_bytes(g);
+    SF_TRY(check_scratch(who, p->scratch_bytes, need, "need"));
+    SF_TRY(check_envs(s, who, n, envs));
+    if (g.W > kWalkMaxWidth) return fail(SF_ENOTSUP, "sf_walk: grids wider than %d cells are not supported (width %d)", kWalkMaxWidth, g.W);
+    SF_TRY(begin_call(s, who, kNeedRt | kNeedReset | kNotVoid));
+    if (n == 0) return SF_OK;
+
+    WalkArgs a;
+    memset(&a, 0, sizeof a);
+    band_args(s, a.r, p->passable, p->passable_per_env, p->k, p->target_mask, p->through_mask);
+    a.r.conn8 = p->connectivity == 8;
+    a.targets = p->targets;
+    a.tgt_env = p->targets_per_env ? (long long)g.H * g.W : 0;
+    a.tgt_vec = p->targets && g.W % 16 == 0 && !((uintptr_t)p->targets & 15);
+    a.max_moves = p->max_moves;
+    a.moves_vec = out->moves && g.W % 4 == 0 && !((uintptr_t)out->moves & 15);
+    const auto at = [&](int c0) {
+        a.moves = out->moves ? out->moves + (size_t)c0 * g.H * g.W : nullptr;
+        a.point_moves = out->point_moves ? out->point_moves + (size_t)c0 * p->k : nullptr;
+        a.point_step = out->point_step ? out->point_step + (size_t)c0 * p->k : nullptr;
+        a.reached = out->reached ? out->reached + c0 : nullptr;
+        a.levels = out->levels ? out->levels + c0 : nullptr;
+    };
+    // (every point has a lane of its own, so a small grid still gets k threads)
+    return band_search(s, who, s->walk, n, envs, p->points, p->scratch_bytes, kWalkScratchDefault, need, a, a.r, at, k_walk<true>, k_walk<false>,
+                       std::max(a.r.nb, p->k), walk_lds_bytes);
+}
+
+// ----------------------------------------------------------------------------- fire behaviour
+// The heat cache made current for the listed tables (host list), modelled on ensure_wterms: allocated at the first call, filled per
+// run of stale tables.  Enqueue layer.
+static int ensure_hpa(sf_sim *s, const std::vector<int32_t> &tabs)
+{
+    const Geo &g = s->g;
+    BehaviorState &b = s->behavior;
+    if (!b.hpa) {
+        SF_TRY(dev_alloc(s, &b.hpa, (size_t)s->tables.size() * g.H * g.W));
+        s->tables.hpa_allocated();
+    }
+    std::vector<int32_t> stale;
+    for (int32_t t : tabs) if (s->tables[t].hpa_stale) stale.push_back(t);
+    std::sort(stale.begin(), stale.end());
+    stale.erase(std::unique(stale.begin(), stale.end()), stale.end());
+    for (size_t i = 0; i < stale.size();) {
+        size_t j = i + 1;
+        while (j < stale.size() && stale[j] == stale[j - 1] + 1 && j - i < 65535) ++j;
+        hipLaunchKernelGGL(k_behavior_hpa, dim3((unsigned)((g.W + kBehThreads - 1) / kBehThreads), (unsigned)g.H, (unsigned)(j - i)), dim3(kBehThreads), 0,
+                           s->stream, g.H, g.W, (const double *)s->lay_all, (int)stale[i], (float)s->p.h, (float)s->p.S_T, (float)s->p.S_e,
+                           (float)s->p.p_p, (float)s->p.M_f, b.hpa);
+        for (size_t k = i; k < j; ++k) s->tables.hpa_built(stale[k]);
+        b.builds += (int64_t)(j - i);
+        i = j;
+    }
+    HIPCHK(hipGetLastError());
+    return SF_OK;
+}
+
+// No scratch and no chunks: the stale parts of the heat cache are rebuilt, the summary outputs zeroed, then ONE launch serves the
+// whole list: k_behavior where a plane is asked for, else k_behavior_scan.  No state of the handle changes but the cache.
+extern "C" int sf_behavior(sf_sim *s, const sf_behavior_params *p, const sf_behavior_out *out, const int32_t *envs, int32_t n)
+{
+    const char *who = "sf_behavior";
+    if (!s || !p || !out) return fail(SF_EINVAL, "sf_behavior: null argument");
+    const Geo &g = s->g;
+    if (n < 0 || (n > 0 && !envs)) return fail(SF_EINVAL, "sf_behavior: bad environment list");
+    const bool planes = out->hpa || out->ros || out->intensity || out->flame_length || out->head || out->workable;
+    const bool summary = out->max_flame || out->max_intensity || out->classes;
+    if (!planes && !summary && !out->point_flame) return fail(SF_EINVAL, "sf_behavior: every output is null");
+    if (p->status_mask < 0 || p->status_mask > 63) return fail(SF_EINVAL, "sf_behavior: status_mask %d (bit s selects BurnStatus s: 1..63, or 0 for every cell)", p->status_mask);
+    if (p->summary_mask < 1 || p->summary_mask > 63) return fail(SF_EINVAL, "sf_behavior: summary_mask %d (bit s selects BurnStatus s: 1..63)", p->summary_mask);
+    SF_TRY(check_reserved(who, p->reserved));
+    if (!(p->edges[0] < p->edges[1] && p->edges[1] < p->edges[2] && p->edges[2] < p->edges[3]))
+        return fail(SF_EINVAL, "sf_behavior: the class edges must increase (%g, %g, %g, %g)", (double)p->edges[0], (double)p->edges[1], (double)p->edges[2], (double)p->edges[3]);
+    if (!(p->flame_limit >= 0.0f)) return fail(SF_EINVAL, "sf_behavior: flame_limit %g (>= 0)", (double)p->flame_limit);
+    SF_TRY(check_points(who, p->k, p->points, true));
+    if (out->point_flame && p->k == 0) return fail(SF_EINVAL, "sf_behavior: point_flame needs k > 0");
+    if (p->k > 0 && !out->point_flame) return fail(SF_EINVAL, "sf_behavior: points without point_flame");
+    SF_TRY(check_aligned(who, ((uintptr_t)out->hpa | (uintptr_t)out->ros | (uintptr_t)out->intensity | (uintptr_t)out->flame_length | (uintptr_t)out->max_flame |
+                               (uintptr_t)out->max_intensity | (uintptr_t)out->classes | (uintptr_t)out->point_flame | (uintptr_t)p->points) & 3));
+    SF_TRY(check_envs(s, who, n, envs));
+    SF_TRY(check_ready(s, who, kNeedRt | kNeedReset));
+    const bool per_env = s->tables.size() > 1;
+    std::vector<int32_t> tabs;
+    for (int i = 0; i < n; ++i) {
+        const int t = per_env ? envs[i] : 0;
+        if (!s->tables[t].layers)
+            return fail(SF_ESTATE, "sf_behavior: environment %d's table came from sf_set_rtable: there are no layers to take the reaction intensity from", envs[i]);
+        tabs.push_back(t);
+    }
+    SF_TRY(begin_call(s, who, kNeedRt | kNeedReset | kNotVoid));
+    if (n == 0) return SF_OK;
+
+    BehaviorState &b = s->behavior;
+    SF_TRY(ensure_hpa(s, tabs));
+    BehArgs a;
+    memset(&a, 0, sizeof a);
+    SF_TRY(block_stage(s, b.blk, &a.envs, envs, (size_t)n * sizeof(int32_t)));
+    if (out->max_flame) HIPCHK(hipMemsetAsync(out->max_flame, 0, (size_t)n * sizeof(float), s->stream));
+    if (out->max_intensity) HIPCHK(hipMemsetAsync(out->max_intensity, 0, (size_t)n * sizeof(float), s->stream));
+    if (out->classes) HIPCHK(hipMemsetAsync(out->classes, 0, (size_t)n * 5 * sizeof(int32_t), s->stream));
+
+    a.H = g.H; a.W = g.W; a.P = g.P; a.PV = g.PV;
+    a.plane_env = g.plane_env; a.rt_env = g.rt_env; a.cells_env = g.cells_env;
+    a.status = s->status;
+    a.cells = s->bl_cur ? s->cells : nullptr;
+    a.rt = s->rt;
+    a.hpa = b.hpa;
+    a.hpa_env = per_env ? (long long)g.H * g.W : 0;
+    a.n = n;
+    a.smask = (uint32_t)p->status_mask;
+    a.summask = (uint32_t)p->summary_mask;
+    a.flame_limit = p->flame_limit;
+    for (int i = 0; i < 4; ++i) a.edge[i] = p->edges[i];
+    a.o_hpa = out->hpa; a.o_ros = out->ros; a.o_int = out->intensity; a.o_flame = out->flame_length; a.o_head = out->head; a.o_work = out->workable;
+    a.max_flame = out->max_flame; a.max_int = out->max_intensity; a.classes = out->classes;
+    a.points = p->points; a.point_flame = out->point_flame; a.k = p->k;
+    a.planes = planes; a.summary = summary;
+    // items per environment: (row, 4 columns) with planes, (row, 16-cell vector) for the scan
+    a.blocks_env = ((long long)g.H * (planes ? (g.W + 3) / 4 : g.PV) + kBehThreads - 1) / kBehThreads;
+    a.total = (planes || summary) ? (long long)n * a.blocks_env : 0;
+    const bool vec = g.W % 4 == 0 && !(((uintptr_t)out->hpa | (uintptr_t)out->ros | (uintptr_t)out->intensity | (uintptr_t)out->flame_length) & 15) &&
+                     !(((uintptr_t)out->head | (uintptr_t)out->workable) & 3);
+    const long long pblocks = ((long long)n * p->k + kBehThreads - 1) / kBehThreads;
+    const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>(std::max(a.total, pblocks), (long long)s->n_cu * 8));
+    if (!planes) hipLaunchKernelGGL(k_behavior_scan, dim3(grid), dim3(kBehThreads), 0, s->stream, a);
+    else if (vec) hipLaunchKernelGGL(k_behavior<true>, dim3(grid), dim3(kBehThreads), 0, s->stream, a);
+    else hipLaunchKernelGGL(k_behavior<false>, dim3(grid), dim3(kBehThreads), 0, s->stream, a);
+    return finish_call(s, who, !s->async, nullptr);
+}
+
+extern "C" int sf_get_behavior_builds(sf_sim *s, int64_t *n_out)
+{
+    if (!s || !n_out) return fail(SF_EINVAL, "sf_get_behavior_builds: null argument");
+    *n_out = s->behavior.builds;
+    return SF_OK;
+}

@@ -128,17 +128,6 @@ static int state_chunk(const StateArgs &a, bool device)
 }
 
 // ----------------------------------------------------------------------------- resets
-// A call's environment list / host ignitions -> device memory through the pinned buffer, one copy; *dev is where they are.
-static int reset_stage(sf_sim *s, const void *a, size_t na, const void *b, size_t nb, uint8_t **dev)
-{
-    CallBlock &blk = s->rs_blk;
-    SF_TRY(block_reserve(s, blk, na + nb));
-    if (na) memcpy(blk.pinned, a, na);
-    if (nb) memcpy(blk.pinned + na, b, nb);
-    *dev = blk.dev;
-    return block_send(s, blk, na + nb);
-}
-
 // The two launches of a reset, the one way an environment gets a new episode: every environment taken is written in the layout that is
 // current.  envs_dev: the list form's environments (distinct), else the mask form over all of them.  full: the list names every
 // environment (sf_reset), so the handle-wide bookkeeping starts afresh too.
@@ -195,9 +184,9 @@ static int check_ignitions(const sf_sim *s, const char *who, int n, const int32_
 // (sf_get_fire_map_delta: a reset map is all UNBURNED - the caller zeroes its mirror, the next delta reports the ignition)
 static int reset_list(sf_sim *s, const int32_t *envs, const int32_t *xy, int m, bool full = false)
 {
-    uint8_t *dev = nullptr;
-    SF_TRY(reset_stage(s, envs, (size_t)m * 4, xy, (size_t)m * 8, &dev));
-    SF_TRY(reset_launch(s, reinterpret_cast<const int32_t *>(dev), nullptr, reinterpret_cast<const int32_t *>(dev + (size_t)m * 4), m, full));
+    const int32_t *dev = nullptr;
+    SF_TRY(block_stage(s, s->rs_blk, &dev, envs, (size_t)m * 4, xy, (size_t)m * 8));
+    SF_TRY(reset_launch(s, dev, nullptr, dev + m, m, full));
     if (s->delta.snap) for (int i = 0; i < m; ++i) s->delta.snap_valid[envs[i]] = 1;
     return SF_OK;
 }
@@ -275,11 +264,7 @@ extern "C" int sf_reset_where(sf_sim *s, const uint8_t *device_mask, const int32
     const Geo &g = s->g;
     SF_TRY(begin_call(s, "sf_reset_where", kStateCall));
     const int32_t *xy_dev = xy;
-    if (!xy_device_pointer) {
-        uint8_t *dev = nullptr;
-        SF_TRY(reset_stage(s, xy, (size_t)g.E * 8, nullptr, 0, &dev));
-        xy_dev = reinterpret_cast<const int32_t *>(dev);
-    }
+    if (!xy_device_pointer) SF_TRY(block_stage(s, s->rs_blk, &xy_dev, xy, (size_t)g.E * 8));
     SF_TRY(reset_launch(s, nullptr, device_mask, xy_dev, g.E));
     // which environments were taken is known on the device only: no host mirror of a map can be told to zero itself, so the next
     // delta query of every environment hands back the whole map once

@@ -215,17 +215,11 @@ extern "C" int sf_ensemble_stats(sf_sim *s, const sf_ensemble_params *p, const i
     if (out->loss && !s->values.plane) return fail(SF_ESTATE, "sf_ensemble_stats: loss needs a value plane (sf_values_set)");
     SF_TRY(begin_call(s, "sf_ensemble_stats", kNotVoid));
 
-    const size_t bytes = (size_t)G * K * sizeof(int32_t);
-    CallBlock &blk = s->ens_blk;
-    SF_TRY(block_reserve(s, blk, bytes));
-    memcpy(blk.pinned, members, bytes);
-    SF_TRY(block_send(s, blk, bytes));
-
     EnsArgs a;
     memset(&a, 0, sizeof a);
+    SF_TRY(block_stage(s, s->ens_blk, &a.members, members, (size_t)G * K * sizeof(int32_t)));
     a.arrival1 = s->arrival.plane; a.plane_env = g.plane_env;
     a.H = g.H; a.W = g.W; a.P = g.P; a.Q = (g.W + 3) / 4;
-    a.members = reinterpret_cast<const int32_t *>(blk.dev);
     a.G = G; a.K = K; a.T = T;
     int TP = 1;
     while (TP < T) TP *= 2;
@@ -461,189 +455,6 @@ extern "C" int sf_observe(sf_sim *s, const sf_obs_params *p, int32_t n, const in
     a.norm = p->normalize != 0; a.bf16 = p->dtype == 1; a.pad = p->pad;
     hipLaunchKernelGGL(k_observe, dim3((unsigned)((long long)n * tiles)), dim3(kObsThreads), 0, s->stream, a);
     return finish_call(s, "sf_observe", !s->async, nullptr);
-}
-
-// ----------------------------------------------------------------------------- distance fields
-// The environment list goes through the feature's call block; the list is then worked through in chunks of as many environments as
-// the scratch budget holds planes of g: per chunk the two column passes and k_dist_rows (plane form) or k_dist_points.  All of it on
-// the handle's stream, so a chunk's passes follow the chunk before it; no state of the handle changes but the scratch plane.
-extern "C" int sf_distance(sf_sim *s, const sf_dist_params *p, int32_t n, const int32_t *envs, void *device_out)
-{
-    if (!s || !p) return fail(SF_EINVAL, "sf_distance: null argument");
-    const Geo &g = s->g;
-    if (n < 0 || (n > 0 && (!envs || !device_out))) return fail(SF_EINVAL, "sf_distance: bad environment list or output");
-    if (p->status_mask < 1 || p->status_mask > 63) return fail(SF_EINVAL, "sf_distance: status_mask %d (bit s selects BurnStatus s: 1..63)", p->status_mask);
-    if (p->max_d2 < 0) return fail(SF_EINVAL, "sf_distance: max_d2 %d (0: no cap)", p->max_d2);
-    if (p->dtype != SF_DIST_I32 && p->dtype != SF_DIST_F32) return fail(SF_EINVAL, "sf_distance: dtype %d (0 int32, 1 float32)", p->dtype);
-    if (p->k < 0 || p->k > SF_DIST_MAX_POINTS) return fail(SF_EINVAL, "sf_distance: %d points per environment (0..%d)", p->k, SF_DIST_MAX_POINTS);
-    if (p->k > 0 && !p->points) return fail(SF_EINVAL, "sf_distance: k = %d needs points", p->k);
-    if (!std::isfinite(p->scale) || !(p->scale > 0.0)) return fail(SF_EINVAL, "sf_distance: scale must be finite and > 0");
-    if (p->reserved[0] != 0 || p->reserved[1] != 0) return fail(SF_EINVAL, "sf_distance: reserved must be 0");
-    if ((uintptr_t)device_out & 3) return fail(SF_EINVAL, "sf_distance: the output is not aligned to its element");
-    const size_t plane = (size_t)g.plane_env * sizeof(uint16_t);          // one environment's g
-    if (p->scratch_bytes < 0 || (p->scratch_bytes > 0 && (size_t)p->scratch_bytes < plane))
-        return fail(SF_EINVAL, "sf_distance: scratch_bytes %lld is less than one environment's plane (%zu bytes)", (long long)p->scratch_bytes, plane);
-    SF_TRY(check_envs(s, "sf_distance", n, envs));
-    if ((long long)(g.H - 1) * (g.H - 1) + (long long)(g.W - 1) * (g.W - 1) >= (long long)SF_DIST_FAR)
-        return fail(SF_ENOTSUP, "sf_distance: squared distances on a %d x %d grid do not fit int32", g.H, g.W);
-    if (g.W > kDistMaxWidth) return fail(SF_ENOTSUP, "sf_distance: grids wider than %d cells are not supported (width %d)", kDistMaxWidth, g.W);
-    SF_TRY(begin_call(s, "sf_distance", kNeedRt | kNeedReset | kNotVoid));
-    if (n == 0) return SF_OK;
-
-    const size_t budget = p->scratch_bytes > 0 ? (size_t)p->scratch_bytes : (size_t)kDistScratchDefault;
-    const int chunk = (int)std::min<size_t>({(size_t)n, budget / plane, (size_t)32768});      // (32768: the launch grid's y)
-    DistState &d = s->dist;
-    if ((size_t)chunk * plane > d.cap) {              // growing waits for the device: enqueued kernels may still use the plane
-        HIPCHK(hipStreamSynchronize(s->stream));
-        s->bytes -= (int64_t)d.cap;
-        HIPCHK(d.release());
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&d.plane), (size_t)chunk * plane));
-        d.cap = (size_t)chunk * plane;
-        s->bytes += (int64_t)d.cap;
-    }
-    const size_t bytes = (size_t)n * sizeof(int32_t);
-    SF_TRY(block_reserve(s, d.blk, bytes));
-    memcpy(d.blk.pinned, envs, bytes);
-    SF_TRY(block_send(s, d.blk, bytes));
-
-    DistArgs a;
-    memset(&a, 0, sizeof a);
-    a.g = g;
-    a.status = s->status;
-    a.cells = s->bl_cur ? s->cells : nullptr;
-    a.gp = d.plane;
-    a.k = p->k;
-    for (int st = 0; st < 8; ++st)
-        if (st < 6 && ((p->status_mask >> st) & 1)) (st < 4 ? a.tlo : a.thi) |= 1u << (8 * (st & 3));
-    a.limit = p->max_d2 > 0 ? p->max_d2 : SF_DIST_FAR;
-    a.reach = g.W;
-    if (p->max_d2 > 0) {
-        a.reach = (int)std::sqrt((double)p->max_d2);
-        while ((long long)a.reach * a.reach < p->max_d2) a.reach++;
-        a.reach = std::min(a.reach, g.W);
-    }
-    a.f32 = p->dtype == SF_DIST_F32;
-    a.scale = p->scale;
-    a.vec = g.W % 4 == 0 && !((uintptr_t)device_out & 15);
-    a.rows = std::max(1, std::min({1024 / g.P, kDistMaxRows, g.H}));
-    const size_t per_env = (p->k ? (size_t)p->k : (size_t)g.H * g.W) * 4;      // output bytes per listed environment
-    for (int c0 = 0; c0 < n; c0 += chunk) {
-        a.cn = std::min(chunk, n - c0);
-        a.envs = reinterpret_cast<const int32_t *>(d.blk.dev) + c0;
-        a.out = static_cast<uint8_t *>(device_out) + (size_t)c0 * per_env;
-        a.points = p->k ? p->points + (size_t)c0 * p->k * 3 : nullptr;
-        const unsigned col_blocks = (unsigned)(((long long)a.cn * g.PV + kDistColsThreads - 1) / kDistColsThreads);
-        hipLaunchKernelGGL(k_dist_cols_down, dim3(col_blocks), dim3(kDistColsThreads), 0, s->stream, a);
-        hipLaunchKernelGGL(k_dist_cols_up, dim3(col_blocks), dim3(kDistColsThreads), 0, s->stream, a);
-        if (p->k)
-            hipLaunchKernelGGL(k_dist_points, dim3((unsigned)((p->k + kDistRowsThreads / 64 - 1) / (kDistRowsThreads / 64)), (unsigned)a.cn),
-                               dim3(kDistRowsThreads), 0, s->stream, a);
-        else
-            hipLaunchKernelGGL(k_dist_rows, dim3((unsigned)((g.H + a.rows - 1) / a.rows), (unsigned)a.cn), dim3(kDistRowsThreads),
-                               (size_t)a.rows * g.P * sizeof(int32_t), s->stream, a);
-    }
-    return finish_call(s, "sf_distance", !s->async, nullptr);
-}
-
-// ----------------------------------------------------------------------------- reach of the fire
-// The environment list goes through the feature's call block; the list is then worked through in chunks of as many environments as
-// the scratch budget holds (reach_env_bytes each), one k_reach launch per chunk with one workgroup per listed environment.  All of
-// it on the handle's stream; no state of the handle changes but the scratch.
-extern "C" int sf_reach(sf_sim *s, const sf_reach_params *p, int32_t n, const int32_t *envs, const sf_reach_out *out)
-{
-    if (!s || !p || !out) return fail(SF_EINVAL, "sf_reach: null argument");
-    const Geo &g = s->g;
-    if (n < 0 || (n > 0 && !envs)) return fail(SF_EINVAL, "sf_reach: bad environment list");
-    if (p->source_mask < 1 || p->source_mask > 63) return fail(SF_EINVAL, "sf_reach: source_mask %d (bit s selects BurnStatus s: 1..63)", p->source_mask);
-    if (p->through_mask < 1 || p->through_mask > 63) return fail(SF_EINVAL, "sf_reach: through_mask %d (bit s selects BurnStatus s: 1..63)", p->through_mask);
-    if (p->source_mask & p->through_mask) return fail(SF_EINVAL, "sf_reach: source_mask %d and through_mask %d overlap", p->source_mask, p->through_mask);
-    if (p->connectivity != 0 && p->connectivity != 4 && p->connectivity != 8)
-        return fail(SF_EINVAL, "sf_reach: connectivity %d (0: the handle's diagonal_spread, 4, 8)", p->connectivity);
-    if (p->k < 0 || p->k > SF_DIST_MAX_POINTS) return fail(SF_EINVAL, "sf_reach: %d points per environment (0..%d)", p->k, SF_DIST_MAX_POINTS);
-    if (p->k > 0 && !p->points) return fail(SF_EINVAL, "sf_reach: k = %d needs points", p->k);
-    if (out->point_in && p->k == 0) return fail(SF_EINVAL, "sf_reach: point_in needs k > 0");
-    if (p->max_rounds < 0) return fail(SF_EINVAL, "sf_reach: max_rounds %d (0: to the fixed point)", p->max_rounds);
-    if (p->reserved[0] != 0 || p->reserved[1] != 0) return fail(SF_EINVAL, "sf_reach: reserved must be 0");
-    if (!out->count && !out->value && !out->mask && !out->seeds && !out->point_in && !out->rounds)
-        return fail(SF_EINVAL, "sf_reach: every output is null");
-    if (((uintptr_t)out->count | (uintptr_t)out->seeds | (uintptr_t)out->point_in | (uintptr_t)out->rounds) & 3 || ((uintptr_t)out->value & 7))
-        return fail(SF_EINVAL, "sf_reach: an output is not aligned to its element");
-    const size_t need = (size_t)reach_env_bytes(g);
-    if (p->scratch_bytes < 0 || (p->scratch_bytes > 0 && (size_t)p->scratch_bytes < need))
-        return fail(SF_EINVAL, "sf_reach: scratch_bytes %lld is less than one environment's need (%zu bytes)", (long long)p->scratch_bytes, need);
-    SF_TRY(check_envs(s, "sf_reach", n, envs));
-    if (g.W > kReachMaxWidth) return fail(SF_ENOTSUP, "sf_reach: grids wider than %d cells are not supported (width %d)", kReachMaxWidth, g.W);
-    SF_TRY(check_ready(s, "sf_reach", kNeedRt | kNeedReset));
-    if (out->value && !s->values.plane) return fail(SF_ESTATE, "sf_reach: value needs a value plane (sf_values_set)");
-    SF_TRY(begin_call(s, "sf_reach", kNeedRt | kNeedReset | kNotVoid));
-    if (n == 0) return SF_OK;
-
-    const size_t budget = p->scratch_bytes > 0 ? (size_t)p->scratch_bytes : (size_t)kReachScratchDefault;
-    const int chunk = (int)std::min<size_t>({(size_t)n, std::max<size_t>(budget / need, 1), (size_t)65535});
-    ReachState &r = s->reach;
-    if ((size_t)chunk * need > r.cap) {               // growing waits for the device: enqueued kernels may still use the scratch
-        HIPCHK(hipStreamSynchronize(s->stream));
-        s->bytes -= (int64_t)r.cap;
-        HIPCHK(r.release());
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&r.mem), (size_t)chunk * need));
-        r.cap = (size_t)chunk * need;
-        s->bytes += (int64_t)r.cap;
-    }
-    // the call block: the environment list | one ReachArgs per chunk (the kernel takes its arguments from there)
-    const int chunks = (n + chunk - 1) / chunk;
-    const size_t o_args = ((size_t)n * sizeof(int32_t) + 15) / 16 * 16, bytes = o_args + (size_t)chunks * sizeof(ReachArgs);
-    SF_TRY(block_reserve(s, r.blk, bytes));
-    memcpy(r.blk.pinned, envs, (size_t)n * sizeof(int32_t));
-
-    ReachArgs a;
-    memset(&a, 0, sizeof a);
-    a.g = g;
-    a.status = s->status;
-    a.cells = s->bl_cur ? s->cells : nullptr;
-    a.passable = p->passable;
-    a.pass_env = p->passable_per_env ? (long long)g.H * g.W : 0;
-    a.pass_vec = p->passable && g.W % 16 == 0 && !((uintptr_t)p->passable & 15);
-    a.vals = out->value ? s->values.plane : nullptr;
-    a.val_env = s->values.per_env ? g.plane_env : 0;
-    a.k = p->k;
-    a.scratch = r.mem;
-    a.scratch_env = (long long)need;
-    for (int st = 0; st < 6; ++st) {
-        if ((p->source_mask >> st) & 1) (st < 4 ? a.slo : a.shi) |= 1u << (8 * (st & 3));
-        if ((p->through_mask >> st) & 1) (st < 4 ? a.tlo : a.thi) |= 1u << (8 * (st & 3));
-    }
-    a.conn8 = p->connectivity == 0 ? g.diag : (p->connectivity == 8);
-    a.max_rounds = p->max_rounds;
-    a.WORDS = reach_words(g); a.BR = reach_band_rows(g); a.nb = a.BR * a.WORDS;
-    a.mask_vec = out->mask && g.W % 16 == 0 && !((uintptr_t)out->mask & 15);
-    for (int c = 0; c < chunks; ++c) {
-        const int c0 = c * chunk;
-        a.envs = reinterpret_cast<const int32_t *>(r.blk.dev) + c0;
-        a.points = p->k ? p->points + (size_t)c0 * p->k * 3 : nullptr;
-        a.count = out->count ? out->count + c0 : nullptr;
-        a.value = out->value ? reinterpret_cast<long long *>(out->value) + c0 : nullptr;
-        a.mask = out->mask ? out->mask + (size_t)c0 * g.H * g.W : nullptr;
-        a.seeds = out->seeds ? out->seeds + c0 : nullptr;
-        a.point_in = out->point_in ? out->point_in + (size_t)c0 * p->k : nullptr;
-        a.rounds = out->rounds ? out->rounds + c0 : nullptr;
-        memcpy(r.blk.pinned + o_args + (size_t)c * sizeof(ReachArgs), &a, sizeof a);
-    }
-    SF_TRY(block_send(s, r.blk, bytes));
-
-    // one band per thread: F stays in registers for the whole fill (k_reach<true>); else passes of 1024 bands over the scratch planes.
-    // Either way a thread's open words lie in LDS: 136 - 156 KiB at 1024 threads, one workgroup per CU (which 1024 threads are anyway)
-    const bool resident = a.nb <= kReachThreads;
-    const unsigned threads = resident ? (unsigned)((a.nb + 63) / 64 * 64) : (unsigned)kReachThreads;
-    const size_t lds = reach_lds_bytes((int)threads, resident);
-    const void *fn = resident ? reinterpret_cast<const void *>(&k_reach<true>) : reinterpret_cast<const void *>(&k_reach<false>);
-    HIPCHK(allow_lds(s, fn, lds));
-    for (int c = 0; c < chunks; ++c) {
-        const ReachArgs *ap = reinterpret_cast<const ReachArgs *>(r.blk.dev + o_args) + c;
-        const unsigned cn = (unsigned)std::min(chunk, n - c * chunk);
-        if (resident) hipLaunchKernelGGL(k_reach<true>, dim3(cn), dim3(threads), lds, s->stream, ap);
-        else hipLaunchKernelGGL(k_reach<false>, dim3(cn), dim3(threads), lds, s->stream, ap);
-    }
-    return finish_call(s, "sf_reach", !s->async, nullptr);
 }
 
 // ----------------------------------------------------------------------------- frames

@@ -62,16 +62,6 @@ static void wind_sched_count(sf_sim *s)
     s->tables.schedule_changed();
 }
 
-// An environment list -> the wind call block (enqueue layer); *dev: where it is
-static int wind_list(sf_sim *s, const int32_t *envs, int n, const int32_t **dev)
-{
-    CallBlock &blk = s->wind.blk;
-    SF_TRY(block_reserve(s, blk, (size_t)n * 4));
-    memcpy(blk.pinned, envs, (size_t)n * 4);
-    *dev = (const int32_t *)blk.dev;
-    return block_send(s, blk, (size_t)n * 4);
-}
-
 // The tables of these environments were rebuilt from their layers (or their state was loaded): whichever segment a schedule built
 // them for, the next stepping call decides anew.
 static int wind_forget(sf_sim *s, const int32_t *envs, int n)
@@ -80,7 +70,7 @@ static int wind_forget(sf_sim *s, const int32_t *envs, int n)
     for (int k = 0; k < n && !any; ++k) any = s->wind.sched_dev && s->wind.K[envs[k]] != 0;
     if (!any) return SF_OK;
     const int32_t *list_dev = nullptr;
-    SF_TRY(wind_list(s, envs, n, &list_dev));
+    SF_TRY(block_stage(s, s->wind.blk, &list_dev, envs, (size_t)n * 4));
     hipLaunchKernelGGL(k_wind_sched_forget, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, n, list_dev, s->wind.sched_dev);
     HIPCHK(hipGetLastError());
     return SF_OK;

@@ -711,8 +711,7 @@ static int ensure_vbits(sf_sim *s)
 }
 
 #include "sf_host_views.h"
-#include "sf_host_walk.h"
-#include "sf_host_behavior.h"
+#include "sf_host_query.h"
 
 extern "C" int sf_last_step_launch(sf_sim *s, int32_t *kind)
 {

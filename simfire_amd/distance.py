@@ -6,7 +6,7 @@ without a GPU.  The kernels and the scratch budget are described in DESIGN.md se
 import numpy as np
 
 from . import _args
-from ._lib import SF_DIST_F32, SF_DIST_I32, SF_DIST_MAX_POINTS, SfDistParams
+from ._lib import SF_DIST_F32, SF_DIST_I32, SfDistParams
 
 
 def request(status, max_dist=None, max_d2=None, dtype="float32", scale=1.0, scratch_bytes=0):
@@ -40,10 +40,7 @@ class DistSpec:
         self.mask, self.max_d2, self.code, self.scale, self.scratch = request(status, max_dist, max_d2, dtype, scale, scratch_bytes)
         self.envs = _args.env_list(envs, n_envs, "distance", none_all=True)
         n = self.n = int(self.envs.shape[0])
-        self.points, self.k = None, 0
-        if points is not None:
-            self.points = _args.points(points, n, 3, "distance: points", host=False, k_range=(1, SF_DIST_MAX_POINTS))[0]
-            self.k = int(self.points.shape[1])
+        self.points, self.k = _args.query_points("distance", points, n)
         self.shape = (n, self.k) if self.k else (n, H, W)
         self.dtype = "int32" if self.code == SF_DIST_I32 else "float32"         # (the torch dtype's name)
         if out is not None:

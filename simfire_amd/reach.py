@@ -4,10 +4,8 @@
 Pure Python: every check happens here, before a device call, so that a bad request raises ``ValueError`` the same way with or
 without a GPU.  The flood fill and its scratch are described in DESIGN.md section 23.
 """
-import numpy as np
-
 from . import _args
-from ._lib import SF_DIST_MAX_POINTS, SfReachOut, SfReachParams
+from ._lib import SfReachOut, SfReachParams
 
 
 def request(source=("BURNING",), through=("UNBURNED",), connectivity=None, max_rounds=0, scratch_bytes=0):
@@ -28,7 +26,7 @@ def request(source=("BURNING",), through=("UNBURNED",), connectivity=None, max_r
 
 def scratch_need(H, W):
     """Bytes of scratch ``reach`` needs per listed environment of a chunk: two bit planes and the halo of the bands."""
-    bands = ((H + 15) // 16) * (((W + 15) // 16 * 16 + 63) // 64)
+    bands = _args.band_count(H, W)
     return (bands * 16 * 16 + bands * 20 + 255) // 256 * 256
 
 
@@ -42,9 +40,7 @@ class ReachSpec:
         self.envs = _args.env_list(envs, n_envs, "reach", none_all=True)
         n = self.n = int(self.envs.shape[0])
         want = dict(count=count, value=value, mask=mask, seeds=seeds, rounds=rounds)
-        for name, flag in want.items():
-            if not isinstance(flag, (bool, np.bool_)):
-                raise ValueError(f"reach: {name} must be True or False, got {flag!r}")
+        _args.flags("reach", **want)
         if not any(want.values()) and points is None:
             raise ValueError("reach: nothing asked for (count, value, mask, seeds, rounds or points)")
         if value and not values_on:
@@ -54,14 +50,8 @@ class ReachSpec:
             raise ValueError(f"reach: scratch_bytes {self.scratch} is less than one environment's need ({need} bytes)")
         if W > 8192:
             raise ValueError(f"reach: grids wider than 8192 cells are not supported (width {W})")
-        self.passable, self.per_env = None, 0
-        if passable is not None:
-            self.passable = _args.cuda_tensor(passable, "reach: passable", ("uint8",), [(H, W), (n_envs, H, W)]).contiguous()
-            self.per_env = int(passable.dim() == 3)
-        self.points, self.k = None, 0
-        if points is not None:
-            self.points = _args.points(points, n, 3, "reach: points", host=False, k_range=(1, SF_DIST_MAX_POINTS))[0]
-            self.k = int(self.points.shape[1])
+        self.passable, self.per_env = _args.dense_plane("reach", "passable", passable, n_envs, H, W)
+        self.points, self.k = _args.query_points("reach", points, n)
         shapes = dict(count=((n,), "int32"), value=((n,), "int64"), mask=((n, H, W), "uint8"), seeds=((n,), "int32"),
                       point_in=((n, self.k), "int32"), rounds=((n,), "int32"))
         want["point_in"] = bool(self.k)

@@ -1356,6 +1356,13 @@ class BatchedFireSimulation:
         self._engine.sync()
         return d if device else d.cpu().numpy()
 
+    def _agent_points(self, agents):
+        """``agents`` of ``reach``, ``moves_to`` and ``fire_behavior`` as the points of the call: ``True`` stands for the device
+        positions of a ``BatchedFireEnv``, ``False`` / ``None`` for none, anything else is the caller's tensor."""
+        if agents is True:
+            return self._engine.agents_device()
+        return None if agents is False else agents
+
     def reach(self, source=("BURNING",), through=("UNBURNED",), envs=None, connectivity=None, passable=None, agents=False, value=False,
               mask=False, device=True):
         """What the fires of ``envs`` (default: all) can still get to: the flood fill of the cells whose BurnStatus is one of
@@ -1366,11 +1373,7 @@ class BatchedFireSimulation:
         device positions of a ``BatchedFireEnv`` (every environment in order), or a tensor [n, k, 3] = (column, row, id) of the
         caller's.  ``device=True`` returns torch tensors on this GPU, else NumPy arrays; complete on return either way (one wait).
         One call, no host copy of the maps, no change to the simulation."""
-        points = None
-        if agents is True:
-            points = self._engine.agents_device()
-        elif agents is not False and agents is not None:
-            points = agents
+        points = self._agent_points(agents)
         r = self._engine.reach(source, through, envs=envs, connectivity=connectivity, passable=passable, points=points, count=True,
                                value=bool(value), mask=bool(mask), seeds=True)
         self._engine.sync()
@@ -1387,11 +1390,7 @@ class BatchedFireSimulation:
         caller's, and with ``step`` ``point_step`` [n, k], the move code 1..4 of a shortest route's first move (0: stay).
         ``max_moves`` caps the values.  ``device=True`` returns torch tensors on this GPU, else NumPy arrays; complete on return
         either way (one wait).  One call, no host copy of the maps, no change to the simulation."""
-        points = None
-        if agents is True:
-            points = self._engine.agents_device()
-        elif agents is not False and agents is not None:
-            points = agents
+        points = self._agent_points(agents)
         r = self._engine.walk(target, through, envs=envs, connectivity=connectivity, passable=passable, targets=targets, points=points,
                               max_moves=max_moves, plane=bool(plane), step=bool(step), reached=True, levels=True)
         self._engine.sync()
@@ -1410,11 +1409,7 @@ class BatchedFireSimulation:
         tensor [n, k, 3] = (column, row, id) of the caller's: the largest flame length among the ``summary`` cells of the 3 x 3
         block around each.  ``device=True`` returns torch tensors on this GPU, else NumPy arrays; complete on return either way
         (one wait).  One call, no host copy of tables or maps, no change to the simulation."""
-        points = None
-        if agents is True:
-            points = self._engine.agents_device()
-        elif agents is not False and agents is not None:
-            points = agents
+        points = self._agent_points(agents)
         r = self._engine.behavior(envs=envs, status=status, summary=summary, flame_limit=flame_limit, edges=edges, points=points,
                                   planes=planes, workable=flame_limit is not None, stats=True)
         self._engine.sync()

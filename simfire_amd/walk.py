@@ -7,7 +7,7 @@ without a GPU.  The search and its scratch are described in DESIGN.md section 24
 import numpy as np
 
 from . import _args
-from ._lib import SF_DIST_MAX_POINTS, SF_WALK_BLOCKED, SF_WALK_FAR, SfWalkOut, SfWalkParams  # noqa: F401
+from ._lib import SF_WALK_BLOCKED, SF_WALK_FAR, SfWalkOut, SfWalkParams  # noqa: F401
 
 #: the move codes of ``point_step`` (the action word of DESIGN.md section 16): (d_row, d_column)
 MOVES = {1: (-1, 0), 2: (1, 0), 3: (0, -1), 4: (0, 1)}
@@ -35,7 +35,7 @@ def request(target=("BURNING",), through=("UNBURNED",), connectivity=4, max_move
 
 def scratch_need(H, W):
     """Bytes of scratch ``walk`` needs per listed environment of a chunk: three bit planes and two halos of the bands."""
-    bands = ((H + 15) // 16) * (((W + 15) // 16 * 16 + 63) // 64)
+    bands = _args.band_count(H, W)
     return (bands * 16 * 24 + bands * 40 + 255) // 256 * 256
 
 
@@ -49,9 +49,7 @@ class WalkSpec:
         self.envs = _args.env_list(envs, n_envs, "walk", none_all=True)
         n = self.n = int(self.envs.shape[0])
         want = dict(plane=plane, step=step, reached=reached, levels=levels)
-        for name, flag in want.items():
-            if not isinstance(flag, (bool, np.bool_)):
-                raise ValueError(f"walk: {name} must be True or False, got {flag!r}")
+        _args.flags("walk", **want)
         if not (plane or reached or levels) and points is None:
             raise ValueError("walk: nothing asked for (plane, reached, levels or points)")
         if step and points is None:
@@ -63,18 +61,9 @@ class WalkSpec:
             raise ValueError(f"walk: scratch_bytes {self.scratch} is less than one environment's need ({need} bytes)")
         if W > 8192:
             raise ValueError(f"walk: grids wider than 8192 cells are not supported (width {W})")
-        self.passable, self.passable_per_env = None, 0
-        if passable is not None:
-            self.passable = _args.cuda_tensor(passable, "walk: passable", ("uint8",), [(H, W), (n_envs, H, W)]).contiguous()
-            self.passable_per_env = int(passable.dim() == 3)
-        self.targets, self.targets_per_env = None, 0
-        if targets is not None:
-            self.targets = _args.cuda_tensor(targets, "walk: targets", ("uint8",), [(H, W), (n_envs, H, W)]).contiguous()
-            self.targets_per_env = int(targets.dim() == 3)
-        self.points, self.k = None, 0
-        if points is not None:
-            self.points = _args.points(points, n, 3, "walk: points", host=False, k_range=(1, SF_DIST_MAX_POINTS))[0]
-            self.k = int(self.points.shape[1])
+        self.passable, self.passable_per_env = _args.dense_plane("walk", "passable", passable, n_envs, H, W)
+        self.targets, self.targets_per_env = _args.dense_plane("walk", "targets", targets, n_envs, H, W)
+        self.points, self.k = _args.query_points("walk", points, n)
         shapes = dict(moves=((n, H, W), "int32"), point_moves=((n, self.k), "int32"), point_step=((n, self.k), "int32"),
                       reached=((n,), "int32"), levels=((n,), "int32"))
         asked = dict(moves=bool(plane), point_moves=bool(self.k), point_step=bool(step), reached=bool(reached), levels=bool(levels))

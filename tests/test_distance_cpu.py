@@ -116,7 +116,7 @@ def test_header_declares_and_lib_binds_distance():
     assert open(os.path.join(csrc, "simfire_hip.hip")).read().count('#include "sf_dist_kernels.h"') == 1
     # the step kernels and the other features do not know the new kernels
     for unit in sorted(os.listdir(csrc)):
-        if unit.endswith((".hip", ".h")) and unit not in ("simfire_hip.hip", "sf_host_views.h", "sf_dist_kernels.h"):
+        if unit.endswith((".hip", ".h")) and unit not in ("simfire_hip.hip", "sf_host_query.h", "sf_dist_kernels.h"):
             assert "k_dist_" not in open(os.path.join(csrc, unit)).read(), unit
 
 

@@ -178,7 +178,7 @@ def test_header_declares_and_lib_binds_reach():
     assert open(os.path.join(csrc, "simfire_hip.hip")).read().count('#include "sf_reach_kernels.h"') == 1
     # the step kernels and the other features do not know the new kernel
     for unit in sorted(os.listdir(csrc)):
-        if unit.endswith((".hip", ".h")) and unit not in ("simfire_hip.hip", "sf_host_views.h", "sf_reach_kernels.h"):
+        if unit.endswith((".hip", ".h")) and unit not in ("simfire_hip.hip", "sf_host_query.h", "sf_reach_kernels.h"):
             assert "k_reach" not in open(os.path.join(csrc, unit)).read(), unit
     kernels = open(os.path.join(csrc, "sf_reach_kernels.h")).read()
     assert "asm" not in re.sub(r"//[^\n]*", "", kernels)        # plain C++ only
