@@ -6,7 +6,7 @@ echo "# kernel resource usage, product build (hipcc -O3 --offload-arch=gfx950 -R
 echo "# $(/opt/rocm/bin/hipcc --version | grep 'HIP version')"
 echo "# k_run<MAXD, ATT, DIAG, MIT, TEAM>: MIT 0 = sf_step (with the window phase where MAXD <= 2, TEAM != 2), -1 = sf_step_mitigated, -2 = the closed loop;"
 echo "#   TEAM 1 = teams of a size fixed for the launch, 2 = teams that grow inside the launch (NOTEBOOK.md 5.8)"
-echo "# The argument block: by value in k_run<*, *, *, 0, 0>, <2, *, *, *, 1>, <*, *, *, -2, *>, <*, *, *, *, 2>; read through the kernel-argument segment in the others (sf_run_kernels.h)"
+echo "# The argument block: by value in k_run<*, *, *, 0, 0>, <2, *, *, *, 1>, <*, *, *, -2, *>; split in <*, *, *, *, 2> (the geometry and the step boundary's words by value, the rest through the segment: round 8); read through the kernel-argument segment in the others (sf_run_kernels.h)"
 echo "# translation unit | kernel | VGPRs | SGPRs | SGPR spills | VGPR spills | scratch B/lane | waves/SIMD"
 echo
 for u in simfire_hip simfire_hip_run2 simfire_hip_run3 simfire_hip_run4; do

@@ -129,12 +129,11 @@ struct WalkCell {
 };
 
 template <int ATT, int CNT = 0>
-__device__ __forceinline__ WalkAcc run_walk(const StepArgs &a, const RunEnv &ev, const Masks &mk, int complete,
+__device__ __forceinline__ WalkAcc run_walk(const Geo &g, const RunEnv &ev, const Masks &mk, int complete,
                                             uint32_t lo_mask, uint32_t hi_mask, const uint32_t *strips,
                                             uint32_t pend, int lane, int th_log, PhaseClock &pc,
                                             uint32_t excl, uint32_t w16, uint4 s7)
 {
-    const Geo &g = a.g;
     WalkAcc acc = {0u, 0u, 0u, 0u};
     // first half of a cell: who, winner source, operands requested
     auto front = [&](uint32_t j, int own) {
@@ -433,9 +432,22 @@ __device__ __forceinline__ void kernarg_touch()
                  "+s"(d13), "+s"(d14), "+s"(d15));
 }
 
+// TEAM = 3: TEAM = 2 (every `kGrow` below) with the statistics behind sf_get_counters.  k_run<1, 0, 1, 0, 2> - bench.py's kernel - is built WITHOUT them (kStats below:
+// vectors visited, frontier items, walks, candidates, ignitions, the clocks of the team boundaries are not computed at all - some forty
+// instructions per batch and seven registers in a kernel at the register cap, carried through every update of a rollout that is timed with
+// the counters off); a handle with the counters on launches k_run<1, 0, 1, 0, 3> in its place (the host: launch_k_run_join).  Every other
+// instantiation keeps the statistics behind its look at a.counters: a second instantiation each costs build time, and they are not what is
+// timed.  (A body shared by two kernels through an inlined function was tried: it changes the code of every instantiation that takes its
+// arguments by value - the closed loop's kernel then spills 18 vector registers.  NOTEBOOK.md 5.18)
 template <int MAXD, int ATT, int DIAG, int MIT, int TEAM = 0>
 __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_steps_launch, int vcap, int bsz)
 {
+    constexpr bool kGrow = TEAM >= 2;            // teams that grow inside the launch
+#if defined(SF_PHASES) || defined(SF_NO_LEAN_STATS)
+    constexpr bool kStats = true;                // (the phase build logs the vectors visited; profiles/: the A / B build)
+#else
+    constexpr bool kStats = !(MAXD == 1 && ATT == 0 && DIAG == 1 && MIT == 0 && TEAM == 2);
+#endif
     kernarg_touch<(int)sizeof(StepArgs) + 12>();
     // The argument block is read where it is used, through the kernel-argument segment (constant address space: scalar loads), instead of
     // being taken by value - by value the compiler loads all of it in the entry block and spills most of it at once (239 of the join kernel's
@@ -444,20 +456,33 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
     // the copy - and so do the kernels that were measured SLOWER reading the segment (scalar loads inside the step loop): sf_step's on one-word
     // rows (the general loop on young fires 5.5 -> 5.7 us per update; the window phase the same either way) and the two-word team kernels
     // (C4's share over 300 updates 13.1 -> 13.5).  sf_step_mitigated's kernels and the one-word team kernels: the same speed either way.
+    // The kernel whose teams grow takes the block BOTH ways (NOTEBOOK.md 5.18).  What a step of the loop looks at - the geometry and the four
+    // words of the team's step boundary (`ah` below) - comes by value: loaded once, and where the registers run out spilled to a lane and read
+    // back by one v_readlane.  Everything else - what only a cut, a join, the prologue or the way out needs: the join arguments, the board, the
+    // time-outs, the result block's addresses - is read from the segment where it is used and is not alive across the step loop at all.  All by
+    // value, the entry block stored 228 scalar registers to spill lanes (334 spilled in all: six vector registers of a kernel at the 128 cap);
+    // all through the segment, the batch loop itself reloads 13 words per batch with a wait each (the compiler rather loads a kernel argument
+    // again than keep it).  Split: 252 spilled, no scalar load in the batch loop, and room for the two sets of rows of the unrolled loop.
 #ifdef SF_ARGS_BY_VALUE
     constexpr bool kArgsByValue = true;          // (profiles/: the A / B build)
+    constexpr bool kArgsSplit = false;
+#elif defined(SF_NO_ARGS_SPLIT)
+    constexpr bool kArgsByValue = kGrow || MIT == -2 || (MIT == 0 && TEAM == 0) || (TEAM == 1 && MAXD == 2);      // (profiles/: round 7's rule)
+    constexpr bool kArgsSplit = false;
 #else
-    constexpr bool kArgsByValue = TEAM == 2 || MIT == -2 || (MIT == 0 && TEAM == 0) || (TEAM == 1 && MAXD == 2);
+    constexpr bool kArgsByValue = MIT == -2 || (MIT == 0 && TEAM == 0) || (TEAM == 1 && MAXD == 2);
+    constexpr bool kArgsSplit = kGrow;
 #endif
     const StepArgs &a = kArgsByValue ? a_by_value : *(const StepArgs *)__builtin_amdgcn_kernarg_segment_ptr();
+    const StepArgs &ah = kArgsSplit ? a_by_value : a;      // the words every step looks at: team_recut, xg, xbuf, xrow (and the geometry)
     extern __shared__ uint4 s_dyn[];
-    const Geo &g = a.g;
+    const Geo &g = ah.g;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n_waves = blockDim.x >> 6, nthr = blockDim.x;
     int e_ = 0, tm_ = 0, tn_ = 1;
     bool no_work = false;
     if (TEAM) {
         const uint32_t tt = a.team_tab[blockIdx.x];
-        if (tt == kTeamUnused) { if (TEAM != 2) return; no_work = true; }      // (TEAM = 2: a slot without an environment looks for a team to join)
+        if (tt == kTeamUnused) { if (!kGrow) return; no_work = true; }      // (TEAM = 2: a slot without an environment looks for a team to join)
         else { e_ = (int)(tt & 0xFFFFu); tm_ = (int)((tt >> 16) & 0xFFu); tn_ = (int)(tt >> 24); }
     } else if (a.todo_cnt) {
         // behind k_win: only the environments whose fires outgrew their windows have anything left - most workgroups leave here, after one
@@ -470,7 +495,7 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
     int j_s0 = -1;            // TEAM = 2: >= 0 - this workgroup JOINS environment e_ as member tm_ of a team of tn_ in front of update j_s0
     // TEAM = 2: a workgroup serves one environment after the other (find_team below); everything else: one pass
     for (bool first_pass = true;; first_pass = false) {
-    if (TEAM == 2 && (!first_pass || no_work)) {
+    if (kGrow && (!first_pass || no_work)) {
         if (a.team_recut >= n_steps_launch) return;                 // (no cut inside this launch: nobody is taken in anywhere)
         uint32_t *sc = reinterpret_cast<uint32_t *>(s_dyn);        // (scratch: the LDS of a pass that is over)
         JoinArgs ja;
@@ -511,7 +536,7 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
     // of its own: nothing told the compiler that the outputs of the first were not ready before the second - ADVICE r5); a load that a launch
     // has no use for asks for the environment's state once more.)
     constexpr bool kWinPre = (MIT == 0 || MIT == -1) && MAXD == 1 && TEAM == 0;
-    constexpr bool kWinAny = ((MIT == 0 && MAXD <= 2) || (MIT == -1 && MAXD == 1 && TEAM == 0 && DIAG == 1)) && TEAM != 2;
+    constexpr bool kWinAny = ((MIT == 0 && MAXD <= 2) || (MIT == -1 && MAXD == 1 && TEAM == 0 && DIAG == 1)) && !kGrow;
     constexpr bool kWinAdvice = kWinAny && !(MAXD == 1 && TEAM == 0);      // (the window code's general path: sf_win_kernels.h, ADV)
     unsigned long long pre_w = 0ull, hint_v = 0ull;
     int32_t todo_v = 0;
@@ -556,7 +581,7 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
     // (and, on one-word rows without teams, with control lines inside the launch - sf_step_mitigated, up to 64 points per step: C5)
     // (not where teams grow inside the launch, TEAM = 2: calls of hundreds of updates, of which a window saves the first 25 some 3 us each - and
     // the window code and the team code in one body spill 450 SGPRs and 68 VGPRs)
-    constexpr bool kWin = ((MIT == 0 && MAXD <= 2) || (MIT == -1 && MAXD == 1 && TEAM == 0 && DIAG == 1)) && TEAM != 2;
+    constexpr bool kWin = ((MIT == 0 && MAXD <= 2) || (MIT == -1 && MAXD == 1 && TEAM == 0 && DIAG == 1)) && !kGrow;
     constexpr int kWinGen = (MAXD == 1 && TEAM == 0) ? 0 : 1;
     constexpr int kWinMit = MIT == -1 ? 1 : 0;
     int32_t px = 0, py = 0, pty = 0;       // control lines inside the launch: lane i of the LAST wave holds point i of the coming step
@@ -589,7 +614,7 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
         if (a.counters && tid == 0 && s_begin)           // (statistics slot 8: updates made inside a window - a slot of its own, whatever the instantiation)
             atomicAdd(a.counters + (size_t)((blockIdx.x * 16) & (kCounterShards - 1)) * kCounterRow + 8, (unsigned long long)s_begin);
     }
-    if (TEAM == 2 && j_s0 >= 0) s_begin = j_s0;          // a workgroup that joins: the team's next update (st: what member 0 left in commit[] at the cut)
+    if (kGrow && j_s0 >= 0) s_begin = j_s0;          // a workgroup that joins: the team's next update (st: what member 0 left in commit[] at the cut)
     const bool general = !kWin || (TEAM && tn > 1) || (s_begin < n_steps && (st.running || mit));       // (uniform) the bitmaps in LDS, the loop over the vector list
     if (TEAM == 0 && kWin && MIT == 0 && !general) {       // (sf_step's kernels: with control lines inside the launch the same lines cost C5's kernel 2 % - its code moved)
         // A launch that never leaves the window phase - every launch of the driver's window - hands its environment back HERE: the general
@@ -704,13 +729,13 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
     // write-through), loads that skip the L1 - ~1 us instead of the ~4 - 5 us of a written-through hand-off between busy CUs.  This is
     // found out at run time from the hardware's XCC id, never assumed from the slot number: either path is correct wherever the
     // members sit.  (Third granule of every member: {1, XCC id}; also the team's start line.)
-    if (TEAM == 2 && tm == 0 && j_s0 < 0 && tid == 0)           // (the board: where this environment's members sit)
+    if (kGrow && tm == 0 && j_s0 < 0 && tid == 0)           // (the board: where this environment's members sit)
         __hip_atomic_store(a.xj + 2 * g.E + 2 + e, (uint32_t)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)) & 15u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // What a team's members hand each other through memory at a cut: released / acquired at agent scope (write-back and invalidation of the
     // XCD's L2) - unless they are known to sit on ONE XCD (TEAM = 2, join_local = 1): the L1 is write-through, so a store that has been
     // acknowledged is in the L2 they share - no write-back of the L2 - and only the reader's L1 can be stale.
     auto team_release = [&]() {
-        if (TEAM == 2 && a.join_local == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (kGrow && a.join_local == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         else __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     };
     auto team_acquire = [&]() { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); };      // (drops the CU's L1; this device's memory is never stale in an L2)
@@ -835,8 +860,8 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
     if (TEAM && tn > 1) {
         // the team's start line (nobody writes before everybody has loaded its band and halo rows); a workgroup that has JOINED lines up with
         // the team behind its cut
-        if (wave == 0) line_up(TEAM == 2 && j_s0 >= 0 ? 2u + (uint32_t)(j_s0 / a.team_recut) : 1u, TEAM == 2 && j_s0 >= 0);
-        if (TEAM == 2) __syncthreads();
+        if (wave == 0) line_up(kGrow && j_s0 >= 0 ? 2u + (uint32_t)(j_s0 / a.team_recut) : 1u, kGrow && j_s0 >= 0);
+        if (kGrow) __syncthreads();
     }
 
     RunEnv ev;
@@ -1317,14 +1342,22 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
             // retires the walk's last stores: one in-order counter).  (Reading a neighbour vector before or after the
             // current batch rewrites it makes no difference: in-place update, see above.)
             struct VecIn { uint32_t item; uint4 up, mid, dn, sr; uint32_t l0, l1, l2, r0, r1, r2; };
-            // (a young fire's one or two batches: wave w takes batch w, no round trip to the cursor on the way - driver window - 3 %; longer
-            // lists are handed out by the cursor from the start: dealing the first round out by wave number cost C4 and the 1024-environment
-            // batch 5 - 8 %)
-            const bool dealt = n_waves == 16 && n_chunk <= 2u * (uint32_t)bsz;      // (16 waves = alone on its CU: with two workgroups per CU "always wave 0" means both on one SIMD)
+            // (a list of ONE ROUND - no more batches than waves, a team member's normal state and every young fire's -: wave w takes batch w
+            // and knows that no second one exists; neither of the two returning LDS atomics per wave and step is made - the first `grab`, and the
+            // one for a next batch that is not there - and the cursor word ctl[6 + k] stays at the zero the ring's reset gave it.  Longer lists
+            // are handed out by the cursor from the start: dealing the first round of a multi-round list out by wave number cost C4 and the
+            // 1024-environment batch 5 - 8 %.  NOTEBOOK.md 5.18; round 6 dealt only lists of one or two batches.)
+#ifdef SF_NO_ONE_ROUND
+            const bool one_round = n_waves == 16 && n_chunk <= 2u * (uint32_t)bsz;      // (profiles/: the A / B build - round 7's rule)
+            const uint32_t grab_off = one_round ? (uint32_t)(n_waves * bsz) : 0u;
+#else
+            const bool one_round = n_waves == 16 && n_chunk <= (uint32_t)(n_waves * bsz);      // (16 waves = alone on its CU: with two workgroups per CU "always wave 0" means both on one SIMD)
+            constexpr uint32_t grab_off = 0u;
+#endif
             auto grab = [&]() {
                 uint32_t j = 0;
                 if (lane == 0) j = atomicAdd(&ctl[6 + k], (uint32_t)bsz);
-                return (uint32_t)__builtin_amdgcn_readfirstlane((int)j) + (dealt ? (uint32_t)(n_waves * bsz) : 0u);
+                return (uint32_t)__builtin_amdgcn_readfirstlane((int)j) + grab_off;
             };
             auto fetch = [&](uint32_t j0, VecIn &in) {
                 const bool has = lane < bsz && j0 + lane < n_chunk;
@@ -1363,16 +1396,36 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
                 // (TEAM: for a band's first / last row the `far` row loaded here belongs to a neighbour and is replaced by the LDS halo row
                 // where the rows are consumed, at the top of `batch` - replacing it here would wait for the loads)
             };
-            const uint32_t j_first = dealt ? (uint32_t)(wave * bsz) : grab();
+            // (the wave number is uniform, which the compiler does not know: told so in the kernel whose teams grow, the batch loop's counters
+            // live in scalar registers and its branches are scalar; the other kernels were not measured with it and keep their code -
+            // the closed loop's would spill 18 vector registers)
+            const uint32_t j_first = one_round ? (kGrow ? (uint32_t)__builtin_amdgcn_readfirstlane(wave * bsz) : (uint32_t)(wave * bsz)) : grab();
             pc.note(16);     // first batch known
             // (two sets of rows that change roles from batch to batch - the loop below is unrolled by two where the registers allow -: "this
             // batch's rows = the rows requested during the batch before" as a copy is 46 register moves per batch; C3 - 1.4 %)
+            // (two sets where the registers allow it: the plain kernels on one-word rows, and - since its argument block is split and its
+            // statistics are gone, which gave it the registers: 128 VGPRs, no scratch - k_run<1, 0, 1, 0, 2>, whose teams grow.  With attenuation
+            // that kernel spills 33 vector registers unrolled, with the statistics 6: they stay on the copy.  NOTEBOOK.md 5.18)
+#ifdef SF_NO_UNROLL_TEAM2
+            constexpr bool kTwoSets = TEAM == 0 && MAXD == 1;          // (profiles/: the A / B build - round 7's rule)
+#else
+            constexpr bool kTwoSets = (TEAM == 0 || (kGrow && !kStats)) && MAXD == 1;
+#endif
             VecIn vin_a, vin_b;
             if (j_first < n_chunk) fetch(j_first, vin_a);
             pc.note(17);     // its rows requested
             auto batch = [&](const VecIn &cur, const uint32_t j0, VecIn &nxt, uint32_t &j_next) __attribute__((always_inline)) {
-                // (a batch that reaches the end of the list was the last one: no need to ask the cursor again)
+                // (a batch that reaches the end of the list was the last one: no need to ask the cursor again; nor in a list of one round)
+#ifdef SF_NO_ONE_ROUND
                 j_next = j0 + (uint32_t)bsz < n_chunk ? grab() : n_chunk;
+#else
+                j_next = !one_round && j0 + (uint32_t)bsz < n_chunk ? grab() : n_chunk;
+#endif
+                // (the team kernel's unrolled loop: this batch's rows are waited for HERE, where the copy of the other form made the wave wait
+                // for them - left to itself the compiler sinks that wait behind the prefetch, on the path that has none, and the path that
+                // has one then waits for the next batch's rows as well: tests/test_batch_prefetch_isa_cpu.py)
+                if (kGrow && kTwoSets)
+                    asm volatile("" :: "v"(cur.mid.x), "v"(cur.sr.x), "v"(cur.up.x), "v"(cur.dn.x), "v"(cur.l0), "v"(cur.l1), "v"(cur.l2), "v"(cur.r0), "v"(cur.r1), "v"(cur.r2));
                 pc.note(18); // next batch known
                 // (the team kernel for two-word rows has no registers for two batches' rows at once - it would spill 16 of them to
                 // scratch -: it asks for the next batch's rows when it is done with this one's)
@@ -1411,7 +1464,7 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
                 }
                 const uint32_t item_l = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)item, 0x138, 0xF, 0xF, false);   // wave_shr:1
                 const uint32_t item_r = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)item, 0x130, 0xF, 0xF, false);   // wave_shl:1
-                n_vec_done += (lane == 0) ? (n_chunk - j0 < (uint32_t)bsz ? n_chunk - j0 : (uint32_t)bsz) : 0u;
+                if (kStats) n_vec_done += (lane == 0) ? (n_chunk - j0 < (uint32_t)bsz ? n_chunk - j0 : (uint32_t)bsz) : 0u;
                 const uint4 midL = and4(mid, L4);
                 const uint4 vsrc = and4(or4(up, dn), L4);
                 const uint4 hsrc = diag ? or4(midL, vsrc) : midL;
@@ -1547,13 +1600,11 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
                     __builtin_amdgcn_wave_barrier();
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
                     pc.mark(6);  // prefix sum
-                    const WalkAcc wk = run_walk<ATT, loop ? 1 : 0>(a, ev, mk, st.complete, lo_mask, hi_mask, strips, total, lane, th_log, pc, excl, m16 | (line16 << 16), s7n);
-                    n_active += wk.n_active;
-                    n_ignite += wk.n_ignite;
+                    const WalkAcc wk = run_walk<ATT, loop ? 1 : 0>(g, ev, mk, st.complete, lo_mask, hi_mask, strips, total, lane, th_log, pc, excl, m16 | (line16 << 16), s7n);
+                    if (kStats) { n_active += wk.n_active; n_ignite += wk.n_ignite; }
                     if (loop && wk.n_ignite && lane == 0) { atomicAdd(ev.tot + SF_UNBURNED, -(int32_t)wk.n_ignite); atomicAdd(ev.tot + SF_BURNING, (int32_t)wk.n_ignite); }
                     if (wk.cand && lane == 0) reinterpret_cast<uint8_t *>(ctl + 3 + k)[1] = 1;                 // FLAG_CAND
-                    n_items_acc += (lane == 0) ? total : 0u;
-                    n_phase2++;
+                    if (kStats) { n_items_acc += (lane == 0) ? total : 0u; n_phase2++; }
                 } else {
                     // (the strip buffer is rewritten by the next batch: order this batch's LDS traffic before it)
                     __builtin_amdgcn_wave_barrier();
@@ -1561,7 +1612,7 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
                 pc.mark(10);
                 if (!kEarly && j_next < n_chunk) fetch(j_next, nxt);
             };
-            if (TEAM == 0 && MAXD == 1) {
+            if (kTwoSets) {
                 for (uint32_t ja = j_first; ja < n_chunk;) {
                     uint32_t jb;
                     batch(vin_a, ja, vin_b, jb);
@@ -1592,19 +1643,19 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
         // member's granule it ACQUIRES, cuts the bands from the global bitmap like the prologue - every member the same cut from
         // the same data -, loads its new band and lines up once more (a member that started the next step early would be writing
         // rows whose old contents a slower one is still loading as its halo).
-        const bool cut_step = TEAM && a.team_recut > 0 && (s + 1) % a.team_recut == 0 && s + 1 < n_steps;      // (uniform over the team)
+        const bool cut_step = TEAM && ah.team_recut > 0 && (s + 1) % ah.team_recut == 0 && s + 1 < n_steps;      // (uniform over the team)
         const bool recut_now = cut_step && tn > 1;
         // TEAM = 2, teams that GROW: workgroups whose environment is done have put their names down for this one (xj[e], find_team); at a cut
         // member 0 looks how many there are and what its own updates have cost since the last cut (the board the others choose from), and
         // tells the team with its granule of this update; a team of ONE asks at the same updates and becomes a team when somebody waits.
         int tn_new = tn;
-        if (TEAM == 2 && cut_step) {
+        if (kGrow && cut_step) {
             if (tm == 0 && tid == 0) {
                 const uint32_t c = __hip_atomic_load(a.xj + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 0xFFu;
                 const uint32_t t_cap = (uint32_t)(kTeamMax < g.TY ? kTeamMax : g.TY);          // (every member owns a tile row at least)
                 ctl[20] = c > t_cap ? t_cap : (c < (uint32_t)tn ? (uint32_t)tn : c);
                 const unsigned long long now = __builtin_readcyclecounter();
-                long long per = (long long)((now - join_clk) / (unsigned long long)a.team_recut);     // what an update costs this member
+                long long per = (long long)((now - join_clk) / (unsigned long long)ah.team_recut);     // what an update costs this member
                 join_clk = now;
                 if (tn > 1) per = (per - a.join_ovh) * tn;                // ... and the team as a whole
                 if (per < a.join_floor) per = a.join_floor;
@@ -1619,7 +1670,7 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
             team_release();
             __syncthreads();
         }
-        if (TEAM == 2 && cut_step && tm == 0) tn_new = __builtin_amdgcn_readfirstlane((int)ctl[20]);
+        if (kGrow && cut_step && tm == 0) tn_new = __builtin_amdgcn_readfirstlane((int)ctl[20]);
         if (TEAM && tn > 1) {
             // ---- the team's step boundary: publish this member's boundary rows and predicates, wait for every member's, take the
             // neighbours' rows into the LDS halo (wave 0; the other waves wait at the barrier below)
@@ -1629,9 +1680,9 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
                 // invariants otherwise, and the compiler keeps them in VGPRs across the whole step loop, where they are what gets spilled)
                 int lane = threadIdx.x & 63;
                 asm volatile("" : "+v"(lane));
-                const unsigned long long xt0 = a.counters ? __builtin_readcyclecounter() : 0ull;
+                const unsigned long long xt0 = kStats && a.counters ? __builtin_readcyclecounter() : 0ull;
                 const uint32_t epoch = (uint32_t)s + 1u, par = (uint32_t)s & 1u;
-                uint8_t *xb_me = a.xbuf + ((size_t)(e * kTeamMax + tm) * 4) * (size_t)a.xrow;      // [side][parity][xrow]
+                uint8_t *xb_me = ah.xbuf + ((size_t)(e * kTeamMax + tm) * 4) * (size_t)ah.xrow;      // [side][parity][xrow]
                 // Members on ONE XCD (one_l2): nothing is copied.  A member's boundary rows ARE in the L2 the team shares once its waves' stores are
                 // acknowledged (above), and the neighbour reads them there (below) - two L2 round trips (granules, rows) instead of four (own rows,
                 // the copy acknowledged, granules, the copy).  What it may see beyond the step's state - the owner is at most one step ahead - are bits
@@ -1639,7 +1690,7 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
                 for (int side = 0; side < 2 && !one_l2; ++side) {
                     if (!(side ? has_dn : has_up)) continue;           // (uniform)
                     const int yb = side ? R1 - 1 : R0;                 // my last row is the row above the band below, my first row the row below the band above
-                    u64 *dst = reinterpret_cast<u64 *>(xb_me + (size_t)(side * 2 + par) * a.xrow);
+                    u64 *dst = reinterpret_cast<u64 *>(xb_me + (size_t)(side * 2 + par) * ah.xrow);
                     for (int v = lane; v < g.PV; v += 64)
                         if ((vb[yb * VW + (v >> 6)] >> (v & 63)) & 1ull) {       // (vectors without a sprite bit are zero: the reader knows from the bitmap word)
                             const uint4 val = *reinterpret_cast<const uint4 *>(ev.cells + bl_vec(g, yb, v) + (yb & 1) * 16);
@@ -1658,16 +1709,16 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
                 }
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the rows are acknowledged (by the L2 / written through) ...
                 if (lane == 0) {                                        // ... before the one tagged word that says so
-                    const u64 gv = ((u64)epoch << 32) | (u64)(ctl[3 + k] & 0xFFFFu) | (TEAM == 2 ? (u64)tn_new << 16 : 0ull);       // (member 0's: the team's size from the next update on)
-                    if (one_l2) __hip_atomic_store(a.xg + ((size_t)e * kTeamMax + tm) * 3 + par, gv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    else __hip_atomic_store(a.xg + ((size_t)e * kTeamMax + tm) * 3 + par, gv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    const u64 gv = ((u64)epoch << 32) | (u64)(ctl[3 + k] & 0xFFFFu) | (kGrow ? (u64)tn_new << 16 : 0ull);       // (member 0's: the team's size from the next update on)
+                    if (one_l2) __hip_atomic_store(ah.xg + ((size_t)e * kTeamMax + tm) * 3 + par, gv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    else __hip_atomic_store(ah.xg + ((size_t)e * kTeamMax + tm) * 3 + par, gv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
                 // every member's granule of this step (a member can be one step ahead at most: two granules by parity)
                 u64 x = (u64)epoch << 32;
                 {
                     const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
                     for (;;) {
-                        if (lane < tn) x = __hip_atomic_load(a.xg + ((size_t)e * kTeamMax + lane) * 3 + par, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // (skips the L1)
+                        if (lane < tn) x = __hip_atomic_load(ah.xg + ((size_t)e * kTeamMax + lane) * 3 + par, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // (skips the L1)
                         if (__all((uint32_t)(x >> 32) == epoch)) break;
                         __builtin_amdgcn_s_sleep(1);
                         if (gave_up || __builtin_amdgcn_s_memrealtime() - t0 > a.team_timeout) {       // (bounded - wall clock, SF_TUNE_TEAM_TIMEOUT_MS, 2 s by default: a lost member must not hang the GPU)
@@ -1679,7 +1730,7 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
                 }
                 const bool live_any = __ballot(lane < tn && (x & 0xFFull)) != 0ull, cand_any = __ballot(lane < tn && (x & 0xFF00ull)) != 0ull;
                 if (lane == 0) ctl[3 + k] = (live_any ? FLAG_LIVE : 0u) | (cand_any ? FLAG_CAND : 0u);     // fire.py:637, 651: over the whole environment
-                if (TEAM == 2 && cut_step && lane == 0) ctl[20] = (uint32_t)(x >> 16) & 0xFFu;             // (lane 0 holds member 0's granule)
+                if (kGrow && cut_step && lane == 0) ctl[20] = (uint32_t)(x >> 16) & 0xFFu;             // (lane 0 holds member 0's granule)
                 for (int side = 0; side < 2 && one_l2; ++side) {
                     if (!(side ? has_dn : has_up)) continue;
                     const int yh = side ? R1 : R0 - 1;
@@ -1700,7 +1751,7 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
                 for (int side = 0; side < 2 && !one_l2; ++side) {
                     if (!(side ? has_dn : has_up)) continue;
                     const int nj = side ? tm + 1 : tm - 1, yh = side ? R1 : R0 - 1;
-                    const u64 *src = reinterpret_cast<const u64 *>(a.xbuf + ((size_t)(e * kTeamMax + nj) * 4 + (size_t)((side ^ 1) * 2 + par)) * a.xrow);
+                    const u64 *src = reinterpret_cast<const u64 *>(ah.xbuf + ((size_t)(e * kTeamMax + nj) * 4 + (size_t)((side ^ 1) * 2 + par)) * ah.xrow);
                     u64 word = 0;
                     if (lane < 3 * VW) word = __hip_atomic_load(src + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     for (int v0 = 0; v0 < g.PV; v0 += 64) {
@@ -1723,7 +1774,7 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
                         (which == 0 ? vb : (which == 1 ? vf : vl))[yh * VW + w] = word;
                     }
                 }
-                if (a.counters && lane == 0) { x_clocks += __builtin_readcyclecounter() - xt0; x_steps++; }
+                if (kStats && a.counters && lane == 0) { x_clocks += __builtin_readcyclecounter() - xt0; x_steps++; }
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");       // (what the others read next is all in LDS)
             __builtin_amdgcn_s_barrier();
@@ -1736,16 +1787,16 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
         st.complete = __builtin_amdgcn_readfirstlane(st.complete);
         st.time_quit = __builtin_amdgcn_readfirstlane(st.time_quit);
         if (loop) loop_finish();
-        if (TEAM == 2 && cut_step && tn > 1) tn_new = __builtin_amdgcn_readfirstlane((int)ctl[20]);      // (behind the barrier of the step boundary)
-        if (TEAM == 2 && gave_up) tn_new = tn;
+        if (kGrow && cut_step && tn > 1) tn_new = __builtin_amdgcn_readfirstlane((int)ctl[20]);      // (behind the barrier of the step boundary)
+        if (kGrow && gave_up) tn_new = tn;
         if ((recut_now || tn_new > tn) && (st.running || mit)) {
-            if (TEAM == 2 && tn == 1) {
+            if (kGrow && tn == 1) {
                 // a team of one takes members: what a team does in front of its step boundary - the bitmaps back to memory, everything released
                 store_band();
                 team_release();
                 __syncthreads();
             }
-            if (TEAM == 2 && tn_new > tn && tm == 0 && tid == 0) {
+            if (kGrow && tn_new > tn && tm == 0 && tid == 0) {
                 // every member's rows are in memory and released (their granules of this update came behind that): the newcomers may read.
                 // The state they start from, then the word they wait for.
                 a.commit[e] = st;
@@ -1756,19 +1807,19 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
                 if (li < (uint32_t)kJoinLog) { a.jlog[1 + 3 * li] = (uint32_t)e; a.jlog[2 + 3 * li] = (uint32_t)(s + 1); a.jlog[3 + 3 * li] = (uint32_t)tn_new; }
             }
             team_acquire();
-            if (TEAM == 2) { tn = tn_new; has_up = tm > 0; has_dn = tm + 1 < tn; }
+            if (kGrow) { tn = tn_new; has_up = tm > 0; has_dn = tm + 1 < tn; }
             const int left = n_steps - (s + 1);
-            cut_bands(a.team_recut < left ? a.team_recut : left);        // (fits: the host offers this only where t_min members hold the whole grid)
+            cut_bands(ah.team_recut < left ? ah.team_recut : left);        // (fits: the host offers this only where t_min members hold the whole grid)
             load_band();
             ev.vb = vb; ev.vf = vf; ev.vl = vl;
             rpt = (R1 - R0 + nthr - 1) / nthr;
             row0 = R0;
             __syncthreads();
-            if (wave == 0) line_up(2u + (uint32_t)((s + 1) / a.team_recut), true);      // the second line-up: nobody writes before everybody has loaded
+            if (wave == 0) line_up(2u + (uint32_t)((s + 1) / ah.team_recut), true);      // the second line-up: nobody writes before everybody has loaded
             __syncthreads();
         }
     }
-    if (TEAM == 2 && tm == 0 && tid == 0) {
+    if (kGrow && tm == 0 && tid == 0) {
         // this environment takes no more members: whoever waits for a place is sent on, whoever looks for one does not look here
         atomicOr(a.xj + e, kJoinClosed);
         __hip_atomic_store(a.xcut + e, ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1811,7 +1862,7 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
             }
     }
     wpc.note(49);            // state committed, bitmaps handed back
-    if (a.counters && lane == 0) {
+    if (kStats && a.counters && lane == 0) {
         // (the wave number through an opaque copy: the address is then worked out here, once per launch, and not ahead of the step loop,
         // where it held two vector registers through every batch - in the kernels at the register cap, two spilled ones)
         int cw = wave;
@@ -1843,7 +1894,7 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
         }
         __syncthreads();
         if (!ctl[0]) {             // (uniform)
-            if (TEAM == 2) continue;       // (on to the next environment that can use a workgroup)
+            if (kGrow) continue;       // (on to the next environment that can use a workgroup)
             return;
         }
     }
@@ -1857,7 +1908,7 @@ __global__ __launch_bounds__(1024) void k_run(StepArgs a_by_value, const int n_s
         wpc.note(37);        // result block written
     }
     }
-    if (TEAM != 2) return;
+    if (!kGrow) return;
     }
 }
 

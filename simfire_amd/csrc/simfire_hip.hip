@@ -747,7 +747,7 @@ static RunKey run_key(const Geo &g, RunKind kind, int words, bool lines)
 {
     const int att = g.att ? 1 : 0, diag = g.diag ? 1 : -1;
     switch (kind) {
-    case kRunJoin: return {1, att, 1, 0, 2};                      // (one-word rows, diagonal spread, no control lines inside the launch)
+    case kRunJoin: return {1, att, 1, 0, 2};                      // (one-word rows, diagonal spread, no control lines inside the launch; launch_k_run_join: TEAM = 3 with the counters on)
     case kRunLoop: return {words, att, -1, -2, 0};                // (the closed loop looks diagonal spread up at run time)
     // teams: diagonal spread on, no control lines inside the launch on two-word rows = BASELINE config C4: its own instantiations, without the
     // control-line code and its registers; one-word teams look control lines up at run time
@@ -943,7 +943,11 @@ static int launch_k_run_join(sf_sim *s, StepArgs &a, int n_steps, const TeamGeo 
     const int place = s->tune.v[SF_TUNE_TEAM_PLACEMENT];
     a.join_local = place == 1 ? 0 : (place == 2 ? 2 : 1);
     a.join_floor = eager ? 0 : 12000; a.join_ovh = eager ? 0 : (a.join_local == 1 ? 3000 : 12000);
-    return launch_run(s, run_key(g, kRunJoin, 1, false), (unsigned)t.slots, (unsigned)t.waves * 64, t.lds, a, n_steps, t.vcap, 64);
+    // (counters on: the instantiation that keeps the statistics, TEAM = 3, where TEAM = 2 is built without them - sf_run_kernels.h)
+    RunKey key = run_key(g, kRunJoin, 1, false), counted = key;
+    counted.team = 3;
+    if (a.counters && run_fn(counted)) key = counted;
+    return launch_run(s, key, (unsigned)t.slots, (unsigned)t.waves * 64, t.lds, a, n_steps, t.vcap, 64);
 }
 
 

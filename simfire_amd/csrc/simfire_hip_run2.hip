@@ -22,7 +22,8 @@ RunTable sf_run2_table()
         // teams on one-word rows: [attenuation][diagonal spread read at run time / known to be on]
         SF_RUN_ENTRY(1, 0, -1, -1, 1), SF_RUN_ENTRY(1, 0, 1, -1, 1), SF_RUN_ENTRY(1, 1, -1, -1, 1), SF_RUN_ENTRY(1, 1, 1, -1, 1),
         // teams that grow inside the launch: one-word rows, diagonal spread, no control lines inside the launch
-        SF_RUN_ENTRY(1, 0, 1, 0, 2), SF_RUN_ENTRY(1, 1, 1, 0, 2),
+        // (the first without the statistics of sf_get_counters - bench.py's kernel - and once more with them, TEAM = 3, for handles with the counters on)
+        SF_RUN_ENTRY(1, 0, 1, 0, 2), SF_RUN_ENTRY(1, 0, 1, 0, 3), SF_RUN_ENTRY(1, 1, 1, 0, 2),
         // the closed loop of sf_loop_start: one workgroup per environment, steps until the host's stop
         // (diagonal spread is looked up at run time: the two instantiations that knew it at compile time were retired in round 6 for k_win's two -
         // a select or two per batch in a call whose time is the signalling between host and device)
