@@ -6,6 +6,7 @@
 // one and then makes its own adjustment of `bytes`.
 #pragma once
 #include "sf_tables.h"
+#include "sf_planes.h"
 
 // ------------------------------------------------------------------------------- errors
 static thread_local std::string g_err;
@@ -269,6 +270,8 @@ struct BehaviorState {
 }  // namespace
 
 // ----------------------------------------------------------------------------- handle
+// The step path's buffers and knobs stand flat in the handle; which cell layout is current and which structures derived from it still
+// match it - the step path's coherence state - is the PlaneBook's (planes, sf_planes.h), as the per-table flags are the TableBook's.
 struct sf_sim {
     sf_params p;
     Geo g;
@@ -276,7 +279,6 @@ struct sf_sim {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     uint8_t *status = nullptr, *age_alloc = nullptr, *age = nullptr;
     uint8_t *cells_alloc = nullptr, *cells = nullptr;      // blocked cell plane of the resident launch (allocated at its first use)
-    bool bl_cur = false;               // the blocked plane holds the sprite masks / status bytes; the row-major planes are stale
     double *burn = nullptr, *rt = nullptr;
     mutable std::map<std::tuple<const void *, unsigned, size_t>, int> occ_cache;      // k_run instantiations: workgroups per CU by hipOccupancyMaxActiveBlocksPerMultiprocessor (occupancy)
     double *rtc = nullptr;             // the R table(s) cell-major (k_rt_cellmajor): built when the resident launch first needs it, stale after every change of rt (TableBook)
@@ -284,6 +286,7 @@ struct sf_sim {
     double *lay_all = nullptr;         // [tables][7][H*W] dense: w0 delta Mx sigma elev U Udir (kept for the observation planes)
     double *layer(int table, int i) const { return lay_all + ((size_t)table * 7 + i) * (size_t)g.H * g.W; }
     TableBook tables;                  // per terrain table: what has been supplied, what is stale (sf_tables.h)
+    PlaneBook planes;                  // which cell layout is current, what derived from it still matches it (sf_planes.h)
     int8_t *history = nullptr;         // sf_enable_history: [E][history_cap][H][W] fire maps after each update
     int history_cap = 0;
     double *smag = nullptr, *sdir = nullptr;
@@ -304,9 +307,7 @@ struct sf_sim {
     uint16_t *thist = nullptr;         // per wave tile: cells per BurnStatus 1..5 (u16 [tiles][8])
     size_t n_tiles_max = 0;
     void *status_pinned = nullptr;     // pinned landing zone of the result block (int32 [E][8] + double [E])
-    bool status_fresh = false;         // status_block / elapsed_dev (and the sink) hold the current result block: the resident launch wrote it
     int32_t *sink = nullptr;           // sf_set_result_sink: caller-owned device copy of the result block, written by every refresh
-    bool tdirty_all = true;            // every histogram is stale (reset, fire_map replaced, geometry changed, per-cell kernel ran)
     int last_launches = 0;             // k_run launches of the last step call (sf_get_last_launches)
     // run(1) loops (one update per call, the result block looked at after each - FireSimulation.run(1) in a harness): after two such
     // pairs in a row the single update runs as the resident launch too, which leaves the block behind itself (measured, step(1) +
@@ -314,14 +315,7 @@ struct sf_sim {
     // looks at the maps after each, is faster on the per-step kernels and keeps them)
     bool last_was_step1 = false;       // the last step call was one update and nothing has looked at its result yet
     int step1_polls = 0;               // step(1) + status pairs in a row
-    int fire_rows = 0;                 // no environment's fire spans more rows than this (0: not known): 1 after sf_reset, + 2 per update (a fire
-                                       // advances one row per update at most, fire.py:163-234), the grid's height after sf_load_fire_map
     unsigned long long *vbits = nullptr;   // vector bitmap of the resident launch (k_run)
-    bool vbits_valid = false;          // vbits matches the sprite-mask planes (k_run / reset keep it; the per-step kernels do not)
-    bool vbits_fl_valid = true;        // ... planes 1 / 2 of it too (first / last cell of the vector holds a sprite bit): k_run on rows of several words keeps only
-                                       // plane 0 (plain dilation) unless it runs as teams - which need all three (rebuilt when a team launch follows such a launch)
-    bool tiles_valid = false;          // tile activity map + seam planes match them (the per-step tiled kernels keep them; k_run does not)
-    int last_kind = -1;                // launch structure of the last sf_step call: 0 k_select + k_step, 1 fused, 2 k_run, 3 per-cell
     int32_t *todo = nullptr;           // team launches with windows of rows: the steps an environment's team could not make (the catch-up launch's) [E]
     ncclComm_t comm = nullptr;         // sf_comm_init: communicator of the result-block all-gather
     int comm_world = 0;
@@ -347,10 +341,9 @@ struct sf_sim {
     int32_t *mit_stage = nullptr;      // sf_step_mitigated: device copy of a host point block / expanded rows of one step
     size_t mit_stage_bytes = 0;
     bool async = false;                // sf_set_async: calls that return no data do not synchronise
-    bool was_reset = false, counters_on = false;
+    bool counters_on = false;
     int seq = 0;                       // index (mod 6) of the next step launch
     Tuning tune;                       // sf_set_tuning
-    bool committed = true;             // commit[] is current (no step launch since the last k_commit / reset)
     int64_t bytes = 0;
     std::vector<int32_t> last_ign;     // the ignitions of the last sf_reset (host copy; sf_episodes_set)
     // the features, each with its own state
@@ -376,6 +369,16 @@ struct sf_sim {
     long long *val_tick(int i) const { return reinterpret_cast<long long *>(values.aux + (size_t)g.E * (sizeof(ValueRec) + 8 * i)); }      // 0: base, 1: loss
     uint32_t *val_bad() const { return reinterpret_cast<uint32_t *>(values.aux + (size_t)g.E * (sizeof(ValueRec) + 16)); }
 };
+
+// the blocked plane if it is the current one, else null: what a kernel that reads whichever layout is current takes as `cells`
+static uint8_t *cur_cells(const sf_sim *s) { return s->planes.blocked() ? s->cells : nullptr; }
+// In front of a launch that looks after the per-tile histograms: while every one is stale, say so on the device.
+static int mark_hist_dirty(sf_sim *s)
+{
+    if (s->planes.hist_all_stale()) HIPCHK(hipMemsetAsync(s->tdirty, 1, s->n_tiles_max, s->stream));
+    s->planes.hist_marked();
+    return SF_OK;
+}
 
 // The host code of the step path has two layers.  The ENQUEUE layer (enqueue_steps, enqueue_call, enqueue_pair, stage_lines, step_impl,
 // refresh_status, scatter_points, delta_enqueue, reset_launch, arrival_pass) puts work on the handle's stream and keeps the handle's
@@ -411,7 +414,7 @@ enum { kNeedRt = 1, kNeedReset = 2, kNotVoid = 4, kCommit = 8, kStateCall = kNee
 static int check_ready(const sf_sim *s, const char *who, int need)
 {
     if ((need & kNeedRt) && !s->tables.have_rt()) return fail(SF_ESTATE, "%s: call sf_set_layers or sf_set_rtable first", who);
-    if ((need & kNeedReset) && !s->was_reset) return fail(SF_ESTATE, "%s: call sf_reset first", who);
+    if ((need & kNeedReset) && !s->planes.was_reset()) return fail(SF_ESTATE, "%s: call sf_reset first", who);
     return SF_OK;
 }
 static int begin_call(sf_sim *s, const char *who, int need)

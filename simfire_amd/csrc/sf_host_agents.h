@@ -244,7 +244,7 @@ static AgentArgs agent_args(const sf_sim *s, const int32_t *actions, const sf_ag
     memset(&a, 0, sizeof a);
     a.g = s->g;
     a.status = s->status;
-    a.cells = s->bl_cur ? s->cells : nullptr;        // (whichever plane is current NOW: the step between the two kernels may change it)
+    a.cells = cur_cells(s);        // (whichever plane is current NOW: the step between the two kernels may change it)
     a.rows = s->status_block;
     a.actions = actions;
     a.xyid = s->agents.xyid; a.start = s->agents.start; a.points = s->agents.points; a.prev_cnt = s->agents.prev; a.terms = s->agents.terms;

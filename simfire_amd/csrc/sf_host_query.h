@@ -84,7 +84,7 @@ extern "C" int sf_distance(sf_sim *s, const sf_dist_params *p, int32_t n, const 
     memset(&a, 0, sizeof a);
     a.g = g;
     a.status = s->status;
-    a.cells = s->bl_cur ? s->cells : nullptr;
+    a.cells = cur_cells(s);
     a.gp = reinterpret_cast<uint16_t *>(d.mem);
     a.k = p->k;
     mask_tables(p->status_mask, a.tlo, a.thi);
@@ -126,7 +126,7 @@ static void band_args(const sf_sim *s, ReachArgs &r, const uint8_t *passable, in
     const Geo &g = s->g;
     r.g = g;
     r.status = s->status;
-    r.cells = s->bl_cur ? s->cells : nullptr;
+    r.cells = cur_cells(s);
     r.passable = passable;
     r.pass_env = per_env ? (long long)g.H * g.W : 0;
     r.pass_vec = passable && g.W % 16 == 0 && !((uintptr_t)passable & 15);
@@ -347,7 +347,7 @@ extern "C" int sf_behavior(sf_sim *s, const sf_behavior_params *p, const sf_beha
     a.H = g.H; a.W = g.W; a.P = g.P; a.PV = g.PV;
     a.plane_env = g.plane_env; a.rt_env = g.rt_env; a.cells_env = g.cells_env;
     a.status = s->status;
-    a.cells = s->bl_cur ? s->cells : nullptr;
+    a.cells = cur_cells(s);
     a.rt = s->rt;
     a.hpa = b.hpa;
     a.hpa_env = per_env ? (long long)g.H * g.W : 0;

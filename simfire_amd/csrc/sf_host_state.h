@@ -60,7 +60,7 @@ extern "C" int sf_copy_envs(sf_sim *s, const int32_t *src, const int32_t *dst, i
     }
     if (terrain && s->wind.sched_dev) wind_sched_count(s);
     if (s->values.per_env) SF_TRY(value_recount(s));
-    // (fire_rows bounds every environment's fire, dst's copy included; status_fresh: dst's row is src's current row)
+    // (the book's fire_rows bounds every environment's fire, dst's copy included; its row_fresh: dst's row is src's current row)
     return finish_call(s, nullptr, !s->async, nullptr);
 }
 
@@ -73,7 +73,7 @@ static StateHeader state_header(const sf_sim *s)
     h.bytes = state_layout(g, s->parents != nullptr, s->arrival.plane != nullptr).bytes;
     h.H = g.H; h.W = g.W; h.md = g.md; h.ab = g.ab;
     h.diag = g.diag; h.att = g.att; h.has_max_time = g.has_max_time; h.prune_after_quit = g.prune_after_quit;
-    h.has_parents = s->parents != nullptr; h.fire_rows = s->fire_rows; h.has_arrival = s->arrival.plane != nullptr;
+    h.has_parents = s->parents != nullptr; h.fire_rows = s->planes.fire_rows(); h.has_arrival = s->arrival.plane != nullptr;
     h.max_time = g.has_max_time ? g.max_time : 0.0; h.update_rate = g.update_rate; h.pixel_scale = g.pixel_scale;
     return h;
 }
@@ -113,7 +113,7 @@ static StateArgs state_args(sf_sim *s)
     StateArgs a;
     memset(&a, 0, sizeof a);
     a.g = s->g;
-    a.status = s->status; a.age = s->age; a.cells = s->bl_cur ? s->cells : nullptr;
+    a.status = s->status; a.age = s->age; a.cells = cur_cells(s);
     a.burn = s->burn; a.settled = s->settled; a.parents = s->parents; a.arrival = s->arrival.plane; a.vbits = s->vbits;
     a.commit = s->commit; a.res_block = s->status_block; a.res_sink = s->sink; a.res_elapsed = s->elapsed_dev;
     a.lay = state_layout(s->g, s->parents != nullptr, s->arrival.plane != nullptr);
@@ -137,14 +137,14 @@ static int reset_launch(sf_sim *s, const int32_t *envs_dev, const uint8_t *mask,
     ResetArgs a;
     memset(&a, 0, sizeof a);
     a.g = g;
-    const bool seams = !s->bl_cur && g.ab == 1;       // (the tile bookkeeping is not kept while the blocked plane is current: tiles_valid is false)
+    const bool seams = !s->planes.blocked() && g.ab == 1;       // (the tile bookkeeping is not kept while the blocked plane is current: PlaneBook)
     // the tile histograms of a reset environment are known (all UNBURNED, the ignition's tile to be recounted); a partial reset leaves
     // it at that while every histogram of the handle is marked stale anyway
-    const bool hist_known = g.ab == 1 && !s->generic && (full || !s->tdirty_all);
-    if (full) { s->status_fresh = true; s->cost_steps = 0; }      // every result row is written; the old episodes' costs (run_cost, zeroed) say nothing
+    const bool hist_known = g.ab == 1 && !s->generic && (full || !s->planes.hist_all_stale());
+    if (full) s->cost_steps = 0;       // the old episodes' costs (run_cost, zeroed) say nothing
     a.n_seg = value_seg(s, a.seg, arrival_seg(s, a.seg, env_segs(s, (kResetKinds & ~(seams ? 0u : kSegSeam) & ~(hist_known ? 0u : kSegHist)) | (full ? kSegCost : 0u), a.seg)));
     a.envs = envs_dev; a.mask = mask; a.xy = xy_dev; a.n = n;
-    a.status = s->status; a.age = s->age; a.cells = s->bl_cur ? s->cells : nullptr;
+    a.status = s->status; a.age = s->age; a.cells = cur_cells(s);
     a.commit = s->commit; a.tflags = s->tflags; a.ring = s->ring; a.vbits = s->vbits; a.win_hint = s->win_hint;
     a.seam = seams ? s->seam : nullptr;
     a.tdirty = hist_known ? s->tdirty : nullptr;
@@ -167,7 +167,7 @@ static int reset_launch(sf_sim *s, const int32_t *envs_dev, const uint8_t *mask,
     hipLaunchKernelGGL(k_reset_ignite, dim3((n + 255) / 256), dim3(256), 0, s->stream, a);
     HIPCHK(hipGetLastError());
     SF_TRY(lab_stop(s, s->reset_timer));
-    s->tdirty_all = !hist_known;
+    s->planes.reset_written(full, hist_known);      // (a full one: every result row is written)
     return arrival_pass(s);             // the ignitions are the sprites of update 0 (recording off: nothing)
 }
 // Host ignitions: every one on the grid, or SF_EINVAL in the words of the entry `who` (envs: whose they are, null = 0 .. n - 1).
@@ -201,15 +201,15 @@ extern "C" int sf_reset(sf_sim *s, const int32_t *init_xy)
     SF_TRY(begin_call(s, "sf_reset", kCommit));
     // everything is rewritten, nothing to convert: into the blocked plane if the resident launch is what steps this handle
     // (it did last, or nothing has stepped yet and it is the automatic choice), else into the row-major planes
-    const bool bl = prefers_bl(s) && (s->bl_cur || s->last_kind == 2 || s->last_kind == -1);
+    const bool bl = prefers_bl(s) && (s->planes.blocked() || s->planes.last_kind() == 2 || s->planes.last_kind() == -1);
     if (bl) SF_TRY(alloc_bl(s));
-    s->bl_cur = bl;
+    s->planes.reset_layout(bl);
     std::vector<int32_t> all((size_t)E);
     for (int e = 0; e < E; ++e) all[e] = e;
     SF_TRY(reset_list(s, all.data(), init_xy, E, true));
     SF_TRY(finish_call(s, nullptr, true, nullptr));
     s->last_ign.assign(init_xy, init_xy + (size_t)2 * E);      // (where a new episode ignites when sf_episodes_set draws no ignition)
-    s->was_reset = true; s->vbits_valid = true; s->vbits_fl_valid = true; s->tiles_valid = !s->bl_cur; s->fire_rows = 1;     // every environment freshly written
+    s->planes.reset_done();            // every environment freshly written
     if (s->team.xerr_pinned) *s->team.xerr_pinned = 0;      // (cells, bitmaps, states of every environment are new: what a failed team launch left is gone)
     return SF_OK;
 }
@@ -219,7 +219,7 @@ extern "C" int sf_reset_env(sf_sim *s, int32_t env, int32_t x, int32_t y)
 {
     if (!s) return fail(SF_EINVAL, "sf_reset_env: null handle");
     if (env < 0 || env >= s->g.E) return fail(SF_EINVAL, "sf_reset_env: environment %d out of range", env);
-    if (!s->was_reset) return fail(SF_ESTATE, "sf_reset_env: call sf_reset once first");
+    if (!s->planes.was_reset()) return fail(SF_ESTATE, "sf_reset_env: call sf_reset once first");
     const int32_t xy[2] = {x, y};
     SF_TRY(check_ignitions(s, "reset", 1, &env, xy));
     SF_TRY(begin_call(s, "sf_reset_env", kCommit));
@@ -325,18 +325,18 @@ extern "C" int sf_load_state(sf_sim *s, int32_t n, const int32_t *envs, const vo
     } else {
         for (int i = 0; i < n; ++i) memcpy(&hdr[i], static_cast<const uint8_t *>(in) + (size_t)i * bytes, sizeof(StateHeader));
     }
-    int fire_rows = 0;
+    int bound = 0;                     // the largest bound on a fire's rows the blobs carry (INT32_MAX: one carries none)
     for (int i = 0; i < n; ++i) {
         SF_TRY(header_check(s, hdr[i], i));
-        fire_rows = std::max(fire_rows, hdr[i].fire_rows > 0 ? hdr[i].fire_rows : INT32_MAX);
+        bound = std::max(bound, hdr[i].fire_rows > 0 ? hdr[i].fire_rows : INT32_MAX);
     }
     SF_TRY(begin_call(s, "sf_load_state", kStateCall));
     const Geo &g = s->g;
     StateArgs a = state_args(s);
     const int chunk = state_chunk(a, device_pointer != 0);
     if (!device_pointer) SF_TRY(ensure_stage(s, (size_t)chunk * a.stride));
-    const bool per_env_tiles = !s->bl_cur && s->tiles_valid;      // the tile maps / seams are kept: rebuild this environment's
-    const bool recount = g.ab == 1 && !s->generic && !s->tdirty_all;
+    const bool per_env_tiles = s->planes.tiles_kept();      // the tile maps / seams are kept: rebuild this environment's
+    const bool recount = g.ab == 1 && !s->generic && !s->planes.hist_all_stale();
     EnvSeg seg[kEnvSegs];
     const int n_seg = env_segs(s, kSegCells | kSegHint, seg);
     for (int i0 = 0; i0 < n; i0 += chunk) {
@@ -364,11 +364,10 @@ extern "C" int sf_load_state(sf_sim *s, int32_t n, const int32_t *envs, const vo
             }
         if (!device_pointer) HIPCHK(hipStreamSynchronize(s->stream));      // (the staging buffer is reused by the next pass)
     }
-    if (s->bl_cur) s->tiles_valid = false;
     SF_TRY(wind_forget(s, envs, n));      // (a scheduled environment's table stands for the update count it had: decided anew)
     for (int i = 0; i < n; ++i) if (s->delta.snap) s->delta.snap_valid[envs[i]] = 0;
-    // fire_rows bounds every environment's fire: the saving handle's bound covers a loaded one (a blob without one makes it unknown)
-    s->fire_rows = (s->fire_rows > 0 && fire_rows != INT32_MAX) ? std::max(s->fire_rows, fire_rows) : 0;
+    // the bound on the fires' rows covers every environment: the saving handle's covers a loaded one (a blob without one makes it unknown)
+    s->planes.state_loaded(bound != INT32_MAX ? bound : 0);
     SF_TRY(value_recount(s));      // section 20: the restored planes say what counts
     if (device_pointer && !s->async) HIPCHK(hipStreamSynchronize(s->stream));
     return SF_OK;

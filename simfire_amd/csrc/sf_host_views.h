@@ -12,13 +12,13 @@ static int arrival_pass(sf_sim *s)
     if (!s->arrival.plane) return SF_OK;
     { int rc0 = ensure_commit(s); if (rc0) return rc0; }
     const Geo &g = s->g;
-    const bool sparse = s->bl_cur && s->vbits_valid && s->vbits_fl_valid && !s->arrival.dense;
+    const bool sparse = s->planes.bits_cover_cells() && !s->arrival.dense;
     if (sparse) {
         hipLaunchKernelGGL(k_arrival_bits, dim3((unsigned)((g.H * g.VW + 255) / 256), (unsigned)g.E), dim3(256), 0, s->stream, g, (const uint8_t *)s->cells,
                            (const unsigned long long *)s->vbits, (const EnvState *)s->commit, s->arrival.plane);
     } else {
         const dim3 grd((unsigned)((g.W + 255) / 256), (unsigned)g.H, (unsigned)g.E), blk(256);
-        const uint8_t *cells = s->bl_cur ? s->cells : nullptr;
+        const uint8_t *cells = cur_cells(s);
         if (g.ab == 1) hipLaunchKernelGGL(k_arrival_cells<uint8_t>, grd, blk, 0, s->stream, g, (const uint8_t *)s->age, cells, (const EnvState *)s->commit, s->arrival.plane);
         else if (g.ab == 2) hipLaunchKernelGGL(k_arrival_cells<uint16_t>, grd, blk, 0, s->stream, g, (const uint8_t *)s->age, cells, (const EnvState *)s->commit, s->arrival.plane);
         else hipLaunchKernelGGL(k_arrival_cells<uint32_t>, grd, blk, 0, s->stream, g, (const uint8_t *)s->age, cells, (const EnvState *)s->commit, s->arrival.plane);
@@ -52,7 +52,7 @@ static ValueArgs value_args(const sf_sim *s)
 static int value_pass(sf_sim *s)
 {
     const Geo &g = s->g;
-    const bool sparse = s->bl_cur && s->vbits_valid && s->vbits_fl_valid && !s->values.dense;
+    const bool sparse = s->planes.bits_cover_cells() && !s->values.dense;
     if (sparse) hipLaunchKernelGGL(k_value_bits, dim3((unsigned)((g.H * g.VW + 255) / 256), (unsigned)g.E), dim3(256), 0, s->stream, g,
                                    (const unsigned long long *)s->vbits, value_args(s));
     else hipLaunchKernelGGL(k_value_cells, dim3((unsigned)((g.W + 255) / 256), (unsigned)g.H, (unsigned)g.E), dim3(256), 0, s->stream, g, value_args(s));
@@ -68,7 +68,7 @@ static int value_recount(sf_sim *s)
     if (!s->values.plane) return SF_OK;
     const Geo &g = s->g;
     HIPCHK(hipMemsetAsync(s->val_rec(), 0, (size_t)g.E * sizeof(ValueRec), s->stream));
-    if (!s->was_reset) return SF_OK;
+    if (!s->planes.was_reset()) return SF_OK;
     if (s->arrival.pending) return arrival_pass(s);       // (a call that failed half way left updates behind: the plane first, the pass behind it counts)
     SF_TRY(ensure_commit(s));
     hipLaunchKernelGGL(k_value_cells, dim3((unsigned)((g.W + 255) / 256), (unsigned)g.H, (unsigned)g.E), dim3(256), 0, s->stream, g, value_args(s));
@@ -130,7 +130,7 @@ extern "C" int sf_values_set(sf_sim *s, const int32_t *values, int32_t per_env, 
     if (err != hipSuccess || bad) {
         (void)hipFree(plane);
         if (!s->values.aux) (void)hipFree(aux);
-        else if (s->was_reset) (void)value_recount(s);      // (the records were zeroed above: counted again under the plane that stays)
+        else if (s->planes.was_reset()) (void)value_recount(s);      // (the records were zeroed above: counted again under the plane that stays)
         if (bad) return fail(SF_EINVAL, "sf_values_set: a value of the device plane is outside -2^24 .. 2^24");
         return fail(SF_EHIP, "sf_values_set: %s", hipGetErrorString(err));
     }
@@ -306,7 +306,7 @@ extern "C" int sf_enable_arrival(sf_sim *s, int32_t on)
     SF_TRY(dev_alloc(s, &s->arrival.plane, n));
     HIPCHK(hipMemsetAsync(s->arrival.plane, 0, n * sizeof(uint32_t), s->stream));
     s->arrival.pending = 0;
-    if (s->was_reset) SF_TRY(arrival_pass(s));      // the sprites that are live now carry their true updates
+    if (s->planes.was_reset()) SF_TRY(arrival_pass(s));      // the sprites that are live now carry their true updates
     return finish_call(s, nullptr, !s->async, nullptr);
 }
 
@@ -361,7 +361,7 @@ extern "C" int sf_get_arrival_passes(sf_sim *s, int64_t *out)
 extern "C" int sf_cell_layout(sf_sim *s, int32_t *blocked)
 {
     if (!s || !blocked) return fail(SF_EINVAL, "sf_cell_layout: null argument");
-    *blocked = s->bl_cur ? 1 : 0;
+    *blocked = s->planes.blocked() ? 1 : 0;
     return SF_OK;
 }
 
@@ -442,7 +442,7 @@ extern "C" int sf_observe(sf_sim *s, const sf_obs_params *p, int32_t n, const in
     memset(&a, 0, sizeof a);
     a.g = g;
     a.status = s->status;
-    a.cells = s->bl_cur ? s->cells : nullptr;
+    a.cells = cur_cells(s);
     a.lay = s->lay_all;
     a.lay_tab = (size_t)s->tables.size() > 1 ? 7LL * g.H * g.W : 0;
     a.head = reinterpret_cast<const ObsHead *>(blk.dev);
@@ -572,7 +572,7 @@ extern "C" int sf_render(sf_sim *s, const sf_render_params *p, int32_t n, const 
     memset(&a, 0, sizeof a);
     a.g = g;
     a.status = s->status;
-    a.cells = !hist && s->bl_cur ? s->cells : nullptr;
+    a.cells = hist ? nullptr : cur_cells(s);
     a.hist = hist ? s->history : nullptr;
     a.cap = s->history_cap; a.first = hist ? p->first : 0; a.count = count;
     a.bg = s->render.bg;

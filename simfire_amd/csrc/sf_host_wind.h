@@ -92,7 +92,7 @@ static int wind_sched_pass(sf_sim *s)
     SF_TRY(lab_start(s, s->wind.timer));
     HIPCHK(hipMemsetAsync(s->wind.due_cnt, 0, sizeof(uint32_t), s->stream));
     hipLaunchKernelGGL(k_wind_due, dim3((unsigned)((g.E + 255) / 256)), dim3(256), 0, s->stream, g, (const EnvState *)s->commit, (const EnvState *)s->tmp,
-                       (const uint32_t *)s->flags, s->seq, s->committed ? 1 : 0, s->wind.sched_dev, s->wind.due_cnt, s->wind.due, s->wind.due_U, s->wind.due_D);
+                       (const uint32_t *)s->flags, s->seq, s->planes.committed() ? 1 : 0, s->wind.sched_dev, s->wind.due_cnt, s->wind.due, s->wind.due_U, s->wind.due_D);
     SF_TRY(wind_launch(s, s->wind.due, s->wind.due_cnt, 0, n, s->wind.due_U, s->wind.due_D, 0, cached));
     SF_TRY(lab_stop(s, s->wind.timer));
     return SF_OK;

@@ -296,9 +296,7 @@ extern "C" int sf_set_rows_per_band(sf_sim *s, int32_t rows)
     HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
     { int rc0 = ensure_commit(s); if (rc0) return rc0; }     // also clears the list counters of the tiled path
     choose_rows_per_band(s->g, rows);
-    s->status_fresh = false;
-    s->tdirty_all = true;
-    s->tiles_valid = false;            // the tile activity map is laid out per wave tile: rebuilt for the new geometry before the next tiled step
+    s->planes.geometry_changed();      // the tile activity map is laid out per wave tile: rebuilt for the new geometry before the next tiled step
     return SF_OK;
 }
 
@@ -377,7 +375,7 @@ extern "C" int sf_set_generic(sf_sim *s, int32_t on)
     HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
     { int rc0 = ensure_commit(s); if (rc0) return rc0; }     // the list counters of the tiled path restart clean
     s->generic = on != 0;
-    s->tdirty_all = true;
+    s->planes.family_switched();
     return SF_OK;
 }
 
@@ -477,11 +475,11 @@ extern "C" int sf_set_dense(sf_sim *s, int32_t dense)
 static int ensure_commit(sf_sim *s)
 {
     LOOP_QUIESCE(s);
-    if (s->committed) return SF_OK;
+    if (s->planes.committed()) return SF_OK;
     hipLaunchKernelGGL(k_commit, dim3((s->g.E + 255) / 256), dim3(256), 0, s->stream, s->g, s->commit,
                        (const EnvState *)s->tmp, s->flags, (s->seq + 5) % 6, s->n_active);
     HIPCHK(hipGetLastError());
-    s->committed = true;
+    s->planes.rings_folded();
     return SF_OK;
 }
 
@@ -497,7 +495,7 @@ static int env_segs(const sf_sim *s, unsigned kinds, EnvSeg *out)
         assert(n < kEnvSegs);
         out[n++] = {static_cast<uint8_t *>(base), len, len};
     };
-    if (s->bl_cur) add(kSegCells, s->cells_alloc, g.cells_env);
+    if (s->planes.blocked()) add(kSegCells, s->cells_alloc, g.cells_env);
     else {
         add(kSegCells, s->status, g.plane_env);
         add(kSegCells, s->age_alloc, g.age_env * g.ab);      // (with its guard rows)
@@ -537,15 +535,15 @@ static unsigned seg_grid_x(const EnvSeg *seg, int n)
 static int scatter_points(sf_sim *s, const int32_t *pts_dev, int n)
 {
     const Geo &g = s->g;
-    uint8_t *cells = s->bl_cur ? s->cells : nullptr;
-    s->status_fresh = false;
+    uint8_t *cells = cur_cells(s);
+    s->planes.points_scattered();
     const dim3 grd((unsigned)((n + 255) / 256)), blk(256);
     hipLaunchKernelGGL(k_mitigate_clear, grd, blk, 0, s->stream, g, s->status, cells, (const uint32_t *)s->settled, s->burn,
                        (const EnvState *)s->commit, (const EnvState *)s->tmp, (const uint32_t *)s->flags, s->seq,
-                       s->committed ? 1 : 0, pts_dev, n);
+                       s->planes.committed() ? 1 : 0, pts_dev, n);
     hipLaunchKernelGGL(k_mitigate_write, grd, blk, 0, s->stream, g, s->status, cells, s->settled, s->tdirty,
                        (const EnvState *)s->commit, (const EnvState *)s->tmp, (const uint32_t *)s->flags, s->seq,
-                       s->committed ? 1 : 0, pts_dev, n);
+                       s->planes.committed() ? 1 : 0, pts_dev, n);
     HIPCHK(hipGetLastError());
     return SF_OK;
 }
@@ -605,13 +603,12 @@ extern "C" int sf_load_fire_map(sf_sim *s, int32_t env, const uint8_t *map)
     for (size_t i = 0; i < n; ++i)
         if (map[i] > SF_WETLINE) return fail(SF_EINVAL, "sf_load_fire_map: value %d at cell %zu is not a BurnStatus", map[i], i);
     HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    s->fire_rows = 0;                  // (a map from outside: its fire may be of any size)
     if (s->delta.snap) s->delta.snap_valid[env] = 0;      // (sf_get_fire_map_delta: no reference point any more)
     SF_TRY(ensure_stage(s, n));
     dim3 blk(256), grd((g.W + 255) / 256, g.H);
     SF_TRY(ensure_commit(s));
     SF_TRY(ensure_rm(s));
-    s->status_fresh = false;
+    s->planes.map_loaded();            // (from here on the environment's map is being replaced)
     if (g.att)
         hipLaunchKernelGGL(k_settle_env, grd, blk, 0, s->stream, g, (const uint8_t *)s->status, s->settled, s->burn,
                            (const EnvState *)s->commit, env, 1);
@@ -619,9 +616,7 @@ extern "C" int sf_load_fire_map(sf_sim *s, int32_t env, const uint8_t *map)
     hipLaunchKernelGGL(k_pack_status, grd, blk, 0, s->stream, g, s->status, s->settled, (const EnvState *)s->commit, env,
                        (const uint8_t *)s->stage);
     HIPCHK(hipGetLastError());
-    const int rc = rebuild_tflags(s, env, 1);
-    s->tdirty_all = true;
-    if (rc) return rc;
+    SF_TRY(rebuild_tflags(s, env, 1));
     HIPCHK(hipStreamSynchronize(s->stream));
     return SF_OK;
 }
@@ -630,11 +625,11 @@ extern "C" int sf_load_fire_map(sf_sim *s, int32_t env, const uint8_t *map)
 // one that is current is converted when the other kind of work comes next (one sweep over the cell planes).
 static int ensure_rm(sf_sim *s)
 {
-    if (!s->bl_cur) return SF_OK;
+    if (!s->planes.blocked()) return SF_OK;
     const Geo &g = s->g;
     hipLaunchKernelGGL(k_bl_to_rm, dim3((g.PV + 63) / 64, g.H, g.E), dim3(64), 0, s->stream, g, (const uint8_t *)s->cells, s->status, s->age);
     HIPCHK(hipGetLastError());
-    s->bl_cur = false;
+    s->planes.converted_to_rm();
     return SF_OK;
 }
 static int alloc_bl(sf_sim *s)
@@ -677,12 +672,12 @@ static int ensure_rtc(sf_sim *s)
 
 static int ensure_bl(sf_sim *s)
 {
-    if (s->bl_cur) return SF_OK;
+    if (s->planes.blocked()) return SF_OK;
     const Geo &g = s->g;
     SF_TRY(alloc_bl(s));
     hipLaunchKernelGGL(k_rm_to_bl, dim3((g.PV + 63) / 64, g.H, g.E), dim3(64), 0, s->stream, g, (const uint8_t *)s->status, (const uint8_t *)s->age, s->cells);
     HIPCHK(hipGetLastError());
-    s->bl_cur = true;
+    s->planes.converted_to_bl();
     return SF_OK;
 }
 
@@ -690,23 +685,22 @@ static int ensure_bl(sf_sim *s)
 // bitmap; whichever a launch needs is rebuilt from the sprite-mask planes if the other kind ran in between.
 static int ensure_tiles(sf_sim *s)
 {
-    if (s->tiles_valid) return SF_OK;
+    if (s->planes.tiles_valid()) return SF_OK;
     { int rc0 = ensure_rm(s); if (rc0) return rc0; }
     HIPCHK(hipMemsetAsync(s->tflags, 0, s->tflags_bytes, s->stream));
     SF_TRY(rebuild_tflags(s, 0, s->g.E));
     SF_TRY(rebuild_seams(s, 0, s->g.E));
-    s->tiles_valid = true;
+    s->planes.tiles_rebuilt();
     return SF_OK;
 }
 static int ensure_vbits(sf_sim *s)
 {
-    if (s->vbits_valid) return SF_OK;
+    if (s->planes.bits_valid()) return SF_OK;
     { int rc0 = ensure_rm(s); if (rc0) return rc0; }
     const Geo &g = s->g;
     hipLaunchKernelGGL(k_rebuild_vbits, dim3(g.VW, g.H, g.E), dim3(64), 0, s->stream, g, (const uint8_t *)s->age, s->vbits, 0);
     HIPCHK(hipGetLastError());
-    s->vbits_valid = true;
-    s->vbits_fl_valid = true;
+    s->planes.bits_rebuilt();
     return SF_OK;
 }
 
@@ -716,7 +710,7 @@ static int ensure_vbits(sf_sim *s)
 extern "C" int sf_last_step_launch(sf_sim *s, int32_t *kind)
 {
     if (!s || !kind) return fail(SF_EINVAL, "sf_last_step_launch: null argument");
-    *kind = s->last_kind;
+    *kind = s->planes.last_kind();
     return SF_OK;
 }
 
@@ -1011,7 +1005,7 @@ static void plan_modes(const sf_sim *s, StepPlan &p, int n_steps)
         // update, fire.py:163-234) sits in a window placed to the row and - where a window placed to the vector may not hold it for the call -
         // around the middle of the (F + 14) / 16 + 1 vectors it can straddle at worst (run_window, PL4): (64 - F) / 2 rows and 32 - 8 x vectors
         // columns lie between it and the window's ring on every open side, and it needs one per update (+ 1: the ring itself).
-        const int F = s->fire_rows, wv = (F + 14) / 16 + 1;
+        const int F = s->planes.fire_rows(), wv = (F + 14) / 16 + 1;
         const int room = wv > 3 ? 0 : std::min((64 - F) / 2, 32 - 8 * wv);
         p.win_only = n_steps + 1 <= room && p.win == 1;      // (SF_TUNE_RUN_WINDOW = k > 1 leaves the window after k updates: tests)
     }
@@ -1057,12 +1051,12 @@ static StepPlan plan_step(const sf_sim *s, int n_steps, bool lines)
         // update on 1024 environments in the driver's window.)  SF_TUNE_RUN_COMPACT = 2: the window kernel in front whatever the batch size (tests).
         // (k_win needs the window phase: SF_TUNE_RUN_WINDOW > 0)
         p.win_first = p.win != 0 && tn.v[SF_TUNE_RUN_COMPACT] != 0 && (g.E > s->n_cu || tn.v[SF_TUNE_RUN_COMPACT] == 2) && !lines && g.VW == 1 &&
-                      g.H >= 64 && g.H <= 1024 && g.PV >= 4 && !g.dense && s->fire_rows > 0 && s->fire_rows <= 62 && n_steps <= 64 && !tn.set[SF_TUNE_RUN_WAVES] &&
+                      g.H >= 64 && g.H <= 1024 && g.PV >= 4 && !g.dense && s->planes.fire_rows() > 0 && s->planes.fire_rows() <= 62 && n_steps <= 64 && !tn.set[SF_TUNE_RUN_WAVES] &&
                       g.diag && (tn.v[SF_TUNE_RUN_TEAM] == 0 || tn.v[SF_TUNE_RUN_TEAM] == 1) && s->fused_mode != 2;
         // (the launch behind k_win: while every fire surely ends the call inside 64 rows, 16-wave workgroups - an environment whose fire reached the
         // ring of a window placed to the vector gets a new window of 64 rows around where the fire stands now, 2 us per update instead of the
         // general loop's 6 in an 8-wave workgroup; everybody else's workgroup returns at once)
-        const bool all_young = tn.v[SF_TUNE_RUN_WINDOW] != 0 && s->fire_rows > 0 && s->fire_rows + 2LL * n_steps <= 60;
+        const bool all_young = tn.v[SF_TUNE_RUN_WINDOW] != 0 && s->planes.fire_rows() > 0 && s->planes.fire_rows() + 2LL * n_steps <= 60;
         if (tn.v[SF_TUNE_RUN_COMPACT] && g.E > s->n_cu && nw > 8 && min_nw <= 8 && !tn.set[SF_TUNE_RUN_WAVES] && !all_young) {
             const int vcap2 = vcap > 1024 ? 1024 : vcap;
             const size_t lds2 = run_lds_bytes(g, 8, vcap2);
@@ -1141,14 +1135,14 @@ static Segment plan_segment(const sf_sim *s, const StepPlan &p, int n_steps, int
     // after sf_reset and advances one row per update at most.  A call that ends with every fire still under 480 rows gives every
     // environment ONE member.
     bool young = false;
-    if (p.team_wide && !p.team_forced && tk == 0 && tgeo.rcap > 0 && s->fire_rows > 0) {
+    if (p.team_wide && !p.team_forced && tk == 0 && tgeo.rcap > 0 && s->planes.fire_rows() > 0) {
         // (cut_bands: the fire's tile rows, + ceil((updates + 1) / tile height) + 1 tile rows either side)
-        const long long room = (long long)tgeo.rcap - s->fire_rows - 2LL * done - 7LL * g.LR * g.RB - 2;
+        const long long room = (long long)tgeo.rcap - s->planes.fire_rows() - 2LL * done - 7LL * g.LR * g.RB - 2;
         const long long fit = room / 2;              // updates the window is sure to hold
         // (only where the whole call stays young - measured on C4's share: one member for the first ~ 380 of 1000 updates and two
         // for the rest loses to two members throughout, 23.5 against 21.9 us per step; the driver's 20 after 5: 7.0 against 8.7)
         // (C4's share, calls of 60 / 100 / 150 / 250 / 350 updates after 20: one member 7.8 / 8.3 / 9.6 / 11.9 / 15.8 us per step, two 9.1 / 9.3 / 10.8 / 12.1 / 14.1)
-        if (done == 0 && fit >= n_steps && s->fire_rows + 2LL * n_steps <= 480) { young = true; sg.n = n_steps - done; sg.recut = 0; }
+        if (done == 0 && fit >= n_steps && s->planes.fire_rows() + 2LL * n_steps <= 480) { young = true; sg.n = n_steps - done; sg.recut = 0; }
     }
     // Teams that grow inside the launch (k_run<TEAM = 2>): long calls on one-word rows with at most one environment per CU - the CUs of
     // fires that go out (C3: three quarters of them over 1000 updates) join the fires that are left.  SF_TUNE_RUN_JOIN.
@@ -1197,10 +1191,7 @@ static int run_resident(sf_sim *s, const StepPlan &p, StepArgs &a, int n_steps, 
     const Geo &g = s->g;
     const int32_t *mit_dev = a.mit;
     const int mit_k = a.mit_k;
-    if (p.result) {
-        if (s->tdirty_all) HIPCHK(hipMemsetAsync(s->tdirty, 1, s->n_tiles_max, s->stream));
-        s->tdirty_all = false;
-    }
+    if (p.result) SF_TRY(mark_hist_dirty(s));
     a.cost = s->run_cost;
     s->last_team_max = 0;
     if (p.win_first) {
@@ -1250,7 +1241,7 @@ static int run_resident(sf_sim *s, const StepPlan &p, StepArgs &a, int n_steps, 
             int rc0 = launch_run(s, run_key(g, kRunPlain, run_words(g.H, p.nw, g.VW), a.mit != nullptr), (unsigned)g.E, (unsigned)p.nw * 64, p.lds, a,
                                  sg.n, p.vcap, p.bsz);
             if (rc0) return rc0;
-            if (g.VW > 1) s->vbits_fl_valid = false;
+            if (g.VW > 1) s->planes.plain_run_wide();
         }
         if (sg.join || sg.team) s->last_team_max = sg.team_max;
         s->cost_steps = sg.n;
@@ -1258,9 +1249,7 @@ static int run_resident(sf_sim *s, const StepPlan &p, StepArgs &a, int n_steps, 
         s->last_launches++;
     }
     if (p.win_only) s->cost_steps = n_steps;
-    s->status_fresh = p.result;
-    s->tiles_valid = false;                // the tile activity map / seam planes are not kept by k_run
-    s->last_kind = p.win_first ? 4 : 2;
+    s->planes.resident_done(p.result, p.win_first);
     return SF_OK;
 }
 
@@ -1271,8 +1260,7 @@ static int enqueue_steps(sf_sim *s, StepPlan p, int n_steps, const int32_t *mit_
 {
     const Geo &g = s->g;
     const Tuning &tn = s->tune;
-    const bool row_was_fresh = s->status_fresh;      // the result block on the device is current as this call starts
-    s->status_fresh = false;
+    const bool row_was_fresh = s->planes.call_begins();      // the result block on the device is current as this call starts
     s->last_launches = 0;
     const int n_requested = n_steps;
     if (n_steps != 1 || mit_dev || s->last_was_step1) s->step1_polls = 0;       // (another kind of call, or nobody looked at the last update's result)
@@ -1280,7 +1268,7 @@ static int enqueue_steps(sf_sim *s, StepPlan p, int n_steps, const int32_t *mit_
         int rc0 = ensure_commit(s);            // k_run starts from commit[] and leaves the new states there
         if (rc0) return rc0;
         // (a team launch reads all three planes of the vector bitmap; a launch of the plain kernel on rows of several words has kept only the first)
-        if ((p.team_forced || p.team_wide || p.team_auto) && !s->vbits_fl_valid) s->vbits_valid = false;
+        if (p.team_forced || p.team_wide || p.team_auto) s->planes.team_launch_next();
         rc0 = ensure_vbits(s);
         if (rc0) return rc0;
         rc0 = ensure_bl(s);
@@ -1309,10 +1297,6 @@ static int enqueue_steps(sf_sim *s, StepPlan p, int n_steps, const int32_t *mit_
         int rc0 = run_resident(s, p, a, n_steps, row_was_fresh);
         if (rc0) return rc0;
         n_steps = 0;                           // nothing left for the per-step loop
-    } else if (n_steps > 0) {
-        s->vbits_valid = false;                // the per-step kernels do not keep the vector bitmap
-        if (p.generic) s->tiles_valid = false; // nor does the per-cell kernel keep the tile maps
-        s->last_kind = p.generic ? 3 : (p.fused ? 1 : 0);
     }
     const long long n_wave_tiles = (long long)g.E * g.TY * g.TX;
     const dim3 sel_grid((unsigned)((n_wave_tiles + kSelectThreads - 1) / kSelectThreads));
@@ -1324,7 +1308,7 @@ static int enqueue_steps(sf_sim *s, StepPlan p, int n_steps, const int32_t *mit_
     const dim3 cell_grid((unsigned)((g.W + 255) / 256), (unsigned)g.H, (unsigned)g.E);
     for (int i = 0; i < n_steps; ++i) {
         a.launch = s->seq;
-        a.from_commit = s->committed ? 1 : 0;
+        a.from_commit = (i == 0 && s->planes.committed()) ? 1 : 0;      // (the first launch leaves the states in the rings)
         a.ring = s->ring;
         if (p.generic) {
             if (g.ab == 1) hipLaunchKernelGGL(k_step_cells<uint8_t>, cell_grid, dim3(256), 0, s->stream, a);
@@ -1342,9 +1326,9 @@ static int enqueue_steps(sf_sim *s, StepPlan p, int n_steps, const int32_t *mit_
         if (s->history) hipLaunchKernelGGL(k_record, cell_grid, dim3(256), 0, s->stream, g, (const uint8_t *)s->status,
                                            (const EnvState *)(s->tmp + (size_t)(a.launch & 1) * g.E), s->history, s->history_cap);
         s->seq = (s->seq + 1) % 6;
-        s->committed = false;
     }
-    if (s->fire_rows > 0) { const long long fr = (long long)s->fire_rows + 2LL * n_requested; s->fire_rows = fr > g.H ? g.H : (int)fr; }
+    s->planes.per_step_enqueued(p.generic, p.fused, n_steps);
+    s->planes.updates_made(n_requested, g.H);
     s->last_was_step1 = n_requested == 1 && !mit_dev;
     // no commit here: the states stay in the rings until something asks for them (ensure_commit)
     return SF_OK;
@@ -1487,7 +1471,7 @@ static int stage_lines(sf_sim *s, int n_steps, const int32_t *pts, int k, int de
 static int enqueue_pair(sf_sim *s, const int32_t *blk, int k, int i, hipEvent_t t0)
 {
     const Geo &g = s->g;
-    if (i == 0) { s->status_fresh = false; s->last_launches = 0; s->step1_polls = 0; }
+    if (i == 0) { (void)s->planes.call_begins(); s->last_launches = 0; s->step1_polls = 0; }
     hipLaunchKernelGGL(k_expand_pts, dim3((unsigned)((g.E * k + 255) / 256)), dim3(256), 0, s->stream, g.E, k,
                        blk + (size_t)i * g.E * k * 3, s->mit_stage);
     const int rc = scatter_points(s, s->mit_stage, g.E * k);
@@ -1607,14 +1591,11 @@ extern "C" int sf_loop_start(sf_sim *s, int32_t k)
     __sync_synchronize();
     HIPCHK(hipMemsetAsync(s->loop.mem, 0, sizeof(uint32_t) * (32 + (size_t)g.E), s->stream));
     HIPCHK(hipMemsetAsync(s->loop.pts_mem, 0, pts_bytes, s->stream));
-    if (s->tdirty_all) HIPCHK(hipMemsetAsync(s->tdirty, 1, s->n_tiles_max, s->stream));
-    s->tdirty_all = false;
-    s->status_fresh = false;
-    { int rc0 = loop_launch(s); if (rc0) return rc0; }
+    SF_TRY(mark_hist_dirty(s));
+    s->planes.loop_started();
+    SF_TRY(loop_launch(s));
     HIPCHK(hipGetLastError());
     s->loop.on = true;
-    s->tiles_valid = false;
-    s->last_kind = 2;
     return SF_OK;
 }
 
@@ -1639,7 +1620,7 @@ extern "C" int sf_loop_step(sf_sim *s, const int32_t *pts, int32_t *status_out, 
     __sync_synchronize();                                    // the points are in memory before the number that announces them
     db[0] = seq;
     s->loop.seq = seq;
-    if (s->fire_rows > 0 && s->fire_rows < g.H) s->fire_rows = s->fire_rows + 2 > g.H ? g.H : s->fire_rows + 2;
+    s->planes.updates_made(1, g.H);
     // wait for the "done" number; should the launch have left by itself (no ring for loop_timeout clocks), start it again: every
     // workgroup resumes from its own "done" number, the points of this step are still in their slot
     const volatile uint32_t *res = reinterpret_cast<const volatile uint32_t *>(s->loop.res);
@@ -1686,7 +1667,7 @@ static int loop_stop(sf_sim *s)
     __sync_synchronize();
     s->loop.on = false;
     HIPCHK(hipStreamSynchronize(s->stream));      // the workgroups commit their environments and leave the result block behind
-    s->status_fresh = true;
+    s->planes.loop_stopped();
     return SF_OK;
 }
 
@@ -1705,7 +1686,7 @@ static int get_maps(sf_sim *s, int env0, int n, uint8_t *out)
     const size_t bytes = (size_t)n * g.H * g.W;
     SF_TRY(ensure_stage(s, bytes));
     dim3 blk(256), grd((g.W + 255) / 256, g.H, n);
-    hipLaunchKernelGGL(k_unpack_status, grd, blk, 0, s->stream, g, (const uint8_t *)s->status, (const uint8_t *)(s->bl_cur ? s->cells : nullptr), env0, (uint8_t *)s->stage, (uint8_t *)nullptr);
+    hipLaunchKernelGGL(k_unpack_status, grd, blk, 0, s->stream, g, (const uint8_t *)s->status, (const uint8_t *)cur_cells(s), env0, (uint8_t *)s->stage, (uint8_t *)nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, s->stage, bytes, hipMemcpyDeviceToHost, s->stream));
     return finish_call(s, "sf_get_fire_map(s)", true, nullptr);
@@ -1761,13 +1742,13 @@ static int delta_enqueue(sf_sim *s, int env, int cap, int *mode, bool with_row =
         // no reference point: the current map becomes it, the caller fetches the whole map
         dim3 blk(256), grd((g.W + 255) / 256, g.H, 1);
         SF_TRY(ensure_stage(s, (size_t)g.H * g.W));
-        hipLaunchKernelGGL(k_unpack_status, grd, blk, 0, s->stream, g, (const uint8_t *)s->status, (const uint8_t *)(s->bl_cur ? s->cells : nullptr), env, (uint8_t *)s->stage, s->delta.snap);
+        hipLaunchKernelGGL(k_unpack_status, grd, blk, 0, s->stream, g, (const uint8_t *)s->status, (const uint8_t *)cur_cells(s), env, (uint8_t *)s->stage, s->delta.snap);
         HIPCHK(hipGetLastError());
         s->delta.snap_valid[env] = 1;
         *mode = 1;
         return SF_OK;
     }
-    hipLaunchKernelGGL(k_map_delta, dim3((g.PV + 255) / 256, g.H), dim3(256), 0, s->stream, g, (const uint8_t *)s->status, (const uint8_t *)(s->bl_cur ? s->cells : nullptr), env,
+    hipLaunchKernelGGL(k_map_delta, dim3((g.PV + 255) / 256, g.H), dim3(256), 0, s->stream, g, (const uint8_t *)s->status, (const uint8_t *)cur_cells(s), env,
                        s->delta.snap + (size_t)env * g.plane_env, s->delta.dev, cap, s->delta.base,
                        with_row ? (const int32_t *)(s->status_block + (size_t)env * 8) : nullptr, (const double *)(s->elapsed_dev + env));
     HIPCHK(hipGetLastError());
@@ -1886,7 +1867,7 @@ static int refresh_status(sf_sim *s, int32_t *copy_to)
 {
     const Geo &g = s->g;
     { int rc0 = ensure_commit(s); if (rc0) return rc0; }
-    if (s->status_fresh) {
+    if (s->planes.row_fresh()) {
         // the resident launch has left the block (and the registered sink's copy) behind: nothing to count
         if (copy_to && copy_to != s->sink)
             HIPCHK(hipMemcpyAsync(copy_to, s->status_block, sizeof(int32_t) * 8 * g.E, hipMemcpyDeviceToDevice, s->stream));
@@ -1895,19 +1876,18 @@ static int refresh_status(sf_sim *s, int32_t *copy_to)
     int32_t *sink2 = s->sink && s->sink != copy_to ? s->sink : nullptr;       // the registered sink follows every refresh
     if (g.ab == 1 && !s->generic) {
         // per-tile histograms: only the tiles touched since the last query are recounted; one launch writes the whole block
-        if (s->tdirty_all) HIPCHK(hipMemsetAsync(s->tdirty, 1, s->n_tiles_max, s->stream));
-        s->tdirty_all = false;
-        hipLaunchKernelGGL(k_counts_tiles, dim3((unsigned)g.E), dim3(1024), 0, s->stream, g, (const uint8_t *)s->status, (const uint8_t *)(s->bl_cur ? s->cells : nullptr), s->tdirty, s->thist,
+        SF_TRY(mark_hist_dirty(s));
+        hipLaunchKernelGGL(k_counts_tiles, dim3((unsigned)g.E), dim3(1024), 0, s->stream, g, (const uint8_t *)s->status, (const uint8_t *)cur_cells(s), s->tdirty, s->thist,
                            (const EnvState *)s->commit, s->status_block, s->elapsed_dev, copy_to ? copy_to : sink2);
         if (copy_to && sink2) HIPCHK(hipMemcpyAsync(sink2, s->status_block, sizeof(int32_t) * 8 * g.E, hipMemcpyDeviceToDevice, s->stream));
-        s->status_fresh = true;            // (the block - and the registered sink's copy - is current until something changes a status byte)
+        s->planes.counted(true);           // (the block - and the registered sink's copy - is current until something changes a status byte)
     } else {
         { int rc0 = ensure_rm(s); if (rc0) return rc0; }
         HIPCHK(hipMemsetAsync(s->status_block, 0, sizeof(int32_t) * 8 * g.E, s->stream));
         int bx = g.H < 64 ? g.H : 64;
         hipLaunchKernelGGL(k_counts, dim3(bx, g.E), dim3(256), 0, s->stream, g, (const uint8_t *)s->status,
                            (const EnvState *)s->commit, s->status_block);
-        s->tdirty_all = true;
+        s->planes.counted(false);
         hipLaunchKernelGGL(k_elapsed, dim3((g.E + 255) / 256), dim3(256), 0, s->stream, g.E, (const EnvState *)s->commit,
                            s->elapsed_dev);
         if (copy_to) HIPCHK(hipMemcpyAsync(copy_to, s->status_block, sizeof(int32_t) * 8 * g.E, hipMemcpyDeviceToDevice, s->stream));
@@ -1992,7 +1972,7 @@ extern "C" int sf_set_result_sink(sf_sim *s, void *device_dst)
     HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
     HIPCHK(hipStreamSynchronize(s->stream));       // nothing in flight may still write the old sink
     s->sink = static_cast<int32_t *>(device_dst);
-    s->status_fresh = false;                       // the new sink is filled by the next refresh
+    s->planes.sink_replaced();                     // the new sink is filled by the next refresh
     return SF_OK;
 }
 
@@ -2009,13 +1989,13 @@ extern "C" int sf_fire_map_device(sf_sim *s, void **ptr, int64_t *row_pitch, int
 {
     if (!s || !ptr || !row_pitch || !env_stride) return fail(SF_EINVAL, "sf_fire_map_device: null argument");
     HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
-    if (s->bl_cur) {
+    if (s->planes.blocked()) {
         // the resident launch keeps the cells in its blocked plane: the row-major status plane is refreshed from it (one sweep) and
         // is a snapshot until the next call - the blocked plane stays the current one, nothing is converted back
         const Geo &g = s->g;
         hipLaunchKernelGGL(k_bl_to_rm, dim3((g.PV + 63) / 64, g.H, g.E), dim3(64), 0, s->stream, g, (const uint8_t *)s->cells, s->status, (uint8_t *)nullptr);
         HIPCHK(hipGetLastError());
-    } else { s->tdirty_all = true; s->status_fresh = false; }      // the caller holds a writable alias of the status plane: recount everything at the next query
+    } else s->planes.alias_handed_out();      // the caller holds a writable alias of the status plane: recount everything at the next query
     HIPCHK(hipStreamSynchronize(s->stream));
     *ptr = s->status; *row_pitch = s->g.P; *env_stride = s->g.plane_env;
     return SF_OK;

@@ -150,7 +150,7 @@ def test_segment_capacity_covers_the_largest_selection():
             branch.append(line)
         else:
             count[m.group(1)] += int(loop.group(1)) if loop else 1
-    assert len(branch) == 3 and "bl_cur" in branch[0]    # the blocked plane | status + the sprite-mask plane
+    assert len(branch) == 3 and "planes.blocked()" in branch[0]   # the blocked plane | status + the sprite-mask plane
     count["kSegCells"] = 2
     assert all(count.values()), count                    # every kind has a slice
     assert len(re.findall(r"\badd\(", host)) == len(re.findall(r"\badd\(kSeg", body))          # (no second table beside it)
