@@ -577,6 +577,76 @@ typedef struct sf_walk_out {             /* device pointers, any may be NULL, at
  * work on passable, targets, points and the outputs before the call. */
 int sf_walk(sf_sim *sim, const sf_walk_params *params, int32_t n, const int32_t *envs /* [n] host */, const sf_walk_out *out);
 
+/* Fire travel time: WHEN the fire gets to a cell - the minimum time, in minutes from now, over the R table the
+ * handle holds NOW (it follows sf_set_wind, and a schedule segment once a stepping call has applied it).  This is Finney's minimum
+ * travel time on the automaton's own graph, a FORECAST in continuous time and NOT the automaton: the automaton accumulates burn from
+ * the newest burning neighbour in whole updates and its sources burn out; here the fastest neighbour counts, time is continuous and a
+ * source burns for ever.  The reference has no counterpart; the semantics are this library's own.
+ * For a listed environment e, its table rt and s(c) the status byte & 7 of cell c, read from whichever cell plane is current:
+ *   source(c) = bit s(c) of source_mask, or sources[c] != 0 when a sources plane is given (device u8, dense [height * width], one
+ *   plane for all or - sources_per_env - one per environment, indexed by the environment's number).  source_mask may be 0 only with
+ *   a sources plane.
+ *   pass(c) = bit s(c) of through_mask and, with a passable plane (same forms, passable_per_env), passable[c] != 0.  The masks may
+ *   overlap; a cell that is both is a source.  The pitch padding (x >= width) is neither.
+ *   w_k(c) = float32(pixel_scale / rt[k][c]): the division in float64, rounded once; +inf where rt[k][c] is not > 0.  rt[k][c] is the
+ *   rate at which fire enters c from its neighbour n_k = c + the k-th source offset, and a cell takes pixel_scale feet of burn.  A
+ *   diagonal costs pixel_scale like the automaton's.  connectivity 8: all eight k; 4: the k whose offset has a zero component; 0: the
+ *   handle's diagonal_spread.
+ *   T (float32) is the greatest solution of: T(c) = 0 on sources; T(c) = min_k float32(T(n_k) + w_k(c)) on passable cells over the
+ *   on-grid neighbours that are source or passable, +inf when none is.  Every sum is one float32 addition; the solution is unique
+ *   (float32 addition is monotone, the weights are >= 0) - what a float32 Dijkstra settles -, so no bit depends on scheduling.
+ * minutes float32 [n][height][width]: T on source and passable cells (+inf where no route arrives), SF_TRAVEL_BLOCKED on cells that
+ * are neither.  pred int8 [n][height][width]: on passable non-source cells with a finite T the LOWEST k with float32(T(n_k) + w_k(c))
+ * == T(c) - following it leads to a source along a fastest route -, -1 elsewhere.
+ * Point form, points device int32 [n][k][3] = (column, row, id), sf_agents_device's layout, point_minutes float32 [n][k]: T(c) on a
+ * source or passable cell; on any other cell (an agent on the line it has just drawn) min_k float32(T(n_k) + w_k(c)) over its source
+ * or passable neighbours - when it would be reached were it passable -, +inf if there is none; -1 for id <= 0 or a cell off the grid.
+ * reached int32 [n]: the passable non-source cells with a finite T; last float32 [n]: the largest such T, 0 if there is none.
+ * activations int32 [n]: how many times the search loaded a tile (a measure of its work, not of the fire).
+ * max_minutes = M > 0 caps the search: a candidate above M is dropped, so every value <= M stays exact, and every value that would
+ * exceed M, +inf included, is reported as M (the convention of sf_distance's max_d2); pred is -1 there and reached / last do not
+ * count it.  M = 0: no cap.
+ * A control line is a wall unless through_mask names it; it is then crossed at the plain rate - attenuate_line_ros is not modelled. */
+#define SF_TRAVEL_BLOCKED (-1.0f)
+typedef struct sf_travel_params {
+    int32_t source_mask, through_mask;   /* 0..63 (0 only with sources) / 1..63 */
+    int32_t connectivity;                /* 0 (the handle's diagonal_spread), 4, 8 */
+    int32_t k;                           /* 0, or 1..SF_DIST_MAX_POINTS points per listed environment */
+    float max_minutes;                   /* 0: no cap; > 0: the cap */
+    int32_t passable_per_env;            /* passable is [n_envs][H*W] (indexed by environment number), else [H*W] */
+    int32_t sources_per_env;             /* the same for sources */
+    const uint8_t *passable;             /* device, or NULL */
+    const uint8_t *sources;              /* device, or NULL */
+    const int32_t *points;               /* device int32 [n][k][3] = (column, row, id); NULL with k == 0 */
+    int64_t scratch_bytes;               /* 0: the default budget */
+    int32_t reserved[2];                 /* 0 */
+} sf_travel_params;
+typedef struct sf_travel_out {           /* device pointers, any may be NULL, at least one not */
+    float *minutes;        /* [n][H][W]  dense */
+    int8_t *pred;          /* [n][H][W] */
+    float *point_minutes;  /* [n][k] */
+    int32_t *reached;      /* [n] */
+    float *last;           /* [n] */
+    int32_t *activations;  /* [n] */
+} sf_travel_out;
+/* Environment envs[i] (a host array; any order, repeats allowed) lands in row i of every output.  Anything invalid is SF_EINVAL before
+ * anything is enqueued (source_mask outside 0..63 or through_mask outside 1..63, source_mask 0 without a sources plane, an unknown
+ * connectivity, k outside 0..256, k > 0 without points or points with k == 0, point_minutes without k or k without point_minutes, a
+ * negative or NaN max_minutes, reserved != 0, every output null, a float32 or int32 output or points not aligned to 4 bytes, an
+ * environment out of range, a positive scratch_bytes below one environment's need); a handle without an R table (sf_set_layers* or
+ * sf_set_rtable* - layers are not needed) or without a reset is SF_ESTATE; a grid wider than 8192 cells or of more than 131072 tiles
+ * is SF_ENOTSUP.
+ * One workgroup searches one environment: tiles of 32 x 32 cells are relaxed in LDS and wake their neighbours until no tile is active.
+ * The call reads the state and writes nothing but its outputs and its own scratch - not the current plane, the tile books, the
+ * reference point of sf_get_fire_map_delta, the result block, any ring, the arrival or value planes.  The working array of a listed
+ * environment is its row of minutes where that is asked for; else it lies in a scratch that belongs to the handle, 4 * height * width
+ * bytes rounded up to 256 per listed environment of a chunk: allocated at the first such call, grown (never shrunk) when a later
+ * call needs more, freed by sf_destroy, counted by sf_memory_bytes - a growth is a hipMalloc and waits for the device.  The default
+ * budget is 1 GiB; the list is worked through in chunks so that scratch never exceeds the budget, which changes no bit of the result.
+ * In async mode the call only enqueues (the outputs are complete when the handle's stream has got there); the caller orders its own
+ * work on passable, sources, points and the outputs before the call. */
+int sf_travel(sf_sim *sim, const sf_travel_params *params, int32_t n, const int32_t *envs /* [n] host */, const sf_travel_out *out);
+
 /* Fire behaviour per cell: heat per unit area, head rate of spread, Byram's fireline intensity and flame
  * length - the quantities of the fire characteristics chart - from the R table the handle holds NOW (it follows sf_set_wind, and a
  * schedule segment once a stepping call has applied it).  The reference computes I_R on its way to R (rothermel.py:74-92) and keeps

@@ -1,5 +1,5 @@
 """Argument checks shared by the binding (``engine.py``) and the request classes (``observe.py``, ``render.py``, ``ensemble.py``
-and the four queries ``distance.py``, ``reach.py``, ``walk.py``, ``behavior.py``).
+and the five queries ``distance.py``, ``reach.py``, ``walk.py``, ``travel.py``, ``behavior.py``).
 
 Pure Python on NumPy; torch is imported inside the functions that are handed a tensor.  Every check raises before a device call,
 so a bad request fails the same way with or without a GPU.  ``who`` names the caller in the message (``"reach"`` gives
@@ -151,7 +151,7 @@ def points(x, n, last, name, host=True, k_range=None):
 
 
 def query_points(who, x, n):
-    """The points of a query (``distance``, ``reach``, ``walk``, ``behavior``): ``None``, or a CUDA int32 tensor [n, k, 3] =
+    """The points of a query (``distance``, ``reach``, ``walk``, ``travel``, ``behavior``): ``None``, or a CUDA int32 tensor [n, k, 3] =
     (column, row, id) with k in 1..SF_DIST_MAX_POINTS -> (contiguous tensor or ``None``, k)."""
     from ._lib import SF_DIST_MAX_POINTS
     if x is None:

@@ -146,6 +146,22 @@ class SfWalkOut(C.Structure):
                 ("levels", C.c_void_p)]
 
 
+SF_TRAVEL_BLOCKED = -1.0
+
+
+class SfTravelParams(C.Structure):
+    """``sf_travel_params`` (include/simfire_hip.h)."""
+    _fields_ = [("source_mask", C.c_int32), ("through_mask", C.c_int32), ("connectivity", C.c_int32), ("k", C.c_int32),
+                ("max_minutes", C.c_float), ("passable_per_env", C.c_int32), ("sources_per_env", C.c_int32), ("passable", C.c_void_p),
+                ("sources", C.c_void_p), ("points", C.c_void_p), ("scratch_bytes", C.c_int64), ("reserved", C.c_int32 * 2)]
+
+
+class SfTravelOut(C.Structure):
+    """``sf_travel_out`` (include/simfire_hip.h): device pointers, any may be null, not all."""
+    _fields_ = [("minutes", C.c_void_p), ("pred", C.c_void_p), ("point_minutes", C.c_void_p), ("reached", C.c_void_p),
+                ("last", C.c_void_p), ("activations", C.c_void_p)]
+
+
 class SfBehaviorParams(C.Structure):
     """``sf_behavior_params`` (include/simfire_hip.h)."""
     _fields_ = [("status_mask", C.c_int32), ("summary_mask", C.c_int32), ("k", C.c_int32), ("reserved", C.c_int32),
@@ -229,6 +245,7 @@ SIGNATURES = {
     "sf_distance": [_VP, C.POINTER(SfDistParams), _I32, _VP, _VP],
     "sf_reach": [_VP, C.POINTER(SfReachParams), _I32, _VP, C.POINTER(SfReachOut)],
     "sf_walk": [_VP, C.POINTER(SfWalkParams), _I32, _VP, C.POINTER(SfWalkOut)],
+    "sf_travel": [_VP, C.POINTER(SfTravelParams), _I32, _VP, C.POINTER(SfTravelOut)],
     "sf_behavior": [_VP, C.POINTER(SfBehaviorParams), C.POINTER(SfBehaviorOut), _VP, _I32],
     "sf_get_behavior_builds": [_VP, C.POINTER(_I64)],
     "sf_cell_layout": [_VP, C.POINTER(_I32)],

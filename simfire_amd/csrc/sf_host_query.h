@@ -1,4 +1,4 @@
-// Host code of the queries: sf_distance, sf_reach (23), sf_walk (24) and sf_behavior (25).  Each takes a list
+// Host code of the queries: sf_distance, sf_reach (23), sf_walk (24), sf_behavior (25) and sf_travel (26).  Each takes a list
 // of environments, optional points and caller-owned device outputs, reads the state and changes none of it.  Included once from
 // simfire_hip.hip, behind sf_host_views.h.
 //
@@ -269,6 +269,84 @@ extern "C" int sf_walk(sf_sim *s, const sf_walk_params *p, int32_t n, const int3
     // (every point has a lane of its own, so a small grid still gets k threads)
     return band_search(s, who, s->walk, n, envs, p->points, p->scratch_bytes, kWalkScratchDefault, need, a, a.r, at, k_walk<true>, k_walk<false>,
                        std::max(a.r.nb, p->k), walk_lds_bytes);
+}
+
+// ----------------------------------------------------------------------------- fire travel time
+// One launch of k_travel per chunk, one workgroup per listed environment.  The working array of an environment is its row of the
+// minutes plane where that is asked for (no scratch, no chunks but the launch grid's); else 4 * H * W bytes of scratch, as many
+// environments per chunk as the budget holds.  The call block is the environment list; the arguments travel with the launch.
+extern "C" int sf_travel(sf_sim *s, const sf_travel_params *p, int32_t n, const int32_t *envs, const sf_travel_out *out)
+{
+    const char *who = "sf_travel";
+    if (!s || !p || !out) return fail(SF_EINVAL, "sf_travel: null argument");
+    const Geo &g = s->g;
+    if (n < 0 || (n > 0 && !envs)) return fail(SF_EINVAL, "sf_travel: bad environment list");
+    if (p->source_mask < 0 || p->source_mask > 63) return fail(SF_EINVAL, "sf_travel: source_mask %d (bit s selects BurnStatus s: 0..63)", p->source_mask);
+    if (p->through_mask < 1 || p->through_mask > 63) return fail(SF_EINVAL, "sf_travel: through_mask %d (bit s selects BurnStatus s: 1..63)", p->through_mask);
+    if (p->source_mask == 0 && !p->sources) return fail(SF_EINVAL, "sf_travel: source_mask 0 needs a sources plane");
+    if (p->connectivity != 0 && p->connectivity != 4 && p->connectivity != 8)
+        return fail(SF_EINVAL, "sf_travel: connectivity %d (0: the handle's diagonal_spread, 4, 8)", p->connectivity);
+    SF_TRY(check_points(who, p->k, p->points, true));
+    if (out->point_minutes && p->k == 0) return fail(SF_EINVAL, "sf_travel: point_minutes needs k > 0");
+    if (p->k > 0 && !out->point_minutes) return fail(SF_EINVAL, "sf_travel: points without point_minutes");
+    if (!(p->max_minutes >= 0.0f)) return fail(SF_EINVAL, "sf_travel: max_minutes %g (0: no cap, or > 0)", (double)p->max_minutes);
+    SF_TRY(check_reserved(who, p->reserved[0] | p->reserved[1]));
+    if (!out->minutes && !out->pred && !out->point_minutes && !out->reached && !out->last && !out->activations)
+        return fail(SF_EINVAL, "sf_travel: every output is null");
+    SF_TRY(check_aligned(who, ((uintptr_t)out->minutes | (uintptr_t)out->point_minutes | (uintptr_t)out->reached | (uintptr_t)out->last |
+                               (uintptr_t)out->activations | (uintptr_t)p->points) & 3));
+    const size_t need = (size_t)travel_env_bytes(g);
+    SF_TRY(check_scratch(who, p->scratch_bytes, need, "need"));
+    SF_TRY(check_envs(s, who, n, envs));
+    if (g.W > kTravelMaxWidth) return fail(SF_ENOTSUP, "sf_travel: grids wider than %d cells are not supported (width %d)", kTravelMaxWidth, g.W);
+    const long long tiles = (long long)((g.W + kTravelTile - 1) / kTravelTile) * ((g.H + kTravelTile - 1) / kTravelTile);
+    if (tiles > kTravelMaxTiles) return fail(SF_ENOTSUP, "sf_travel: a %d x %d grid has more than %d tiles", g.H, g.W, kTravelMaxTiles);
+    SF_TRY(begin_call(s, who, kNeedRt | kNeedReset | kNotVoid));
+    if (n == 0) return SF_OK;
+
+    QueryState &q = s->travel;
+    const size_t cells = (size_t)g.H * g.W;
+    int chunk = std::min(n, 65535);
+    if (!out->minutes) {
+        chunk = query_chunk(n, p->scratch_bytes, kTravelScratchDefault, need, 65535);
+        SF_TRY(scratch_reserve(s, q, (size_t)chunk * need));
+    }
+    const int32_t *envs_dev = nullptr;
+    SF_TRY(block_stage(s, q.blk, &envs_dev, envs, (size_t)n * sizeof(int32_t)));
+
+    TravelArgs a;
+    memset(&a, 0, sizeof a);
+    a.g = g;
+    a.status = s->status;
+    a.cells = cur_cells(s);
+    a.rt = s->rt;
+    a.sources = p->sources;
+    a.src_env = p->sources_per_env ? (long long)cells : 0;
+    a.passable = p->passable;
+    a.pass_env = p->passable_per_env ? (long long)cells : 0;
+    a.k = p->k;
+    a.smask = (uint32_t)p->source_mask;
+    a.tmask = (uint32_t)p->through_mask;
+    a.conn8 = p->connectivity == 0 ? g.diag : (p->connectivity == 8);
+    a.cap = p->max_minutes > 0.0f ? p->max_minutes : HUGE_VALF;
+    a.work_env = out->minutes ? (long long)cells : (long long)(need / sizeof(float));
+    a.fix_cap = out->minutes && p->max_minutes > 0.0f;
+    a.pred_vec = out->pred && g.W % 4 == 0 && !((uintptr_t)out->pred & 3);
+    const size_t lds = (size_t)((tiles + 31) / 32) * 2 * sizeof(uint32_t);
+    for (int c0 = 0; c0 < n; c0 += chunk) {
+        const int cn = std::min(chunk, n - c0);
+        a.envs = envs_dev + c0;
+        a.points = p->k ? p->points + (size_t)c0 * p->k * 3 : nullptr;
+        a.work = out->minutes ? out->minutes + (size_t)c0 * cells : reinterpret_cast<float *>(q.mem);
+        a.work_vec = g.W % 4 == 0 && !((uintptr_t)a.work & 15);
+        a.pred = out->pred ? out->pred + (size_t)c0 * cells : nullptr;
+        a.point_minutes = out->point_minutes ? out->point_minutes + (size_t)c0 * p->k : nullptr;
+        a.reached = out->reached ? out->reached + c0 : nullptr;
+        a.last = out->last ? out->last + c0 : nullptr;
+        a.activations = out->activations ? out->activations + c0 : nullptr;
+        hipLaunchKernelGGL(k_travel, dim3((unsigned)cn), dim3(kTravelThreads), lds, s->stream, a);
+    }
+    return finish_call(s, who, !s->async, nullptr);
 }
 
 // ----------------------------------------------------------------------------- fire behaviour

@@ -4,7 +4,7 @@ This is the only module that touches the HIP library; the reference-shaped class
 ``fire.py`` / ``simulation.py`` are written on top of it.  Arrays cross the boundary as
 NumPy host arrays (copied during the call) or as torch CUDA tensors, read and written in place; torch is imported only by the
 methods that take or return one.  Layout (binding map): argument checks in ``_args.py``, one request class per feature
-(``observe.py``, ``render.py``, ``distance.py``, ``reach.py``, ``walk.py``, ``behavior.py``, ``ensemble.py``), and one frame, ``_device_call``, for every call
+(``observe.py``, ``render.py``, ``distance.py``, ``reach.py``, ``walk.py``, ``travel.py``, ``behavior.py``, ``ensemble.py``), and one frame, ``_device_call``, for every call
 that hands the library a tensor.
 """
 import ctypes as C
@@ -943,6 +943,45 @@ class FireEngine:
         if spec.n:
             p, o = spec.params(), spec.out(res)
             self._device_call(self._L.sf_walk, C.byref(p), spec.n, _ptr(spec.envs), C.byref(o), tensors=list(res.values()) + spec.device_tensors())
+        return res
+
+    # ---------------------------------------------------------------- fire travel time
+    TRAVEL_BLOCKED = _lib.SF_TRAVEL_BLOCKED
+
+    def travel_scratch_bytes(self):
+        from . import travel
+        return travel.scratch_need(self.H, self.W)
+
+    def travel(self, source=("BURNING",), through=("UNBURNED",), envs=None, connectivity=None, passable=None, sources=None, points=None,
+               max_minutes=None, plane=True, pred=False, reached=False, last=False, scratch_bytes=0, activations=False):
+        """WHEN the fire of ``envs`` (default: all, in order; any order, repeats allowed) gets to every cell: the minimum travel time
+        in minutes from now over the rate-of-spread table the handle holds now (``sf_travel``).  A forecast in
+        continuous time over the automaton's own graph - cell c is entered from its neighbour ``SRC_OFFSETS[k]`` after
+        ``pixel_scale / rt[k][c]`` minutes -, NOT the automaton: no whole updates, no burn-out of sources.  Sources: the cells whose
+        BurnStatus ``source`` selects, or - with ``sources``, a uint8 CUDA tensor [H, W] for all or [n_envs, H, W] indexed by
+        environment number - the cells where that is not 0 (``source`` may then be ``None``).  Passable: the cells ``through`` selects
+        and, with ``passable`` (same forms), only where it is not 0 - a candidate control line costs a plane, not a fork of the
+        state.  ``source`` / ``through``: masks (bit s = BurnStatus s) or iterables of ``BurnStatus`` members, names or ints; they
+        may overlap, a cell that is both is a source.  ``connectivity`` 4, 8 or None (the simulation's ``diagonal_spread``).  Read
+        from whichever cell plane is current; no state of the handle changes.
+        Returns a dict of torch tensors on this GPU, one per output asked for: with ``plane`` ``minutes`` float32 [n, H, W] (+inf
+        where no route arrives, ``TRAVEL_BLOCKED`` = -1 on cells that are neither source nor passable); with ``pred`` ``pred`` int8
+        [n, H, W], the index into ``SRC_OFFSETS`` of the neighbour the fastest route comes from (-1 on sources, unreached and blocked
+        cells); with ``points`` - int32 CUDA [n, k, 3] = (column, row, id), k <= 256, e.g. ``agents_device()`` - ``point_minutes``
+        float32 [n, k] (the plane's value; on a blocked cell the time at which it would be reached were it passable; -1 for id <= 0
+        or off the grid); ``reached`` int32 [n]: passable cells with a route; ``last`` float32 [n]: the largest finite time;
+        ``activations`` int32 [n]: tiles the search loaded (measurement).  ``max_minutes`` = M: the search stops at M, values above
+        M, +inf included, are reported as M and ``pred`` is -1 there.  ``scratch_bytes``: the most scratch a call without ``plane``
+        may use (0: 1 GiB); less than ``travel_scratch_bytes()`` is a ``ValueError``.  Torch's queued work is waited for first; in
+        async mode the call only enqueues: the tensors are complete after ``sync()`` and kept alive until then."""
+        from .travel import TravelSpec
+        spec = TravelSpec(self.n_envs, self.H, self.W, source=source, through=through, envs=envs, connectivity=connectivity,
+                          passable=passable, sources=sources, points=points, max_minutes=max_minutes, plane=plane, pred=pred,
+                          reached=reached, last=last, activations=activations, scratch_bytes=scratch_bytes)
+        res = self._outputs("travel", spec)
+        if spec.n:
+            p, o = spec.params(), spec.out(res)
+            self._device_call(self._L.sf_travel, C.byref(p), spec.n, _ptr(spec.envs), C.byref(o), tensors=list(res.values()) + spec.device_tensors())
         return res
 
     # ---------------------------------------------------------------- fire behaviour (DESIGN.md section 25)

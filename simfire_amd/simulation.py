@@ -34,6 +34,22 @@ def _total_updates(time: Union[str, int], update_rate: float) -> int:
     raise TypeError("time must be a string such as '1h 30m' or an int number of updates")
 
 
+def _travel_unit(r, unit, update_rate):
+    """The times of a ``travel`` result (torch tensors) in ``unit``: "minutes" as they are, "updates" divided by
+    float32(update_rate) - every value below 0 (blocked cells, padding points) stays what it is."""
+    if unit == "minutes":
+        return r
+    if unit != "updates":
+        raise ValueError(f"time_to_fire: unit must be 'minutes' or 'updates', got {unit!r}")
+    import torch
+    out = dict(r)
+    for name in ("minutes", "point_minutes", "last"):
+        if name in out:
+            v = out[name]
+            out[name] = torch.where(v < 0, v, v / np.float32(update_rate))
+    return out
+
+
 class _TerrainView:
     """What ``FireSimulation.terrain`` exposes to callers: ``fuels`` and ``elevations``."""
 
@@ -618,6 +634,22 @@ class FireSimulation:
                               max_moves=max_moves, plane=True)
         self._engine.sync()
         return r["moves"][0].cpu().numpy()
+
+    def time_to_fire(self, source=("BURNING",), through=("UNBURNED",), connectivity=None, passable=None, sources=None, max_minutes=None,
+                     unit="minutes"):
+        """WHEN the fire gets to every cell: the minimum travel time from the cells whose BurnStatus is one of ``source`` (or where
+        ``sources``, a uint8 CUDA tensor [H, W], is not 0) through the cells whose BurnStatus is one of ``through`` (and where
+        ``passable``, same form, is not 0), over the rates of spread as they stand - a forecast in continuous time, not the
+        automaton's own arrival.  Returns the NumPy float32 plane [H, W] in minutes (``unit="updates"``: divided by the update
+        rate): 0 on sources, +inf where no route arrives, -1 on cells that are neither; ``max_minutes`` caps the values.  Host edits
+        of ``fire_map`` are pushed to the device first, as ``moves_to`` does (``BatchedFireSimulation.time_to_fire``; DESIGN.md
+        section 26)."""
+        _travel_unit({}, unit, 1.0)                              # (a bad unit raises before anything is done)
+        self._sync_to_device()
+        r = self._engine.travel(source, through, envs=[0], connectivity=connectivity, passable=passable, sources=sources,
+                                max_minutes=max_minutes, plane=True)
+        self._engine.sync()
+        return _travel_unit(r, unit, float(self._engine.params.update_rate))["minutes"][0].cpu().numpy()
 
     def fire_behavior(self, status=None, flame_limit=None, planes=("flame_length",)):
         """Fire behaviour per cell from the rates of spread as they stand: a dict of NumPy [H, W] planes, any of ``hpa`` (heat per
@@ -1394,6 +1426,31 @@ class BatchedFireSimulation:
         r = self._engine.walk(target, through, envs=envs, connectivity=connectivity, passable=passable, targets=targets, points=points,
                               max_moves=max_moves, plane=bool(plane), step=bool(step), reached=True, levels=True)
         self._engine.sync()
+        return r if device else {k: v.cpu().numpy() for k, v in r.items()}
+
+    def time_to_fire(self, source=("BURNING",), through=("UNBURNED",), envs=None, connectivity=None, passable=None, sources=None,
+                     points=None, max_minutes=None, plane=True, pred=False, reached=False, last=False, scratch_bytes=0, agents=False,
+                     unit="minutes", device=True):
+        """WHEN the fires of ``envs`` (default: all) get to every cell: the minimum travel time from the cells whose BurnStatus is
+        one of ``source`` (or where ``sources``, uint8 CUDA [H, W] or [n_envs, H, W], is not 0) through the cells whose BurnStatus
+        is one of ``through`` (and where ``passable``, same forms, is not 0), over the rate-of-spread tables as they stand (after
+        ``set_wind`` too).  A forecast in continuous time - Finney's minimum travel time on the automaton's graph -, not the
+        automaton's own arrival: no whole updates, no burn-out.  A dict: with ``plane`` ``minutes`` float32 [n, H, W] (0 on sources,
+        +inf where no route arrives, -1 on cells that are neither), with ``pred`` the int8 index into ``SRC_OFFSETS`` of the
+        neighbour the fastest route comes from, ``reached`` int32 [n], ``last`` float32 [n]; with ``agents=True`` ``point_minutes``
+        float32 [n, k] for the device positions of a ``BatchedFireEnv`` (every environment in order), or ``points`` / ``agents`` =
+        a tensor [n, k, 3] = (column, row, id) of the caller's: the time until each is reached.  ``max_minutes`` caps the search
+        and the values.  ``unit="updates"`` divides the times by float32(update_rate) and leaves -1 as it is.  ``device=True``
+        returns torch tensors on this GPU, else NumPy arrays; complete on return either way (one wait).  One call, no fork of the
+        state, no change to the simulation."""
+        if points is not None and agents is not False:
+            raise ValueError("time_to_fire: give points or agents, not both")
+        _travel_unit({}, unit, 1.0)                              # (a bad unit raises before anything is done)
+        pts = points if points is not None else self._agent_points(agents)
+        r = self._engine.travel(source, through, envs=envs, connectivity=connectivity, passable=passable, sources=sources, points=pts,
+                                max_minutes=max_minutes, plane=plane, pred=pred, reached=reached, last=last, scratch_bytes=scratch_bytes)
+        self._engine.sync()
+        r = _travel_unit(r, unit, float(self._engine.params.update_rate))
         return r if device else {k: v.cpu().numpy() for k, v in r.items()}
 
     def fire_behavior(self, envs=None, status=None, summary=("BURNING",), flame_limit=None, edges=None, agents=False,

@@ -66,11 +66,18 @@ class BatchedFireEnv:
     largest over the environment (``FireEngine.behavior``), both from the state the observation shows.  Off by
     default: calls and ``info`` are what they are without it.
 
+    ``time_to_fire``: ``None``, or a dict with ``source``, ``through`` (BurnStatus members, names or ints; default BURNING /
+    UNBURNED), ``passable`` (uint8 CUDA [H, W] or [n_envs, H, W]) and ``max_minutes``: ``info["minutes_to_fire"]`` is then float32
+    [n_envs, n_agents], the minimum travel time of the fire to every agent's cell in minutes (``FireEngine.travel``, the point form;
+    DESIGN.md section 26) - on a cell the fire cannot enter, such as the line an agent has just drawn, the time at which it would be
+    reached were it passable -, from the state the observation shows.  A forecast over the rates of spread, not the automaton's own
+    arrival.  Off by default: calls and ``info`` are what they are without it.
+
     Agents are not part of an environment's state: ``clone_envs`` / ``get_state`` / ``set_state`` do not carry them."""
 
     def __init__(self, sim, n_agents, start_xy, n_updates=1, weights=(-1, 0, 0, 0), only_unburned=True, done_on_burn=False,
                  max_ticks=0, auto_reset=True, obs=None, values=None, value_weight=None, fire_distance=None, reach=None,
-                 moves_to=None, behavior=None):
+                 moves_to=None, behavior=None, time_to_fire=None):
         self.sim = sim
         self.engine = sim._engine
         self.n_envs, self.n_agents = int(sim.n_envs), int(n_agents)
@@ -118,6 +125,17 @@ class BatchedFireEnv:
                              targets=self.moves_to["targets"] is not None)
             except ValueError as err:
                 raise ValueError(f"BatchedFireEnv: moves_to: {err}") from None
+        self.time_to_fire = None
+        if time_to_fire is not None:
+            if not isinstance(time_to_fire, dict) or set(time_to_fire) - {"source", "through", "passable", "max_minutes"}:
+                raise ValueError("BatchedFireEnv: time_to_fire is None or a dict of source, through, passable and max_minutes")
+            self.time_to_fire = dict(source=time_to_fire.get("source", ("BURNING",)), through=time_to_fire.get("through", ("UNBURNED",)),
+                                     passable=time_to_fire.get("passable"), max_minutes=time_to_fire.get("max_minutes"))
+            from . import travel                                    # (raises before anything is created)
+            try:
+                travel.request(self.time_to_fire["source"], self.time_to_fire["through"], None, self.time_to_fire["max_minutes"])
+            except ValueError as err:
+                raise ValueError(f"BatchedFireEnv: time_to_fire: {err}") from None
         self.behavior = None
         if behavior is not None:
             if not isinstance(behavior, dict) or set(behavior) - {"flame_limit", "edges", "summary"}:
@@ -159,6 +177,8 @@ class BatchedFireEnv:
         if info is not None and self.behavior is not None:
             r = self.engine.behavior(points=self.engine.agents_device(), planes=(), stats=True, **self.behavior)
             info["flame_length"], info["max_flame"] = r["point_flame"], r["max_flame"]
+        if info is not None and self.time_to_fire is not None:
+            info["minutes_to_fire"] = self.engine.travel(points=self.engine.agents_device(), plane=False, **self.time_to_fire)["point_minutes"]
         self.engine.sync()
         return obs
 
