@@ -701,6 +701,74 @@ typedef struct sf_behavior_out {         /* device pointers, any may be NULL, at
  * work on points and the outputs before the call. */
 int sf_behavior(sf_sim *sim, const sf_behavior_params *params, const sf_behavior_out *out, const int32_t *envs /* [n] host */, int32_t n);
 
+/* Perimeters of the fire: WHERE the edge of a set S of cells runs - its length, the cells of S that lie on it,
+ * and the edge itself as ordered polygons.  All integers; the reference has no counterpart, the semantics are this library's own.
+ * S, for a listed environment, comes from exactly one of three sources:
+ *   status_mask in 1..63: the cells whose status byte & 7, read from whichever cell plane is current, the mask selects;
+ *   member: a device u8 plane, dense [height * width], one for all or - member_per_env - one per environment, indexed by the
+ *   environment's number: the cells where it is not 0;
+ *   at_update >= 0: the cells whose arrival is not "never" and is <= at_update (the raw plane of sf_arrival_device: uint32 update + 1,
+ *   0 = never; needs sf_enable_arrival).
+ * Cells off the grid are not in S.
+ * Lattice: cell (x = column, y = row) is the square [x, x + 1] x [y, y + 1], y pointing down; vertices (vx, vy), 0 <= vx <= width,
+ * 0 <= vy <= height.  A directed crack edge leaves its tail vertex in direction d (0: +x, 1: +y, 2: -x, 3: -y) and exists iff its
+ * right cell is in S and its left cell is not; relative to the tail the (right, left) cells are d = 0: (0, 0), (0, -1); 1: (-1, 0),
+ * (0, 0); 2: (-1, -1), (-1, 0); 3: (0, -1), (-1, -1).  Outer loops therefore run E, S, W, N and the shoelace sum
+ * 1/2 sum (x_i * y_i+1 - x_i+1 * y_i) is positive for them and negative for holes.
+ * Successor: at an edge's head, AR and AL are the right and the left cell of an edge leaving the head in direction d (the cells
+ * ahead).  connectivity 4 (diagonal neighbours are separate): AR not in S: d + 1; else AL not in S: d; else d + 3.  connectivity 8
+ * (diagonal neighbours are joined): AL in S: d + 3; else AR in S: d; else d + 1.  0: the handle's diagonal_spread.
+ * Canonical order: an edge's id is (vy * (width + 1) + vx) * 4 + d of its tail; a loop starts at its smallest-id edge, loops are
+ * listed by that id, a loop's vertices are the tails of its edges in order - with simplify only the tails where the direction
+ * changes (the start vertex always is one).
+ * Cheap outputs (no tracing): edges int32 [n], the perimeter in cell edges; cells int32 [n], |S|; front uint8 [n][height][width], 1
+ * where a cell of S has at least one crack edge, else 0.
+ * Traced outputs: loops, holes int32 [n] (holes: the loops of negative area); n_vertices int32 [n], the vertex count of the full
+ * answer, also when it exceeds the capacity; vertices int32 [n][max_vertices][2] = (x, y); loop_start int32 [n][max_loops + 1], loop
+ * l's vertices are [loop_start[l], loop_start[l + 1]); loop_area int32 [n][max_loops], signed, in cells; loop_edges int32
+ * [n][max_loops].  The signed areas of an environment add up to |S|.
+ * Overflow is decided per environment, never by a failure of the call: more than max_edges edges give -1 in loops, holes and
+ * n_vertices and leave that environment's rows of the four lists untouched; n_vertices > max_vertices or loops > max_loops alone
+ * leave the counts right and the four lists untouched; the entries of a list beyond the answer's are never written.  edges, cells and
+ * front are always right. */
+typedef struct sf_perimeter_params {
+    int32_t status_mask;                 /* 1..63, or 0 with member or at_update */
+    int32_t at_update;                   /* -1: off */
+    int32_t connectivity;                /* 0 (the handle's diagonal_spread), 4, 8 */
+    int32_t simplify;                    /* != 0: corners only */
+    int32_t member_per_env;              /* member is [n_envs][H*W] (indexed by environment number), else [H*W] */
+    int32_t max_edges, max_vertices, max_loops;      /* capacities per listed environment, >= 0 */
+    const uint8_t *member;               /* device, or NULL */
+    int64_t scratch_bytes;               /* 0: the default budget */
+    int32_t reserved[2];                 /* 0 */
+} sf_perimeter_params;
+typedef struct sf_perimeter_out {        /* device pointers, any may be NULL, at least one not */
+    int32_t *edges, *cells;              /* [n] */
+    uint8_t *front;                      /* [n][H][W] dense */
+    int32_t *loops, *holes, *n_vertices; /* [n] */
+    int32_t *vertices;                   /* [n][max_vertices][2] */
+    int32_t *loop_start;                 /* [n][max_loops + 1] */
+    int32_t *loop_area, *loop_edges;     /* [n][max_loops] */
+} sf_perimeter_out;
+/* Environment envs[i] (a host array; any order, repeats allowed) lands in row i of every output.  Anything invalid is SF_EINVAL before
+ * anything is enqueued (a null argument, a bad environment list, none or more than one of the three sources, status_mask outside
+ * 0..63, at_update < -1, an unknown connectivity, a negative capacity, vertices with max_vertices == 0 or a loop list with max_loops
+ * == 0, every output null, an int32 output not aligned to 4 bytes, a positive scratch_bytes below one environment's need, reserved
+ * != 0, an environment out of range); a grid wider than 8192 cells, or of 2^25 or more edge words ((height + 1) * ceil((width + 1) /
+ * 16)), is SF_ENOTSUP; a handle without a reset is SF_ESTATE, and so is at_update without arrival recording.
+ * Without a traced output ONE streaming launch (k_perim_summary) serves the whole list and no scratch is used.  With one, one
+ * workgroup traces one environment (k_perim_trace): the edges are ranked in id order, every loop is found by pointer doubling over
+ * the successor permutation, positions, vertex numbers and areas come from scans - no result depends on scheduling.  Its scratch
+ * belongs to the handle: per listed environment of a chunk 8 * height * ceil(width / 64) + 12 * (height + 1) * ceil((width + 1) / 16)
+ * + 32 * max_edges bytes rounded up to 256 - allocated at the first such call, grown (never shrunk) when a later call needs more,
+ * freed by sf_destroy, counted by sf_memory_bytes; a growth is a hipMalloc and waits for the device.  The default budget is 1 GiB; the
+ * list is worked through in chunks so that scratch never exceeds the budget, which changes no bit of the result.
+ * The call reads the state and writes nothing but its outputs and its own scratch - not the current plane, the tile books, the
+ * reference point of sf_get_fire_map_delta, the result block, any ring, the arrival or value planes.  In async mode the call only
+ * enqueues (the outputs are complete when the handle's stream has got there); the caller orders its own work on member and the
+ * outputs before the call. */
+int sf_perimeter(sf_sim *sim, const sf_perimeter_params *params, int32_t n, const int32_t *envs /* [n] host */, const sf_perimeter_out *out);
+
 /* Agents on the device: K agents per environment that walk the grid and draw control lines where they stand,
  * stepped from a policy's action tensor without a host read.  The reference records agent positions only (simulation.py:480-499) and
  * leaves the loop to the harness (the run docstring, 505-509); the semantics are this library's own.

@@ -175,6 +175,20 @@ class SfBehaviorOut(C.Structure):
                 ("point_flame", C.c_void_p)]
 
 
+class SfPerimeterParams(C.Structure):
+    """``sf_perimeter_params`` (include/simfire_hip.h)."""
+    _fields_ = [("status_mask", C.c_int32), ("at_update", C.c_int32), ("connectivity", C.c_int32), ("simplify", C.c_int32),
+                ("member_per_env", C.c_int32), ("max_edges", C.c_int32), ("max_vertices", C.c_int32), ("max_loops", C.c_int32),
+                ("member", C.c_void_p), ("scratch_bytes", C.c_int64), ("reserved", C.c_int32 * 2)]
+
+
+class SfPerimeterOut(C.Structure):
+    """``sf_perimeter_out`` (include/simfire_hip.h): device pointers, any may be null, not all."""
+    _fields_ = [("edges", C.c_void_p), ("cells", C.c_void_p), ("front", C.c_void_p), ("loops", C.c_void_p), ("holes", C.c_void_p),
+                ("n_vertices", C.c_void_p), ("vertices", C.c_void_p), ("loop_start", C.c_void_p), ("loop_area", C.c_void_p),
+                ("loop_edges", C.c_void_p)]
+
+
 # name -> argtypes; every function returns int except the two string getters
 _VP, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
 SIGNATURES = {
@@ -248,6 +262,7 @@ SIGNATURES = {
     "sf_travel": [_VP, C.POINTER(SfTravelParams), _I32, _VP, C.POINTER(SfTravelOut)],
     "sf_behavior": [_VP, C.POINTER(SfBehaviorParams), C.POINTER(SfBehaviorOut), _VP, _I32],
     "sf_get_behavior_builds": [_VP, C.POINTER(_I64)],
+    "sf_perimeter": [_VP, C.POINTER(SfPerimeterParams), _I32, _VP, C.POINTER(SfPerimeterOut)],
     "sf_cell_layout": [_VP, C.POINTER(_I32)],
     "sf_render": [_VP, C.POINTER(SfRenderParams), _I32, _VP, _VP],
     "sf_status_device": [_VP, C.POINTER(_VP)],

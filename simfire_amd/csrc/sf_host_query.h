@@ -1,4 +1,4 @@
-// Host code of the queries: sf_distance, sf_reach (23), sf_walk (24), sf_behavior (25) and sf_travel (26).  Each takes a list
+// Host code of the queries: sf_distance, sf_reach (23), sf_walk (24), sf_behavior (25), sf_travel (26) and sf_perimeter (27).  Each takes a list
 // of environments, optional points and caller-owned device outputs, reads the state and changes none of it.  Included once from
 // simfire_hip.hip, behind sf_host_views.h.
 //
@@ -456,4 +456,102 @@ extern "C" int sf_get_behavior_builds(sf_sim *s, int64_t *n_out)
     if (!s || !n_out) return fail(SF_EINVAL, "sf_get_behavior_builds: null argument");
     *n_out = s->behavior.builds;
     return SF_OK;
+}
+
+// ----------------------------------------------------------------------------- perimeters of the fire
+// Without a traced output: the summary outputs zeroed, then ONE launch of k_perim_summary for the whole list - no scratch, no chunks.
+// With one: k_perim_trace, one workgroup per listed environment, chunk by chunk as the scratch budget allows (it writes edges and
+// cells itself); a front plane asked for beside it comes from a launch of k_perim_summary.  The call block is the environment list.
+extern "C" int sf_perimeter(sf_sim *s, const sf_perimeter_params *p, int32_t n, const int32_t *envs, const sf_perimeter_out *out)
+{
+    const char *who = "sf_perimeter";
+    if (!s || !p || !out) return fail(SF_EINVAL, "sf_perimeter: null argument");
+    const Geo &g = s->g;
+    if (n < 0 || (n > 0 && !envs)) return fail(SF_EINVAL, "sf_perimeter: bad environment list");
+    if (p->status_mask < 0 || p->status_mask > 63) return fail(SF_EINVAL, "sf_perimeter: status_mask %d (bit s selects BurnStatus s: 1..63, or 0 with member or at_update)", p->status_mask);
+    if (p->at_update < -1) return fail(SF_EINVAL, "sf_perimeter: at_update %d (-1: off, or an update >= 0)", p->at_update);
+    const int sources = (p->status_mask != 0) + (p->member != nullptr) + (p->at_update >= 0);
+    if (sources != 1) return fail(SF_EINVAL, "sf_perimeter: %s (exactly one of status_mask, member, at_update)", sources ? "more than one source" : "no source");
+    if (p->connectivity != 0 && p->connectivity != 4 && p->connectivity != 8)
+        return fail(SF_EINVAL, "sf_perimeter: connectivity %d (0: the handle's diagonal_spread, 4, 8)", p->connectivity);
+    if (p->max_edges < 0 || p->max_vertices < 0 || p->max_loops < 0)
+        return fail(SF_EINVAL, "sf_perimeter: negative capacity (max_edges %d, max_vertices %d, max_loops %d)", p->max_edges, p->max_vertices, p->max_loops);
+    if (out->vertices && p->max_vertices == 0) return fail(SF_EINVAL, "sf_perimeter: vertices needs max_vertices > 0");
+    if ((out->loop_start || out->loop_area || out->loop_edges) && p->max_loops == 0)
+        return fail(SF_EINVAL, "sf_perimeter: loop_start, loop_area and loop_edges need max_loops > 0");
+    const bool traced = out->loops || out->holes || out->n_vertices || out->vertices || out->loop_start || out->loop_area || out->loop_edges;
+    if (!traced && !out->edges && !out->cells && !out->front) return fail(SF_EINVAL, "sf_perimeter: every output is null");
+    SF_TRY(check_aligned(who, ((uintptr_t)out->edges | (uintptr_t)out->cells | (uintptr_t)out->loops | (uintptr_t)out->holes | (uintptr_t)out->n_vertices |
+                               (uintptr_t)out->vertices | (uintptr_t)out->loop_start | (uintptr_t)out->loop_area | (uintptr_t)out->loop_edges) & 3));
+    const size_t need = traced ? (size_t)perim_env_bytes(g.H, g.W, p->max_edges) : 0;
+    SF_TRY(check_scratch(who, p->scratch_bytes, need, "need"));
+    SF_TRY(check_reserved(who, p->reserved[0] | p->reserved[1]));
+    SF_TRY(check_envs(s, who, n, envs));
+    if (g.W > kPerimMaxWidth) return fail(SF_ENOTSUP, "sf_perimeter: grids wider than %d cells are not supported (width %d)", kPerimMaxWidth, g.W);
+    if ((long long)(g.H + 1) * ((g.W + 16) / 16) >= (1ll << 25)) return fail(SF_ENOTSUP, "sf_perimeter: the edge ids of a %d x %d grid do not fit int32", g.H, g.W);
+    SF_TRY(check_ready(s, who, kNeedReset));
+    if (p->at_update >= 0 && !s->arrival.plane) return fail(SF_ESTATE, "sf_perimeter: at_update needs arrival recording (sf_enable_arrival)");
+    SF_TRY(begin_call(s, who, kNeedReset | kNotVoid));
+    if (n == 0) return SF_OK;
+
+    QueryState &q = s->perimeter;
+    PerimArgs a;
+    memset(&a, 0, sizeof a);
+    const size_t cells = (size_t)g.H * g.W;
+    int chunk = n;
+    if (traced) {
+        chunk = query_chunk(n, p->scratch_bytes, kPerimScratchDefault, need, 65535);
+        SF_TRY(scratch_reserve(s, q, (size_t)chunk * need));
+    }
+    const int32_t *envs_dev = nullptr;
+    SF_TRY(block_stage(s, q.blk, &envs_dev, envs, (size_t)n * sizeof(int32_t)));
+    a.g.H = g.H; a.g.W = g.W; a.g.P = g.P; a.g.PV = g.PV; a.g.plane_env = g.plane_env; a.g.cells_env = g.cells_env;
+    a.status = s->status;
+    a.cells = cur_cells(s);
+    a.member = p->member;
+    a.mem_env = p->member_per_env ? (long long)cells : 0;
+    a.arrival = s->arrival.plane;
+    a.at = (uint32_t)std::max(p->at_update, 0);
+    a.source = p->member ? 1 : (p->at_update >= 0 ? 2 : 0);
+    mask_tables(p->status_mask, a.tlo, a.thi);
+    a.conn8 = p->connectivity == 0 ? g.diag : (p->connectivity == 8);
+    a.simplify = p->simplify != 0;
+    a.max_edges = p->max_edges; a.max_vertices = p->max_vertices; a.max_loops = p->max_loops;
+    a.BW = (g.W + 63) / 64; a.EW = (g.W + 16) / 16;
+    a.blocks_env = ((long long)((g.H + kPerimStrip - 1) / kPerimStrip) * a.BW + kPerimThreads - 1) / kPerimThreads;
+
+    if (!traced || out->front) {                 // the summary form, or the front plane of a traced call
+        PerimArgs b = a;
+        b.envs = envs_dev;
+        b.n = n;
+        b.total = (long long)n * b.blocks_env;
+        b.front = out->front;
+        b.front_vec = out->front && g.W % 16 == 0 && !((uintptr_t)out->front & 15);
+        if (!traced) {
+            b.edges = out->edges; b.ncells = out->cells;
+            if (out->edges) HIPCHK(hipMemsetAsync(out->edges, 0, (size_t)n * sizeof(int32_t), s->stream));
+            if (out->cells) HIPCHK(hipMemsetAsync(out->cells, 0, (size_t)n * sizeof(int32_t), s->stream));
+        }
+        const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>(b.total, (long long)s->n_cu * 8));
+        hipLaunchKernelGGL(k_perim_summary, dim3(grid), dim3(kPerimThreads), 0, s->stream, b);
+    }
+    if (traced) {
+        a.scratch = q.mem;
+        a.scratch_env = (long long)need;
+        for (int c0 = 0; c0 < n; c0 += chunk) {
+            a.n = std::min(chunk, n - c0);
+            a.envs = envs_dev + c0;
+            a.edges = out->edges ? out->edges + c0 : nullptr;
+            a.ncells = out->cells ? out->cells + c0 : nullptr;
+            a.loops = out->loops ? out->loops + c0 : nullptr;
+            a.holes = out->holes ? out->holes + c0 : nullptr;
+            a.n_vertices = out->n_vertices ? out->n_vertices + c0 : nullptr;
+            a.vertices = out->vertices ? out->vertices + (size_t)c0 * p->max_vertices * 2 : nullptr;
+            a.loop_start = out->loop_start ? out->loop_start + (size_t)c0 * ((size_t)p->max_loops + 1) : nullptr;
+            a.loop_area = out->loop_area ? out->loop_area + (size_t)c0 * p->max_loops : nullptr;
+            a.loop_edges = out->loop_edges ? out->loop_edges + (size_t)c0 * p->max_loops : nullptr;
+            hipLaunchKernelGGL(k_perim_trace, dim3((unsigned)a.n), dim3(kPerimTraceThreads), 0, s->stream, a);
+        }
+    }
+    return finish_call(s, who, !s->async, nullptr);
 }

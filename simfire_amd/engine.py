@@ -4,7 +4,7 @@ This is the only module that touches the HIP library; the reference-shaped class
 ``fire.py`` / ``simulation.py`` are written on top of it.  Arrays cross the boundary as
 NumPy host arrays (copied during the call) or as torch CUDA tensors, read and written in place; torch is imported only by the
 methods that take or return one.  Layout (binding map): argument checks in ``_args.py``, one request class per feature
-(``observe.py``, ``render.py``, ``distance.py``, ``reach.py``, ``walk.py``, ``travel.py``, ``behavior.py``, ``ensemble.py``), and one frame, ``_device_call``, for every call
+(``observe.py``, ``render.py``, ``distance.py``, ``reach.py``, ``walk.py``, ``travel.py``, ``behavior.py``, ``perimeter.py``, ``ensemble.py``), and one frame, ``_device_call``, for every call
 that hands the library a tensor.
 """
 import ctypes as C
@@ -1008,6 +1008,45 @@ class FireEngine:
         if spec.n:
             p, o = spec.params(), spec.out(res)
             self._device_call(self._L.sf_behavior, C.byref(p), C.byref(o), _ptr(spec.envs), spec.n, tensors=list(res.values()) + spec.device_tensors())
+        return res
+
+    # ---------------------------------------------------------------- fire perimeters
+    def perimeter_scratch_bytes(self, max_edges=None):
+        from . import perimeter
+        return perimeter.scratch_need(self.H, self.W, perimeter.default_capacities(self.H, self.W, max_edges)[0])
+
+    def perimeter(self, status=None, envs=None, member=None, at_update=None, connectivity=None, simplify=True, counts=True, front=False,
+                  trace=False, max_edges=None, max_vertices=None, max_loops=None, scratch_bytes=0):
+        """WHERE the edge of the fire of ``envs`` (default: all, in order; any order, repeats allowed) runs (``sf_perimeter``; DESIGN.md
+        section 27), in integers.  The set S is exactly one of: the cells whose BurnStatus ``status`` selects (a mask, or members, names
+        or ints; default BURNING | BURNED), read from whichever cell plane is current; the cells where ``member`` - a uint8 CUDA tensor
+        [H, W] for all or [n_envs, H, W] indexed by environment number - is not 0; the cells the fire had reached by update
+        ``at_update`` (needs ``enable_arrival``).  Cell (x, y) is the square [x, x + 1] x [y, y + 1], y down; the edge runs along the
+        cracks between a cell of S and a cell outside it (off the grid counts as outside).
+        Returns a dict of torch tensors on this GPU.  ``counts``: ``edges`` int32 [n], the perimeter in cell edges, and ``cells``
+        int32 [n], |S|.  ``front``: uint8 [n, H, W], 1 on the cells of S with a crack.  ``trace``: the edge as polygons in canonical
+        order - ``loops``, ``holes``, ``n_vertices`` int32 [n]; ``vertices`` int32 [n, max_vertices, 2] = (x, y) lattice corners;
+        ``loop_start`` int32 [n, max_loops + 1] (zeroed first); ``loop_area`` int32 [n, max_loops], signed: outer loops run clockwise
+        on the screen and are positive, holes negative; ``loop_edges`` int32 [n, max_loops] (``perimeter.rings`` cuts one
+        environment's lists into polygons).  ``connectivity`` 4 keeps diagonal neighbours apart, 8 joins them, None is the
+        simulation's ``diagonal_spread``; ``simplify`` keeps corners only.  Capacities per environment: ``max_edges`` (default
+        min(2 H W + 2, 2^18)), ``max_vertices`` (default ``max_edges``), ``max_loops`` (default ``max_edges // 4``); an environment
+        with more edges reports -1 in the three counts, one whose vertices or loops do not fit reports the right counts, and either
+        way its rows of the four lists are left as they were.  ``scratch_bytes``: the most scratch a traced call may use (0: 1 GiB);
+        less than ``perimeter_scratch_bytes(max_edges)`` is a ``ValueError``.  No state of the handle changes.  Torch's queued work
+        is waited for first; in async mode the call only enqueues: the tensors are complete after ``sync()`` and kept alive until
+        then."""
+        from .perimeter import PerimeterSpec
+        spec = PerimeterSpec(self.n_envs, self.H, self.W, status=status, envs=envs, member=member, at_update=at_update,
+                             connectivity=connectivity, simplify=simplify, counts=counts, front=front, trace=trace, max_edges=max_edges,
+                             max_vertices=max_vertices, max_loops=max_loops, scratch_bytes=scratch_bytes,
+                             arrival_on=bool(getattr(self, "arrival_on", False)))
+        res = self._outputs("perimeter", spec)
+        if "loop_start" in res:
+            res["loop_start"].zero_()
+        if spec.n:
+            p, o = spec.params(), spec.out(res)
+            self._device_call(self._L.sf_perimeter, C.byref(p), spec.n, _ptr(spec.envs), C.byref(o), tensors=list(res.values()) + spec.device_tensors())
         return res
 
     def behavior_builds(self):

@@ -34,6 +34,13 @@ def _total_updates(time: Union[str, int], update_rate: float) -> int:
     raise TypeError("time must be a string such as '1h 30m' or an int number of updates")
 
 
+def _perimeter_unit(unit, pixel_scale):
+    """The factor of a ``perimeter`` result's lengths in ``unit``: "cells" 1, "ft" ``pixel_scale``."""
+    if unit not in ("cells", "ft"):
+        raise ValueError(f'perimeter: unit must be "cells" or "ft", got {unit!r}')
+    return 1.0 if unit == "cells" else float(pixel_scale)
+
+
 def _travel_unit(r, unit, update_rate):
     """The times of a ``travel`` result (torch tensors) in ``unit``: "minutes" as they are, "updates" divided by
     float32(update_rate) - every value below 0 (blocked cells, padding points) stays what it is."""
@@ -650,6 +657,31 @@ class FireSimulation:
                                 max_minutes=max_minutes, plane=True)
         self._engine.sync()
         return _travel_unit(r, unit, float(self._engine.params.update_rate))["minutes"][0].cpu().numpy()
+
+    def perimeter(self, status=None, at_update=None, connectivity=None, simplify=True, unit="cells", max_edges=None):
+        """WHERE the fire's edge runs: the cracks between the cells whose BurnStatus is one of ``status`` (members, names or ints;
+        default BURNING | BURNED) - or, with ``at_update`` and ``record_arrival``, the cells the fire had reached by that update - and
+        the cells outside the set.  Returns a dict: ``length`` (the edge in cell edges; ``unit="ft"``: times ``pixel_scale``),
+        ``area`` (the cells of the set; ``"ft"``: times ``pixel_scale`` squared), ``loops``, ``holes`` and ``rings``, a list of
+        ``(ndarray[m, 2] of (x, y) corners, is_hole)`` in canonical order - lattice corners, cell (x, y) being the square
+        [x, x + 1] x [y, y + 1] with y down; in ``"ft"`` float64 times ``pixel_scale``.  ``connectivity`` 4 keeps diagonal
+        neighbours apart, 8 joins them, None is the configured ``diagonal_spread``.  An answer of more than ``max_edges`` edges
+        (default min(2 H W + 2, 2^18)) has ``loops`` = ``holes`` = -1 and no rings.  Host edits of ``fire_map`` are pushed to the
+        device first, as ``moves_to`` does (``BatchedFireSimulation.perimeter``)."""
+        _perimeter_unit(unit, 1.0)                               # (a bad unit raises before anything is done)
+        scale = _perimeter_unit(unit, float(self._engine.params.pixel_scale))
+        self._sync_to_device()
+        r = self._engine.perimeter(status, envs=[0], at_update=at_update, connectivity=connectivity, simplify=simplify, trace=True,
+                                   max_edges=max_edges)
+        self._engine.sync()
+        r = {k: v[0].cpu().numpy() for k, v in r.items()}
+        from .perimeter import rings
+        polys = rings(r["vertices"], r["loop_start"], r["loop_area"], loops=int(r["loops"]))
+        if scale != 1.0:
+            polys = [(v.astype(np.float64) * scale, hole) for v, hole in polys]
+        return dict(length=int(r["edges"]) * scale if scale != 1.0 else int(r["edges"]),
+                    area=int(r["cells"]) * scale * scale if scale != 1.0 else int(r["cells"]), loops=int(r["loops"]), holes=int(r["holes"]),
+                    rings=polys)
 
     def fire_behavior(self, status=None, flame_limit=None, planes=("flame_length",)):
         """Fire behaviour per cell from the rates of spread as they stand: a dict of NumPy [H, W] planes, any of ``hpa`` (heat per
@@ -1451,6 +1483,23 @@ class BatchedFireSimulation:
                                 max_minutes=max_minutes, plane=plane, pred=pred, reached=reached, last=last, scratch_bytes=scratch_bytes)
         self._engine.sync()
         r = _travel_unit(r, unit, float(self._engine.params.update_rate))
+        return r if device else {k: v.cpu().numpy() for k, v in r.items()}
+
+    def perimeter(self, status=None, envs=None, member=None, at_update=None, connectivity=None, simplify=True, front=False, trace=False,
+                  max_edges=None, max_vertices=None, max_loops=None, scratch_bytes=0, device=True):
+        """WHERE the edges of the fires of ``envs`` (default: all) run, in integers: the cracks between the cells of a set - BurnStatus
+        one of ``status`` (default BURNING | BURNED), or ``member`` (uint8 CUDA [H, W] or [n_envs, H, W]) not 0, or reached by update
+        ``at_update`` (needs ``record_arrival``) - and the cells outside it.  A dict: ``edges`` int32 [n], the perimeter in cell
+        edges, and ``cells`` int32 [n]; with ``front`` uint8 [n, H, W], 1 on the cells of the set that touch the edge; with ``trace``
+        the ordered polygons: ``loops``, ``holes``, ``n_vertices``, ``vertices`` [n, max_vertices, 2] = (x, y) lattice corners,
+        ``loop_start``, ``loop_area`` (signed: holes negative), ``loop_edges`` - ``simfire_amd.perimeter.rings`` cuts one
+        environment's lists into polygons.  Without ``trace`` the call is one streaming launch and needs no scratch.
+        ``device=True`` returns torch tensors on this GPU, else NumPy arrays; complete on return either way (one wait).  One call, no
+        host copy of the maps, no change to the simulation (``FireEngine.perimeter``)."""
+        r = self._engine.perimeter(status, envs=envs, member=member, at_update=at_update, connectivity=connectivity, simplify=simplify,
+                                   front=front, trace=trace, max_edges=max_edges, max_vertices=max_vertices, max_loops=max_loops,
+                                   scratch_bytes=scratch_bytes)
+        self._engine.sync()
         return r if device else {k: v.cpu().numpy() for k, v in r.items()}
 
     def fire_behavior(self, envs=None, status=None, summary=("BURNING",), flame_limit=None, edges=None, agents=False,

@@ -73,11 +73,17 @@ class BatchedFireEnv:
     reached were it passable -, from the state the observation shows.  A forecast over the rates of spread, not the automaton's own
     arrival.  Off by default: calls and ``info`` are what they are without it.
 
+    ``perimeter``: ``None``, or a dict with ``status`` (BurnStatus members, names or ints; default BURNING | BURNED):
+    ``info["fire_perimeter"]`` is then int32 [n_envs], the length of the fire's edge in cell edges, and ``info["fire_cells"]`` int32
+    [n_envs] the cells of the set (``FireEngine.perimeter``, the summary form: one streaming launch, nothing is traced or read back;
+    DESIGN.md section 27), both from the state the observation shows.  Off by default: calls and ``info`` are what they are
+    without it.
+
     Agents are not part of an environment's state: ``clone_envs`` / ``get_state`` / ``set_state`` do not carry them."""
 
     def __init__(self, sim, n_agents, start_xy, n_updates=1, weights=(-1, 0, 0, 0), only_unburned=True, done_on_burn=False,
                  max_ticks=0, auto_reset=True, obs=None, values=None, value_weight=None, fire_distance=None, reach=None,
-                 moves_to=None, behavior=None, time_to_fire=None):
+                 moves_to=None, behavior=None, time_to_fire=None, perimeter=None):
         self.sim = sim
         self.engine = sim._engine
         self.n_envs, self.n_agents = int(sim.n_envs), int(n_agents)
@@ -136,6 +142,16 @@ class BatchedFireEnv:
                 travel.request(self.time_to_fire["source"], self.time_to_fire["through"], None, self.time_to_fire["max_minutes"])
             except ValueError as err:
                 raise ValueError(f"BatchedFireEnv: time_to_fire: {err}") from None
+        self.perimeter = None
+        if perimeter is not None:
+            if not isinstance(perimeter, dict) or set(perimeter) - {"status"}:
+                raise ValueError("BatchedFireEnv: perimeter is None or a dict of status")
+            from . import perimeter as _perimeter                   # (raises before anything is created)
+            self.perimeter = dict(status=perimeter.get("status", _perimeter.DEFAULT_STATUS))
+            try:
+                _perimeter.request(self.perimeter["status"])
+            except ValueError as err:
+                raise ValueError(f"BatchedFireEnv: {err}") from None
         self.behavior = None
         if behavior is not None:
             if not isinstance(behavior, dict) or set(behavior) - {"flame_limit", "edges", "summary"}:
@@ -179,6 +195,9 @@ class BatchedFireEnv:
             info["flame_length"], info["max_flame"] = r["point_flame"], r["max_flame"]
         if info is not None and self.time_to_fire is not None:
             info["minutes_to_fire"] = self.engine.travel(points=self.engine.agents_device(), plane=False, **self.time_to_fire)["point_minutes"]
+        if info is not None and self.perimeter is not None:
+            r = self.engine.perimeter(**self.perimeter)
+            info["fire_perimeter"], info["fire_cells"] = r["edges"], r["cells"]
         self.engine.sync()
         return obs
 
