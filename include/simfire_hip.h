@@ -769,6 +769,98 @@ typedef struct sf_perimeter_out {        /* device pointers, any may be NULL, at
  * outputs before the call. */
 int sf_perimeter(sf_sim *sim, const sf_perimeter_params *params, int32_t n, const int32_t *envs /* [n] host */, const sf_perimeter_out *out);
 
+/* Influence of a cell on the fire: WHICH cells matter - how much of the fire passes, or passed, through each
+ * cell of a forest of parent pointers, and the route from a point up to its root.  The reference has the idea as
+ * FireSpreadGraph.get_descendant_heatmap (simfire/utils/graph.py:53-82), an all-pairs networkx.descendants loop; minimum-travel-time
+ * tools ship it as the influence grid and the major paths.  All results are integers and no bit depends on scheduling.
+ * Parent codes: a code is an index into the source offsets of the R table's planes, (dx, dy) = (+1,+1) (0,+1) (-1,+1) (+1,0) (-1,0)
+ * (+1,-1) (0,-1) (-1,-1): the convention of sf_travel's pred.  For a listed environment and a cell c, par(c) is c + offset[code] when
+ * 0 <= code <= 7 and that neighbour is on the grid; any other byte, or a code that points off the grid (a dense plane has no pitch
+ * padding: column `width` is off the grid), is "no parent", not an error.  A cell with a parent is a FOREST cell; a cell without a
+ * parent and with at least one child is a ROOT; C is the set of cells on a cycle of par (possible only with a caller's plane); D(c) is
+ * the set of cells d != c whose parent chain reaches c - for c outside C it is finite and holds no cell of C.
+ * pred_source says where the codes come from:
+ *   SF_INFLUENCE_PRED_PLANE: pred, a device int8 plane, dense: [n][height * width] with row i belonging to envs[i] (pred_per_env != 0;
+ *   what sf_travel writes) or one [height * width] for all;
+ *   SF_INFLUENCE_PRED_HISTORY: the ignition tree of the episode so far; needs sf_enable_spread_graph and sf_enable_arrival.  With a(c)
+ *   the value sf_get_arrival returns: a cell with a(c) < 0 has no parent; else the candidates are the neighbours n_j for which bit j is
+ *   set in c's parent mask (sf_get_spread_parents, graph.py:125-134's order), n_j is on the grid, a(n_j) >= 0 and a(n_j) < a(c); the
+ *   parent is the candidate of the greatest arrival (the newest, as the automaton's winner rule), ties go to the lowest code, no
+ *   candidate is a root.  The strict inequality makes the result acyclic although a line drawn on a burning cell ORs later parents
+ *   into its mask and cells painted by sf_load_fire_map have no arrival.
+ * Weights: w1(c) = 1, or include[c] != 0 with an include plane (device u8, one [height * width] for all or - include_per_env -
+ * [n_envs][height * width] indexed by environment number: the forms of sf_travel's passable).  wv(c) = w1(c) ? weight[c] : 0 where
+ * weight is the handle's value plane (weight_mode SF_INFLUENCE_WEIGHT_VALUES; needs sf_values_set) or the caller's weights, device
+ * int32, the same two forms (SF_INFLUENCE_WEIGHT_PLANE); with SF_INFLUENCE_WEIGHT_NONE value may not be asked for.  A cell with
+ * w1 = 0 still links its children to its ancestors.
+ * Plane outputs, dense [n][height][width]: cells int32 = sum of w1(d) over D(c), plus w1(c) with inclusive != 0; SF_INFLUENCE_CYCLE on
+ * C.  value int64 = the same sum with wv; 0 on C.  pred int8 = the sanitised codes actually used, -1 where there is no parent - with
+ * the history source the ignition tree itself.  forest, roots, cyclic int32 [n]: the three counts.
+ * With inclusive = 0, a history in which every ignition had exactly one BURNING neighbour makes cells equal the reference's
+ * len(nx.descendants(...)) before its uint8 cast; in general it is a lower bound: the tree keeps one parent where the graph keeps all.
+ * Point form, points device int32 [n][k][3] = (column, row, id), sf_agents_device's layout, k <= SF_DIST_MAX_POINTS: point_cells int32
+ * [n][k] and point_value int64 [n][k] are the plane values at the point's cell, -1 and 0 for id <= 0 or a point off the grid.
+ * max_route = R > 0 (R <= 2^20) enables point_route int32 [n][k][R] and point_hops int32 [n][k]: a route holds flat cell indices
+ * row * width + column - the point's cell, its parent, that cell's parent ...; the walk stops at a cell without a parent or after R
+ * cells; unwritten entries are -1.  point_hops is cells written - 1 when the walk ended at a parentless cell, -2 when R cut it short
+ * (a longer route, or a cycle), -1 for an invalid point. */
+#define SF_INFLUENCE_PRED_PLANE 0
+#define SF_INFLUENCE_PRED_HISTORY 1
+#define SF_INFLUENCE_WEIGHT_NONE 0
+#define SF_INFLUENCE_WEIGHT_VALUES 1
+#define SF_INFLUENCE_WEIGHT_PLANE 2
+#define SF_INFLUENCE_CYCLE (-2)
+typedef struct sf_influence_params {
+    int32_t pred_source;                 /* SF_INFLUENCE_PRED_PLANE, SF_INFLUENCE_PRED_HISTORY */
+    int32_t pred_per_env;                /* pred is [n][H*W] (row i: envs[i]), else [H*W] */
+    int32_t weight_mode;                 /* SF_INFLUENCE_WEIGHT_NONE, _VALUES, _PLANE */
+    int32_t weights_per_env;             /* weights is [n_envs][H*W] (indexed by environment number), else [H*W] */
+    int32_t include_per_env;             /* the same for include */
+    int32_t inclusive;                   /* != 0: a cell counts itself */
+    int32_t k;                           /* 0, or 1..SF_DIST_MAX_POINTS points per listed environment */
+    int32_t max_route;                   /* 0: no routes, or 1..2^20 cells per route */
+    const int8_t *pred;                  /* device; NULL with the history source */
+    const int32_t *weights;              /* device; NULL unless weight_mode is SF_INFLUENCE_WEIGHT_PLANE */
+    const uint8_t *include;              /* device, or NULL */
+    const int32_t *points;               /* device int32 [n][k][3]; NULL with k == 0 */
+    int64_t scratch_bytes;               /* 0: the default budget */
+    int32_t reserved[2];                 /* 0 */
+} sf_influence_params;
+typedef struct sf_influence_out {        /* device pointers, any may be NULL, at least one not */
+    int32_t *cells;                      /* [n][H][W] dense */
+    int64_t *value;                      /* [n][H][W] */
+    int8_t *pred;                        /* [n][H][W] */
+    int32_t *forest, *roots, *cyclic;    /* [n] */
+    int32_t *point_cells;                /* [n][k] */
+    int64_t *point_value;                /* [n][k] */
+    int32_t *point_route;                /* [n][k][max_route] */
+    int32_t *point_hops;                 /* [n][k] */
+} sf_influence_out;
+/* Environment envs[i] (a host array; any order, repeats allowed) lands in row i of every output.  Anything invalid is SF_EINVAL before
+ * anything is enqueued (a null argument, a bad environment list, an unknown pred_source or weight_mode, the plane source without pred
+ * or the history source with one, weight_mode 2 without weights or weights without it, value or point_value without weights, k outside
+ * 0..256, k > 0 without points or points with k == 0, a point output without k or k without one, max_route outside 0..2^20, max_route
+ * > 0 without point_route and point_hops or either of them with max_route == 0, an int32 output, points or weights not aligned to 4
+ * bytes or an int64 output not aligned to 8, a positive scratch_bytes below one environment's need, reserved != 0, every output null,
+ * an environment out of range); a grid wider than 8192 cells is SF_ENOTSUP; a handle without a reset is SF_ESTATE, and so are the
+ * history source while the spread graph is switched off (its masks would miss every ignition since) or without arrival recording, and
+ * weight_mode 1 without a value plane.
+ * Per chunk of listed environments four launches, a thread per cell: k_infl_stage derives (history) and sanitises the codes and counts
+ * every cell's children; k_infl_walk starts a walker on every childless forest cell, which adds its finished sums to its parent's
+ * accumulators and carries on upward only if it was the last child to arrive - agent-scope atomics only, no waiting, so the pass
+ * cannot hang on any input, and on a cycle no walker ever finishes a cycle cell; k_infl_finish marks C, applies inclusive and counts;
+ * k_infl_points answers the points, a lane each, with a walk of at most R cells.
+ * The scratch belongs to the handle: per listed environment of a chunk, with N = height * width and every term rounded up to 256,
+ * N + 4 * N bytes (codes, counters) + 4 * N where cells is not asked for + 8 * N where there are weights and value is not asked for
+ * (an accumulator that is no output lives in scratch) - allocated at the first call, grown (never shrunk) when a later call needs
+ * more, freed by sf_destroy, counted by sf_memory_bytes; a growth is a hipMalloc and waits for the device.  The default budget is
+ * 1 GiB; the list is worked through in chunks so that scratch never exceeds the budget, which changes no bit of the result.
+ * The call reads the state and writes nothing but its outputs and its own scratch - not the current plane, the tile books, the
+ * reference point of sf_get_fire_map_delta, the result block, any ring, the parent masks, the arrival or value planes.  In async mode
+ * the call only enqueues (the outputs are complete when the handle's stream has got there); the caller orders its own work on pred,
+ * weights, include, points and the outputs before the call. */
+int sf_influence(sf_sim *sim, const sf_influence_params *params, int32_t n, const int32_t *envs /* [n] host */, const sf_influence_out *out);
+
 /* Agents on the device: K agents per environment that walk the grid and draw control lines where they stand,
  * stepped from a policy's action tensor without a host read.  The reference records agent positions only (simulation.py:480-499) and
  * leaves the loop to the harness (the run docstring, 505-509); the semantics are this library's own.

@@ -1,5 +1,6 @@
 """Argument checks shared by the binding (``engine.py``) and the request classes (``observe.py``, ``render.py``, ``ensemble.py``
-and the six queries ``distance.py``, ``reach.py``, ``walk.py``, ``travel.py``, ``behavior.py``, ``perimeter.py``).
+and the seven queries ``distance.py``, ``reach.py``, ``walk.py``, ``travel.py``, ``behavior.py``, ``perimeter.py``,
+``influence.py``).
 
 Pure Python on NumPy; torch is imported inside the functions that are handed a tensor.  Every check raises before a device call,
 so a bad request fails the same way with or without a GPU.  ``who`` names the caller in the message (``"reach"`` gives

@@ -189,6 +189,26 @@ class SfPerimeterOut(C.Structure):
                 ("loop_edges", C.c_void_p)]
 
 
+SF_INFLUENCE_PRED_PLANE, SF_INFLUENCE_PRED_HISTORY = 0, 1
+SF_INFLUENCE_WEIGHT_NONE, SF_INFLUENCE_WEIGHT_VALUES, SF_INFLUENCE_WEIGHT_PLANE = 0, 1, 2
+SF_INFLUENCE_CYCLE = -2
+
+
+class SfInfluenceParams(C.Structure):
+    """``sf_influence_params`` (include/simfire_hip.h)."""
+    _fields_ = [("pred_source", C.c_int32), ("pred_per_env", C.c_int32), ("weight_mode", C.c_int32), ("weights_per_env", C.c_int32),
+                ("include_per_env", C.c_int32), ("inclusive", C.c_int32), ("k", C.c_int32), ("max_route", C.c_int32),
+                ("pred", C.c_void_p), ("weights", C.c_void_p), ("include", C.c_void_p), ("points", C.c_void_p),
+                ("scratch_bytes", C.c_int64), ("reserved", C.c_int32 * 2)]
+
+
+class SfInfluenceOut(C.Structure):
+    """``sf_influence_out`` (include/simfire_hip.h): device pointers, any may be null, not all."""
+    _fields_ = [("cells", C.c_void_p), ("value", C.c_void_p), ("pred", C.c_void_p), ("forest", C.c_void_p), ("roots", C.c_void_p),
+                ("cyclic", C.c_void_p), ("point_cells", C.c_void_p), ("point_value", C.c_void_p), ("point_route", C.c_void_p),
+                ("point_hops", C.c_void_p)]
+
+
 # name -> argtypes; every function returns int except the two string getters
 _VP, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
 SIGNATURES = {
@@ -263,6 +283,7 @@ SIGNATURES = {
     "sf_behavior": [_VP, C.POINTER(SfBehaviorParams), C.POINTER(SfBehaviorOut), _VP, _I32],
     "sf_get_behavior_builds": [_VP, C.POINTER(_I64)],
     "sf_perimeter": [_VP, C.POINTER(SfPerimeterParams), _I32, _VP, C.POINTER(SfPerimeterOut)],
+    "sf_influence": [_VP, C.POINTER(SfInfluenceParams), _I32, _VP, C.POINTER(SfInfluenceOut)],
     "sf_cell_layout": [_VP, C.POINTER(_I32)],
     "sf_render": [_VP, C.POINTER(SfRenderParams), _I32, _VP, _VP],
     "sf_status_device": [_VP, C.POINTER(_VP)],

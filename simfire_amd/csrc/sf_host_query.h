@@ -1,4 +1,4 @@
-// Host code of the queries: sf_distance, sf_reach (23), sf_walk (24), sf_behavior (25), sf_travel (26) and sf_perimeter (27).  Each takes a list
+// Host code of the queries: sf_distance, sf_reach (23), sf_walk (24), sf_behavior (25), sf_travel (26), sf_perimeter (27) and sf_influence (28).  Each takes a list
 // of environments, optional points and caller-owned device outputs, reads the state and changes none of it.  Included once from
 // simfire_hip.hip, behind sf_host_views.h.
 //
@@ -552,6 +552,112 @@ extern "C" int sf_perimeter(sf_sim *s, const sf_perimeter_params *p, int32_t n, 
             a.loop_edges = out->loop_edges ? out->loop_edges + (size_t)c0 * p->max_loops : nullptr;
             hipLaunchKernelGGL(k_perim_trace, dim3((unsigned)a.n), dim3(kPerimTraceThreads), 0, s->stream, a);
         }
+    }
+    return finish_call(s, who, !s->async, nullptr);
+}
+
+// ----------------------------------------------------------------------------- fire influence
+// Per chunk: the counters zeroed, then k_infl_stage, k_infl_walk, k_infl_finish and - with points - k_infl_points, a thread per cell
+// (per point).  The scratch of a listed environment holds the sanitised codes, the child counters and whichever accumulator is no
+// output of the call (infl_env_bytes).  The call block is the environment list; the arguments travel with the launches.
+extern "C" int sf_influence(sf_sim *s, const sf_influence_params *p, int32_t n, const int32_t *envs, const sf_influence_out *out)
+{
+    const char *who = "sf_influence";
+    if (!s || !p || !out) return fail(SF_EINVAL, "sf_influence: null argument");
+    const Geo &g = s->g;
+    if (n < 0 || (n > 0 && !envs)) return fail(SF_EINVAL, "sf_influence: bad environment list");
+    if (p->pred_source != SF_INFLUENCE_PRED_PLANE && p->pred_source != SF_INFLUENCE_PRED_HISTORY)
+        return fail(SF_EINVAL, "sf_influence: pred_source %d (0: a pred plane, 1: the episode's history)", p->pred_source);
+    if (p->weight_mode < SF_INFLUENCE_WEIGHT_NONE || p->weight_mode > SF_INFLUENCE_WEIGHT_PLANE)
+        return fail(SF_EINVAL, "sf_influence: weight_mode %d (0: none, 1: the handle's value plane, 2: a weights plane)", p->weight_mode);
+    const bool history = p->pred_source == SF_INFLUENCE_PRED_HISTORY;
+    if (!history && !p->pred) return fail(SF_EINVAL, "sf_influence: pred_source 0 needs a pred plane");
+    if (history && p->pred) return fail(SF_EINVAL, "sf_influence: pred_source 1 (history) takes no pred plane");
+    if ((p->weight_mode == SF_INFLUENCE_WEIGHT_PLANE) != (p->weights != nullptr))
+        return fail(SF_EINVAL, "sf_influence: weight_mode 2 and a weights plane go together");
+    const bool weighted = p->weight_mode != SF_INFLUENCE_WEIGHT_NONE;
+    if ((out->value || out->point_value) && !weighted) return fail(SF_EINVAL, "sf_influence: value and point_value need weights (weight_mode 1 or 2)");
+    SF_TRY(check_points(who, p->k, p->points, true));
+    if (p->max_route < 0 || p->max_route > kInflMaxRoute) return fail(SF_EINVAL, "sf_influence: max_route %d (0: no routes, at most %d)", p->max_route, kInflMaxRoute);
+    const bool point_out = out->point_cells || out->point_value || out->point_route || out->point_hops;
+    if (point_out && p->k == 0) return fail(SF_EINVAL, "sf_influence: point outputs need k > 0");
+    if (p->k > 0 && !point_out) return fail(SF_EINVAL, "sf_influence: points without a point output");
+    if (p->max_route > 0 && (!out->point_route || !out->point_hops)) return fail(SF_EINVAL, "sf_influence: max_route > 0 needs point_route and point_hops");
+    if (p->max_route == 0 && (out->point_route || out->point_hops)) return fail(SF_EINVAL, "sf_influence: point_route and point_hops need max_route > 0");
+    SF_TRY(check_aligned(who, (((uintptr_t)out->cells | (uintptr_t)out->forest | (uintptr_t)out->roots | (uintptr_t)out->cyclic | (uintptr_t)out->point_cells |
+                                (uintptr_t)out->point_route | (uintptr_t)out->point_hops | (uintptr_t)p->points | (uintptr_t)p->weights) & 3) |
+                                   (((uintptr_t)out->value | (uintptr_t)out->point_value) & 7)));
+    const size_t need = (size_t)infl_env_bytes(g.H, g.W, out->cells != nullptr, weighted, out->value != nullptr);
+    SF_TRY(check_scratch(who, p->scratch_bytes, need, "need"));
+    SF_TRY(check_reserved(who, p->reserved[0] | p->reserved[1]));
+    if (!out->cells && !out->value && !out->pred && !out->forest && !out->roots && !out->cyclic && !point_out)
+        return fail(SF_EINVAL, "sf_influence: every output is null");
+    SF_TRY(check_envs(s, who, n, envs));
+    if (g.W > kInflMaxWidth) return fail(SF_ENOTSUP, "sf_influence: grids wider than %d cells are not supported (width %d)", kInflMaxWidth, g.W);
+    if ((long long)g.H * g.W >= (1ll << 31)) return fail(SF_ENOTSUP, "sf_influence: the cells of a %d x %d grid do not fit int32", g.H, g.W);
+    SF_TRY(check_ready(s, who, kNeedReset));
+    // (a graph switched off keeps its masks allocated, but they miss every ignition since: no tree from those)
+    if (history && !(s->parents && s->graph_on)) return fail(SF_ESTATE, "sf_influence: the history source needs the spread graph (sf_enable_spread_graph)");
+    if (history && !s->arrival.plane) return fail(SF_ESTATE, "sf_influence: the history source needs arrival recording (sf_enable_arrival)");
+    if (p->weight_mode == SF_INFLUENCE_WEIGHT_VALUES && !s->values.plane) return fail(SF_ESTATE, "sf_influence: weight_mode 1 needs a value plane (sf_values_set)");
+    SF_TRY(begin_call(s, who, kNeedReset | kNotVoid));
+    if (n == 0) return SF_OK;
+
+    QueryState &q = s->influence;
+    const size_t cells = (size_t)g.H * g.W;
+    const int chunk = query_chunk(n, p->scratch_bytes, kInflScratchDefault, need, 65535);      // (65535: the launch grid's y)
+    SF_TRY(scratch_reserve(s, q, (size_t)chunk * need));
+    const int32_t *envs_dev = nullptr;
+    SF_TRY(block_stage(s, q.blk, &envs_dev, envs, (size_t)n * sizeof(int32_t)));
+    for (int32_t *cnt : {out->forest, out->roots, out->cyclic})
+        if (cnt) HIPCHK(hipMemsetAsync(cnt, 0, (size_t)n * sizeof(int32_t), s->stream));
+
+    InflArgs a;
+    memset(&a, 0, sizeof a);
+    a.H = g.H; a.W = g.W; a.P = g.P;
+    a.plane_env = g.plane_env;
+    a.source = p->pred_source;
+    a.pred_env = p->pred_per_env ? (long long)cells : 0;
+    a.parents = s->parents;
+    a.arrival = s->arrival.plane;
+    a.include = p->include;
+    a.inc_env = p->include_per_env ? (long long)cells : 0;
+    if (p->weight_mode == SF_INFLUENCE_WEIGHT_VALUES) {
+        a.weights = s->values.plane; a.w_env = s->values.per_env ? g.plane_env : 0; a.w_pitch = g.P;
+    } else if (weighted) {
+        a.weights = p->weights; a.w_env = p->weights_per_env ? (long long)cells : 0; a.w_pitch = g.W;
+    }
+    a.inclusive = p->inclusive != 0;
+    a.scratch = q.mem;
+    a.scratch_env = (long long)need;
+    a.o_cnt = infl_round((long long)cells);
+    long long o = a.o_cnt + infl_round(4 * (long long)cells);
+    a.o_acc_c = -1; a.o_acc_v = -1;
+    if (!out->cells) { a.o_acc_c = o; o += infl_round(4 * (long long)cells); }
+    if (weighted && !out->value) { a.o_acc_v = o; o += infl_round(8 * (long long)cells); }
+    a.k = p->k; a.max_route = p->max_route;
+    const unsigned cell_blocks = (unsigned)((cells + kInflThreads - 1) / kInflThreads);
+    for (int c0 = 0; c0 < n; c0 += chunk) {
+        const int cn = std::min(chunk, n - c0);
+        a.envs = envs_dev + c0;
+        a.pred_in = p->pred ? p->pred + (size_t)c0 * (size_t)a.pred_env : nullptr;
+        a.cells = out->cells ? out->cells + (size_t)c0 * cells : nullptr;
+        a.value = out->value ? reinterpret_cast<long long *>(out->value) + (size_t)c0 * cells : nullptr;
+        a.pred_out = out->pred ? out->pred + (size_t)c0 * cells : nullptr;
+        a.forest = out->forest ? out->forest + c0 : nullptr;
+        a.roots = out->roots ? out->roots + c0 : nullptr;
+        a.cyclic = out->cyclic ? out->cyclic + c0 : nullptr;
+        a.points = p->k ? p->points + (size_t)c0 * p->k * 3 : nullptr;
+        a.point_cells = out->point_cells ? out->point_cells + (size_t)c0 * p->k : nullptr;
+        a.point_value = out->point_value ? reinterpret_cast<long long *>(out->point_value) + (size_t)c0 * p->k : nullptr;
+        a.point_route = out->point_route ? out->point_route + (size_t)c0 * p->k * p->max_route : nullptr;
+        a.point_hops = out->point_hops ? out->point_hops + (size_t)c0 * p->k : nullptr;
+        HIPCHK(hipMemset2DAsync(q.mem + a.o_cnt, need, 0, cells * sizeof(int32_t), (size_t)cn, s->stream));
+        hipLaunchKernelGGL(k_infl_stage, dim3(cell_blocks, (unsigned)cn), dim3(kInflThreads), 0, s->stream, a);
+        hipLaunchKernelGGL(k_infl_walk, dim3(cell_blocks, (unsigned)cn), dim3(kInflThreads), 0, s->stream, a);
+        hipLaunchKernelGGL(k_infl_finish, dim3(cell_blocks, (unsigned)cn), dim3(kInflThreads), 0, s->stream, a);
+        if (p->k)
+            hipLaunchKernelGGL(k_infl_points, dim3((unsigned)(((long long)cn * p->k + kInflThreads - 1) / kInflThreads)), dim3(kInflThreads), 0, s->stream, a, cn);
     }
     return finish_call(s, who, !s->async, nullptr);
 }

@@ -4,7 +4,7 @@ This is the only module that touches the HIP library; the reference-shaped class
 ``fire.py`` / ``simulation.py`` are written on top of it.  Arrays cross the boundary as
 NumPy host arrays (copied during the call) or as torch CUDA tensors, read and written in place; torch is imported only by the
 methods that take or return one.  Layout (binding map): argument checks in ``_args.py``, one request class per feature
-(``observe.py``, ``render.py``, ``distance.py``, ``reach.py``, ``walk.py``, ``travel.py``, ``behavior.py``, ``perimeter.py``, ``ensemble.py``), and one frame, ``_device_call``, for every call
+(``observe.py``, ``render.py``, ``distance.py``, ``reach.py``, ``walk.py``, ``travel.py``, ``behavior.py``, ``perimeter.py``, ``influence.py``, ``ensemble.py``), and one frame, ``_device_call``, for every call
 that hands the library a tensor.
 """
 import ctypes as C
@@ -1047,6 +1047,46 @@ class FireEngine:
         if spec.n:
             p, o = spec.params(), spec.out(res)
             self._device_call(self._L.sf_perimeter, C.byref(p), spec.n, _ptr(spec.envs), C.byref(o), tensors=list(res.values()) + spec.device_tensors())
+        return res
+
+    # ---------------------------------------------------------------- fire influence
+    INFLUENCE_CYCLE = _lib.SF_INFLUENCE_CYCLE
+
+    def influence_scratch_bytes(self, cells=True, weighted=False, value=False):
+        from . import influence
+        return influence.scratch_need(self.H, self.W, cells=cells, weighted=weighted, value=value)
+
+    def influence(self, pred=None, history=False, envs=None, weights=None, include=None, inclusive=False, points=None, max_route=0,
+                  cells=True, value=False, pred_out=False, counts=False, scratch_bytes=0):
+        """WHICH cells matter in ``envs`` (default: all, in order; any order, repeats allowed): how much of the fire passes through
+        each cell of a forest of parent pointers (``sf_influence``), in integers.  The parents come from exactly
+        one source: ``pred``, an int8 CUDA tensor of codes into ``travel.SRC_OFFSETS`` - [H, W] for all or [n, H, W] with row i
+        belonging to ``envs[i]``, which is what ``travel(pred=True)`` returns; any byte outside 0..7 and any code that points off the
+        grid is "no parent" -, or ``history=True``: the ignition tree of the episode so far, the spread-graph parent masks narrowed to
+        the newest neighbour that burned strictly earlier (needs ``enable_spread_graph`` and ``enable_arrival``).  D(c) is the set of
+        cells whose parent chain reaches c.
+        Returns a dict of torch tensors on this GPU.  ``cells``: int32 [n, H, W], the cells of D(c) - with ``include`` (uint8 CUDA
+        [H, W] or [n_envs, H, W] by environment number) only those where it is not 0, with ``inclusive`` c itself too -,
+        ``INFLUENCE_CYCLE`` = -2 on the cells of a cycle (a caller's plane only).  ``value``: int64 [n, H, W], the same sum weighted
+        by ``weights`` - ``"values"`` (the plane of ``values_set``) or an int32 CUDA tensor [H, W] / [n_envs, H, W] -, 0 on a cycle.
+        ``pred_out``: ``pred`` int8 [n, H, W], the sanitised codes used, -1 without a parent (with ``history`` the ignition tree).
+        ``counts``: ``forest`` (cells with a parent), ``roots`` (without one, with children) and ``cyclic`` int32 [n].  With
+        ``points`` - int32 CUDA [n, k, 3] = (column, row, id), k <= 256, e.g. ``agents_device()`` - ``point_cells`` int32 [n, k]
+        and, with weights, ``point_value`` int64 [n, k]: the plane values at the point (-1 and 0 for id <= 0 or off the grid); with
+        ``max_route`` = R > 0 also ``point_route`` int32 [n, k, R] - flat cell indices row * W + column from the point's cell up
+        its parent chain, -1 beyond its end - and ``point_hops`` int32 [n, k]: the route's length - 1, -2 where R cut it short (a
+        longer route or a cycle), -1 for an invalid point.  ``scratch_bytes``: the most scratch the call may use (0: 1 GiB); less
+        than ``influence_scratch_bytes(...)`` is a ``ValueError``.  No state of the handle changes.  Torch's queued work is waited
+        for first; in async mode the call only enqueues: the tensors are complete after ``sync()`` and kept alive until then."""
+        from .influence import InfluenceSpec
+        spec = InfluenceSpec(self.n_envs, self.H, self.W, pred=pred, history=history, envs=envs, weights=weights, include=include,
+                             inclusive=inclusive, points=points, max_route=max_route, cells=cells, value=value, pred_out=pred_out,
+                             counts=counts, scratch_bytes=scratch_bytes, graph_on=self.spread_graph_on, arrival_on=self.arrival_on,
+                             values_on=self.values_on)                # (spread_graph_on: the switch, not "masks exist" - masks of a graph switched off are stale)
+        res = self._outputs("influence", spec)
+        if spec.n:
+            p, o = spec.params(), spec.out(res)
+            self._device_call(self._L.sf_influence, C.byref(p), spec.n, _ptr(spec.envs), C.byref(o), tensors=list(res.values()) + spec.device_tensors())
         return res
 
     def behavior_builds(self):

@@ -41,6 +41,50 @@ def _perimeter_unit(unit, pixel_scale):
     return 1.0 if unit == "cells" else float(pixel_scale)
 
 
+def _fire_influence(engine, source, envs, weights, include, inclusive, points, max_route, cells, value, pred_out, counts, scratch_bytes,
+                    horizon, travel_kwargs):
+    """``fire_influence`` of both simulation classes: ``source`` turned into the arguments of ``FireEngine.influence``.  "forecast"
+    runs ``travel(pred=True)`` first and hands its ``pred`` plane on (device to device); ``horizon`` (minutes) asks it for the
+    ``minutes`` plane too and makes ``include = minutes <= horizon`` of it in torch, combined with a caller's ``include`` - torch
+    works on a stream of its own, so that form waits once for the forecast before the influence call is enqueued."""
+    forecast = isinstance(source, str) and source == "forecast"
+    if isinstance(source, str) and source not in ("history", "forecast"):
+        raise ValueError(f'fire_influence: source must be "history", "forecast" or an int8 CUDA tensor of parent codes, got {source!r}')
+    if not forecast and (travel_kwargs or horizon is not None):
+        raise ValueError('fire_influence: horizon and the arguments of time_to_fire go with source="forecast" only')
+    if horizon is not None and (isinstance(horizon, bool) or not isinstance(horizon, (int, float, np.integer, np.floating)) or not horizon >= 0):
+        raise ValueError(f"fire_influence: horizon must be None or a number of minutes >= 0, got {horizon!r}")
+    for name in ("envs", "points", "plane", "pred", "reached", "last", "activations"):
+        if name in travel_kwargs:
+            raise ValueError(f"fire_influence: {name} is not an argument of the forecast (it is set by fire_influence itself)")
+    kw = dict(envs=envs, weights=weights, include=include, inclusive=inclusive, points=points, max_route=max_route, cells=cells, value=value,
+              pred_out=pred_out, counts=counts, scratch_bytes=scratch_bytes)
+    if not forecast:
+        return engine.influence(history=True, **kw) if isinstance(source, str) else engine.influence(pred=source, **kw)
+    if horizon is not None and include is not None:              # (checked before torch touches it: a bad plane is a ValueError, as everywhere)
+        from . import _args
+        include = _args.dense_plane("fire_influence", "include", include, engine.n_envs, engine.H, engine.W)[0]
+        if include.device != engine.torch_device:
+            raise ValueError(f"fire_influence: a tensor on {include.device}, the simulation runs on {engine.torch_device}")
+    t = engine.travel(envs=envs, plane=horizon is not None, pred=True, **travel_kwargs)
+    if horizon is not None:
+        import torch
+        engine.sync()                                            # (torch reads the minutes plane on its own stream)
+        inc = (t["minutes"] >= 0) & (t["minutes"] <= float(horizon))
+        listed = _args_env_list(envs, engine.n_envs)
+        full = torch.zeros((engine.n_envs, engine.H, engine.W), dtype=torch.uint8, device=inc.device)
+        full[torch.as_tensor(listed, device=inc.device, dtype=torch.long)] = inc.to(torch.uint8)       # (a repeated environment has one forecast)
+        if include is not None:
+            full &= (include != 0).to(torch.uint8)
+        kw["include"] = full
+    return engine.influence(pred=t["pred"], **kw)
+
+
+def _args_env_list(envs, n_envs):
+    from . import _args
+    return _args.env_list(envs, n_envs, "fire_influence", none_all=True)
+
+
 def _travel_unit(r, unit, update_rate):
     """The times of a ``travel`` result (torch tensors) in ``unit``: "minutes" as they are, "updates" divided by
     float32(update_rate) - every value below 0 (blocked cells, padding points) stays what it is."""
@@ -657,6 +701,24 @@ class FireSimulation:
                                 max_minutes=max_minutes, plane=True)
         self._engine.sync()
         return _travel_unit(r, unit, float(self._engine.params.update_rate))["minutes"][0].cpu().numpy()
+
+    def fire_influence(self, source="history", weights=None, include=None, inclusive=False, value=False, horizon=None, **travel_kwargs):
+        """WHICH cells matter: for every cell, how many cells the fire reaches - or reached - THROUGH it.  ``source="history"``: the
+        ignition tree of the episode so far (needs ``enable_spread_graph`` and ``record_arrival`` from the reset on);
+        ``"forecast"``: the fastest routes of ``time_to_fire`` from now (``travel_kwargs`` go to it; ``horizon`` in minutes counts
+        only the cells reached within it); or an int8 CUDA tensor [H, W] of parent codes into ``travel.SRC_OFFSETS``.  Returns the
+        NumPy int32 plane [H, W] - with ``value`` a dict of ``cells`` and the int64 ``value`` plane weighted by ``weights``
+        (``"values"``: the plane of ``set_values``, or an int32 CUDA tensor [H, W]).  Relation to the reference's
+        ``FireSpreadGraph.get_descendant_heatmap`` (simfire/utils/graph.py:53-82): that counts ``len(nx.descendants(...))`` on the
+        spread graph, where a cell keeps EVERY neighbour that was BURNING when it ignited, and casts to uint8; the ignition tree
+        keeps the newest one, so with ``inclusive=False`` this plane is a lower bound of that count before the cast, and equals it
+        wherever every descendant had exactly one BURNING neighbour.  Host edits of ``fire_map`` are pushed to the device first, as
+        ``moves_to`` does (``BatchedFireSimulation.fire_influence``)."""
+        self._sync_to_device()
+        r = _fire_influence(self._engine, source, [0], weights, include, inclusive, None, 0, True, value, False, False, 0, horizon, travel_kwargs)
+        self._engine.sync()
+        r = {k: v[0].cpu().numpy() for k, v in r.items()}
+        return r if value else r["cells"]
 
     def perimeter(self, status=None, at_update=None, connectivity=None, simplify=True, unit="cells", max_edges=None):
         """WHERE the fire's edge runs: the cracks between the cells whose BurnStatus is one of ``status`` (members, names or ints;
@@ -1483,6 +1545,28 @@ class BatchedFireSimulation:
                                 max_minutes=max_minutes, plane=plane, pred=pred, reached=reached, last=last, scratch_bytes=scratch_bytes)
         self._engine.sync()
         r = _travel_unit(r, unit, float(self._engine.params.update_rate))
+        return r if device else {k: v.cpu().numpy() for k, v in r.items()}
+
+    def fire_influence(self, source="history", envs=None, weights=None, include=None, inclusive=False, points=None, max_route=0, cells=True,
+                       value=False, pred_out=False, counts=False, scratch_bytes=0, agents=False, horizon=None, device=True, **travel_kwargs):
+        """WHICH cells matter in ``envs`` (default: all): for every cell, how many cells the fire reaches - or reached - THROUGH it,
+        in integers.  ``source="history"``: the ignition tree of the episode so far (needs ``enable_spread_graph`` and
+        ``enable_arrival`` from the reset on) - credit after an episode; ``"forecast"``: the fastest routes of ``time_to_fire`` from
+        now - ``engine.travel(pred=True, **travel_kwargs)``, its ``pred`` plane fed on without a host copy; ``horizon`` in minutes
+        counts only the cells reached within it -, the prior for where a line buys the most; or an int8 CUDA tensor [H, W] /
+        [n, H, W] of parent codes into ``travel.SRC_OFFSETS``.  A dict: ``cells`` int32 [n, H, W]; with ``value`` int64 [n, H, W]
+        weighted by ``weights`` (``"values"``, or int32 CUDA [H, W] / [n_envs, H, W]); with ``pred_out`` the codes used; with
+        ``counts`` ``forest``, ``roots``, ``cyclic`` int32 [n]; with ``agents=True`` (the device positions of a ``BatchedFireEnv``,
+        every environment in order) or ``points`` [n, k, 3] ``point_cells`` / ``point_value`` and, with ``max_route``, the routes
+        ``point_route`` / ``point_hops`` from each point up to its root.  ``include``, ``inclusive``: as ``FireEngine.influence``.
+        ``device=True`` returns torch tensors on this GPU, else NumPy arrays; complete on return either way (one wait).  Nothing is
+        read back, no state of the simulation changes."""
+        if points is not None and agents is not False:
+            raise ValueError("fire_influence: give points or agents, not both")
+        pts = points if points is not None else self._agent_points(agents)
+        r = _fire_influence(self._engine, source, envs, weights, include, inclusive, pts, max_route, cells, value, pred_out, counts,
+                            scratch_bytes, horizon, travel_kwargs)
+        self._engine.sync()
         return r if device else {k: v.cpu().numpy() for k, v in r.items()}
 
     def perimeter(self, status=None, envs=None, member=None, at_update=None, connectivity=None, simplify=True, front=False, trace=False,
