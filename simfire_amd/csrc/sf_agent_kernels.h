@@ -20,8 +20,7 @@ static_assert(kAgentsMax == 64, "the agent kernels are written for workgroups of
 
 struct AgentArgs {
     Geo g;
-    const uint8_t *status;     // row-major status plane (read when cells is null)
-    const uint8_t *cells;      // the blocked plane of the resident launch when it is current (bl_cell), else null
+    CellPlanes pl;             // the status bytes, in whichever plane is current
     const int32_t *rows;       // the result block [E][8]: running, update() calls, cells per BurnStatus 0..5 - current when the kernel runs
     const int32_t *actions;    // [E][K] action words: move + 5 * interact (k_agents_act)
     int32_t *xyid;             // [E][K][3] (column, row, id): the layout sf_observe takes as agents
@@ -49,14 +48,10 @@ struct AgentArgs {
     double *o_ret;
 };
 
-// BurnStatus of cell (x, y) of environment e in the plane that is current (the status byte of the blocked plane sits kBlStatus
-// behind the cell's sprite mask; & 7 as k_unpack_status takes it)
+// BurnStatus of cell (x, y) of environment e in the plane that is current (& 7 as k_unpack_status takes it)
 __device__ __forceinline__ uint32_t agent_cell(const AgentArgs &a, int e, int x, int y)
 {
-    const Geo &g = a.g;
-    const uint8_t *p = a.cells ? a.cells + (long long)e * g.cells_env + bl_cell(g, y, x) + kBlStatus
-                               : a.status + (long long)e * g.plane_env + (long long)y * g.P + x;
-    return *p & 7u;
+    return *cell_status(a.pl, a.g, e, y, x) & 7u;
 }
 
 // One wave per environment, one lane per agent.  Steps a and b of a tick: the move (one that would leave the grid does not

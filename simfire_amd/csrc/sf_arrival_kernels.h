@@ -57,13 +57,12 @@ __global__ __launch_bounds__(256) void k_arrival_bits(Geo g, const uint8_t *cell
     if (!word) return;
     const ArrivalKey q = arrival_key(commit[e].steps, g);
     const int y = i / g.VW, v0 = (i - y * g.VW) * 64;
-    const uint8_t *env_cells = cells + (long long)e * g.cells_env;
     uint32_t *row = arrival1 + (long long)e * g.plane_env + (long long)y * g.P;
     while (word) {
         const int v = v0 + __ffsll((long long)word) - 1;
         word &= word - 1ull;
         if (v >= g.PV) break;                                  // (no bit beyond the row's vectors; the bound of every access below)
-        const uint4 m = *reinterpret_cast<const uint4 *>(env_cells + bl_vec(g, y, v) + (y & 1) * 16);
+        const uint4 m = *reinterpret_cast<const uint4 *>(bl_mask_vec(cells, g, e, y, v));
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const uint32_t d = pick(m, j);
@@ -87,7 +86,7 @@ __global__ __launch_bounds__(256) void k_arrival_cells(Geo g, const uint8_t *age
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, e = blockIdx.z;
     if (x >= g.W) return;
     uint32_t m;
-    if (cells) m = cells[(long long)e * g.cells_env + bl_cell(g, y, x)];
+    if (cells) m = *bl_mask(cells, g, e, y, x);
     else m = reinterpret_cast<const T *>(age)[(long long)e * g.age_env + (long long)y * g.P + x];
     if (!m) return;
     const uint32_t a1 = arrival_of(arrival_key(commit[e].steps, g), m);

@@ -160,15 +160,14 @@ __global__ void k_unpack_f64(int H, int W, int P, const double *pitched, double 
     dense[((long long)k * H + y) * W + x] = pitched[((long long)k * H + y) * P + x];
 }
 #endif
-// (cells: the blocked cell plane when it is the current one - sf_common.h, bl_vec - else null)
+// (pl: the status bytes in whichever cell plane is current - sf_cells.h)
 #ifndef SF_RUN_UNIT
 // (snap: the reference point of sf_get_fire_map_delta to be set to this map - when that call finds none -, or null)
-__global__ void k_unpack_status(Geo g, const uint8_t *status, const uint8_t *cells, int env0, uint8_t *dense, uint8_t *snap)
+__global__ void k_unpack_status(Geo g, CellPlanes pl, int env0, uint8_t *dense, uint8_t *snap)
 {
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, i = blockIdx.z;
     if (x >= g.W) return;
-    const uint8_t st = cells ? cells[(long long)(env0 + i) * g.cells_env + bl_cell(g, y, x) + kBlStatus]
-                             : status[(long long)(env0 + i) * g.plane_env + (long long)y * g.P + x];
+    const uint8_t st = *cell_status(pl, g, env0 + i, y, x);
     dense[((long long)i * g.H + y) * g.W + x] = st & 7u;
     if (snap) snap[(long long)(env0 + i) * g.plane_env + (long long)y * g.P + x] = st & 7u;
 }
@@ -183,16 +182,14 @@ __global__ void k_unpack_status(Geo g, const uint8_t *status, const uint8_t *cel
 constexpr int kDeltaHead = 11;      // words in front of the list: the count, a result row, its elapsed_time
 // (out[0] counts on from launch to launch - base is what it stood at before this one -, so that nothing has to zero it: a fill launch in front
 // of every query cost the stream 4 us)
-__global__ __launch_bounds__(256) void k_map_delta(Geo g, const uint8_t *status, const uint8_t *cells, int e, uint8_t *snap, uint32_t *out, int cap, uint32_t base,
+__global__ __launch_bounds__(256) void k_map_delta(Geo g, CellPlanes pl, int e, uint8_t *snap, uint32_t *out, int cap, uint32_t base,
                                                    const int32_t *row, const double *el)
 {
     const int v = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (row && y == 0 && v < 10)       // sf_run_delta: the environment's row of the result block and its elapsed_time travel with the count (one copy)
         out[1 + v] = v < 8 ? (uint32_t)row[v] : reinterpret_cast<const uint32_t *>(el)[v - 8];
     if (v >= g.PV) return;
-    const uint8_t *src = cells ? cells + (long long)e * g.cells_env + bl_vec(g, y, v) + (y & 1) * 16 + kBlStatus
-                               : status + (long long)e * g.plane_env + (long long)y * g.P + v * 16;
-    uint4 now = *reinterpret_cast<const uint4 *>(src);
+    uint4 now = *reinterpret_cast<const uint4 *>(cell_status_vec(pl, g, e, y, v));
     now = and4(now, 0x07070707u);
     uint4 *ref = reinterpret_cast<uint4 *>(snap + (long long)y * g.P + v * 16);
     const uint4 was = *ref;
@@ -279,7 +276,7 @@ __global__ void k_pack_burn(Geo g, double *burn, int e, const double *dense)
 //                     w.r.t. the old status (mitigation.py:75-78) because pass 1 cleared it.  The
 //                     new line cell owes attenuation from the next update on.
 #ifndef SF_RUN_UNIT
-__global__ void k_mitigate_clear(Geo g, uint8_t *status, uint8_t *cells, const uint32_t *settled, double *burn, const EnvState *commit,
+__global__ void k_mitigate_clear(Geo g, CellPlanesMut pl, const uint32_t *settled, double *burn, const EnvState *commit,
                                  const EnvState *tmp, const uint32_t *flags, int launch, int from_commit,
                                  const int32_t *pts, int n)
 {
@@ -289,7 +286,7 @@ __global__ void k_mitigate_clear(Geo g, uint8_t *status, uint8_t *cells, const u
     if (ty < SF_FIRELINE || ty > SF_WETLINE) return;                 // simulation.py:469-473
     if (e < 0 || e >= g.E || x < 0 || x >= g.W || y < 0 || y >= g.H) return;   // device-side lists are not pre-checked
     const long long o = (long long)e * g.plane_env + (long long)y * g.P + x;
-    uint32_t *word = reinterpret_cast<uint32_t *>(cells ? cells + (long long)e * g.cells_env + bl_cell(g, y, x & ~3) + kBlStatus : status + (o & ~3ll));
+    uint32_t *word = cell_status_word(pl, g, e, y, x, o);
     const int sh = (x & 3) * 8;
     const uint32_t old = (atomicAnd(word, ~(0xFFu << sh)) >> sh) & 7u;
     if (g.att && old >= SF_FIRELINE) {
@@ -300,7 +297,7 @@ __global__ void k_mitigate_clear(Geo g, uint8_t *status, uint8_t *cells, const u
 #endif
 
 #ifndef SF_RUN_UNIT
-__global__ void k_mitigate_write(Geo g, uint8_t *status, uint8_t *cells, uint32_t *settled, uint8_t *tdirty, const EnvState *commit,
+__global__ void k_mitigate_write(Geo g, CellPlanesMut pl, uint32_t *settled, uint8_t *tdirty, const EnvState *commit,
                                  const EnvState *tmp, const uint32_t *flags, int launch, int from_commit,
                                  const int32_t *pts, int n)
 {
@@ -310,7 +307,7 @@ __global__ void k_mitigate_write(Geo g, uint8_t *status, uint8_t *cells, uint32_
     if (ty < SF_FIRELINE || ty > SF_WETLINE) return;
     if (e < 0 || e >= g.E || x < 0 || x >= g.W || y < 0 || y >= g.H) return;
     const long long o = (long long)e * g.plane_env + (long long)y * g.P + x;
-    uint32_t *word = reinterpret_cast<uint32_t *>(cells ? cells + (long long)e * g.cells_env + bl_cell(g, y, x & ~3) + kBlStatus : status + (o & ~3ll));
+    uint32_t *word = cell_status_word(pl, g, e, y, x, o);
     const int sh = (x & 3) * 8;
     uint32_t old = *word, seen;
     do {
@@ -389,6 +386,7 @@ __device__ __forceinline__ void counts_env(const Geo &g, int e, const uint8_t *s
                                            int32_t (*s_tot)[6])
 {
     // LDS of the caller: s_tot [16][6] int32, then one counter, then the list of dirty tiles of the round [kCountsListCap] u16
+    const CellPlanes pl{status, cells};      // (cells: the blocked plane when it is the current one, else null)
     uint32_t *s_n = reinterpret_cast<uint32_t *>(&s_tot[16][0]);
     uint16_t *s_list = reinterpret_cast<uint16_t *>(s_n + 1);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
@@ -434,8 +432,7 @@ __device__ __forceinline__ void counts_env(const Geo &g, int e, const uint8_t *s
                 for (int i = 0; i < g.RB; ++i) {
                     if (y0 + i >= g.H) break;
                     const int y = y0 + i;
-                    const uint4 v = *reinterpret_cast<const uint4 *>(cells ? cells + (long long)e * g.cells_env + bl_vec(g, y, cv) + (y & 1) * 16 + kBlStatus
-                                                                           : status + (long long)e * g.plane_env + (long long)y * g.P + cv * 16);
+                    const uint4 v = *reinterpret_cast<const uint4 *>(cell_status_vec(pl, g, e, y, cv));
                     if ((v.x | v.y | v.z | v.w) == 0u) continue;
                     const uint32_t w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
@@ -480,12 +477,12 @@ __device__ __forceinline__ void counts_env(const Geo &g, int e, const uint8_t *s
 }
 
 #ifndef SF_RUN_UNIT
-__global__ __launch_bounds__(1024) void k_counts_tiles(Geo g, const uint8_t *status, const uint8_t *cells, uint8_t *tdirty, uint16_t *thist,
+__global__ __launch_bounds__(1024) void k_counts_tiles(Geo g, CellPlanes pl, uint8_t *tdirty, uint16_t *thist,
                                                        const EnvState *commit, int32_t *out, double *elapsed, int32_t *out2)
 {
     __shared__ int32_t s_mem[16 * 6 + 1 + kCountsListCap / 2];        // s_tot [16][6], the list counter, the list (u16)
     const int e = blockIdx.x;
-    counts_env(g, e, status, cells, tdirty, thist, commit[e].running, commit[e].steps, commit[e].elapsed, out, elapsed, out2,
+    counts_env(g, e, pl.status, pl.cells, tdirty, thist, commit[e].running, commit[e].steps, commit[e].elapsed, out, elapsed, out2,
                reinterpret_cast<int32_t (*)[6]>(s_mem));
 }
 #endif

@@ -9,7 +9,7 @@
 //   L     = (float)(0.45 * pow(I_B (f64), 0.46)); I_B and L are 0 where the float64 I_B is not > 0                  ft (Byram 1959)
 // Compiled with -ffp-contract=off like the rest: the rounding sequence above is the specification.
 #pragma once
-#include "sf_common.h"
+#include "sf_query_dev.h"
 #include "rothermel_dev.h"
 
 namespace {
@@ -33,11 +33,10 @@ __global__ __launch_bounds__(kBehThreads) void k_behavior_hpa(int H, int W, cons
 }
 
 struct BehArgs {
-    int H, W, P, PV;           // the grid, the row pitch and its 16-cell vectors (Geo)
-    long long plane_env, rt_env, cells_env;      // Geo's strides: cells of a plane, elements between two tables (0: shared), bytes of the blocked plane
-    const uint8_t *status;     // row-major status plane (read when cells is null)
-    const uint8_t *cells;      // the blocked plane of the resident launch when it is current (bl_cell), else null
-    const double *rt;          // [tables][8][H][P]; rt_env elements between two environments' tables (0: one shared table)
+    CellGeo g;
+    CellPlanes pl;             // the status bytes, in whichever plane is current
+    long long rt_env;          // Geo's: elements between two environments' tables (0: one shared table)
+    const double *rt;          // [tables][8][H][P]
     const float *hpa;          // the heat cache [tables][H * W]
     long long hpa_env;         // floats between two environments' tables (0: one shared table)
     const int32_t *envs;       // [n]
@@ -85,34 +84,14 @@ __device__ __forceinline__ BehCell beh_cell(const double (&r)[8], float hpa)
     return b;
 }
 
-__device__ __forceinline__ const uint8_t *beh_status_ptr(const BehArgs &a, int e, int y, int x)
-{
-    // (bl_cell of sf_common.h, written out for the few fields of Geo this kernel carries)
-    const int bl = ((y >> 2) * a.PV + (x >> 4)) * 128 + ((y >> 1) & 1) * 64 + (y & 1) * 16 + (x & 15) + kBlStatus;
-    return a.cells ? a.cells + (long long)e * a.cells_env + bl : a.status + (long long)e * a.plane_env + (long long)y * a.P + x;
-}
-
-__device__ __forceinline__ uint32_t beh_wave_max(uint32_t v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const uint32_t u = (uint32_t)__shfl_xor((int)v, o); v = u > v ? u : v; }
-    return v;
-}
-__device__ __forceinline__ uint32_t beh_wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-    return v;
-}
-
 // the quantities of cell (y, x) of environment e, loaded cell by cell (the point form and the scan: a few cells per lane at most)
 __device__ __forceinline__ BehCell beh_cell_at(const BehArgs &a, int e, int y, int x)
 {
     double r[8];
-    const double *rp = a.rt + (long long)e * a.rt_env + (long long)y * a.P + x;
+    const double *rp = a.rt + (long long)e * a.rt_env + (long long)y * a.g.P + x;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) r[k] = rp[(long long)k * a.plane_env];
-    return beh_cell(r, a.hpa[(long long)e * a.hpa_env + (long long)y * a.W + x]);
+    for (int k = 0; k < 8; ++k) r[k] = rp[(long long)k * a.g.plane_env];
+    return beh_cell(r, a.hpa[(long long)e * a.hpa_env + (long long)y * a.g.W + x]);
 }
 
 // What the lanes of a workgroup found for listed environment i -> the outputs: a wave reduction where a wave has a selected cell,
@@ -121,10 +100,10 @@ __device__ __forceinline__ BehCell beh_cell_at(const BehArgs &a, int e, int y, i
 __device__ __forceinline__ void beh_reduce(const BehArgs &a, uint32_t *s_red, int i, int t, bool sel_any, uint32_t mf, uint32_t mi, uint32_t (&cls)[5])
 {
     if (__any(sel_any)) {
-        mf = beh_wave_max(mf);
-        mi = beh_wave_max(mi);
+        mf = wave_max(mf);
+        mi = wave_max(mi);
 #pragma unroll
-        for (int q = 0; q < 5; ++q) cls[q] = beh_wave_sum(cls[q]);
+        for (int q = 0; q < 5; ++q) cls[q] = wave_sum(cls[q]);
         if ((t & 63) == 0) {
             atomicMax(&s_red[0], mf);
             atomicMax(&s_red[1], mi);
@@ -155,16 +134,15 @@ __device__ __forceinline__ void beh_points(const BehArgs &a, int t)
         if (idx >= npts) continue;
         const int i = (int)(idx / a.k);
         const int e = a.envs[i];
-        const int32_t *p = a.points + idx * 3;
-        const int px = p[0], py = p[1], id = p[2];
+        const QueryPoint p = query_point(a.points, idx, a.g.W, a.g.H);
         float best = -1.0f;
-        if (id > 0 && px >= 0 && px < a.W && py >= 0 && py < a.H) {
+        if (p.ok) {
             best = 0.0f;
             for (int dy = -1; dy <= 1; ++dy)
                 for (int dx = -1; dx <= 1; ++dx) {
-                    const int y = py + dy, x = px + dx;
-                    if (y < 0 || y >= a.H || x < 0 || x >= a.W) continue;
-                    const uint32_t s = *beh_status_ptr(a, e, y, x) & 7u;
+                    const int y = p.y + dy, x = p.x + dx;
+                    if (y < 0 || y >= a.g.H || x < 0 || x >= a.g.W) continue;
+                    const uint32_t s = *cell_status(a.pl, a.g, e, y, x) & 7u;
                     if (!((a.summask >> s) & 1u)) continue;
                     const BehCell b = beh_cell_at(a, e, y, x);
                     best = b.L > best ? b.L : best;
@@ -182,7 +160,7 @@ template <bool VEC>
 __global__ __launch_bounds__(kBehThreads) void k_behavior(BehArgs a)
 {
     __shared__ uint32_t s_red[8];      // 0: max flame bits, 1: max intensity bits, 2..6: class counts
-    const BehArgs &g = a;
+    const CellGeo &g = a.g;
     const int t = threadIdx.x;
     const int gx = (g.W + 3) >> 2;
     const int items = g.H * gx;
@@ -197,7 +175,7 @@ __global__ __launch_bounds__(kBehThreads) void k_behavior(BehArgs a)
         if (item < items) {
             const int y = item / gx, x = (item - y * gx) * 4;
             uint32_t sw = 0u;
-            if (a.smask || a.summary) sw = *reinterpret_cast<const uint32_t *>(beh_status_ptr(a, e, y, x)) & 0x07070707u;
+            if (a.smask || a.summary) sw = *reinterpret_cast<const uint32_t *>(cell_status(a.pl, g, e, y, x)) & 0x07070707u;
             bool show[4], sel[4], need = false;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -212,7 +190,7 @@ __global__ __launch_bounds__(kBehThreads) void k_behavior(BehArgs a)
             int o_head[4] = {-1, -1, -1, -1};
             if (need) {
                 double r[4][8];
-                const double *rp = a.rt + (long long)e * g.rt_env + (long long)y * g.P + x;
+                const double *rp = a.rt + (long long)e * a.rt_env + (long long)y * g.P + x;
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
                     const double2 lo = *reinterpret_cast<const double2 *>(rp + (long long)k * g.plane_env);
@@ -282,7 +260,8 @@ __global__ __launch_bounds__(kBehThreads) void k_behavior_scan(BehArgs a)
 {
     __shared__ uint32_t s_red[8];      // 0: max flame bits, 1: max intensity bits, 2..6: class counts
     const int t = threadIdx.x;
-    const int items = a.H * a.PV;
+    const CellGeo &g = a.g;
+    const int items = g.H * g.PV;
     if (t < 8) s_red[t] = 0u;
     __syncthreads();
     for (long long w = blockIdx.x; w < a.total; w += gridDim.x) {
@@ -292,12 +271,12 @@ __global__ __launch_bounds__(kBehThreads) void k_behavior_scan(BehArgs a)
         uint32_t mf = 0u, mi = 0u, cls[5] = {0u, 0u, 0u, 0u, 0u};
         uint32_t m = 0u;               // bit j: cell x0 + j is on the grid and selected
         if (item < items) {
-            const int y = item / a.PV, x0 = (item - y * a.PV) * 16;
-            const uint4 q = and4(*reinterpret_cast<const uint4 *>(beh_status_ptr(a, e, y, x0)), 0x07070707u);
+            const int y = item / g.PV, x0 = (item - y * g.PV) * 16;
+            const uint4 q = and4(*reinterpret_cast<const uint4 *>(cell_status(a.pl, g, e, y, x0)), 0x07070707u);
 #pragma unroll
             for (int j = 0; j < 16; ++j) {
                 const uint32_t s = (pick(q, j >> 2) >> (8 * (j & 3))) & 7u;
-                m |= (x0 + j < a.W && ((a.summask >> s) & 1u)) ? 1u << j : 0u;
+                m |= (x0 + j < g.W && ((a.summask >> s) & 1u)) ? 1u << j : 0u;
             }
             for (uint32_t left = m; left; left &= left - 1u) {
                 const BehCell b = beh_cell_at(a, e, y, x0 + __ffs((int)left) - 1);

@@ -8,6 +8,7 @@
 
 #include "../../include/simfire_hip.h"
 #include "../../include/simfire_hip_lab.h"
+#include "sf_cells.h"
 
 namespace {
 
@@ -54,25 +55,14 @@ struct Geo {
     int prune_after_quit;         // 1: environments that QUIT on the runtime check keep pruning (EnvState.running = 2)
     int VW;                       // 64-bit words per row of the vector bitmap = ceil(PV / 64)
     long long vb_env;             // words of vector bitmap per environment = H * VW
-    long long cells_env;          // bytes of the blocked cell plane per environment (resident launch) = (ceil(H / 4) + 2) * PV * 128
+    long long cells_env;          // bytes of the blocked cell plane per environment (resident launch) (sf_cells.h, bl_env_bytes)
 };
 
-// ------------------------------------------------------------------------------------------
-// Blocked cell plane of the resident launch (k_run).  A 16-cell vector visit needs the sprite masks of rows y - 1, y, y + 1
-// and the status bytes of row y: four 64-byte sectors in four different lines of the row-major planes.  Here a SECTOR holds,
-// for one 16-cell vector and one PAIR of rows (2p, 2p + 1):  [mask row 2p | mask row 2p + 1 | status row 2p | status row 2p + 1],
-// and the two pairs of a row quad share a 128-byte line (the lines of a quad row run along x).  A visit then touches exactly
-// two sectors - the pair of y, and the pair above (y even) or below (y odd) - in one line (y mod 4 = 1, 2) or two.
-// One guard quad above and below every environment (row -1 and row H are zero for ever).
-__host__ __device__ inline int bl_vec(const Geo &g, int y, int v)      // byte offset of the sector of (row pair of y, vector v)
-{
-    return ((y >> 2) * g.PV + v) * 128 + ((y >> 1) & 1) * 64;
-}
-__host__ __device__ inline int bl_cell(const Geo &g, int y, int x)     // sprite mask of cell (y, x); its status byte is 32 further
-{
-    return bl_vec(g, y, x >> 4) + (y & 1) * 16 + (x & 15);
-}
-constexpr int kBlStatus = 32;      // status row = mask row + 32 inside a sector
+// The blocked cell plane of the resident launch (k_run): its layout is sf_cells.h's; these are its offsets for a whole Geo
+__host__ __device__ constexpr int bl_vec(const Geo &g, int y, int v) { return bl_vec(g.PV, y, v); }
+__host__ __device__ constexpr int bl_cell(const Geo &g, int y, int x) { return bl_cell(g.PV, y, x); }
+constexpr Geo bl_check_geo() { Geo g{}; g.W = 40; g.P = 48; g.PV = 3; return g; }      // (tests/cells_check.cpp checks the PV forms; Geo needs HIP)
+static_assert(bl_vec(bl_check_geo(), 6, 2) == bl_vec(3, 6, 2) && bl_cell(bl_check_geo(), 7, 37) == bl_cell(3, 7, 37), "the Geo forwards agree with the PV forms");
 
 constexpr uint32_t kLoopStop = 0x80000000u;     // doorbell bit: the host ends the loop
 constexpr uint32_t kJoinClosed = 0x80000000u;  // k_run<TEAM = 2>: bit of xj[e] - the environment takes no more members

@@ -5,7 +5,7 @@
 // along each row, k_dist_points the same minimum for single cells.  Part of the single translation unit simfire_hip.hip.  The status
 // bytes are read from whichever cell plane is current; nothing but the scratch plane and `out` is written.
 #pragma once
-#include "sf_common.h"
+#include "sf_query_dev.h"
 
 namespace {
 
@@ -20,14 +20,13 @@ constexpr long long kDistScratchDefault = 128ll << 20;     // bytes of scratch a
 
 struct DistArgs {
     Geo g;
-    const uint8_t *status;     // row-major status plane (read when cells is null)
-    const uint8_t *cells;      // the blocked plane of the resident launch when it is current (bl_vec), else null
+    CellPlanes pl;             // the status bytes, in whichever plane is current
     const int32_t *envs;       // the listed environments of this chunk [cn]
     uint16_t *gp;              // scratch: [cn][H][P]
     const int32_t *points;     // this chunk's [cn][k][3] (column, row, id), or null (plane form)
     void *out;                 // this chunk's part of the output: [cn][H][W] or [cn][k]
     int cn, k;
-    uint32_t tlo, thi;         // byte s of (thi : tlo) = 1 if the mask selects BurnStatus s (the table of one byte permute)
+    uint32_t tlo, thi;         // the mask as the table of one byte permute (mask_sel01)
     int limit;                 // max_d2, or SF_DIST_FAR without a cap
     int reach;                 // columns either side of a point that can still lower its value: the smallest r with r^2 >= limit, W without a cap
     int f32, vec, rows;        // float output; 16-byte stores (W % 4 == 0 and an aligned output); rows per k_dist_rows workgroup
@@ -37,17 +36,12 @@ struct DistArgs {
 // 0/1 per byte of the 16 cells of vector v in row y: the cell is on the grid and its status is selected
 __device__ __forceinline__ uint4 dist_sel01(const DistArgs &a, uint4 q, int v)
 {
-    q = and4(q, 0x07070707u);
-    const int in = a.g.W - v * 16;               // cells of the vector on the grid (the rest is pitch padding: never a source)
-    return make_uint4(__builtin_amdgcn_perm(a.thi, a.tlo, q.x) & first01(in), __builtin_amdgcn_perm(a.thi, a.tlo, q.y) & first01(in - 4),
-                      __builtin_amdgcn_perm(a.thi, a.tlo, q.z) & first01(in - 8), __builtin_amdgcn_perm(a.thi, a.tlo, q.w) & first01(in - 12));
+    // (the cells of the vector past the width are pitch padding: never a source)
+    return and44(mask_sel01(a.tlo, a.thi, and4(q, 0x07070707u)), first01x16(a.g.W - v * 16));
 }
-__device__ __forceinline__ const uint4 *dist_status(const DistArgs &a, int e, int y, int v)
+__device__ __forceinline__ uint4 dist_vec(const DistArgs &a, int e, int y, int v)      // the 16 status bytes of vector v in row y
 {
-    const Geo &g = a.g;
-    const uint8_t *p = a.cells ? a.cells + (long long)e * g.cells_env + bl_vec(g, y, v) + (y & 1) * 16 + kBlStatus
-                               : a.status + (long long)e * g.plane_env + (long long)y * g.P + v * 16;
-    return reinterpret_cast<const uint4 *>(p);
+    return *reinterpret_cast<const uint4 *>(cell_status_vec(a.pl, a.g, e, y, v));
 }
 __device__ __forceinline__ int dist_next(int d) { return d + 1 < kDistNone ? d + 1 : kDistNone; }
 
@@ -67,10 +61,10 @@ __global__ __launch_bounds__(kDistColsThreads) void k_dist_cols_down(DistArgs a)
     for (int c = 0; c < 16; ++c) d[c] = kDistNone;
     uint4 cur[kDistDownAhead], nxt[kDistDownAhead];
 #pragma unroll
-    for (int j = 0; j < kDistDownAhead; ++j) cur[j] = *dist_status(a, e, min(j, g.H - 1), v);
+    for (int j = 0; j < kDistDownAhead; ++j) cur[j] = dist_vec(a, e, min(j, g.H - 1), v);
     for (int y0 = 0; y0 < g.H; y0 += kDistDownAhead) {
 #pragma unroll
-        for (int j = 0; j < kDistDownAhead; ++j) nxt[j] = *dist_status(a, e, min(y0 + kDistDownAhead + j, g.H - 1), v);
+        for (int j = 0; j < kDistDownAhead; ++j) nxt[j] = dist_vec(a, e, min(y0 + kDistDownAhead + j, g.H - 1), v);
 #pragma unroll
         for (int j = 0; j < kDistDownAhead; ++j) {
             const int y = y0 + j;
@@ -227,10 +221,10 @@ __global__ __launch_bounds__(kDistRowsThreads) void k_dist_points(DistArgs a)
     const int lane = threadIdx.x & 63;
     const int i = blockIdx.y, j = blockIdx.x * (kDistRowsThreads / 64) + (threadIdx.x >> 6);
     if (j >= a.k) return;                            // (wave-uniform)
-    const int32_t *p = a.points + ((long long)i * a.k + j) * 3;
-    const int x = p[0], y = p[1], id = p[2];
+    const QueryPoint p = query_point(a.points, (long long)i * a.k + j, g.W, g.H);
+    const int x = p.x, y = p.y;
     int32_t val;
-    if (id <= 0 || x < 0 || x >= g.W || y < 0 || y >= g.H) {
+    if (!p.ok) {
         val = a.f32 ? __float_as_int(-1.0f) : -1;
     } else {
         const uint16_t *row = a.gp + ((long long)i * g.H + y) * g.P;

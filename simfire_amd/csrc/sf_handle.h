@@ -375,6 +375,9 @@ struct sf_sim {
 
 // the blocked plane if it is the current one, else null: what a kernel that reads whichever layout is current takes as `cells`
 static uint8_t *cur_cells(const sf_sim *s) { return s->planes.blocked() ? s->cells : nullptr; }
+// the status bytes as the kernels off the step path take them (sf_cells.h): to read, and to write
+static CellPlanes cur_planes(const sf_sim *s) { return CellPlanes{s->status, cur_cells(s)}; }
+static CellPlanesMut cur_planes_mut(const sf_sim *s) { return CellPlanesMut{s->status, cur_cells(s)}; }
 // In front of a launch that looks after the per-tile histograms: while every one is stale, say so on the device.
 static int mark_hist_dirty(sf_sim *s)
 {

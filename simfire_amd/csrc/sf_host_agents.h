@@ -243,8 +243,7 @@ static AgentArgs agent_args(const sf_sim *s, const int32_t *actions, const sf_ag
     AgentArgs a;
     memset(&a, 0, sizeof a);
     a.g = s->g;
-    a.status = s->status;
-    a.cells = cur_cells(s);        // (whichever plane is current NOW: the step between the two kernels may change it)
+    a.pl = cur_planes(s);          // (whichever plane is current NOW: the step between the two kernels may change it)
     a.rows = s->status_block;
     a.actions = actions;
     a.xyid = s->agents.xyid; a.start = s->agents.start; a.points = s->agents.points; a.prev_cnt = s->agents.prev; a.terms = s->agents.terms;

@@ -35,7 +35,7 @@ static int check_scratch(const char *who, int64_t scratch_bytes, size_t need, co
     return SF_OK;
 }
 
-// A status mask as the table of one byte permute: byte s of (hi : lo) = 1 if the mask selects BurnStatus s
+// A status mask as the table of one byte permute: byte s of (hi : lo) = 1 if the mask selects BurnStatus s (read by mask_sel01, sf_query_dev.h)
 static void mask_tables(int mask, uint32_t &lo, uint32_t &hi)
 {
     lo = hi = 0;
@@ -83,8 +83,7 @@ extern "C" int sf_distance(sf_sim *s, const sf_dist_params *p, int32_t n, const 
     DistArgs a;
     memset(&a, 0, sizeof a);
     a.g = g;
-    a.status = s->status;
-    a.cells = cur_cells(s);
+    a.pl = cur_planes(s);
     a.gp = reinterpret_cast<uint16_t *>(d.mem);
     a.k = p->k;
     mask_tables(p->status_mask, a.tlo, a.thi);
@@ -125,8 +124,7 @@ static void band_args(const sf_sim *s, ReachArgs &r, const uint8_t *passable, in
 {
     const Geo &g = s->g;
     r.g = g;
-    r.status = s->status;
-    r.cells = cur_cells(s);
+    r.pl = cur_planes(s);
     r.passable = passable;
     r.pass_env = per_env ? (long long)g.H * g.W : 0;
     r.pass_vec = passable && g.W % 16 == 0 && !((uintptr_t)passable & 15);
@@ -317,8 +315,7 @@ extern "C" int sf_travel(sf_sim *s, const sf_travel_params *p, int32_t n, const 
     TravelArgs a;
     memset(&a, 0, sizeof a);
     a.g = g;
-    a.status = s->status;
-    a.cells = cur_cells(s);
+    a.pl = cur_planes(s);
     a.rt = s->rt;
     a.sources = p->sources;
     a.src_env = p->sources_per_env ? (long long)cells : 0;
@@ -422,10 +419,9 @@ extern "C" int sf_behavior(sf_sim *s, const sf_behavior_params *p, const sf_beha
     if (out->max_intensity) HIPCHK(hipMemsetAsync(out->max_intensity, 0, (size_t)n * sizeof(float), s->stream));
     if (out->classes) HIPCHK(hipMemsetAsync(out->classes, 0, (size_t)n * 5 * sizeof(int32_t), s->stream));
 
-    a.H = g.H; a.W = g.W; a.P = g.P; a.PV = g.PV;
-    a.plane_env = g.plane_env; a.rt_env = g.rt_env; a.cells_env = g.cells_env;
-    a.status = s->status;
-    a.cells = cur_cells(s);
+    a.g = cell_geo(g);
+    a.pl = cur_planes(s);
+    a.rt_env = g.rt_env;
     a.rt = s->rt;
     a.hpa = b.hpa;
     a.hpa_env = per_env ? (long long)g.H * g.W : 0;
@@ -505,9 +501,8 @@ extern "C" int sf_perimeter(sf_sim *s, const sf_perimeter_params *p, int32_t n, 
     }
     const int32_t *envs_dev = nullptr;
     SF_TRY(block_stage(s, q.blk, &envs_dev, envs, (size_t)n * sizeof(int32_t)));
-    a.g.H = g.H; a.g.W = g.W; a.g.P = g.P; a.g.PV = g.PV; a.g.plane_env = g.plane_env; a.g.cells_env = g.cells_env;
-    a.status = s->status;
-    a.cells = cur_cells(s);
+    a.g = cell_geo(g);
+    a.pl = cur_planes(s);
     a.member = p->member;
     a.mem_env = p->member_per_env ? (long long)cells : 0;
     a.arrival = s->arrival.plane;

@@ -113,7 +113,7 @@ static StateArgs state_args(sf_sim *s)
     StateArgs a;
     memset(&a, 0, sizeof a);
     a.g = s->g;
-    a.status = s->status; a.age = s->age; a.cells = cur_cells(s);
+    a.pl = cur_planes_mut(s); a.age = s->age;
     a.burn = s->burn; a.settled = s->settled; a.parents = s->parents; a.arrival = s->arrival.plane; a.vbits = s->vbits;
     a.commit = s->commit; a.res_block = s->status_block; a.res_sink = s->sink; a.res_elapsed = s->elapsed_dev;
     a.lay = state_layout(s->g, s->parents != nullptr, s->arrival.plane != nullptr);
@@ -144,7 +144,7 @@ static int reset_launch(sf_sim *s, const int32_t *envs_dev, const uint8_t *mask,
     if (full) s->cost_steps = 0;       // the old episodes' costs (run_cost, zeroed) say nothing
     a.n_seg = value_seg(s, a.seg, arrival_seg(s, a.seg, env_segs(s, (kResetKinds & ~(seams ? 0u : kSegSeam) & ~(hist_known ? 0u : kSegHist)) | (full ? kSegCost : 0u), a.seg)));
     a.envs = envs_dev; a.mask = mask; a.xy = xy_dev; a.n = n;
-    a.status = s->status; a.age = s->age; a.cells = cur_cells(s);
+    a.pl = cur_planes_mut(s); a.age = s->age;
     a.commit = s->commit; a.tflags = s->tflags; a.ring = s->ring; a.vbits = s->vbits; a.win_hint = s->win_hint;
     a.seam = seams ? s->seam : nullptr;
     a.tdirty = hist_known ? s->tdirty : nullptr;

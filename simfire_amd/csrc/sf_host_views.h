@@ -441,8 +441,7 @@ extern "C" int sf_observe(sf_sim *s, const sf_obs_params *p, int32_t n, const in
     ObsArgs a;
     memset(&a, 0, sizeof a);
     a.g = g;
-    a.status = s->status;
-    a.cells = cur_cells(s);
+    a.pl = cur_planes(s);
     a.lay = s->lay_all;
     a.lay_tab = (size_t)s->tables.size() > 1 ? 7LL * g.H * g.W : 0;
     a.head = reinterpret_cast<const ObsHead *>(blk.dev);
@@ -571,8 +570,8 @@ extern "C" int sf_render(sf_sim *s, const sf_render_params *p, int32_t n, const 
     RenderArgs a;
     memset(&a, 0, sizeof a);
     a.g = g;
-    a.status = s->status;
-    a.cells = hist ? nullptr : cur_cells(s);
+    a.pl = cur_planes(s);
+    if (hist) a.pl.cells = nullptr;      // (the history ring is the source: neither plane is read)
     a.hist = hist ? s->history : nullptr;
     a.cap = s->history_cap; a.first = hist ? p->first : 0; a.count = count;
     a.bg = s->render.bg;

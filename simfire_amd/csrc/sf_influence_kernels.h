@@ -23,7 +23,7 @@
 //   k_infl_points  the plane values at each point's cell and the route up the parent chain, bounded by max_route.
 // Part of the single translation unit simfire_hip.hip.  Nothing but the scratch and the outputs is written.
 #pragma once
-#include "sf_common.h"
+#include "sf_query_dev.h"
 
 namespace {
 
@@ -212,10 +212,9 @@ __global__ __launch_bounds__(kInflThreads) void k_infl_points(InflArgs a, int cn
     const long long t = (long long)blockIdx.x * kInflThreads + threadIdx.x;
     if (t >= (long long)cn * a.k) return;
     const int i = (int)(t / a.k);
-    const int32_t *p = a.points + t * 3;
-    const int px = p[0], py = p[1];
-    const bool ok = p[2] > 0 && px >= 0 && px < a.W && py >= 0 && py < a.H;
-    long long c = (long long)py * a.W + px;
+    const QueryPoint p = query_point(a.points, t, a.W, a.H);
+    const bool ok = p.ok;
+    long long c = (long long)p.y * a.W + p.x;
     if (a.point_cells) a.point_cells[t] = ok ? infl_acc_c(a, i)[c] : -1;
     if (a.point_value) a.point_value[t] = ok ? infl_acc_v(a, i)[c] : 0ll;
     if (a.max_route > 0) {

@@ -20,8 +20,7 @@ struct ObsHead {
 
 struct ObsArgs {
     Geo g;
-    const uint8_t *status;     // row-major status plane (read when cells is null)
-    const uint8_t *cells;      // the blocked plane of the resident launch when it is current (bl_vec), else null
+    CellPlanes pl;             // the status bytes, in whichever plane is current
     const double *lay;         // dense layers [tables][7][H * W]: w_0 delta M_x sigma elevation U U_dir
     long long lay_tab;         // doubles between two environments' tables (0: one shared table)
     const ObsHead *head;
@@ -91,9 +90,7 @@ __global__ __launch_bounds__(kObsThreads) void k_observe(ObsArgs a)
         const long long y = sya + r, v = va + j;
         uint4 q = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
         if (y >= 0 && y < g.H && v >= 0 && v < g.PV) {
-            const uint8_t *src = a.cells ? a.cells + (long long)e * g.cells_env + bl_vec(g, (int)y, (int)v) + ((int)y & 1) * 16 + kBlStatus
-                                         : a.status + (long long)e * g.plane_env + y * g.P + v * 16;
-            q = and4(*reinterpret_cast<const uint4 *>(src), 0x07070707u);
+            q = and4(*reinterpret_cast<const uint4 *>(cell_status_vec(a.pl, g, e, y, v)), 0x07070707u);
             const int in = g.W - (int)v * 16;        // cells of the vector on the grid (the rest is pitch padding)
             if (in < 16) {
                 const uint32_t m0 = spread01(first01(in)), m1 = spread01(first01(in - 4)), m2 = spread01(first01(in - 8)),

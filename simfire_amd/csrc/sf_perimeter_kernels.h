@@ -12,7 +12,7 @@
 //   d = 0: SE & ~NE, 1: SW & ~SE, 2: NW & ~SW, 3: NE & ~NW.  Its id is (vy * (W + 1) + vx) * 4 + d; the kernel orders by
 //   (vy * VP + vx) * 4 + d with VP = 16 * ceil((W + 1) / 16), which is the same order: 16 vertices x 4 directions fill a 64-bit word.
 #pragma once
-#include "sf_common.h"
+#include "sf_query_dev.h"
 
 namespace {
 
@@ -23,22 +23,15 @@ constexpr int kPerimMaxWidth = 8192;
 constexpr int kPerimArrays = 8;               // int32 arrays of max_edges in an environment's scratch
 constexpr long long kPerimScratchDefault = 1ll << 30;      // bytes of scratch a call uses unless it names a budget
 
-// the few fields of Geo these kernels carry
-struct PerimGeo {
-    int H, W, P, PV;           // the grid, the row pitch and its 16-cell vectors
-    long long plane_env, cells_env;      // cells of a plane, bytes of the blocked plane per environment
-};
-
 struct PerimArgs {
-    PerimGeo g;
-    const uint8_t *status;     // row-major status plane (read when cells is null)
-    const uint8_t *cells;      // the blocked plane of the resident launch when it is current (bl_vec), else null
+    CellGeo g;
+    CellPlanes pl;             // the status bytes, in whichever plane is current
     const uint8_t *member;     // source 1: dense [H * W] u8, mem_env bytes between two environments' planes (0: one for all)
     long long mem_env;
     const uint32_t *arrival;   // source 2: the raw arrival plane [E][H][P], update + 1, 0 = never
     uint32_t at;               // source 2: the horizon (an update)
     int source;                // 0: status mask, 1: member, 2: arrival
-    uint32_t tlo, thi;         // source 0: byte s of (thi : tlo) = 1 if the mask selects BurnStatus s (the table of one byte permute)
+    uint32_t tlo, thi;         // source 0: the mask as the table of one byte permute (mask_sel16)
     const int32_t *envs;       // the listed environments of this launch [n]
     int n;
     int conn8, simplify;
@@ -68,22 +61,16 @@ __host__ __device__ inline long long perim_env_bytes(int H, int W, int max_edges
 // bit j: cell (16 v + j, y) is on the grid and in S; 0 <= y < H, v >= 0
 __device__ __forceinline__ uint32_t perim_vec16(const PerimArgs &a, int e, int y, int v)
 {
-    const PerimGeo &g = a.g;
+    const CellGeo &g = a.g;
     const int in = g.W - v * 16;                 // cells of the vector on the grid (the rest is pitch padding: never in S)
     if (in <= 0) return 0u;
     uint32_t m = 0u;
     if (a.source == 0) {
-        // (bl_vec of sf_common.h, written out for PerimGeo)
-        const uint8_t *p = a.cells ? a.cells + (long long)e * g.cells_env + ((y >> 2) * g.PV + v) * 128 + ((y >> 1) & 1) * 64 + (y & 1) * 16 + kBlStatus
-                                   : a.status + (long long)e * g.plane_env + (long long)y * g.P + v * 16;
-        const uint4 q = and4(*reinterpret_cast<const uint4 *>(p), 0x07070707u);
-        m = pack4(__builtin_amdgcn_perm(a.thi, a.tlo, q.x)) | (pack4(__builtin_amdgcn_perm(a.thi, a.tlo, q.y)) << 4) |
-            (pack4(__builtin_amdgcn_perm(a.thi, a.tlo, q.z)) << 8) | (pack4(__builtin_amdgcn_perm(a.thi, a.tlo, q.w)) << 12);
-    } else if (a.source == 1) {
+        m = mask_sel16(a.tlo, a.thi, and4(*reinterpret_cast<const uint4 *>(cell_status_vec(a.pl, g, e, y, v)), 0x07070707u));
+    } else if (a.source == 1) {      // (decided by the address, vector by vector - not dense_vec16, whose flag holds for a whole plane)
         const uint8_t *p = a.member + (long long)e * a.mem_env + (long long)y * g.W + v * 16;
         if (in >= 16 && !((uintptr_t)p & 15)) {
-            const uint4 q = *reinterpret_cast<const uint4 *>(p);
-            m = pack4(nz01(q.x)) | (pack4(nz01(q.y)) << 4) | (pack4(nz01(q.z)) << 8) | (pack4(nz01(q.w)) << 12);
+            m = pack16(nz01x16(*reinterpret_cast<const uint4 *>(p)));
         } else {
             const int k = in < 16 ? in : 16;
             for (int j = 0; j < k; ++j) m |= p[j] ? 1u << j : 0u;
@@ -107,13 +94,6 @@ __device__ __forceinline__ unsigned long long perim_word(const PerimArgs &a, int
            ((unsigned long long)perim_vec16(a, e, y, 4 * w + 2) << 32) | ((unsigned long long)perim_vec16(a, e, y, 4 * w + 3) << 48);
 }
 
-__device__ __forceinline__ uint32_t perim_wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-    return v;
-}
-
 // 4 bits -> 4 bytes of 0 / 1
 __device__ __forceinline__ uint32_t perim_bytes4(uint32_t n) { return ((n & 0xFu) * 0x00204081u) & 0x01010101u; }
 
@@ -124,7 +104,7 @@ __device__ __forceinline__ uint32_t perim_bytes4(uint32_t n) { return ((n & 0xFu
 __global__ __launch_bounds__(kPerimThreads) void k_perim_summary(PerimArgs a)
 {
     __shared__ uint32_t s_red[2];
-    const PerimGeo &g = a.g;
+    const CellGeo &g = a.g;
     const int t = threadIdx.x;
     const int items = (g.H + kPerimStrip - 1) / kPerimStrip * a.BW;
     if (t < 2) s_red[t] = 0u;
@@ -168,7 +148,7 @@ __global__ __launch_bounds__(kPerimThreads) void k_perim_summary(PerimArgs a)
         }
         // integer sums: a wave, the workgroup's two LDS slots, one atomic each per item block
         if (a.edges || a.ncells) {
-            ne = perim_wave_sum(ne); nc = perim_wave_sum(nc);
+            ne = wave_sum(ne); nc = wave_sum(nc);
             if ((t & 63) == 0) { if (ne) atomicAdd(&s_red[0], ne); if (nc) atomicAdd(&s_red[1], nc); }
             __syncthreads();
             if (t < 2) {
@@ -251,7 +231,7 @@ __global__ __launch_bounds__(kPerimTraceThreads) void k_perim_trace(PerimArgs a)
 {
     __shared__ int32_t s_w[kPerimTraceThreads / 64];
     __shared__ int s_cnt[2];
-    const PerimGeo &g = a.g;
+    const CellGeo &g = a.g;
     const int t = threadIdx.x, T = (int)blockDim.x;
     const int i = blockIdx.x, e = a.envs[i];
     const int H = g.H, W = g.W, BW = a.BW, EW = a.EW, VP = EW * 16, ME = a.max_edges;
@@ -275,7 +255,7 @@ __global__ __launch_bounds__(kPerimTraceThreads) void k_perim_trace(PerimArgs a)
             B[idx] = v;
             nc += (uint32_t)__popcll(v);
         }
-        nc = perim_wave_sum(nc);
+        nc = wave_sum(nc);
         if ((t & 63) == 0 && nc) atomicAdd(&s_cnt[0], (int)nc);
     }
     __syncthreads();
@@ -414,7 +394,7 @@ __global__ __launch_bounds__(kPerimTraceThreads) void k_perim_trace(PerimArgs a)
             if (a.loop_edges) a.loop_edges[(long long)i * a.max_loops + l] = len;
         }
     }
-    nh = (int)perim_wave_sum((uint32_t)nh);
+    nh = (int)wave_sum((uint32_t)nh);
     if ((t & 63) == 0 && nh) atomicAdd(&s_cnt[1], nh);
     __syncthreads();
     if (t == 0) {

@@ -17,7 +17,7 @@
 // Part of the single translation unit simfire_hip.hip.  The status bytes are read from whichever cell plane is current; nothing but
 // the scratch and the outputs is written.
 #pragma once
-#include "sf_common.h"
+#include "sf_query_dev.h"
 
 namespace {
 
@@ -30,8 +30,7 @@ typedef unsigned long long reach_word;
 
 struct ReachArgs {
     Geo g;
-    const uint8_t *status;       // row-major status plane (read when cells is null)
-    const uint8_t *cells;        // the blocked plane of the resident launch when it is current (bl_vec), else null
+    CellPlanes pl;               // the status bytes, in whichever plane is current
     const int32_t *envs;         // the listed environments of this chunk [cn]
     const uint8_t *passable;     // dense u8 [H * W] (pass_env = 0) or [E][H * W], or null
     long long pass_env;
@@ -48,7 +47,7 @@ struct ReachArgs {
     int32_t *seeds;
     int32_t *point_in;
     int32_t *rounds;
-    uint32_t slo, shi, tlo, thi; // byte s of (shi : slo) / (thi : tlo) = 1 if source_mask / through_mask selects BurnStatus s
+    uint32_t slo, shi, tlo, thi; // source_mask / through_mask as tables of one byte permute (mask_sel01)
     int conn8, max_rounds;
     int WORDS, BR, nb;           // words per row, band rows = ceil(H / kReachRows), bands = BR * WORDS
     int mask_vec;                // 16-byte stores of the mask (W % 16 == 0 and an aligned output)
@@ -70,35 +69,14 @@ __device__ __forceinline__ long long reach_at(int WORDS, int y, int wi)
     return ((long long)(y / kReachRows) * WORDS + wi) * kReachRows + (y % kReachRows);
 }
 
-__device__ __forceinline__ const uint4 *reach_status(const ReachArgs &a, int e, int y, int v)
-{
-    const Geo &g = a.g;
-    const uint8_t *p = a.cells ? a.cells + (long long)e * g.cells_env + bl_vec(g, y, v) + (y & 1) * 16 + kBlStatus
-                               : a.status + (long long)e * g.plane_env + (long long)y * g.P + v * 16;
-    return reinterpret_cast<const uint4 *>(p);
-}
-
 // 0/1 per byte of the 16 passable bytes of vector v in row y (cells past the width: 0)
 __device__ __forceinline__ uint4 reach_passable01(const ReachArgs &a, int e, int y, int v)
 {
-    const Geo &g = a.g;
-    const uint8_t *p = a.passable + a.pass_env * e + (long long)y * g.W + v * 16;
-    uint4 q;
-    if (a.pass_vec) {
-        q = *reinterpret_cast<const uint4 *>(p);
-    } else {
-        uint32_t w[4] = {0, 0, 0, 0};
-        const int in = g.W - v * 16;
-#pragma unroll
-        for (int c = 0; c < 16; ++c)
-            if (c < in) w[c >> 2] |= (uint32_t)p[c] << (8 * (c & 3));
-        q = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-    return make_uint4(nz01(q.x), nz01(q.y), nz01(q.z), nz01(q.w));
+    return nz01x16(dense_vec16(a.passable + a.pass_env * e, a.pass_vec, a.g.W, y, v));
 }
 
-// The seed and the open bits of word wi of row y: four status vectors, one byte permute per dword and mask (the masks as 8-entry
-// tables), the on-grid mask, passable; rows past the height, vectors past the pitch and the pitch padding give 0.
+// The seed and the open bits of word wi of row y: four status vectors, both masks (mask_sel01), the on-grid mask, passable; rows
+// past the height, vectors past the pitch and the pitch padding give 0.
 __device__ __forceinline__ void reach_stage(const ReachArgs &a, int e, int y, int wi, reach_word &sd, reach_word &op)
 {
     const Geo &g = a.g;
@@ -108,20 +86,13 @@ __device__ __forceinline__ void reach_stage(const ReachArgs &a, int e, int y, in
     for (int q = 0; q < 4; ++q) {
         const int v = wi * 4 + q;
         if (v >= g.PV) break;
-        const uint4 s = and4(*reach_status(a, e, y, v), 0x07070707u);
-        const int in = g.W - v * 16;
-        const uint32_t m0 = first01(in), m1 = first01(in - 4), m2 = first01(in - 8), m3 = first01(in - 12);
-        const uint32_t sb = pack4(__builtin_amdgcn_perm(a.shi, a.slo, s.x) & m0) | pack4(__builtin_amdgcn_perm(a.shi, a.slo, s.y) & m1) << 4 |
-                            pack4(__builtin_amdgcn_perm(a.shi, a.slo, s.z) & m2) << 8 | pack4(__builtin_amdgcn_perm(a.shi, a.slo, s.w) & m3) << 12;
-        uint4 o = make_uint4(__builtin_amdgcn_perm(a.thi, a.tlo, s.x) & m0, __builtin_amdgcn_perm(a.thi, a.tlo, s.y) & m1,
-                             __builtin_amdgcn_perm(a.thi, a.tlo, s.z) & m2, __builtin_amdgcn_perm(a.thi, a.tlo, s.w) & m3);
-        if (a.passable) {
-            const uint4 p = reach_passable01(a, e, y, v);
-            o = make_uint4(o.x & p.x, o.y & p.y, o.z & p.z, o.w & p.w);
-        }
-        const uint32_t ob = pack4(o.x) | pack4(o.y) << 4 | pack4(o.z) << 8 | pack4(o.w) << 12;
+        const uint4 s = and4(*reinterpret_cast<const uint4 *>(cell_status_vec(a.pl, g, e, y, v)), 0x07070707u);
+        const uint4 on = first01x16(g.W - v * 16);
+        const uint32_t sb = pack16(and44(mask_sel01(a.slo, a.shi, s), on));
+        uint4 o = and44(mask_sel01(a.tlo, a.thi, s), on);
+        if (a.passable) o = and44(o, reach_passable01(a, e, y, v));
         sd |= (reach_word)sb << (16 * q);
-        op |= (reach_word)ob << (16 * q);
+        op |= (reach_word)pack16(o) << (16 * q);
     }
 }
 
@@ -359,10 +330,9 @@ __global__ __launch_bounds__(kReachThreads) void k_reach(const ReachArgs *__rest
     }
     if (a.point_in) {
         for (int j = t; j < a.k; j += nt) {
-            const int32_t *p = a.points + ((long long)i * a.k + j) * 3;
-            const int x = p[0], y = p[1], id = p[2];
+            const QueryPoint p = query_point(a.points, (long long)i * a.k + j, g.W, g.H);
             int32_t val = -1;
-            if (id > 0 && x >= 0 && x < g.W && y >= 0 && y < g.H) val = (int32_t)((pl_f[reach_at(WORDS, y, x >> 6)] >> (x & 63)) & 1u);
+            if (p.ok) val = (int32_t)((pl_f[reach_at(WORDS, p.y, p.x >> 6)] >> (p.x & 63)) & 1u);
             a.point_in[(long long)i * a.k + j] = val;
         }
     }

@@ -227,8 +227,7 @@ __global__ void k_render_fuel_ix(long long n, const int32_t *codes, const int32_
 
 struct RenderArgs {
     Geo g;
-    const uint8_t *status;      // row-major status plane (read when cells and hist are null)
-    const uint8_t *cells;       // the blocked plane of the resident launch when it is current, else null
+    CellPlanes pl;              // the status bytes, in whichever plane is current (read when hist is null)
     const int8_t *hist;         // the history ring [E][cap][H][W] (history source), else null
     int cap, first, count;      // history: frame t of an item shows update first + t (slot (first + t) % cap)
     const uint32_t *bg;         // background words [tables][H * W]
@@ -311,9 +310,7 @@ __global__ __launch_bounds__(kRdThreads) void k_render(RenderArgs a)
     } else {
         for (int idx = t; idx < rows * g.PV; idx += kRdThreads) {
             const int r = idx / g.PV, v = idx - r * g.PV, y = y0 + r;
-            const uint8_t *src = a.cells ? a.cells + (long long)e * g.cells_env + bl_vec(g, y, v) + (y & 1) * 16 + kBlStatus
-                                         : a.status + (long long)e * g.plane_env + (long long)y * g.P + v * 16;
-            *reinterpret_cast<uint4 *>(st + r * a.stride + v * 16) = and4(*reinterpret_cast<const uint4 *>(src), 0x07070707u);
+            *reinterpret_cast<uint4 *>(st + r * a.stride + v * 16) = and4(*reinterpret_cast<const uint4 *>(cell_status_vec(a.pl, g, e, y, v)), 0x07070707u);
         }
     }
     __syncthreads();

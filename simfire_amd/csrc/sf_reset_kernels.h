@@ -24,7 +24,8 @@ struct ResetArgs {
     const int32_t *xy;
     int n;
     // what k_reset_ignite writes
-    uint8_t *status, *age, *cells;       // cells: the blocked plane when it is current, else null (row-major planes)
+    CellPlanesMut pl;                    // the status bytes - and, blocked, the sprite masks - in whichever plane is current
+    uint8_t *age;                        // the row-major sprite masks
     EnvState *commit;
     uint8_t *tflags;
     int ring;
@@ -81,12 +82,12 @@ __global__ __launch_bounds__(256) void k_reset_ignite(ResetArgs a)
     if (e < 0) return;
     const int tyw = y / (g.LR * g.RB), tx = (x / 16) / g.LC;
     if (a.tdirty) a.tdirty[((long long)e * g.TY + tyw) * g.TX + tx] = 1;      // only the ignition's tile is to be recounted
-    if (a.cells) {                      // the blocked cell plane is the current one (1-byte sprite masks)
-        uint8_t *cell = a.cells + (long long)e * g.cells_env + bl_cell(g, y, x);
-        cell[kBlStatus] = SF_BURNING;
-        cell[0] = 1u;
+    if (a.pl.cells) {                   // the blocked cell plane is the current one (1-byte sprite masks)
+        uint8_t *sp = bl_status(a.pl.cells, g, e, y, x);
+        *sp = SF_BURNING;
+        *bl_mask_beside(sp) = 1u;
     } else {
-        a.status[(long long)e * g.plane_env + (long long)y * g.P + x] = SF_BURNING;
+        a.pl.status[(long long)e * g.plane_env + (long long)y * g.P + x] = SF_BURNING;
         age_store(g, a.age + (long long)e * g.age_env * g.ab, (long long)y * g.P + x, 1u);   // ignition step 0
     }
     if (a.seam) {                       // the copies of the sprite columns either side of a chunk boundary (k_rebuild_seams)

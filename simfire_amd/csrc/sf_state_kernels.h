@@ -72,7 +72,8 @@ __host__ __device__ inline StateLayout state_layout(const Geo &g, bool parents, 
 constexpr int kStateEnvs = 128;     // environments per launch (their numbers travel as kernel arguments)
 struct StateArgs {
     Geo g;
-    uint8_t *status, *age, *cells;                 // cells: the blocked plane when it is current, else null (row-major planes)
+    CellPlanesMut pl;                              // the status bytes - and, blocked, the sprite masks - in whichever plane is current
+    uint8_t *age;                                  // the row-major sprite masks
     double *burn;
     uint32_t *settled;
     uint8_t *parents;
@@ -117,13 +118,13 @@ __global__ __launch_bounds__(256) void k_state_pack(StateArgs a)
     const long long c = (long long)y * g.W + x, o = (long long)e * g.plane_env + (long long)y * g.P + x;
     uint8_t st;
     uint32_t m;
-    if (a.cells) {
-        const uint8_t *cell = a.cells + (long long)e * g.cells_env + bl_cell(g, y, x);
-        m = cell[0];
-        st = cell[kBlStatus];
+    if (a.pl.cells) {
+        const uint8_t *sp = bl_status(a.pl.cells, g, e, y, x);
+        m = *bl_mask_beside(sp);
+        st = *sp;
     } else {
         m = age_load(g, a.age + (long long)e * g.age_env * g.ab, (long long)y * g.P + x);
-        st = a.status[o];
+        st = a.pl.status[o];
     }
     b[a.lay.status + c] = st;
     uint8_t *ma = b + a.lay.age + c * g.ab;
@@ -164,13 +165,13 @@ __global__ __launch_bounds__(256) void k_state_unpack(StateArgs a)
     const uint8_t *ma = b + a.lay.age + c * g.ab;
     uint32_t m = 0;
     for (int k = 0; k < g.ab; ++k) m |= (uint32_t)ma[k] << (8 * k);
-    if (a.cells) {
-        uint8_t *cell = a.cells + (long long)e * g.cells_env + bl_cell(g, y, x);
-        cell[0] = (uint8_t)m;
-        cell[kBlStatus] = st;
+    if (a.pl.cells) {
+        uint8_t *sp = bl_status(a.pl.cells, g, e, y, x);
+        *bl_mask_beside(sp) = (uint8_t)m;
+        *sp = st;
     } else {
         age_store(g, a.age + (long long)e * g.age_env * g.ab, (long long)y * g.P + x, m);
-        a.status[o] = st;
+        a.pl.status[o] = st;
     }
     a.burn[o] = reinterpret_cast<const double *>(b + a.lay.burn)[c];
     if (g.att) a.settled[o] = reinterpret_cast<const uint32_t *>(b + a.lay.settled)[c];

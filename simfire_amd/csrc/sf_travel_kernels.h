@@ -18,7 +18,7 @@
 // Part of the single translation unit simfire_hip.hip.  The status bytes are read from whichever cell plane is current; nothing but
 // the scratch and the outputs is written.  Compiled with -ffp-contract=off like the rest: every sum is one float32 addition.
 #pragma once
-#include "sf_common.h"
+#include "sf_query_dev.h"
 
 namespace {
 
@@ -32,8 +32,7 @@ static_assert(kTravelTile * kTravelTile == kTravelThreads, "k_travel: a thread p
 
 struct TravelArgs {
     Geo g;
-    const uint8_t *status;       // row-major status plane (read when cells is null)
-    const uint8_t *cells;        // the blocked plane of the resident launch when it is current (bl_cell), else null
+    CellPlanes pl;               // the status bytes, in whichever plane is current
     const double *rt;            // [tables][8][H][P]; g.rt_env elements between two environments' tables (0: one shared table)
     const int32_t *envs;         // the listed environments of this chunk
     const uint8_t *sources;      // dense u8 [H * W] (src_env = 0) or [E][H * W], or null
@@ -56,12 +55,6 @@ struct TravelArgs {
 
 // bytes of scratch per listed environment: the working array
 __host__ __device__ inline long long travel_env_bytes(const Geo &g) { return ((long long)g.H * g.W * 4 + 255) / 256 * 256; }
-
-__device__ __forceinline__ const uint8_t *travel_status(const TravelArgs &a, int e, int y, int x)
-{
-    const Geo &g = a.g;
-    return a.cells ? a.cells + (long long)e * g.cells_env + bl_cell(g, y, x) + kBlStatus : a.status + (long long)e * g.plane_env + (long long)y * g.P + x;
-}
 
 // 2: source, 1: passable (and not a source), 0: neither - cell (y, x) on the grid with the status byte s
 __device__ __forceinline__ int travel_class(const TravelArgs &a, int e, int y, int x, uint32_t s)
@@ -142,7 +135,7 @@ __global__ __launch_bounds__(kTravelThreads) void k_travel(TravelArgs a)
 #pragma unroll 1
     for (int idx = t; idx < H * G4; idx += nt) {
         const int y = idx / G4, x0 = (idx - y * G4) * 4;
-        const uint32_t sw = *reinterpret_cast<const uint32_t *>(travel_status(a, e, y, x0));
+        const uint32_t sw = *reinterpret_cast<const uint32_t *>(cell_status(a.pl, a.g, e, y, x0));
         const int in = min(4, W - x0);
         float v[4] = {-1.0f, -1.0f, -1.0f, -1.0f};
         bool src = false;
@@ -268,7 +261,7 @@ __global__ __launch_bounds__(kTravelThreads) void k_travel(TravelArgs a)
                 const float v = travel_load(a, T, s_T, ty * kTravelTile, tx * kTravelTile, t, in);
                 __syncthreads();
                 bool cand = in && v >= 0.0f && v < inf;
-                if (cand && v == 0.0f) cand = travel_class(a, e, y, x, *travel_status(a, e, y, x)) == 1;      // (a weight that rounds to 0)
+                if (cand && v == 0.0f) cand = travel_class(a, e, y, x, *cell_status(a.pl, a.g, e, y, x)) == 1;      // (a weight that rounds to 0)
                 if (cand) {
                     ++cnt;
                     mx = max(mx, __float_as_uint(v));
@@ -293,10 +286,10 @@ __global__ __launch_bounds__(kTravelThreads) void k_travel(TravelArgs a)
 
     // the points: lane t answers point t.  On a cell that is neither source nor passable: the time at which it would be reached
     if (t < a.k && a.point_minutes) {
-        const int32_t *p = a.points + ((long long)i * a.k + t) * 3;
-        const int px = p[0], py = p[1];
+        const QueryPoint p = query_point(a.points, (long long)i * a.k + t, W, H);
+        const int px = p.x, py = p.y;
         float r = -1.0f;
-        if (p[2] > 0 && px >= 0 && px < W && py >= 0 && py < H) {
+        if (p.ok) {
             float v = T[(long long)py * W + px];
             if (v < 0.0f) {
                 const double *rp = travel_rt(a, e, py, px);

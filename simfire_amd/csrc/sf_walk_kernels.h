@@ -28,7 +28,7 @@ constexpr long long kWalkScratchDefault = 256ll << 20;
 constexpr int32_t kWalkFar = 2147483647, kWalkBlocked = -1;
 
 struct WalkArgs {
-    // of these the search uses: g, status, cells, envs, passable, pass_env, pass_vec, points, k, scratch, scratch_env, slo / shi (the
+    // of these the search uses: g, pl, envs, passable, pass_env, pass_vec, points, k, scratch, scratch_env, slo / shi (the
     // target mask), tlo / thi (the through mask), conn8, WORDS, BR, nb - the staging helper takes them in this form
     ReachArgs r;
     const uint8_t *targets;      // dense u8 [H * W] (tgt_env = 0) or [E][H * W], or null
@@ -56,20 +56,7 @@ __device__ __forceinline__ reach_word walk_plane_bits(const uint8_t *plane, int 
     for (int q = 0; q < 4; ++q) {
         const int v = wi * 4 + q;
         if (v >= g.PV) break;
-        const uint8_t *p = plane + (long long)y * g.W + v * 16;
-        const int in = g.W - v * 16;
-        uint4 d;
-        if (vec) {
-            d = *reinterpret_cast<const uint4 *>(p);
-        } else {
-            uint32_t w[4] = {0, 0, 0, 0};
-#pragma unroll
-            for (int c = 0; c < 16; ++c)
-                if (c < in) w[c >> 2] |= (uint32_t)p[c] << (8 * (c & 3));
-            d = make_uint4(w[0], w[1], w[2], w[3]);
-        }
-        const uint32_t b = pack4(nz01(d.x) & first01(in)) | pack4(nz01(d.y) & first01(in - 4)) << 4 |
-                           pack4(nz01(d.z) & first01(in - 8)) << 8 | pack4(nz01(d.w) & first01(in - 12)) << 12;
+        const uint32_t b = pack16(and44(nz01x16(dense_vec16(plane, vec, g.W, y, v)), first01x16(g.W - v * 16)));
         out |= (reach_word)b << (16 * q);
     }
     return out;
@@ -190,9 +177,9 @@ __global__ __launch_bounds__(kWalkThreads) void k_walk(const WalkArgs *__restric
     int32_t pval = -1, pstep = -1;
     const int nn = conn8 ? 8 : 4;
     if (t < k) {
-        const int32_t *p = r.points + ((long long)i * k + t) * 3;
-        px = p[0]; py = p[1];
-        if (p[2] > 0 && px >= 0 && px < g.W && py >= 0 && py < g.H) {
+        const QueryPoint p = query_point(r.points, (long long)i * k + t, g.W, g.H);
+        px = p.x; py = p.y;
+        if (p.ok) {
             pstep = 0;
             if (walk_bit(pl_a, WORDS, py, px)) {
                 pval = 0;

@@ -23,7 +23,7 @@
 //     only written where something happens, and a step runs IN PLACE: every concurrent writer of
 //     a step touches only the two slots (t and t - md - 2) that readers mask out.
 //   * n steps of an sf_step(n) call = ONE launch of k_run (sf_run_kernels.h): a workgroup owns an environment for all n
-//     steps, its vector bitmaps live in LDS, the cells in a blocked plane (sf_common.h); the automatic choice for n >= 2 on
+//     steps, its vector bitmaps live in LDS, the cells in a blocked plane (sf_cells.h); the automatic choice for n >= 2 on
 //     grids up to 1024 cells wide.  Otherwise:
 //   * One step = k_select + k_step.  k_select (one thread per 64 x 32 wave tile) folds the
 //     per-environment predicates of fire.py:637-652 of the previous step (3-deep ring of flag
@@ -197,7 +197,7 @@ extern "C" int sf_create(const sf_params *p, sf_sim **out)
     TRY(dev_alloc(s, &s->seam, (size_t)g.E * g.seam_env));
     if (g.att) TRY(dev_alloc(s, &s->settled, cells));
     g.VW = (g.PV + 63) / 64; g.vb_env = (long long)g.H * g.VW;
-    g.cells_env = (long long)((g.H + 3) / 4 + 2) * g.PV * 128;
+    g.cells_env = bl_env_bytes(g.H, g.PV);
     TRY(dev_alloc(s, &s->vbits, (size_t)3 * g.E * g.vb_env));
     TRY(dev_alloc(s, &s->todo, (size_t)g.E));
     TRY(dev_alloc(s, &s->run_cost, (size_t)g.E));
@@ -538,13 +538,13 @@ static unsigned seg_grid_x(const EnvSeg *seg, int n)
 static int scatter_points(sf_sim *s, const int32_t *pts_dev, int n)
 {
     const Geo &g = s->g;
-    uint8_t *cells = cur_cells(s);
+    const CellPlanesMut pl = cur_planes_mut(s);
     s->planes.points_scattered();
     const dim3 grd((unsigned)((n + 255) / 256)), blk(256);
-    hipLaunchKernelGGL(k_mitigate_clear, grd, blk, 0, s->stream, g, s->status, cells, (const uint32_t *)s->settled, s->burn,
+    hipLaunchKernelGGL(k_mitigate_clear, grd, blk, 0, s->stream, g, pl, (const uint32_t *)s->settled, s->burn,
                        (const EnvState *)s->commit, (const EnvState *)s->tmp, (const uint32_t *)s->flags, s->seq,
                        s->planes.committed() ? 1 : 0, pts_dev, n);
-    hipLaunchKernelGGL(k_mitigate_write, grd, blk, 0, s->stream, g, s->status, cells, s->settled, s->tdirty,
+    hipLaunchKernelGGL(k_mitigate_write, grd, blk, 0, s->stream, g, pl, s->settled, s->tdirty,
                        (const EnvState *)s->commit, (const EnvState *)s->tmp, (const uint32_t *)s->flags, s->seq,
                        s->planes.committed() ? 1 : 0, pts_dev, n);
     HIPCHK(hipGetLastError());
@@ -624,7 +624,7 @@ extern "C" int sf_load_fire_map(sf_sim *s, int32_t env, const uint8_t *map)
     return SF_OK;
 }
 
-// The resident launch works on the blocked cell plane (sf_common.h, bl_vec), everything else on the row-major planes; the
+// The resident launch works on the blocked cell plane (sf_cells.h), everything else on the row-major planes; the
 // one that is current is converted when the other kind of work comes next (one sweep over the cell planes).
 static int ensure_rm(sf_sim *s)
 {
@@ -1689,7 +1689,7 @@ static int get_maps(sf_sim *s, int env0, int n, uint8_t *out)
     const size_t bytes = (size_t)n * g.H * g.W;
     SF_TRY(ensure_stage(s, bytes));
     dim3 blk(256), grd((g.W + 255) / 256, g.H, n);
-    hipLaunchKernelGGL(k_unpack_status, grd, blk, 0, s->stream, g, (const uint8_t *)s->status, (const uint8_t *)cur_cells(s), env0, (uint8_t *)s->stage, (uint8_t *)nullptr);
+    hipLaunchKernelGGL(k_unpack_status, grd, blk, 0, s->stream, g, cur_planes(s), env0, (uint8_t *)s->stage, (uint8_t *)nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, s->stage, bytes, hipMemcpyDeviceToHost, s->stream));
     return finish_call(s, "sf_get_fire_map(s)", true, nullptr);
@@ -1745,13 +1745,13 @@ static int delta_enqueue(sf_sim *s, int env, int cap, int *mode, bool with_row =
         // no reference point: the current map becomes it, the caller fetches the whole map
         dim3 blk(256), grd((g.W + 255) / 256, g.H, 1);
         SF_TRY(ensure_stage(s, (size_t)g.H * g.W));
-        hipLaunchKernelGGL(k_unpack_status, grd, blk, 0, s->stream, g, (const uint8_t *)s->status, (const uint8_t *)cur_cells(s), env, (uint8_t *)s->stage, s->delta.snap);
+        hipLaunchKernelGGL(k_unpack_status, grd, blk, 0, s->stream, g, cur_planes(s), env, (uint8_t *)s->stage, s->delta.snap);
         HIPCHK(hipGetLastError());
         s->delta.snap_valid[env] = 1;
         *mode = 1;
         return SF_OK;
     }
-    hipLaunchKernelGGL(k_map_delta, dim3((g.PV + 255) / 256, g.H), dim3(256), 0, s->stream, g, (const uint8_t *)s->status, (const uint8_t *)cur_cells(s), env,
+    hipLaunchKernelGGL(k_map_delta, dim3((g.PV + 255) / 256, g.H), dim3(256), 0, s->stream, g, cur_planes(s), env,
                        s->delta.snap + (size_t)env * g.plane_env, s->delta.dev, cap, s->delta.base,
                        with_row ? (const int32_t *)(s->status_block + (size_t)env * 8) : nullptr, (const double *)(s->elapsed_dev + env));
     HIPCHK(hipGetLastError());
@@ -1880,7 +1880,7 @@ static int refresh_status(sf_sim *s, int32_t *copy_to)
     if (g.ab == 1 && !s->generic) {
         // per-tile histograms: only the tiles touched since the last query are recounted; one launch writes the whole block
         SF_TRY(mark_hist_dirty(s));
-        hipLaunchKernelGGL(k_counts_tiles, dim3((unsigned)g.E), dim3(1024), 0, s->stream, g, (const uint8_t *)s->status, (const uint8_t *)cur_cells(s), s->tdirty, s->thist,
+        hipLaunchKernelGGL(k_counts_tiles, dim3((unsigned)g.E), dim3(1024), 0, s->stream, g, cur_planes(s), s->tdirty, s->thist,
                            (const EnvState *)s->commit, s->status_block, s->elapsed_dev, copy_to ? copy_to : sink2);
         if (copy_to && sink2) HIPCHK(hipMemcpyAsync(sink2, s->status_block, sizeof(int32_t) * 8 * g.E, hipMemcpyDeviceToDevice, s->stream));
         s->planes.counted(true);           // (the block - and the registered sink's copy - is current until something changes a status byte)
