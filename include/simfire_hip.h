@@ -317,6 +317,26 @@ int sf_apply_mitigation(sf_sim *sim, const int32_t *pts, int32_t n);
  * policy): rows (env, column, row, type) int32; rows with an out-of-range field are skipped. */
 int sf_apply_mitigation_device(sf_sim *sim, const int32_t *device_pts, int32_t n);
 
+/* New fire during an episode: burn-out and backfire operations, spot fires, a second start.  The reference has
+ * no such call; the definition follows its sprite list: fire_manager.sprites / durations are parallel lists (fire.py:102-103) that
+ * every update() leaves ordered by age, oldest first, and inside one age by (y, x) ascending (np.unique, fire.py:566-587).  For every
+ * row whose cell is UNBURNED a Fire sprite of duration 0 is inserted at the place that keeps this order - among the duration-0 sprites,
+ * by (y, x) - and fire_map[y, x] = BURNING: the cell cannot be told from one the last update() ignited.  burn_amounts, elapsed_time and
+ * the update counts are untouched; the cell is a root of the spread graph; with arrival recording on its arrival is the number of
+ * update() calls its episode has made (0 right after a reset) and damage counts its value once, both complete when the call is.
+ * rows = int32 [n][4] = (env, column, row, reserved = 0), the row shape of sf_apply_mitigation.  A row is skipped silently when its
+ * cell is not UNBURNED (a control line, BURNING, BURNED) or its environment is not running (finished, or QUIT and still pruning); a
+ * cell without fuel is lit like any other and burns out without spreading; a cell listed several times is lit once; an environment
+ * whose last sprite is about to be pruned goes on with the new ones.
+ * sf_ignite: host rows; an environment, column or row out of range or reserved != 0 is SF_EINVAL naming the row, before any device
+ * work.  sf_ignite_device: rows in device memory, 16-byte aligned (else SF_EINVAL), e.g. a policy's tensor - nothing is read back,
+ * such rows are skipped by the kernel.  Both: a null handle, n < 0 or a null list with n > 0 is SF_EINVAL; n == 0 does nothing; before
+ * the first sf_reset SF_ESTATE; a running closed loop is ended first and a handle whose last team launch failed is refused; in async
+ * mode (sf_set_async) they only enqueue, otherwise they wait once at their end.  Not part of sf_loop_step, sf_rollout or
+ * sf_step_mitigated: between such calls only. */
+int sf_ignite(sf_sim *sim, const int32_t *pts, int32_t n);
+int sf_ignite_device(sf_sim *sim, const int32_t *device_pts, int32_t n);
+
 /* FireSimulation.load_mitigation (simulation.py:425-447): fire_map of one environment is
  * replaced wholesale (uint8 [H*W], values 0..5 else SF_EINVAL); burning sprites persist. */
 int sf_load_fire_map(sf_sim *sim, int32_t env, const uint8_t *fire_map);

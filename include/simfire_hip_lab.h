@@ -20,6 +20,10 @@ int sf_step_timed(sf_sim *sim, int32_t n_steps, float *ms_out);
  * are the ones sf_step_timed uses. */
 int sf_time_resets(sf_sim *sim, int32_t on);
 int sf_get_reset_ms(sf_sim *sim, float *ms_out);
+/* The same for sf_ignite / sf_ignite_device: the events go around the one scatter launch of every such call (not around the arrival
+ * and value passes behind it); sf_get_ignite_ms reports the last one's GPU time (SF_ESTATE when none has been timed). */
+int sf_time_ignites(sf_sim *sim, int32_t on);
+int sf_get_ignite_ms(sf_sim *sim, float *ms_out);
 
 /* Introspection for benchmarks: out[0] = active cell-updates (cells whose burn_amounts were
  * read+written: candidates and attenuated line cells), out[1] = ignitions, out[2] = cells handed

@@ -99,6 +99,28 @@ def cells(xy, shape, H, W, who, what="cell"):
     return a
 
 
+def ignite_rows(points, n_envs, H, W, who):
+    """Host ignition rows, ``[n, 3]`` = (env, x, y) or ``[n, 4]`` with a reserved 0 behind, as the contiguous int32 ``[n, 4]`` array
+    the library takes: an environment outside 0..n_envs - 1 is an ``IndexError``, anything else wrong a ``ValueError`` - as
+    ``reset_envs`` tells them apart.  An empty list of either width passes."""
+    a = np.asarray(points)
+    if a.size == 0 and a.ndim <= 2:
+        return np.zeros((0, 4), dtype=np.int32)
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"{who}: rows must be integers, got {a.dtype}")
+    if a.ndim != 2 or a.shape[1] not in (3, 4):
+        raise ValueError(f"{who}: rows must have shape (n, 3) = (env, x, y) or (n, 4), got {a.shape}")
+    if a.shape[1] == 4 and (a[:, 3] != 0).any():
+        raise ValueError(f"{who}: the fourth field of row {int(np.flatnonzero(a[:, 3] != 0)[0])} is reserved and must be 0")
+    if a.min() < -2 ** 31 or a.max() >= 2 ** 31:
+        raise ValueError(f"{who}: rows hold values outside int32")
+    env_range(a[:, 0], n_envs, who, "rows", exc=IndexError)
+    cells(a[:, 1:3], (a.shape[0], 2), H, W, who, "ignition")
+    q = np.zeros((a.shape[0], 4), dtype=np.int32)
+    q[:, :3] = a[:, :3]
+    return q
+
+
 def box(b, H, W, who, name):
     """(x0, y0, x1, y1), inclusive, on the grid, as a list of ints."""
     b = [int(v) for v in b]

@@ -259,6 +259,10 @@ SIGNATURES = {
     "sf_get_reset_ms": [_VP, C.POINTER(C.c_float)],
     "sf_apply_mitigation": [_VP, _VP, _I32],
     "sf_apply_mitigation_device": [_VP, _VP, _I32],
+    "sf_ignite": [_VP, _VP, _I32],
+    "sf_ignite_device": [_VP, _VP, _I32],
+    "sf_time_ignites": [_VP, _I32],
+    "sf_get_ignite_ms": [_VP, C.POINTER(C.c_float)],
     "sf_load_fire_map": [_VP, _I32, _VP],
     "sf_step": [_VP, _I32],
     "sf_step_timed": [_VP, _I32, C.POINTER(C.c_float)],

@@ -364,6 +364,7 @@ struct sf_sim {
     CallBlock obs_blk;                 // sf_observe: ObsHead, environment list, host centers / agents
     CallBlock rs_blk;                  // sf_reset_envs / sf_reset_where: the environment list and host ignitions of a call
     LabTimer reset_timer;              // sf_time_resets: ev0 / ev1 recorded around the launches of every batched reset
+    LabTimer ignite_timer;             // sf_time_ignites: the same around the scatter launch of every sf_ignite / sf_ignite_device
     CallBlock gen_blk;                 // sf_generate_layers: its descriptors + environment list
     CallBlock ens_blk;                 // sf_ensemble_stats: the member list of a call
     size_t val_plane_bytes() const { return (size_t)(values.per_env ? g.E : 1) * g.plane_env * sizeof(int32_t); }

@@ -6,8 +6,9 @@
 // ----------------------------------------------------------------------------- arrival times
 // The pass behind the launches (sf_arrival_kernels.h): reads every environment's update count from commit[], so the step rings are
 // folded first.  Sparse where the blocked plane is current and every plane of the vector bitmap is known to match it, else dense over
-// whichever plane is current.  Recording off: nothing.
-static int arrival_pass(sf_sim *s)
+// whichever plane is current.  Recording off: nothing.  arrival_scan: the plane alone, without the value pass behind it (a caller
+// that counts the damage again from the plane anyway: ignite_rows).
+static int arrival_scan(sf_sim *s)
 {
     if (!s->arrival.plane) return SF_OK;
     { int rc0 = ensure_commit(s); if (rc0) return rc0; }
@@ -26,6 +27,12 @@ static int arrival_pass(sf_sim *s)
     HIPCHK(hipGetLastError());
     s->arrival.passes[sparse ? 0 : 1]++;
     s->arrival.pending = 0;
+    return SF_OK;
+}
+static int arrival_pass(sf_sim *s)
+{
+    if (!s->arrival.plane) return SF_OK;
+    SF_TRY(arrival_scan(s));
     return s->values.plane ? value_pass(s) : SF_OK;      // the plane is complete up to commit[].steps: so is the damage behind this
 }
 // The plane's per-environment slice behind the n slices env_segs has filled (a reset zeroes it, a fork copies it): appended here and not

@@ -48,6 +48,9 @@ public:
 
     // ---- changes from outside the step kernels
     void points_scattered() { row_fresh_ = false; }      // control-line points were written into the status bytes (scatter_points)
+    // new sprites were written into running environments (ignite_rows), each into every derived structure that is valid: the fires
+    // may be of any size, as after map_loaded, and status bytes changed
+    void cells_ignited() { fire_rows_ = 0; row_fresh_ = false; }
     // another number of rows per band (sf_set_rows_per_band): tiles and histograms are laid out per wave tile
     void geometry_changed() { row_fresh_ = false; hist_all_stale_ = true; tiles_valid_ = false; }
     void family_switched() { hist_all_stale_ = true; }      // tiled <-> per-cell kernels (sf_set_generic): only the tiled ones keep the histograms

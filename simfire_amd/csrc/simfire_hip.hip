@@ -89,6 +89,7 @@
 #include "sf_perimeter_kernels.h"
 #include "sf_influence_kernels.h"
 #include "sf_behavior_kernels.h"
+#include "sf_ignite_kernels.h"
 
 // The host code: the handle and the prologue / epilogue of a call (sf_handle.h), then one fragment per feature (sf_host_*.h, included
 // below where their functions stood while this was one file: kernel templates are instantiated in the order the host code names
@@ -551,18 +552,10 @@ static int scatter_points(sf_sim *s, const int32_t *pts_dev, int n)
     return SF_OK;
 }
 
-extern "C" int sf_apply_mitigation(sf_sim *s, const int32_t *pts, int32_t n)
+// n host rows of four int32 -> the next buffer of the pinned, device-mapped ring (sf_apply_mitigation, sf_ignite): *slot names it,
+// s->pts_mapped[*slot] is what a kernel reads, and the caller records s->ev_pts[*slot] behind the kernels that do.
+static int pts_stage(sf_sim *s, const int32_t *pts, int n, int *slot_out)
 {
-    if (!s) return fail(SF_EINVAL, "sf_apply_mitigation: null handle");
-    if (n < 0 || (n > 0 && !pts)) return fail(SF_EINVAL, "sf_apply_mitigation: bad point list");
-    if (n == 0) return SF_OK;
-    const Geo &g = s->g;
-    for (int i = 0; i < n; ++i) {
-        const int32_t *q = pts + 4 * i;
-        if (q[0] < 0 || q[0] >= g.E || q[1] < 0 || q[1] >= g.W || q[2] < 0 || q[2] >= g.H)
-            return fail(SF_EINVAL, "sf_apply_mitigation: point %d = (env %d, x %d, y %d) is out of range", i, q[0], q[1], q[2]);
-    }
-    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
     const size_t bytes = (size_t)4 * n * sizeof(int32_t);
     if ((size_t)4 * n > s->pts_cap) {
         HIPCHK(hipStreamSynchronize(s->stream));
@@ -582,6 +575,24 @@ extern "C" int sf_apply_mitigation(sf_sim *s, const int32_t *pts, int32_t n)
     // KB over the host link; no copy to enqueue).  It may still feed kernels enqueued kPtsRing calls ago.
     HIPCHK(hipEventSynchronize(s->ev_pts[slot]));
     memcpy(s->pts_pinned[slot], pts, bytes);
+    *slot_out = slot;
+    return SF_OK;
+}
+
+extern "C" int sf_apply_mitigation(sf_sim *s, const int32_t *pts, int32_t n)
+{
+    if (!s) return fail(SF_EINVAL, "sf_apply_mitigation: null handle");
+    if (n < 0 || (n > 0 && !pts)) return fail(SF_EINVAL, "sf_apply_mitigation: bad point list");
+    if (n == 0) return SF_OK;
+    const Geo &g = s->g;
+    for (int i = 0; i < n; ++i) {
+        const int32_t *q = pts + 4 * i;
+        if (q[0] < 0 || q[0] >= g.E || q[1] < 0 || q[1] >= g.W || q[2] < 0 || q[2] >= g.H)
+            return fail(SF_EINVAL, "sf_apply_mitigation: point %d = (env %d, x %d, y %d) is out of range", i, q[0], q[1], q[2]);
+    }
+    HIPCHK(hipSetDevice(s->p.device)); LOOP_QUIESCE(s);
+    int slot = 0;
+    SF_TRY(pts_stage(s, pts, n, &slot));
     SF_TRY(scatter_points(s, s->pts_mapped[slot], n));
     HIPCHK(hipEventRecord(s->ev_pts[slot], s->stream));
     return finish_call(s, nullptr, !s->async, nullptr);
@@ -1862,6 +1873,7 @@ extern "C" int sf_set_burn(sf_sim *s, int32_t env, const double *burn)
 }
 
 #include "sf_host_state.h"
+#include "sf_host_ignite.h"
 
 #include "sf_host_agents.h"
 

@@ -381,6 +381,38 @@ class FireEngine:
             # many times in async mode without a sync(), and the list would grow with every one
             self._keep_alive = pts          # until the next call: the scatter may still be queued (async mode)
 
+    def ignite(self, points):
+        """New fire in running environments (``sf_ignite``): rows ``(env, x, y)`` - ``[n, 3]``, or ``[n, 4]``
+        with a reserved 0 behind.  Every listed cell that is UNBURNED becomes BURNING with a sprite of age 0, as if the last update
+        had ignited it; rows on other cells, or in environments that are not running, are skipped.  Argument errors are raised
+        before any device call: ``IndexError`` for an environment out of range, ``ValueError`` otherwise.  In async mode the call
+        only enqueues."""
+        q = _args.ignite_rows(points, self.n_envs, self.H, self.W, "ignite")
+        if len(q):
+            self._chk(self._L.sf_ignite(self._h, _ptr(q), len(q)))
+
+    def ignite_torch(self, points):
+        """The same for a contiguous torch int32 tensor ``[n, 4]`` = (env, x, y, 0) that already lives on this GPU
+        (``sf_ignite_device``): no host round trip; rows with an out-of-range field or a fourth field that is not 0 are skipped.
+        The library works on a stream of its own and waits for nothing here: the caller orders its own stream before this call (a
+        device-wide wait, a stream wait or an event), as for ``apply_mitigation_torch`` - which is why a tensor that is not
+        contiguous is refused, not copied (the copy would run on torch's stream behind the caller's back).  The tensor is kept
+        alive until the next call."""
+        points = _args.cuda_tensor(points, "ignite_torch: points", ("int32",), [(None, 4)], contiguous=True)
+        if points.device != self.torch_device:
+            raise ValueError(f"ignite_torch: a tensor on {points.device}, the simulation runs on {self.torch_device}")
+        if points.shape[0]:
+            self._chk(self._L.sf_ignite_device(self._h, C.c_void_p(points.data_ptr()), int(points.shape[0])))
+            self._keep_alive_ignite = points      # one slot, as apply_mitigation_torch keeps its own: the launch may still be queued (async mode)
+
+    def time_ignites(self, on=True):
+        """Measurement only: record HIP events around the scatter launch of every ``ignite`` / ``ignite_torch`` (``sf_time_ignites``)."""
+        self._switch(self._L.sf_time_ignites, on)
+
+    def ignite_ms(self):
+        """GPU milliseconds of the last timed ignition's scatter launch (``sf_get_ignite_ms``; waits for it)."""
+        return self._get(self._L.sf_get_ignite_ms, C.c_float)
+
     def load_fire_map(self, env, fire_map):
         m = np.asarray(fire_map)
         if m.shape != (self.H, self.W):

@@ -566,6 +566,20 @@ class FireSimulation:
                     if t == kind:
                         plain[y, x] = int(kind)
 
+    def ignite(self, points: Iterable[Tuple[int, int]]) -> None:
+        """New fire between two ``run`` calls (``FireEngine.ignite``): ``(column, row)`` pairs, the order of
+        ``update_mitigation``.  Every listed cell that is UNBURNED becomes BURNING with a sprite of age 0, as if the last update
+        had ignited it; other cells are skipped, and so is everything once the fire has QUIT.  ``fire_map`` - the one array - shows
+        the new cells when the call returns; an edit the caller made before it is taken over first."""
+        q = np.asarray(list(points) if not isinstance(points, np.ndarray) else points)
+        if q.size == 0:
+            return
+        if q.ndim != 2 or q.shape[1] != 2:
+            raise ValueError(f"ignite: points must have shape (n, 2) = (column, row), got {q.shape}")
+        self._sync_to_device()
+        self._engine.ignite(np.concatenate([np.zeros((len(q), 1), dtype=q.dtype), q], axis=1))
+        self._refresh_map()                       # (the device has these writes: the cells that changed, not a caller's edit)
+
     def load_mitigation(self, mitigation_map: np.ndarray) -> None:
         """simulation.py:425-447: the map replaces ``fire_map`` if all values are BurnStatus values."""
         category_values = [status.value for status in BurnStatus]
@@ -1383,6 +1397,29 @@ class BatchedFireSimulation:
             q[:, 1] %= W
             q[:, 2] %= H
             self._engine.apply_mitigation(q)
+
+    def ignite(self, points) -> None:
+        """New fire between two stepping calls: rows ``(env, column, row)`` - a host array, checked like
+        ``reset``'s ignitions (``IndexError`` / ``ValueError``), or an int32 CUDA tensor ``[n, 3]`` / ``[n, 4]`` (a reserved 0
+        behind), which is not read on the host: its rows with a field out of range are dropped by the kernel.  A tensor needs no
+        ordering by the caller: it is made contiguous and four wide on torch's current stream, and that stream is waited for
+        before the handle's own stream reads it (work queued on OTHER torch streams is the caller's to order).  Every listed cell
+        that is UNBURNED becomes BURNING with a sprite of age 0, as if the last update had ignited it - burn-out and backfire
+        operations, spot fires, a fork (``clone_envs``) that also starts there; rows on other cells or in environments that are not
+        running are skipped."""
+        if hasattr(points, "data_ptr"):
+            import torch
+            from . import _args
+            points = _args.cuda_tensor(points, "ignite: a device points", ("int32",), [(None, 3), (None, 4)])
+            if points.shape[1] == 3:
+                points = torch.nn.functional.pad(points, (0, 1))
+            points = points.contiguous()
+            # the pad, the copy and whatever the caller's current stream still writes into the tensor: through before the handle's
+            # stream, which torch does not know, reads the rows
+            torch.cuda.current_stream(points.device).synchronize()
+            self._engine.ignite_torch(points)
+        else:
+            self._engine.ignite(points)
 
     def rollout(self, points, return_maps: bool = False):
         """``for s in range(n): update_mitigation(points[s]); run(1)`` for every environment as one device call

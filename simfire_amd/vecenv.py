@@ -247,6 +247,13 @@ class BatchedFireEnv:
         episode restarted inside ``step`` is under its schedule's first row from the next ``step`` on."""
         self.sim.set_wind_schedule(envs, segments)
 
+    def ignite(self, points):
+        """``BatchedFireSimulation.ignite``: rows ``(env, column, row)``, NumPy or a CUDA tensor - new fire from the next tick on.
+        A CUDA tensor written on torch's current stream (a policy's output) needs no ordering by the caller: that stream is waited
+        for before the rows are read; other torch streams are the caller's to order.  Not an agent action: the action words stay
+        what they are."""
+        self.sim.ignite(points)
+
     def positions(self):
         """torch int32 [n_envs, n_agents, 3] = (column, row, id): a view of the device positions (current after ``reset`` / ``step``,
         which wait for the handle's stream)."""
