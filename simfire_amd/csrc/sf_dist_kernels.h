@@ -234,8 +234,7 @@ __global__ __launch_bounds__(kDistRowsThreads) void k_dist_points(DistArgs a)
             const int gv = row[c];
             if (gv != kDistNone) best = min(best, (c - x) * (c - x) + gv * gv);
         }
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) best = min(best, __shfl_xor(best, m));
+        best = wave_min(best);
         val = dist_value(a, best);
     }
     if (lane == 0) static_cast<int32_t *>(a.out)[(long long)i * a.k + j] = val;

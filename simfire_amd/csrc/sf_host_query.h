@@ -118,9 +118,9 @@ extern "C" int sf_distance(sf_sim *s, const sf_dist_params *p, int32_t n, const 
 }
 
 // ----------------------------------------------------------------------------- band searches: sf_reach and sf_walk (DESIGN.md sections 23, 24)
-// What k_reach and k_walk read alike (WalkArgs begins with a ReachArgs): the state, the passable plane, the two masks (`seeds`: where
-// the search starts - sources, targets), the points' count and the band geometry.
-static void band_args(const sf_sim *s, ReachArgs &r, const uint8_t *passable, int per_env, int k, int seed_mask, int through_mask)
+// What k_reach and k_walk read alike (both Args begin with a BandArgs, `band`): the state, the passable plane, the two masks
+// (`seed_mask`: where the search starts - sources, targets), the points' count, the connectivity and the band geometry.
+static void band_args(const sf_sim *s, BandArgs &r, const uint8_t *passable, int per_env, int k, int seed_mask, int through_mask, int conn8)
 {
     const Geo &g = s->g;
     r.g = g;
@@ -131,22 +131,23 @@ static void band_args(const sf_sim *s, ReachArgs &r, const uint8_t *passable, in
     r.k = k;
     mask_tables(seed_mask, r.slo, r.shi);
     mask_tables(through_mask, r.tlo, r.thi);
-    r.WORDS = reach_words(g); r.BR = reach_band_rows(g); r.nb = r.BR * r.WORDS;
+    r.conn8 = conn8;
+    r.WORDS = band_words(g.P); r.BR = band_rows(g.H); r.nb = r.BR * r.WORDS;
 }
 
 // The launches of a band search and the end of its call: one launch per chunk of as many environments as the budget holds (`need`
 // bytes of scratch each), one workgroup per listed environment.  The call block is the environment list | one Args per chunk (the
-// kernel takes its arguments from there): `a` with r - `a` itself or its first member - pointed at the chunk's environments and
-// points, and at(c0) having pointed the outputs at the part of the chunk that begins with list entry c0.
+// kernel takes its arguments from there): `a` with a.band pointed at the chunk's environments and points, and at(c0) having pointed
+// the outputs at the part of the chunk that begins with list entry c0.
 // One band per thread where the grid allows it: the search's own planes stay in registers and LDS for all of it (k_resident, with
-// `lanes` threads rounded up to whole waves); else passes of kReachThreads bands over the scratch planes (k_passes).  Up to 156 KiB
+// `lanes` threads rounded up to whole waves); else passes of kBandThreads bands over the scratch planes (k_passes).  Up to 156 KiB
 // of LDS at 1024 threads, one workgroup per CU (which 1024 threads are anyway).
-static_assert(kWalkThreads == kReachThreads, "band_search: one workgroup size for both searches");
 template <typename Args, typename At>
 static int band_search(sf_sim *s, const char *who, QueryState &q, int32_t n, const int32_t *envs, const int32_t *points, int64_t scratch_bytes,
-                       long long budget_default, size_t need, Args &a, ReachArgs &r, At at, void (*k_resident)(const Args *),
+                       long long budget_default, size_t need, Args &a, At at, void (*k_resident)(const Args *),
                        void (*k_passes)(const Args *), int lanes, size_t (*lds_bytes)(int, bool))
 {
+    BandArgs &r = a.band;
     const int chunk = query_chunk(n, scratch_bytes, budget_default, need, 65535), chunks = (n + chunk - 1) / chunk;
     SF_TRY(scratch_reserve(s, q, (size_t)chunk * need));
     r.scratch = q.mem;
@@ -163,8 +164,8 @@ static int band_search(sf_sim *s, const char *who, QueryState &q, int32_t n, con
     }
     SF_TRY(block_send(s, q.blk, bytes));
 
-    const bool resident = r.nb <= kReachThreads;
-    const unsigned threads = resident ? (unsigned)((lanes + 63) / 64 * 64) : (unsigned)kReachThreads;
+    const bool resident = r.nb <= kBandThreads;
+    const unsigned threads = resident ? (unsigned)((lanes + 63) / 64 * 64) : (unsigned)kBandThreads;
     const size_t lds = lds_bytes((int)threads, resident);
     const auto kernel = resident ? k_resident : k_passes;
     HIPCHK(allow_lds(s, reinterpret_cast<const void *>(kernel), lds));
@@ -204,10 +205,9 @@ extern "C" int sf_reach(sf_sim *s, const sf_reach_params *p, int32_t n, const in
 
     ReachArgs a;
     memset(&a, 0, sizeof a);
-    band_args(s, a, p->passable, p->passable_per_env, p->k, p->source_mask, p->through_mask);
+    band_args(s, a.band, p->passable, p->passable_per_env, p->k, p->source_mask, p->through_mask, p->connectivity == 0 ? g.diag : (p->connectivity == 8));
     a.vals = out->value ? s->values.plane : nullptr;
     a.val_env = s->values.per_env ? g.plane_env : 0;
-    a.conn8 = p->connectivity == 0 ? g.diag : (p->connectivity == 8);
     a.max_rounds = p->max_rounds;
     a.mask_vec = out->mask && g.W % 16 == 0 && !((uintptr_t)out->mask & 15);
     const auto at = [&](int c0) {
@@ -218,8 +218,8 @@ extern "C" int sf_reach(sf_sim *s, const sf_reach_params *p, int32_t n, const in
         a.point_in = out->point_in ? out->point_in + (size_t)c0 * p->k : nullptr;
         a.rounds = out->rounds ? out->rounds + c0 : nullptr;
     };
-    return band_search(s, who, s->reach, n, envs, p->points, p->scratch_bytes, kReachScratchDefault, need, a, a, at, k_reach<true>, k_reach<false>,
-                       a.nb, reach_lds_bytes);
+    return band_search(s, who, s->reach, n, envs, p->points, p->scratch_bytes, kReachScratchDefault, need, a, at, k_reach<true>, k_reach<false>,
+                       a.band.nb, reach_lds_bytes);
 }
 
 extern "C" int sf_walk(sf_sim *s, const sf_walk_params *p, int32_t n, const int32_t *envs, const sf_walk_out *out)
@@ -250,8 +250,7 @@ extern "C" int sf_walk(sf_sim *s, const sf_walk_params *p, int32_t n, const int3
 
     WalkArgs a;
     memset(&a, 0, sizeof a);
-    band_args(s, a.r, p->passable, p->passable_per_env, p->k, p->target_mask, p->through_mask);
-    a.r.conn8 = p->connectivity == 8;
+    band_args(s, a.band, p->passable, p->passable_per_env, p->k, p->target_mask, p->through_mask, p->connectivity == 8);
     a.targets = p->targets;
     a.tgt_env = p->targets_per_env ? (long long)g.H * g.W : 0;
     a.tgt_vec = p->targets && g.W % 16 == 0 && !((uintptr_t)p->targets & 15);
@@ -265,8 +264,8 @@ extern "C" int sf_walk(sf_sim *s, const sf_walk_params *p, int32_t n, const int3
         a.levels = out->levels ? out->levels + c0 : nullptr;
     };
     // (every point has a lane of its own, so a small grid still gets k threads)
-    return band_search(s, who, s->walk, n, envs, p->points, p->scratch_bytes, kWalkScratchDefault, need, a, a.r, at, k_walk<true>, k_walk<false>,
-                       std::max(a.r.nb, p->k), walk_lds_bytes);
+    return band_search(s, who, s->walk, n, envs, p->points, p->scratch_bytes, kWalkScratchDefault, need, a, at, k_walk<true>, k_walk<false>,
+                       std::max(a.band.nb, p->k), walk_lds_bytes);
 }
 
 // ----------------------------------------------------------------------------- fire travel time

@@ -12,6 +12,7 @@
 //   d = 0: SE & ~NE, 1: SW & ~SE, 2: NW & ~SW, 3: NE & ~NW.  Its id is (vy * (W + 1) + vx) * 4 + d; the kernel orders by
 //   (vy * VP + vx) * 4 + d with VP = 16 * ceil((W + 1) / 16), which is the same order: 16 vertices x 4 directions fill a 64-bit word.
 #pragma once
+#include "sf_bands.h"
 #include "sf_query_dev.h"
 
 namespace {
@@ -31,7 +32,7 @@ struct PerimArgs {
     const uint32_t *arrival;   // source 2: the raw arrival plane [E][H][P], update + 1, 0 = never
     uint32_t at;               // source 2: the horizon (an update)
     int source;                // 0: status mask, 1: member, 2: arrival
-    uint32_t tlo, thi;         // source 0: the mask as the table of one byte permute (mask_sel16)
+    uint32_t tlo, thi;         // source 0: the mask as the table of one byte permute (mask_sel01)
     const int32_t *envs;       // the listed environments of this launch [n]
     int n;
     int conn8, simplify;
@@ -65,8 +66,8 @@ __device__ __forceinline__ uint32_t perim_vec16(const PerimArgs &a, int e, int y
     const int in = g.W - v * 16;                 // cells of the vector on the grid (the rest is pitch padding: never in S)
     if (in <= 0) return 0u;
     uint32_t m = 0u;
-    if (a.source == 0) {
-        m = mask_sel16(a.tlo, a.thi, and4(*reinterpret_cast<const uint4 *>(cell_status_vec(a.pl, g, e, y, v)), 0x07070707u));
+    if (a.source == 0) {             // (not mask_bits16: the last line is the grid mask of all three sources, and with both the kernels need more registers)
+        m = pack16(mask_sel01(a.tlo, a.thi, status_vec7(a.pl, g, e, y, v)));
     } else if (a.source == 1) {      // (decided by the address, vector by vector - not dense_vec16, whose flag holds for a whole plane)
         const uint8_t *p = a.member + (long long)e * a.mem_env + (long long)y * g.W + v * 16;
         if (in >= 16 && !((uintptr_t)p & 15)) {
@@ -93,9 +94,6 @@ __device__ __forceinline__ unsigned long long perim_word(const PerimArgs &a, int
     return (unsigned long long)perim_vec16(a, e, y, 4 * w) | ((unsigned long long)perim_vec16(a, e, y, 4 * w + 1) << 16) |
            ((unsigned long long)perim_vec16(a, e, y, 4 * w + 2) << 32) | ((unsigned long long)perim_vec16(a, e, y, 4 * w + 3) << 48);
 }
-
-// 4 bits -> 4 bytes of 0 / 1
-__device__ __forceinline__ uint32_t perim_bytes4(uint32_t n) { return ((n & 0xFu) * 0x00204081u) & 0x01010101u; }
 
 // The summary form.  A grid-stride loop over (listed environment, block of kPerimThreads items); an item is (strip of kPerimStrip
 // rows, 64-cell word).  Per row: cells = popc(w); the cracks above the row = popc(w ^ row above) - row -1 is empty, and the last row
@@ -135,8 +133,9 @@ __global__ __launch_bounds__(kPerimThreads) void k_perim_summary(PerimArgs a)
 #pragma unroll
                         for (int v = 0; v < 4; ++v) {
                             if (64 * w + 16 * v >= g.W) break;
-                            const uint32_t b = (uint32_t)(f >> (16 * v)) & 0xFFFFu;
-                            *reinterpret_cast<uint4 *>(o + 16 * v) = make_uint4(perim_bytes4(b), perim_bytes4(b >> 4), perim_bytes4(b >> 8), perim_bytes4(b >> 12));
+                            uint32_t d[4];
+                            bits_bytes16((uint32_t)(f >> (16 * v)) & 0xFFFFu, d);
+                            *reinterpret_cast<uint4 *>(o + 16 * v) = make_uint4(d[0], d[1], d[2], d[3]);
                         }
                     } else {
                         const int k = min(64, g.W - 64 * w);

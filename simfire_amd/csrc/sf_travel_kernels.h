@@ -276,11 +276,7 @@ __global__ __launch_bounds__(kTravelThreads) void k_travel(TravelArgs a)
                 }
             }
         }
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) {
-            cnt += (uint32_t)__shfl_xor((int)cnt, m);
-            mx = max(mx, (uint32_t)__shfl_xor((int)mx, m));
-        }
+        cnt = wave_sum(cnt); mx = wave_max(mx);
         if ((t & 63) == 0 && cnt) { atomicAdd(&s_sum[0], cnt); atomicMax(&s_sum[1], mx); }      // (the values are >= 0: their bits order as they do)
     }
 
