@@ -667,6 +667,84 @@ typedef struct sf_travel_out {           /* device pointers, any may be NULL, at
  * work on passable, sources, points and the outputs before the call. */
 int sf_travel(sf_sim *sim, const sf_travel_params *params, int32_t n, const int32_t *envs /* [n] host */, const sf_travel_out *out);
 
+/* Escape routes: how many more moves a walker may wait where it stands and still reach a target cell without
+ * ever standing on a cell at or after the moment the fire closes it - the ESCAPE SLACK.  It joins sf_travel (when a cell closes) and
+ * sf_walk (one cell per move).  The reference has no counterpart; the semantics are this library's own.
+ * For a listed environment, s(c) is the status byte & 7 of cell c, read from whichever cell plane is current.
+ *   target(c) and walk(c): as sf_walk's (target_mask or a targets plane; through_mask and a passable plane; a cell that is both is a
+ *   target; the pitch padding is neither).  The neighbourhood is the 4-neighbourhood (connectivity 4, and 0) or the 8-neighbourhood.
+ *   minutes float32 [n][height][width], row i for envs[i]: the time in minutes from now at which the fire closes a cell - the layout
+ *   and conventions of sf_travel's minutes output, which can be handed over as it is; any plane of closing times will do.
+ *   Deadline D(c), with T = minutes[c]: NEVER if T < 0 or not T < horizon_minutes (+inf, NaN, sf_travel's cap and SF_TRAVEL_BLOCKED);
+ *   else q = ((double)T - margin_minutes) / minutes_per_move in float64 and D(c) = q > 0 ? (int)ceil(q) : 0.  A walker may stand on c
+ *   at move index m (now is m = 0) exactly when m < D(c).  ceil((horizon_minutes - margin_minutes) / minutes_per_move) must not exceed
+ *   SF_ESCAPE_MAX_MOVES, so every finite D is at most that.
+ *   SF_ESCAPE_UNREACHED_SAFE in flags makes every walkable cell with D = NEVER a target too.
+ *   A route from c is p_0 = c, p_1 ... p_L, L >= 0, consecutive cells neighbours, p_L a target, p_0 .. p_(L-1) walkable non-targets;
+ *   targets are safe and have no deadline.  Started after waiting w >= 0 moves it is feasible when w + j < D(p_j) for every j < L.
+ *   slack(c) = SF_ESCAPE_SAFE on targets and where w is unbounded (a route over NEVER cells only); SF_ESCAPE_LOST on a walkable cell
+ *   with no feasible route even for w = 0; SF_ESCAPE_BLOCKED on cells that are neither target nor walkable; else the largest feasible
+ *   w.  Equivalently the unique solution of S(c) = min(D(c) - 1, max over the target-or-walkable neighbours n of S(n) - 1), with
+ *   SAFE - 1 = SAFE, NEVER - 1 = SAFE and the maximum over nothing LOST: a bottleneck shortest path, not a level count.
+ * slack int32 [n][height][width]: that plane.
+ * Point form, points device int32 [n][k][3] = (column, row, id), sf_agents_device's layout.  point_slack [n][k]: SAFE on a target,
+ * S(c) on a walkable cell; on a blocked cell (an agent on the line it has just drawn) min(D(c) - 1, max_n S(n) - 1) with its own D(c)
+ * formed from minutes[c]; -2 for id <= 0 or a cell off the grid.  point_step [n][k]: where 0 <= point_slack < SAFE and the
+ * connectivity is 4, the sf_walk move code (1: row - 1, 2: row + 1, 3: column - 1, 4: column + 1) of the LOWEST-numbered neighbour
+ * that attains max_n S(n); 0 on a target, when lost, when the slack is SAFE (no hurry: sf_walk routes) and with connectivity 8; -1
+ * where point_slack is -2.  Following it raises S by at least 1 per move, so it never cycles.
+ * Summaries int32 [n]: safe - walkable non-target cells with SAFE; escapable - with 0 <= S < SAFE; lost - with S = -1; top - the
+ * largest finite D among walkable non-target cells, 0 if none. */
+#define SF_ESCAPE_SAFE 2147483647
+#define SF_ESCAPE_LOST (-1)
+#define SF_ESCAPE_BLOCKED (-2)
+#define SF_ESCAPE_MAX_MOVES 32768
+#define SF_ESCAPE_UNREACHED_SAFE 1
+typedef struct sf_escape_params {
+    int32_t target_mask, through_mask;   /* 0..63 (0 only with targets) / 1..63 */
+    int32_t connectivity;                /* 0 or 4 (the agents' moves), 8 */
+    int32_t k;                           /* 0, or 1..SF_DIST_MAX_POINTS points per listed environment */
+    int32_t flags;                       /* 0 or SF_ESCAPE_UNREACHED_SAFE */
+    int32_t passable_per_env;            /* passable is [n_envs][H*W] (indexed by environment number), else [H*W] */
+    int32_t targets_per_env;             /* the same for targets */
+    const uint8_t *passable;             /* device, or NULL */
+    const uint8_t *targets;              /* device, or NULL */
+    const int32_t *points;               /* device int32 [n][k][3] = (column, row, id); NULL with k == 0 */
+    const float *minutes;                /* device float32 [n][H][W] dense, row i for envs[i] */
+    double minutes_per_move;             /* finite, > 0 */
+    double margin_minutes;               /* finite, >= 0 */
+    double horizon_minutes;              /* finite, > 0 */
+    int64_t scratch_bytes;               /* 0: the default budget */
+    int32_t reserved[2];                 /* 0 */
+} sf_escape_params;
+typedef struct sf_escape_out {           /* device pointers, any may be NULL, at least one not */
+    int32_t *slack;        /* [n][H][W]  dense */
+    int32_t *point_slack;  /* [n][k] */
+    int32_t *point_step;   /* [n][k] */
+    int32_t *safe;         /* [n] */
+    int32_t *escapable;    /* [n] */
+    int32_t *lost;         /* [n] */
+    int32_t *top;          /* [n] */
+} sf_escape_out;
+/* Environment envs[i] (a host array; any order, repeats allowed) lands in row i of every output.  Anything invalid is SF_EINVAL before
+ * anything is enqueued, in this order: target_mask outside 0..63 or through_mask outside 1..63, target_mask 0 without a targets plane,
+ * an unknown connectivity or flag, k outside 0..256, k > 0 without points or points with k == 0, point_slack or point_step without k;
+ * every output null; an output, points or minutes not aligned to 4 bytes; a time parameter that is not finite, minutes_per_move or
+ * horizon_minutes not > 0, margin_minutes < 0; a move bound above SF_ESCAPE_MAX_MOVES; minutes null; reserved != 0; a positive
+ * scratch_bytes below one environment's need; an environment out of range.  A grid wider than 8192 cells or of 2^31 cells or more is
+ * SF_ENOTSUP; a handle without layers or reset is SF_ESTATE.
+ * One workgroup searches one environment: the cells with a finite deadline are sorted by it, the safe set is flooded from the targets
+ * over the NEVER cells, then the move indices run from the largest deadline down to 0 - a level opens the cells of its deadline and
+ * grows the set by one ring.
+ * The call reads the state and writes nothing but its outputs and its own scratch.  The scratch belongs to the handle: per listed
+ * environment of a chunk three bit planes and two halos (as sf_walk), 4 * height * width bytes for the sorted cells and 262400 bytes
+ * for the bounds of the deadlines' buckets, each rounded up to 256; allocated at the first call, grown (never shrunk) when a later
+ * call needs more, freed by sf_destroy, counted by sf_memory_bytes.  The default budget is 1280 MiB (256 environments of 1024 x 1024
+ * are one chunk); the list is worked through in chunks so that scratch never exceeds the budget, which changes no bit of the result.
+ * In async mode the call only enqueues; the caller orders its own work on minutes, passable, targets, points and the outputs before
+ * the call. */
+int sf_escape(sf_sim *sim, const sf_escape_params *params, int32_t n, const int32_t *envs /* [n] host */, const sf_escape_out *out);
+
 /* Fire behaviour per cell: heat per unit area, head rate of spread, Byram's fireline intensity and flame
  * length - the quantities of the fire characteristics chart - from the R table the handle holds NOW (it follows sf_set_wind, and a
  * schedule segment once a stepping call has applied it).  The reference computes I_R on its way to R (rothermel.py:74-92) and keeps

@@ -146,6 +146,24 @@ class SfWalkOut(C.Structure):
                 ("levels", C.c_void_p)]
 
 
+SF_ESCAPE_SAFE, SF_ESCAPE_LOST, SF_ESCAPE_BLOCKED, SF_ESCAPE_MAX_MOVES, SF_ESCAPE_UNREACHED_SAFE = 2 ** 31 - 1, -1, -2, 32768, 1
+
+
+class SfEscapeParams(C.Structure):
+    """``sf_escape_params`` (include/simfire_hip.h)."""
+    _fields_ = [("target_mask", C.c_int32), ("through_mask", C.c_int32), ("connectivity", C.c_int32), ("k", C.c_int32),
+                ("flags", C.c_int32), ("passable_per_env", C.c_int32), ("targets_per_env", C.c_int32), ("passable", C.c_void_p),
+                ("targets", C.c_void_p), ("points", C.c_void_p), ("minutes", C.c_void_p), ("minutes_per_move", C.c_double),
+                ("margin_minutes", C.c_double), ("horizon_minutes", C.c_double), ("scratch_bytes", C.c_int64),
+                ("reserved", C.c_int32 * 2)]
+
+
+class SfEscapeOut(C.Structure):
+    """``sf_escape_out`` (include/simfire_hip.h): device pointers, any may be null, not all."""
+    _fields_ = [("slack", C.c_void_p), ("point_slack", C.c_void_p), ("point_step", C.c_void_p), ("safe", C.c_void_p),
+                ("escapable", C.c_void_p), ("lost", C.c_void_p), ("top", C.c_void_p)]
+
+
 SF_TRAVEL_BLOCKED = -1.0
 
 
@@ -283,6 +301,7 @@ SIGNATURES = {
     "sf_distance": [_VP, C.POINTER(SfDistParams), _I32, _VP, _VP],
     "sf_reach": [_VP, C.POINTER(SfReachParams), _I32, _VP, C.POINTER(SfReachOut)],
     "sf_walk": [_VP, C.POINTER(SfWalkParams), _I32, _VP, C.POINTER(SfWalkOut)],
+    "sf_escape": [_VP, C.POINTER(SfEscapeParams), _I32, _VP, C.POINTER(SfEscapeOut)],
     "sf_travel": [_VP, C.POINTER(SfTravelParams), _I32, _VP, C.POINTER(SfTravelOut)],
     "sf_behavior": [_VP, C.POINTER(SfBehaviorParams), C.POINTER(SfBehaviorOut), _VP, _I32],
     "sf_get_behavior_builds": [_VP, C.POINTER(_I64)],

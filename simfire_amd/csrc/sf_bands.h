@@ -167,4 +167,30 @@ SF_HD bool band_level(band_word (&f)[kBandRows], band_word *ub, const BandHalo &
     return any != 0;
 }
 
+// ---- the growing set (the escape search of DESIGN.md section 30).  One level of a band: the WHOLE set a, not a front, is dilated -
+// n = dilate(a) & U row by row, those cells join a and leave U (ub: the band's 16 words of U, LDS or the scratch plane; a and U are
+// disjoint).  Jacobi as band_level: every row is dilated from the OLD rows.  added(j, n) is called for every row j that gained the
+// cells n (the caller numbers them: no second array of rows is kept); returns whether a cell was added.
+template <class Added>
+SF_HD bool band_grow(band_word (&a)[kBandRows], band_word *ub, const BandHalo &h, int conn8, Added &&added)
+{
+    band_word any = 0, prev = h.top;
+    SF_BAND_UNROLL
+    for (int j = 0; j < kBandRows; ++j) {
+        const band_word cur = a[j], next = j == kBandRows - 1 ? h.bot : a[j + 1];
+        band_word w = (cur << 1) | (cur >> 1) | (band_word)((h.el >> (j + 1)) & 1u) | (band_word)((h.er >> (j + 1)) & 1u) << 63;
+        w |= band_spread(prev, (h.el >> j) & 1u, (h.er >> j) & 1u, conn8) | band_spread(next, (h.el >> (j + 2)) & 1u, (h.er >> (j + 2)) & 1u, conn8);
+        const band_word u = ub[j], n = w & u;
+        if (n) {
+            ub[j] = u & ~n;
+            a[j] = cur | n;
+            added(j, n);
+        }
+        prev = cur;
+        any |= n;
+        if ((j & 3) == 3) SF_BAND_SCHED_BARRIER();
+    }
+    return any != 0;
+}
+
 }  // namespace

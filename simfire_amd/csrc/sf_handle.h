@@ -249,7 +249,7 @@ struct EpisodeState {
 // working on - allocated at the first call, grown but never shrunk when a call's chunk needs more (scratch_reserve), freed with the
 // handle -, its size in bytes, and the call block (the environment list of a call).  What lies in it, per listed environment of a
 // chunk: sf_distance the plane g, u16 [H][P]; sf_reach two bit planes and the halo (reach_env_bytes); sf_walk three bit planes and
-// two halos (walk_env_bytes); sf_travel the working array, float32 [H][W] dense (travel_env_bytes) - only when the call asks for no
+// two halos (walk_env_bytes); sf_escape those, the sorted cells and the buckets (escape_env_bytes); sf_travel the working array, float32 [H][W] dense (travel_env_bytes) - only when the call asks for no
 // minutes plane, which is the working array otherwise; sf_perimeter the bit plane, the edge words and eight arrays of max_edges
 // (perim_env_bytes) - only when the call asks for a traced output; sf_influence the parent codes, the child counters and the
 // accumulators that are no output of the call (infl_env_bytes).
@@ -359,7 +359,7 @@ struct sf_sim {
     WindState wind;
     AgentState agents;
     EpisodeState episodes;
-    QueryState dist, reach, walk, travel, perimeter, influence;      // one block and one scratch per feature (as for CallBlock: calls of different features do not wait for each other)
+    QueryState dist, reach, walk, escape, travel, perimeter, influence;      // one block and one scratch per feature (as for CallBlock: calls of different features do not wait for each other)
     BehaviorState behavior;
     CallBlock obs_blk;                 // sf_observe: ObsHead, environment list, host centers / agents
     CallBlock rs_blk;                  // sf_reset_envs / sf_reset_where: the environment list and host ignitions of a call

@@ -1,4 +1,4 @@
-// Host code of the queries: sf_distance, sf_reach (23), sf_walk (24), sf_behavior (25), sf_travel (26), sf_perimeter (27) and sf_influence (28).  Each takes a list
+// Host code of the queries: sf_distance, sf_reach (23), sf_walk (24), sf_behavior (25), sf_travel (26), sf_perimeter (27), sf_influence (28) and sf_escape (30).  Each takes a list
 // of environments, optional points and caller-owned device outputs, reads the state and changes none of it.  Included once from
 // simfire_hip.hip, behind sf_host_views.h.
 //
@@ -266,6 +266,69 @@ extern "C" int sf_walk(sf_sim *s, const sf_walk_params *p, int32_t n, const int3
     // (every point has a lane of its own, so a small grid still gets k threads)
     return band_search(s, who, s->walk, n, envs, p->points, p->scratch_bytes, kWalkScratchDefault, need, a, at, k_walk<true>, k_walk<false>,
                        std::max(a.band.nb, p->k), walk_lds_bytes);
+}
+
+// ----------------------------------------------------------------------------- escape routes
+// A band search like sf_walk: one launch of k_escape per chunk, one workgroup per listed environment; the scratch of an environment
+// holds the bit planes and halos, the cells sorted by deadline and the bounds of the buckets (escape_env_bytes).
+extern "C" int sf_escape(sf_sim *s, const sf_escape_params *p, int32_t n, const int32_t *envs, const sf_escape_out *out)
+{
+    const char *who = "sf_escape";
+    if (!s || !p || !out) return fail(SF_EINVAL, "sf_escape: null argument");
+    const Geo &g = s->g;
+    if (n < 0 || (n > 0 && !envs)) return fail(SF_EINVAL, "sf_escape: bad environment list");
+    if (p->target_mask < 0 || p->target_mask > 63) return fail(SF_EINVAL, "sf_escape: target_mask %d (bit s selects BurnStatus s: 0..63)", p->target_mask);
+    if (p->through_mask < 1 || p->through_mask > 63) return fail(SF_EINVAL, "sf_escape: through_mask %d (bit s selects BurnStatus s: 1..63)", p->through_mask);
+    if (p->target_mask == 0 && !p->targets) return fail(SF_EINVAL, "sf_escape: target_mask 0 needs a targets plane");
+    if (p->connectivity != 0 && p->connectivity != 4 && p->connectivity != 8)
+        return fail(SF_EINVAL, "sf_escape: connectivity %d (0 or 4: the agents' moves, 8)", p->connectivity);
+    if (p->flags & ~SF_ESCAPE_UNREACHED_SAFE) return fail(SF_EINVAL, "sf_escape: flags %d (0 or SF_ESCAPE_UNREACHED_SAFE)", p->flags);
+    SF_TRY(check_points(who, p->k, p->points, true));
+    if ((out->point_slack || out->point_step) && p->k == 0) return fail(SF_EINVAL, "sf_escape: point_slack and point_step need k > 0");
+    if (!out->slack && !out->point_slack && !out->point_step && !out->safe && !out->escapable && !out->lost && !out->top)
+        return fail(SF_EINVAL, "sf_escape: every output is null");
+    SF_TRY(check_aligned(who, ((uintptr_t)out->slack | (uintptr_t)out->point_slack | (uintptr_t)out->point_step | (uintptr_t)out->safe | (uintptr_t)out->escapable |
+                               (uintptr_t)out->lost | (uintptr_t)out->top | (uintptr_t)p->points | (uintptr_t)p->minutes) & 3));
+    if (!std::isfinite(p->minutes_per_move) || !(p->minutes_per_move > 0.0)) return fail(SF_EINVAL, "sf_escape: minutes_per_move must be finite and > 0");
+    if (!std::isfinite(p->margin_minutes) || !(p->margin_minutes >= 0.0)) return fail(SF_EINVAL, "sf_escape: margin_minutes must be finite and >= 0");
+    if (!std::isfinite(p->horizon_minutes) || !(p->horizon_minutes > 0.0)) return fail(SF_EINVAL, "sf_escape: horizon_minutes must be finite and > 0");
+    const double bound = std::ceil((p->horizon_minutes - p->margin_minutes) / p->minutes_per_move);      // (the kernel divides the same way: no deadline exceeds it)
+    if (bound > (double)SF_ESCAPE_MAX_MOVES)
+        return fail(SF_EINVAL, "sf_escape: the horizon is %.0f moves away, more than SF_ESCAPE_MAX_MOVES (%d)", bound, SF_ESCAPE_MAX_MOVES);
+    if (!p->minutes) return fail(SF_EINVAL, "sf_escape: minutes is null");
+    SF_TRY(check_reserved(who, p->reserved[0] | p->reserved[1]));
+    const size_t need = (size_t)escape_env_bytes(g);
+    SF_TRY(check_scratch(who, p->scratch_bytes, need, "need"));
+    SF_TRY(check_envs(s, who, n, envs));
+    if (g.W > kEscapeMaxWidth) return fail(SF_ENOTSUP, "sf_escape: grids wider than %d cells are not supported (width %d)", kEscapeMaxWidth, g.W);
+    if ((long long)g.H * g.W >= (1ll << 31)) return fail(SF_ENOTSUP, "sf_escape: the cells of a %d x %d grid do not fit int32", g.H, g.W);
+    SF_TRY(begin_call(s, who, kNeedRt | kNeedReset | kNotVoid));
+    if (n == 0) return SF_OK;
+
+    EscapeArgs a;
+    memset(&a, 0, sizeof a);
+    band_args(s, a.band, p->passable, p->passable_per_env, p->k, p->target_mask, p->through_mask, p->connectivity == 8);
+    a.targets = p->targets;
+    a.tgt_env = p->targets_per_env ? (long long)g.H * g.W : 0;
+    a.tgt_vec = p->targets && g.W % 16 == 0 && !((uintptr_t)p->targets & 15);
+    a.per_move = p->minutes_per_move; a.margin = p->margin_minutes; a.horizon = p->horizon_minutes;
+    a.unreached_safe = (p->flags & SF_ESCAPE_UNREACHED_SAFE) != 0;
+    a.bins = bound > 0.0 ? (int)bound : 0;
+    a.slack_vec = out->slack && g.W % 4 == 0 && !((uintptr_t)out->slack & 15);
+    a.o_list = escape_list_offset(g);
+    a.o_buckets = (long long)need - kEscapeBoundsBytes;
+    const auto at = [&](int c0) {
+        a.minutes = p->minutes + (size_t)c0 * g.H * g.W;
+        a.slack = out->slack ? out->slack + (size_t)c0 * g.H * g.W : nullptr;
+        a.point_slack = out->point_slack ? out->point_slack + (size_t)c0 * p->k : nullptr;
+        a.point_step = out->point_step ? out->point_step + (size_t)c0 * p->k : nullptr;
+        a.safe = out->safe ? out->safe + c0 : nullptr;
+        a.escapable = out->escapable ? out->escapable + c0 : nullptr;
+        a.lost = out->lost ? out->lost + c0 : nullptr;
+        a.top = out->top ? out->top + c0 : nullptr;
+    };
+    return band_search(s, who, s->escape, n, envs, p->points, p->scratch_bytes, kEscapeScratchDefault, need, a, at, k_escape<true>, k_escape<false>,
+                       std::max(a.band.nb, p->k), escape_lds_bytes);
 }
 
 // ----------------------------------------------------------------------------- fire travel time

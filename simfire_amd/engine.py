@@ -4,7 +4,7 @@ This is the only module that touches the HIP library; the reference-shaped class
 ``fire.py`` / ``simulation.py`` are written on top of it.  Arrays cross the boundary as
 NumPy host arrays (copied during the call) or as torch CUDA tensors, read and written in place; torch is imported only by the
 methods that take or return one.  Layout (binding map): argument checks in ``_args.py``, one request class per feature
-(``observe.py``, ``render.py``, ``distance.py``, ``reach.py``, ``walk.py``, ``travel.py``, ``behavior.py``, ``perimeter.py``, ``influence.py``, ``ensemble.py``), and one frame, ``_device_call``, for every call
+(``observe.py``, ``render.py``, ``distance.py``, ``reach.py``, ``walk.py``, ``escape.py``, ``travel.py``, ``behavior.py``, ``perimeter.py``, ``influence.py``, ``ensemble.py``), and one frame, ``_device_call``, for every call
 that hands the library a tensor.
 """
 import ctypes as C
@@ -975,6 +975,49 @@ class FireEngine:
         if spec.n:
             p, o = spec.params(), spec.out(res)
             self._device_call(self._L.sf_walk, C.byref(p), spec.n, _ptr(spec.envs), C.byref(o), tensors=list(res.values()) + spec.device_tensors())
+        return res
+
+    # ---------------------------------------------------------------- escape routes
+    ESCAPE_SAFE, ESCAPE_LOST, ESCAPE_BLOCKED = _lib.SF_ESCAPE_SAFE, _lib.SF_ESCAPE_LOST, _lib.SF_ESCAPE_BLOCKED
+
+    def escape_scratch_bytes(self):
+        from . import escape
+        return escape.scratch_need(self.H, self.W)
+
+    def escape(self, minutes, target=(), targets=None, through=("UNBURNED",), passable=None, envs=None, connectivity=4,
+               minutes_per_move=None, margin_minutes=0.0, horizon_minutes=None, unreached_safe=False, points=None, plane=False,
+               step=False, summary=False, scratch_bytes=0):
+        """The escape slack of ``envs`` (default: all, in order; any order, repeats allowed): how many more moves a walker may wait
+        where it stands and still reach a target cell, one cell per move through walkable cells, never standing on a cell at or
+        after the moment the fire closes it (``sf_escape``).  ``minutes``: a float32 CUDA tensor [n, H, W],
+        row i for ``envs[i]``, the closing time of every cell in minutes from now - the ``minutes`` of ``travel`` as it is.  A cell
+        with T = ``minutes`` < 0 or not < ``horizon_minutes`` never closes; else its deadline is ``ceil((T - margin_minutes) /
+        minutes_per_move)`` moves (at least 0), and a walker may stand on it at move index m (now: 0) while m is below that.
+        ``minutes_per_move=None``: the simulation's ``update_rate`` - one move per tick of ``agents_step``.  Targets and walkable
+        cells: ``target`` / ``targets`` and ``through`` / ``passable`` as for ``walk`` (``target`` may be empty with a ``targets``
+        plane); targets are safe.  ``unreached_safe``: every walkable cell that never closes is a target too.  ``connectivity`` 4
+        (the agents' moves) or 8.  Read from whichever cell plane is current; no state of the handle changes.
+        Returns a dict of int32 torch tensors on this GPU, one per output asked for: with ``plane`` ``slack`` [n, H, W]
+        (``ESCAPE_SAFE`` on targets and where no deadline binds, ``ESCAPE_LOST`` = -1 on walkable cells without a feasible route,
+        ``ESCAPE_BLOCKED`` = -2 on cells that are neither); with ``points`` - int32 CUDA [n, k, 3] = (column, row, id), k <= 256,
+        e.g. ``agents_device()`` - ``point_slack`` [n, k] (the point need not be walkable; -2 for id <= 0 or off the grid) and with
+        ``step`` ``point_step`` [n, k]: where 0 <= slack < ``ESCAPE_SAFE``, the move code 1..4 of the lowest-numbered neighbour
+        with the largest slack - following it raises the slack by at least 1 per move; 0 on a target, when lost, when the slack is
+        ``ESCAPE_SAFE`` (no hurry: ``walk`` routes) and with connectivity 8; with ``summary`` ``safe``, ``escapable``, ``lost``
+        (walkable non-target cells by slack) and ``top`` (the largest finite deadline) [n].  The horizon may be at most 32768 moves
+        away.  ``scratch_bytes``: the most scratch the call may use (0: 1280 MiB); less than ``escape_scratch_bytes()`` is a
+        ``ValueError``.  Torch's queued work is waited for first; in async mode the call only enqueues: the tensors are complete
+        after ``sync()`` and kept alive until then."""
+        from .escape import EscapeSpec
+        spec = EscapeSpec(self.n_envs, self.H, self.W, minutes, target=target, targets=targets, through=through, passable=passable,
+                          envs=envs, connectivity=connectivity,
+                          minutes_per_move=float(self.params.update_rate) if minutes_per_move is None else minutes_per_move,
+                          margin_minutes=margin_minutes, horizon_minutes=horizon_minutes, unreached_safe=unreached_safe, points=points,
+                          plane=plane, step=step, summary=summary, scratch_bytes=scratch_bytes)
+        res = self._outputs("escape", spec)
+        if spec.n:
+            p, o = spec.params(), spec.out(res)
+            self._device_call(self._L.sf_escape, C.byref(p), spec.n, _ptr(spec.envs), C.byref(o), tensors=list(res.values()) + spec.device_tensors())
         return res
 
     # ---------------------------------------------------------------- fire travel time (DESIGN.md section 26)

@@ -41,6 +41,25 @@ def _perimeter_unit(unit, pixel_scale):
     return 1.0 if unit == "cells" else float(pixel_scale)
 
 
+def _escape_routes(engine, envs, minutes, kwargs):
+    """``engine.escape`` with the closing times of ``time_to_fire`` up to the horizon when the caller gives none: the request is
+    checked first, the travel times stay on the device.  The cap handed to ``travel`` is the least float32 >= the horizon, so a
+    capped cell never looks as if the fire closed it within the horizon."""
+    import torch
+    from . import escape
+    mpm = float(engine.params.update_rate) if kwargs.get("minutes_per_move") is None else kwargs["minutes_per_move"]
+    escape.request(kwargs["target"], kwargs["through"], kwargs["connectivity"], mpm, kwargs["margin_minutes"], kwargs["horizon_minutes"],
+                   kwargs["unreached_safe"], kwargs.get("scratch_bytes", 0), targets=kwargs["targets"] is not None)
+    if minutes is None:
+        cap = np.float32(kwargs["horizon_minutes"])
+        if float(cap) < float(kwargs["horizon_minutes"]):
+            cap = np.nextafter(cap, np.float32(np.inf))
+        minutes = engine.travel(envs=envs, max_minutes=float(cap), plane=True)["minutes"]
+    elif isinstance(minutes, torch.Tensor) and minutes.dim() == 2:
+        minutes = minutes[None]
+    return engine.escape(minutes, envs=envs, **kwargs)
+
+
 def _fire_influence(engine, source, envs, weights, include, inclusive, points, max_route, cells, value, pred_out, counts, scratch_bytes,
                     horizon, travel_kwargs):
     """``fire_influence`` of both simulation classes: ``source`` turned into the arguments of ``FireEngine.influence``.  "forecast"
@@ -715,6 +734,23 @@ class FireSimulation:
                                 max_minutes=max_minutes, plane=True)
         self._engine.sync()
         return _travel_unit(r, unit, float(self._engine.params.update_rate))["minutes"][0].cpu().numpy()
+
+    def escape_routes(self, targets=None, horizon_minutes=None, target=(), through=("UNBURNED",), passable=None, connectivity=4,
+                      minutes_per_move=None, margin_minutes=0.0, unreached_safe=False, minutes=None):
+        """How many more moves a walker may wait on every cell and still reach a target cell - BurnStatus one of ``target``, or
+        ``targets`` (a uint8 CUDA tensor [H, W]) not 0 - through cells whose BurnStatus is one of ``through`` (and where
+        ``passable`` is not 0), never standing on a cell at or after the moment the fire closes it: ``time_to_fire`` up to
+        ``horizon_minutes``, or ``minutes`` (a float32 CUDA tensor [H, W] or [1, H, W] of closing times).  Returns the NumPy int32
+        plane [H, W]: 2147483647 on targets and where no deadline binds, -1 where no route is left, -2 on cells that are neither
+        target nor walkable.  Host edits of ``fire_map`` are pushed to the device first, as ``moves_to`` does
+        (``BatchedFireSimulation.escape_routes``)."""
+        self._sync_to_device()
+        r = _escape_routes(self._engine, [0], minutes, dict(target=target, targets=targets, through=through, passable=passable,
+                                                           connectivity=connectivity, minutes_per_move=minutes_per_move,
+                                                           margin_minutes=margin_minutes, horizon_minutes=horizon_minutes,
+                                                           unreached_safe=unreached_safe, plane=True))
+        self._engine.sync()
+        return r["slack"][0].cpu().numpy()
 
     def fire_influence(self, source="history", weights=None, include=None, inclusive=False, value=False, horizon=None, **travel_kwargs):
         """WHICH cells matter: for every cell, how many cells the fire reaches - or reached - THROUGH it.  ``source="history"``: the
@@ -1582,6 +1618,31 @@ class BatchedFireSimulation:
                                 max_minutes=max_minutes, plane=plane, pred=pred, reached=reached, last=last, scratch_bytes=scratch_bytes)
         self._engine.sync()
         r = _travel_unit(r, unit, float(self._engine.params.update_rate))
+        return r if device else {k: v.cpu().numpy() for k, v in r.items()}
+
+    def escape_routes(self, targets=None, horizon_minutes=None, target=(), through=("UNBURNED",), passable=None, envs=None, connectivity=4,
+                      minutes_per_move=None, margin_minutes=0.0, unreached_safe=False, minutes=None, agents=False, step=False,
+                      plane=False, scratch_bytes=0, device=True):
+        """The escape slack in ``envs`` (default: all): how many more moves a walker may wait where it stands and still reach a
+        target cell - BurnStatus one of ``target``, or ``targets`` (uint8 CUDA [H, W] or [n_envs, H, W]) not 0 - one cell per move
+        through cells whose BurnStatus is one of ``through`` (and where ``passable`` is not 0), never standing on a cell at or after
+        the moment the fire closes it.  ``minutes=None``: the closing times are ``time_to_fire(max_minutes=horizon_minutes)``, kept
+        on the device and handed over; else a float32 CUDA tensor [n, H, W] of the caller's, e.g. one derived from
+        ``ensemble_stats``' ``first``.  ``minutes_per_move=None``: the update rate, one move per tick; ``margin_minutes``: leave a
+        cell that much before the fire; ``unreached_safe``: every walkable cell the fire does not close within the horizon is a
+        target too.  A dict of int32 arrays: ``safe``, ``escapable``, ``lost``, ``top`` [n]; with ``plane`` ``slack`` [n, H, W]
+        (2147483647: no deadline binds, -1: no route is left, -2: neither target nor walkable); with ``agents=True``
+        ``point_slack`` [n, k] for the device positions of a ``BatchedFireEnv`` (every environment in order), or for a tensor
+        [n, k, 3] = (column, row, id) of the caller's, and with ``step`` ``point_step`` [n, k], the move code 1..4 towards the
+        neighbour with the largest slack (0: no hurry, or lost).  ``device=True`` returns torch tensors on this GPU, else NumPy
+        arrays; complete on return either way (one wait).  No host copy of the maps, no change to the simulation (DESIGN.md
+        section 30)."""
+        r = _escape_routes(self._engine, envs, minutes, dict(target=target, targets=targets, through=through, passable=passable,
+                                                            connectivity=connectivity, minutes_per_move=minutes_per_move,
+                                                            margin_minutes=margin_minutes, horizon_minutes=horizon_minutes,
+                                                            unreached_safe=unreached_safe, points=self._agent_points(agents),
+                                                            plane=bool(plane), step=bool(step), summary=True, scratch_bytes=scratch_bytes))
+        self._engine.sync()
         return r if device else {k: v.cpu().numpy() for k, v in r.items()}
 
     def fire_influence(self, source="history", envs=None, weights=None, include=None, inclusive=False, points=None, max_route=0, cells=True,

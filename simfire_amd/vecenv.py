@@ -79,11 +79,19 @@ class BatchedFireEnv:
     DESIGN.md section 27), both from the state the observation shows.  Off by default: calls and ``info`` are what they are
     without it.
 
+    ``escape``: ``None``, or a dict with ``horizon_minutes`` and any of ``target``, ``targets``, ``through``, ``passable``,
+    ``minutes_per_move``, ``margin_minutes`` and ``unreached_safe`` (``BatchedFireSimulation.escape_routes``): ``info["escape_slack"]``
+    is then int32 [n_envs, n_agents], how many more ticks every agent may stay where it is and still reach a target cell ahead of the
+    fire (2147483647: no deadline binds; -1: no route is left), and ``info["escape_move"]`` int32 [n_envs, n_agents] the move code
+    1..4 towards the neighbour with the largest slack (0: no hurry, or lost) - ``time_to_fire`` up to the horizon and
+    ``FireEngine.escape``, both from the state the observation shows.  Off by default: calls and ``info`` are
+    what they are without it.
+
     Agents are not part of an environment's state: ``clone_envs`` / ``get_state`` / ``set_state`` do not carry them."""
 
     def __init__(self, sim, n_agents, start_xy, n_updates=1, weights=(-1, 0, 0, 0), only_unburned=True, done_on_burn=False,
                  max_ticks=0, auto_reset=True, obs=None, values=None, value_weight=None, fire_distance=None, reach=None,
-                 moves_to=None, behavior=None, time_to_fire=None, perimeter=None):
+                 moves_to=None, behavior=None, time_to_fire=None, perimeter=None, escape=None):
         self.sim = sim
         self.engine = sim._engine
         self.n_envs, self.n_agents = int(sim.n_envs), int(n_agents)
@@ -152,6 +160,23 @@ class BatchedFireEnv:
                 _perimeter.request(self.perimeter["status"])
             except ValueError as err:
                 raise ValueError(f"BatchedFireEnv: {err}") from None
+        self.escape = None
+        if escape is not None:
+            keys = {"target", "targets", "through", "passable", "horizon_minutes", "minutes_per_move", "margin_minutes", "unreached_safe"}
+            if not isinstance(escape, dict) or set(escape) - keys:
+                raise ValueError("BatchedFireEnv: escape is None or a dict of " + ", ".join(sorted(keys)))
+            self.escape = dict(target=escape.get("target", ()), targets=escape.get("targets"), through=escape.get("through", ("UNBURNED",)),
+                               passable=escape.get("passable"), horizon_minutes=escape.get("horizon_minutes"),
+                               minutes_per_move=escape.get("minutes_per_move"), margin_minutes=escape.get("margin_minutes", 0.0),
+                               unreached_safe=escape.get("unreached_safe", False))
+            from . import escape as _escape                         # (raises before anything is created)
+            try:
+                _escape.request(self.escape["target"], self.escape["through"], 4,
+                                float(self.engine.params.update_rate) if self.escape["minutes_per_move"] is None else self.escape["minutes_per_move"],
+                                self.escape["margin_minutes"], self.escape["horizon_minutes"], self.escape["unreached_safe"],
+                                targets=self.escape["targets"] is not None)
+            except ValueError as err:
+                raise ValueError(f"BatchedFireEnv: {err}") from None
         self.behavior = None
         if behavior is not None:
             if not isinstance(behavior, dict) or set(behavior) - {"flame_limit", "edges", "summary"}:
@@ -198,6 +223,10 @@ class BatchedFireEnv:
         if info is not None and self.perimeter is not None:
             r = self.engine.perimeter(**self.perimeter)
             info["fire_perimeter"], info["fire_cells"] = r["edges"], r["cells"]
+        if info is not None and self.escape is not None:
+            from .simulation import _escape_routes
+            r = _escape_routes(self.engine, None, None, dict(points=self.engine.agents_device(), connectivity=4, step=True, **self.escape))
+            info["escape_slack"], info["escape_move"] = r["point_slack"], r["point_step"]
         self.engine.sync()
         return obs
 
