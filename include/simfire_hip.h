@@ -959,6 +959,78 @@ typedef struct sf_influence_out {        /* device pointers, any may be NULL, at
  * weights, include, points and the outputs before the call. */
 int sf_influence(sf_sim *sim, const sf_influence_params *params, int32_t n, const int32_t *envs /* [n] host */, const sf_influence_out *out);
 
+/* Connected components: the selected cells of an environment as separate fires or separate unburned pockets -
+ * how many there are, which one a cell or a point belongs to, and what each is worth.  The reference has no counterpart; the
+ * semantics are this library's own.
+ * For a listed environment, s(c) is the status byte & 7 of cell c = (y, x), x < width, read from whichever cell plane is current.
+ *   sel(c) = bit s(c) of select_mask and, with a member plane, member[c] != 0 (device u8, dense [height * width], one plane for all or
+ *   - member_per_env - one per environment, indexed by the environment's number).  The pitch padding is never selected.
+ *   The neighbourhood N is the 8-neighbourhood (connectivity 8) or the 4-neighbourhood (4); connectivity 0 takes the handle's own
+ *   diagonal_spread.
+ *   A component is a maximal N-connected set of selected cells.  Components are numbered 1..C by the row-major index y * width + x of
+ *   their first cell, ascending (the numbering of scipy.ndimage.label), so every output is a pure function of the map: the same bits
+ *   on every run and whatever the launch geometry.
+ * cap = max_components.  Components beyond cap keep their numbers in labels and point_label and count in count, selected and largest;
+ * they have no row in cells, value, first, bbox and touch.
+ * touch: bit s (0..5) is set iff some cell of the component has an N-neighbour on the grid that is not selected and has status s; bit
+ * 6 iff some cell of the component lies on the grid's border.
+ * Points: device int32 [n][k][3] = (column, row, id), sf_agents_device's layout, as sf_distance takes them. */
+#define SF_COMPONENTS_MAX 4096
+typedef struct sf_components_params {
+    int32_t select_mask;                 /* 1..63 */
+    int32_t connectivity;                /* 0 (the handle's diagonal_spread), 4, 8 */
+    int32_t k;                           /* 0, or 1..SF_DIST_MAX_POINTS points per listed environment */
+    int32_t max_components;              /* cap: 1..SF_COMPONENTS_MAX rows of cells, value, first, bbox, touch */
+    int32_t member_per_env;              /* member is [n_envs][H*W] (indexed by environment number), else [H*W] */
+    int32_t reserved0;                   /* 0 (counts as reserved) */
+    const uint8_t *member;               /* device, or NULL */
+    const int32_t *points;               /* device int32 [n][k][3] = (column, row, id); NULL with k == 0 */
+    int64_t scratch_bytes;               /* 0: the default budget */
+    int32_t reserved[2];                 /* 0 */
+} sf_components_params;
+typedef struct sf_components_out {       /* device pointers, any may be NULL, at least one not */
+    int32_t *count;        /* [n]             C, the true number, also when it exceeds cap */
+    int32_t *selected;     /* [n]             number of selected cells */
+    int32_t *labels;       /* [n][H][W]       dense: 0 where not selected, else the component's number (not capped) */
+    int32_t *cells;        /* [n][cap]        size of component j + 1; rows j >= C are 0 */
+    int64_t *value;        /* [n][cap]        the value plane (sf_values_set; the environment's own under per_env) summed over it */
+    int32_t *first;        /* [n][cap]        y * width + x of its first cell; -1 for j >= C */
+    int32_t *bbox;         /* [n][cap][4]     (x0, y0, x1, y1) inclusive; (-1, -1, -1, -1) for j >= C */
+    int32_t *touch;        /* [n][cap]        see above; 0 for j >= C */
+    int32_t *largest;      /* [n][2]          (number, cells) of the largest component over ALL C; ties to the lower number; (0, 0) if C == 0 */
+    int32_t *point_label;  /* [n][k]          the label under each point; 0: not selected; -1 for id <= 0 or a cell off the grid */
+} sf_components_out;
+/* Environment envs[i] (a host array; any order, repeats allowed) lands in row i of every output.  Every refusal is SF_EINVAL before
+ * anything is enqueued:
+ *   | refused                                                              |
+ *   | select_mask outside 1..63                                            |
+ *   | connectivity not 0, 4 or 8                                           |
+ *   | k outside 0..256                                                     |
+ *   | k > 0 without points, points with k == 0                             |
+ *   | max_components outside 1..4096                                       |
+ *   | point_label with k == 0, k > 0 without point_label                   |
+ *   | reserved != 0 (reserved0 included)                                   |
+ *   | every output null                                                    |
+ *   | an output or points not aligned to its element (4 bytes, 8 for value)|
+ *   | a positive scratch_bytes below one environment's need                |
+ *   | an environment out of range                                          |
+ *   | value without a value plane (sf_values_set)                          |
+ * A grid wider than 8192 cells or of 2^31 cells or more is SF_ENOTSUP; a handle without a reset is SF_ESTATE.  A running closed loop is
+ * ended first, as by every query.
+ * The work is a union-find over a label plane of one int32 per cell - the labels output where that is asked for, else scratch - in
+ * separate launches per chunk of listed environments: stage and initialise (a cell's first parent is the first cell of its
+ * horizontal run), merge (a lock-free union wherever a contact with the row above begins; agent-scope atomics only), flatten, rank
+ * the roots in row-major order, relabel and gather the statistics with integer atomics.  No workgroup waits for another.
+ * The call reads the state and writes nothing but its outputs and its own scratch.  The scratch belongs to the handle: per listed
+ * environment of a chunk, every term rounded up to 256, 256 bytes + height * ceil(width / 64) * 8 (the selected bits) + 4 * (height +
+ * 1) + 4 * height * width (ranks, then sizes) + 4 * height * width where labels is not asked for (the label plane); allocated at the
+ * first call, grown (never shrunk) when a later call needs more, freed by sf_destroy, counted by sf_memory_bytes.  The default budget
+ * is 3 GiB (256 environments of 1024 x 1024 are one chunk); the list is worked through in chunks so that scratch never exceeds the
+ * budget, which changes no bit of the result.
+ * In async mode the call only enqueues (the outputs are complete when the handle's stream has got there); the caller orders its own
+ * work on member, points and the outputs before the call. */
+int sf_components(sf_sim *sim, const sf_components_params *params, int32_t n, const int32_t *envs /* [n] host */, const sf_components_out *out);
+
 /* Agents on the device: K agents per environment that walk the grid and draw control lines where they stand,
  * stepped from a policy's action tensor without a host read.  The reference records agent positions only (simulation.py:480-499) and
  * leaves the loop to the harness (the run docstring, 505-509); the semantics are this library's own.

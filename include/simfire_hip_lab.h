@@ -24,6 +24,10 @@ int sf_get_reset_ms(sf_sim *sim, float *ms_out);
  * and value passes behind it); sf_get_ignite_ms reports the last one's GPU time (SF_ESTATE when none has been timed). */
 int sf_time_ignites(sf_sim *sim, int32_t on);
 int sf_get_ignite_ms(sf_sim *sim, float *ms_out);
+/* The same for sf_components: the events go around everything the call enqueues behind its call block - the memsets of the outputs
+ * and every chunk's launches; sf_get_components_ms reports the last call's GPU time (SF_ESTATE when none has been timed). */
+int sf_time_components(sf_sim *sim, int32_t on);
+int sf_get_components_ms(sf_sim *sim, float *ms_out);
 
 /* Introspection for benchmarks: out[0] = active cell-updates (cells whose burn_amounts were
  * read+written: candidates and attenuated line cells), out[1] = ignitions, out[2] = cells handed

@@ -227,6 +227,22 @@ class SfInfluenceOut(C.Structure):
                 ("point_hops", C.c_void_p)]
 
 
+SF_COMPONENTS_MAX = 4096
+
+
+class SfComponentsParams(C.Structure):
+    """``sf_components_params`` (include/simfire_hip.h)."""
+    _fields_ = [("select_mask", C.c_int32), ("connectivity", C.c_int32), ("k", C.c_int32), ("max_components", C.c_int32),
+                ("member_per_env", C.c_int32), ("reserved0", C.c_int32), ("member", C.c_void_p), ("points", C.c_void_p),
+                ("scratch_bytes", C.c_int64), ("reserved", C.c_int32 * 2)]
+
+
+class SfComponentsOut(C.Structure):
+    """``sf_components_out`` (include/simfire_hip.h): device pointers, any may be null, not all."""
+    _fields_ = [("count", C.c_void_p), ("selected", C.c_void_p), ("labels", C.c_void_p), ("cells", C.c_void_p), ("value", C.c_void_p),
+                ("first", C.c_void_p), ("bbox", C.c_void_p), ("touch", C.c_void_p), ("largest", C.c_void_p), ("point_label", C.c_void_p)]
+
+
 # name -> argtypes; every function returns int except the two string getters
 _VP, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
 SIGNATURES = {
@@ -281,6 +297,8 @@ SIGNATURES = {
     "sf_ignite_device": [_VP, _VP, _I32],
     "sf_time_ignites": [_VP, _I32],
     "sf_get_ignite_ms": [_VP, C.POINTER(C.c_float)],
+    "sf_time_components": [_VP, _I32],
+    "sf_get_components_ms": [_VP, C.POINTER(C.c_float)],
     "sf_load_fire_map": [_VP, _I32, _VP],
     "sf_step": [_VP, _I32],
     "sf_step_timed": [_VP, _I32, C.POINTER(C.c_float)],
@@ -307,6 +325,7 @@ SIGNATURES = {
     "sf_get_behavior_builds": [_VP, C.POINTER(_I64)],
     "sf_perimeter": [_VP, C.POINTER(SfPerimeterParams), _I32, _VP, C.POINTER(SfPerimeterOut)],
     "sf_influence": [_VP, C.POINTER(SfInfluenceParams), _I32, _VP, C.POINTER(SfInfluenceOut)],
+    "sf_components": [_VP, C.POINTER(SfComponentsParams), _I32, _VP, C.POINTER(SfComponentsOut)],
     "sf_cell_layout": [_VP, C.POINTER(_I32)],
     "sf_render": [_VP, C.POINTER(SfRenderParams), _I32, _VP, _VP],
     "sf_status_device": [_VP, C.POINTER(_VP)],

@@ -252,7 +252,8 @@ struct EpisodeState {
 // two halos (walk_env_bytes); sf_escape those, the sorted cells and the buckets (escape_env_bytes); sf_travel the working array, float32 [H][W] dense (travel_env_bytes) - only when the call asks for no
 // minutes plane, which is the working array otherwise; sf_perimeter the bit plane, the edge words and eight arrays of max_edges
 // (perim_env_bytes) - only when the call asks for a traced output; sf_influence the parent codes, the child counters and the
-// accumulators that are no output of the call (infl_env_bytes).
+// accumulators that are no output of the call (infl_env_bytes); sf_components the selected bits, the rows' root counts, the second plane
+// and - unless the labels output is the label plane - the label plane (cc_env_bytes).
 struct QueryState {
     uint8_t *mem = nullptr;
     size_t cap = 0;
@@ -359,11 +360,12 @@ struct sf_sim {
     WindState wind;
     AgentState agents;
     EpisodeState episodes;
-    QueryState dist, reach, walk, escape, travel, perimeter, influence;      // one block and one scratch per feature (as for CallBlock: calls of different features do not wait for each other)
+    QueryState dist, reach, walk, escape, travel, perimeter, influence, components;      // one block and one scratch per feature (as for CallBlock: calls of different features do not wait for each other)
     BehaviorState behavior;
     CallBlock obs_blk;                 // sf_observe: ObsHead, environment list, host centers / agents
     CallBlock rs_blk;                  // sf_reset_envs / sf_reset_where: the environment list and host ignitions of a call
     LabTimer reset_timer;              // sf_time_resets: ev0 / ev1 recorded around the launches of every batched reset
+    LabTimer components_timer;         // sf_time_components: the same around the memsets and launches of every sf_components
     LabTimer ignite_timer;             // sf_time_ignites: the same around the scatter launch of every sf_ignite / sf_ignite_device
     CallBlock gen_blk;                 // sf_generate_layers: its descriptors + environment list
     CallBlock ens_blk;                 // sf_ensemble_stats: the member list of a call

@@ -1,4 +1,4 @@
-// Host code of the queries: sf_distance, sf_reach (23), sf_walk (24), sf_behavior (25), sf_travel (26), sf_perimeter (27), sf_influence (28) and sf_escape (30).  Each takes a list
+// Host code of the queries: sf_distance, sf_reach (23), sf_walk (24), sf_behavior (25), sf_travel (26), sf_perimeter (27), sf_influence (28), sf_escape (30) and sf_components (31).  Each takes a list
 // of environments, optional points and caller-owned device outputs, reads the state and changes none of it.  Included once from
 // simfire_hip.hip, behind sf_host_views.h.
 //
@@ -717,4 +717,136 @@ extern "C" int sf_influence(sf_sim *s, const sf_influence_params *p, int32_t n, 
             hipLaunchKernelGGL(k_infl_points, dim3((unsigned)(((long long)cn * p->k + kInflThreads - 1) / kInflThreads)), dim3(kInflThreads), 0, s->stream, a, cn);
     }
     return finish_call(s, who, !s->async, nullptr);
+}
+
+// ----------------------------------------------------------------------------- connected components
+// Per chunk: the head of every environment's scratch zeroed, then k_comp_stage, k_comp_merge, k_comp_heads, k_comp_flatten and
+// k_comp_scan (count is done here); with any output beyond count and selected k_comp_assign and k_comp_relabel; with a stats row or
+// largest k_comp_stats (around it k_comp_zero and k_comp_largest); with largest or points k_comp_finish.  The scratch of a listed
+// environment is cc_env_bytes: the label plane is the caller's labels output where that is asked for.  The call block is the
+// environment list | one CompArgs per chunk; the kernels take their arguments from there.
+extern "C" int sf_components(sf_sim *s, const sf_components_params *p, int32_t n, const int32_t *envs, const sf_components_out *out)
+{
+    const char *who = "sf_components";
+    if (!s || !p || !out) return fail(SF_EINVAL, "sf_components: null argument");
+    const Geo &g = s->g;
+    if (n < 0 || (n > 0 && !envs)) return fail(SF_EINVAL, "sf_components: bad environment list");
+    if (p->select_mask < 1 || p->select_mask > 63) return fail(SF_EINVAL, "sf_components: select_mask %d (bit s selects BurnStatus s: 1..63)", p->select_mask);
+    if (p->connectivity != 0 && p->connectivity != 4 && p->connectivity != 8)
+        return fail(SF_EINVAL, "sf_components: connectivity %d (0: the handle's diagonal_spread, 4, 8)", p->connectivity);
+    SF_TRY(check_points(who, p->k, p->points, true));
+    if (p->max_components < 1 || p->max_components > kCompMaxCap)
+        return fail(SF_EINVAL, "sf_components: max_components %d (1..%d)", p->max_components, kCompMaxCap);
+    if (out->point_label && p->k == 0) return fail(SF_EINVAL, "sf_components: point_label needs k > 0");
+    if (p->k > 0 && !out->point_label) return fail(SF_EINVAL, "sf_components: points without point_label");
+    SF_TRY(check_reserved(who, p->reserved0 | p->reserved[0] | p->reserved[1]));
+    if (!out->count && !out->selected && !out->labels && !out->cells && !out->value && !out->first && !out->bbox && !out->touch && !out->largest && !out->point_label)
+        return fail(SF_EINVAL, "sf_components: every output is null");
+    SF_TRY(check_aligned(who, (((uintptr_t)out->count | (uintptr_t)out->selected | (uintptr_t)out->labels | (uintptr_t)out->cells | (uintptr_t)out->first |
+                                (uintptr_t)out->bbox | (uintptr_t)out->touch | (uintptr_t)out->largest | (uintptr_t)out->point_label | (uintptr_t)p->points) & 3) |
+                                   ((uintptr_t)out->value & 7)));
+    const size_t need = (size_t)cc_env_bytes(g.H, g.W, out->labels != nullptr);
+    SF_TRY(check_scratch(who, p->scratch_bytes, need, "need"));
+    SF_TRY(check_envs(s, who, n, envs));
+    if (out->value && !s->values.plane) return fail(SF_EINVAL, "sf_components: value needs a value plane (sf_values_set)");
+    if (g.W > kCompMaxWidth) return fail(SF_ENOTSUP, "sf_components: grids wider than %d cells are not supported (width %d)", kCompMaxWidth, g.W);
+    if ((long long)g.H * g.W >= (1ll << 31)) return fail(SF_ENOTSUP, "sf_components: the cells of a %d x %d grid do not fit int32", g.H, g.W);
+    SF_TRY(begin_call(s, who, kNeedReset | kNotVoid));
+    if (n == 0) return SF_OK;
+
+    QueryState &q = s->components;
+    const size_t cells = (size_t)g.H * g.W;
+    const int cap = p->max_components;
+    const int chunk = query_chunk(n, p->scratch_bytes, kCompScratchDefault, need, 65535), chunks = (n + chunk - 1) / chunk;      // (65535: the launch grid's y)
+    SF_TRY(scratch_reserve(s, q, (size_t)chunk * need));
+    SF_TRY(lab_start(s, s->components_timer));
+    // rows past the count: 0 (cells, value, touch) and -1 (first, bbox); selected is added to
+    if (out->selected) HIPCHK(hipMemsetAsync(out->selected, 0, (size_t)n * sizeof(int32_t), s->stream));
+    if (out->cells) HIPCHK(hipMemsetAsync(out->cells, 0, (size_t)n * cap * sizeof(int32_t), s->stream));
+    if (out->value) HIPCHK(hipMemsetAsync(out->value, 0, (size_t)n * cap * sizeof(int64_t), s->stream));
+    if (out->touch) HIPCHK(hipMemsetAsync(out->touch, 0, (size_t)n * cap * sizeof(int32_t), s->stream));
+    if (out->first) HIPCHK(hipMemsetAsync(out->first, 0xFF, (size_t)n * cap * sizeof(int32_t), s->stream));
+    if (out->bbox) HIPCHK(hipMemsetAsync(out->bbox, 0xFF, (size_t)n * cap * 4 * sizeof(int32_t), s->stream));
+
+    CompArgs a;
+    memset(&a, 0, sizeof a);
+    a.g = cell_geo(g);
+    a.pl = cur_planes(s);
+    a.member = p->member;
+    a.mem_env = p->member_per_env ? (long long)cells : 0;
+    a.mem_vec = p->member && g.W % 16 == 0 && !((uintptr_t)p->member & 15);
+    mask_tables(p->select_mask, a.tlo, a.thi);
+    a.conn8 = p->connectivity == 0 ? g.diag : (p->connectivity == 8);
+    a.WORDS = cc_words(g.W);
+    a.cap = cap;
+    a.k = p->k;
+    a.scratch = q.mem;
+    a.scratch_env = (long long)need;
+    a.o_rows = cc_off_rows(g.H, g.W); a.o_aux = cc_off_aux(g.H, g.W); a.o_par = cc_off_par(g.H, g.W);
+    a.vals = out->value ? s->values.plane : nullptr;
+    a.val_env = s->values.per_env ? g.plane_env : 0;
+    a.lab_vec = cells % 4 == 0 && !((uintptr_t)out->labels & 15);
+
+    const size_t o_args = ((size_t)n * sizeof(int32_t) + 15) / 16 * 16, bytes = o_args + (size_t)chunks * sizeof(CompArgs);
+    SF_TRY(block_reserve(s, q.blk, bytes));
+    memcpy(q.blk.pinned, envs, (size_t)n * sizeof(int32_t));
+    for (int c = 0; c < chunks; ++c) {
+        const int c0 = c * chunk;
+        a.envs = reinterpret_cast<const int32_t *>(q.blk.dev) + c0;
+        a.points = p->k ? p->points + (size_t)c0 * p->k * 3 : nullptr;
+        a.count = out->count ? out->count + c0 : nullptr;
+        a.selected = out->selected ? out->selected + c0 : nullptr;
+        a.labels = out->labels ? out->labels + (size_t)c0 * cells : nullptr;
+        a.cells = out->cells ? out->cells + (size_t)c0 * cap : nullptr;
+        a.value = out->value ? reinterpret_cast<long long *>(out->value) + (size_t)c0 * cap : nullptr;
+        a.first = out->first ? out->first + (size_t)c0 * cap : nullptr;
+        a.bbox = out->bbox ? out->bbox + (size_t)c0 * cap * 4 : nullptr;
+        a.touch = out->touch ? out->touch + (size_t)c0 * cap : nullptr;
+        a.largest = out->largest ? out->largest + (size_t)c0 * 2 : nullptr;
+        a.point_label = out->point_label ? out->point_label + (size_t)c0 * p->k : nullptr;
+        memcpy(q.blk.pinned + o_args + (size_t)c * sizeof(CompArgs), &a, sizeof a);
+    }
+    SF_TRY(block_send(s, q.blk, bytes));
+
+    const bool stats = out->cells || out->value || out->bbox || out->touch || out->largest;
+    const bool numbered = stats || out->labels || out->first || out->point_label;
+    const unsigned row_blocks = (unsigned)((g.H + kCompThreads / 64 - 1) / (kCompThreads / 64));
+    const unsigned word_blocks = (unsigned)(((long long)g.H * a.WORDS + kCompThreads - 1) / kCompThreads);
+    const unsigned cell_blocks = (unsigned)(((a.lab_vec ? cells / 4 : cells) + kCompThreads - 1) / kCompThreads);
+    const unsigned max_blocks = (unsigned)std::max<size_t>(1, std::min<size_t>((cells / 2 + kCompThreads * 8 - 1) / (kCompThreads * 8), 64));
+    for (int c = 0; c < chunks; ++c) {
+        const unsigned cn = (unsigned)std::min(chunk, n - c * chunk);
+        const CompArgs *ap = reinterpret_cast<const CompArgs *>(q.blk.dev + o_args) + c;
+        HIPCHK(hipMemset2DAsync(q.mem, need, 0, kCompHeadBytes, cn, s->stream));
+        hipLaunchKernelGGL(k_comp_stage, dim3(row_blocks, cn), dim3(kCompThreads), 0, s->stream, ap);
+        hipLaunchKernelGGL(k_comp_merge, dim3(word_blocks, cn), dim3(kCompThreads), 0, s->stream, ap);
+        hipLaunchKernelGGL(k_comp_heads, dim3(word_blocks, cn), dim3(kCompThreads), 0, s->stream, ap);
+        hipLaunchKernelGGL(k_comp_flatten, dim3(row_blocks, cn), dim3(kCompThreads), 0, s->stream, ap);
+        hipLaunchKernelGGL(k_comp_scan, dim3(cn), dim3(kCompScanThreads), 0, s->stream, ap);
+        if (!numbered) continue;
+        hipLaunchKernelGGL(k_comp_assign, dim3(row_blocks, cn), dim3(kCompThreads), 0, s->stream, ap);
+        hipLaunchKernelGGL(k_comp_relabel, dim3(cell_blocks, cn), dim3(kCompThreads), 0, s->stream, ap);
+        if (stats) {
+            if (out->largest) hipLaunchKernelGGL(k_comp_zero, dim3(max_blocks, cn), dim3(kCompThreads), 0, s->stream, ap);
+            hipLaunchKernelGGL(k_comp_stats, dim3(word_blocks, cn), dim3(kCompThreads), 0, s->stream, ap);
+            if (out->largest) hipLaunchKernelGGL(k_comp_largest, dim3(max_blocks, cn), dim3(kCompThreads), 0, s->stream, ap);
+        }
+        if (out->largest || p->k)
+            hipLaunchKernelGGL(k_comp_finish, dim3((unsigned)(((long long)cn * (p->k + 1) + kCompThreads - 1) / kCompThreads)), dim3(kCompThreads), 0, s->stream, ap, (int)cn);
+    }
+    SF_TRY(lab_stop(s, s->components_timer));
+    return finish_call(s, who, !s->async, nullptr);
+}
+
+extern "C" int sf_time_components(sf_sim *s, int32_t on)
+{
+    if (!s) return fail(SF_EINVAL, "sf_time_components: null handle");
+    s->components_timer = {on != 0, false};
+    return SF_OK;
+}
+
+extern "C" int sf_get_components_ms(sf_sim *s, float *ms_out)
+{
+    if (!s || !ms_out) return fail(SF_EINVAL, "sf_get_components_ms: null argument");
+    return lab_ms(s, s->components_timer, "sf_get_components_ms", "no sf_components call has been timed (sf_time_components)", ms_out);
 }

@@ -89,6 +89,7 @@
 #include "sf_travel_kernels.h"
 #include "sf_perimeter_kernels.h"
 #include "sf_influence_kernels.h"
+#include "sf_components_kernels.h"
 #include "sf_behavior_kernels.h"
 #include "sf_ignite_kernels.h"
 
@@ -243,8 +244,8 @@ static int destroy(sf_sim *s)
     // every feature frees what it owns; the step path's own buffers are listed here
     (void)s->team.release(); (void)s->loop.release(); (void)s->delta.release(); (void)s->arrival.release(); (void)s->values.release();
     (void)s->render.release(); (void)s->wind.release(); (void)s->agents.release(); (void)s->episodes.release();
-    (void)s->dist.release(); (void)s->reach.release(); (void)s->walk.release(); (void)s->escape.release(); (void)s->travel.release(); (void)s->perimeter.release(); (void)s->influence.release(); (void)s->behavior.release();
-    for (CallBlock *b : {&s->obs_blk, &s->render.blk, &s->rs_blk, &s->gen_blk, &s->agents.blk, &s->wind.blk, &s->ens_blk, &s->dist.blk, &s->reach.blk, &s->walk.blk, &s->escape.blk, &s->travel.blk, &s->perimeter.blk, &s->influence.blk, &s->behavior.blk}) b->release();
+    (void)s->dist.release(); (void)s->reach.release(); (void)s->walk.release(); (void)s->escape.release(); (void)s->travel.release(); (void)s->perimeter.release(); (void)s->influence.release(); (void)s->components.release(); (void)s->behavior.release();
+    for (CallBlock *b : {&s->obs_blk, &s->render.blk, &s->rs_blk, &s->gen_blk, &s->agents.blk, &s->wind.blk, &s->ens_blk, &s->dist.blk, &s->reach.blk, &s->walk.blk, &s->escape.blk, &s->travel.blk, &s->perimeter.blk, &s->influence.blk, &s->components.blk, &s->behavior.blk}) b->release();
     void *ptrs[] = {s->status, s->age_alloc, s->cells_alloc, s->burn, s->rt, s->rtc, s->lay_all, s->history, s->smag, s->sdir, s->commit, s->tmp, s->flags, s->counters, s->tflags, s->tile_list, s->n_active, s->seam, s->settled, s->tdirty, s->thist, s->vbits, s->todo, s->run_cost, s->run_order, s->todo_cnt, s->win_hint, s->mit_stage,
                     s->status_block, s->elapsed_dev, s->stage, s->parents};
     for (void *p : ptrs) if (p) hipFree(p);

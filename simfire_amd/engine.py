@@ -4,7 +4,7 @@ This is the only module that touches the HIP library; the reference-shaped class
 ``fire.py`` / ``simulation.py`` are written on top of it.  Arrays cross the boundary as
 NumPy host arrays (copied during the call) or as torch CUDA tensors, read and written in place; torch is imported only by the
 methods that take or return one.  Layout (binding map): argument checks in ``_args.py``, one request class per feature
-(``observe.py``, ``render.py``, ``distance.py``, ``reach.py``, ``walk.py``, ``escape.py``, ``travel.py``, ``behavior.py``, ``perimeter.py``, ``influence.py``, ``ensemble.py``), and one frame, ``_device_call``, for every call
+(``observe.py``, ``render.py``, ``distance.py``, ``reach.py``, ``walk.py``, ``escape.py``, ``travel.py``, ``behavior.py``, ``perimeter.py``, ``influence.py``, ``components.py``, ``ensemble.py``), and one frame, ``_device_call``, for every call
 that hands the library a tensor.
 """
 import ctypes as C
@@ -1162,6 +1162,52 @@ class FireEngine:
         if spec.n:
             p, o = spec.params(), spec.out(res)
             self._device_call(self._L.sf_influence, C.byref(p), spec.n, _ptr(spec.envs), C.byref(o), tensors=list(res.values()) + spec.device_tensors())
+        return res
+
+    # ---------------------------------------------------------------- connected components
+    TOUCH_BORDER = 64
+
+    def components_scratch_bytes(self, labels=False):
+        from . import components
+        return components.scratch_need(self.H, self.W, labels)
+
+    def time_components(self, on=True):
+        """Measurement only: record HIP events around the memsets and launches of every ``components`` call (``sf_time_components``)."""
+        self._switch(self._L.sf_time_components, on)
+
+    def components_ms(self):
+        """GPU milliseconds of the last timed ``components`` call (``sf_get_components_ms``; waits for it)."""
+        return self._get(self._L.sf_get_components_ms, C.c_float)
+
+    def components(self, select=("BURNING",), envs=None, connectivity=None, member=None, points=None, max_components=64, count=True,
+                   labels=False, cells=False, value=False, first=False, bbox=False, touch=False, largest=False, selected=False,
+                   scratch_bytes=0):
+        """The separate fires - or pockets - of ``envs`` (default: all, in order; any order, repeats allowed): the maximal connected
+        sets of the cells whose BurnStatus ``select`` selects (a mask, or members, names or ints) and, with ``member`` (a uint8 CUDA
+        tensor [H, W] for all or [n_envs, H, W] indexed by environment number), only where it is not 0, over the 8- or
+        4-neighbourhood (``connectivity``; None: the simulation's ``diagonal_spread``) (``sf_components``).
+        Components are numbered 1..C by the row-major index of their first cell, as ``scipy.ndimage.label`` numbers them.  Read from
+        whichever cell plane is current; no state of the handle changes.
+        Returns a dict of torch tensors on this GPU, one per output asked for: ``count`` int32 [n] (C, also beyond
+        ``max_components``), ``selected`` int32 [n], ``labels`` int32 [n, H, W] (0: not selected), ``largest`` int32 [n, 2] = (number,
+        cells) over all C, ties to the lower number; one row per component for the first ``max_components`` (1..4096): ``cells``
+        int32 [n, cap], ``value`` int64 [n, cap] (the value plane of ``values_set`` summed over it), ``first`` int32 [n, cap]
+        (y * W + x of its first cell, -1 past C), ``bbox`` int32 [n, cap, 4] = (x0, y0, x1, y1) inclusive (-1 past C), ``touch`` int32
+        [n, cap]: bit s = some cell has an unselected neighbour of BurnStatus s, bit 6 (``TOUCH_BORDER``) = some cell lies on the
+        grid's border; and with ``points`` - int32 CUDA [n, k, 3] = (column, row, id), k <= 256, e.g. ``agents_device()`` -
+        ``point_label`` int32 [n, k]: the label under the point, 0 not selected, -1 for id <= 0 or off the grid.
+        ``scratch_bytes``: the most scratch the call may use (0: 3 GiB); less than ``components_scratch_bytes(labels)`` is a
+        ``ValueError``.  Torch's queued work is waited for first; in async mode the call only enqueues: the tensors are complete after
+        ``sync()`` and kept alive until then."""
+        from .components import ComponentsSpec
+        spec = ComponentsSpec(self.n_envs, self.H, self.W, getattr(self, "values_on", False), select=select, envs=envs,
+                              connectivity=connectivity, member=member, points=points, max_components=max_components, count=count,
+                              labels=labels, cells=cells, value=value, first=first, bbox=bbox, touch=touch, largest=largest,
+                              selected=selected, scratch_bytes=scratch_bytes)
+        res = self._outputs("components", spec)
+        if spec.n:
+            p, o = spec.params(), spec.out(res)
+            self._device_call(self._L.sf_components, C.byref(p), spec.n, _ptr(spec.envs), C.byref(o), tensors=list(res.values()) + spec.device_tensors())
         return res
 
     def behavior_builds(self):

@@ -706,6 +706,23 @@ class FireSimulation:
         self._engine.sync()
         return r["mask"][0].cpu().numpy().astype(bool), int(r["count"][0]), int(r["value"][0]) if value else None
 
+    def components(self, select=("BURNING",), connectivity=None, member=None, max_components=64, labels=True, cells=True, value=False,
+                   first=False, bbox=False, touch=False, largest=False):
+        """The separate fires (or pockets): the maximal connected sets of the cells whose BurnStatus is one of ``select`` (members,
+        names or ints; ``member``: a uint8 CUDA tensor [H, W], 0 = left out), over the 8- or 4-neighbourhood (``connectivity``; None:
+        the configured ``diagonal_spread``), numbered 1..C by their first cell in row-major order.  Returns a dict of NumPy arrays
+        without a batch axis: ``count`` (an int), ``selected`` (an int), and per flag ``labels`` int32 [H, W], ``cells`` [cap],
+        ``value`` int64 [cap], ``first`` [cap], ``bbox`` [cap, 4], ``touch`` [cap], ``largest`` [2].  Host edits of ``fire_map`` are
+        pushed to the device first, as ``reach`` does (``BatchedFireSimulation.components``)."""
+        self._sync_to_device()
+        r = self._engine.components(select, envs=[0], connectivity=connectivity, member=member, max_components=max_components, count=True,
+                                    labels=bool(labels), cells=bool(cells), value=bool(value), first=bool(first), bbox=bool(bbox),
+                                    touch=bool(touch), largest=bool(largest), selected=True)
+        self._engine.sync()
+        out = {k: v[0].cpu().numpy() for k, v in r.items()}
+        out["count"], out["selected"] = int(out["count"]), int(out["selected"])
+        return out
+
     def moves_to(self, target=("BURNING",), through=("UNBURNED",), connectivity=4, passable=None, targets=None, max_moves=None):
         """How many moves a walker needs from every cell to step onto a target cell - BurnStatus one of ``target``, or ``targets``
         (a uint8 CUDA tensor [H, W]) not 0 - when it enters only cells whose BurnStatus is one of ``through`` (and where ``passable``,
@@ -1577,6 +1594,38 @@ class BatchedFireSimulation:
                                value=bool(value), mask=bool(mask), seeds=True)
         self._engine.sync()
         return r if device else {k: v.cpu().numpy() for k, v in r.items()}
+
+    def components(self, select=("BURNING",), envs=None, connectivity=None, member=None, agents=False, max_components=64, count=True,
+                   labels=False, cells=False, value=False, first=False, bbox=False, touch=False, largest=False, selected=False,
+                   scratch_bytes=0, device=True):
+        """The separate fires - or pockets - of ``envs`` (default: all): the maximal connected sets of the cells whose BurnStatus is
+        one of ``select`` (members, names or ints; or a mask) and, with ``member`` (uint8 CUDA [H, W] or [n_envs, H, W]), only where
+        it is not 0; ``connectivity`` 4, 8 or None (the configured ``diagonal_spread``).  Components are numbered 1..C by their
+        first cell in row-major order.  A dict, one entry per output asked for (``FireEngine.components`` describes them):
+        ``count``, ``selected``, ``labels``, ``largest``, the rows ``cells``, ``value``, ``first``, ``bbox``, ``touch`` of the first
+        ``max_components``, and with ``agents=True`` ``point_label`` int32 [n, k] for the device positions of a ``BatchedFireEnv``
+        (every environment in order), or for a tensor [n, k, 3] = (column, row, id) of the caller's: which fire or pocket each
+        stands in.  ``device=True`` returns torch tensors on this GPU, else NumPy arrays; complete on return either way (one wait).
+        One call, no host copy of the maps, no change to the simulation."""
+        r = self._engine.components(select, envs=envs, connectivity=connectivity, member=member, points=self._agent_points(agents),
+                                    max_components=max_components, count=count, labels=labels, cells=cells, value=value, first=first,
+                                    bbox=bbox, touch=touch, largest=largest, selected=selected, scratch_bytes=scratch_bytes)
+        self._engine.sync()
+        return r if device else {k: v.cpu().numpy() for k, v in r.items()}
+
+    def pockets(self, fire=("BURNING",), through=("UNBURNED",), envs=None, connectivity=None, value=False, max_components=64):
+        """The unburned pockets of ``envs`` (default: all) and which of them the fire cannot get into: the components of the cells
+        whose BurnStatus is one of ``through``, a pocket being EXPOSED when one of its cells has a neighbour whose BurnStatus is one
+        of ``fire``.  A dict of torch tensors on this GPU, made without a host read: ``count`` int32 [n], ``cells`` int32 [n, cap],
+        ``exposed`` bool [n, cap], ``safe_cells`` [n] - the cells of the pockets that are not exposed, the "saved" compartments -,
+        ``truncated`` bool [n] (``count > max_components``: the sums then cover the first ``max_components`` pockets only), and
+        with ``value`` ``value`` int64 [n, cap] and ``safe_value`` int64 [n] under the value plane."""
+        from . import components
+        fire_mask = components.mask_of(fire)
+        r = self._engine.components(through, envs=envs, connectivity=connectivity, max_components=max_components, count=True, cells=True,
+                                    value=bool(value), touch=True)
+        self._engine.sync()
+        return components.pockets_summary(r, fire_mask, int(max_components))
 
     def moves_to(self, target=("BURNING",), through=("UNBURNED",), envs=None, connectivity=4, passable=None, targets=None,
                  max_moves=None, agents=False, step=False, plane=False, device=True):

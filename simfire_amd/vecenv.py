@@ -87,11 +87,16 @@ class BatchedFireEnv:
     ``FireEngine.escape``, both from the state the observation shows.  Off by default: calls and ``info`` are
     what they are without it.
 
+    ``components``: ``None``, or a dict with ``select`` (BurnStatus members, names or ints; default BURNING) and ``connectivity``
+    (4, 8 or None: the configured ``diagonal_spread``): ``info["fire_count"]`` is then int32 [n_envs], the number of separate fires,
+    and ``info["largest_fire_cells"]`` int32 [n_envs] the cells of the largest (``FireEngine.components``), both
+    from the state the observation shows.  Off by default: calls and ``info`` are what they are without it.
+
     Agents are not part of an environment's state: ``clone_envs`` / ``get_state`` / ``set_state`` do not carry them."""
 
     def __init__(self, sim, n_agents, start_xy, n_updates=1, weights=(-1, 0, 0, 0), only_unburned=True, done_on_burn=False,
                  max_ticks=0, auto_reset=True, obs=None, values=None, value_weight=None, fire_distance=None, reach=None,
-                 moves_to=None, behavior=None, time_to_fire=None, perimeter=None, escape=None):
+                 moves_to=None, behavior=None, time_to_fire=None, perimeter=None, escape=None, components=None):
         self.sim = sim
         self.engine = sim._engine
         self.n_envs, self.n_agents = int(sim.n_envs), int(n_agents)
@@ -177,6 +182,16 @@ class BatchedFireEnv:
                                 targets=self.escape["targets"] is not None)
             except ValueError as err:
                 raise ValueError(f"BatchedFireEnv: {err}") from None
+        self.components = None
+        if components is not None:
+            if not isinstance(components, dict) or set(components) - {"select", "connectivity"}:
+                raise ValueError("BatchedFireEnv: components is None or a dict of select and connectivity")
+            self.components = dict(select=components.get("select", ("BURNING",)), connectivity=components.get("connectivity"))
+            from . import components as _components                 # (raises before anything is created)
+            try:
+                _components.request(self.components["select"], self.components["connectivity"])
+            except ValueError as err:
+                raise ValueError(f"BatchedFireEnv: {err}") from None
         self.behavior = None
         if behavior is not None:
             if not isinstance(behavior, dict) or set(behavior) - {"flame_limit", "edges", "summary"}:
@@ -227,6 +242,9 @@ class BatchedFireEnv:
             from .simulation import _escape_routes
             r = _escape_routes(self.engine, None, None, dict(points=self.engine.agents_device(), connectivity=4, step=True, **self.escape))
             info["escape_slack"], info["escape_move"] = r["point_slack"], r["point_step"]
+        if info is not None and self.components is not None:
+            r = self.engine.components(count=True, largest=True, **self.components)
+            info["fire_count"], info["largest_fire_cells"] = r["count"], r["largest"][:, 1]
         self.engine.sync()
         return obs
 
